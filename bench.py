@@ -3,6 +3,8 @@
 32 regions x 1000 sampled permutations per cloud (BASELINE.json configs[1]).
 
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts its own N ranks (interpret_quality_amd/launch.py)
+    python bench.py ... --dump-outputs DIR                 # also write the last timed step's outputs as DIR/<name>.npy
+    python bench.py ... --full                             # everything below the headline as well (roofline, baselines, ...)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     ... bench.py --scaling strong [--model dgcnn]          # the path's OWN shard axes at N ranks (poses, pairs)
     ... bench.py --scaling sweep [--sweep-clouds 1]        # BASELINE configs[4]: all models x datasets, units pulled by the ranks
@@ -15,10 +17,24 @@ the generator state, the weights.  With N > 1 every rank works on its own cloud 
 per step brings the per-coalition logits to every rank, as the artefact writer on rank 0 needs them.
 IQ_FORCE_DIST=1 creates the process group (and runs the barrier / all-gather) at N = 1 too.  Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then `--repeats` (5) timed regions of at least `--min-region-s` (2 s) each, whatever K
-is: a region is ceil(2 s / block time) back-to-back BLOCKS of EXACTLY K steps, every block bracketed by barrier + synchronize on
-both sides and reduced with MAX over ranks; `value` / `ms_per_step` are the MEDIAN block's (`timing.region_s` states the region).  The library's HIP-event profiler is OFF in the timed regions; kernel durations come from a separate
-profiled pass afterwards.
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE block of exactly K timed steps (barrier + synchronize
+on both sides, MAX over ranks), the outputs of the last timed step if `--dump-outputs DIR` is given, and the JSON line
+(`value`, `ms_per_step` = that block's time / K).  Everything else below - the timing protocol of SURVEY.md 8d, the sanity checks on
+the last step, `roofline`, `strong_scaling`, `other_models` and the baselines - runs with `--full` only.
+
+`--dump-outputs DIR`: what a caller of the timed path receives from its last step, as DIR/<name>.npy in float32 / float64
+(integers as float64, exact): `phi_sum` (R,) and `sv_rows` (S, R) float64, `logits` (S*(R+1), 10) and `reward` (S*(R+1),)
+float32, `orders` (S, R); with collectives also `logits_all_ranks`, the all-gathered logits rank 0 holds.  Rank 0 writes.
+The inputs are seeded, so the same arguments give the same inputs on every run; above 64 MB in all, the large arrays are
+cut to a fixed seeded sample of their rows (the row indices go to <name>_rows.npy).
+
+Timing with `--full`: W warm-up steps, then `--repeats` (5) timed regions of at least `--min-region-s` (2 s) each,
+whatever K is: a region is ceil(2 s / block time) back-to-back BLOCKS of EXACTLY K steps, every block bracketed by barrier +
+synchronize on both sides and reduced with MAX over ranks; `value` / `ms_per_step` are the MEDIAN block's (`timing.region_s`
+states the region).  Every block starts from the generator state the warm-up left, so its steps draw the same permutations as
+those of any other block and the last timed step is the same whatever the number of blocks.  (A plain run is this protocol with
+one region of one block: `--repeats` 1, `--min-region-s` 0.)  The library's HIP-event profiler is OFF in the timed regions;
+kernel durations come from a separate profiled pass afterwards.
 
 `roofline` (dominant kernel = pn_chain_kernel, matrix-pipe bound): `achieved` = the float32 FLOP of the MFMA tiles it issues over
 its HIP-event launch time; `peak` = the matrix pipe's float32-equivalent rate for the kernel's instruction mix (layers 1-2 on the
@@ -27,14 +43,14 @@ fp32 MFMA at 157.3 TF, layer 3 as six exact bf16 products per float32 product on
 `frac_algorithmic` is SURVEY 8d's figure, the dense reference layers over all 1024 rows of every coalition (the kernel skips
 duplicate points, exactly: DESIGN.md 3).
 
-Every default line also carries `strong_scaling` (`--strong-steps`, default 1 step after the headline measurement): the same
+Every `--full` line also carries `strong_scaling` (`--strong-steps`, default 1 step after the headline measurement): the same
 workload as `--scaling strong` at this rank count, so the driver's N = 1, 2, 4, 8 runs hold a strong-scaling curve too.
 `--scaling strong`: ONE cloud's work sharded over the N ranks with the drivers' own code - the 216-pose rotation sweep
 (pose_sweep.sharded_shapley: poses sharded, tools/final_common.py:158) and one 300-pair x 13-ratio interaction setting
 (interaction.compute_order_interaction_logits: pairs sharded, final_point_binary_interaction_logits.py:37), every coalition a
 forward pass (no driver-level de-duplication), plus the share of the step spent in the all-gathers.
 
-After the timed regions (N = 1 only): the other model families on their BASELINE shapes with a roofline each
+With `--full`, after the timed regions (N = 1 only): the other model families on their BASELINE shapes with a roofline each
 (`other_models`), the stock PyTorch-ROCm eager restatement on the same GPU (`gpu_eager_baseline`), the CPU oracle on the host
 cores (`cpu_baseline`), and the HBM traffic of the dominant kernel from two rocprofv3 counter passes of this script
 (`roofline.traffic`; null when the profiler is unavailable).
@@ -77,10 +93,17 @@ SLOT_DOMINANT = 5
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30, help="steps per timed region (30 x 70 ms = 2.1 s)")
+    ap.add_argument("--steps", type=int, default=30, help="timed steps: a plain run times exactly this many; with --full, the steps of "
+                    "one block of a timed region")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions; each is as many blocks of --steps steps as --min-region-s needs")
-    ap.add_argument("--min-region-s", type=float, default=2.0, help="seconds of work per timed region (SURVEY 8d: >= 2 s)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: the timing protocol of "
+                    "SURVEY 8d, the sanity checks, roofline, strong_scaling, other_models, the eager-GPU and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all; headline mode only)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions; each is as many blocks of --steps steps as --min-region-s "
+                    "needs (default: 5 with --full, else 1)")
+    ap.add_argument("--min-region-s", type=float, default=None, help="seconds of work per timed region (SURVEY 8d: >= 2 s; default: 2 "
+                    "with --full, else 0 = one block)")
     ap.add_argument("--scaling", choices=["weak", "strong", "sweep"], default="weak",
                     help="weak: one cloud per rank (headline); strong: one cloud's pose sweep + interaction setting sharded over the ranks; "
                          "sweep: BASELINE configs[4], all models x datasets through both pipelines (tools/sweep.py), --sweep-clouds each")
@@ -90,21 +113,28 @@ def parse():
     ap.add_argument("--sweep-reduced", type=int, default=0, help="--scaling sweep: 1 = rehearsal sizes (100 saved permutations, 5 pairs, "
                     "3 contexts) instead of the reference's")
     ap.add_argument("--model", default="pointnet", help="model of the strong-scaling mode")
-    ap.add_argument("--profile-steps", type=int, default=3, help="steps of the separate profiled pass (kernel durations)")
-    ap.add_argument("--strong-steps", type=int, default=1, help="weak mode: also time this many strong-scaling steps (one cloud sharded over the "
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: steps of the separate profiled pass (kernel durations)")
+    ap.add_argument("--strong-steps", type=int, default=1, help="--full, weak mode: also time this many strong-scaling steps (one cloud sharded over the "
                     "ranks) after the headline measurement and report them under `strong_scaling` (0: skip)")
     ap.add_argument("--perms", type=int, default=NUM_PERMS, help="permutations per cloud per step")
     ap.add_argument("--regions", type=int, default=NUM_REGIONS)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU oracle on rank 0 at N=1")
-    ap.add_argument("--cpu-perms", type=int, default=40, help="permutations of the bounded CPU sample")
-    ap.add_argument("--eager-baseline", type=int, default=1, help="time the stock PyTorch-ROCm eager restatement (N=1)")
-    ap.add_argument("--other-models", type=int, default=1, help="after the timed region (N=1 only): coalitions/s and the "
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: time the CPU oracle on rank 0 at N=1")
+    ap.add_argument("--cpu-perms", type=int, default=40, help="--full: permutations of the bounded CPU sample")
+    ap.add_argument("--eager-baseline", type=int, default=1, help="--full: time the stock PyTorch-ROCm eager restatement (N=1)")
+    ap.add_argument("--other-models", type=int, default=1, help="--full, after the timed region (N=1 only): coalitions/s and the "
                     "dominant kernel's roofline of the other model families on BASELINE configs[2..3] shapes")
-    ap.add_argument("--sustained-s", type=float, default=1.5, help="seconds of the register-only bf16 MFMA loop that measures the "
+    ap.add_argument("--sustained-s", type=float, default=1.5, help="--full: seconds of the register-only bf16 MFMA loop that measures the "
                     "board's sustained matrix rate after the timed regions (0 = skip; frac_of_sustained_bf16_ceiling is then null)")
-    ap.add_argument("--traffic", type=int, default=1, help="measure the chain kernel's HBM bytes with two rocprofv3 "
+    ap.add_argument("--traffic", type=int, default=1, help="--full: measure the chain kernel's HBM bytes with two rocprofv3 "
                     "counter passes of this script (N=1 only; null if rocprofv3 is unavailable)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_region_s is None:
+        args.min_region_s = 2.0 if args.full else 0.0
+    if args.dump_outputs and args.scaling != "weak":
+        ap.error("--dump-outputs writes the outputs of the headline (weak) mode's timed path, not of --scaling %s" % args.scaling)
+    return args
 
 
 def host_cores():
@@ -370,6 +400,30 @@ def measure_traffic():
     return tot / n, detail
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_MIN_BYTES = 1 << 20   # arrays below this are always written whole
+
+
+def dump_outputs(outdir, arrays):
+    """`--dump-outputs`: every array as outdir/<name>.npy, float32 kept, every other dtype as float64 (the integers written here
+    are exact in it).  Above DUMP_MAX_BYTES in all, each array of DUMP_SAMPLE_MIN_BYTES or more keeps a fixed seeded sample of
+    its rows, the same on every run for the same shapes, and the row indices go to <name>_rows.npy."""
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for k, a in arrays.items()}
+    big = sorted(k for k, a in arrays.items() if a.ndim and a.nbytes >= DUMP_SAMPLE_MIN_BYTES)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES and big:
+        small = sum(a.nbytes for k, a in arrays.items() if k not in big)
+        # a kept row costs its own bytes and 8 for its index; 4 KB per file for the .npy headers
+        frac = (DUMP_MAX_BYTES - small - 4096 * len(arrays)) / sum(arrays[k].nbytes + 8 * arrays[k].shape[0] for k in big)
+        for k in big:
+            n = arrays[k].shape[0]
+            rows = np.sort(np.random.RandomState(0).choice(n, max(1, int(n * frac)), replace=False))
+            arrays[k] = arrays[k][rows]
+            arrays[k + "_rows"] = rows.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 def rows_of(keep_np, sizes, regions):
     """Distinct rows of each coalition (kept points + one centre row when anything is masked)."""
     bits = ((keep_np[:, None] >> np.arange(regions, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.int64)
@@ -541,7 +595,7 @@ def main():
             out = strong_scaling(args, rank, world, dev, collectives, rehearsal)
         else:
             out = weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist)
-            if args.strong_steps > 0:
+            if args.full and args.strong_steps > 0:
                 # the SAME line also carries the path's own shard axes at this rank count (one cloud's pose sweep + interaction
                 # setting, poses / pairs sharded): the driver's N = 1, 2, 4, 8 runs then hold a strong-scaling curve as well
                 strong = strong_scaling(args, rank, world, dev, collectives, rehearsal, steps=args.strong_steps, warmup=1, repeats=1)
@@ -590,10 +644,10 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
         keep = hip_ops.prefix_keep_masks(orders)                   # region masking, as bit masks (tools/final_common.py:56-60)
         logits = model.coalition_logits(data, center, region_id, keep, None, num_regions=R, validate=False)
         v = hip_ops.reward(logits, label, True)
-        phi_sum, _, _ = hip_ops.shapley_accum(v, orders)
+        phi_sum, sv_rows, _ = hip_ops.shapley_accum(v, orders)
         if collectives:
             dist.all_gather_into_tensor(gathered, logits)
-        return phi_sum, logits, orders, keep
+        return phi_sum, logits, orders, keep, sv_rows, v
 
     def fence():
         if collectives:
@@ -602,9 +656,11 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
 
     for _ in range(args.warmup):
         step()
+    mt_start = mt_state.clone()     # every block starts from here: its last step is the same whatever the number of blocks
 
     def block():
         """EXACTLY args.steps steps, barrier + synchronize on both sides, MAX over ranks -> seconds."""
+        mt_state.copy_(mt_start)
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -624,13 +680,39 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
     for _ in range(max(args.repeats, 1)):
         this = []
         while not this or sum(this) < args.min_region_s:
-            el, (phi_sum, logits, orders, keep) = block()
+            el, (phi_sum, logits, orders, keep, sv_rows, v) = block()
             this.append(el)
         blocks_s.extend(this)
         blocks_per_region.append(len(this))
         regions_s.append(float(np.sum(this)))
     blocks = int(np.median(blocks_per_region))
     elapsed = float(np.sort(blocks_s)[len(blocks_s) // 2])        # the median block of args.steps steps
+    if args.dump_outputs and rank == 0:
+        outputs = {"phi_sum": phi_sum, "sv_rows": sv_rows, "logits": logits, "reward": v, "orders": orders}
+        if collectives:
+            outputs["logits_all_ranks"] = gathered
+        dump_outputs(args.dump_outputs, {k: t.cpu().numpy() for k, t in outputs.items()})
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "coalitions/sec (masked forward passes/sec), PointNet 1024-pt ModelNet10",
+            "value": n_coal * args.steps * world / elapsed, "unit": "coalitions/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "PointNet ModelNet10-style Shapley, %d regions x %d permutations per cloud "
+                                   "(%d coalitions per step per GPU), BASELINE configs[1]; permutations sampled and masked on the "
+                                   "device inside the timed step" % (R, S, n_coal),
+                       "num_points": NUM_POINTS, "num_regions": R, "permutations": S,
+                       "parallelism": "clouds sharded over %d GPU(s), one all_gather_into_tensor of the logits per step%s"
+                                      % (world, " (forced single-rank RCCL group)" if force_dist and world == 1 else "")},
+            "timing": {"protocol": "%d region(s) of >= %.1f s, each %d block(s) of exactly %d steps; barrier + synchronize around every block, "
+                                   "MAX over ranks; value / ms_per_step = the median block; HIP-event profiler off"
+                                   % (len(regions_s), args.min_region_s, blocks, args.steps),
+                       "blocks_per_region": blocks, "region_s": float(np.median(regions_s)), "regions_s": regions_s,
+                       "blocks_s": blocks_s, "block_spread": float((max(blocks_s) - min(blocks_s)) / elapsed)},
+        }
+    if not args.full:
+        return out
     if collectives:
         # every rank's chunk of the gather must hold that rank's logits (rank r's own chunk is checkable locally)
         assert torch.equal(gathered[rank * n_coal:(rank + 1) * n_coal], logits), "all-gather returned a wrong chunk"
@@ -657,7 +739,6 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
     call_ms, call_n, _ = _read_slot(lib, 3)
 
     if rank == 0:
-        total = n_coal * args.steps * world
         launches = f_n + t_n
         launch_s = (f_ms + t_ms) * 1e-3                            # all chain launches of the profiled pass (2 per step)
         # what the chain kernel (feature-STN and trunk instantiations: same shape) executes per launch: each coalition's
@@ -689,22 +770,7 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
         traffic, traffic_detail = (None, "not measured (N > 1 or --traffic 0)")
         if world == 1 and args.traffic and not force_dist:
             traffic, traffic_detail = measure_traffic()
-        out = {
-            "metric": "coalitions/sec (masked forward passes/sec), PointNet 1024-pt ModelNet10",
-            "value": total / elapsed, "unit": "coalitions/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "PointNet ModelNet10-style Shapley, %d regions x %d permutations per cloud "
-                                   "(%d coalitions per step per GPU), BASELINE configs[1]; permutations sampled and masked on the "
-                                   "device inside the timed step" % (R, S, n_coal),
-                       "num_points": NUM_POINTS, "num_regions": R, "permutations": S,
-                       "parallelism": "clouds sharded over %d GPU(s), one all_gather_into_tensor of the logits per step%s"
-                                      % (world, " (forced single-rank RCCL group)" if force_dist and world == 1 else "")},
-            "timing": {"protocol": "%d regions of >= %.1f s, each %d block(s) of exactly %d steps; barrier + synchronize around every block, "
-                                   "MAX over ranks; value / ms_per_step = the median block; HIP-event profiler off"
-                                   % (len(regions_s), args.min_region_s, blocks, args.steps),
-                       "blocks_per_region": blocks, "region_s": float(np.median(regions_s)), "regions_s": regions_s,
-                       "blocks_s": blocks_s, "block_spread": float((max(blocks_s) - min(blocks_s)) / elapsed)},
+        out.update({
             "roofline": {"bound": "mfma", "kernel": "pn_chain_kernel<fstn|trunk>", "achieved": achieved,
                          "peak": peak_mix, "unit": "TFLOP/s", "frac": achieved / peak_mix,
                          "frac_basis": "executed",
@@ -737,7 +803,7 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
                                  "same script, measured now",
                          "step_tflops_algorithmic": step_flops / (elapsed / args.steps) / 1e12,
                          "prepool_ms_per_launch": pre_ms / max(pre_n, 1), "call_ms": call_ms / max(call_n, 1)},
-        }
+        })
         if world == 1 and args.other_models:
             out["other_models"] = other_models(dev, lib, R)
         if world == 1 and args.eager_baseline:
@@ -747,8 +813,7 @@ def weak_scaling(args, rank, world, dev, collectives, rehearsal, force_dist):
                 out["gpu_eager_baseline"] = {"error": repr(e)[:300]}
         if world == 1 and args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(R, args.cpu_perms)
-        return out
-    return None
+    return out
 
 
 if __name__ == "__main__":

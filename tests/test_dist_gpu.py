@@ -88,7 +88,7 @@ def test_bench_runs_its_collectives_on_rccl_with_a_forced_single_rank_group(tmp_
     """bench.py under `torchrun --nproc-per-node 1` with IQ_FORCE_DIST=1: process group "nccl" (= RCCL), barrier on both sides
     of the timed region, all_gather_into_tensor of the logits every step, max-reduce of the elapsed time."""
     bench = os.path.join(REPO, "bench.py")
-    flags = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1", "--perms", "100", "--other-models", "0", "--cpu-baseline", "0",
+    flags = ["--gpus", "1", "--full", "--steps", "2", "--warmup", "1", "--repeats", "1", "--perms", "100", "--other-models", "0", "--cpu-baseline", "0",
              "--eager-baseline", "0", "--traffic", "0", "--strong-steps", "0", "--sustained-s", "0.3"]
     # under torchrun, and (second chain, side by side) without it - RANK / WORLD_SIZE absent: defaults, a free rendezvous port
     (r,), (r2,) = _run_chains([[(_torchrun(1, 29611) + [bench] + flags, tmp_path, _env(IQ_FORCE_DIST="1"))],
@@ -115,12 +115,12 @@ def bench_runs(tmp_path_factory):
     dirs = {k: root / k for k in ("self", "sweep", "strong1", "strong2", "n2")}
     for v in dirs.values():
         v.mkdir()
-    weak = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--repeats", "1", "--perms", "100", "--strong-steps", "0", "--profile-steps", "1"]
+    weak = ["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--repeats", "1", "--perms", "100", "--strong-steps", "0", "--profile-steps", "1"]
     sweep = ["--gpus", "2", "--scaling", "sweep", "--sweep-models", "pointnet,gcnn", "--sweep-datasets", "modelnet10", "--sweep-clouds", "1",
              "--sweep-reduced", "1"]
     strong = lambda n: ["--gpus", str(n), "--scaling", "strong", "--steps", "1", "--warmup", "0", "--repeats", "1"]
-    # the driver's own launch form for N = 2 (torchrun, every default leg of the line on)
-    n2 = ["--gpus", "2", "--steps", "1", "--warmup", "1", "--repeats", "1", "--perms", "100", "--sustained-s", "0.3"]
+    # the driver's own launch form for N = 2 (torchrun, every leg of the --full line on)
+    n2 = ["--gpus", "2", "--full", "--steps", "1", "--warmup", "1", "--repeats", "1", "--perms", "100", "--sustained-s", "0.3"]
     (r_self, r_sweep), (r_s1, r_s2, r_n2) = _run_chains([
         [([sys.executable, bench] + weak, dirs["self"], _env(IQ_REHEARSAL="1")),
          ([sys.executable, bench] + sweep, dirs["sweep"], _env(IQ_REHEARSAL="1"))],

@@ -7,9 +7,9 @@ sample() {  # $1 = tag, $2 = pid to watch
   done
 }
 rocm-smi --showpower --showclocks --showmaxpower 2>&1 | head -40 > $O/idle.txt
-python3 $R/bench.py --steps 30 --repeats 8 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0 > $O/bench.json 2> $O/bench.err &
+python3 $R/bench.py --full --steps 30 --repeats 8 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0 > $O/bench.json 2> $O/bench.err &
 P=$!; sleep 14; sample headline $P; wait $P
-IQ_BENCH_FP32_L3=1 python3 $R/bench.py --steps 30 --repeats 8 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0 > $O/bench_fp32.json 2> $O/bench_fp32.err &
+IQ_BENCH_FP32_L3=1 python3 $R/bench.py --full --steps 30 --repeats 8 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0 > $O/bench_fp32.json 2> $O/bench_fp32.err &
 P=$!; sleep 14; sample headline_fp32_l3 $P; wait $P
 python3 $R/tools/bench_models.py --model dgcnn --mode interaction --steps 40 > $O/dgcnn.log 2>&1 &
 P=$!; sleep 10; sample dgcnn $P; wait $P

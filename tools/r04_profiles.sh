@@ -2,7 +2,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r04f; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 5 --warmup 2 --repeats 1 --min-region-s 0 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0"
+B="python3 $R/bench.py --full --steps 5 --warmup 2 --repeats 1 --min-region-s 0 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- $B > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/bench_pmc -- $B > $O/bench_pmc.log 2>&1
 for m in pointnet2 dgcnn gcnn pointconv; do
@@ -13,8 +13,8 @@ for m in pointnet2 dgcnn gcnn pointconv; do
 done
 # the headline line itself (the driver's command), then the self-launched 2-rank rehearsal and the configs[4] sweep line on one GPU
 cd $R
-python3 bench.py > $O/bench.json 2> $O/bench.err
-IQ_REHEARSAL=1 python3 bench.py --gpus 2 --steps 5 --repeats 2 --strong-steps 0 > $O/bench_2rank_rehearsal.json 2> $O/bench_2rank_rehearsal.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+IQ_REHEARSAL=1 python3 bench.py --gpus 2 --full --steps 5 --repeats 2 --strong-steps 0 > $O/bench_2rank_rehearsal.json 2> $O/bench_2rank_rehearsal.err
 python3 bench.py --scaling sweep --sweep-datasets modelnet10 --sweep-clouds 1 > $O/bench_sweep_1gpu.json 2> $O/bench_sweep_1gpu.err
 IQ_REHEARSAL=1 python3 bench.py --gpus 2 --scaling sweep --sweep-datasets modelnet10 --sweep-clouds 2 --sweep-models pointnet,gcnn,dgcnn > $O/bench_sweep_2rank_rehearsal.json 2> $O/bench_sweep_2rank_rehearsal.err
 tail -c 600 $O/bench.json; echo; tail -c 400 $O/bench_sweep_1gpu.json

@@ -13,7 +13,7 @@ for rep in 1 2 3; do
     echo "pointconv 7=$t: $(python3 tools/bench_models.py --model pointconv --mode shapley --steps 8 --tune 7=$t 2>&1 | tail -1 | cut -c1-200)"
   done
 done
-hl() { python3 bench.py --steps 20 --repeats 3 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0 --sustained-s 0 2>/dev/null | python3 -c "
+hl() { python3 bench.py --full --steps 20 --repeats 3 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0 --sustained-s 0 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().split('\n')[-1]); r=d['roofline']
 print('headline %.0f coalitions/s, %.2f ms/step, chain launch %.3f ms' % (d['value'], d['ms_per_step'], r.get('avg_launch_ms')))"; }

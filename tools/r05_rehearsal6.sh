@@ -11,7 +11,7 @@ echo "== bench.py --gpus 6 --scaling strong (one cloud's pose sweep + interactio
 python3 bench.py --gpus 6 --scaling strong --steps 1 --warmup 0 --repeats 1 > $O/bench_strong_6rank.json 2> $O/bench_strong_6rank.err
 tail -c 600 $O/bench_strong_6rank.json; echo
 echo "== bench.py --gpus 6 (weak: every rank its own cloud, one all-gather of the logits per step)"
-python3 bench.py --gpus 6 --steps 2 --warmup 1 --repeats 1 --perms 200 --strong-steps 0 --profile-steps 1 > $O/bench_weak_6rank.json 2> $O/bench_weak_6rank.err
+python3 bench.py --gpus 6 --full --steps 2 --warmup 1 --repeats 1 --perms 200 --strong-steps 0 --profile-steps 1 > $O/bench_weak_6rank.json 2> $O/bench_weak_6rank.err
 tail -c 400 $O/bench_weak_6rank.json; echo
 echo "== tools/sweep.py --gpus 6, all six models x modelnet10, reduced sizes, against ONE process: artefacts bitwise"
 FLAGS="--datasets modelnet10 --synthetic --num_clouds 2 --num_samples_save 100 --num_pairs_random 5 --num_save_context_max 3"

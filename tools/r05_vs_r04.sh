@@ -13,7 +13,7 @@ for m in pointnet2:shapley pointconv:shapley dgcnn:interaction gcnn:interaction;
     echo "r5 $(one $R $mod $mode)"
   done
 done
-B="bench.py --repeats 1 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0"
+B="bench.py --repeats 1 --min-region-s 2 --cpu-baseline 0 --other-models 0 --eager-baseline 0 --traffic 0 --strong-steps 0"
 for rep in 1 2; do
   echo "r4 headline $(cd $O && timeout -k 10 300 python3 $B 2>/dev/null | python3 -c 'import sys,json; b=json.loads([l for l in sys.stdin if l.startswith("{")][-1]); print(round(b["value"]), round(b["ms_per_step"],2))')"
   echo "r5 headline $(cd $R && timeout -k 10 300 python3 $B --sustained-s 0 2>/dev/null | python3 -c 'import sys,json; b=json.loads([l for l in sys.stdin if l.startswith("{")][-1]); print(round(b["value"]), round(b["ms_per_step"],2))')"
