@@ -124,9 +124,6 @@ SIGNATURES = {
                                           ctypes.POINTER(ctypes.c_int), _P]),
     "iq_profile_enable": (_I, [_I]),
     "iq_set_tuning": (_I, [_I, _I]),
-    "iq_debug_chain_occupancy": (_I, []),
-    "iq_debug_stamps": (_I, [_I, ctypes.POINTER(ctypes.c_ulonglong)]),
-    "iq_debug_knn_counters": (_I, [ctypes.POINTER(ctypes.c_ulonglong)]),
     "iq_profile_read_work": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
     "iq_profile_read": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]),
     "iq_debug_mfma_sustained": (_I, [ctypes.c_double, _P, _SZ, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _P]),
@@ -137,7 +134,7 @@ ABI_VERSION = 102   # IQ_ABI_VERSION of include/iq.h these struct layouts were w
 
 
 def lib_path():
-    """The product library; IQ_LIBPATH names another BUILD of the same sources (A/B runs of tools/, e.g. lib_packed_ab/)."""
+    """The product library; IQ_LIBPATH names another BUILD of the same sources (A/B runs of tools/: another libdir of build.build)."""
     return os.environ.get("IQ_LIBPATH") or _build.LIBPATH
 
 

@@ -63,8 +63,8 @@ def _run(cmd, verbose):
         raise subprocess.CalledProcessError(p.returncode, cmd)
 
 
-def build(force=False, verbose=True, extra_flags=(), packed_fp32=False, libdir=None):
-    """Compile csrc/*.hip into <libdir>/libiq_hip.so.  packed_fp32=True / another libdir: A/B builds only (tools/r05_pk_ab.sh)."""
+def build(force=False, verbose=True, extra_flags=(), libdir=None):
+    """Compile csrc/*.hip into <libdir>/libiq_hip.so.  extra_flags / another libdir: A/B builds only (IQ_LIBPATH, _lib.py)."""
     libdir = libdir or LIBDIR
     libpath = os.path.join(libdir, "libiq_hip.so")
     if not force and libdir == LIBDIR and up_to_date():
@@ -83,8 +83,7 @@ def build(force=False, verbose=True, extra_flags=(), packed_fp32=False, libdir=N
                 cmd.append("-ffp-contract=off")
             if os.path.basename(src) in NO_NANS:
                 cmd.append("-fno-honor-nans")
-            if not packed_fp32:
-                cmd += NO_PACKED_FP32_FLAGS
+            cmd += NO_PACKED_FP32_FLAGS
             _run(cmd, verbose)
         objs.append(obj)
     _run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", libpath] + objs, verbose)
@@ -92,7 +91,4 @@ def build(force=False, verbose=True, extra_flags=(), packed_fp32=False, libdir=N
 
 
 if __name__ == "__main__":
-    if "--packed-ab" in sys.argv:      # the round-4 code generation (packed float32 allowed), beside the product build, for A/B runs
-        print(build(force=True, packed_fp32=True, libdir=os.path.join(HERE, "lib_packed_ab")))
-    else:
-        print(build(force="--force" in sys.argv))
+    print(build(force="--force" in sys.argv))

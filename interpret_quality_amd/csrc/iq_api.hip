@@ -18,7 +18,8 @@ struct Span { hipEvent_t start, stop; int which; double work; };
 struct ThreadState {
     std::vector<Span> spans;
     bool enabled = false;
-    int tune[kTuneCount] = {2, 0, 0, 0, 0, 0, 0, 0};  // default: L3 variant 2 (B-fragment ring)
+    bool no_lds_gemm = false;
+    int twin = 0;
 };
 ThreadState& ts() {
     static thread_local ThreadState s;
@@ -28,8 +29,8 @@ ThreadState& ts() {
 
 bool profile_enabled() { return ts().enabled; }
 
-int tuning(int key) { return (key >= 0 && key < kTuneCount) ? ts().tune[key] : 0; }
-void set_tuning(int key, int value) { if (key >= 0 && key < kTuneCount) ts().tune[key] = value; }
+bool no_lds_gemm() { return ts().no_lds_gemm; }
+int twin() { return ts().twin; }
 
 ProfileSpan::ProfileSpan(int which, hipStream_t st, double work) : which_(which), st_(st), on_(ts().enabled), work_(work) {
     if (!on_) return;
@@ -46,9 +47,21 @@ ProfileSpan::~ProfileSpan() {
 }  // namespace iq
 
 extern "C" int iq_set_tuning(int key, int value) {
-    IQ_REQUIRE(key >= 0 && key < iq::kTuneCount, "iq_set_tuning: key %d", key);
-    iq::set_tuning(key, value);
-    return IQ_OK;
+    if (key == iq::kTuneNoLdsGemm && (value == 0 || value == 1)) {
+        iq::ts().no_lds_gemm = value != 0;
+        return IQ_OK;
+    }
+    if (key == iq::kTuneTwin) {
+        switch (value) {
+            case 0: case iq::kTwinEdgeGemmL2: case iq::kTwinEdgeGemmLds: case iq::kTwinKnnCompact: case iq::kTwinPcKnn:
+            case iq::kTwinPcGroupedMlp: case iq::kTwinKnnFp32Rank: case iq::kTwinPn2MemberWalk: case iq::kTwinKnnFp32Mfma:
+            case iq::kTwinPcTwoKernel: case iq::kTwinChainL3Fp32: case iq::kTwinChainL3Fp32NoTail16: case iq::kTwinGroupFp32:
+            case iq::kTwinDenseFp32: case iq::kTwinChainL3Single: case iq::kTwinGroupFp32Chunk64:
+                iq::ts().twin = value;
+                return IQ_OK;
+        }
+    }
+    return iq::fail(IQ_EINVAL, "iq_set_tuning: key %d value %d is not an experiment knob", key, value);
 }
 
 extern "C" int iq_profile_enable(int on) {

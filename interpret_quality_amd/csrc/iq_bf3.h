@@ -45,29 +45,6 @@ __device__ __forceinline__ f32x16 mfma_bf3(const bf16x8 (&a)[3], const B3& b, f3
     return acc;
 }
 
-// One 32x32 C tile (lane: column lane & 31, rows c_row_i(i) + 4 (lane >> 5)) -> three bf16 planes in LDS.  Two lanes (columns c,
-// c + 1) trade one value of each pair of rows (DPP quad_perm [1,0,3,2]) so that every store is a whole dword: 24 ds_write_b32
-// instead of 48 ds_write_b16.  `tile`: plane 0, first row of the m-tile, first column of the n-tile; value(i): element i after
-// bias / activation.
-template <int ROWB, int PLANEB, typename F>
-__device__ __forceinline__ void c_tile_to_planes(unsigned char* tile, int lane, F value) {
-    const int odd = lane & 1;
-    unsigned char* d = tile + (4 * (lane >> 5) + odd) * ROWB + ((lane & 31) & ~1) * 2;
-#pragma unroll
-    for (int i = 0; i < 16; i += 2) {
-        const float v0 = value(i), v1 = value(i + 1);                                         // rows r, r + 1 of column c
-        const float got = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, odd ? v0 : v1), 0xB1, 0xF, 0xF, false));
-        const float lo = odd ? got : v0, hi = odd ? v1 : got;                                 // columns c & ~1, c | 1 of row r + odd
-        const unsigned h = bf16_pair(lo, hi);
-        const float rl = lo - bf16_lo(h), rh = hi - bf16_hi(h);
-        const unsigned m = bf16_pair(rl, rh);
-        unsigned char* o = d + c_row_i(i) * ROWB;
-        *reinterpret_cast<unsigned*>(o) = h;
-        *reinterpret_cast<unsigned*>(o + PLANEB) = m;
-        *reinterpret_cast<unsigned*>(o + 2 * PLANEB) = bf16_pair(rl - bf16_lo(m), rh - bf16_hi(m));
-    }
-}
-
 // four consecutive channels of one row -> the three planes (8 bytes each); dst = plane 0 + row * ROWB + channel * 2
 template <int PLANEB>
 __device__ __forceinline__ void row4_to_planes(unsigned char* dst, f32x4 v) {
@@ -93,7 +70,7 @@ __device__ __forceinline__ void split4(f32x4 v, u32x2& h, u32x2& m, u32x2& l) {
 // The TRANSPOSED C tile of a layer whose output goes back to LDS as an activation image (round 5): with the weight fragment as the
 // A operand and the activation fragment as B - the same two fragments, swapped - lane (row = lane & 31 of the m-tile, half) holds its
 // row's channels 8 g + 4 half + 0..3 in registers 4 g .. 4 g + 3: four consecutive channels per register quad, so the three bf16
-// planes take whole 8-byte stores and the two-lane DPP trade of c_tile_to_planes (4 VALU per value pair) is not needed.
+// planes take whole 8-byte stores and the two-lane DPP trade of the untransposed tile (4 VALU per value pair) is not needed.
 // `tile`: plane 0, first row of the m-tile, first channel of the n-tile; value(r): register r after bias / activation, where
 // register r is channel c_row_i(r) + 4 * (lane >> 5) of the n-tile.
 template <int ROWB, int PLANEB, typename F>

@@ -325,11 +325,10 @@ __global__ __launch_bounds__(kThreads, 2) void pn_gemm_lds_kernel(const float* _
 // Not bit-identical to the fp32-MFMA kernel (another summation order), equal to it within float32 rounding.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // POOL = false: the plain dense layer out (M, ldo) = act(A W^T + b) on the same tiles (launch_linear, for layers that carry
 // iq_dense_layer.w_bf3); tile_nu / rows_per_cloud as in pn_gemm_lds_kernel.
-template <bool POOL, int PROBE = 0, int NW = 4, bool RAGGED = false, bool SPLITK = false>
+template <bool POOL, int NW = 4, bool RAGGED = false, bool SPLITK = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(const float* __restrict__ A, int lda,
                                                                   const unsigned short* __restrict__ w3,
                                                                   const float* __restrict__ bias, float* __restrict__ out, int ldo,
@@ -404,14 +403,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(c
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             if (RAGGED && outside) stage[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if constexpr (PROBE == 1) {   // timing probe: the planes without the split's arithmetic (results WRONG)
-                unsigned char* d = As[buf] + soff[i];
-                const f32x2 lo = {stage[i][0], stage[i][1]}, hi = {stage[i][2], stage[i][3]};
-                *reinterpret_cast<f32x2*>(d) = lo;
-                *reinterpret_cast<f32x2*>(d + PLANE) = hi;
-                *reinterpret_cast<f32x2*>(d + 2 * PLANE) = lo;
-                continue;
-            }
             bf16x4 h, m, l;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -516,19 +507,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(c
         }
         return;
     }
-    // (Round 5, measured: the staging split costs 9 % of conv5 (PROBE 1) and this epilogue 8 % (PROBE 2).  NW = 8 - one workgroup
+    // (Round 5, measured: the staging split costs 9 % of conv5 and this epilogue 8 % (timing probes without them).  NW = 8 - one workgroup
     // of eight waves per CU on 128 rows x 512 columns, the split shared by twice as many waves: conv5 29.5 ms against 29.1, no.  Taking the column maximum
     // over the raw sums - bias and activation are increasing maps - with an additive -inf mask for the dead rows, 8 instead of 10
     // VALU instructions per value: conv5 30.0 ms against 30.0, not adopted.)
-    if constexpr (PROBE == 2) {   // timing probe: no pooling epilogue (results WRONG)
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) sacc += acc[i][j][0] + acc[i][j][5];
-        if (sacc == 12345.678f) out[0] = sacc;
-        return;
-    }
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         const int trow = m0 + i * 32;
@@ -572,16 +554,16 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
     const int ntiles = (L.cout + 31) / 32;
     if (tile_nu && (rows_per_cloud <= 0 || rows_per_cloud % 128 != 0)) tile_nu = nullptr;   // tiles must not straddle clouds
     // bf16x3 on the bf16 matrix pipe, float32-exact - for EVERY M, so that a row's result does not depend on the launch it is in
-    // (5 = 57: fp32 MFMA, A/B and tests)
+    // (twin kTwinDenseFp32: fp32 MFMA, A/B and tests)
     // (column blocks of 256: 320 outputs would leave the second block a quarter full, and lose to the NT = 5 fp32 tiling - so the
     // whole blocks of such a layer go to the bf16 pipe and its last 64 columns to the fp32 MFMA as a layer of their own; which
     // columns take which arithmetic depends on the layer only, never on M)
     const int Kp = (L.cin + 31) & ~31;     // the bf16x3 image's k range (iq_pack_weight_bf3 pads with zero columns)
-    if (L.w_bf3 && L.cout > 256 && L.cout % 256 == 64 && L.cin >= 32 && iq::tuning(iq::kTuneExperiment) != 57 &&
-        iq::tuning(iq::kTuneExperiment) != 59) {       // 5 = 59: these layers alone on the fp32 MFMA (A/B)
+    const bool fp32 = iq::twin() == iq::kTwinDenseFp32;
+    if (L.w_bf3 && L.cout > 256 && L.cout % 256 == 64 && L.cin >= 32 && !fp32) {
         const int gx = (M + 127) / 128, gy = L.cout / 256;
         if (Kp != L.cin)
-            hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 0, 4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
+            hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
                                reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy,
                                tile_nu, rows_per_cloud, L.cin, 0);
         else
@@ -597,11 +579,10 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
         rest.w_bf3 = nullptr;
         return launch_linear(A, lda, rest, out + 256 * gy, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud);
     }
-    if (L.w_bf3 && L.cout % 256 == 0 && L.cin >= 32 && iq::tuning(iq::kTuneExperiment) != 57 &&
-        !(Kp != L.cin && iq::tuning(iq::kTuneExperiment) == 59)) {      // (59 also: the layers whose inputs are no multiple of 32)
+    if (L.w_bf3 && L.cout % 256 == 0 && L.cin >= 32 && !fp32) {
         const int gx = (M + 127) / 128, gy = (L.cout + 255) / 256;
         if (Kp != L.cin)
-            hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 0, 4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
+            hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
                                reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy,
                                tile_nu, rows_per_cloud, L.cin, 0);
         else
@@ -610,9 +591,8 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
                                tile_nu, rows_per_cloud, L.cin, 0);
         return iq::check_launch("pn_gemm_bf3_kernel");
     }
-    if (M >= 2048 && (ntiles >= 4 || (ntiles == 2 && (M + 255) / 256 >= 2048)) && L.cin % 32 == 0 && iq::tuning(iq::kTuneNoLdsGemm) == 0) {
-        const int shape = iq::tuning(iq::kTuneExperiment);   // 5 = 30: round 3's choice of shapes (A/B runs)
-        if (ntiles % 10 == 0 && shape != 30 && (long long)((M + 127) / 128) * (ntiles / 10) >= 2048) {
+    if (M >= 2048 && (ntiles >= 4 || (ntiles == 2 && (M + 255) / 256 >= 2048)) && L.cin % 32 == 0 && !iq::no_lds_gemm()) {
+        if (ntiles % 10 == 0 && (long long)((M + 127) / 128) * (ntiles / 10) >= 2048) {
             // 320 / 640 ... outputs: column blocks of exactly 10 tiles (NT = 5), nothing padded
             dim3 grid((M + 127) / 128, ntiles / 10);
             hipLaunchKernelGGL((pn_gemm_lds_kernel<5, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
@@ -622,14 +602,14 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
             dim3 grid((M + 255) / 256, 1);
             hipLaunchKernelGGL((pn_gemm_lds_kernel<2, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
                                L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
-        } else if (ntiles == 4 && shape != 30 && (M + 255) / 256 >= 2048) {
+        } else if (ntiles == 4 && (M + 255) / 256 >= 2048) {
             // 128 outputs: 256-row workgroup tiles, every wave all four column tiles
             dim3 grid((M + 255) / 256, 1);
             hipLaunchKernelGGL((pn_gemm_lds_kernel<4, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
                                L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
         } else if (ntiles >= 8 && (long long)((M + 127) / 128) * ((ntiles + 7) / 8) >= 2048) {
             const int gx = (M + 127) / 128, gy = (ntiles + 7) / 8;
-            const bool flat = gy > 1 && shape != 48;       // column blocks of a row tile side by side on one XCD (see the kernel)
+            const bool flat = gy > 1;       // column blocks of a row tile side by side on one XCD (see the kernel)
             hipLaunchKernelGGL((pn_gemm_lds_kernel<4, false>), flat ? dim3((unsigned)((gx + 7) / 8 * 8 * gy)) : dim3(gx, gy), dim3(kThreads), 0,
                                st, A, lda, L.w, L.b, out, ldo, M, L.cin, L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, flat ? gy : 0);
         } else {
@@ -680,12 +660,12 @@ int iq::launch_linear_splitk(const float* A, int lda, const iq_dense_layer& L, f
     const int kbs = 64;
     const int splits = (KB + kbs - 1) / kbs;
     if (splits <= 1 || ntiles < 4) return launch_linear(A, lda, L, out, ldo, M, relu, st);
-    if (L.w_bf3 && L.cout % 256 == 0 && L.cin % 32 == 0 && iq::tuning(iq::kTuneExperiment) != 57 && iq::tuning(iq::kTuneExperiment) != 59) {
+    if (L.w_bf3 && L.cout % 256 == 0 && L.cin % 32 == 0 && iq::twin() != iq::kTwinDenseFp32) {
         // the same 512-k splits on the bf16 matrix pipe (three-term products): 16 chunks of 32 k per workgroup row
         IQ_REQUIRE(scratch && (size_t)splits * M * L.cout <= scratch_floats, "split-K dense layer: scratch %zu floats < %zu",
                    scratch_floats, (size_t)splits * M * L.cout);
         const int gx = (M + 127) / 128, gy = L.cout / 256;
-        hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 0, 4, false, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy), (unsigned)splits), dim3(kThreads), 0,
+        hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, false, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy), (unsigned)splits), dim3(kThreads), 0,
                            st, A, lda, reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, scratch, L.cout, M, L.cin, L.cout, 0, nullptr, nullptr,
                            gy, nullptr, 0, L.cin, kbs * 8 / 32);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
@@ -710,29 +690,14 @@ int iq::launch_linear_pool(const float* A, int lda, const iq_dense_layer& L, flo
     if (L.cin % 32 != 0 || ntiles < 8 || L.cout % 32 != 0)
         return iq::fail(IQ_EUNSUPPORTED, "dense layer + pool: cin=%d cout=%d", L.cin, L.cout);
     const int gy = (ntiles + 7) / 8, gx = (M + 127) / 128;
-    if (w_bf3 && L.cout % 256 == 0 && iq::tuning(iq::kTuneExperiment) != 53) {   // 5 = 53: the fp32 MFMA (A/B and tests)
-        const int probe = iq::tuning(iq::kTuneExperiment);     // 94 / 95: timing probes (no split arithmetic / no pooling; results WRONG)
-        if (probe == 94 || probe == 95) {
-            if (probe == 94)
-                hipLaunchKernelGGL((pn_gemm_bf3_kernel<true, 1>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                                   reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy, nullptr, 0, L.cin, 0);
-            else
-                hipLaunchKernelGGL((pn_gemm_bf3_kernel<true, 2>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                                   reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy, nullptr, 0, L.cin, 0);
-            return iq::check_launch("pn_gemm_bf3_kernel<pool, probe>");
-        }
+    if (w_bf3 && L.cout % 256 == 0) {
         hipLaunchKernelGGL(pn_gemm_bf3_kernel<true>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
                            reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy,
                            nullptr, 0, L.cin, 0);
         return iq::check_launch("pn_gemm_bf3_kernel<pool>");
     }
-    if (iq::tuning(iq::kTuneExperiment) == 48) {   // 5 = 48: the (tiles, column blocks) grid of rounds 1-3 (A/B)
-        hipLaunchKernelGGL((pn_gemm_lds_kernel<4, true>), dim3(gx, gy), dim3(kThreads), 0, st, A, lda, L.w, L.b, partial, 0, M, L.cin, L.cout,
-                           relu, m_dev, row_w, nullptr, 0, 0);
-    } else {
-        hipLaunchKernelGGL((pn_gemm_lds_kernel<4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda, L.w, L.b,
-                           partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, nullptr, 0, gy);
-    }
+    hipLaunchKernelGGL((pn_gemm_lds_kernel<4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda, L.w, L.b,
+                       partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, nullptr, 0, gy);
     return iq::check_launch("pn_gemm_lds_kernel<pool>");
 }
 

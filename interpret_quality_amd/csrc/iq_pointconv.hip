@@ -412,7 +412,7 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_kernel(PcGroupArgs a) {
 // activations as three bf16 planes of 272-byte rows, act1 and act2 in ONE 52 KB image (layer 2's tiles wait in registers for
 // the barrier), layer 3 as 2 x 2 tiles per wave, weights through small register rings.  The contraction over the members stays
 // on v_mfma_f32_16x16x4_f32 (float32 operands straight out of the accumulators).
-template <int MTS, bool TR>   // TR: transposed tiles (weights as the A operand), as gb_layer2 in iq_pointnet2.hip
+template <int MTS>   // transposed tiles (weights as the A operand), as gb_layer2 in iq_pointnet2.hip
 __device__ __forceinline__ void pcb_layer2(const unsigned char* abase, const __amdgpu_buffer_rsrc_t& rs, int voff, int nt,
                                            B3 (&ring)[4], f32x16 (&acc)[MTS][1]) {
     constexpr int ROWB = 272, PLANEB = 64 * ROWB, TS = 4 * 8 * 1024;
@@ -421,10 +421,9 @@ __device__ __forceinline__ void pcb_layer2(const unsigned char* abase, const __a
         bf16x8 af[MTS][3];
 #pragma unroll
         for (int i = 0; i < MTS; ++i) a3_load<PLANEB>(af[i], abase + i * 32 * ROWB, ks);
-        const B3 b[1] = {ring[ks & 3]};
+        const B3 b = ring[ks & 3];
         if (ks + 4 < 8) ring[ks & 3] = b3_load_at(rs, voff, (nt * 8 + ks + 4) * 1024, TS);
-        if (TR) mfma_bf3_block_tr<MTS>(af, b[0], acc);
-        else mfma_bf3_block<MTS, 1>(af, b, acc);
+        mfma_bf3_block_tr<MTS>(af, b, acc);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -447,9 +446,7 @@ __device__ __forceinline__ void pcb_layer3(const unsigned char* abase, const __a
     }
 }
 
-// TR (the default): layer 2's tiles transposed - act2 stored with whole 8-byte stores, no two-lane DPP trade (tuning key 7 = 1: the
-// untransposed form; same products in the same order).
-template <bool TR>
+// Layer 2's tiles transposed: act2 stored with whole 8-byte stores, no two-lane DPP trade.
 __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a) {
     constexpr int C1 = 128, C3 = 256, ROWB = 272, PLANEB = kMC * ROWB, LDS_SW = kMC + 2;
     constexpr int Q1 = C1 / 4, NR = kMC * Q1 / kThreads;
@@ -525,7 +522,7 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a
         __syncthreads();  // act1 complete
         // ---- layer 2: tiles (m-tile 0..1, n-tile = wave) kept in registers ---------------------------------------------------
         f32x16 acc2[2][1] = {{{0}}, {{0}}};
-        pcb_layer2<2, TR>(abase, w2rs, voff, wave_s, ring2, acc2);
+        pcb_layer2<2>(abase, w2rs, voff, wave_s, ring2, acc2);
         PcB3x2 ring3[2];                             // layer 3's weights (n-tiles wave, wave + 4), in flight across the epilogue
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -534,18 +531,12 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a
         }
         if (ch + 1 < nchunks) stage0a(ch + 1, nxt);
         __syncthreads();  // every wave has read act1: the image is free
-        {
-            if (TR) {   // register r = channel c_row_i(r) + 4 fh of this wave's n-tile
-                f32x4 bq[4];
+        {   // register r = channel c_row_i(r) + 4 fh of this wave's n-tile
+            f32x4 bq[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave * 32 + 8 * g + 4 * fh);
-                ct_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int r) { return fmaxf(acc2[0][0][r] + bq[r >> 2][r & 3], 0.f); });
-                ct_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane, [&](int r) { return fmaxf(acc2[1][0][r] + bq[r >> 2][r & 3], 0.f); });
-            } else {
-                const float bias = a.b2[wave * 32 + fl];
-                c_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int i) { return fmaxf(acc2[0][0][i] + bias, 0.f); });
-                c_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane, [&](int i) { return fmaxf(acc2[1][0][i] + bias, 0.f); });
-            }
+            for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave * 32 + 8 * g + 4 * fh);
+            ct_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int r) { return fmaxf(acc2[0][0][r] + bq[r >> 2][r & 3], 0.f); });
+            ct_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane, [&](int r) { return fmaxf(acc2[1][0][r] + bq[r >> 2][r & 3], 0.f); });
         }
         __syncthreads();  // act2 complete; rel[nxt] / swT[nxt] visible
         if (ch + 1 < nchunks) gather_u(nxt);                                // consumed after layer 3
@@ -1108,11 +1099,8 @@ int launch_pc_group(const iq_pointconv_sa& sa, const float* xyz, const float* ne
         // every group runs all its K members (sums, not maxima: nothing is skipped); MFMA work = the two dense layers + the
         // contraction's 16x16x4 tiles
         iq::ProfileSpan dom(iq::kSlotDominant, st, 2.0 * (double)B * S * K * ((double)c1 * c2 + (double)c2 * c3 + 16.0 * c3));
-        if (a.w2_bf3 && a.w3_bf3 && iq::tuning(iq::kTuneExperiment) != 56)   // 5 = 56: the fp32-MFMA kernel (A/B and tests)
-        {
-            if (!iq::tuning(iq::kTuneNoTranspose)) hipLaunchKernelGGL(pc_group_bf3_kernel<true>, grid, dim3(kThreads), 0, st, a);
-            else hipLaunchKernelGGL(pc_group_bf3_kernel<false>, grid, dim3(kThreads), 0, st, a);
-        }
+        if (a.w2_bf3 && a.w3_bf3 && iq::twin() != iq::kTwinGroupFp32)   // the twin: the fp32-MFMA kernel (A/B and tests)
+            hipLaunchKernelGGL(pc_group_bf3_kernel, grid, dim3(kThreads), 0, st, a);
         else
             hipLaunchKernelGGL((pc_group_kernel<128, 128, 256>), grid, dim3(kThreads), 0, st, a);
     }
@@ -1171,8 +1159,8 @@ int run_pointconv(const iq_pointconv_weights* w, const float* xyz, float* logits
             hipLaunchKernelGGL(pc_member_kernel<32>, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, xyz, s.nx1,
                                s.idx1, s.inv1, nets, s.mrel, s.msw, N, S1, total, s.nu1);
             const iq_dense_layer& lin = w->sa[0].linear;
-            if (lin.cin == 2048 && lin.cout == 128 && iq::tuning(iq::kTuneExperiment) != 31) {
-                // contraction + the 2048 -> 128 layer in one kernel (5 = 31: the two-kernel form, A/B runs and tests)
+            if (lin.cin == 2048 && lin.cout == 128 && iq::twin() != iq::kTwinPcTwoKernel) {
+                // contraction + the 2048 -> 128 layer in one kernel (twin kTwinPcTwoKernel: the two-kernel form, A/B runs and tests)
                 PcFusedArgs fa{walk->feat_tab, s.msw, s.idx1, s.fps1, walk->kept, s.nu1, walk->cloud_of, lin.w, lin.b, s.l1, N, S1, B,
                                walk->nclouds};
                 hipLaunchKernelGGL(pc_tab_fused_kernel, dim3((unsigned)(8 * ((B + 7) / 8) * (S1 / 32))), dim3(kThreads), 0, st, fa);
@@ -1381,10 +1369,10 @@ extern "C" int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, con
                        t.X, N, B, nclouds);
     if ((rc = iq::check_launch("pc_mask_kernel"))) return rc;
     // the lists for up to 8 source clouds whatever B is: the two ways of forming a group differ in the order of the sum over its
-    // members, and a coalition's logits must not depend on how many others share its launch (5 = 14: pc_knn_kernel)
+    // members, and a coalition's logits must not depend on how many others share its launch (twin kTwinPcKnn: pc_knn_kernel)
     // tables_state bits 2-3 (in): 1 = always the list walk, 2 = never - a caller that splits one batch over several launches names
     // the path once, so that every launch (a short tail included) forms its groups the same way; 0 = decide from this launch
-    const bool use_walk = (force == 1 || (force == 0 && (nclouds <= 8 || (long long)nclouds * 8 <= B))) && iq::tuning(iq::kTuneExperiment) != 14;
+    const bool use_walk = (force == 1 || (force == 0 && (nclouds <= 8 || (long long)nclouds * 8 <= B))) && iq::twin() != iq::kTwinPcKnn;
     PcWalk walk{};
     if (use_walk) {
         if (!(have & 1)) {
@@ -1398,7 +1386,7 @@ extern "C" int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, con
         const iq_pointconv_sa& sa = w->sa[0];
         // (whatever B is: a coalition's logits must not depend on how many others share its launch)
         if (nclouds <= kTabClouds && sa.l2.cin == 64 && sa.l2.cout == 64 && sa.l3.cout == 128 &&
-            iq::tuning(iq::kTuneExperiment) != 15) {   // 5 = 15: the grouped MLP (A/B runs, tests)
+            iq::twin() != iq::kTwinPcGroupedMlp) {   // the twin: the grouped MLP (A/B runs, tests)
             const int n1 = N + 1;
             const size_t rows = (size_t)n1 * n1;
             for (int c = 0; c < nclouds && !(have & 2); ++c) {

@@ -61,37 +61,10 @@ struct ChainArgs {
     int32_t* argrow;           // (items,1024) point index of the row that attains each column maximum, or null [ARGMAX trunk only]
     int N, R, items, nclouds, with_centre;
     int tail16;                  // last m-tile of an item on 16x16x4 MFMAs when it holds at most 16 rows (l3_tail16)
-    int l3_single;               // bf16x3 layer 3 one n-tile per pass (tuning key 5 = 58: A/B against two per pass)
-    unsigned long long* stamps;  // diagnostic build only
+    int l3_single;               // bf16x3 layer 3 one n-tile per pass (twin kTwinChainL3Single: A/B against two per pass)
 };
 
 // ---- L3: 128 -> 1024 for one 64-row chunk; wave `wave` owns the n-tiles q*4 + wave ------------
-// Variant 0: B fragments two K-blocks ahead in a small register ring, compiler-scheduled.
-template <int MTS>
-__device__ __forceinline__ void l3_pass_v0(const WBuf& w3, const float* abase, int wave_s, float (&runmax)[8]) {
-    int wq = wave_s * 16 * kFragBytes;
-    f32x4 b0 = wbuf_load(w3, wq);
-    f32x4 b1 = wbuf_load(w3, wq + kFragBytes);
-#pragma unroll 1
-    for (int q = 0; q < 8; ++q) {
-        const int wnext = (min(q + 1, 7) * 4 + wave_s) * 16 * kFragBytes;
-        f32x16 acc0 = {0}, acc1 = {0};
-#pragma unroll 4
-        for (int kb = 0; kb < 16; ++kb) {
-            const f32x4 bn = wbuf_load(w3, (kb + 2 < 16) ? wq + (kb + 2) * kFragBytes : wnext + (kb + 2 - 16) * kFragBytes);
-            acc0 = mfma4(lds_frag<kLd2>(abase, 0, kb), b0, acc0);
-            if (MTS == 2) acc1 = mfma4(lds_frag<kLd2>(abase, 1, kb), b0, acc1);
-            b0 = b1;
-            b1 = bn;
-        }
-        float m = max16(acc0);
-        if (MTS == 2) m = fmaxf(m, max16(acc1));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) runmax[i] = (i == q) ? fmaxf(runmax[i], m) : runmax[i];
-        wq = wnext;
-    }
-}
-
 // Variant 2: an 8-deep register ring of B fragments (32 VGPRs) that runs 8 K-blocks (4 096 MFMA
 // cycles) ahead and never drains: it rolls over n-tile boundaries and, through `ring`, over chunk
 // boundaries (the last n-tile of a chunk prefetches the first K-blocks of n-tile 0).  A fragments are
@@ -257,9 +230,7 @@ __device__ __forceinline__ void l3_pass_bf3(const __amdgpu_buffer_rsrc_t& rs, in
 // LDS once for both, half the LDS traffic of l3_pass_bf3 (the kernel is power-bound: operand bytes cost clock).  Every tile sees
 // the same products in the same order, so the maxima are bit-identical to l3_pass_bf3's.  ring.r[2 i + j] = fragment (k-step
 // parity i, n-tile j of the pair), two k-steps (1 536 matrix cycles) ahead, rolling over pair and chunk boundaries.
-// PROBE (diagnostic instantiations, tuning key 5 = 91 / 92 / 93, results WRONG, timing only): bit 0 = the weight fragments are
-// never refilled (no L2 / L1 traffic in the loop), bit 1 = the A terms are read from LDS for the first k-step of a pass only.
-template <int MTS, int PROBE = 0>
+template <int MTS>
 __device__ __forceinline__ void l3_pass_bf3_2x2(const __amdgpu_buffer_rsrc_t& rs, int voff, const unsigned char* abase, int wave_s,
                                                 float (&runmax)[8], B3Ring& ring) {
 #pragma unroll 1
@@ -270,17 +241,13 @@ __device__ __forceinline__ void l3_pass_bf3_2x2(const __amdgpu_buffer_rsrc_t& rs
         bf16x8 af[MTS][3];
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            if (!(PROBE & 2) || s == 0) {
 #pragma unroll
-                for (int i = 0; i < MTS; ++i) a3_load<kPlaneB>(af[i], abase + i * 32 * kLdB, s);
-            }
+            for (int i = 0; i < MTS; ++i) a3_load<kPlaneB>(af[i], abase + i * 32 * kLdB, s);
             const B3 b[2] = {ring.r[2 * (s & 1)], ring.r[2 * (s & 1) + 1]};
             // k-step s + 2 of this pair, or k-step s - 6 of the next one (b3_load takes the n-tile index mod 8)
             const int qn = s + 2 < 8 ? 2 * qp : 2 * qp + 2, sn = (s + 2) & 7;
-            if (!(PROBE & 1)) {
-                ring.r[2 * (s & 1)] = b3_load(rs, voff, qn * 8 + sn, wave_s);
-                ring.r[2 * (s & 1) + 1] = b3_load(rs, voff, (qn + 1) * 8 + sn, wave_s);
-            }
+            ring.r[2 * (s & 1)] = b3_load(rs, voff, qn * 8 + sn, wave_s);
+            ring.r[2 * (s & 1) + 1] = b3_load(rs, voff, (qn + 1) * 8 + sn, wave_s);
             mfma_bf3_block<MTS, 2>(af, b, acc);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -350,24 +317,7 @@ __device__ __forceinline__ void l3_tail16(const WBuf& w3, const float* act2, int
     }
 }
 
-// Diagnostic build only (STAMP): per-phase shader-clock sums, added to a.stamps by lane 0 of every wave.
-__device__ __forceinline__ unsigned long long stamp_now() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define IQ_STAMP(slot)                                              \
-    do {                                                            \
-        if (STAMP) {                                                \
-            const unsigned long long t_ = stamp_now();              \
-            tsum[slot] += (unsigned)(t_ - tlast);                   \
-            tlast = t_;                                             \
-        }                                                           \
-    } while (0)
-
-template <int MODE, int L3V, bool STAMP = false, bool ARGMAX = false, int PROBE = 0>
+template <int MODE, int L3V, bool ARGMAX = false>
 __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(ChainArgs a) {
     // act0 (ld 68) then act2: float image (ld 132), or - L3V = 3 - three bf16 planes of 272-byte rows
     __shared__ __attribute__((aligned(16))) float bufA[L3V == 3 ? 3 * kPlaneB / 4 : kMC * kLd2];
@@ -441,8 +391,6 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         for (int i = 0; i < 4; ++i)   // l3_pass_bf3: k-steps 0..3 of n-tile 0; l3_pass_bf3_2x2: k-steps 0..1 of n-tiles 0 and 1
             ring3.r[i] = b3_load(w3rs, lane * 16, ARGMAX || a.l3_single ? i : (i & 1) * 8 + (i >> 1), wave_s);
     }
-    unsigned tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long tlast = STAMP ? stamp_now() : 0ull;
     for (int ch = 0; ch < nchunks; ++ch) {
         const int rows_here = min(kMC, nrows - ch * kMC);
         const int mts = rows_here > 32 ? 2 : 1;
@@ -459,9 +407,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             }
             *reinterpret_cast<f32x4*>(xs + frow * 4) = (f32x4){x, y, z, 0.f};
         }
-        IQ_STAMP(0);
         __syncthreads();  // also orders the previous chunk's L3 reads of bufA before stage 0b rewrites it
-        IQ_STAMP(1);
         if (fetcher && ch + 1 < nchunks) {
             load_point(pnext);
             if (ch + 2 < nchunks) pnext = rowp[(ch + 2) * kMC];
@@ -483,9 +429,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             f32x4 bw[8];  // weight fragments are requested before the barrier, consumed after it
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) bw[kb] = wbuf_load(w1b, wq + kb * kFragBytes);
-            IQ_STAMP(2);
             __syncthreads();
-            IQ_STAMP(3);
             if (mt < mts) {
                 f32x16 acc = {0};
 #pragma unroll
@@ -526,9 +470,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             B3 bw[PF];
 #pragma unroll
             for (int ks = 0; ks < PF; ++ks) bw[ks] = b3_load_l2(w2rs, lane * 16, nts, ks);
-            IQ_STAMP(4);
             __syncthreads();
-            IQ_STAMP(3);
             if (mt < mts) {
                 const unsigned char* arow = reinterpret_cast<const unsigned char*>(bufB) + (mt * 32 + frag_lane) * kLd1B + frag_h * 16;
 #pragma unroll
@@ -558,9 +500,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             f32x4 bw[8];
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb) bw[kb] = wbuf_load(w2b, wq0 + kb * kFragBytes);
-            IQ_STAMP(4);
             __syncthreads();
-            IQ_STAMP(3);
             if (mt < mts) {
                 const float* arow = a1base_B + mt * 32 * kLd1;
                 float* dst = c2base + mt * 32 * kLd2 + nt0 * 32;
@@ -579,9 +519,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
                 }
             }
         }
-        IQ_STAMP(5);
         __syncthreads();
-        IQ_STAMP(3);
         // ---- L3: 128 -> 1024, running column max -------------------------------------------
         if (L3V == 3) {
             const unsigned char* ab3 = reinterpret_cast<const unsigned char*>(bufA) + frag_lane * kLdB + frag_h * 16;
@@ -589,23 +527,15 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
                 if (mts == 2) l3_pass_bf3<2, ARGMAX>(w3rs, lane * 16, ab3, wave_s, runmax, ring3, runarg, ch * kMC, frag_h);
                 else          l3_pass_bf3<1, ARGMAX>(w3rs, lane * 16, ab3, wave_s, runmax, ring3, runarg, ch * kMC, frag_h);
             } else {
-                if (mts == 2) l3_pass_bf3_2x2<2, PROBE>(w3rs, lane * 16, ab3, wave_s, runmax, ring3);
-                else          l3_pass_bf3_2x2<1, PROBE>(w3rs, lane * 16, ab3, wave_s, runmax, ring3);
+                if (mts == 2) l3_pass_bf3_2x2<2>(w3rs, lane * 16, ab3, wave_s, runmax, ring3);
+                else          l3_pass_bf3_2x2<1>(w3rs, lane * 16, ab3, wave_s, runmax, ring3);
             }
-        } else if (L3V == 0) {
-            if (mts == 2) l3_pass_v0<2>(w3b, a2base, wave_s, runmax);
-            else          l3_pass_v0<1>(w3b, a2base, wave_s, runmax);
         } else {
             const bool tail = !ARGMAX && a.tail16 && rows_here - 32 * (mts - 1) <= 16;   // (uniform) the last m-tile holds <= 16 rows
             if (mts == 2 && !tail) l3_pass_v2<2, ARGMAX>(w3b, a2base, wave_s, runmax, ring, runarg, ch * kMC, frag_h);
             else if (mts == 2 || !tail) l3_pass_v2<1, ARGMAX>(w3b, a2base, wave_s, runmax, ring, runarg, ch * kMC, frag_h);
             if (tail) l3_tail16(w3b, bufA, 32 * (mts - 1), wave_s, lane, runmax, ring);
         }
-        IQ_STAMP(6);
-    }
-    if (STAMP && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) atomicAdd(&a.stamps[i], (unsigned long long)tsum[i]);
     }
 
     // max commutes with the (monotone) per-column bias add and relu
@@ -800,26 +730,16 @@ __global__ __launch_bounds__(kThreads) void pn_fill_rows_kernel(float* __restric
 
 template <int MODE>
 void launch_chain(const ChainArgs& a, hipStream_t st) {
-    const size_t extra_lds = (size_t)iq::tuning(iq::kTuneExtraLds);  // experiment: lower the occupancy
-    const int knob = iq::tuning(iq::kTuneExperiment);
-    const bool fp32_l3 = knob == 54 || knob == 55;   // layer 3 on the fp32 MFMA (round 3's kernel; A/B and tests), 55: without tail16
-    if (a.stamps && MODE == kFstn)
-        hipLaunchKernelGGL((pn_chain_kernel<kFstn, 2, true>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
-    else if (iq::tuning(iq::kTuneL3Variant) == 0)
-        hipLaunchKernelGGL((pn_chain_kernel<MODE, 0>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
-    else if (MODE == kTrunk && a.argrow && a.w3_bf3 && a.w2_bf3 && !fp32_l3)
-        hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 3, false, true>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
+    // twins kTwinChainL3Fp32 / kTwinChainL3Fp32NoTail16: layer 3 on the fp32 MFMA (round 3's kernel; A/B and tests)
+    const bool fp32_l3 = iq::twin() == iq::kTwinChainL3Fp32 || iq::twin() == iq::kTwinChainL3Fp32NoTail16;
+    if (MODE == kTrunk && a.argrow && a.w3_bf3 && a.w2_bf3 && !fp32_l3)
+        hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 3, true>), dim3(a.items), dim3(kThreads), 0, st, a);
     else if (MODE == kTrunk && a.argrow)
-        hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 2, false, true>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
-    else if (MODE != kPrepool && a.w3_bf3 && a.w2_bf3 && !fp32_l3 && knob >= 91 && knob <= 93) {   // timing probes, results wrong
-        if (knob == 91) hipLaunchKernelGGL((pn_chain_kernel<MODE == kPrepool ? kFstn : MODE, 3, false, false, 1>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
-        else if (knob == 92) hipLaunchKernelGGL((pn_chain_kernel<MODE == kPrepool ? kFstn : MODE, 3, false, false, 2>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
-        else hipLaunchKernelGGL((pn_chain_kernel<MODE == kPrepool ? kFstn : MODE, 3, false, false, 3>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
-    }
+        hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 2, true>), dim3(a.items), dim3(kThreads), 0, st, a);
     else if (MODE != kPrepool && a.w3_bf3 && a.w2_bf3 && !fp32_l3)
-        hipLaunchKernelGGL((pn_chain_kernel<MODE, 3>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
+        hipLaunchKernelGGL((pn_chain_kernel<MODE, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
     else
-        hipLaunchKernelGGL((pn_chain_kernel<MODE, 2>), dim3(a.items), dim3(kThreads), extra_lds, st, a);
+        hipLaunchKernelGGL((pn_chain_kernel<MODE, 2>), dim3(a.items), dim3(kThreads), 0, st, a);
 }
 
 }  // namespace
@@ -875,32 +795,6 @@ Workspace carve(void* base, int B, int nclouds, int N, int R) {
 
 }  // namespace
 
-namespace { unsigned long long* g_stamps = nullptr; }
-
-// Diagnostic: phase stamps of the feature-STN chain (STAMP build).  enable allocates/zeroes a
-// device buffer of 8 counters; read copies them to the host (synchronises the device).
-extern "C" int iq_debug_stamps(int enable, unsigned long long* out_host /*8 or null*/) {
-    if (out_host && g_stamps) {
-        if (hipDeviceSynchronize() != hipSuccess) return IQ_ELAUNCH;
-        if (hipMemcpy(out_host, g_stamps, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return IQ_ELAUNCH;
-    }
-    if (enable) {
-        if (!g_stamps && hipMalloc(&g_stamps, 8 * sizeof(unsigned long long)) != hipSuccess) return IQ_ELAUNCH;
-        if (hipMemset(g_stamps, 0, 8 * sizeof(unsigned long long)) != hipSuccess) return IQ_ELAUNCH;
-    } else if (g_stamps) {
-        (void)hipFree(g_stamps);
-        g_stamps = nullptr;
-    }
-    return IQ_OK;
-}
-
-extern "C" int iq_debug_chain_occupancy(void) {
-    int n0 = -1, n2 = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n0, pn_chain_kernel<kFstn, 0>, kThreads, 0) != hipSuccess) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, pn_chain_kernel<kFstn, 2>, kThreads, 0) != hipSuccess) return -1;
-    return n0 * 100 + n2;
-}
-
 extern "C" size_t iq_pointnet_workspace_bytes(int B, int nclouds, int N, int R) {
     if (B < 0 || nclouds < 0 || N < 0 || R < 0) return 0;
     return carve(nullptr, B, nclouds, N, R).bytes;
@@ -936,7 +830,6 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
     IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == B, "iq_pointnet_coalitions: cloud_of required when 1 < nclouds != B");
     const int with_centre = centers ? 1 : 0;  // no centre = dense mode (nothing is ever masked)
     IQ_REQUIRE(centers || !keep, "iq_pointnet_coalitions: keep masks need centers");
-    IQ_REQUIRE(!crt_points || iq::tuning(iq::kTuneL3Variant) == 2, "iq_pointnet_coalitions_crt: crt_points need the default L3 variant");
     if (B == 0) return IQ_OK;
     const size_t need = iq_pointnet_workspace_bytes(B, nclouds, N, R);
     if (!workspace || workspace_bytes < need)
@@ -955,17 +848,14 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
                        ws.nrows, N, R, nclouds, with_centre, 0);
     if ((rc = iq::check_launch("pn_rows_kernel"))) return rc;
     // launch order of the coalition chains: most rows first, so the grid drains evenly
-    const bool lpt = iq::tuning(iq::kTuneNoLpt) == 0;
-    if (lpt) {
-        if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
-            return iq::fail(IQ_ELAUNCH, "iq_pointnet_coalitions: memset failed");
-        hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
-                           ws.bin_of, ws.hist, B);
-        hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
-        hipLaunchKernelGGL(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                           ws.bin_of, ws.hist, ws.order, B);
-        if ((rc = iq::check_launch("pn_order kernels"))) return rc;
-    }
+    if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
+        return iq::fail(IQ_ELAUNCH, "iq_pointnet_coalitions: memset failed");
+    hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
+                       ws.bin_of, ws.hist, B);
+    hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
+    hipLaunchKernelGGL(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+                       ws.bin_of, ws.hist, ws.order, B);
+    if ((rc = iq::check_launch("pn_order kernels"))) return rc;
 
     ChainArgs a{};
     a.clouds = clouds;
@@ -976,9 +866,8 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
     a.nrows = ws.nrows_pre;
     a.item_order = nullptr;
     a.N = N; a.R = R; a.nclouds = nclouds; a.with_centre = with_centre;
-    a.stamps = g_stamps;
-    a.tail16 = iq::tuning(iq::kTuneExperiment) != 16 && iq::tuning(iq::kTuneExperiment) != 55;   // 16, 55: 32-row tiles only
-    a.l3_single = iq::tuning(iq::kTuneExperiment) == 58;
+    a.tail16 = iq::twin() != iq::kTwinChainL3Fp32NoTail16;
+    a.l3_single = iq::twin() == iq::kTwinChainL3Single;
 
 
     // 1. input-STN chain, pre-pooled per (cloud, region) [+ centre]
@@ -1005,7 +894,7 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
     // 2. feature-STN chain over each coalition's distinct points
     a.cloud_of = cloud_of; a.trans = ws.trans;
     a.rows = ws.rows; a.nrows = ws.nrows;
-    a.item_order = lpt ? ws.order : nullptr;
+    a.item_order = ws.order;
     a.w_in = w->feat_in;
     a.items = B;
     a.out = ws.gbuf;

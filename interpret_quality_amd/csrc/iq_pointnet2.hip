@@ -176,7 +176,6 @@ struct GroupArgs {
     int ldo;
     int N, S, K, blocks_per_wg;
     int B, wgs_per_cloud;
-    int probe;               // tuning key 5 (79: per-phase cycle counts of pn2_group_bf3_kernel)
 };
 
 __device__ __forceinline__ void merge_max(float* addr, float v) {
@@ -436,9 +435,9 @@ __global__ __launch_bounds__(kThreads, WPS) void pn2_group_kernel(GroupArgs a) {
 // loops is what saturates it; (3) the VALU phases (layer 1, the three-term splits) written stage by stage over eight independent
 // values instead of value by value (the compiler's schedule is one dependent chain after the other on two or three temporaries):
 // bit-identical, no change (81.5 / 81.9 k; PointConv 85.0 / 84.9 k; chain kernel 781.2 / 781.7 k).
-__device__ unsigned long long g_gb_dbg[12];
-// TR: the TRANSPOSED tiles (weights as the A operand, iq_bf3.h ct_tile_to_planes): same fragments, same products, swapped operands
-template <int MTS, bool TR>
+// Layer 2 on TRANSPOSED tiles (weights as the A operand, iq_bf3.h ct_tile_to_planes), so that act2 is stored with whole 8-byte
+// stores and without the two-lane DPP trade
+template <int MTS>
 __device__ __forceinline__ void gb_layer2(const unsigned char* abase, const __amdgpu_buffer_rsrc_t& rs, int voff, int nt,
                                           B3 (&ring)[4], f32x16 (&acc)[MTS][1]) {
     constexpr int ROWB = 272, PLANEB = 64 * ROWB, TS = 4 * 8 * 1024;
@@ -447,10 +446,9 @@ __device__ __forceinline__ void gb_layer2(const unsigned char* abase, const __am
         bf16x8 af[MTS][3];
 #pragma unroll
         for (int i = 0; i < MTS; ++i) a3_load<PLANEB>(af[i], abase + i * 32 * ROWB, ks);
-        const B3 b[1] = {ring[ks & 3]};
+        const B3 b = ring[ks & 3];
         if (ks + 4 < 8) ring[ks & 3] = b3_load_at(rs, voff, (nt * 8 + ks + 4) * 1024, TS);
-        if (TR) mfma_bf3_block_tr<MTS>(af, b[0], acc);
-        else mfma_bf3_block<MTS, 1>(af, b, acc);
+        mfma_bf3_block_tr<MTS>(af, b, acc);
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -474,9 +472,6 @@ __device__ __forceinline__ void gb_layer3(const unsigned char* abase, const __am
     }
 }
 
-// TR (the default): layer 2's tiles transposed, so that act2 is stored with whole 8-byte stores and without the two-lane DPP trade
-// (tuning key 7 = 1: the untransposed form; same products in the same order).
-template <bool STAMP, bool TR>   // STAMP: diagnostic build (tuning key 5 = 79)
 __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a) {
     constexpr int C1 = 128, kMC = 64, ROWB = 272, PLANEB = kMC * ROWB, BPC = kMC / kBlk;
     __shared__ __attribute__((aligned(16))) unsigned char planes[3 * PLANEB];   // act1, then act2: three bf16 planes [64][136]
@@ -498,21 +493,10 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
 
     const int fl = lane & 31, fh = lane >> 5;
     const unsigned char* abase = planes + fl * ROWB + 16 * fh;
-    // STAMP: shader cycles per phase of wave 0, summed over workgroups (g_gb_dbg, printed by launch_group_t).  Measured (r4,
-    // cycles per 64-row chunk and wave, two workgroups per CU): stage 0b 4 400, layer 2 5 700, stage 0a 1 850, layer-2
-    // epilogue 4 000, layer 3 + pooling 14 300, barrier waits 1 250, prologue + flush 2 000 per chunk = 33 400, of which the
-    // 288 MFMAs need 9 200: the other wave of the SIMD does the same, and its VALU phases do not hide under this wave's MFMAs
-    // (the two share the SIMD's issue and register ports) - 0.55 MFMA-busy.
-    unsigned long long t_last = 0;
-    unsigned t_sum[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto stamp = [&](int slot) {
-        if (STAMP) {
-            unsigned long long t;
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-            if (slot >= 0) t_sum[slot] += (unsigned)(t - t_last);
-            t_last = t;
-        }
-    };
+    // Measured (r4, s_memtime stamps of wave 0, cycles per 64-row chunk and wave, two workgroups per CU): stage 0b 4 400, layer 2
+    // 5 700, stage 0a 1 850, layer-2 epilogue 4 000, layer 3 + pooling 14 300, barrier waits 1 250, prologue + flush 2 000 per
+    // chunk = 33 400, of which the 288 MFMAs need 9 200: the other wave of the SIMD does the same, and its VALU phases do not hide
+    // under this wave's MFMAs (the two share the SIMD's issue and register ports) - 0.55 MFMA-busy.
 
     constexpr int Q1 = C1 / 4, NR = kMC * Q1 / kThreads;   // stage 0b: a thread owns 4 consecutive channels of NR rows
     const int c4 = tid % Q1, rsub = tid / Q1;
@@ -549,11 +533,9 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
             else ureg[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
     };
-    stamp(-1);
     stage0a(0, 0);
     __syncthreads();
     gather_u(0);
-    stamp(0);   // prologue
 
     int run_g[2] = {-1, -1};
     float run_v[2] = {0.f, 0.f};
@@ -597,16 +579,14 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
                 h[e] = fmaxf(fmaf(w1[e][2], v[2], fmaf(w1[e][1], v[1], w1[e][0] * v[0])) + w1[e][3] + ureg[i][e], 0.f);
             row4_to_planes<PLANEB>(planes + r * ROWB + c4 * 8, h);
         }
-        stamp(1);   // ring prime + stage 0b
         __syncthreads();  // act1 complete
-        stamp(2);   // wait
         // ---- layer 2: 128 -> 128, tiles (m-tile 0..1, n-tile = wave) kept in registers -------------------
         f32x16 acc2[2][1] = {{{0}}, {{0}}};
         if (mts == 2) {
-            gb_layer2<2, TR>(abase, w2rs, voff, wave_s, ring2, acc2);
+            gb_layer2<2>(abase, w2rs, voff, wave_s, ring2, acc2);
         } else {
             f32x16 one[1][1] = {{{0}}};
-            gb_layer2<1, TR>(abase, w2rs, voff, wave_s, ring2, one);
+            gb_layer2<1>(abase, w2rs, voff, wave_s, ring2, one);
             acc2[0][0] = one[0][0];
         }
         B3x2 ring3[2];                               // layer 3's weights (n-tiles wave, wave + 4), in flight across the epilogue
@@ -615,30 +595,18 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
             ring3[i].b[0] = b3_load_at(w3rs, voff, (wave_s * 8 + i) * 1024, 8 * 8 * 1024);
             ring3[i].b[1] = b3_load_at(w3rs, voff, ((wave_s + 4) * 8 + i) * 1024, 8 * 8 * 1024);
         }
-        stamp(3);   // layer 2 MFMAs + ring 3 prime
         if (ch + 1 < nchunks) stage0a(ch + 1, nxt);
-        stamp(4);   // stage 0a of the next chunk
         __syncthreads();  // every wave has read act1: the image is free
-        stamp(5);   // wait
-        {
-            if (TR) {   // register r = channel c_row_i(r) + 4 fh of this wave's n-tile: the biases of the lane's 16 channels
-                f32x4 bq[4];
+        {   // register r = channel c_row_i(r) + 4 fh of this wave's n-tile: the biases of the lane's 16 channels
+            f32x4 bq[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave * 32 + 8 * g + 4 * fh);
-                ct_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int r) { return fmaxf(acc2[0][0][r] + bq[r >> 2][r & 3], 0.f); });
-                if (mts == 2)
-                    ct_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane,
-                                                    [&](int r) { return fmaxf(acc2[1][0][r] + bq[r >> 2][r & 3], 0.f); });
-            } else {
-                const float bias = a.b2[wave * 32 + fl];
-                c_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int i) { return fmaxf(acc2[0][0][i] + bias, 0.f); });
-                if (mts == 2)
-                    c_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane, [&](int i) { return fmaxf(acc2[1][0][i] + bias, 0.f); });
-            }
+            for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave * 32 + 8 * g + 4 * fh);
+            ct_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int r) { return fmaxf(acc2[0][0][r] + bq[r >> 2][r & 3], 0.f); });
+            if (mts == 2)
+                ct_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane,
+                                                [&](int r) { return fmaxf(acc2[1][0][r] + bq[r >> 2][r & 3], 0.f); });
         }
-        stamp(6);   // layer 2 epilogue
         __syncthreads();  // act2 complete; rel[nxt] visible
-        stamp(7);   // wait
         if (ch + 1 < nchunks) gather_u(nxt);  // consumed after layer 3
         // ---- layer 3: 128 -> 256, 2 x 2 tiles per wave, block maxima merged into the owning groups -------
         if (mts == 2) {
@@ -665,17 +633,10 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
                 for (int i = 0; i < 4; ++i) feed(q, gq[i], m0.v[i]);
             }
         }
-        stamp(8);   // gather + layer 3 + pooling
         __syncthreads();  // every wave has read act2: the next chunk's stage 0b may overwrite the image
-        stamp(9);   // wait
     }
     flush_group(0);
     flush_group(1);
-    stamp(10);
-    if (STAMP && tid == 0) {
-        for (int i = 0; i < 11; ++i) atomicAdd(&g_gb_dbg[i], (unsigned long long)t_sum[i]);
-        atomicAdd(&g_gb_dbg[11], (unsigned long long)nchunks);
-    }
 }
 
 // rows s >= n_unique[b] := row 0 (duplicate centroids), columns [c0, c0+ncols)
@@ -707,26 +668,12 @@ int launch_group_t(GroupArgs a, int B, hipStream_t st) {
     a.wgs_per_cloud = (a.maxblocks + a.blocks_per_wg - 1) / a.blocks_per_wg;  // workgroups past a cloud's block count exit
     dim3 grid((unsigned)((B + 7) / 8 * 8 * a.wgs_per_cloud));
     // the widest stage (128-128-256: 70 KB of LDS and 150 registers at 64 rows = 2 workgroups per CU) runs 32-row chunks,
-    // 4 workgroups per CU: 44.5 k -> 46.3 k coalitions/s (tuning key 5 = 64 forces 64-row chunks for A/B runs)
-    if (C1 == 128 && C2 == 128 && C3 == 256 && a.w2_bf3 && a.w3_bf3 && iq::tuning(iq::kTuneExperiment) != 56 &&
-        iq::tuning(iq::kTuneExperiment) != 64)    // 5 = 56 / 64: the fp32-MFMA kernel with 32- / 64-row chunks (A/B and tests)
-    {
-        if (a.probe != 79 && !iq::tuning(iq::kTuneNoTranspose)) hipLaunchKernelGGL((pn2_group_bf3_kernel<false, true>), grid, dim3(kThreads), 0, st, a);
-        else if (a.probe != 79) hipLaunchKernelGGL((pn2_group_bf3_kernel<false, false>), grid, dim3(kThreads), 0, st, a);
-        else {   // diagnostic: synchronous
-            hipLaunchKernelGGL((pn2_group_bf3_kernel<true, true>), grid, dim3(kThreads), 0, st, a);
-            unsigned long long h[12];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_gb_dbg), sizeof(h));
-            const double n = (double)h[11];
-            fprintf(stderr, "pn2_group_bf3 (wave 0, cycles per chunk over %.0f chunks): prologue/chunk %.0f | ring2+stage0b %.0f wait %.0f | L2 %.0f stage0a %.0f "
-                            "wait %.0f | epilogue %.0f wait %.0f | gather+L3+pool %.0f wait %.0f | flush/chunk %.0f\n", n, h[0] / n, h[1] / n, h[2] / n,
-                    h[3] / n, h[4] / n, h[5] / n, h[6] / n, h[7] / n, h[8] / n, h[9] / n, h[10] / n);
-            for (auto& v : h) v = 0;
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gb_dbg), h, sizeof(h));
-        }
-    }
-    else if (C3 >= 256 && iq::tuning(iq::kTuneExperiment) != 64)
+    // 4 workgroups per CU: 44.5 k -> 46.3 k coalitions/s (twin kTwinGroupFp32Chunk64 forces 64-row chunks for A/B runs)
+    // twins kTwinGroupFp32 / kTwinGroupFp32Chunk64: the fp32-MFMA kernel with 32- / 64-row chunks (A/B and tests)
+    const bool fp32 = iq::twin() == iq::kTwinGroupFp32 || iq::twin() == iq::kTwinGroupFp32Chunk64;
+    if (C1 == 128 && C2 == 128 && C3 == 256 && a.w2_bf3 && a.w3_bf3 && !fp32)
+        hipLaunchKernelGGL(pn2_group_bf3_kernel, grid, dim3(kThreads), 0, st, a);
+    else if (C3 >= 256 && iq::twin() != iq::kTwinGroupFp32Chunk64)
         hipLaunchKernelGGL((pn2_group_kernel<C1, C2, C3, 32>), grid, dim3(kThreads), 0, st, a);
     else
         hipLaunchKernelGGL((pn2_group_kernel<C1, C2, C3, 64>), grid, dim3(kThreads), 0, st, a);
@@ -754,15 +701,14 @@ double group_work(const GroupArgs& a, int B, int c1, int c2, int c3, hipStream_t
 int launch_group(const iq_pn2_scale& sc, GroupArgs a, const int32_t* n_unique, int B, hipStream_t st, bool dominant = false,
                  const void* l2_bf3 = nullptr, const void* l3_bf3 = nullptr) {
     a.w1x = sc.w1x;
-    a.probe = iq::tuning(iq::kTuneExperiment);
     a.w2_bf3 = reinterpret_cast<const unsigned short*>(l2_bf3);
     a.w3_bf3 = reinterpret_cast<const unsigned short*>(l3_bf3);
     a.w2 = sc.l2.w; a.b2 = sc.l2.b;
     a.w3 = sc.l3.w; a.b3 = sc.l3.b;
     a.K = sc.nsample;
     // 24 blocks = 192 rows = 3 chunks of 64 rows per workgroup: enough to amortise the prologue, small enough for an even
-    // tail (512 rows: -4 %, 2048: -18 %); tuning key 6 overrides for experiments (a multiple of 8: whole chunks)
-    a.blocks_per_wg = iq::tuning(iq::kTuneGroupBlocks) > 0 ? (iq::tuning(iq::kTuneGroupBlocks) + 7) / 8 * 8 : 24;
+    // tail (512 rows: -4 %, 2048: -18 %)
+    a.blocks_per_wg = 24;
     a.maxblocks = a.S * ((a.K + kBlk - 1) / kBlk);
     const int c1 = sc.l2.cin, c2 = sc.l2.cout, c3 = sc.l3.cout;
     IQ_REQUIRE(sc.l3.cin == c2, "pointnet2 scale: layer sizes do not chain");
@@ -1043,7 +989,7 @@ struct GatherArgs {
 // the output is max over the kept regions r of  T[p][r] = max over the members of region r of row(p, member).  T depends
 // on the source cloud only: it is built once per call (pt_regtab_kernel) and a group then reads one row per kept region that
 // touches its ball (r = 0.4: ~4 rows instead of ~32 member rows; the same rows for every coalition, so they stay in L2).
-// Max is exact and order-free: bit-identical to the member walk (tested with tuning key 5 = 21, which disables the tables).
+// Max is exact and order-free: bit-identical to the member walk (tested with twin kTwinPn2MemberWalk, which disables the tables).
 // Balls around the centre (6 % at r = 0.4) and over-full balls keep the member walk.
 constexpr int kRegSlots = 64;
 
@@ -1477,7 +1423,7 @@ extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const floa
             if ((rc = iq::launch_linear(t.h1, sc.l2.cin, sc.l2, t.h2, sc.l2.cout, row0, 1, st))) return rc;
             if ((rc = iq::launch_linear(t.h2, sc.l2.cout, sc.l3, t.feat[q], sc.l3.cout, row0, 1, st))) return rc;
         }
-        if (iq::tuning(iq::kTuneExperiment) != 21) {   // region-reduced rows of this scale (21: member walk only, A/B and tests)
+        if (iq::twin() != iq::kTwinPn2MemberWalk) {   // region-reduced rows of this scale (the twin: member walk only, A/B and tests)
             int r0c = 0;
             for (int c = 0; c < nclouds; ++c) {
                 hipLaunchKernelGGL(pt_regtab_kernel, dim3(n1), dim3(kThreads), (size_t)kRegSlots * sc.l3.cout * 4, st, t.feat[q], t.pairs,
@@ -1489,8 +1435,8 @@ extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const floa
             tab.touch[q] = t.touch[q]; tab.regtab[q] = t.regtab[q];
         }
     }
-    if (tab.use[0] && tab.use[1] && tab.use[2] && N <= 1024 && iq::tuning(iq::kTuneExperiment) != 13) {
-        // sa1's ball query by bit operations on the row maps just built (tuning key 5 = 13: ball_query_kernel)
+    if (tab.use[0] && tab.use[1] && tab.use[2] && N <= 1024) {
+        // sa1's ball query by bit operations on the row maps just built
         for (int q = 0; q < 3; ++q) {
             hipLaunchKernelGGL(pt_bits_kernel, dim3(n1, nclouds), dim3(64), 0, st, t.map[q], t.ball_bits[q], n1);
             tab.ball_bits[q] = t.ball_bits[q];

@@ -19,7 +19,7 @@ def lib():
 
 def test_header_symbols_exported_and_bound(lib):
     declared = {}
-    for h in ("iq.h", "iq_debug.h"):      # the drop-in surface | diagnostics (profiler, experiment knobs, debug counters)
+    for h in ("iq.h", "iq_debug.h"):      # the drop-in surface | diagnostics (profiler, experiment knobs, matrix-pipe rate)
         header = open(os.path.join(REPO, "include", h)).read()
         header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)  # drop comments
         declared[h] = set(re.findall(r"\b(iq_[a-z0-9_]+)\s*\(", header))
@@ -34,6 +34,24 @@ def test_header_symbols_exported_and_bound(lib):
     assert declared["iq_debug.h"] == {n for n in _lib.SIGNATURES if n.startswith(("iq_debug_", "iq_profile_", "iq_set_tuning"))}
     m = re.search(r"#define IQ_ABI_VERSION (\d+)", open(os.path.join(REPO, "include", "iq.h")).read())
     assert lib.iq_version() == int(m.group(1)) >= 101
+
+
+# the (key, value) pairs iq_set_tuning accepts (include/iq_debug.h): the twins a test or bench.py selects, and 0 = the product paths
+TUNING = {3: (0, 1), 5: (0, 7, 8, 12, 14, 15, 20, 21, 22, 31, 54, 55, 56, 57, 58, 64)}
+
+
+def test_set_tuning_accepts_the_twins_and_refuses_the_rest(lib):
+    try:
+        for key, values in TUNING.items():
+            for v in values:
+                assert lib.iq_set_tuning(key, v) == 0, (key, v, lib.iq_last_error())
+        # retired knobs and timing probes: a stale script fails instead of timing the default path
+        for key, v in ((5, 91), (5, 79), (5, 10), (5, 53), (0, 0), (0, 2), (4, 3), (6, 16), (7, 1), (3, 2), (8, 0), (-1, 0)):
+            assert lib.iq_set_tuning(key, v) == -1, (key, v)       # IQ_EINVAL
+            assert ("key %d value %d" % (key, v)).encode() in lib.iq_last_error(), lib.iq_last_error()
+    finally:
+        lib.iq_set_tuning(3, 0)
+        lib.iq_set_tuning(5, 0)
 
 
 def test_pack_weight_layout(lib):

@@ -8,6 +8,7 @@ which removes the instructions at instruction selection; beside MFMAs they are a
 cycle constants).  This test disassembles the shared library itself (tools/isa_audit.py), so a compiler bump, a new flag or an
 explicit float2 expression cannot bring them back silently."""
 import os
+import re
 import sys
 
 import pytest
@@ -43,3 +44,28 @@ def test_no_packed_float32_anywhere_in_the_library(audit):
     assert any("smooth_enum_kernel" in k for k in audit)
     offenders = {k: r["packed_kinds"] for k, r in audit.items() if r["packed"]}
     assert not offenders, offenders
+
+
+def _instantiations(audit, kernel):
+    """Template argument lists of every instantiation of `kernel` in the shipped library (None: not a template)."""
+    out = []
+    for name in isa_audit.demangle(sorted(audit)).values():
+        m = re.search(r"\b%s(<([^()]*)>)?\(" % kernel, name)
+        if m:
+            out.append(None if m.group(2) is None else [a.strip() for a in m.group(2).split(",")])
+    return out
+
+
+def test_no_retired_variants_shipped(audit):
+    """Concluded A/B variants and timing probes are not compiled in: the chain kernel is <MODE, L3V, ARGMAX> with the ring (2)
+    or bf16x3 (3) layer 3, the bf16x3 GEMM <POOL, NW, RAGGED, SPLITK>, the grouped bf16x3 kernels have only the transposed
+    layer 2 (no template argument left), and no diagnostic *_dbg_* kernel ships."""
+    chain = _instantiations(audit, "pn_chain_kernel")
+    assert chain and all(len(a) == 3 and a[1] in ("2", "3") for a in chain), chain
+    gemm = _instantiations(audit, "pn_gemm_bf3_kernel")
+    assert gemm and all(len(a) == 4 and a[1] in ("4", "8") for a in gemm), gemm
+    for kernel in ("pn2_group_bf3_kernel", "pc_group_bf3_kernel"):
+        inst = _instantiations(audit, kernel)
+        assert inst == [None], (kernel, inst)
+    dbg = [n for n in isa_audit.demangle(sorted(audit)).values() if re.search(r"\w_dbg_\w", n)]
+    assert not dbg, dbg

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B the co-compiled chain-kernel variants in ONE process, interleaved rounds (guide rule 24).
-usage: python tools/ab_chain.py [--key 0] [--values 0,1] [--rounds 7] [--perms 1000]"""
+usage: python tools/ab_chain.py [--key 5] [--values 0,54] [--rounds 7] [--perms 1000]"""
 import argparse
 import ctypes
 import os
@@ -14,10 +14,9 @@ from interpret_quality_amd import _lib, final_common, hip_ops, synth  # noqa: E4
 from interpret_quality_amd.pointnet import PointNetCls  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--key", type=int, default=0)
-ap.add_argument("--values", default="0,1")
+ap.add_argument("--key", type=int, default=5)
+ap.add_argument("--values", default="0,54")
 ap.add_argument("--rounds", type=int, default=7)
-ap.add_argument("--stamps", type=int, default=0, help="run the diagnostic STAMP build once and print phase shares")
 ap.add_argument("--fixed", default="", help="key=value,... set once before the runs")
 ap.add_argument("--perms", type=int, default=1000)
 ap.add_argument("--regions", type=int, default=32)
@@ -47,28 +46,18 @@ def read(slot):
     return ms.value / max(n.value, 1)
 
 
+def tune(key, value):
+    _lib.check(lib.iq_set_tuning(key, value), "iq_set_tuning(%d, %d)" % (key, value))
+
+
 for kv in [x for x in args.fixed.split(",") if x]:
     k, v = kv.split("=")
-    lib.iq_set_tuning(int(k), int(v))
-if args.stamps:
-    lib.iq_set_tuning(0, 2)
-    model.coalition_logits(data, center, region_id, keep, None, num_regions=R)
-    torch.cuda.synchronize()
-    lib.iq_debug_stamps(1, None)
-    model.coalition_logits(data, center, region_id, keep, None, num_regions=R)
-    buf = (ctypes.c_ulonglong * 8)()
-    lib.iq_debug_stamps(0, buf)
-    names = ["stage0a (transform)", "wait barrier 1", "stage0b + L1 weight issue", "wait barriers (L1/L2/L3 entry)",
-             "L1 compute + L2 weight issue", "L2 compute", "L3", "-"]
-    tot = float(sum(buf))
-    for n, v in zip(names, buf):
-        print("  %-34s %6.2f %%" % (n, 100.0 * v / tot))
-    sys.exit(0)
+    tune(int(k), int(v))
 ref = None
 times = {v: [] for v in values}
 for rnd in range(args.rounds + 1):
     for v in values:
-        lib.iq_set_tuning(args.key, v)
+        tune(args.key, v)
         lib.iq_profile_enable(1)
         logits = model.coalition_logits(data, center, region_id, keep, None, num_regions=R)
         torch.cuda.synchronize()

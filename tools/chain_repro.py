@@ -2,7 +2,7 @@
 """Does the headline launch give the same bits every time?  33 000 PointNet coalitions (1000 permutations x 33 prefixes, 32 regions)
 evaluated over and over for --seconds; every launch's logits are compared bit by bit, on the device, with the first launch's.
 
-    [IQ_LIBPATH=interpret_quality_amd/lib_packed_ab/libiq_hip.so] python tools/chain_repro.py [--seconds 15] [--model pointnet|pointnet2|dgcnn|pointconv]
+    [IQ_LIBPATH=<another build>/libiq_hip.so] python tools/chain_repro.py [--seconds 15] [--model pointnet|pointnet2|dgcnn|pointconv]
 
 Why: round 4 blamed packed float32 instructions beside bf16 MFMAs for a few-ulp nondeterminism of ANOTHER
 process's kernel; the chain kernel itself held 51 of them beside its own 480 bf16 MFMAs.  If that mechanism were real inside one

@@ -66,12 +66,14 @@ def audit(so_path):
 
 
 def demangle(names):
-    try:
-        res = subprocess.run([os.path.join(LLVM_BIN, "llvm-cxxfilt")], input="\n".join(names), capture_output=True, text=True,
-                             check=True).stdout.split("\n")
-        return dict(zip(names, res))
-    except Exception:
-        return {n: n for n in names}
+    """{symbol: demangled name} by llvm-cxxfilt, else binutils' c++filt; the symbols themselves if neither is installed."""
+    for tool in (os.path.join(LLVM_BIN, "llvm-cxxfilt"), shutil.which("c++filt")):
+        try:
+            res = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+            return dict(zip(names, res))
+        except Exception:
+            continue
+    return {n: n for n in names}
 
 
 def main():
