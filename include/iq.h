@@ -48,8 +48,9 @@ enum {
  * dereferenced on the device.  A client built against an older header must be rebuilt (the structs grew).
  * 102 (round 5): no layout change; a bf16x3 weight image (iq_pack_weight_bf3) now has its k range padded to a multiple of 32 (only images of layers with cin % 32 == 16 differ, and no kernel consumed those before), dense
  * layers take the image for any cin >= 32 and cout = 256 n or 256 n + 64, iq_knn uses a larger tmp when it is given one, PointNet
- * takes clouds of up to IQ_MAX_POINTS points and PointConv of 64 and more. */
-#define IQ_ABI_VERSION 102
+ * takes clouds of up to IQ_MAX_POINTS points and PointConv of 64 and more.
+ * 103: new entry points, no layout change (the standalone geometric ops: iq_index_points .. iq_density). */
+#define IQ_ABI_VERSION 103
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -447,6 +448,60 @@ int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, const float* c
                                    const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
                                    void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int* tables_state,
                                    iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Standalone geometric ops of the model files (the building blocks the fused model kernels use
+ * internally, for callers that keep their own PyTorch modules)
+ *
+ * Every index read is guarded: an index outside [0, N) never addresses memory, and every output
+ * element that depends on one is written as NaN (iq_sort_neighbours: the row is left as it is).
+ * The Python front end validates caller indices with iq_check_index_range before it launches.
+ * Float outputs must be 16-byte aligned (every torch allocation is).
+ * ------------------------------------------------------------------------------------------- */
+
+/* models/pointnet2.py:27-43 and models/pointconv.py:35-52 (index_points):
+ * out[b,m,:] = points[b, idx[b,m], :].  points (B,N,C), any C >= 1; idx (B,M) int32 where M is the
+ * product of the reference's trailing index dims; out (B,M,C).  B*M*C < 2^31. */
+int iq_index_points(const float* points, const int32_t* idx, float* out, int B, int N, int M, int C,
+                    iq_stream_t stream);
+
+/* Grouping: models/pointnet2.py:93-137 (sample_and_group / _all), models/pointconv.py:117-197
+ * (sample_and_group / _all / group) with xyz_first = 1, and PointNetSetAbstractionMsg.forward
+ * (models/pointnet2.py:222-230) with xyz_first = 0.  Row (b,s,k) of out (B,S,K,3+D) is
+ * [xyz[b,i] - c, points[b,i]] (xyz_first) or [points[b,i], xyz[b,i] - c] with i = idx[b,s,k] and
+ * c = new_xyz[b,s]: one float32 subtraction per coordinate, as the reference's.  new_xyz = NULL:
+ * nothing subtracted; idx = NULL: all N points in order (S = 1, K = N); points = NULL: D = 0.
+ * B*S*K*(3+D) < 2^31. */
+int iq_group_points(const float* xyz /*B,N,3*/, const float* points /*B,N,D*/, const float* new_xyz /*B,S,3*/,
+                    const int32_t* idx /*B,S,K*/, float* out, int xyz_first, int B, int N, int S, int K, int D,
+                    iq_stream_t stream);
+
+/* models/dgcnn.py:21-47 (get_graph_feature) for a given idx:
+ * out[b,c,n,j] = x[b,c,idx[b,n,j]] - x[b,c,n] and out[b,C+c,n,j] = x[b,c,n] (c < C).
+ * x is (B,C,N) if channel_first, else (B,N,C); idx (B,N,k) int32; out (B,2C,N,k).  B*2C*N*k < 2^31. */
+int iq_edgeconv_gather(const float* x, const int32_t* idx, float* out, int channel_first, int B, int N, int C,
+                       int k, iq_stream_t stream);
+
+/* models/pointconv.py:103-114 (knn_point): per query the K nearest keys by square_distance(new_xyz, xyz)
+ * in the reference's op order (the region assignment's expression), SORTED nearest first, ties to the
+ * lower index (the reference returns the same set unsorted).  xyz (B,N,3), new_xyz (B,S,3) -> idx
+ * (B,S,K) int32.  1 <= N <= IQ_MAX_POINTS, 1 <= K <= min(N, 128).  tmp / tmp_bytes: reserved, the
+ * kernel needs no scratch (NULL, 0). */
+int iq_knn_point(const float* xyz, const float* new_xyz, int K, int32_t* idx, void* tmp, size_t tmp_bytes,
+                 int B, int N, int S, iq_stream_t stream);
+
+/* The order of models/dgcnn.py:12-18 (knn: topk(sorted=True)) for an index set that iq_knn returns
+ * unordered: each row of idx (B,S,k) int32 is reordered in place nearest first by the float32
+ * distance in the association of -xx - inner - xx^T: (|x|^2 + (-2 q.x)) + |q|^2 (channel-sequential
+ * sums, the dot product as an fma chain), ties to the lower index.  q (B,S,C), keys (B,N,C); for knn(x) both are x as (B,N,C).
+ * 1 <= k <= 128, N <= 2^24. */
+int iq_sort_neighbours(const float* q, const float* keys, int32_t* idx, int B, int N, int S, int C, int k,
+                       iq_stream_t stream);
+
+/* models/pointconv.py:199-209 (compute_density): out[b,i] = mean_j exp(-d_ij / (2h^2)) / (2.5h) with
+ * d = square_distance(xyz, xyz) - the density itself (the fused PointConv path keeps its inverse).
+ * Within 2e-6 relative of the reference.  xyz (B,N,3) -> out (B,N); B <= 65535. */
+int iq_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream);
 
 /* The diagnostic entry points (HIP-event profiler, experiment knobs, debug counters) are NOT part of the drop-in surface:
  * they are declared in iq_debug.h. */

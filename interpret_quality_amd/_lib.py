@@ -122,6 +122,12 @@ SIGNATURES = {
     "iq_pointconv_tables_bytes": (_SZ, [_I, _I]),
     "iq_pointconv_coalitions_cached": (_I, [ctypes.POINTER(PointConvWeights), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I,
                                           ctypes.POINTER(ctypes.c_int), _P]),
+    "iq_index_points": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "iq_group_points": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "iq_edgeconv_gather": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "iq_knn_point": (_I, [_P, _P, _I, _P, _P, _SZ, _I, _I, _I, _P]),
+    "iq_sort_neighbours": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "iq_density": (_I, [_P, ctypes.c_double, _P, _I, _I, _P]),
     "iq_profile_enable": (_I, [_I]),
     "iq_set_tuning": (_I, [_I, _I]),
     "iq_profile_read_work": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -130,7 +136,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 102   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 103   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -1,4 +1,6 @@
-// Geometry kernels: nearest-centre region assignment (K6) and farthest point sampling (K7).
+// Geometry kernels: nearest-centre region assignment (K6), farthest point sampling (K7) and the standalone
+// distance-valued ops of the model files: PointConv's knn_point and compute_density, and the nearest-first ordering
+// of a neighbour list.
 //
 // Both are index-valued, so the floating-point expressions are written with explicitly rounded
 // operations (__fmul_rn/__fadd_rn: no FMA contraction) in the order the reference's PyTorch
@@ -12,6 +14,22 @@
 
 namespace {
 
+// |p|^2 as torch.sum(p ** 2, -1) evaluates it for three coordinates
+__device__ __forceinline__ float norm3(float x, float y, float z) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
+}
+
+// square_distance(src, dst) (tools/final_util.py:134-147, models/pointnet2.py:12-25, models/pointconv.py:13-32) for one pair:
+// the matmul row (K = 3) as an fma chain, then * -2, + |src|^2, + |dst|^2
+__device__ __forceinline__ float sqdist3(float sx, float sy, float sz, float sn, float dx, float dy, float dz, float dn) {
+    float dot = __fmul_rn(sx, dx);
+    dot = __fmaf_rn(sy, dy, dot);
+    dot = __fmaf_rn(sz, dz, dot);
+    float d = __fmul_rn(-2.f, dot);
+    d = __fadd_rn(d, sn);
+    return __fadd_rn(d, dn);
+}
+
 // ---- K6: tools/final_util.py:134-147 + final_shapley_value.py:29-31 -------------------------
 __global__ __launch_bounds__(256) void region_assign_kernel(const float* __restrict__ cloud,
                                                             const int32_t* __restrict__ fps_idx,
@@ -23,23 +41,17 @@ __global__ __launch_bounds__(256) void region_assign_kernel(const float* __restr
         cs[threadIdx.x * 4 + 0] = x;
         cs[threadIdx.x * 4 + 1] = y;
         cs[threadIdx.x * 4 + 2] = z;
-        cs[threadIdx.x * 4 + 3] = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
+        cs[threadIdx.x * 4 + 3] = norm3(x, y, z);
     }
     __syncthreads();
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= N) return;
     const float x = cloud[p * 3], y = cloud[p * 3 + 1], z = cloud[p * 3 + 2];
-    const float sx = __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
+    const float sx = norm3(x, y, z);
     float best = INFINITY;
     int arg = 0;
     for (int r = 0; r < R; ++r) {
-        // matmul row (K = 3) as an fma chain, then * -2, + |src|^2, + |dst|^2
-        float dot = __fmul_rn(x, cs[r * 4]);
-        dot = __fmaf_rn(y, cs[r * 4 + 1], dot);
-        dot = __fmaf_rn(z, cs[r * 4 + 2], dot);
-        float d = __fmul_rn(-2.f, dot);
-        d = __fadd_rn(d, sx);
-        d = __fadd_rn(d, cs[r * 4 + 3]);
+        const float d = sqdist3(x, y, z, sx, cs[r * 4], cs[r * 4 + 1], cs[r * 4 + 2], cs[r * 4 + 3]);
         if (d < best) { best = d; arg = r; }
     }
     region_id[p] = arg;
@@ -183,6 +195,123 @@ __global__ __launch_bounds__(64) void fps_wave_kernel(const float* __restrict__ 
     if (lane == 0 && n_unique) n_unique[blockIdx.x] = S;
 }
 
+// ---- ordered distance keys -----------------------------------------------------------------------------------------
+// A float32 distance as an order-preserving unsigned word (negative values - the expanded form can give slightly negative
+// distances - below positive ones) above a 32-bit tie-breaker: comparing keys as integers orders by distance, then tie-breaker.
+__device__ __forceinline__ unsigned long long dist_key(float d, unsigned tie) {
+    const unsigned u = __float_as_uint(d);
+    return ((unsigned long long)(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u)) << 32) | tie;
+}
+
+// ---- models/pointconv.py:103-114 (knn_point), nearest first -------------------------------------------------------
+// One wave per query: the keys of all N points (distance, index) go to LDS, padded to a power of two P with keys above every
+// real one, and a bitonic sort puts them in ascending order - nearest first, ties to the lower index; the first K are the answer.
+__global__ __launch_bounds__(64) void knn_point_kernel(const float* __restrict__ xyz, const float* __restrict__ new_xyz,
+                                                       int32_t* __restrict__ idx, int N, int S, int K, int P) {
+    extern __shared__ unsigned long long keys[];   // P
+    const int q = blockIdx.x;                      // b * S + s
+    const int b = q / S, lane = threadIdx.x;
+    const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
+    const float qn = norm3(qx, qy, qz);
+    const float* kb = xyz + (size_t)b * N * 3;
+    for (int j = lane; j < P; j += 64) {
+        unsigned long long key = ~0ull;
+        if (j < N) {
+            const float x = kb[j * 3], y = kb[j * 3 + 1], z = kb[j * 3 + 2];
+            key = dist_key(sqdist3(qx, qy, qz, qn, x, y, z, norm3(x, y, z)), (unsigned)j);   // square_distance(new_xyz, xyz)
+        }
+        keys[j] = key;
+    }
+    __syncthreads();
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = lane; t < P / 2; t += 64) {
+                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const unsigned long long a = keys[lo], c = keys[hi];
+                if ((a > c) == ((lo & size) == 0)) { keys[lo] = c; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int r = lane; r < K; r += 64) idx[(size_t)q * K + r] = (int32_t)(unsigned)keys[r];
+}
+
+// ---- the ordering of models/dgcnn.py:12-18 (topk(sorted=True)) for a given neighbour set ------------------------------------
+// One wave per row (4 rows per workgroup).  Every entry's distance to the query in the reference's association: row i of
+// -xx - inner - xx^T is -((|x_j|^2 + inner_ij) + |x_i|^2) with inner = -2 x_i.x_j, so the distance is (|k|^2 + (-2 q.k)) + |q|^2
+// (dot product as an fma chain, norms as channel-sequential sums of rounded squares).  An entry's rank is the number of entries
+// with a smaller (distance, index, position) key.  A row holding an index outside [0, N) is left as it is.
+constexpr int kSortMaxK = 128;
+
+__global__ __launch_bounds__(256) void sort_neighbours_kernel(const float* __restrict__ qs, const float* __restrict__ keys,
+                                                              int32_t* __restrict__ idx, int rows, int N, int S, int C, int k) {
+    __shared__ unsigned long long list[4][kSortMaxK];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;   // b * S + s
+    const bool live = row < rows;
+    bool bad = false;
+    if (live) {
+        const int b = row / S;
+        const float* qp = qs + (size_t)row * C;
+        float qn = __fmul_rn(qp[0], qp[0]);
+        for (int c = 1; c < C; ++c) qn = __fadd_rn(qn, __fmul_rn(qp[c], qp[c]));
+        for (int e = lane; e < k; e += 64) {
+            const int i = idx[(size_t)row * k + e];
+            if ((unsigned)i >= (unsigned)N) { bad = true; continue; }
+            const float* kp = keys + ((size_t)b * N + i) * C;
+            float dot = __fmul_rn(qp[0], kp[0]), kn = __fmul_rn(kp[0], kp[0]);
+            for (int c = 1; c < C; ++c) {
+                dot = __fmaf_rn(qp[c], kp[c], dot);
+                kn = __fadd_rn(kn, __fmul_rn(kp[c], kp[c]));
+            }
+            const float d = __fadd_rn(__fadd_rn(kn, __fmul_rn(-2.f, dot)), qn);
+            list[wave][e] = dist_key(d, ((unsigned)i << 7) | (unsigned)e);
+        }
+    }
+    const bool skip = __any(bad);
+    __syncthreads();
+    if (!live || skip) return;
+    for (int e = lane; e < k; e += 64) {
+        const unsigned long long key = list[wave][e];
+        int rank = 0;
+        for (int f = 0; f < k; ++f) rank += list[wave][f] < key ? 1 : 0;
+        idx[(size_t)row * k + rank] = (int32_t)((unsigned)key >> 7);
+    }
+}
+
+// ---- models/pointconv.py:199-209 (compute_density) -------------------------------------------------------------------------
+// density[i] = mean_j exp(-d_ij / c0) / c1 with d = square_distance(xyz, xyz), c0 = 2 h^2 and c1 = 2.5 h rounded to float32 as
+// torch rounds the Python scalars; exp and both divisions per pair as in the reference, the mean accumulated in float64.
+// One thread per point, the cloud staged through LDS in tiles.
+constexpr int kDensityTile = 1024;
+
+__global__ __launch_bounds__(256) void density_kernel(const float* __restrict__ xyz, float c0, float c1, float* __restrict__ out,
+                                                      int N) {
+    __shared__ float4 pts[kDensityTile];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const float* src = xyz + (size_t)b * N * 3;
+    const int iq = min(i, N - 1);
+    const float qx = src[iq * 3], qy = src[iq * 3 + 1], qz = src[iq * 3 + 2];
+    const float qn = norm3(qx, qy, qz);
+    double sum = 0.0;
+    for (int j0 = 0; j0 < N; j0 += kDensityTile) {
+        const int nt = min(kDensityTile, N - j0);
+        __syncthreads();
+        for (int p = threadIdx.x; p < nt; p += 256) {
+            const float x = src[(j0 + p) * 3], y = src[(j0 + p) * 3 + 1], z = src[(j0 + p) * 3 + 2];
+            pts[p] = make_float4(x, y, z, norm3(x, y, z));
+        }
+        __syncthreads();
+        for (int p = 0; p < nt; ++p) {
+            const float4 k = pts[p];
+            const float d = sqdist3(qx, qy, qz, qn, k.x, k.y, k.z, k.w);
+            sum += (double)__fdiv_rn(expf(__fdiv_rn(-d, c0)), c1);
+        }
+    }
+    if (i < N) out[(size_t)b * N + i] = (float)(sum / (double)N);
+}
+
 }  // namespace
 
 extern "C" int iq_region_assign(const float* cloud, const int32_t* fps_idx, int32_t* region_id,
@@ -216,4 +345,43 @@ int iq::launch_fps(const float* xyz, int32_t* idx, int32_t* n_unique, int B, int
 
 extern "C" int iq_fps(const float* xyz, int32_t* idx, int B, int N, int S, iq_stream_t stream) {
     return iq::launch_fps(xyz, idx, nullptr, B, N, S, iq::as_stream(stream));
+}
+
+extern "C" int iq_knn_point(const float* xyz, const float* new_xyz, int K, int32_t* idx, void* tmp, size_t tmp_bytes, int B, int N,
+                            int S, iq_stream_t stream) {
+    (void)tmp;
+    (void)tmp_bytes;
+    IQ_REQUIRE(B >= 0 && S >= 0 && N >= 1 && N <= IQ_MAX_POINTS, "iq_knn_point: N=%d outside 1..%d", N, IQ_MAX_POINTS);
+    IQ_REQUIRE(K >= 1 && K <= N && K <= 128, "iq_knn_point: K=%d outside 1..min(N=%d, 128)", K, N);
+    if ((size_t)B * S == 0) return IQ_OK;
+    IQ_REQUIRE(xyz && new_xyz && idx, "iq_knn_point: null pointer");
+    IQ_REQUIRE((size_t)B * S <= 0x7fffffffu, "iq_knn_point: B*S=%zu queries", (size_t)B * S);
+    int P = 2;
+    while (P < N) P <<= 1;
+    hipLaunchKernelGGL(knn_point_kernel, dim3((unsigned)(B * S)), dim3(64), (size_t)P * 8, iq::as_stream(stream), xyz, new_xyz, idx,
+                       N, S, K, P);
+    return iq::check_launch("knn_point_kernel");
+}
+
+extern "C" int iq_sort_neighbours(const float* q, const float* keys, int32_t* idx, int B, int N, int S, int C, int k,
+                                  iq_stream_t stream) {
+    IQ_REQUIRE(B >= 0 && S >= 0 && N >= 1 && N <= (1 << 24) && C >= 1, "iq_sort_neighbours: B=%d N=%d S=%d C=%d", B, N, S, C);
+    IQ_REQUIRE(k >= 1 && k <= kSortMaxK, "iq_sort_neighbours: k=%d outside 1..%d", k, kSortMaxK);
+    const size_t rows = (size_t)B * S;
+    if (rows == 0) return IQ_OK;
+    IQ_REQUIRE(q && keys && idx, "iq_sort_neighbours: null pointer");
+    IQ_REQUIRE(rows <= 0x7ffffff0u, "iq_sort_neighbours: B*S=%zu rows", rows);
+    hipLaunchKernelGGL(sort_neighbours_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, iq::as_stream(stream), q, keys, idx,
+                       (int)rows, N, S, C, k);
+    return iq::check_launch("sort_neighbours_kernel");
+}
+
+extern "C" int iq_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream) {
+    IQ_REQUIRE(B >= 0 && B <= 65535 && N >= 1, "iq_density: B=%d N=%d", B, N);
+    IQ_REQUIRE(bandwidth > 0.0, "iq_density: bandwidth %g must be positive", bandwidth);
+    if (B == 0) return IQ_OK;
+    IQ_REQUIRE(xyz && out, "iq_density: null pointer");
+    const float c0 = (float)(2.0 * bandwidth * bandwidth), c1 = (float)(2.5 * bandwidth);
+    hipLaunchKernelGGL(density_kernel, dim3((N + 255) / 256, B), dim3(256), 0, iq::as_stream(stream), xyz, c0, c1, out, N);
+    return iq::check_launch("density_kernel");
 }

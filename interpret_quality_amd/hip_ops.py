@@ -250,6 +250,115 @@ def knn(x, k=20):
     return out
 
 
+def _shape(t, what, *dims):
+    """The shape of tensor ``t``; IqError unless it has len(dims) dimensions and matches every dims entry that is not None."""
+    if not isinstance(t, torch.Tensor) or t.dim() != len(dims) or any(d is not None and t.shape[i] != d for i, d in enumerate(dims)):
+        want = "(%s)" % ",".join("*" if d is None else str(d) for d in dims)
+        raise _lib.IqError("%s must be %s, got %s" % (what, want, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    return tuple(t.shape)
+
+
+_INDEX_DTYPES = (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _valid_idx(idx, n, what):
+    """Caller indices -> int32 device tensor, validated to lie in [0, n) (IqError otherwise) before any kernel reads them.
+    A wider index is clamped to [-1, n] before the cast, so a value outside the int32 range cannot wrap into [0, n)."""
+    if not isinstance(idx, torch.Tensor) or not idx.is_cuda:
+        raise _lib.IqError("%s must be a CUDA/HIP tensor (the HIP path has no CPU fallback)" % what)
+    if idx.dtype not in _INDEX_DTYPES:
+        raise _lib.IqError("%s must be an integer tensor, got %s" % (what, idx.dtype))
+    t = (idx.clamp(-1, n) if idx.dtype == torch.int64 else idx).to(dtype=torch.int32).contiguous()
+    check_index_range(t, 0, n, what)
+    return t
+
+
+def index_points(points, idx):
+    """points (B,N,C) f32, idx (B,...) integer -> (B,...,C) f32: points[b, idx[b,...], :] (models/pointnet2.py:27-43)."""
+    lib = _lib.load()
+    b, n, c = _shape(points, "points", None, None, None)
+    if not isinstance(idx, torch.Tensor) or idx.dim() < 1 or idx.shape[0] != b:
+        raise _lib.IqError("idx must be (%d,...), got %s" % (b, tuple(idx.shape) if isinstance(idx, torch.Tensor) else type(idx).__name__))
+    t = _valid_idx(idx, n, "idx")
+    out = torch.empty(tuple(t.shape) + (c,), dtype=torch.float32, device=points.device)
+    m = t[0].numel() if b else 0
+    _lib.check(lib.iq_index_points(_dev(points, torch.float32, "points"), _p(t), _p(out), b, n, m, c, _stream()), "iq_index_points")
+    return out
+
+
+def group_points(xyz, points=None, new_xyz=None, idx=None, xyz_first=True):
+    """xyz (B,N,3), points (B,N,D) or None, new_xyz (B,S,3) or None, idx (B,S,K) integer or None -> (B,S,K,3+D) f32 rows
+    [xyz[idx] - new_xyz, points[idx]] (xyz_first) or [points[idx], xyz[idx] - new_xyz]; new_xyz None: nothing subtracted;
+    idx None: all N points (S = 1, K = N) (models/pointnet2.py:93-137, 222-230; models/pointconv.py:117-197)."""
+    lib = _lib.load()
+    b, n, _ = _shape(xyz, "xyz", None, None, 3)
+    d = _shape(points, "points", b, n, None)[2] if points is not None else 0
+    if idx is not None:
+        _, s, k = _shape(idx, "idx", b, None, None)
+    else:
+        s, k = 1, n
+    if new_xyz is not None:
+        _shape(new_xyz, "new_xyz", b, s, 3)
+    t = _valid_idx(idx, n, "idx") if idx is not None else None
+    out = torch.empty((b, s, k, 3 + d), dtype=torch.float32, device=xyz.device)
+    _lib.check(lib.iq_group_points(_dev(xyz, torch.float32, "xyz"),
+                                   _dev(points, torch.float32, "points") if points is not None else ctypes.c_void_p(0),
+                                   _dev(new_xyz, torch.float32, "new_xyz") if new_xyz is not None else ctypes.c_void_p(0),
+                                   _p(t), _p(out), int(bool(xyz_first)), b, n, s, k, d, _stream()), "iq_group_points")
+    return out
+
+
+def edgeconv_gather(x, idx, channel_first=True):
+    """x (B,C,N) (channel_first) or (B,N,C) f32, idx (B,N,k) integer -> (B,2C,N,k) f32 [x_j - x_i ; x_i]
+    (models/dgcnn.py:21-47 with idx given)."""
+    lib = _lib.load()
+    if channel_first:
+        b, c, n = _shape(x, "x", None, None, None)
+    else:
+        b, n, c = _shape(x, "x", None, None, None)
+    k = _shape(idx, "idx", b, n, None)[2]
+    t = _valid_idx(idx, n, "idx")
+    out = torch.empty((b, 2 * c, n, k), dtype=torch.float32, device=x.device)
+    _lib.check(lib.iq_edgeconv_gather(_dev(x, torch.float32, "x"), _p(t), _p(out), int(bool(channel_first)), b, n, c, k, _stream()),
+               "iq_edgeconv_gather")
+    return out
+
+
+def knn_point(xyz, new_xyz, k):
+    """xyz (B,N,3), new_xyz (B,S,3) f32 -> (B,S,k) i32: the k nearest points by square_distance, nearest first, ties to the
+    lower index (models/pointconv.py:103-114); N <= 4096, k <= min(N, 128)."""
+    lib = _lib.load()
+    b, n, _ = _shape(xyz, "xyz", None, None, 3)
+    s = _shape(new_xyz, "new_xyz", b, None, 3)[1]
+    out = torch.empty((b, s, k), dtype=torch.int32, device=xyz.device)
+    _lib.check(lib.iq_knn_point(_dev(xyz, torch.float32, "xyz"), _dev(new_xyz, torch.float32, "new_xyz"), int(k), _p(out),
+                                ctypes.c_void_p(0), 0, b, n, s, _stream()), "iq_knn_point")
+    return out
+
+
+def sort_neighbours(q, keys, idx):
+    """q (B,S,C), keys (B,N,C) f32, idx (B,S,k) i32 -> idx reordered in place nearest first by the distance of
+    models/dgcnn.py:13-15 in float32 (ties to the lower index): the order of knn's topk(sorted=True).  Returns idx."""
+    lib = _lib.load()
+    b, n, c = _shape(keys, "keys", None, None, None)
+    s = _shape(q, "q", b, None, c)[1]
+    k = _shape(idx, "idx", b, s, None)[2]
+    _dev(idx, torch.int32, "idx")
+    check_index_range(idx, 0, n, "idx")
+    _lib.check(lib.iq_sort_neighbours(_dev(q, torch.float32, "q"), _dev(keys, torch.float32, "keys"), _p(idx), b, n, s, c, k,
+                                      _stream()), "iq_sort_neighbours")
+    return idx
+
+
+def density(xyz, bandwidth):
+    """xyz (B,N,3) f32 -> (B,N) f32 Gaussian kernel density (models/pointconv.py:199-209, compute_density)."""
+    lib = _lib.load()
+    b, n, _ = _shape(xyz, "xyz", None, None, 3)
+    out = torch.empty((b, n), dtype=torch.float32, device=xyz.device)
+    _lib.check(lib.iq_density(_dev(xyz, torch.float32, "xyz"), float(bandwidth), _p(out), b, n, _stream()), "iq_density")
+    return out
+
+
 SMOOTHNESS_MODES = ("linearity", "planarity", "scattering")
 
 
