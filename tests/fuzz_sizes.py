@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised size probe (GPU): for every model family, random cloud sizes (a cluster just above each family's minimum and the whole
-range), region counts 1-64, 1-9 source clouds and 1-89 random coalitions (plus the full and the empty one) - the coalition path
+range), region counts 1-64, 1-9 source clouds and 2-89 random coalitions (plus the full and the empty one) - the coalition path
 against the dense forward on the masked clouds (both HIP) and, for small or sampled cases, against the CPU oracle.
 
     python tests/fuzz_sizes.py [seed] [seconds]
@@ -8,70 +8,37 @@ against the dense forward on the masked clouds (both HIP) and, for small or samp
 Prints every case that raises or disagrees (> 1e-4 of the logit range; DGCNN against the float32 oracle: 1e-2, its feature-space kNN
 cannot be held tighter than the reference holds itself) and a final count.  Round 5: 600 cases found two bugs that
 only small clouds reach (PointConv below 512 points, DGCNN coalitions on 21- to 38-point clouds); 575 cases clean afterwards.
-Test infrastructure (lives under tests/ because it imports oracle/); not collected by pytest."""
-import sys, os, argparse, time
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np, torch
-from interpret_quality_amd import synth, hip_ops
-from interpret_quality_amd.pointnet import PointNetCls
-from interpret_quality_amd.pointnet2 import PointNet2ClsMsg
-from interpret_quality_amd.pointconv import PointConvDensityClsSsg
-from interpret_quality_amd.dgcnn import DGCNN_cls, GCNN_cls
-from oracle import ref_cpu as O
+The case generator and the checks live in tests/probes.py; a seeded slice of them, with the boundary sizes spelled out, runs in
+the suite as tests/test_fuzz_gpu.py.  Test infrastructure (imports oracle/); not collected by pytest."""
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import numpy as np
+import torch
+
+import probes
+
 d = torch.device("cuda:0")
-def first(o): return (o[0] if isinstance(o, tuple) else o)
-ns = argparse.Namespace(dataset="modelnet10", k=20)
-models = {}
-def get(name):
-    if name not in models:
-        cls, sdf = {"pointnet": (PointNetCls, synth.pointnet_state_dict), "pointnet2": (PointNet2ClsMsg, synth.pointnet2_state_dict),
-                    "pointconv": (PointConvDensityClsSsg, synth.pointconv_state_dict), "dgcnn": (DGCNN_cls, synth.dgcnn_state_dict),
-                    "gcnn": (GCNN_cls, synth.dgcnn_state_dict)}[name]
-        sd = synth.to_torch(sdf(0))
-        m = cls(ns if "cnn" in name else None); m.load_state_dict(sd); m = m.to(d).eval()
-        models[name] = (m, sd)
-    return models[name]
-def oracle_logits(name, sd, x_bn3):
-    x = x_bn3.permute(0, 2, 1).contiguous()
-    with torch.no_grad():
-        if name == "pointnet": return first(O.PointNetOracle(sd)(x)).numpy() if hasattr(O, "PointNetOracle") else None
-        if name == "pointnet2": return first(O.PointNet2Oracle(sd)(x)).numpy()
-        if name == "pointconv": return first(O.PointConvOracle(sd)(x)).numpy()
-        return O.dgcnn_forward(sd, x, 20, name == "gcnn").numpy()
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
+budget = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
 t0 = time.time(); ncase = nbad = 0
-lims = {"pointnet": (8, 4096), "pointnet2": (128, 2100), "pointconv": (64, 2100), "dgcnn": (21, 2100), "gcnn": (21, 2100)}
-while time.time() - t0 < float(sys.argv[2]) if len(sys.argv) > 2 else 60:
-    name = list(lims)[ncase % 5]
-    lo, hi = lims[name]
-    n = int(rng.choice([rng.integers(lo, min(hi, lo + 40)), rng.integers(lo, hi)]))
-    R = int(rng.choice([1, 2, 8, 32, 64]))
-    nc = int(rng.choice([1, 2, 3, 9]))                    # (more than 8 source clouds: no pair tables)
-    b = int(rng.choice([rng.integers(1, 12), rng.integers(12, 90)]))   # (8 coalitions per source cloud and more: groups from the source lists)
-    m, sd = get(name)
+while time.time() - t0 < budget:
+    case = probes.random_coalition_case(rng, probes.FAMILIES[ncase % len(probes.FAMILIES)])
+    desc = "%s N=%d R=%d nc=%d b=%d" % (case.family, case.n, case.r, case.nc, case.b)
     try:
-        pts = torch.from_numpy(np.stack([synth.make_cloud(int(rng.integers(0, 1000)), num_points=n)[0] for _ in range(nc)]))
-        clouds = pts.to(d); centers = clouds.mean(dim=1)
-        rid = torch.from_numpy(rng.integers(0, R, size=(nc, n)).astype(np.int32)).to(d)
-        keep = [int(x) & ((1 << R) - 1) for x in rng.integers(0, 1 << 63, size=b)]
-        if rng.random() < 0.5: keep[0] = (1 << R) - 1
-        if rng.random() < 0.5: keep[-1] = 0
-        co = [int(x) for x in rng.integers(0, nc, size=b)]
-        got = m.coalition_logits(clouds, centers, rid, hip_ops.masks_to_tensor(keep, d), torch.tensor(co, dtype=torch.int32, device=d), num_regions=R).cpu().numpy()
-        masked = torch.cat([hip_ops.mask_coalitions(clouds[c].contiguous(), rid[c].contiguous(), hip_ops.masks_to_tensor([k], d), centers[c].contiguous()) for k, c in zip(keep, co)])
-        dense = m.forward_points(masked).cpu().numpy() if name != "pointnet" else None
-        want = oracle_logits(name, sd, masked.cpu()) if (name == "pointnet" or n <= 300 or ncase % 4 == 0) else None
-        ref = want if want is not None else dense
-        sc = np.abs(ref).max()
-        e1 = np.abs(got - ref).max() / sc
-        e2 = np.abs(got - dense).max() / sc if dense is not None else 0.0
+        # the oracle on every PointNet case, small clouds and every fourth case otherwise
+        cap = None if (case.family == "pointnet" or case.n <= 300 or ncase % 4 == 0) else 0
+        got, dense, want, masked = probes.run_coalition_case(case, d, oracle_cap=cap)
         ncase += 1
-        tol = 1e-4 if name != 'dgcnn' or want is None else 1e-2
-        if not (e1 < tol and e2 < tol) or not np.isfinite(got).all():
+        if probes.coalition_problems(case.family, got, dense, want):
             nbad += 1
-            print("MISMATCH %s N=%d R=%d nc=%d b=%d: vs %s %.2g, vs dense %.2g; kept %s" % (name, n, R, nc, b, "oracle" if want is not None else "dense", e1, e2,
-                  [int(sum(((k >> int(r)) & 1) for r in rid[c].cpu().numpy())) for k, c in zip(keep, co)]), flush=True)
-    except Exception as e:
+            _, rid, keep, co = probes.coalition_inputs(case)
+            print("MISMATCH %s: vs %s %.2g, vs dense %.2g; kept %s" % (
+                desc, "oracle" if want is not None else "dense", probes.rel_max_err(got, want if want is not None else dense),
+                probes.rel_max_err(got, dense), [int(sum(((k >> int(r)) & 1) for r in rid[c])) for k, c in zip(keep, co)]), flush=True)
+    except Exception as e:   # noqa: BLE001 - a probe: report and go on
         ncase += 1
-        print("%s N=%d R=%d nc=%d b=%d: %s: %s" % (name, n, R, nc, b, type(e).__name__, str(e)[:160]), flush=True)
+        print("%s: %s: %s" % (desc, type(e).__name__, str(e)[:160]), flush=True)
 print("cases %d, mismatches %d" % (ncase, nbad))

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from probes import assert_rows_nearest_first, set_mismatches
 from interpret_quality_amd import _lib, hip_ops, synth
 
 pytestmark = pytest.mark.gpu
@@ -130,28 +131,6 @@ def pairwise(x_cf):
     inner = torch.matmul(x_cf.transpose(2, 1), x_cf) * -2
     xx = torch.sum(x_cf ** 2, dim=1, keepdim=True)
     return (-xx - inner - xx.transpose(2, 1)).numpy()
-
-
-def set_mismatches(got, want, score, tol):
-    """Rows whose index sets differ may differ only by candidates whose scores are within `tol` of each other."""
-    bad = 0
-    for b in range(got.shape[0]):
-        for i in range(got.shape[1]):
-            sg, sw = set(got[b, i].tolist()), set(want[b, i].tolist())
-            assert len(sg) == got.shape[2], "duplicate neighbour in row (%d,%d)" % (b, i)
-            if sg != sw:
-                dg, dw = np.sort(score[b, i, list(sg - sw)]), np.sort(score[b, i, list(sw - sg)])
-                scale = max(1.0, float(np.abs(score[b, i]).max()))
-                assert np.allclose(dg, dw, rtol=0, atol=tol * scale), (b, i, dg, dw)
-                bad += 1
-    return bad
-
-
-def assert_rows_nearest_first(idx, dist, tol):
-    """dist (B,S,N) distances (smaller = nearer): every row of idx non-decreasing up to `tol` of the row's scale."""
-    d = np.take_along_axis(dist, idx.astype(np.int64), axis=2)
-    scale = np.maximum(1.0, np.abs(dist).max(axis=2, keepdims=True))
-    assert (np.diff(d, axis=2) >= -tol * scale).all()
 
 
 def test_dgcnn_knn_is_ordered_like_the_reference(oracle):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import assert_close_elementwise, load_golden
+from probes import ball_mismatch
 from interpret_quality_amd import final_common, hip_ops, synth
 from interpret_quality_amd.pointnet2 import PointNet2ClsMsg
 
@@ -56,19 +57,6 @@ def test_fps_two_levels_incl_exhaustion(masked):
     assert (g["fps1"][0] == 0).all()  # the all-centre cloud: one distinct location
 
 
-def _ball_mismatch(got, want, xyz, new_xyz, radius, oracle):
-    """Index-valued: rows may differ only where a point sits within rounding of the sphere."""
-    bad = np.nonzero((got != want).any(axis=-1))
-    if len(bad[0]) == 0:
-        return 0
-    d = oracle.square_distance(new_xyz, xyz).numpy()
-    r2 = np.float32(radius ** 2)
-    for b, s in zip(*bad):
-        near = np.abs(d[b, s] - r2) < 4e-7
-        assert near.any(), "ball query row (%d,%d) differs without a boundary point" % (b, s)
-    return len(bad[0])
-
-
 def test_ball_query_matches_reference(masked, oracle):
     g = load_golden("pointnet2.npz")
     sel = list(g["sel"])
@@ -77,11 +65,11 @@ def test_ball_query_matches_reference(masked, oracle):
     nbad = 0
     for r, k in ((0.1, 16), (0.2, 32), (0.4, 128)):
         got = hip_ops.ball_query(xyz.to(dev()), new_xyz.to(dev()), r, k).cpu().numpy()
-        nbad += _ball_mismatch(got, g["sa1_ball_r%g" % r].astype(np.int32), xyz, new_xyz, r, oracle)
+        nbad += ball_mismatch(got, g["sa1_ball_r%g" % r].astype(np.int32), xyz, new_xyz, r, oracle)
     new_xyz2 = oracle.index_points(new_xyz, torch.from_numpy(g["fps2"][sel].astype(np.int64)))
     for r, k in ((0.2, 32), (0.4, 64), (0.8, 128)):
         got = hip_ops.ball_query(new_xyz.contiguous().to(dev()), new_xyz2.contiguous().to(dev()), r, k).cpu().numpy()
-        nbad += _ball_mismatch(got, g["sa2_ball_r%g" % r].astype(np.int32), new_xyz, new_xyz2, r, oracle)
+        nbad += ball_mismatch(got, g["sa2_ball_r%g" % r].astype(np.int32), new_xyz, new_xyz2, r, oracle)
     assert nbad <= 8  # of 3*(512+128)*3 rows
 
 
