@@ -11,6 +11,7 @@
 // features never leave the CU.
 #include "iq_common.h"
 #include "iq_bf3.h"
+#include "iq_group_mlp.h"
 #include "iq_mfma.h"
 #include "iq_profile.h"
 #include "iq_srclist.h"
@@ -408,45 +409,10 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_kernel(PcGroupArgs a) {
 }
 
 // ---- the 128-128-256 stage (sa2) on the bf16 matrix pipe: bf16x3, float32-exact (iq_bf3.h) ----------------------
-// pc_group_kernel with layers 2 and 3 as six bf16 products per float32 product.  As in pn2_group_bf3_kernel (iq_pointnet2.hip):
-// activations as three bf16 planes of 272-byte rows, act1 and act2 in ONE 52 KB image (layer 2's tiles wait in registers for
-// the barrier), layer 3 as 2 x 2 tiles per wave, weights through small register rings.  The contraction over the members stays
-// on v_mfma_f32_16x16x4_f32 (float32 operands straight out of the accumulators).
-template <int MTS>   // transposed tiles (weights as the A operand), as gb_layer2 in iq_pointnet2.hip
-__device__ __forceinline__ void pcb_layer2(const unsigned char* abase, const __amdgpu_buffer_rsrc_t& rs, int voff, int nt,
-                                           B3 (&ring)[4], f32x16 (&acc)[MTS][1]) {
-    constexpr int ROWB = 272, PLANEB = 64 * ROWB, TS = 4 * 8 * 1024;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        bf16x8 af[MTS][3];
-#pragma unroll
-        for (int i = 0; i < MTS; ++i) a3_load<PLANEB>(af[i], abase + i * 32 * ROWB, ks);
-        const B3 b = ring[ks & 3];
-        if (ks + 4 < 8) ring[ks & 3] = b3_load_at(rs, voff, (nt * 8 + ks + 4) * 1024, TS);
-        mfma_bf3_block_tr<MTS>(af, b, acc);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-struct PcB3x2 { B3 b[2]; };
-__device__ __forceinline__ void pcb_layer3(const unsigned char* abase, const __amdgpu_buffer_rsrc_t& rs, int voff, int nt0,
-                                           PcB3x2 (&ring)[2], f32x16 (&acc)[2][2]) {
-    constexpr int ROWB = 272, PLANEB = 64 * ROWB, TS = 8 * 8 * 1024;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-        bf16x8 af[2][3];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) a3_load<PLANEB>(af[i], abase + i * 32 * ROWB, ks);
-        const B3 b[2] = {ring[ks & 1].b[0], ring[ks & 1].b[1]};
-        if (ks + 2 < 8) {
-            ring[ks & 1].b[0] = b3_load_at(rs, voff, (nt0 * 8 + ks + 2) * 1024, TS);
-            ring[ks & 1].b[1] = b3_load_at(rs, voff, ((nt0 + 4) * 8 + ks + 2) * 1024, TS);
-        }
-        mfma_bf3_block<2, 2>(af, b, acc);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// Layer 2's tiles transposed: act2 stored with whole 8-byte stores, no two-lane DPP trade.
+// pc_group_kernel with layers 2 and 3 as six bf16 products per float32 product, with the layer helpers, LDS layout and schedule it
+// shares with pn2_group_bf3_kernel (iq_group_mlp.h): activations as three bf16 planes, act1 and act2 in ONE 52 KB image, layer 3 as
+// 2 x 2 tiles per wave.  The contraction over the members stays on v_mfma_f32_16x16x4_f32 (float32 operands straight out of the
+// accumulators).
 __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a) {
     constexpr int C1 = 128, C3 = 256, ROWB = 272, PLANEB = kMC * ROWB, LDS_SW = kMC + 2;
     constexpr int Q1 = C1 / 4, NR = kMC * Q1 / kThreads;
@@ -522,8 +488,8 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a
         __syncthreads();  // act1 complete
         // ---- layer 2: tiles (m-tile 0..1, n-tile = wave) kept in registers ---------------------------------------------------
         f32x16 acc2[2][1] = {{{0}}, {{0}}};
-        pcb_layer2<2>(abase, w2rs, voff, wave_s, ring2, acc2);
-        PcB3x2 ring3[2];                             // layer 3's weights (n-tiles wave, wave + 4), in flight across the epilogue
+        gb_layer2<2>(abase, w2rs, voff, wave_s, ring2, acc2);
+        B3x2 ring3[2];                               // layer 3's weights (n-tiles wave, wave + 4), in flight across the epilogue
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             ring3[i].b[0] = b3_load_at(w3rs, voff, (wave_s * 8 + i) * 1024, 8 * 8 * 1024);
@@ -542,7 +508,7 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a
         if (ch + 1 < nchunks) gather_u(nxt);                                // consumed after layer 3
         // ---- layer 3 (2 x 2 tiles per wave) + contraction over the members (fp32 MFMA, as pc_group_kernel) -------------------
         f32x16 acc3[2][2] = {{{0}, {0}}, {{0}, {0}}};
-        pcb_layer3(abase, w3rs, voff, wave_s, ring3, acc3);
+        gb_layer3<2>(abase, w3rs, voff, wave_s, ring3, acc3);
         const float* swc = swlane + cur * 16 * LDS_SW;
         const int g_first = (ch0 + ch) * (kMC / K);
 #pragma unroll
