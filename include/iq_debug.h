@@ -53,6 +53,12 @@ int iq_profile_read(int slot, double* total_ms, int* launches);
  * on MI355X are power-bound: bench.py divides by THIS figure for `frac_of_sustained_bf16_ceiling` instead of a constant. */
 int iq_debug_mfma_sustained(double seconds, float* scratch /*device*/, size_t scratch_floats, double* tflops /*host*/,
                             double* clock_ghz /*host or NULL*/, iq_stream_t stream);
+/* The same diagnostic per instruction shape: shape = 32 is the loop above (v_mfma_f32_32x32x16_bf16, four accumulator tiles of 16
+ * registers per wave), shape = 16 the same loop on v_mfma_f32_16x16x32_bf16 (sixteen tiles of 4 registers: the same 64 accumulator
+ * VGPRs, the same operands, the same FLOP per iteration and the same FLOP accounting).  The kernel is power-bound and the two shapes
+ * draw different power per FLOP: tools/chain_shape_probe.py alternates them.  Any other shape: IQ_EINVAL. */
+int iq_debug_mfma_sustained_shape(int shape, double seconds, float* scratch /*device*/, size_t scratch_floats, double* tflops /*host*/,
+                                  double* clock_ghz /*host or NULL*/, iq_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-// bf16x3 building blocks (gfx950, v_mfma_f32_32x32x16_bf16): float32 GEMMs on the bf16 matrix pipe, float32-exact.
+// bf16x3 building blocks (gfx950, v_mfma_f32_32x32x16_bf16; the 16x16x32 forms at the end are the PointNet chain kernel's layer 3):
+// float32 GEMMs on the bf16 matrix pipe, float32-exact.
 // A float32 is three bf16 terms, x = h + m + l (round to nearest, residuals exact); a product is the six largest of the nine
 // term products, each exact, accumulated in float32 (small terms first).  See DESIGN.md 5a and iq_pack_weight_bf3 (iq_linear.hip)
 // for the weight image: fragment (term, n-tile, k-step of 16) = 1 KiB at ((term * NT + n-tile) * KS + k-step) KiB, lane l at l * 16.
@@ -138,4 +139,103 @@ __device__ __forceinline__ void mfma_bf3_block(const bf16x8 (&a)[MT][3], const B
     mfma_term_block<1, 0, MT, NT>(a, b, acc);
     mfma_term_block<0, 1, MT, NT>(a, b, acc);
     mfma_term_block<0, 0, MT, NT>(a, b, acc);
+}
+
+// ---- v_mfma_f32_16x16x32_bf16 forms (PointNet chain kernel, layer 3) ---------------------------------------------------
+// Operands (lane l: c = l & 15, kq = l >> 4): A = row c, channels 8 kq .. 8 kq + 7 of the 32-channel k-step; B = column c, the same
+// channels; C = rows 4 kq + i (register i < 4) of column c.
+//
+// B comes out of the SAME iq_pack_weight_bf3 image as the 32x32x16 fragments: the 16 columns 16 hf .. 16 hf + 15 (hf = 0, 1) of a 32-column
+// n-tile and the 32 channels of k-step t are, inside the adjacent 1 KiB blocks of the 16-channel k-steps 2 t and 2 t + 1, the bytes
+// 1024 (kq >> 1) + 512 (kq & 1) + 256 hf + 16 c (four whole 256-byte runs per wave load).  b16_lane_off is the per-lane part.
+__device__ __forceinline__ int b16_lane_off(int lane) {
+    const int c = lane & 15, kq = lane >> 4;
+    return 1024 * (kq >> 1) + 512 * (kq & 1) + 16 * c;
+}
+
+// The activation operand comes from three bf16 planes in LDS with UNPADDED rows (ROWB = 256 bytes: 128 channels, 128: 64 channels)
+// whose 16-byte pieces are stored XOR-swizzled by the row: piece p of row r lies at ROWB r + 16 (p ^ swz(r)), swz(r) = r & 15
+// (256-byte rows) or (r >> 1) & 7 (128-byte rows: two rows share a 256-byte bank line).  The 16x16x32 read (row c, piece 4 t + kq)
+// is then conflict-free: a ds_read_b128 lane group holds rows {0-3, 12-15} of one kq and rows {4-11} of the next, the XOR maps both
+// sets onto disjoint sixteen-byte bank groups (with padded rows that pattern is 2-way conflicted).  The planes' only writers are the
+// epilogues of layers 1 and 2 (ct_tile_to_planes_swz, c16_tile_to_planes_swz).  a16_lane_off: the per-lane byte offset of k-step
+// 0; k-step t is that offset ^ (64 t).
+template <int ROWB>
+__device__ __forceinline__ int swz_of_row(int row) {
+    static_assert(ROWB == 256 || ROWB == 128, "swizzled planes have 256- or 128-byte rows");
+    return ROWB == 256 ? (row & 15) : ((row >> 1) & 7);
+}
+template <int ROWB>
+__device__ __forceinline__ int a16_lane_off(int lane) {
+    const int r = lane & 15, kq = lane >> 4;
+    return r * ROWB + 16 * (kq ^ swz_of_row<ROWB>(r));
+}
+// fragment of m-tile mi (16 rows) and k-step t (32 channels); plane0 = row 0 of the tile range (a multiple of 16 rows)
+template <int ROWB, int PLANEB>
+__device__ __forceinline__ void a16_load(bf16x8 (&a)[3], const unsigned char* plane0, int lane_off, int mi, int t) {
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+        a[e] = *reinterpret_cast<const bf16x8*>(plane0 + (lane_off ^ (64 * t)) + e * PLANEB + mi * 16 * ROWB);
+}
+
+// ct_tile_to_planes into a swizzled image: `row` = the lane's row of the chunk (first row of the m-tile + (lane & 31)), piece0 =
+// first channel of the n-tile / 8; the lane's register quad g holds channels 8 g + 4 (lane >> 5) + 0..3 = one half of piece piece0 + g
+template <int ROWB, int PLANEB, typename F>
+__device__ __forceinline__ void ct_tile_to_planes_swz(unsigned char* plane0, int row, int piece0, int lane, F value) {
+    unsigned char* d = plane0 + row * ROWB + 8 * (lane >> 5);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        u32x2 h, m, l;
+        split4(f32x4{value(4 * g), value(4 * g + 1), value(4 * g + 2), value(4 * g + 3)}, h, m, l);
+        unsigned char* o = d + 16 * ((piece0 + g) ^ swz_of_row<ROWB>(row));
+        *reinterpret_cast<u32x2*>(o) = h;
+        *reinterpret_cast<u32x2*>(o + PLANEB) = m;
+        *reinterpret_cast<u32x2*>(o + 2 * PLANEB) = l;
+    }
+}
+// the TRANSPOSED 16x16x32 C tile (weights as the A operand): lane (point c = lane & 15, kq) holds channels 4 kq + 0..3 of the
+// 16-channel tile = one half of piece piece0 + (kq >> 1); `row` = the lane's row of the chunk, v = the four values after bias / activation
+template <int ROWB, int PLANEB>
+__device__ __forceinline__ void c16_tile_to_planes_swz(unsigned char* plane0, int row, int piece0, int lane, f32x4 v) {
+    const int kq = lane >> 4;
+    unsigned char* o = plane0 + row * ROWB + 16 * ((piece0 + (kq >> 1)) ^ swz_of_row<ROWB>(row)) + 8 * (kq & 1);
+    u32x2 h, m, l;
+    split4(v, h, m, l);
+    *reinterpret_cast<u32x2*>(o) = h;
+    *reinterpret_cast<u32x2*>(o + PLANEB) = m;
+    *reinterpret_cast<u32x2*>(o + 2 * PLANEB) = l;
+}
+
+// MT m-tiles x ONE 16-column n-tile of one 32-channel k-step: the six products of mfma_bf3 in the same order (small terms first),
+// term-major over the m-tiles (a dependent MFMA is MT instructions away)
+template <int TA, int TB, int MT>
+__device__ __forceinline__ void mfma16_term_col(const bf16x8 (&a)[MT][3], const B3& b, f32x4 (&acc)[MT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][TA], TB == 0 ? b.h : (TB == 1 ? b.m : b.l), acc[i], 0, 0, 0);
+}
+template <int MT>
+__device__ __forceinline__ void mfma16_bf3_col(const bf16x8 (&a)[MT][3], const B3& b, f32x4 (&acc)[MT]) {
+    mfma16_term_col<2, 0, MT>(a, b, acc);
+    mfma16_term_col<0, 2, MT>(a, b, acc);
+    mfma16_term_col<1, 1, MT>(a, b, acc);
+    mfma16_term_col<1, 0, MT>(a, b, acc);
+    mfma16_term_col<0, 1, MT>(a, b, acc);
+    mfma16_term_col<0, 0, MT>(a, b, acc);
+}
+// the same with the operands swapped (weights = A operand, transposed C tile: layer 2): MT point tiles x ONE 16-channel tile
+template <int TW, int TX, int MT>
+__device__ __forceinline__ void mfma16_term_col_tr(const B3& w, const bf16x8 (&x)[MT][3], f32x4 (&acc)[MT]) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(TW == 0 ? w.h : (TW == 1 ? w.m : w.l), x[i][TX], acc[i], 0, 0, 0);
+}
+template <int MT>
+__device__ __forceinline__ void mfma16_bf3_col_tr(const B3& w, const bf16x8 (&x)[MT][3], f32x4 (&acc)[MT]) {
+    mfma16_term_col_tr<0, 2, MT>(w, x, acc);   // (activation l) x (weight h)
+    mfma16_term_col_tr<2, 0, MT>(w, x, acc);   // (activation h) x (weight l)
+    mfma16_term_col_tr<1, 1, MT>(w, x, acc);
+    mfma16_term_col_tr<0, 1, MT>(w, x, acc);   // (activation m) x (weight h)
+    mfma16_term_col_tr<1, 0, MT>(w, x, acc);   // (activation h) x (weight m)
+    mfma16_term_col_tr<0, 0, MT>(w, x, acc);
 }

@@ -12,9 +12,12 @@
 //   L1  (MFMA)     64->64   (fstn.conv1 | per-coalition trans_feat product)  -> LDS act1
 //   L2  (MFMA)     64->128  conv2+bn+relu                                    -> LDS act2
 //   L3  (MFMA)     128->1024 conv3+bn(+relu), column max over rows           -> registers
-// v_mfma_f32_32x32x2_f32 throughout (exact fp32 fma chains).  A operands come from LDS
-// (row stride padded by 4 floats: conflict-free ds_read_b128), B operands (weights) stream from L2 in a
-// pre-packed fragment order (1 KiB contiguous per wave-load).  LDS = 52 KB -> 3 workgroups/CU.
+// L3V = 2: v_mfma_f32_32x32x2_f32 throughout (exact fp32 fma chains).  A operands come from LDS (row stride padded by 4 floats:
+// conflict-free ds_read_b128), B operands (weights) stream from L2 in a pre-packed fragment order (1 KiB contiguous per wave-load).
+// LDS = 52 KB -> 3 workgroups/CU.
+// L3V = 3 (the product path of the feature-STN and trunk chains): layers 2-3 as six exact bf16 products per float32 product on
+// v_mfma_f32_16x16x32_bf16 (iq_bf3.h; DESIGN.md 5a: the kernel is power-bound and this shape holds a 10 % higher clock than
+// 32x32x16), activations as three swizzled bf16 planes in LDS.  LDS = 74.8 KB, <= 256 VGPRs -> 2 workgroups/CU.
 #include <algorithm>
 
 #include "iq_common.h"
@@ -139,125 +142,149 @@ __device__ __forceinline__ void l3_pass_v2(const WBuf& w3, const float* abase, i
 
 // ---- Variant 3: L3 on the bf16 matrix pipe, float32-exact -----------------------------------------------------------------------
 // (csrc/iq_linear.hip, pn_gemm_bf3_kernel<pool>, has the arithmetic: a float32 is three bf16 terms, a product the six largest of the
-// nine term products, each exact, accumulated in float32; 16 k cost 192 matrix cycles instead of 512.)  act2 lives in LDS as three
-// bf16 planes [64][136] (row stride 272 bytes = 68 dwords: the same conflict-free ds_read_b128 pattern as the float image), written
-// split by layer 2's epilogue; the weights come split and packed from the host (iq_pack_weight_bf3: fragment (term, n-tile, k-step)
-// at ((term 32 + n-tile) 8 + k-step) KB), through a ring four k-steps (1 536 matrix cycles) ahead that rolls over n-tile and chunk
-// boundaries like BRing.  A row's result does not depend on the tile or chunk it sits in, so the pooled maxima are those of the
-// same rows in any arrangement (fused = materialised, bitwise, as before).  16-row tail tiles are not used here (a 32-row tile).
-constexpr int kLdB = 272;                 // bytes per act2 row of one bf16 plane
+// nine term products, each exact, accumulated in float32; 32 k cost 6 x 16 matrix cycles per 16 x 16 tile.)  The instruction is
+// v_mfma_f32_16x16x32_bf16 (iq_bf3.h, 16x16x32 forms; DESIGN.md 5a: the kernel is power-bound and this shape draws less power per
+// FLOP than 32x32x16, so the board holds a higher clock).  act2 lives in LDS as three bf16 planes [64][128] of unpadded, XOR-swizzled
+// 256-byte rows (conflict-free ds_read_b128 for this shape), written split by layer 2's epilogue; the weights come split and packed
+// from the host (iq_pack_weight_bf3: fragment (term, n-tile, k-step of 16) at ((term 32 + n-tile) 8 + k-step) KB - the 16x16x32
+// fragments are read out of the same image), through a register ring that rolls over pass and chunk boundaries like BRing.  A row's
+// result does not depend on the tile, lane group or chunk it sits in, so the pooled maxima are those of the same rows in any
+// arrangement (fused = materialised, bitwise, as before).  16-row tail tiles are not used here (m-tiles go in pairs of 16 rows).
+constexpr int kLdB = 256;                 // bytes per act2 row of one bf16 plane (128 k, unpadded, swizzled)
 constexpr int kPlaneB = kMC * kLdB;       // bytes per plane
 struct B3Ring { B3 r[4]; };
-constexpr int kLd1B = 144;                // bytes per act1 row of one bf16 plane (64 k; 36 dwords: conflict-free ds_read_b128)
+constexpr int kLd1B = 128;                // bytes per act1 row of one bf16 plane (64 k, unpadded, swizzled)
 constexpr int kPlane1B = kMC * kLd1B;
 
-// layer 2's weight fragment (n-tile nt of 4, k-step ks of 4) as three terms: iq_pack_weight_bf3 of a (128,64) matrix
-__device__ __forceinline__ B3 b3_load_l2(const __amdgpu_buffer_rsrc_t& rs, int voff, int nt, int ks) {
-    const int o = (nt * 4 + ks) * 1024;
-    return B3{__builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, o, 0)),
-              __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, o + 16 * 1024, 0)),
-              __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, o + 2 * 16 * 1024, 0))};
+// layer 2's 16x16x32 weight fragment (the A operand of the transposed tile): 32-channel n-tile nt of 4, its half hf, k-step t of 2
+// (32 input channels), out of iq_pack_weight_bf3 of a (128,64) matrix; voff = b16_lane_off(lane)
+__device__ __forceinline__ B3 b3_load16_l2(const __amdgpu_buffer_rsrc_t& rs, int voff, int nt, int t, int hf) {
+    return b3_load_at(rs, voff, (nt * 4 + 2 * t) * 1024 + 256 * hf, 16 * 1024);
 }
 
-__device__ __forceinline__ B3 b3_load(const __amdgpu_buffer_rsrc_t& rs, int voff, int step, int wave_s) {
-    // step = q * 8 + ks (mod 64): n-tile q * 4 + wave, k-step ks
-    const int o = ((((step >> 3) & 7) * 4 + wave_s) * 8 + (step & 7)) * 1024;
-    return B3{__builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, o, 0)),
-              __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, o + 32 * 8 * 1024, 0)),
-              __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, o + 2 * 32 * 8 * 1024, 0))};
+// layer 3's 16x16x32 weight fragment: 32-column n-tile (q mod 8) 4 + wave, its column half hf, k-step t of 4 (32 channels);
+// voff = b16_lane_off(lane)
+__device__ __forceinline__ B3 b3_load16(const __amdgpu_buffer_rsrc_t& rs, int voff, int q, int t, int hf, int wave_s) {
+    return b3_load_at(rs, voff, (((q & 7) * 4 + wave_s) * 8 + 2 * t) * 1024 + 256 * hf, 32 * 8 * 1024);
 }
 
-template <int MTS, bool ARGMAX = false>
-__device__ __forceinline__ void l3_pass_bf3(const __amdgpu_buffer_rsrc_t& rs, int voff, const unsigned char* abase, int wave_s,
-                                            float (&runmax)[8], B3Ring& ring, int (&runarg)[8], int rowbase = 0, int fh = 0) {
-#pragma unroll 1
-    for (int q = 0; q < 8; ++q) {
-        f32x16 acc0 = {0}, acc1 = {0};
+// running column maxima of a lane: runmax[2 q + hf] = column ((q 4 + wave) 32 + 16 hf + (lane & 15)) over the rows 4 kq + i of every
+// 16-row m-tile seen so far; the four kq lanes of a column meet in the kernel's epilogue.  ARGMAX: with the position in the item's
+// row list of the row that attains it (largest value, then lowest row: rows ascend with i, m-tile and chunk, so strict > everywhere).
+template <int MT, bool ARGMAX>
+__device__ __forceinline__ void l3_pool16(const f32x4 (&acc)[MT], bool take, float& runmax, int& runarg, int row0) {
+    if (ARGMAX) {
+        float m = -INFINITY;
+        int r = 0;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            bf16x8 a0[3], a1[3];
+        for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                a0[e] = *reinterpret_cast<const bf16x8*>(abase + e * kPlaneB + s * 32);
-                if (MTS == 2) a1[e] = *reinterpret_cast<const bf16x8*>(abase + e * kPlaneB + 32 * kLdB + s * 32);
-            }
-            const B3 b = ring.r[s & 3];
-            ring.r[s & 3] = b3_load(rs, voff, q * 8 + s + 4, wave_s);
-            // small terms first; with two m-tiles the two accumulation chains alternate
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[2], b.h, acc0, 0, 0, 0);
-            if (MTS == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[2], b.h, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0], b.l, acc0, 0, 0, 0);
-            if (MTS == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b.l, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[1], b.m, acc0, 0, 0, 0);
-            if (MTS == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[1], b.m, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[1], b.h, acc0, 0, 0, 0);
-            if (MTS == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[1], b.h, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0], b.m, acc0, 0, 0, 0);
-            if (MTS == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b.m, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[0], b.h, acc0, 0, 0, 0);
-            if (MTS == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b.h, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);     // one k-step at a time: left alone the scheduler hoists every step's operand
-                                                   // reads to the top of the n-tile (256 registers, one wave per SIMD)
+            for (int i = 0; i < 4; ++i)
+                if (acc[mi][i] > m) { m = acc[mi][i]; r = row0 + 16 * mi + i; }
+        const bool better = take && m > runmax;
+        runarg = better ? r : runarg;
+        runmax = better ? m : runmax;
+    } else {
+        float m = fmaxf(fmaxf(acc[0][0], acc[0][1]), acc[0][2]);
+        m = fmaxf(fmaxf(m, acc[0][3]), acc[1][0]);
+        m = fmaxf(fmaxf(m, acc[1][1]), acc[1][2]);
+        m = fmaxf(m, acc[1][3]);
+        if (MT == 4) {
+            float n = fmaxf(fmaxf(acc[2][0], acc[2][1]), acc[2][2]);
+            n = fmaxf(fmaxf(n, acc[2][3]), acc[3][0]);
+            n = fmaxf(fmaxf(n, acc[3][1]), acc[3][2]);
+            m = fmaxf(fmaxf(m, n), acc[3][3]);
         }
-        if (ARGMAX) {   // as l3_pass_v2
-            float m = -INFINITY;
-            int r = 0;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                if (acc0[i] > m) { m = acc0[i]; r = rowbase + c_row_i(i) + 4 * fh; }
-            }
-            if (MTS == 2) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i)
-                    if (acc1[i] > m) { m = acc1[i]; r = rowbase + 32 + c_row_i(i) + 4 * fh; }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const bool better = (i == q) && m > runmax[i];
-                runarg[i] = better ? r : runarg[i];
-                runmax[i] = better ? m : runmax[i];
-            }
-        } else {
-            float m = max16(acc0);
-            if (MTS == 2) m = fmaxf(m, max16(acc1));
-#pragma unroll
-            for (int i = 0; i < 8; ++i) runmax[i] = (i == q) ? fmaxf(runmax[i], m) : runmax[i];
-        }
+        runmax = take ? fmaxf(runmax, m) : runmax;
     }
 }
 
-// The same layer with TWO n-tiles per pass (n-tiles (2 qp) 4 + wave and (2 qp + 1) 4 + wave): the A terms of a k-step are read from
-// LDS once for both, half the LDS traffic of l3_pass_bf3 (the kernel is power-bound: operand bytes cost clock).  Every tile sees
-// the same products in the same order, so the maxima are bit-identical to l3_pass_bf3's.  ring.r[2 i + j] = fragment (k-step
-// parity i, n-tile j of the pair), two k-steps (1 536 matrix cycles) ahead, rolling over pair and chunk boundaries.
-template <int MTS>
-__device__ __forceinline__ void l3_pass_bf3_2x2(const __amdgpu_buffer_rsrc_t& rs, int voff, const unsigned char* abase, int wave_s,
-                                                float (&runmax)[8], B3Ring& ring) {
+// One n-tile of 32 columns (two 16-column halves) per pass: the ARGMAX instantiation and twin kTwinChainL3Single.
+// ring.r[2 (t & 1) + hf] = fragment (k-step parity, half), two k-steps ahead, rolling over n-tile and chunk boundaries.
+// abase: plane 0 of act2; aoff = a16_lane_off(lane); row0 = first row of this chunk + 4 kq.
+template <int MTS, bool ARGMAX = false>
+__device__ __forceinline__ void l3_pass_bf3(const __amdgpu_buffer_rsrc_t& rs, int voff, const unsigned char* abase, int aoff, int wave_s,
+                                            float (&runmax)[16], B3Ring& ring, int (&runarg)[16], int row0 = 0) {
+    constexpr int MT = 2 * MTS;
 #pragma unroll 1
-    for (int qp = 0; qp < 4; ++qp) {
-        f32x16 acc[MTS][2];
+    for (int q = 0; q < 8; ++q) {
+        f32x4 acc[2][MT];
 #pragma unroll
-        for (int i = 0; i < MTS; ++i) { acc[i][0] = (f32x16){0}; acc[i][1] = (f32x16){0}; }
-        bf16x8 af[MTS][3];
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
+            for (int i = 0; i < MT; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int i = 0; i < MTS; ++i) a3_load<kPlaneB>(af[i], abase + i * 32 * kLdB, s);
-            const B3 b[2] = {ring.r[2 * (s & 1)], ring.r[2 * (s & 1) + 1]};
-            // k-step s + 2 of this pair, or k-step s - 6 of the next one (b3_load takes the n-tile index mod 8)
-            const int qn = s + 2 < 8 ? 2 * qp : 2 * qp + 2, sn = (s + 2) & 7;
-            ring.r[2 * (s & 1)] = b3_load(rs, voff, qn * 8 + sn, wave_s);
-            ring.r[2 * (s & 1) + 1] = b3_load(rs, voff, (qn + 1) * 8 + sn, wave_s);
-            mfma_bf3_block<MTS, 2>(af, b, acc);
+        for (int t = 0; t < 4; ++t) {
+            bf16x8 af[MT][3];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) a16_load<kLdB, kPlaneB>(af[i], abase, aoff, i, t);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const B3 b = ring.r[2 * (t & 1) + j];
+                mfma16_bf3_col<MT>(af, b, acc[j]);
+                // k-step t + 2 of this n-tile, or k-step t - 2 of the next one (b3_load16 takes the n-tile index mod 8)
+                ring.r[2 * (t & 1) + j] = b3_load16(rs, voff, t + 2 < 4 ? q : q + 1, (t + 2) & 3, j, wave_s);
+            }
+            // issue order inside a k-step: the A reads, then per column tile its MFMAs and its ring refill (left alone the
+            // scheduler sinks every refill to the end of the k-step); one k-step at a time (it otherwise hoists every step's
+            // operand reads to the top of the n-tile)
+            __builtin_amdgcn_sched_group_barrier(0x100, 3 * MT, 0);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 6 * MT, 0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float m = max16(acc[0][j]);
-            if (MTS == 2) m = fmaxf(m, max16(acc[MTS - 1][j]));
+        for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) runmax[i] = (i == 2 * qp + j) ? fmaxf(runmax[i], m) : runmax[i];
+            for (int i = 0; i < 8; ++i) l3_pool16<MT, ARGMAX>(acc[j], i == q, runmax[2 * i + j], runarg[2 * i + j], row0);
+    }
+}
+
+// The same layer with TWO n-tiles per pass (n-tiles (2 qp) 4 + wave and (2 qp + 1) 4 + wave: 4 x 4 tiles of 16 x 16, the 64 x 64
+// wave tile and the 64 accumulator registers of the former 32x32x16 form): the A terms of a k-step are read from LDS once for all
+// four column tiles.  Every tile sees the same products in the same order, so the maxima are bit-identical to l3_pass_bf3's.  The
+// 96 MFMAs of a k-step go column-tile-major; ring.r[jj] = fragment of column tile jj (n-tile jj >> 1, half jj & 1) of the CURRENT
+// k-step, refilled with the next k-step's as soon as its 6 MT MFMAs are issued: the ring is three quarters of a k-step (1 152
+// matrix cycles) ahead and rolls over pass and chunk boundaries.
+template <int MTS>
+__device__ __forceinline__ void l3_pass_bf3_2x2(const __amdgpu_buffer_rsrc_t& rs, int voff, const unsigned char* abase, int aoff,
+                                                int wave_s, float (&runmax)[16], B3Ring& ring) {
+    constexpr int MT = 2 * MTS;
+    int noarg = 0;
+#pragma unroll 1
+    for (int qp = 0; qp < 4; ++qp) {
+        f32x4 acc[4][MT];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < MT; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            bf16x8 af[MT][3];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) a16_load<kLdB, kPlaneB>(af[i], abase, aoff, i, t);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const B3 b = ring.r[j];
+                mfma16_bf3_col<MT>(af, b, acc[j]);
+                // k-step t + 1 of this pair of n-tiles, or k-step 0 of the next pair
+                ring.r[j] = b3_load16(rs, voff, (t + 1 < 4 ? 2 * qp : 2 * qp + 2) + (j >> 1), (t + 1) & 3, j & 1, wave_s);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x100, 3 * MT, 0);     // as l3_pass_bf3
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 6 * MT, 0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) l3_pool16<MT, false>(acc[j], i == qp, runmax[4 * i + j], noarg, 0);
     }
 }
 
@@ -353,10 +380,12 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     float* c1base = bufB + (4 * frag_h) * kLd1 + frag_lane;         // C tiles of L1 -> act1
     float* c2base = bufA + (4 * frag_h) * kLd2 + frag_lane;         // C tiles of L2 -> act2
 
-    float runmax[8];
-    int runarg[8];
+    // running column maxima: fp32 layer 3 - [q] = n-tile q * 4 + wave, column lane & 31; bf16x3 layer 3 - [2 q + half], l3_pool16
+    constexpr int NRUN = L3V == 3 ? 16 : 8;
+    float runmax[NRUN];
+    int runarg[NRUN];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) { runmax[q] = -INFINITY; runarg[q] = 0; }
+    for (int q = 0; q < NRUN; ++q) { runmax[q] = -INFINITY; runarg[q] = 0; }
 
     // Input points travel ahead in registers: lanes 0..15 of each wave own 16 rows of a chunk.  The
     // row index of chunk c+2 and the coordinates of chunk c+1 are requested while chunk c computes, so
@@ -388,8 +417,10 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(L3V == 3 ? a.w2_bf3 : nullptr), 0, 0x7fffffff, 0x00020000);
     if (L3V == 3) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)   // l3_pass_bf3: k-steps 0..3 of n-tile 0; l3_pass_bf3_2x2: k-steps 0..1 of n-tiles 0 and 1
-            ring3.r[i] = b3_load(w3rs, lane * 16, ARGMAX || a.l3_single ? i : (i & 1) * 8 + (i >> 1), wave_s);
+        for (int i = 0; i < 4; ++i) {  // l3_pass_bf3: k-steps 0..1 of n-tile 0, both halves; l3_pass_bf3_2x2: k-step 0 of n-tiles 0 and 1
+            const bool single = ARGMAX || a.l3_single;
+            ring3.r[i] = b3_load16(w3rs, b16_lane_off(lane), single ? 0 : i >> 1, single ? i >> 1 : 0, i & 1, wave_s);
+        }
     }
     for (int ch = 0; ch < nchunks; ++ch) {
         const int rows_here = min(kMC, nrows - ch * kMC);
@@ -447,7 +478,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
 #pragma unroll
                         for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b1 + nt * 32 + 8 * g + 4 * frag_h);
                     }
-                    ct_tile_to_planes<kLd1B, kPlane1B>(reinterpret_cast<unsigned char*>(bufB) + mt * 32 * kLd1B + nt * 64, lane, [&](int r) {
+                    ct_tile_to_planes_swz<kLd1B, kPlane1B>(reinterpret_cast<unsigned char*>(bufB), mt * 32 + frag_lane, nt * 4, lane, [&](int r) {
                         const float v = acc[r] + bq[r >> 2][r & 3];
                         return (MODE == kFstn) ? fmaxf(v, 0.f) : v;
                     });
@@ -464,34 +495,49 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         }
         // ---- L2: 64 -> 128 (+bn, relu): two passes (n-tiles nt0, nt0+2); the second pass's weights
         //      are requested while the first pass computes ------------------------------------
-        if (L3V == 3) {   // on the bf16 matrix pipe: act1 and the weights as three bf16 terms, six products each (float32-exact)
+        if constexpr (L3V == 3) {   // on the bf16 matrix pipe: act1 and the weights as three bf16 terms, six products each (float32-exact)
+            // v_mfma_f32_16x16x32_bf16, transposed tiles (the weight fragment as the A operand): the lane holds four consecutive
+            // channels of its row.  Per wave 32 rows x 64 channels = two passes of 2 point tiles x 2 channel tiles, 2 k-steps of 32.
             const int mt = wave & 1, nt0 = wave >> 1, nts = wave_s >> 1;
             constexpr int PF = ARGMAX ? 2 : 4;   // weight fragments in flight (the arg-max variant has no registers to spare)
+            const int boff = b16_lane_off(lane);
             B3 bw[PF];
 #pragma unroll
-            for (int ks = 0; ks < PF; ++ks) bw[ks] = b3_load_l2(w2rs, lane * 16, nts, ks);
+            for (int f = 0; f < PF; ++f) bw[f] = b3_load16_l2(w2rs, boff, nts, f >> 1, f & 1);   // fragment f of 8 = (pass, k-step, half)
             __syncthreads();
             if (mt < mts) {
-                const unsigned char* arow = reinterpret_cast<const unsigned char*>(bufB) + (mt * 32 + frag_lane) * kLd1B + frag_h * 16;
+                const unsigned char* a1p = reinterpret_cast<const unsigned char*>(bufB) + mt * 32 * kLd1B;
+                const int a1off = a16_lane_off<kLd1B>(lane), row = mt * 32 + (lane & 15), kq = lane >> 4;
 #pragma unroll
                 for (int pass = 0; pass < 2; ++pass) {
-                    f32x16 acc = {0};
+                    f32x4 acc[2][2];
 #pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        bf16x8 af[3];
+                    for (int hf = 0; hf < 2; ++hf) { acc[hf][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[hf][1] = acc[hf][0]; }
 #pragma unroll
-                        for (int e = 0; e < 3; ++e) af[e] = *reinterpret_cast<const bf16x8*>(arow + e * kPlane1B + ks * 32);
-                        const int t = pass * 4 + ks, nx = t + PF;
-                        const B3 b = bw[t % PF];
-                        if (nx < 8) bw[t % PF] = b3_load_l2(w2rs, lane * 16, nts + 2 * (nx >> 2), nx & 3);
-                        acc = mfma_bf3_tr(b, af, acc);      // transposed tile, as layer 1
+                    for (int t = 0; t < 2; ++t) {
+                        bf16x8 af[2][3];
+#pragma unroll
+                        for (int pi = 0; pi < 2; ++pi) a16_load<kLd1B, kPlane1B>(af[pi], a1p, a1off, pi, t);
+#pragma unroll
+                        for (int hf = 0; hf < 2; ++hf) {
+                            const int f = pass * 4 + t * 2 + hf, nx = f + PF;
+                            const B3 b = bw[f % PF];
+                            if (nx < 8) bw[f % PF] = b3_load16_l2(w2rs, boff, nts + 2 * (nx >> 2), (nx >> 1) & 1, nx & 1);
+                            mfma16_bf3_col_tr<2>(b, af, acc[hf]);
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    f32x4 bq[4];
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + nt0 * 32 + pass * 64 + 8 * g + 4 * frag_h);
-                    ct_tile_to_planes<kLdB, kPlaneB>(reinterpret_cast<unsigned char*>(bufA) + mt * 32 * kLdB + (nt0 * 32 + pass * 64) * 2, lane,
-                                                     [&](int r) { return fmaxf(acc[r] + bq[r >> 2][r & 3], 0.f); });
+                    for (int hf = 0; hf < 2; ++hf) {
+                        const int ch = (nt0 + 2 * pass) * 32 + 16 * hf;
+                        const f32x4 bq = *reinterpret_cast<const f32x4*>(a.b2 + ch + 4 * kq);
+#pragma unroll
+                        for (int pi = 0; pi < 2; ++pi) {
+                            const f32x4 v = {fmaxf(acc[hf][pi][0] + bq[0], 0.f), fmaxf(acc[hf][pi][1] + bq[1], 0.f),
+                                             fmaxf(acc[hf][pi][2] + bq[2], 0.f), fmaxf(acc[hf][pi][3] + bq[3], 0.f)};
+                            c16_tile_to_planes_swz<kLdB, kPlaneB>(reinterpret_cast<unsigned char*>(bufA), row + 16 * pi, ch / 8, lane, v);
+                        }
+                    }
                 }
             }
         } else {
@@ -521,14 +567,19 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         }
         __syncthreads();
         // ---- L3: 128 -> 1024, running column max -------------------------------------------
-        if (L3V == 3) {
-            const unsigned char* ab3 = reinterpret_cast<const unsigned char*>(bufA) + frag_lane * kLdB + frag_h * 16;
-            if (ARGMAX || a.l3_single) {
-                if (mts == 2) l3_pass_bf3<2, ARGMAX>(w3rs, lane * 16, ab3, wave_s, runmax, ring3, runarg, ch * kMC, frag_h);
-                else          l3_pass_bf3<1, ARGMAX>(w3rs, lane * 16, ab3, wave_s, runmax, ring3, runarg, ch * kMC, frag_h);
+        if constexpr (L3V == 3) {
+            const unsigned char* ab3 = reinterpret_cast<const unsigned char*>(bufA);
+            const int aoff = a16_lane_off<kLdB>(lane), boff = b16_lane_off(lane);
+            if constexpr (ARGMAX) {
+                const int row0 = ch * kMC + 4 * (lane >> 4);
+                if (mts == 2) l3_pass_bf3<2, true>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg, row0);
+                else          l3_pass_bf3<1, true>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg, row0);
+            } else if (a.l3_single) {
+                if (mts == 2) l3_pass_bf3<2>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg);
+                else          l3_pass_bf3<1>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg);
             } else {
-                if (mts == 2) l3_pass_bf3_2x2<2>(w3rs, lane * 16, ab3, wave_s, runmax, ring3);
-                else          l3_pass_bf3_2x2<1>(w3rs, lane * 16, ab3, wave_s, runmax, ring3);
+                if (mts == 2) l3_pass_bf3_2x2<2>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3);
+                else          l3_pass_bf3_2x2<1>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3);
             }
         } else {
             const bool tail = !ARGMAX && a.tail16 && rows_here - 32 * (mts - 1) <= 16;   // (uniform) the last m-tile holds <= 16 rows
@@ -539,20 +590,46 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     }
 
     // max commutes with the (monotone) per-column bias add and relu
+    if constexpr (L3V == 3) {   // the four kq lanes of a column hold rows 4 kq + i of every m-tile: larger value wins, then the lower row
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        float v = runmax[q];
-        const int n = (q * 4 + wave) * 32 + (lane & 31);
-        if (ARGMAX) {   // the other half-wave saw rows 4..7 (+8 k) of every tile: larger value wins, then the lower row
-            const float v2 = __shfl_xor(v, 32);
-            const int r2 = __shfl_xor(runarg[q], 32);
-            const int r = (v2 > v || (v2 == v && r2 < runarg[q])) ? r2 : runarg[q];
-            if (lane < 32 && a.argrow) a.argrow[(size_t)item * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
+        for (int x = 0; x < 16; ++x) {
+            float v = runmax[x];
+            const int n = ((x >> 1) * 4 + wave) * 32 + 16 * (x & 1) + (lane & 15);
+            if constexpr (ARGMAX) {
+                int r = runarg[x];
+#pragma unroll
+                for (int d = 16; d <= 32; d *= 2) {
+                    const float v2 = __shfl_xor(v, d);
+                    const int r2 = __shfl_xor(r, d);
+                    const bool other = v2 > v || (v2 == v && r2 < r);
+                    r = other ? r2 : r;
+                    v = other ? v2 : v;
+                }
+                if (lane < 16 && a.argrow) a.argrow[(size_t)item * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
+            } else {
+                v = fmaxf(v, __shfl_xor(v, 16));
+                v = fmaxf(v, __shfl_xor(v, 32));
+            }
+            v += a.b3[n];
+            if (MODE != kTrunk) v = fmaxf(v, 0.f);
+            if (lane < 16) outp[n] = v;
         }
-        v = fmaxf(v, __shfl_xor(v, 32));
-        v += a.b3[n];
-        if (MODE != kTrunk) v = fmaxf(v, 0.f);
-        if (lane < 32) outp[n] = v;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            float v = runmax[q];
+            const int n = (q * 4 + wave) * 32 + (lane & 31);
+            if constexpr (ARGMAX) {   // the other half-wave saw rows 4..7 (+8 k) of every tile: larger value wins, then the lower row
+                const float v2 = __shfl_xor(v, 32);
+                const int r2 = __shfl_xor(runarg[q], 32);
+                const int r = (v2 > v || (v2 == v && r2 < runarg[q])) ? r2 : runarg[q];
+                if (lane < 32 && a.argrow) a.argrow[(size_t)item * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
+            }
+            v = fmaxf(v, __shfl_xor(v, 32));
+            v += a.b3[n];
+            if (MODE != kTrunk) v = fmaxf(v, 0.f);
+            if (lane < 32) outp[n] = v;
+        }
     }
 }
 

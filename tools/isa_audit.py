@@ -65,6 +65,38 @@ def audit(so_path):
     return out
 
 
+RESOURCE_KEYS = {"agpr_count": "agpr", "vgpr_count": "vgpr", "private_segment_fixed_size": "scratch",
+                 "group_segment_fixed_size": "lds", "vgpr_spill_count": "vgpr_spill", "sgpr_spill_count": "sgpr_spill"}
+_RESOURCE_LINE = re.compile(r"^\s*(?:- )?\.(%s|uses_dynamic_stack|symbol):\s*(\S+)\s*$" % "|".join(RESOURCE_KEYS))
+
+
+def resources(so_path):
+    """{kernel symbol: {"vgpr", "agpr" (registers per lane; on gfx950 one file of 512 per SIMD lane, so vgpr + agpr is what
+    limits the waves per SIMD), "scratch" (bytes per lane, spills included), "lds" (static bytes per workgroup), "vgpr_spill",
+    "sgpr_spill", "dynamic_stack"}} from the code-object metadata (amdhsa.kernels) of the gfx950 code inside the library."""
+    out = {}
+    with tempfile.TemporaryDirectory() as scratch:
+        for obj in device_objects(so_path, scratch):
+            text = subprocess.run([os.path.join(LLVM_BIN, "llvm-readobj"), "--notes", obj], check=True, capture_output=True,
+                                  text=True).stdout
+            cur = {}
+            for line in text.split("\n"):       # a kernel's keys come sorted: .agpr_count opens a record, .symbol names it (the
+                                                # keys after .symbol still land in the same record)
+                m = _RESOURCE_LINE.match(line)
+                if not m:
+                    continue
+                key, val = m.group(1), m.group(2)
+                if key == "agpr_count":
+                    cur = {}
+                if key == "symbol":
+                    out[val.strip("'\"")[:-3] if val.strip("'\"").endswith(".kd") else val.strip("'\"")] = cur
+                elif key == "uses_dynamic_stack":
+                    cur["dynamic_stack"] = val == "true"
+                else:
+                    cur[RESOURCE_KEYS[key]] = int(val)
+    return out
+
+
 def demangle(names):
     """{symbol: demangled name} by llvm-cxxfilt, else binutils' c++filt; the symbols themselves if neither is installed."""
     for tool in (os.path.join(LLVM_BIN, "llvm-cxxfilt"), shutil.which("c++filt")):
