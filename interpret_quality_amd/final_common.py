@@ -85,6 +85,29 @@ def coalition_logits_capped(model, clouds, centers, rid, keep, num_regions, cap)
                                              validate=False) for i in range(0, keep.numel(), cap)], dim=0)
 
 
+def materialised_logits(model, cloud, rid, keep, center, bs):
+    """For a model without a coalition entry point: the mask kernel writes the clouds of ``keep`` ((B,) masks of ``cloud``
+    (N,3)) in batches of ``bs`` and the model consumes them, as in the reference."""
+    points_api = hasattr(model, "forward_points")  # consumes (B,N,3) directly: no transpose
+    chunks = []
+    for i in range(0, keep.numel(), bs):
+        x = hip_ops.mask_coalitions(cloud, rid, keep[i:i + bs].contiguous(), center, channel_first=not points_api)
+        chunks.append(model.forward_points(x) if points_api else model(x))
+    return torch.cat(chunks, dim=0)
+
+
+def masked_logits(model, data, center, rid, keep, args, knob):
+    """Logits of the coalitions ``keep`` of one cloud ``data`` (1,N,3).  ``knob``: config.py's batch size in clouds - a floor
+    unless strict_batch_cap is set (rows are independent in eval mode, so larger launches give the same logits; stage 1 sets
+    no batch size: the reference evaluates one permutation per forward there, final_shapley_value.py:138-144), then a cap."""
+    strict = getattr(args, "strict_batch_cap", False)
+    if hasattr(model, "coalition_logits"):
+        return coalition_logits_capped(model, data.contiguous(), center.reshape(1, 3).contiguous(), rid.reshape(1, -1), keep,
+                                       args.num_regions, knob if strict else None)
+    bs = knob if strict else max(knob, getattr(model, "preferred_clouds_per_call", 0))
+    return materialised_logits(model, data[0].contiguous(), rid, keep, center.reshape(3).contiguous(), bs)
+
+
 def shapley_logits(model, data, lbl, region_id, orders, args, center=None):
     """Logits of all prefix coalitions of ``orders`` ((S,R) ndarray) for one cloud (1,N,3), in the reference's row order
     (row o*(R+1)+i keeps orders[o][:i]).  Models with a coalition entry point take the region bit masks directly;
@@ -98,24 +121,9 @@ def shapley_logits(model, data, lbl, region_id, orders, args, center=None):
     uniq, inv = distinct_coalitions(prefix_keep_masks(orders, r))
     work.add(inv.size, uniq.size)
     inv_t = torch.from_numpy(inv.astype(np.int64)).to(dev)
-    keep = hip_ops.masks_to_tensor(uniq, dev)
-    strict = getattr(args, "strict_batch_cap", False)
-    knob = getattr(args, "shapley_batch_size", 1) * (r + 1)
-    if hasattr(model, "coalition_logits"):
-        logits = coalition_logits_capped(model, data.contiguous(), center.reshape(1, 3).contiguous(), rid.reshape(1, -1), keep, r,
-                                         knob if strict else None)
-        return logits.index_select(0, inv_t)
-    # config.py's knob is a floor unless strict_batch_cap is set: rows are independent in eval mode, so larger launches give
-    # the same logits (stage 1 sets no batch size: the reference evaluates one permutation per forward there,
-    # final_shapley_value.py:138-144)
-    bs = knob if strict else max(knob, getattr(model, "preferred_clouds_per_call", 0))
-    chunks = []
-    points_api = hasattr(model, "forward_points")  # consumes (B,N,3) directly: no transpose
-    for i in range(0, keep.numel(), bs):
-        x = hip_ops.mask_coalitions(data[0].contiguous(), rid, keep[i:i + bs].contiguous(), center.reshape(3).contiguous(),
-                                    channel_first=not points_api)
-        chunks.append(model.forward_points(x) if points_api else model(x))
-    return torch.cat(chunks, dim=0).index_select(0, inv_t)
+    logits = masked_logits(model, data, center, rid, hip_ops.masks_to_tensor(uniq, dev), args,
+                           getattr(args, "shapley_batch_size", 1) * (r + 1))
+    return logits.index_select(0, inv_t)
 
 
 def shap_sampling_all_regions_batch(model, data_disturb, lbl, region_id, load_order_list, args):

@@ -392,21 +392,10 @@ class PackedLinear:
     float32-exact (include/iq.h: iq_dense_layer.w_bf3)."""
 
     def __init__(self, weight, bias, device, bf3=False):
-        lib = _lib.load()
-        w = np.ascontiguousarray(weight, dtype=np.float32)
-        self.cout, self.cin = w.shape
-        packed = np.empty(lib.iq_packed_floats(self.cout, self.cin), dtype=np.float32)
-        _lib.check(lib.iq_pack_weight(w.ctypes.data, packed.ctypes.data, self.cout, self.cin), "iq_pack_weight")
-        bp = np.zeros(lib.iq_padded_cout(self.cout), dtype=np.float32)
-        bp[:self.cout] = np.asarray(bias, dtype=np.float32)
-        self.w, self.b = torch.from_numpy(packed).to(device), torch.from_numpy(bp).to(device)
-        self.w3 = None
-        if bf3:
-            terms = np.empty(lib.iq_packed_bf3_elems(self.cout, self.cin), dtype=np.uint16)
-            _lib.check(lib.iq_pack_weight_bf3(w.ctypes.data, terms.ctypes.data, self.cout, self.cin), "iq_pack_weight_bf3")
-            self.w3 = torch.from_numpy(terms.view(np.int16)).to(device)
-        self.struct = _lib.DenseLayer(self.w.data_ptr(), self.b.data_ptr(), self.cin, self.cout,
-                                      self.w3.data_ptr() if self.w3 is not None else None)
+        from .engine import Packer      # engine.py imports this module
+        self.cout, self.cin = np.shape(weight)
+        self._packer = Packer(device)   # keeps the device tensors alive
+        self.struct = self._packer.dense(np.asarray(weight), bias, bf3=bf3)
 
 
 def linear(x, layer, act=0):

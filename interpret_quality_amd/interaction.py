@@ -65,24 +65,8 @@ def compute_order_interaction_logits(model, data_disturb, region_id, region_pair
             keep_np, inv = final_common.distinct_coalitions(context_keep_masks(pairs[lo:hi], ctx[lo:hi], r))
             work.add(inv.size, keep_np.size)
             inv_t = torch.from_numpy(inv.astype(np.int64)).to(dev)
-            strict = getattr(args, "strict_batch_cap", False)
-            if hasattr(model, "coalition_logits"):
-                logits = final_common.coalition_logits_capped(model, data_disturb.contiguous(), center.contiguous(), rid.reshape(1, -1),
-                                                              hip_ops.masks_to_tensor(keep_np, dev), r,
-                                                              4 * args.interaction_batch_size if strict else None)
-            else:
-                # config.py's knob is a floor (a cap with strict_batch_cap): rows are independent in eval mode, larger
-                # launches give the same logits
-                bs = 4 * args.interaction_batch_size if strict else max(4 * args.interaction_batch_size,
-                                                                       getattr(model, "preferred_clouds_per_call", 0))
-                keep = hip_ops.masks_to_tensor(keep_np, dev)
-                chunks = []
-                points_api = hasattr(model, "forward_points")  # consumes (B,N,3) directly: no transpose
-                for i in range(0, keep.numel(), bs):
-                    x = hip_ops.mask_coalitions(data_disturb[0].contiguous(), rid, keep[i:i + bs].contiguous(),
-                                                center.reshape(3).contiguous(), channel_first=not points_api)
-                    chunks.append(model.forward_points(x) if points_api else model(x))
-                logits = torch.cat(chunks, dim=0)
+            logits = final_common.masked_logits(model, data_disturb, center, rid, hip_ops.masks_to_tensor(keep_np, dev), args,
+                                                4 * args.interaction_batch_size)
             logits = logits.index_select(0, inv_t).reshape(hi - lo, 4 * num_context, -1)
         else:
             logits = torch.zeros((0, 4 * num_context, iqdist.num_classes_of(model)), dtype=torch.float32, device=dev)

@@ -15,72 +15,31 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, hip_ops
-
-BN_EPS = 1e-5
-
-
-def _np(t):
-    return t.detach().cpu().double().numpy()
+from . import _lib, hip_ops, workspace
+from .engine import Engine, EngineOwner, Packer, check_coalition_args, fold, ptr, stream
 
 
-def fold_bn(sd, layer, bn):
-    """(W, b) of ``bn(layer(x))`` in eval mode, folded in float64 and rounded once to float32."""
-    w = _np(sd[layer + ".weight"])
-    w = w.reshape(w.shape[0], -1)
-    b = _np(sd[layer + ".bias"])
-    if bn is not None:
-        s = _np(sd[bn + ".weight"]) / np.sqrt(_np(sd[bn + ".running_var"]) + BN_EPS)
-        w = w * s[:, None]
-        b = (b - _np(sd[bn + ".running_mean"])) * s + _np(sd[bn + ".bias"])
-    return w.astype(np.float32), b.astype(np.float32)
-
-
-class PackedWeights:
+class PackedWeights(Packer):
     """Device-resident, BN-folded, fragment-packed weights + the ctypes struct pointing at them."""
 
     def __init__(self, state_dict, device):
-        lib = _lib.load()
-        self.device = device
-        self._keep = []
+        super().__init__(device)
+        lib, sd = self.lib, state_dict
         self.struct = _lib.PointNetWeights()
-        sd = state_dict
-
-        def dev(arr):
-            t = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
-            self._keep.append(t)
-            return t
-
-        def pack(w):
-            cout, cin = w.shape
-            out = np.empty(lib.iq_packed_floats(cout, cin), dtype=np.float32)
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            _lib.check(lib.iq_pack_weight(w.ctypes.data, out.ctypes.data, cout, cin), "iq_pack_weight")
-            return out
 
         def dense(name, layer, bn, extra_bias=None):
-            w, b = fold_bn(sd, layer, bn)
-            if extra_bias is not None:
-                b = (b.astype(np.float64) + extra_bias).astype(np.float32)
+            w, b = fold(sd, layer, bn)
+            if extra_bias is not None:   # added in float64 to the bias already rounded to float32, then rounded again
+                b = b.astype(np.float32).astype(np.float64) + extra_bias
             cout, cin = w.shape
-            bp = np.zeros(lib.iq_padded_cout(cout), dtype=np.float32)
-            bp[:cout] = b
-            wt, bt = dev(pack(w)), dev(bp)
-
-            def bf3():   # the same weights as three bf16 terms (iq_pack_weight_bf3): products on the bf16 matrix pipe, float32-exact
-                w32 = np.ascontiguousarray(w, dtype=np.float32)
-                w3 = np.empty(lib.iq_packed_bf3_elems(cout, cin), dtype=np.uint16)
-                _lib.check(lib.iq_pack_weight_bf3(w32.ctypes.data, w3.ctypes.data, cout, cin), "iq_pack_weight_bf3")
-                return dev(w3.view(np.int16)).data_ptr()
             wide = cout % 256 == 0 and cin % 32 == 0       # the 1024 -> 512 -> 256 heads (include/iq.h: iq_dense_layer.w_bf3)
-            setattr(self.struct, name, _lib.DenseLayer(wt.data_ptr(), bt.data_ptr(), cin, cout, bf3() if wide else None))
+            setattr(self.struct, name, self.dense(w, b, bf3=wide))
             if name in ("fstn_c2", "feat_c2", "fstn_c3", "feat_c3"):   # layers 2-3 of the coalition chains
-                setattr(self.struct, name + "_bf3", bf3())
+                setattr(self.struct, name + "_bf3", self.bf3(w))
 
         def in_layer(name, layer, bn):
-            w, b = fold_bn(sd, layer, bn)  # (64,3), (64,)
-            t = dev(np.concatenate([w, b[:, None]], axis=1).astype(np.float32))
-            setattr(self.struct, name, t.data_ptr())
+            w, b = fold(sd, layer, bn)  # (64,3), (64,)
+            setattr(self.struct, name, self.dev(np.concatenate([w, b[:, None]], axis=1)).data_ptr())
 
         in_layer("stn_in", "feat.stn.conv1", "feat.stn.bn1")
         dense("stn_c2", "feat.stn.conv2", "feat.stn.bn2")
@@ -97,17 +56,17 @@ class PackedWeights:
             dense("fstn_fc1", "feat.fstn.fc1", "feat.fstn.bn4")
             dense("fstn_fc2", "feat.fstn.fc2", "feat.fstn.bn5")
             # fc3 of the feature STN: output = packed B image of trans_feat (+ identity)
-            w3, b3 = fold_bn(sd, "feat.fstn.fc3", None)
+            w3, b3 = fold(sd, "feat.fstn.fc3", None)
         else:   # feature_transform = False: the trunk gets the packed identity (the struct's fstn_c1.w stays NULL)
-            w3, b3 = np.zeros((4096, 256), dtype=np.float32), np.zeros(4096, dtype=np.float32)
-        w3 = np.ascontiguousarray(w3)
-        b3 = np.ascontiguousarray(b3)
+            w3, b3 = np.zeros((4096, 256)), np.zeros(4096)
+        w3 = np.ascontiguousarray(w3, dtype=np.float32)
+        b3 = np.ascontiguousarray(b3, dtype=np.float32)
         ow = np.empty(lib.iq_packed_floats(4096, 256), dtype=np.float32)
         ob = np.empty(4096, dtype=np.float32)
         perm = np.empty(4096, dtype=np.int32)
         _lib.check(lib.iq_pack_fstn_fc3(w3.ctypes.data, b3.ctypes.data, ow.ctypes.data, ob.ctypes.data,
                                         perm.ctypes.data), "iq_pack_fstn_fc3")
-        wt, bt = dev(ow), dev(ob)
+        wt, bt = self.dev(ow), self.dev(ob)
         self.struct.fstn_fc3 = _lib.DenseLayer(wt.data_ptr(), bt.data_ptr(), 256, 4096)
         inv = np.empty(4096, dtype=np.int64)
         inv[perm] = np.arange(4096)
@@ -120,21 +79,9 @@ class PackedWeights:
         self.num_classes = int(sd["fc3.weight"].shape[0])
 
 
-class PointNetEngine:
+class PointNetEngine(Engine):
     """Owns packed weights and a growable workspace; issues iq_pointnet_coalitions."""
-
-    def __init__(self, state_dict, device):
-        if torch.device(device).type != "cuda":
-            raise _lib.IqError("PointNetEngine needs a GPU device (no CPU fallback)")
-        self.lib = _lib.load()
-        self.device = torch.device(device)
-        self.weights = PackedWeights(state_dict, self.device)
-        self._ws = None
-
-    def _workspace(self, nbytes):
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-        return self._ws
+    packed = PackedWeights
 
     def coalition_logits(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None,
                          channel_first=False, return_trans_feat=False, return_crt=False):
@@ -146,23 +93,14 @@ class PointNetEngine:
         n = clouds.shape[2] if channel_first else clouds.shape[1]
         b = keep.shape[0] if keep is not None else (cloud_of.shape[0] if cloud_of is not None else nc)
         r = int(num_regions)
-        for t, dt, nm in ((clouds, torch.float32, "clouds"), (region_id, torch.int32, "region_id")):
-            if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise _lib.IqError("%s must be a contiguous %s GPU tensor" % (nm, dt))
-        for t, dt, nm in ((centers, torch.float32, "centers"), (keep, torch.int64, "keep"),
-                          (cloud_of, torch.int32, "cloud_of")):
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise _lib.IqError("%s must be a contiguous %s GPU tensor" % (nm, dt))
-        logits = torch.empty((b, self.weights.num_classes), dtype=torch.float32, device=self.device)
+        check_coalition_args(clouds, centers, region_id, keep, cloud_of, masked=False)
+        logits = self.new_logits(b)
         tfp = torch.empty((b, 4096), dtype=torch.float32, device=self.device) if return_trans_feat else None
         crt = torch.empty((b, 1024), dtype=torch.int32, device=self.device) if return_crt else None
-        need = self.lib.iq_pointnet_workspace_bytes(b, nc, n, r)
-        ws = self._workspace(need)
-        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-        rc = self.lib.iq_pointnet_coalitions_crt(ctypes.byref(self.weights.struct), p(clouds), p(centers), p(region_id),
-                                                 p(keep), p(cloud_of), p(logits), p(tfp), p(crt), p(ws), ws.numel(),
-                                                 b, nc, n, r, int(channel_first),
-                                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        ws = workspace.ensure(self, self.lib.iq_pointnet_workspace_bytes(b, nc, n, r))
+        rc = self.lib.iq_pointnet_coalitions_crt(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id),
+                                                 ptr(keep), ptr(cloud_of), ptr(logits), ptr(tfp), ptr(crt), ptr(ws), ws.numel(),
+                                                 b, nc, n, r, int(channel_first), stream())
         _lib.check(rc, "iq_pointnet_coalitions")
         out = (logits,) + ((tfp,) if return_trans_feat else ()) + ((crt,) if return_crt else ())
         return out if len(out) > 1 else logits
@@ -186,8 +124,9 @@ def _param_holder_stn(k):
     return m
 
 
-class PointNetCls(nn.Module):
+class PointNetCls(EngineOwner, nn.Module):
     """Parameter container with the reference's state-dict layout; forward runs on the HIP path."""
+    eval_only = "the HIP PointNet path implements eval mode only (BN running stats, no dropout)"
 
     def __init__(self, args=None):
         super().__init__()
@@ -204,24 +143,9 @@ class PointNetCls(nn.Module):
         self.feat = feat
         self.fc1, self.fc2, self.fc3 = nn.Linear(1024, 512), nn.Linear(512, 256), nn.Linear(256, self.output_channels)
         self.bn1, self.bn2 = nn.BatchNorm1d(512), nn.BatchNorm1d(256)
-        self._engine = None
 
-    # any parameter change invalidates the packed image
-    def load_state_dict(self, *a, **k):
-        self._engine = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
-
-    def engine(self):
-        if self.training:
-            raise _lib.IqError("the HIP PointNet path implements eval mode only (BN running stats, no dropout)")
-        if self._engine is None:
-            dev = self.fc3.weight.device
-            self._engine = PointNetEngine(self.state_dict(), dev)
-        return self._engine
+    def _new_engine(self):
+        return PointNetEngine(self.state_dict(), self.fc3.weight.device)
 
     def forward(self, x):
         """x (B,3,N) -> (logits, trans_feat, crt_points), the reference's tuple (models/pointnet.py:109-115): crt_points (B,1024)
