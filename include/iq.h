@@ -41,6 +41,7 @@ enum {
 #define IQ_MAX_REGIONS 64
 #define IQ_MAX_POINTS 4096
 #define IQ_NUM_FEAT 1024
+#define IQ_MAX_EXACT_PLAYERS 24
 
 /* ABI version: 100 * major + minor.  101 (round 4): every weight descriptor (iq_dense_layer, iq_pointnet_weights, ...) gained
  * optional `*_bf3` fields (weights split into three bf16 terms, iq_pack_weight_bf3).  Descriptors MUST be zero-initialised before
@@ -49,8 +50,9 @@ enum {
  * 102 (round 5): no layout change; a bf16x3 weight image (iq_pack_weight_bf3) now has its k range padded to a multiple of 32 (only images of layers with cin % 32 == 16 differ, and no kernel consumed those before), dense
  * layers take the image for any cin >= 32 and cout = 256 n or 256 n + 64, iq_knn uses a larger tmp when it is given one, PointNet
  * takes clouds of up to IQ_MAX_POINTS points and PointConv of 64 and more.
- * 103: new entry points, no layout change (the standalone geometric ops: iq_index_points .. iq_density). */
-#define IQ_ABI_VERSION 103
+ * 103: new entry points, no layout change (the standalone geometric ops: iq_index_points .. iq_density).
+ * 104: new entry points, no layout change (exact games by full enumeration: iq_enum_keep_masks .. iq_exact_scratch_bytes). */
+#define IQ_ABI_VERSION 104
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -502,6 +504,49 @@ int iq_sort_neighbours(const float* q, const float* keys, int32_t* idx, int B, i
  * d = square_distance(xyz, xyz) - the density itself (the fused PointConv path keeps its inverse).
  * Within 2e-6 relative of the reference.  xyz (B,N,3) -> out (B,N); B <= 65535. */
 int iq_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Exact games by full enumeration (csrc/iq_lattice.hip)
+ *
+ * The reference only ever SAMPLES its game: 1000 permutations per cloud (final_shapley_value.py:59-72, 138-156), at most
+ * 100 contexts per pair and order (final_gen_pair.py:25-41).  With n <= IQ_MAX_EXACT_PLAYERS players the game can be
+ * enumerated instead.  Coalition index c in [0, 2^n) has bit k set when player k is present; v[c] is the float32 reward
+ * (iq_reward) of coalition c.  The three reductions accumulate in float64 in an order that depends on (n, P) only - no
+ * floating-point atomics - so two calls give the same bits, however the table was produced.  n = 1 and n = 2 work.
+ * v must be 8-byte aligned (every torch allocation is).
+ * ------------------------------------------------------------------------------------------- */
+
+/* keep[b] = base | (the regions players[k] of every set bit k < n of first + b), b < count <= 2^30: the keep masks every
+ * iq_*_coalitions entry point takes, for a slice of the 2^n coalitions (a table is produced in chunks).  Bits n and above of
+ * first + b are ignored.  players: HOST pointer to n region ids in [0, IQ_MAX_REGIONS), NULL = player k is region k.  base: regions
+ * kept in EVERY coalition; a region in neither is always masked - an exact game among some of the regions.  IQ_EINVAL: a
+ * region named by two players, or by a player and base. */
+int iq_enum_keep_masks(uint64_t* keep /*count*/, uint64_t first, size_t count, const int32_t* players /*host, n*/, int n,
+                       uint64_t base, iq_stream_t stream);
+
+/* Scratch (bytes) that serves iq_exact_shapley(n) and iq_exact_interactions(n, P); 0 for arguments out of range
+ * (n outside 1 .. IQ_MAX_EXACT_PLAYERS, P outside 0 .. 65535). */
+size_t iq_exact_scratch_bytes(int n, int P);
+
+/* The Shapley value itself, where tools/final_common.py:92-97 and final_shapley_value.py:145-150 average marginal
+ * contributions over sampled permutations: phi[k] = sum over s of w(s) * sum over {c without bit k, popcount(c) = s} of
+ * (double)(v[c | 1<<k] - v[c]), w(s) = 1 / (n * C(n-1, s)), the difference taken in float32 as tools/final_common.py:93
+ * takes it.  Each stratum's sum is divided by the integer 1 / w(s).  v (2^n) float32, phi (n) float64. */
+int iq_exact_shapley(const float* v, int n, double* phi, void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* The reference's I_ij^(m) (final_cal_interactions.py:28-36 over the contexts of final_gen_pair.py:25-41, m = int((R-2) * ratio))
+ * with the expectation taken over ALL contexts: for pair p = (i, j) = pairs[p] (player positions) and every order
+ * m = 0 .. n-2, out[p][m] = the mean over the C(n-2, m) contexts c without bits i, j and popcount(c) = m of
+ * ((v[c|i|j] + v[c]) - v[c|i]) - v[c|j], in the float32 association of iq_interaction_reduce.  pairs (P,2) int32 on the
+ * device, out (P, n-1) float64; P <= 65535 pairs per call (IQ_EINVAL beyond).  A pair with an entry outside [0, n) or with i = j reads nothing and gives NaN. */
+int iq_exact_interactions(const float* v, int n, const int32_t* pairs /*P,2*/, int P, double* out /*P,n-1*/, void* scratch,
+                          size_t scratch_bytes, iq_stream_t stream);
+
+/* Harsanyi dividends (Moebius transform): a[c] = sum over subsets t of c of (-1)^(|c|-|t|) v[t], as n butterfly passes
+ * a[c] -= a[c without bit b] over a float64 copy of v, bit 0 first.  v (2^n) float32, a (2^n) float64; needs no scratch.
+ * Ties the two reductions above down: phi_k = sum over {c with bit k} of a[c] / |c|, and the interaction term of context S is
+ * the sum of a[T + {i,j}] over the subsets T of S. */
+int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
 
 /* The diagnostic entry points (HIP-event profiler, experiment knobs, debug counters) are NOT part of the drop-in surface:
  * they are declared in iq_debug.h. */

@@ -128,6 +128,11 @@ SIGNATURES = {
     "iq_knn_point": (_I, [_P, _P, _I, _P, _P, _SZ, _I, _I, _I, _P]),
     "iq_sort_neighbours": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "iq_density": (_I, [_P, ctypes.c_double, _P, _I, _I, _P]),
+    "iq_enum_keep_masks": (_I, [_P, ctypes.c_uint64, _SZ, _P, _I, ctypes.c_uint64, _P]),
+    "iq_exact_scratch_bytes": (_SZ, [_I, _I]),
+    "iq_exact_shapley": (_I, [_P, _I, _P, _P, _SZ, _P]),
+    "iq_exact_interactions": (_I, [_P, _I, _P, _I, _P, _P, _SZ, _P]),
+    "iq_moebius": (_I, [_P, _I, _P, _P]),
     "iq_profile_enable": (_I, [_I]),
     "iq_set_tuning": (_I, [_I, _I]),
     "iq_profile_read_work": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -138,7 +143,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 103   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 104   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -210,6 +210,91 @@ def interaction_reduce(v):
     return out
 
 
+MAX_EXACT_PLAYERS = 24      # IQ_MAX_EXACT_PLAYERS of include/iq.h (tests/test_exact_cpu.py compares the two)
+
+
+def enum_keep_masks(first, count, n, device, players=None, base=0):
+    """iq_enum_keep_masks: (count,) int64-typed keep masks of the coalitions first .. first + count - 1 of an n-player game;
+    player k is region players[k] (None: region k), the regions of the bit mask ``base`` are kept in every coalition."""
+    lib = _lib.load()
+    if torch.device(device).type != "cuda":
+        raise _lib.IqError("enum_keep_masks needs a GPU device (the HIP path has no CPU fallback)")
+    keep = torch.empty((int(count),), dtype=torch.int64, device=device)
+    pl = None
+    if players is not None:
+        pl = np.ascontiguousarray(np.asarray(players, dtype=np.int64).reshape(-1).clip(-1, 64), dtype=np.int32)
+        if pl.size != int(n):
+            raise _lib.IqError("players names %d regions for n=%d players" % (pl.size, int(n)))
+    _lib.check(lib.iq_enum_keep_masks(_p(keep), int(first) & (2 ** 64 - 1), int(count), ctypes.c_void_p(pl.ctypes.data if pl is not None else 0),
+                                      int(n), int(base) & (2 ** 64 - 1), _stream()), "iq_enum_keep_masks")
+    return keep
+
+
+def _value_table(v):
+    """The number of players of a (2^n,) float32 table of coalition rewards."""
+    _dev(v, torch.float32, "v")
+    n = int(v.numel()).bit_length() - 1
+    if v.dim() != 1 or v.numel() != 1 << max(n, 0) or not 1 <= n <= MAX_EXACT_PLAYERS:
+        raise _lib.IqError("v must be a (2^n,) table with 1 <= n <= %d, got shape %s" % (MAX_EXACT_PLAYERS, tuple(v.shape)))
+    return n
+
+
+def _exact_scratch(lib, n, p, device):
+    return torch.empty((lib.iq_exact_scratch_bytes(n, p) // 8,), dtype=torch.float64, device=device)
+
+
+def exact_shapley(v):
+    """v (2^n,) f32 rewards of all coalitions (bit k of the index = player k present) -> (n,) f64 Shapley values
+    (iq_exact_shapley: float64, fixed order, bitwise repeatable)."""
+    lib = _lib.load()
+    n = _value_table(v)
+    phi = torch.empty((n,), dtype=torch.float64, device=v.device)
+    scratch = _exact_scratch(lib, n, 0, v.device)
+    _lib.check(lib.iq_exact_shapley(_p(v), n, _p(phi), _p(scratch), scratch.numel() * 8, _stream()), "iq_exact_shapley")
+    return phi
+
+
+def all_pairs(n):
+    """The n(n-1)/2 pairs (i, j), i < j, of player positions, in lexicographic order: (P,2) int32 ndarray."""
+    return np.array([(i, j) for i in range(n) for j in range(i + 1, n)], dtype=np.int32).reshape(-1, 2)
+
+
+def exact_interactions(v, pairs=None):
+    """v (2^n,) f32, pairs (P,2) player positions (None: all_pairs(n)) -> (P, n-1) f64: out[p][m] = the mean of
+    ((v[c|i|j] + v[c]) - v[c|i]) - v[c|j] over ALL contexts c of m players (iq_exact_interactions)."""
+    lib = _lib.load()
+    n = _value_table(v)
+    if isinstance(pairs, torch.Tensor):
+        pr = pairs.to(device=v.device, dtype=torch.int32).contiguous()
+        if pr.dim() != 2 or pr.shape[1] != 2:
+            raise _lib.IqError("pairs must be (P,2), got %s" % (tuple(pr.shape),))
+        check_index_range(pr, 0, n, "pairs")
+        if bool((pr[:, 0] == pr[:, 1]).any()):
+            raise _lib.IqError("pairs: a pair names the same player twice")
+    else:
+        host = all_pairs(n) if pairs is None else np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        check_host_indices(host, 0, n, "pairs")
+        if host.size and (host[:, 0] == host[:, 1]).any():
+            raise _lib.IqError("pairs: pair %d names the same player twice" % int(np.flatnonzero(host[:, 0] == host[:, 1])[0]))
+        pr = as_i32(host, v.device)
+    p = pr.shape[0]
+    out = torch.empty((p, n - 1), dtype=torch.float64, device=v.device)
+    if p:
+        scratch = _exact_scratch(lib, n, p, v.device)
+        _lib.check(lib.iq_exact_interactions(_p(v), n, _p(pr), p, _p(out), _p(scratch), scratch.numel() * 8, _stream()),
+                   "iq_exact_interactions")
+    return out
+
+
+def moebius(v):
+    """v (2^n,) f32 -> (2^n,) f64 Harsanyi dividends a[c] = sum over subsets t of c of (-1)^(|c|-|t|) v[t] (iq_moebius)."""
+    lib = _lib.load()
+    n = _value_table(v)
+    a = torch.empty((1 << n,), dtype=torch.float64, device=v.device)
+    _lib.check(lib.iq_moebius(_p(v), n, _p(a), _stream()), "iq_moebius")
+    return a
+
+
 def region_assign(cloud, fps_idx):
     lib = _lib.load()
     n = cloud.shape[0]
