@@ -16,7 +16,9 @@
  *  - return value: IQ_OK (0) or a negative IQ_E* code; a message for the calling thread's last
  *    error is available from iq_last_error();
  *  - indices are int32 at the ABI (the Python wrappers convert from int64), coalitions are
- *    uint64 bit masks over regions (bit r set = region r kept), so num_regions <= 64.
+ *    uint64 bit masks over regions (bit r set = region r kept), so num_regions <= 64 - except at the
+ *    iq_*_wide entry points ("Wide coalitions" below), which take rows of ceil(num_regions / 64) words
+ *    for up to IQ_MAX_WIDE_REGIONS regions.
  */
 #ifndef IQ_H_
 #define IQ_H_
@@ -42,6 +44,7 @@ enum {
 #define IQ_MAX_POINTS 4096
 #define IQ_NUM_FEAT 1024
 #define IQ_MAX_EXACT_PLAYERS 24
+#define IQ_MAX_WIDE_REGIONS 1024   /* iq_*_wide: a coalition is a row of at most 16 words */
 
 /* ABI version: 100 * major + minor.  101 (round 4): every weight descriptor (iq_dense_layer, iq_pointnet_weights, ...) gained
  * optional `*_bf3` fields (weights split into three bf16 terms, iq_pack_weight_bf3).  Descriptors MUST be zero-initialised before
@@ -51,8 +54,9 @@ enum {
  * layers take the image for any cin >= 32 and cout = 256 n or 256 n + 64, iq_knn uses a larger tmp when it is given one, PointNet
  * takes clouds of up to IQ_MAX_POINTS points and PointConv of 64 and more.
  * 103: new entry points, no layout change (the standalone geometric ops: iq_index_points .. iq_density).
- * 104: new entry points, no layout change (exact games by full enumeration: iq_enum_keep_masks .. iq_exact_scratch_bytes). */
-#define IQ_ABI_VERSION 104
+ * 104: new entry points, no layout change (exact games by full enumeration: iq_enum_keep_masks .. iq_exact_scratch_bytes).
+ * 105: new entry points, no layout change (wide coalitions: iq_prefix_keep_masks_wide .. iq_pointnet_coalitions_wide). */
+#define IQ_ABI_VERSION 105
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -547,6 +551,48 @@ int iq_exact_interactions(const float* v, int n, const int32_t* pairs /*P,2*/, i
  * Ties the two reductions above down: phi_k = sum over {c with bit k} of a[c] / |c|, and the interaction term of context S is
  * the sum of a[T + {i,j}] over the subsets T of S. */
 int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)
+ *
+ * In the reference NUM_REGIONS is a constant (tools/final_util.py:20-22) and mask_data_batch (tools/final_common.py:46-61),
+ * cal_region_id (final_shapley_value.py:20-35) and the sampling loop (:138-156) work for any region count up to the number of
+ * points.  A WIDE coalition is a row of W = ceil(R / 64) uint64 words: bit (r & 63) of word (r >> 6) set = region r kept; bits
+ * at or above R are ignored.  1 <= R <= IQ_MAX_WIDE_REGIONS.  Every entry point above keeps its R <= 64 check and its code;
+ * for R <= 64 (W = 1) the entry points below give the same bits as their narrow twins.  The permutations of a wide game are
+ * drawn on the host (final_shapley_value.py:59-72 as it stands: NumPy's global generator) - iq_sample_permutations stays narrow.
+ * The interaction, smoothness and pose stages and the compact coalition paths of PointNet++ / DGCNN / PointConv have no wide
+ * form: those families evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.
+ * ------------------------------------------------------------------------------------------- */
+
+/* tools/final_common.py:56-60 as wide masks: row s*(R+1) + i of keep keeps orders[s][0..i-1]; an entry outside [0, R) is ignored. */
+int iq_prefix_keep_masks_wide(const int32_t* orders /*S,R*/, uint64_t* keep /*S*(R+1),W*/, int S, int R, iq_stream_t stream);
+
+/* iq_mask_coalitions for wide keep rows (tools/final_common.py:46-61 for arbitrary coalitions): out row b keeps the regions of
+ * keep[b]; a point whose region id lies outside [0, R) is masked.  out (B,N,3) or (B,3,N); any 1 <= N <= IQ_MAX_POINTS. */
+int iq_mask_coalitions_wide(const float* cloud /*N,3*/, const int32_t* region_id /*N*/, const uint64_t* keep /*B,W*/,
+                            const float* center /*3*/, float* out, int N, int R, int B, int channel_first, iq_stream_t stream);
+
+/* iq_region_assign (final_shapley_value.py:20-35 with tools/final_util.py:134-147) for up to IQ_MAX_WIDE_REGIONS centres: the
+ * same expanded-form distance in the same operation order, first index on ties.  With R = N (one region per point; FPS repeats
+ * index 0 once the distinct locations are used up) duplicate points leave empty regions. */
+int iq_region_assign_wide(const float* cloud /*N,3*/, const int32_t* fps_idx /*R*/, int32_t* region_id /*N*/, int N, int R,
+                          iq_stream_t stream);
+
+/* iq_shapley_accum (tools/final_common.py:92-96, final_shapley_value.py:145-150) for R <= IQ_MAX_WIDE_REGIONS: the same
+ * arguments, the same float32 differences, the same float64 adds in permutation order per region. */
+int iq_shapley_accum_wide(const float* v /*S*(R+1)*/, const int32_t* orders /*S,R*/, double* sv_rows, double* phi_sum,
+                          const int32_t* snap_counts, int n_snap, double* snaps, int R, int S, iq_stream_t stream);
+
+/* iq_pointnet_coalitions for wide keep rows (B,W): the per-cloud counting sort, the row-list builder and the pooled input-STN
+ * gather in their wide form, then the same chain kernels and heads on the resulting lists - for R <= 64 the lists, hence the
+ * logits, are iq_pointnet_coalitions's bit for bit.  A region may be empty (its player's marginal contribution is 0).  The
+ * workspace holds nclouds*(R+1) pre-pooled feature rows of 4 KB and as many row lists. */
+size_t iq_pointnet_wide_workspace_bytes(int B, int nclouds, int N, int R);
+int iq_pointnet_coalitions_wide(const iq_pointnet_weights* w, const float* clouds, const float* centers,
+                                const int32_t* region_id, const uint64_t* keep /*B,W*/, const int32_t* cloud_of, float* logits,
+                                float* trans_feat_packed, void* workspace, size_t workspace_bytes, int B, int nclouds, int N,
+                                int R, int channel_first, iq_stream_t stream);
 
 /* The diagnostic entry points (HIP-event profiler, experiment knobs, debug counters) are NOT part of the drop-in surface:
  * they are declared in iq_debug.h. */

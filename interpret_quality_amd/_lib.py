@@ -133,6 +133,13 @@ SIGNATURES = {
     "iq_exact_shapley": (_I, [_P, _I, _P, _P, _SZ, _P]),
     "iq_exact_interactions": (_I, [_P, _I, _P, _I, _P, _P, _SZ, _P]),
     "iq_moebius": (_I, [_P, _I, _P, _P]),
+    "iq_prefix_keep_masks_wide": (_I, [_P, _P, _I, _I, _P]),
+    "iq_mask_coalitions_wide": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "iq_region_assign_wide": (_I, [_P, _P, _P, _I, _I, _P]),
+    "iq_shapley_accum_wide": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
+    "iq_pointnet_wide_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "iq_pointnet_coalitions_wide": (_I, [ctypes.POINTER(PointNetWeights), _P, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                         _I, _I, _I, _I, _I, _P]),
     "iq_profile_enable": (_I, [_I]),
     "iq_set_tuning": (_I, [_I, _I]),
     "iq_profile_read_work": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -143,7 +150,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 104   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 105   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

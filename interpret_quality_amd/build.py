@@ -18,7 +18,7 @@ DEBUG_HEADER = os.path.join(os.path.dirname(HERE), "include", "iq_debug.h")
 ARCH = "gfx950"
 # Index-valued kernels (FPS, ball query, region assignment) need individually rounded operations:
 # hipcc's default -ffp-contract=fast fuses a*b+c into fma even through the __f*_rn intrinsics.
-NO_CONTRACT = ("iq_geom.hip", "iq_pointnet2.hip", "iq_dgcnn.hip", "iq_pointconv.hip", "iq_smooth.hip")
+NO_CONTRACT = ("iq_geom.hip", "iq_pointnet2.hip", "iq_dgcnn.hip", "iq_pointconv.hip", "iq_smooth.hip", "iq_wide.hip")
 # The PointNet chain kernel pools with fmaxf over MFMA results; without -fno-honor-nans every such operand gets a canonicalising
 # v_max_f32 x, x, x first (iq_mfma.h, max16).  The file holds no index-valued kernel and no NaN test.
 NO_NANS = ("iq_pointnet.hip", "iq_linear.hip", "iq_dgcnn.hip")

@@ -7,6 +7,7 @@
 // expressions evaluate them; ties resolve to the lowest index like the CPU argmin/argmax.
 #include "iq_common.h"
 #include "iq_mfma.h"
+#include "iq_sqdist.h"
 
 // Index-valued results depend on individually rounded operations: forbid the compiler from fusing
 // a*b+c into an fma anywhere in this file (explicit fmaf / MFMA calls are unaffected).
@@ -14,21 +15,8 @@
 
 namespace {
 
-// |p|^2 as torch.sum(p ** 2, -1) evaluates it for three coordinates
-__device__ __forceinline__ float norm3(float x, float y, float z) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z));
-}
-
-// square_distance(src, dst) (tools/final_util.py:134-147, models/pointnet2.py:12-25, models/pointconv.py:13-32) for one pair:
-// the matmul row (K = 3) as an fma chain, then * -2, + |src|^2, + |dst|^2
-__device__ __forceinline__ float sqdist3(float sx, float sy, float sz, float sn, float dx, float dy, float dz, float dn) {
-    float dot = __fmul_rn(sx, dx);
-    dot = __fmaf_rn(sy, dy, dot);
-    dot = __fmaf_rn(sz, dz, dot);
-    float d = __fmul_rn(-2.f, dot);
-    d = __fadd_rn(d, sn);
-    return __fadd_rn(d, dn);
-}
+using iq::norm3;      // iq_sqdist.h: the reference's square_distance for one pair, shared with iq_wide.hip
+using iq::sqdist3;
 
 // ---- K6: tools/final_util.py:134-147 + final_shapley_value.py:29-31 -------------------------
 __global__ __launch_bounds__(256) void region_assign_kernel(const float* __restrict__ cloud,

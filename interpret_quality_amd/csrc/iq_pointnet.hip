@@ -724,6 +724,110 @@ __global__ __launch_bounds__(64) void pn_rows_kernel(const uint16_t* __restrict_
     if (lane == 0) nrows_all[item] = nrows | (add_centre ? (1 << 16) : 0);
 }
 
+// ---- the same two kernels for wide coalitions (R up to IQ_MAX_WIDE_REGIONS, keep rows of W = ceil(R / 64) words) --------------
+// They write what their narrow twins write - points grouped by region in ascending point order; row lists of the kept regions in
+// ascending region order, the centre and the padding by the same rules - so the chain kernel sees the same lists for R <= 64.
+constexpr int kMaxW = IQ_MAX_WIDE_REGIONS / 64;
+
+__global__ __launch_bounds__(kThreads) void pn_prepare_wide_kernel(const int32_t* __restrict__ region_id,
+                                                                   uint16_t* __restrict__ sorted_pts,
+                                                                   int32_t* __restrict__ roff, int N, int R) {
+    __shared__ int16_t rid[kMaxN];
+    __shared__ int cnt[IQ_MAX_WIDE_REGIONS + 1];
+    const int cloud = blockIdx.x;
+    for (int r = threadIdx.x; r <= R; r += kThreads) cnt[r] = 0;
+    for (int p = threadIdx.x; p < N; p += kThreads) {
+        const int r = region_id[(size_t)cloud * N + p];          // outside [0,R): bucket R, which no coalition keeps
+        rid[p] = (int16_t)((unsigned)r < (unsigned)R ? r : R);
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < N; p += kThreads) atomicAdd(&cnt[rid[p]], 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {  // exclusive scan; once per cloud and launch
+        int run = 0;
+        for (int r = 0; r <= R; ++r) { const int c = r < R ? cnt[r] : 0; cnt[r] = run; run += c; }
+    }
+    __syncthreads();
+    for (int r = threadIdx.x; r <= R; r += kThreads) roff[(size_t)cloud * (R + 1) + r] = cnt[r];
+    for (int p = threadIdx.x; p < N; p += kThreads) {
+        const int r = rid[p];
+        if (r >= R) continue;
+        int k = 0;
+        for (int q = 0; q < p; ++q) k += (rid[q] == r);   // rank inside the region: ascending point index
+        sorted_pts[(size_t)cloud * N + cnt[r] + k] = (uint16_t)p;
+    }
+}
+
+// One wave per item.  The start of every kept region in the row list comes from a scan over the regions, 64 at a time.  A region of
+// a wide game holds few points (N / R: one at R = N), so above 64 regions a lane copies whole regions instead of the wave one.
+__global__ __launch_bounds__(64) void pn_rows_wide_kernel(const uint16_t* __restrict__ sorted_all,
+                                                          const int32_t* __restrict__ roff_all,
+                                                          const uint64_t* __restrict__ keep_all,
+                                                          const int32_t* __restrict__ cloud_of, uint16_t* __restrict__ rows_all,
+                                                          int32_t* __restrict__ nrows_all, int N, int R, int W, int nclouds,
+                                                          int with_centre, int prepool) {
+    __shared__ int kst_s[IQ_MAX_WIDE_REGIONS];   // first row of a kept region, -1 = not kept
+    const int item = blockIdx.x, lane = threadIdx.x;
+    uint16_t* rows = rows_all + (size_t)item * kRowCap;
+    int nkept = 0, padval = N;
+    bool add_centre;
+    if (prepool) {   // item = cloud * (R + with_centre) + r: region r alone (no centre), r == R the centre alone
+        const int per = R + with_centre, cloud = item / per, r = item - cloud * per;
+        const int32_t* roff = roff_all + (size_t)cloud * (R + 1);
+        const uint16_t* sorted_pts = sorted_all + (size_t)cloud * N;
+        add_centre = (r == R);
+        if (r < R) {
+            const int off = roff[r];
+            nkept = roff[r + 1] - off;
+            for (int j = lane; j < nkept; j += 64) rows[j] = sorted_pts[off + j];
+            if (nkept > 0) padval = sorted_pts[off + nkept - 1];
+        }
+    } else {
+        const int cloud = cloud_of ? cloud_of[item] : (nclouds == 1 ? 0 : item);
+        const int32_t* roff = roff_all + (size_t)cloud * (R + 1);
+        const uint16_t* sorted_pts = sorted_all + (size_t)cloud * N;
+        const uint64_t* keep = keep_all ? keep_all + (size_t)item * W : nullptr;   // null = everything
+        int last_r = -1;   // the last kept region that holds a point
+        for (int r0 = 0; r0 < R; r0 += 64) {
+            const int r = r0 + lane;
+            const bool kept = r < R && (!keep || ((keep[r0 >> 6] >> lane) & 1));
+            const int sz = kept ? roff[r + 1] - roff[r] : 0;
+            int inc = sz;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(inc, off);
+                if (lane >= off) inc += t;
+            }
+            if (r < R) kst_s[r] = kept ? nkept + inc - sz : -1;
+            const unsigned long long ne = __ballot(sz > 0);
+            if (ne) last_r = r0 + 63 - __clzll((long long)ne);
+            nkept += __shfl(inc, 63);
+        }
+        __syncthreads();
+        add_centre = with_centre && nkept < N;
+        if (R <= 64) {
+            for (int r = 0; r < R; ++r) {
+                const int ks = kst_s[r];
+                if (ks < 0) continue;
+                const int off = roff[r], n = roff[r + 1] - off;
+                for (int j = lane; j < n; j += 64) rows[ks + j] = sorted_pts[off + j];
+            }
+        } else {
+            for (int r = lane; r < R; r += 64) {
+                const int ks = kst_s[r];
+                if (ks < 0) continue;
+                const int off = roff[r], n = roff[r + 1] - off;
+                for (int j = 0; j < n; ++j) rows[ks + j] = sorted_pts[off + j];
+            }
+        }
+        if (!add_centre && nkept > 0) padval = sorted_pts[roff[last_r + 1] - 1];   // padding: the centre if present, else the last kept point
+    }
+    const int nrows = nkept + (add_centre ? 1 : 0);
+    const int npad = (nrows + kMC - 1) / kMC * kMC;
+    for (int i = nkept + lane; i < npad; i += 64) rows[i] = (uint16_t)padval;
+    if (lane == 0) nrows_all[item] = nrows | (add_centre ? (1 << 16) : 0);
+}
+
 // ---- launch order: largest coalitions first (LPT), a counting sort on the chunk count ---------
 constexpr int kBins = kMaxN / kMC + 2;
 
@@ -798,6 +902,54 @@ __global__ __launch_bounds__(kThreads) void pn_stn_gather_kernel(const float* __
     reinterpret_cast<f32x4*>(out)[(size_t)item * (kFeat / 4) + threadIdx.x] = m;
 }
 
+// The same for a wide keep row (W words, in LDS once): the set bits in ascending order, four rows of G in flight per thread (a
+// row read twice to fill a group of four never changes a max).  A coalition reads 4 KB per kept region: 4 MB at most at R = 1024,
+// 2 MB on average over the prefix coalitions of a permutation.
+__global__ __launch_bounds__(kThreads) void pn_stn_gather_wide_kernel(const float* __restrict__ G,
+                                                                      const int32_t* __restrict__ nrows_all,
+                                                                      const uint64_t* __restrict__ keep,
+                                                                      const int32_t* __restrict__ cloud_of,
+                                                                      float* __restrict__ out, int R, int W, int nclouds,
+                                                                      int with_centre) {
+    __shared__ uint64_t ks[kMaxW];
+    const int item = blockIdx.x;
+    const int cloud = cloud_of ? cloud_of[item] : (nclouds == 1 ? 0 : item);
+    if ((int)threadIdx.x < W) {
+        uint64_t k = keep ? keep[(size_t)item * W + threadIdx.x] : ~0ull;
+        if ((int)threadIdx.x == W - 1 && (R & 63)) k &= (1ull << (R & 63)) - 1;   // bits at or above R are ignored
+        ks[threadIdx.x] = k;
+    }
+    __syncthreads();
+    const int per = R + with_centre;
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(G) + (size_t)cloud * per * (kFeat / 4) + threadIdx.x;
+    f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int w = 0; w < W; ++w) {
+        const uint64_t kw = ks[w];
+        uint64_t k = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(kw >> 32)) << 32) |
+                     (unsigned)__builtin_amdgcn_readfirstlane((int)kw);                      // the same for every lane
+        while (k) {
+            int r[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                r[q] = k ? w * 64 + __ffsll((long long)k) - 1 : r[0];
+                k &= k - 1;
+            }
+            f32x4 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v[q] = g4[(size_t)r[q] * (kFeat / 4)];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                m[0] = fmaxf(m[0], v[q][0]); m[1] = fmaxf(m[1], v[q][1]); m[2] = fmaxf(m[2], v[q][2]); m[3] = fmaxf(m[3], v[q][3]);
+            }
+        }
+    }
+    if (nrows_all[item] >> 16) {  // a centre row exists (something was masked)
+        const f32x4 v = g4[(size_t)R * (kFeat / 4)];
+        m[0] = fmaxf(m[0], v[0]); m[1] = fmaxf(m[1], v[1]); m[2] = fmaxf(m[2], v[2]); m[3] = fmaxf(m[3], v[3]);
+    }
+    reinterpret_cast<f32x4*>(out)[(size_t)item * (kFeat / 4) + threadIdx.x] = m;
+}
+
 // every item's 64 x 64 transform := one packed image (4096 floats), float4 per thread
 __global__ __launch_bounds__(kThreads) void pn_fill_rows_kernel(float* __restrict__ out, const float* __restrict__ image, int B) {
     const size_t t = (size_t)blockIdx.x * kThreads + threadIdx.x;
@@ -843,7 +995,8 @@ struct Workspace {
     size_t bytes;
 };
 
-Workspace carve(void* base, int B, int nclouds, int N, int R) {
+// roff_entries: offsets per cloud - IQ_MAX_REGIONS + 1 for the narrow entry points (their layout since ABI 100), R + 1 for the wide one
+Workspace carve(void* base, int B, int nclouds, int N, int R, int roff_entries = IQ_MAX_REGIONS + 1) {
     Workspace w;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -852,7 +1005,7 @@ Workspace carve(void* base, int B, int nclouds, int N, int R) {
         return reinterpret_cast<char*>(base) + o;
     };
     w.sorted_pts = reinterpret_cast<uint16_t*>(take((size_t)nclouds * N * sizeof(uint16_t)));
-    w.roff = reinterpret_cast<int32_t*>(take((size_t)nclouds * (IQ_MAX_REGIONS + 1) * sizeof(int32_t)));
+    w.roff = reinterpret_cast<int32_t*>(take((size_t)nclouds * roff_entries * sizeof(int32_t)));
     w.rows_pre = reinterpret_cast<uint16_t*>(take((size_t)nclouds * (R + 1) * kRowCap * sizeof(uint16_t)));
     w.nrows_pre = reinterpret_cast<int32_t*>(take((size_t)nclouds * (R + 1) * sizeof(int32_t)));
     w.rows = reinterpret_cast<uint16_t*>(take((size_t)B * kRowCap * sizeof(uint16_t)));
@@ -895,38 +1048,54 @@ extern "C" int iq_pointnet_coalitions(const iq_pointnet_weights* w, const float*
                                       workspace_bytes, B, nclouds, N, R, channel_first, stream);
 }
 
-extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const float* clouds, const float* centers,
-                                          const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of,
-                                          float* logits, float* trans_feat_packed, int32_t* crt_points, void* workspace,
-                                          size_t workspace_bytes, int B, int nclouds, int N, int R,
-                                          int channel_first, iq_stream_t stream) {
-    IQ_REQUIRE(B >= 0 && nclouds >= 1, "iq_pointnet_coalitions: B=%d nclouds=%d", B, nclouds);
-    IQ_REQUIRE(w && clouds && region_id && (logits || B == 0), "iq_pointnet_coalitions: null pointer");
-    IQ_REQUIRE(N >= 1 && N <= kMaxN, "iq_pointnet_coalitions: N=%d not in [1,%d]", N, kMaxN);
-    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_REGIONS, "iq_pointnet_coalitions: R=%d not in [1,%d]", R, IQ_MAX_REGIONS);
-    IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == B, "iq_pointnet_coalitions: cloud_of required when 1 < nclouds != B");
+namespace {
+
+// The forward behind iq_pointnet_coalitions[_crt] (wide_words = 0: keep (B) masks, R <= IQ_MAX_REGIONS) and behind
+// iq_pointnet_coalitions_wide (wide_words = W: keep (B,W) rows).  Only the three kernels that read a mask differ; the chains, the
+// launch order and the heads are the same launches.
+int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const float* centers, const int32_t* region_id,
+                        const uint64_t* keep, int wide_words, const int32_t* cloud_of, float* logits, float* trans_feat_packed,
+                        int32_t* crt_points, void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int R,
+                        int channel_first, iq_stream_t stream) {
+    const char* who = wide_words ? "iq_pointnet_coalitions_wide" : "iq_pointnet_coalitions";   // the entry point a message names
+    IQ_REQUIRE(B >= 0 && nclouds >= 1, "%s: B=%d nclouds=%d", who, B, nclouds);
+    IQ_REQUIRE(w && clouds && region_id && (logits || B == 0), "%s: null pointer", who);
+    IQ_REQUIRE(N >= 1 && N <= kMaxN, "%s: N=%d not in [1,%d]", who, N, kMaxN);
+    const int max_regions = wide_words ? IQ_MAX_WIDE_REGIONS : IQ_MAX_REGIONS;
+    IQ_REQUIRE(R >= 1 && R <= max_regions, "%s: R=%d not in [1,%d]", who, R, max_regions);
+    IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == B, "%s: cloud_of required when 1 < nclouds != B", who);
     const int with_centre = centers ? 1 : 0;  // no centre = dense mode (nothing is ever masked)
-    IQ_REQUIRE(centers || !keep, "iq_pointnet_coalitions: keep masks need centers");
+    IQ_REQUIRE(centers || !keep, "%s: keep masks need centers", who);
     if (B == 0) return IQ_OK;
-    const size_t need = iq_pointnet_workspace_bytes(B, nclouds, N, R);
+    const size_t need = wide_words ? iq_pointnet_wide_workspace_bytes(B, nclouds, N, R) : iq_pointnet_workspace_bytes(B, nclouds, N, R);
     if (!workspace || workspace_bytes < need)
-        return iq::fail(IQ_EWORKSPACE, "iq_pointnet_coalitions: workspace %zu < %zu bytes", workspace_bytes, need);
-    Workspace ws = carve(workspace, B, nclouds, N, R);
+        return iq::fail(IQ_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    Workspace ws = wide_words ? carve(workspace, B, nclouds, N, R, R + 1) : carve(workspace, B, nclouds, N, R);
     hipStream_t st = iq::as_stream(stream);
     int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
 
-    hipLaunchKernelGGL(pn_prepare_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
-    if ((rc = iq::check_launch("pn_prepare_kernel"))) return rc;
     const int pre_items = nclouds * (R + with_centre);
-    hipLaunchKernelGGL(pn_rows_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
-                       ws.rows_pre, ws.nrows_pre, N, R, nclouds, with_centre, 1);
-    hipLaunchKernelGGL(pn_rows_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
-                       ws.nrows, N, R, nclouds, with_centre, 0);
-    if ((rc = iq::check_launch("pn_rows_kernel"))) return rc;
+    if (wide_words) {
+        hipLaunchKernelGGL(pn_prepare_wide_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
+        if ((rc = iq::check_launch("pn_prepare_wide_kernel"))) return rc;
+        hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
+                           ws.rows_pre, ws.nrows_pre, N, R, wide_words, nclouds, with_centre, 1);
+        hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
+                           ws.nrows, N, R, wide_words, nclouds, with_centre, 0);
+        if ((rc = iq::check_launch("pn_rows_wide_kernel"))) return rc;
+    } else {
+        hipLaunchKernelGGL(pn_prepare_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
+        if ((rc = iq::check_launch("pn_prepare_kernel"))) return rc;
+        hipLaunchKernelGGL(pn_rows_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
+                           ws.rows_pre, ws.nrows_pre, N, R, nclouds, with_centre, 1);
+        hipLaunchKernelGGL(pn_rows_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
+                           ws.nrows, N, R, nclouds, with_centre, 0);
+        if ((rc = iq::check_launch("pn_rows_kernel"))) return rc;
+    }
     // launch order of the coalition chains: most rows first, so the grid drains evenly
     if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "iq_pointnet_coalitions: memset failed");
+        return iq::fail(IQ_ELAUNCH, "%s: memset failed", who);
     hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
                        ws.bin_of, ws.hist, B);
     hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
@@ -961,9 +1130,13 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
     }
     if ((rc = iq::check_launch("pn_chain_kernel<prepool>"))) return rc;
 
-    hipLaunchKernelGGL(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
-                       R, nclouds, with_centre);
-    if ((rc = iq::check_launch("pn_stn_gather_kernel"))) return rc;
+    if (wide_words)
+        hipLaunchKernelGGL(pn_stn_gather_wide_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
+                           R, wide_words, nclouds, with_centre);
+    else
+        hipLaunchKernelGGL(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
+                           R, nclouds, with_centre);
+    if ((rc = iq::check_launch(wide_words ? "pn_stn_gather_wide_kernel" : "pn_stn_gather_kernel"))) return rc;
     if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st))) return rc;
     if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st))) return rc;
     if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st))) return rc;
@@ -992,7 +1165,7 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
     } else {
         // feature_transform = False (models/pointnet.py:62-63,72-78): no feature STN.  The trunk multiplies by the packed
         // IDENTITY instead (fstn_fc3.b = iq_pack_fstn_fc3 of a zero layer): sum_k f[k] I[k][n] = f[n] + zeros, exact.
-        IQ_REQUIRE(w->fstn_fc3.b, "iq_pointnet_coalitions: without a feature STN, fstn_fc3.b must hold the packed identity");
+        IQ_REQUIRE(w->fstn_fc3.b, "%s: without a feature STN, fstn_fc3.b must hold the packed identity", who);
         hipLaunchKernelGGL(pn_fill_rows_kernel, dim3((unsigned)(((size_t)B * 1024 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                            tfp, w->fstn_fc3.b, B);
         if ((rc = iq::check_launch("pn_fill_rows_kernel"))) return rc;
@@ -1013,6 +1186,31 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
     if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st))) return rc;
     if ((rc = launch_linear(ws.h2, 256, w->cls_fc3, logits, w->cls_fc3.cout, B, 0, st))) return rc;
     return IQ_OK;
+}
+
+}  // namespace
+
+extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const float* clouds, const float* centers,
+                                          const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of,
+                                          float* logits, float* trans_feat_packed, int32_t* crt_points, void* workspace,
+                                          size_t workspace_bytes, int B, int nclouds, int N, int R,
+                                          int channel_first, iq_stream_t stream) {
+    return pointnet_coalitions(w, clouds, centers, region_id, keep, 0, cloud_of, logits, trans_feat_packed, crt_points, workspace,
+                               workspace_bytes, B, nclouds, N, R, channel_first, stream);
+}
+
+extern "C" size_t iq_pointnet_wide_workspace_bytes(int B, int nclouds, int N, int R) {
+    if (B < 0 || nclouds < 0 || N < 0 || R < 0) return 0;
+    return carve(nullptr, B, nclouds, N, R, R + 1).bytes;
+}
+
+extern "C" int iq_pointnet_coalitions_wide(const iq_pointnet_weights* w, const float* clouds, const float* centers,
+                                           const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of,
+                                           float* logits, float* trans_feat_packed, void* workspace, size_t workspace_bytes,
+                                           int B, int nclouds, int N, int R, int channel_first, iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_pointnet_coalitions_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
+    return pointnet_coalitions(w, clouds, centers, region_id, keep, (R + 63) / 64, cloud_of, logits, trans_feat_packed, nullptr,
+                               workspace, workspace_bytes, B, nclouds, N, R, channel_first, stream);
 }
 
 // ---- host-side packing of the feature-STN output layer (generic packing: iq_linear.hip) ------------

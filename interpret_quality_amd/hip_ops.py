@@ -305,6 +305,91 @@ def region_assign(cloud, fps_idx):
     return out
 
 
+# ---- wide coalitions: more than 64 regions, up to one region per point (include/iq.h, "Wide coalitions") ----------------------
+
+MAX_WIDE_REGIONS = 1024     # IQ_MAX_WIDE_REGIONS of include/iq.h (tests/test_wide_cpu.py compares the two)
+
+
+def wide_words(num_regions):
+    """Words per wide keep row: ceil(R / 64), after the range check every wide wrapper makes."""
+    r = int(num_regions)
+    if not 1 <= r <= MAX_WIDE_REGIONS:
+        raise _lib.IqError("num_regions=%d is outside [1, %d]" % (r, MAX_WIDE_REGIONS))
+    return (r + 63) // 64
+
+
+def _wide_keep(keep, num_regions):
+    w = wide_words(num_regions)
+    if keep.dim() != 2 or keep.shape[1] != w:
+        raise _lib.IqError("keep must be (B, %d) for %d regions, got %s" % (w, int(num_regions), tuple(keep.shape)))
+    return _dev(keep, torch.int64, "keep")
+
+
+def wide_masks_to_tensor(masks, device):
+    """(B,W) uint64 keep rows as an int64-typed device tensor (same bits)."""
+    arr = np.ascontiguousarray(np.asarray(masks, dtype=np.uint64))
+    if arr.ndim != 2:
+        raise _lib.IqError("wide masks must be (B,W), got %s" % (arr.shape,))
+    return torch.from_numpy(arr.view(np.int64)).to(device)
+
+
+def prefix_keep_masks_wide(orders):
+    """orders (S,R) i32 -> (S*(R+1), W) int64-typed keep rows of the prefix coalitions (iq_prefix_keep_masks_wide)."""
+    lib = _lib.load()
+    s, r = orders.shape
+    keep = torch.empty((s * (r + 1), wide_words(r)), dtype=torch.int64, device=orders.device)
+    _lib.check(lib.iq_prefix_keep_masks_wide(_dev(orders, torch.int32, "orders"), _p(keep), s, r, _stream()),
+               "iq_prefix_keep_masks_wide")
+    return keep
+
+
+def mask_coalitions_wide(cloud, region_id, keep, center, num_regions, channel_first=False):
+    """cloud (N,3) f32, region_id (N,) i32, keep (B,W) i64, center (3,) f32 -> (B,N,3) or (B,3,N) (iq_mask_coalitions_wide)."""
+    lib = _lib.load()
+    n = cloud.shape[0]
+    kp = _wide_keep(keep, num_regions)
+    b = keep.shape[0]
+    out = torch.empty((b, 3, n) if channel_first else (b, n, 3), dtype=torch.float32, device=cloud.device)
+    _lib.check(lib.iq_mask_coalitions_wide(_dev(cloud, torch.float32, "cloud"), _dev(region_id, torch.int32, "region_id"), kp,
+                                           _dev(center, torch.float32, "center"), _p(out), n, int(num_regions), b,
+                                           int(channel_first), _stream()), "iq_mask_coalitions_wide")
+    return out
+
+
+def region_assign_wide(cloud, fps_idx):
+    """cloud (N,3) f32, fps_idx (R,) i32 with R <= MAX_WIDE_REGIONS -> (N,) i32 region ids (iq_region_assign_wide)."""
+    lib = _lib.load()
+    n = cloud.shape[0]
+    r = fps_idx.shape[0]
+    wide_words(r)
+    out = torch.empty((n,), dtype=torch.int32, device=cloud.device)
+    _lib.check(lib.iq_region_assign_wide(_dev(cloud, torch.float32, "cloud"), _dev(fps_idx, torch.int32, "fps_idx"),
+                                         _p(out), n, r, _stream()), "iq_region_assign_wide")
+    return out
+
+
+def shapley_accum_wide(v, orders, snap_counts=None):
+    """shapley_accum for R <= MAX_WIDE_REGIONS: v (S*(R+1),) f32, orders (S,R) i32 -> (phi_sum (R,) f64, sv_rows (S,R) f64,
+    snaps or None)."""
+    lib = _lib.load()
+    s, r = orders.shape
+    wide_words(r)
+    dev = v.device
+    if v.numel() != s * (r + 1):
+        raise _lib.IqError("v holds %d rewards for %d permutations of %d regions" % (v.numel(), s, r))
+    sv_rows = torch.zeros((max(s, 1), r), dtype=torch.float64, device=dev)
+    phi = torch.empty((r,), dtype=torch.float64, device=dev)
+    snaps = counts = None
+    n_snap = 0
+    if snap_counts is not None and len(snap_counts) > 0:
+        counts = torch.tensor(list(snap_counts), dtype=torch.int32, device=dev)
+        n_snap = counts.numel()
+        snaps = torch.zeros((n_snap, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_shapley_accum_wide(_dev(v, torch.float32, "v"), _dev(orders, torch.int32, "orders"), _p(sv_rows),
+                                         _p(phi), _p(counts), n_snap, _p(snaps), r, s, _stream()), "iq_shapley_accum_wide")
+    return phi, sv_rows[:s], snaps
+
+
 def fps(xyz, npoint):
     """xyz (B,N,3) f32 -> (B,npoint) i32."""
     lib = _lib.load()

@@ -105,6 +105,29 @@ class PointNetEngine(Engine):
         out = (logits,) + ((tfp,) if return_trans_feat else ()) + ((crt,) if return_crt else ())
         return out if len(out) > 1 else logits
 
+    def wide_bytes(self, b, nc, n, r):
+        return self.lib.iq_pointnet_wide_workspace_bytes(b, nc, n, r)
+
+    def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None):
+        """One iq_pointnet_coalitions_wide launch: clouds (nc,N,3), centers (nc,3), region_id (nc,N) int32, keep (B,W) int64 rows of
+        W = ceil(num_regions / 64) words, cloud_of (B,) int32 or None -> logits (B, num_classes).  Unlike ``coalition_logits`` it
+        takes channel-last clouds only and returns neither the packed trans_feat nor crt_points (the C entry point has
+        channel_first and trans_feat_packed; no wide caller needs them), and centers and keep are required: the dense forward
+        goes through the narrow entry."""
+        r = int(num_regions)
+        w = hip_ops.wide_words(r)
+        check_coalition_args(clouds, centers, region_id, keep, cloud_of)
+        if keep.dim() != 2 or keep.shape[1] != w:
+            raise _lib.IqError("keep must be (B, %d) for %d regions, got %s" % (w, r, tuple(keep.shape)))
+        nc, n, b = clouds.shape[0], clouds.shape[1], keep.shape[0]
+        logits = self.new_logits(b)
+        ws = workspace.ensure(self, self.wide_bytes(b, nc, n, r))
+        rc = self.lib.iq_pointnet_coalitions_wide(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id),
+                                                  ptr(keep), ptr(cloud_of), ptr(logits), ptr(None), ptr(ws), ws.numel(),
+                                                  b, nc, n, r, 0, stream())
+        _lib.check(rc, "iq_pointnet_coalitions_wide")
+        return logits
+
     def forward(self, x):
         """Dense forward, x (B,3,N) -> (logits, trans_feat (B,64,64), crt_points (B,1024) int64)."""
         b, _, n = x.shape
@@ -159,3 +182,30 @@ class PointNetCls(EngineOwner, nn.Module):
         if validate:
             hip_ops.check_index_range(region_id, 0, int(num_regions), "region_id")
         return self.engine().coalition_logits(clouds, centers, region_id, keep, cloud_of, num_regions=num_regions)
+
+    max_wide_per_call = 1 << 16   # coalitions per wide launch: 2 GB of workspace at N = 1024; 1000 permutations of 1024 players are 16 launches
+
+    def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None, validate=True):
+        """Logits of B WIDE coalitions: ``keep`` (B, ceil(num_regions / 64)) int64 rows, num_regions up to
+        hip_ops.MAX_WIDE_REGIONS (one region per point included).  Launches of at most ``max_wide_per_call`` coalitions, fewer when
+        the free memory asks for it (workspace.run_in_steps, as CoalitionModel.split_launches does for the other families: only
+        ``keep`` and ``cloud_of`` are sliced); a coalition's logits do not depend on what else is in its launch."""
+        r = int(num_regions)
+        hip_ops.wide_words(r)
+        if validate:
+            hip_ops.check_index_range(region_id, 0, r, "region_id")
+        eng = self.engine()
+        nc, n, b = clouds.shape[0], clouds.shape[1], keep.shape[0]
+        if cloud_of is None and nc not in (1, b):
+            raise _lib.IqError("cloud_of is required when 1 < number of clouds != number of coalitions")
+        names = cloud_of
+
+        def call(lo, hi):
+            nonlocal names
+            if (lo, hi) == (0, b):
+                return eng.coalition_logits_wide(clouds, centers, region_id, keep, cloud_of, num_regions=r)
+            if names is None and nc == b:
+                names = torch.arange(b, dtype=torch.int32, device=keep.device)
+            return eng.coalition_logits_wide(clouds, centers, region_id, keep[lo:hi].contiguous(),
+                                             names[lo:hi].contiguous() if names is not None else None, num_regions=r)
+        return workspace.run_in_steps(eng, b, self.max_wide_per_call, lambda k: eng.wide_bytes(k, nc, n, r), call)
