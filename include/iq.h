@@ -55,8 +55,9 @@ enum {
  * takes clouds of up to IQ_MAX_POINTS points and PointConv of 64 and more.
  * 103: new entry points, no layout change (the standalone geometric ops: iq_index_points .. iq_density).
  * 104: new entry points, no layout change (exact games by full enumeration: iq_enum_keep_masks .. iq_exact_scratch_bytes).
- * 105: new entry points, no layout change (wide coalitions: iq_prefix_keep_masks_wide .. iq_pointnet_coalitions_wide). */
-#define IQ_ABI_VERSION 105
+ * 105: new entry points, no layout change (wide coalitions: iq_prefix_keep_masks_wide .. iq_pointnet_coalitions_wide).
+ * 106: new entry point, no layout change (iq_context_keep_masks_wide: the interaction stage of wide games). */
+#define IQ_ABI_VERSION 106
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -560,13 +561,22 @@ int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
  * points.  A WIDE coalition is a row of W = ceil(R / 64) uint64 words: bit (r & 63) of word (r >> 6) set = region r kept; bits
  * at or above R are ignored.  1 <= R <= IQ_MAX_WIDE_REGIONS.  Every entry point above keeps its R <= 64 check and its code;
  * for R <= 64 (W = 1) the entry points below give the same bits as their narrow twins.  The permutations of a wide game are
- * drawn on the host (final_shapley_value.py:59-72 as it stands: NumPy's global generator) - iq_sample_permutations stays narrow.
- * The interaction, smoothness and pose stages and the compact coalition paths of PointNet++ / DGCNN / PointConv have no wide
- * form: those families evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.
+ * and the contexts of its interaction stage are drawn on the host (final_shapley_value.py:59-72, final_gen_pair.py:18-43 as
+ * they stand: NumPy's global generator) - iq_sample_permutations stays narrow.  The multi-order interactions of a wide game need
+ * one wide entry point only, iq_context_keep_masks_wide: iq_reward and iq_interaction_reduce never see a mask.
+ * The smoothness and pose stages and the compact coalition paths of PointNet++ / DGCNN / PointConv have no wide form: those
+ * families evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.
  * ------------------------------------------------------------------------------------------- */
 
 /* tools/final_common.py:56-60 as wide masks: row s*(R+1) + i of keep keeps orders[s][0..i-1]; an entry outside [0, R) is ignored. */
 int iq_prefix_keep_masks_wide(const int32_t* orders /*S,R*/, uint64_t* keep /*S*(R+1),W*/, int S, int R, iq_stream_t stream);
+
+/* final_point_binary_interaction_logits.py:45-52 as wide masks (iq_context_keep_masks's rows): for pair p = (i, j) and its
+ * context c = contexts[p][c][0..m-1], rows 4(pC + c) + 0..3 of keep = S+{i,j}, S+{i}, S+{j}, S.  0 <= m <= R; contexts may be
+ * NULL when m = 0 (the empty context).  A pair or context entry outside [0, R) is ignored: no bit at or above R is ever set.
+ * For R <= 64 the words are iq_context_keep_masks's.  One wave per context: coalesced loads, one contiguous 32 W-byte store. */
+int iq_context_keep_masks_wide(const int32_t* pairs /*P,2*/, const int32_t* contexts /*P,C,m*/, uint64_t* keep /*4PC,W*/,
+                               int P, int C, int m, int R, iq_stream_t stream);
 
 /* iq_mask_coalitions for wide keep rows (tools/final_common.py:46-61 for arbitrary coalitions): out row b keeps the regions of
  * keep[b]; a point whose region id lies outside [0, R) is masked.  out (B,N,3) or (B,3,N); any 1 <= N <= IQ_MAX_POINTS. */

@@ -134,6 +134,7 @@ SIGNATURES = {
     "iq_exact_interactions": (_I, [_P, _I, _P, _I, _P, _P, _SZ, _P]),
     "iq_moebius": (_I, [_P, _I, _P, _P]),
     "iq_prefix_keep_masks_wide": (_I, [_P, _P, _I, _I, _P]),
+    "iq_context_keep_masks_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_mask_coalitions_wide": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_region_assign_wide": (_I, [_P, _P, _P, _I, _I, _P]),
     "iq_shapley_accum_wide": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
@@ -150,7 +151,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 105   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 106   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -4,7 +4,8 @@
 // R are ignored.  The four small kernels of the Shapley path in their wide form: prefix masks, masking, region assignment and the
 // per-region accumulation.  Each repeats the arithmetic of its narrow twin (iq_sample.hip, iq_mask.hip, iq_geom.hip,
 // iq_reward.hip) operation by operation - the twins' tables and grids are sized for 64 regions, nothing else differs - so for
-// R <= 64 the results are the twins' bits.  The fused PointNet path for wide masks is in iq_pointnet.hip.
+// R <= 64 the results are the twins' bits.  The (pair, context) masks of the interaction stage have the twin's rows and another
+// kernel shape: one wave per context.  The fused PointNet path for wide masks is in iq_pointnet.hip.
 #include "iq_common.h"
 #include "iq_sqdist.h"
 
@@ -36,6 +37,42 @@ __global__ __launch_bounds__(256) void prefix_keep_wide_kernel(const int32_t* __
         const int r = ord[j];
         if ((unsigned)r < (unsigned)R && (r >> 6) == w) m |= 1ull << (r & 63);   // an out-of-range entry is ignored
         out[(size_t)(j + 1) * W] = m;
+    }
+}
+
+// ---- (pair, context) masks: one wave per context ------------------------------------------------------------------------------
+// The narrow kernel gives a lane a whole context; at m up to R - 2 = 1022 that is a thousand dependent loads per lane, each lane on
+// a row of its own.  Here the 64 lanes of a wave stride over the m entries of ONE context (`contexts` is row-contiguous: coalesced),
+// OR their bits into the wave's W words in LDS (OR is order-independent: the words do not depend on the schedule), and lanes
+// 0 .. 4W-1 then store the four rows S+{i,j}, S+{i}, S+{j}, S as one contiguous run of 32 W <= 512 bytes.
+constexpr int kCtxPerWg = 4;   // waves of a workgroup, one context each
+
+__global__ __launch_bounds__(64 * kCtxPerWg) void context_keep_wide_kernel(const int32_t* __restrict__ pairs,
+                                                                           const int32_t* __restrict__ ctx,
+                                                                           uint64_t* __restrict__ keep, size_t PC, int C, int m, int R,
+                                                                           int W) {
+    __shared__ unsigned long long set_s[kCtxPerWg][kMaxW];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const size_t t = (size_t)blockIdx.x * kCtxPerWg + wave;     // (pair, context) index p*C + c
+    const bool live = t < PC;                                   // no early return: every wave reaches both barriers
+    if (lane < W) set_s[wave][lane] = 0ull;
+    __syncthreads();
+    if (live) {
+        const int32_t* row = ctx + t * m;
+        for (int j = lane; j < m; j += 64) {
+            const int r = row[j];
+            if ((unsigned)r < (unsigned)R) atomicOr(&set_s[wave][r >> 6], 1ull << (r & 63));   // an out-of-range entry is ignored
+        }
+    }
+    __syncthreads();
+    if (live && lane < 4 * W) {
+        const int q = lane / W, w = lane - q * W;               // row q of the four, word w of the row
+        const size_t p = t / C;
+        const int i = pairs[2 * p], j = pairs[2 * p + 1];
+        uint64_t v = set_s[wave][w];
+        if (q <= 1 && (unsigned)i < (unsigned)R && (i >> 6) == w) v |= 1ull << (i & 63);          // rows 0, 1 hold region i
+        if ((q & 1) == 0 && (unsigned)j < (unsigned)R && (j >> 6) == w) v |= 1ull << (j & 63);    // rows 0, 2 hold region j
+        keep[t * 4 * W + lane] = v;
     }
 }
 
@@ -176,6 +213,20 @@ extern "C" int iq_prefix_keep_masks_wide(const int32_t* orders, uint64_t* keep, 
     hipLaunchKernelGGL(prefix_keep_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, iq::as_stream(stream), orders, keep,
                        S, R, W);
     return iq::check_launch("prefix_keep_wide_kernel");
+}
+
+extern "C" int iq_context_keep_masks_wide(const int32_t* pairs, const int32_t* contexts, uint64_t* keep, int P, int C, int m, int R,
+                                          iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_context_keep_masks_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
+    IQ_REQUIRE(P >= 0 && C >= 0 && m >= 0 && m <= R, "iq_context_keep_masks_wide: P=%d C=%d m=%d R=%d", P, C, m, R);
+    const size_t n = (size_t)P * C;
+    if (n == 0) return IQ_OK;
+    IQ_REQUIRE(pairs && keep && (contexts || m == 0), "iq_context_keep_masks_wide: null pointer");
+    const size_t grid = (n + kCtxPerWg - 1) / kCtxPerWg;
+    IQ_REQUIRE(grid <= 0x7fffffffu, "iq_context_keep_masks_wide: P=%d C=%d is too large", P, C);
+    hipLaunchKernelGGL(context_keep_wide_kernel, dim3((unsigned)grid), dim3(64 * kCtxPerWg), 0, iq::as_stream(stream), pairs, contexts,
+                       keep, n, C, m, R, words_of(R));
+    return iq::check_launch("context_keep_wide_kernel");
 }
 
 extern "C" int iq_mask_coalitions_wide(const float* cloud, const int32_t* region_id, const uint64_t* keep, const float* center,

@@ -343,6 +343,23 @@ def prefix_keep_masks_wide(orders):
     return keep
 
 
+def context_keep_masks_wide(pairs, contexts, num_regions):
+    """pairs (P,2) i32, contexts (P,C,m) i32, 0 <= m <= R -> (4*P*C, W) int64-typed keep rows S+{i,j}, S+{i}, S+{j}, S per context
+    (iq_context_keep_masks_wide; final_point_binary_interaction_logits.py:45-52).  An entry outside [0, R) is ignored."""
+    lib = _lib.load()
+    r = int(num_regions)
+    w = wide_words(r)
+    _shape(pairs, "pairs", None, 2)
+    p, c, m = _shape(contexts, "contexts", pairs.shape[0], None, None)
+    if m > r:
+        raise _lib.IqError("contexts name %d regions each, the game has %d" % (m, r))
+    keep = torch.empty((4 * p * c, w), dtype=torch.int64, device=pairs.device)
+    _lib.check(lib.iq_context_keep_masks_wide(_dev(pairs, torch.int32, "pairs"),
+                                              _dev(contexts, torch.int32, "contexts") if contexts.numel() else ctypes.c_void_p(0),
+                                              _p(keep), p, c, m, r, _stream()), "iq_context_keep_masks_wide")
+    return keep
+
+
 def mask_coalitions_wide(cloud, region_id, keep, center, num_regions, channel_first=False):
     """cloud (N,3) f32, region_id (N,) i32, keep (B,W) i64, center (3,) f32 -> (B,N,3) or (B,3,N) (iq_mask_coalitions_wide)."""
     lib = _lib.load()

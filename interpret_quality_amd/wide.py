@@ -1,4 +1,4 @@
-"""Wide games: Shapley values over more than 64 regions, up to one region per point.
+"""Wide games: Shapley values and multi-order interactions over more than 64 regions, up to one region per point.
 
 Everywhere else in this package a coalition is one uint64 bit mask, so a game has at most 64 regions.  In the reference
 NUM_REGIONS is a constant one edits (tools/final_util.py:20-22) and mask_data_batch, cal_region_id and the sampling loop work
@@ -7,12 +7,18 @@ for any region count up to the number of points.  Here a WIDE coalition is a row
 
 PointNet evaluates wide coalitions fused (iq_pointnet_coalitions_wide: no masked cloud is ever written).  Every other family
 runs iq_mask_coalitions_wide in batches into its own dense forward, the route final_common.materialised_logits takes: correct,
-at dense-forward speed.  The interaction, smoothness and pose stages have no wide form.
+at dense-forward speed.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
+and the multi-order interactions of sampled (pair, context) coalitions (``gen_context``, ``interaction_logits``, ``interactions``,
+wide_interaction_stage.py).  The smoothness and pose stages have none.
 """
+import itertools
+
 import numpy as np
 import torch
+from scipy.special import comb
 
-from . import final_common, hip_ops, work
+from . import dist as iqdist
+from . import final_common, gen_pair, hip_ops, interaction, work
 from ._lib import IqError
 
 MAX_REGIONS = hip_ops.MAX_WIDE_REGIONS
@@ -102,3 +108,98 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
     total, rows, snaps = hip_ops.shapley_accum_wide(v, orders_dev, snap_counts=counts)
     snaps = snaps.cpu().numpy() if snaps is not None else np.zeros((0, r))
     return {c: snaps[k] for k, c in enumerate(counts)}, rows.cpu().numpy(), total.cpu().numpy()
+
+
+# ---- multi-order interactions: final_gen_pair.py, final_point_binary_interaction_logits.py and final_cal_interactions.py ---------
+
+gen_pair_random = gen_pair.gen_pair_random            # final_gen_pair.py:288-300 does not depend on the region count
+interactions = interaction.compute_order_interaction  # final_cal_interactions.py:14-37: reward and reduction never see a mask
+
+
+def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=np.int64):
+    """``gen_context`` one ratio at a time: a generator of (P, C, m) arrays of ``dtype`` (at R = 1024 one ratio's contexts are up
+    to 30 000 x 1022 entries: a caller that saves them need not hold thirteen of them)."""
+    r, cmax = int(num_regions), int(num_save_context_max)
+    hip_ops.wide_words(r)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    regions = np.arange(r)
+    for ratio in ratios:
+        m = int((r - 2) * ratio)
+        sampled = comb(r - 2, m) > cmax
+        per_pair = []
+        for i, j in pairs:
+            rest = regions[(regions != i) & (regions != j)]        # ascending, as the reference's all_S
+            if sampled:
+                # np.random.choice(rest, m, replace=False) on the legacy generator: the head of a fresh permutation
+                per_pair.append(np.array([rest[np.random.permutation(rest.size)[:m]] for _ in range(cmax)], dtype=dtype).reshape(cmax, m))
+            else:
+                listed = list(itertools.combinations(rest.tolist(), m))
+                per_pair.append(np.array(listed, dtype=dtype).reshape(len(listed), m))
+        yield np.stack(per_pair) if per_pair else np.zeros((0, 0, m), dtype=dtype)
+
+
+def gen_context(pairs, num_regions, ratios, num_save_context_max):
+    """final_gen_pair.py:18-43 for any region count: for each ratio (in order) the (P, C, m) int64 contexts of the (P,2) ``pairs``,
+    m = int((R-2)*ratio) regions out of the R-2 that are not in the pair - ``num_save_context_max`` sampled ones per pair when
+    C(R-2, m) exceeds that number, otherwise all combinations.  The draws come from NumPy's GLOBAL generator on the host in the
+    reference's order (ratio, pair, context), each as rest[np.random.permutation(R-2)[:m]] - what the reference's
+    np.random.choice(rest, m, replace=False) does on the legacy generator, without its per-call overhead: 390 000 draws at
+    R = 1024 take seconds.  The device sampler (gen_pair.gen_context with ``args.device``) stays a 64-region kernel."""
+    return list(iter_contexts(pairs, num_regions, ratios, num_save_context_max))
+
+
+def _pairs_contexts(pairs, contexts, r):
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    ctx = np.asarray(contexts)
+    if ctx.ndim != 3 or ctx.shape[0] != pairs.shape[0] or ctx.shape[2] > r:
+        raise IqError("contexts must be (%d, C, m <= %d), got %s" % (pairs.shape[0], r, ctx.shape))
+    return pairs, ctx
+
+
+def context_keep_masks(pairs, contexts, num_regions):
+    """(P,2) pairs and (P,C,m) contexts -> (4*P*C, W) uint64 keep rows on the host, rows 4k .. 4k+3 = S+{i,j}, S+{i}, S+{j}, S
+    (final_point_binary_interaction_logits.py:45-52).  A pair or context entry outside [0, R) is ignored, as
+    iq_context_keep_masks_wide ignores it; for R <= 64 the words are interaction.context_keep_masks's."""
+    r = int(num_regions)
+    w = hip_ops.wide_words(r)
+    pairs, ctx = _pairs_contexts(pairs, contexts, r)
+    p, c = ctx.shape[0], ctx.shape[1]
+    ctx = ctx.astype(np.int64)
+
+    def words(idx):     # (..., k) region ids -> (..., W) words of the set
+        valid = (idx >= 0) & (idx < r)
+        word = np.where(valid, idx >> 6, -1)
+        bit = np.left_shift(np.uint64(1), (idx & 63).astype(np.uint64))
+        out = np.zeros(idx.shape[:-1] + (w,), dtype=np.uint64)
+        if idx.shape[-1]:
+            for k in range(w):
+                out[..., k] = np.bitwise_or.reduce(np.where(word == k, bit, np.uint64(0)), axis=-1)
+        return out
+
+    s = words(ctx)                                        # (P,C,W)
+    bi, bj = words(pairs[:, :1])[:, None, :], words(pairs[:, 1:])[:, None, :]
+    return np.stack([s | bi | bj, s | bi, s | bj, s], axis=2).reshape(4 * p * c, w)
+
+
+def interaction_logits(model, data, region_id, pairs, contexts, args):
+    """final_point_binary_interaction_logits.py:15-70 for a wide game: the logits of the four coalitions S+{i,j}, S+{i}, S+{j}, S
+    of every (pair, context) of ONE ratio on one cloud ``data`` (1,N,3), perturbed or not (masked points collapse onto
+    torch.mean(data, dim=1)) -> (P, 4C, K) float32.  ``pairs`` (P,2), ``contexts`` (P,C,m) host arrays of any integer type;
+    ``args``: model, num_regions.  The contexts go to the device as int32 (at most about 110 MB at R = 1024), the keep rows are
+    built there (iq_context_keep_masks_wide) and evaluated as ``coalition_logits`` evaluates them: PointNet fused, in launches of
+    at most 2^16 coalitions, every other family through its dense forward.  Sampled contexts of more than 64 regions do not
+    coincide: no de-duplication (interaction.compute_order_interaction_logits, the narrow stage, evaluates distinct sets once)."""
+    dev = data.device
+    r = int(args.num_regions)
+    hip_ops.wide_words(r)
+    pairs, ctx = _pairs_contexts(pairs, contexts, r)
+    hip_ops.check_host_indices(pairs, 0, r, "pairs")
+    hip_ops.check_host_indices(ctx, 0, r, "contexts")
+    p, c = ctx.shape[0], ctx.shape[1]
+    if p * c == 0:
+        return torch.zeros((p, 4 * c, iqdist.num_classes_of(model)), dtype=torch.float32, device=dev)
+    rid = hip_ops.region_ids(region_id, dev, r)
+    with torch.no_grad():
+        keep = hip_ops.context_keep_masks_wide(hip_ops.as_i32(pairs, dev), hip_ops.as_i32(ctx, dev), r)
+        logits = _logits(model, data, rid, keep, r)
+    return logits.reshape(p, 4 * c, -1)

@@ -1,0 +1,145 @@
+"""final_wide_interaction.py - the multi-order interactions (scripts/exp_interaction.sh: final_gen_pair.py,
+final_point_binary_interaction_logits.py, final_cal_interactions.py) for more than 64 regions, up to one region per point.
+
+For every cloud in the interaction selection of the dataset it reads ``region_id.npy`` from the experiment folder that
+final_wide_shapley.py wrote for ``--num_regions`` and writes, under the reference's names and layout:
+
+    interaction_seed<k>/region_pair_list.npy                        (num_pairs_random, 2) int64
+    interaction_seed<k>/ratio<r>_context_list.npy                   (P, C, m) int16, m = int((R-2) * ratio)
+    interaction_seed<k>/normal/ratio<r>_all_logits.pt               (P, 4C, K) float32
+    interaction_seed<k>/normal/ratio<r>_<output_type>_interaction.npy   (P, C) float64
+
+and, with ``--transform_params FILE.npy`` (the angle tuple or translation vector of ``--mode``), the same pairs and contexts on the
+perturbed cloud into ``interaction_seed<k>/<mode>_adv/`` (with transform_params.npy and pred_labels.npy, as final_gen_pair.py
+leaves them there) - how the normal pose is compared with an adversarial one until the pose sweeps have a wide form.
+
+Deviations from the reference, both for size: the context lists are saved in the narrowest integer type that holds R (int16; at
+R = 1024 the reference's int64 would be 1.4 GB per cloud - nothing but this driver reads these files), and pairs and contexts are
+saved for the selected clouds only.  The random stream is final_gen_pair.py's for ``--seed <k>``: NumPy's global generator, seeded
+with ``--gen_pair_seed``, draws the pairs of ALL clouds first and then the contexts of all clouds, selected or not.  Not here
+(DESIGN.md 5e): check_adv_success and the single-region folders (they need the wide pose sweeps), sharding over ranks - under
+several ranks rank 0 does the work and the others wait.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import dist as iqdist
+from . import gen_pair, interaction, wide
+from .final_util import get_folder_name_list, load_model, mkdir, set_random
+from .pose_sweep import rotate_xyz, translate_pc
+from .shapley_stage import data_loader, finish_args
+from .wide_stage import DEFAULT_REGIONS, MIN_REGIONS
+
+CONTEXT_DTYPE = np.int16      # holds every region id of a wide game (wide.MAX_REGIONS = 1024)
+
+
+def _folder(args, name):
+    return args.exp_folder + "%s/" % name + "interaction_seed%d/" % args.gen_pair_seed
+
+
+def _wanted(args, names):
+    """Indices of the clouds this call computes: the interaction selection, within ``args.cloud_subset`` and the loader."""
+    return [i for i in interaction._selected(args) if i < len(names) and iqdist.cloud_selected(args, i)]
+
+
+def draw(args, names, wanted):
+    """The pairs of all clouds, then the contexts of all clouds (gen_pair.run's order); saved for the clouds of ``wanted``."""
+    pairs = [wide.gen_pair_random(args) for _ in names]
+    last = max(wanted)           # nothing later in this call reads the stream: the contexts of the clouds after it are not drawn
+    for i in range(last + 1):
+        folder = _folder(args, names[i])
+        if i in wanted:
+            mkdir(folder + "normal/")
+            np.save(folder + "region_pair_list.npy", pairs[i])
+        contexts = wide.iter_contexts(pairs[i], args.num_regions, args.ratio, args.num_save_context_max, dtype=CONTEXT_DTYPE)
+        for ratio, context_list in zip(args.ratio, contexts):      # one ratio resident at a time
+            if i in wanted:
+                np.save(folder + "ratio%d_context_list.npy" % int(ratio * 100), context_list)
+
+
+def evaluate(model, data, lbl, region_id, folder, save_path, args):
+    """save_logits_all_orders + cal_interaction_all_orders (final_point_binary_interaction_logits.py:73-80,
+    final_cal_interactions.py:40-46) for one pose of one cloud."""
+    mkdir(save_path)
+    pairs = np.load(folder + "region_pair_list.npy")
+    for ratio in args.ratio:
+        tag = int(ratio * 100)
+        context_list = np.load(folder + "ratio%d_context_list.npy" % tag)
+        all_logits = wide.interaction_logits(model, data, region_id, pairs, context_list, args)
+        torch.save(all_logits, save_path + "ratio%d_all_logits.pt" % tag)
+        np.save(save_path + "ratio%d_%s_interaction.npy" % (tag, args.output_type), wide.interactions(all_logits, lbl, args))
+        print("\tratio: %f, logits %s" % (ratio, tuple(all_logits.shape)))
+
+
+def run(args):
+    names = get_folder_name_list(args)
+    wanted = _wanted(args, names)
+    if not wanted:
+        return
+    for i in wanted:
+        path = args.exp_folder + "%s/region_id.npy" % names[i]
+        if not os.path.exists(path):
+            raise SystemExit("%s not found: run final_wide_shapley.py --num_regions %d first" % (path, args.num_regions))
+    model = load_model(args)
+    disturb_fn = translate_pc if args.mode == "trans" else rotate_xyz
+    params = np.load(args.transform_params) if args.transform_params else None
+    set_random(args.gen_pair_seed)        # final_gen_pair.py --seed <k> writes interaction_seed<k>/
+    draw(args, names, wanted)
+    with torch.no_grad():
+        for i, (data, lbl) in enumerate(data_loader(args)):
+            if i > max(wanted):
+                break
+            if i not in wanted:
+                continue
+            print("======= sample %s =========" % names[i])
+            data, lbl = data.to(args.device), lbl.to(args.device)
+            folder = _folder(args, names[i])
+            region_id = np.load(args.exp_folder + "%s/region_id.npy" % names[i])
+            print("##### normal pose")
+            evaluate(model, data, lbl, region_id, folder, folder + "normal/", args)
+            if params is None:
+                continue
+            print("##### %s pose of --transform_params" % args.mode)
+            adv = folder + "%s_adv/" % args.mode
+            mkdir(adv)
+            np.save(adv + "transform_params.npy", params)
+            gen_pair.gen_pred_label(model, data, lbl, disturb_fn, adv, args)
+            pred = torch.tensor([np.load(adv + "pred_labels.npy")[1]], dtype=torch.long, device=args.device)
+            data_disturb = disturb_fn(data, torch.from_numpy(params.astype(np.float32)).to(args.device))
+            evaluate(model, data_disturb, lbl if args.output_type == "gt" else pred, region_id, folder, adv, args)
+
+
+def make_args(argv=None):
+    parser = interaction.build_parser(with_cal_flags=True)
+    parser.set_defaults(device_id=0)
+    parser.add_argument("--num_regions", type=int, default=DEFAULT_REGIONS)     # additive
+    parser.add_argument("--transform_params", type=str, default=None, metavar="FILE.npy",
+                        help="the --mode parameters of one pose: the same pairs and contexts are also evaluated there")
+    args = parser.parse_args(argv)
+    if not MIN_REGIONS <= args.num_regions <= wide.MAX_REGIONS:
+        parser.error("--num_regions %d: the wide stage takes %d .. %d regions (final_gen_pair.py and "
+                     "final_point_binary_interaction_logits.py: up to 64)" % (args.num_regions, MIN_REGIONS, wide.MAX_REGIONS))
+    if args.mode not in ("rotate", "trans"):
+        parser.error("--mode %s: rotate or trans" % args.mode)
+    if args.num_save_context_max < 1 or args.num_pairs_random < 1:
+        parser.error("--num_save_context_max and --num_pairs_random must be at least 1")
+    return args
+
+
+@iqdist.record
+def main(argv=None):
+    args = make_args(argv)
+    finish_args(args)
+    if args.num_regions > args.num_points:
+        raise SystemExit("--num_regions %d exceeds the %d points of a cloud" % (args.num_regions, args.num_points))
+    if iqdist.rank() == 0:
+        run(args)
+    else:
+        print("rank %d: the wide stage runs on rank 0 only; waiting" % iqdist.rank())
+    iqdist.barrier()
+
+
+if __name__ == "__main__":
+    main()

@@ -9,7 +9,8 @@ derives from ``--num_regions`` - so a run never overwrites a 32-region run:
 The permutations come from NumPy's global generator on the host, exactly as the reference's generate_all_orders draws them
 (final_shapley_value.py:59-72); the device sampler of stage 1 stays a 64-region kernel.  The FPS centres go to their own
 fps_<dataset>_<N>_<R>_index_final30.npy.  Single process: under several ranks rank 0 does the work and the others wait.  The
-interaction, smoothness and pose stages have no wide form.
+multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py).  The smoothness and pose
+stages have no wide form.
 """
 import os
 

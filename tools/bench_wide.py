@@ -3,6 +3,7 @@
 
     python tools/bench_wide.py [--out profiles/wide_regions.json] [--repeats 5] [--perms 1000] [--regions 128 256 1024]
     python tools/bench_wide.py --profile-step 1024      # one warmed step only: the program for rocprofv3 --kernel-trace --stats
+    python tools/bench_wide.py --interaction            # the interaction stage only, into the "interaction" key of --out
 
 1. Wide against narrow at R = 32 (the headline's workload: 1000 permutations, 33 000 coalitions) and R = 64: the SAME coalitions
    through iq_pointnet_coalitions (the yardstick: untouched code) and iq_pointnet_coalitions_wide, alternated in one process,
@@ -10,6 +11,13 @@
    spread (max - min over median) of each side - a ratio inside the spread is no difference.  The logits are compared bitwise.
 2. Coalitions/s of the wide path at R = 128, 256 and 1024 (one cloud, N = 1024, ``perms`` permutations' prefix coalitions, masks
    built on the device, launches as wide.shapley issues them), ``repeats`` runs each, median and spread.
+
+3. ``--interaction``: (a) one ratio of the wide interaction stage as final_wide_interaction.py issues it - 300 pairs x 100 contexts
+   at ratio 0.5 (120 000 coalitions) through wide.interaction_logits at R = 128 and R = 1024, contexts drawn by wide.gen_context:
+   coalitions/s, and the seconds of the mask kernel alone; (b) the wide route against the narrow stage
+   (interaction.compute_order_interaction_logits: untouched code) on identical pairs and contexts at R = 64, alternated in one
+   process, ratio and spread as in 1.  Both routes hand the chain kernels the same row lists, so the expectation is a ratio inside
+   the spread (the narrow route also de-duplicates on the host; sampled contexts of 31 regions out of 62 do not repeat).
 
 Times are host clocks around work that ends in a device synchronise.  Kernel shares come from a separate run under the profiler
 (--profile-step): tracing slows the host, so no rate is taken there."""
@@ -105,6 +113,70 @@ def wide_rate(model, r, perms, repeats, dev):
     return out
 
 
+def _interaction_inputs(r, pairs_n, ctx_n, ratio):
+    from interpret_quality_amd import wide
+    np.random.seed(1)
+    pairs = wide.gen_pair_random(argparse.Namespace(num_regions=r, num_pairs_random=pairs_n))
+    return pairs, wide.gen_context(pairs, r, [ratio], ctx_n)[0]
+
+
+def _interaction_args(r):
+    return argparse.Namespace(model="pointnet", softmax_type="modified", num_points=1024, num_regions=r, interaction_batch_size=25)
+
+
+def interaction_rate(model, r, repeats, dev, pairs_n=300, ctx_n=100, ratio=0.5):
+    from interpret_quality_amd import wide
+    data, _, rid = _setup(r, dev)
+    rid_np = rid[0].cpu().numpy().astype(np.int64)
+    pairs, ctx = _interaction_inputs(r, pairs_n, ctx_n, ratio)
+    args = _interaction_args(r)
+    run = lambda: wide.interaction_logits(model, data, rid_np, pairs, ctx, args)      # noqa: E731
+    run()
+    times = [_clock(run)[0] for _ in range(repeats)]
+    pd, cd = hip_ops.as_i32(pairs, dev), hip_ops.as_i32(ctx, dev)
+    masks = lambda: hip_ops.context_keep_masks_wide(pd, cd, r)                        # noqa: E731
+    masks()
+    mask_times = [_clock(masks)[0] for _ in range(repeats)]
+    b = 4 * ctx.shape[0] * ctx.shape[1]
+    out = {"regions": r, "pairs": int(ctx.shape[0]), "contexts": int(ctx.shape[1]), "context_regions": int(ctx.shape[2]), "coalitions": b,
+           "seconds_per_ratio": statistics.median(times), "mask_kernel_seconds": statistics.median(mask_times)}
+    out.update(_summary([b / t for t in times]))
+    return out
+
+
+def interaction_wide_vs_narrow(model, repeats, dev, r=64, pairs_n=300, ctx_n=100, ratio=0.5):
+    import contextlib
+    import io
+    from interpret_quality_amd import interaction, wide
+    data, _, rid = _setup(r, dev)
+    rid_np = rid[0].cpu().numpy().astype(np.int64)
+    pairs, ctx = _interaction_inputs(r, pairs_n, ctx_n, ratio)
+    args = _interaction_args(r)
+
+    def narrow():
+        with contextlib.redirect_stdout(io.StringIO()):
+            return interaction.compute_order_interaction_logits(model, data, rid_np, pairs, ctx, args)
+    wide_run = lambda: wide.interaction_logits(model, data, rid_np, pairs, ctx, args)  # noqa: E731
+    same = bool(torch.equal(narrow(), wide_run()))      # warm-up of both, and the results must not differ
+    tn, tw = [], []
+    for _ in range(repeats):
+        tn.append(_clock(narrow)[0])
+        tw.append(_clock(wide_run)[0])
+    b = 4 * ctx.shape[0] * ctx.shape[1]
+    out = {"regions": r, "coalitions": b, "bitwise_equal": same, "narrow": _summary([b / t for t in tn]),
+           "wide": _summary([b / t for t in tw])}
+    out["ratio_wide_over_narrow"] = out["wide"]["median"] / out["narrow"]["median"]
+    out["ratio_inside_spread"] = abs(out["ratio_wide_over_narrow"] - 1.0) <= max(out["narrow"]["spread"], out["wide"]["spread"])
+    return out
+
+
+def _write(path, res):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "wide_regions.json"))
@@ -113,6 +185,8 @@ def main(argv=None):
     ap.add_argument("--regions", type=int, nargs="+", default=[128, 256, 1024])
     ap.add_argument("--profile-step", type=int, default=0, metavar="R",
                     help="run one warmed step at R regions and exit (the program to put under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--interaction", action="store_true",
+                    help="time the interaction stage only (legs 3a, 3b) and put it under \"interaction\" in --out, keeping what is there")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_wide.py needs a GPU: a time taken elsewhere says nothing about the MI355X")
@@ -124,13 +198,17 @@ def main(argv=None):
         t, _ = _clock(run)
         print(json.dumps({"profile_step_regions": args.profile_step, "coalitions": b, "runs": 2, "seconds_under_profiler": t}))
         return
+    if args.interaction:
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        res["interaction"] = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats,
+                              "wide": [interaction_rate(model, r, args.repeats, dev) for r in (128, 1024)],
+                              "wide_vs_narrow": interaction_wide_vs_narrow(model, args.repeats, dev)}
+        _write(args.out, res)
+        return
     res = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats,
            "wide_vs_narrow": [wide_vs_narrow(model, r, 1000, args.repeats, dev) for r in (32, 64)],
            "wide": [wide_rate(model, r, args.perms, args.repeats, dev) for r in args.regions]}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print(json.dumps(res))
+    _write(args.out, res)
 
 
 if __name__ == "__main__":
