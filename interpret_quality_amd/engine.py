@@ -5,8 +5,6 @@ A family module keeps what is its own: the architecture constants, the walk over
 (with its own rule for which layers are ALSO packed as three bf16 terms - the rule decides which kernel a layer runs on), the
 workspace-size and launch calls of the library, and its specials.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -74,12 +72,7 @@ class Packer:
         return _lib.DenseLayer(wt.data_ptr(), bt.data_ptr(), cin, cout, self.bf3(w32) if bf3 else None)
 
 
-def ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+ptr, stream = hip_ops._p, hip_ops._stream      # tensor or None -> void pointer; the current stream
 
 
 def check_coalition_args(clouds, centers, region_id, keep, cloud_of, masked=True):
@@ -179,25 +172,35 @@ class CoalitionModel(EngineOwner):
         pass False."""
         if validate:
             hip_ops.check_index_range(region_id, 0, int(num_regions) if num_regions else 64, "region_id")
-        eng = self.engine()
-        if cloud_of is None and clouds.shape[0] not in (1, keep.shape[0]):
-            raise _lib.IqError("cloud_of is required when 1 < number of clouds != number of coalitions")
-        return self.split_launches(eng, clouds, centers, region_id, keep, cloud_of)
+        return self.split_launches(self.engine(), clouds, centers, region_id, keep, cloud_of)
 
     def split_launches(self, eng, clouds, centers, region_id, keep, cloud_of, *extra):
-        """One engine launch if the workspace fits, several otherwise.  Every launch gets the caller's own ``clouds``, ``centers``
-        and ``region_id`` tensors (an engine may key a cache on their identity) and the same ``extra``; only ``keep`` and
-        ``cloud_of`` are sliced."""
-        nc, n, b = clouds.shape[0], clouds.shape[1], keep.shape[0]
-        names = cloud_of
+        """``split_launches`` over eng.coalition_logits, at most ``max_clouds_per_call`` coalitions a launch; every launch gets the
+        same ``extra``."""
+        nc, n = clouds.shape[0], clouds.shape[1]
+        return split_launches(eng, lambda k, names: eng.coalition_logits(clouds, centers, region_id, k, names, *extra),
+                              lambda k: eng.coalition_bytes(k, nc, n), self.max_clouds_per_call, clouds, keep, cloud_of)
 
-        def call(lo, hi):
-            nonlocal names
-            if (lo, hi) == (0, b):
-                return eng.coalition_logits(clouds, centers, region_id, keep, cloud_of, *extra)
-            if names is None and nc == b:      # one cloud per coalition, split over launches: name each launch's clouds
-                names = torch.arange(b, dtype=torch.int32, device=keep.device)
-            return eng.coalition_logits(clouds, centers, region_id, keep[lo:hi].contiguous(),
-                                        names[lo:hi].contiguous() if names is not None else None, *extra)
-        # the launch size comes from the memory that is free now (workspace.py), at most max_clouds_per_call
-        return workspace.run_in_steps(eng, b, self.max_clouds_per_call, lambda k: eng.coalition_bytes(k, nc, n), call)
+
+def check_cloud_of(clouds, keep, cloud_of):
+    if cloud_of is None and clouds.shape[0] not in (1, keep.shape[0]):
+        raise _lib.IqError("cloud_of is required when 1 < number of clouds != number of coalitions")
+
+
+def split_launches(eng, launch_fn, bytes_fn, cap, clouds, keep, cloud_of):
+    """``launch_fn(keep, cloud_of) -> logits`` in one engine launch if the workspace fits, several otherwise: the launch size
+    comes from the memory that is free now (workspace.run_in_steps, ``bytes_fn(coalitions)``), at most ``cap``.  Only ``keep`` and
+    ``cloud_of`` are sliced - ``launch_fn`` passes the caller's own ``clouds``, ``centers`` and ``region_id`` tensors on every launch
+    (an engine may key a cache on their identity)."""
+    check_cloud_of(clouds, keep, cloud_of)
+    nc, b = clouds.shape[0], keep.shape[0]
+    names = cloud_of
+
+    def call(lo, hi):
+        nonlocal names
+        if (lo, hi) == (0, b):
+            return launch_fn(keep, cloud_of)
+        if names is None and nc == b:      # one cloud per coalition, split over launches: name each launch's clouds
+            names = torch.arange(b, dtype=torch.int32, device=keep.device)
+        return launch_fn(keep[lo:hi].contiguous(), names[lo:hi].contiguous() if names is not None else None)
+    return workspace.run_in_steps(eng, b, cap, bytes_fn, call)

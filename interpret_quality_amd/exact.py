@@ -94,10 +94,7 @@ def sampled_from_table(v, orders, counts):
         raise IqError("orders of %d players against a table of %d coalitions" % (n, v.numel()))
     idx = final_common.prefix_keep_masks(orders, n).astype(np.int64)
     rewards = v.index_select(0, torch.from_numpy(idx).to(v.device)).contiguous()
-    counts = [c for c in counts if c <= s]
-    _, rows, snaps = hip_ops.shapley_accum(rewards, hip_ops.as_i32(orders, v.device), snap_counts=counts)
-    snaps = snaps.cpu().numpy() if snaps is not None else np.zeros((0, n))
-    return {c: snaps[k] for k, c in enumerate(counts)}, rows.cpu().numpy()
+    return hip_ops.shapley_snapshots(rewards, hip_ops.as_i32(orders, v.device), counts)[:2]
 
 
 def sampling_error(phi, snaps, rows):

@@ -49,11 +49,7 @@ def mask_data_batch(masked_data, center, orders, region_id, args):
 def prefix_keep_masks(orders, num_regions):
     """(S,R) permutations -> (S*(R+1),) uint64 keep masks: row i of order o keeps orders[o][:i]."""
     hip_ops.check_host_indices(orders, 0, num_regions, "orders")
-    orders = np.asarray(orders, dtype=np.uint64)
-    bits = np.left_shift(np.uint64(1), orders)                       # (S,R)
-    pref = np.concatenate([np.zeros((orders.shape[0], 1), dtype=np.uint64),
-                           np.bitwise_or.accumulate(bits, axis=1)], axis=1)
-    return pref.reshape(-1)
+    return hip_ops.region_words(orders, num_regions, prefixes=True).reshape(-1)
 
 
 def distinct_coalitions(keep_masks):
@@ -85,15 +81,21 @@ def coalition_logits_capped(model, clouds, centers, rid, keep, num_regions, cap)
                                              validate=False) for i in range(0, keep.numel(), cap)], dim=0)
 
 
-def materialised_logits(model, cloud, rid, keep, center, bs):
-    """For a model without a coalition entry point: the mask kernel writes the clouds of ``keep`` ((B,) masks of ``cloud``
-    (N,3)) in batches of ``bs`` and the model consumes them, as in the reference."""
+def dense_logits(model, keep, bs, mask_op):
+    """For a model without a coalition entry point: ``mask_op(keep rows, channel_first)`` (the mask kernel, narrow or wide) writes
+    the clouds of ``keep`` in batches of ``bs`` and the model consumes them, as in the reference."""
     points_api = hasattr(model, "forward_points")  # consumes (B,N,3) directly: no transpose
     chunks = []
-    for i in range(0, keep.numel(), bs):
-        x = hip_ops.mask_coalitions(cloud, rid, keep[i:i + bs].contiguous(), center, channel_first=not points_api)
-        chunks.append(model.forward_points(x) if points_api else model(x))
-    return torch.cat(chunks, dim=0)
+    for i in range(0, keep.shape[0], bs):
+        out = mask_op(keep[i:i + bs].contiguous(), not points_api)
+        out = model.forward_points(out) if points_api else model(out)
+        chunks.append(out[0] if isinstance(out, tuple) else out)
+    return torch.cat(chunks, dim=0) if chunks else torch.empty((0, 0), dtype=torch.float32, device=keep.device)
+
+
+def materialised_logits(model, cloud, rid, keep, center, bs):
+    """dense_logits for ``keep`` ((B,) masks of ``cloud`` (N,3))."""
+    return dense_logits(model, keep, bs, lambda k, cf: hip_ops.mask_coalitions(cloud, rid, k, center, channel_first=cf))
 
 
 def masked_logits(model, data, center, rid, keep, args, knob):

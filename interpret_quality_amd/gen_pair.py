@@ -8,7 +8,6 @@ final_gen_pair.py:221-286) and the prediction at a chosen pose (gen_pred_label, 
 """
 import argparse
 import itertools
-import os
 
 import numpy as np
 import torch
@@ -17,10 +16,10 @@ from scipy.special import comb
 from . import final_common, work
 from .final_util import (BALL_QUERY_COEF, ball_query, cal_rank, get_folder_name_list, load_model, mkdir,
                          square_distance_np)  # noqa: F401
-from .interaction import DEFAULT_RATIOS
+from .interaction import DEFAULT_RATIOS, _region_folders
 from .pose_sweep import rotate_xyz, translate_pc
 from . import dist as iqdist
-from .shapley_stage import data_loader, finish_args
+from .shapley_stage import data_loader, finish_args, rank0_only
 
 
 def gen_context(region_pair_list, save_path, args):
@@ -30,22 +29,39 @@ def gen_context(region_pair_list, save_path, args):
     The reference draws every sampled context with np.random.choice(rest, m, replace=False) - the first m entries of a fresh
     np.random.permutation(R - 2) - on the global generator: 330 000 draws of 29 numbers for 300 pairs, 2.5 s of host time per
     cloud.  With ``args.device`` set the SAME stream is continued on the device (iq_sample_permutations, bit-identical, one
-    launch per ratio) and handed back to NumPy; without it (host-only callers) the reference's loop runs as it is."""
+    launch per ratio) and handed back to NumPy; without it (host-only callers) the reference's loop runs on the host
+    (``iter_contexts``)."""
     dev = getattr(args, "device", None)
     if dev is not None and getattr(dev, "type", None) == "cuda" and len(region_pair_list) > 0:
         return _gen_context_device(np.asarray(region_pair_list).reshape(-1, 2), save_path, args, dev)
-    for ratio in args.ratio:
-        m = int((args.num_regions - 2) * ratio)
-        per_pair = []
-        for region_i, region_j in region_pair_list:
-            rest = [r for r in range(args.num_regions) if r != region_i and r != region_j]
-            if comb(len(rest), m) > args.num_save_context_max:
-                per_pair.append([np.random.choice(rest, m, replace=False) for _ in range(args.num_save_context_max)])
-            else:
-                per_pair.append(list(itertools.combinations(rest, m)))
-        context_list = np.array(per_pair)  # (num_pairs, num_context, m)
+    for ratio, context_list in zip(args.ratio, iter_contexts(region_pair_list, args.num_regions, args.ratio, args.num_save_context_max)):
+        if len(region_pair_list) == 0:
+            context_list = np.array([])     # what the reference's np.array(per_pair) makes of no pairs: (0,) float64
         print(context_list.shape)
         np.save(save_path + "ratio%d_context_list.npy" % int(ratio * 100), context_list)
+
+
+def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=None):
+    """The reference's host loop (final_gen_pair.py:18-43), one ratio at a time: a generator of (P, C, m) arrays, drawn from
+    NumPy's GLOBAL generator in the reference's order (ratio, pair, context).  ``dtype`` None: what the reference's
+    np.array(per_pair) gives - int64, and float64 for the one empty context of m = 0.  wide.iter_contexts is this loop for up to
+    wide.MAX_REGIONS regions."""
+    r, cmax = int(num_regions), int(num_save_context_max)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    regions = np.arange(r)
+    for ratio in ratios:
+        m = int((r - 2) * ratio)
+        sampled = comb(r - 2, m) > cmax
+        per_pair = []
+        for i, j in pairs:
+            rest = regions[(regions != i) & (regions != j)]        # ascending, as the reference's all_S
+            if sampled:
+                # np.random.choice(rest, m, replace=False) on the legacy generator: the head of a fresh permutation
+                per_pair.append(np.array([rest[np.random.permutation(rest.size)[:m]] for _ in range(cmax)], dtype=dtype).reshape(cmax, m))
+            else:
+                listed = list(itertools.combinations(rest.tolist(), m))
+                per_pair.append(np.array(listed, dtype=dtype).reshape(len(listed), m))
+        yield np.stack(per_pair) if per_pair else np.zeros((0, 0, m), dtype=dtype)
 
 
 def _gen_context_device(pairs, save_path, args, dev):
@@ -161,12 +177,6 @@ def save_pair_single_region(args, folder_name_list):
             np.save(folder + "region_pair_list.npy", pairs)
 
 
-def _region_folders(single):
-    if not os.path.isdir(single):
-        return []
-    return [single + d + "/" for d in sorted(os.listdir(single)) if os.path.isdir(single + d)]
-
-
 def save_context(args, folder_name_list):
     """final_gen_pair.py:44-70."""
     print("gen context start...")
@@ -237,7 +247,4 @@ def run(args):
 def main(argv=None):
     args = make_args(argv)
     finish_args(args)
-    # under a multi-rank launch rank 0 does the work and the others wait, so that no two ranks write the same files
-    if iqdist.rank() == 0:
-        run(args)
-    iqdist.barrier()
+    rank0_only(run, args, "pair generation")

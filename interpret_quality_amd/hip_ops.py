@@ -183,23 +183,41 @@ def reward(logits, label, modified=True):
     return v
 
 
-def shapley_accum(v, orders, snap_counts=None):
-    """v (S*(R+1),) f32, orders (S,R) i32 -> (phi_sum (R,) f64, sv_rows (S,R) f64, snaps or None)."""
+def _shapley_accum(entry, v, orders, snap_counts, exact=True):
+    """The body of shapley_accum and shapley_accum_wide: ``entry`` names the library call.  The kernel reads the first S*(R+1)
+    rewards: a shorter ``v`` is always refused, a longer one unless ``exact`` is False."""
     lib = _lib.load()
     s, r = orders.shape
     dev = v.device
+    if v.numel() < s * (r + 1) or (exact and v.numel() != s * (r + 1)):
+        raise _lib.IqError("v holds %d rewards for %d permutations of %d regions" % (v.numel(), s, r))
     sv_rows = torch.zeros((max(s, 1), r), dtype=torch.float64, device=dev)
     phi = torch.empty((r,), dtype=torch.float64, device=dev)
-    snaps = None
-    counts = None
+    snaps = counts = None
     n_snap = 0
     if snap_counts is not None and len(snap_counts) > 0:
         counts = torch.tensor(list(snap_counts), dtype=torch.int32, device=dev)
         n_snap = counts.numel()
         snaps = torch.zeros((n_snap, r), dtype=torch.float64, device=dev)
-    _lib.check(lib.iq_shapley_accum(_dev(v, torch.float32, "v"), _dev(orders, torch.int32, "orders"), _p(sv_rows),
-                                    _p(phi), _p(counts), n_snap, _p(snaps), r, s, _stream()), "iq_shapley_accum")
+    _lib.check(getattr(lib, entry)(_dev(v, torch.float32, "v"), _dev(orders, torch.int32, "orders"), _p(sv_rows), _p(phi), _p(counts),
+                                   n_snap, _p(snaps), r, s, _stream()), entry)
     return phi, sv_rows[:s], snaps
+
+
+def shapley_accum(v, orders, snap_counts=None):
+    """v (S*(R+1),) f32, orders (S,R) i32 -> (phi_sum (R,) f64, sv_rows (S,R) f64, snaps or None).  A longer ``v`` is let through as
+    before (pose_sweep.shapley_over_poses passes one when all_orders.npy holds fewer than num_samples permutations)."""
+    return _shapley_accum("iq_shapley_accum", v, orders, snap_counts, exact=False)
+
+
+def shapley_snapshots(v, orders, counts, accum=shapley_accum):
+    """The tail of every sampling loop: ``accum`` (shapley_accum or shapley_accum_wide) with running sums at the ``counts`` that
+    do not exceed S, everything moved to the host -> ({count: (R,) float64 running sum}, rows (S,R) float64, total (R,))."""
+    s, r = orders.shape
+    counts = [int(c) for c in (counts or []) if c <= s]
+    total, rows, snaps = accum(v, orders, snap_counts=counts)
+    snaps = snaps.cpu().numpy() if snaps is not None else np.zeros((0, r))
+    return {c: snaps[k] for k, c in enumerate(counts)}, rows.cpu().numpy(), total.cpu().numpy()
 
 
 def interaction_reduce(v):
@@ -318,11 +336,34 @@ def wide_words(num_regions):
     return (r + 63) // 64
 
 
-def _wide_keep(keep, num_regions):
+def wide_keep(keep, num_regions):
+    """The one check of wide keep rows: (B, wide_words(R)) int64, contiguous, on the GPU -> their pointer."""
     w = wide_words(num_regions)
     if keep.dim() != 2 or keep.shape[1] != w:
         raise _lib.IqError("keep must be (B, %d) for %d regions, got %s" % (w, int(num_regions), tuple(keep.shape)))
     return _dev(keep, torch.int64, "keep")
+
+
+def region_words(ids, num_regions, prefixes=False):
+    """Host: region ids (..., k) -> (..., W) uint64 words of the set they name, bit (r & 63) of word (r >> 6) = region r; an
+    entry outside [0, R) is ignored, as the device builders ignore it.  ``prefixes``: (..., k + 1, W), row i the set of the
+    first i ids (OR-accumulated).  The one builder behind the four host *_keep_masks; one pass over the ids per word."""
+    r = int(num_regions)
+    w = wide_words(r)
+    ids = np.asarray(ids, dtype=np.int64)
+    k = ids.shape[-1]
+    out = np.zeros(ids.shape[:-1] + ((k + 1, w) if prefixes else (w,)), dtype=np.uint64)
+    if k:
+        for j in range(w):
+            # NumPy shifts by a count outside 0..63 to 0: an id of another word, or a negative one (huge as uint64), sets nothing
+            bits = np.left_shift(np.uint64(1), (ids - 64 * j if j else ids).astype(np.uint64))
+            if prefixes:
+                np.bitwise_or.accumulate(bits, axis=-1, out=out[..., 1:, j])
+            else:
+                out[..., j] = np.bitwise_or.reduce(bits, axis=-1)
+        if r & 63:
+            out[..., w - 1] &= np.uint64((1 << (r & 63)) - 1)      # ids in [R, 64 W)
+    return out
 
 
 def wide_masks_to_tensor(masks, device):
@@ -364,7 +405,7 @@ def mask_coalitions_wide(cloud, region_id, keep, center, num_regions, channel_fi
     """cloud (N,3) f32, region_id (N,) i32, keep (B,W) i64, center (3,) f32 -> (B,N,3) or (B,3,N) (iq_mask_coalitions_wide)."""
     lib = _lib.load()
     n = cloud.shape[0]
-    kp = _wide_keep(keep, num_regions)
+    kp = wide_keep(keep, num_regions)
     b = keep.shape[0]
     out = torch.empty((b, 3, n) if channel_first else (b, n, 3), dtype=torch.float32, device=cloud.device)
     _lib.check(lib.iq_mask_coalitions_wide(_dev(cloud, torch.float32, "cloud"), _dev(region_id, torch.int32, "region_id"), kp,
@@ -388,23 +429,8 @@ def region_assign_wide(cloud, fps_idx):
 def shapley_accum_wide(v, orders, snap_counts=None):
     """shapley_accum for R <= MAX_WIDE_REGIONS: v (S*(R+1),) f32, orders (S,R) i32 -> (phi_sum (R,) f64, sv_rows (S,R) f64,
     snaps or None)."""
-    lib = _lib.load()
-    s, r = orders.shape
-    wide_words(r)
-    dev = v.device
-    if v.numel() != s * (r + 1):
-        raise _lib.IqError("v holds %d rewards for %d permutations of %d regions" % (v.numel(), s, r))
-    sv_rows = torch.zeros((max(s, 1), r), dtype=torch.float64, device=dev)
-    phi = torch.empty((r,), dtype=torch.float64, device=dev)
-    snaps = counts = None
-    n_snap = 0
-    if snap_counts is not None and len(snap_counts) > 0:
-        counts = torch.tensor(list(snap_counts), dtype=torch.int32, device=dev)
-        n_snap = counts.numel()
-        snaps = torch.zeros((n_snap, r), dtype=torch.float64, device=dev)
-    _lib.check(lib.iq_shapley_accum_wide(_dev(v, torch.float32, "v"), _dev(orders, torch.int32, "orders"), _p(sv_rows),
-                                         _p(phi), _p(counts), n_snap, _p(snaps), r, s, _stream()), "iq_shapley_accum_wide")
-    return phi, sv_rows[:s], snaps
+    wide_words(orders.shape[1])
+    return _shapley_accum("iq_shapley_accum_wide", v, orders, snap_counts)
 
 
 def fps(xyz, npoint):

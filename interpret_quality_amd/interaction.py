@@ -34,15 +34,9 @@ def context_keep_masks(region_pair_list, context_list, num_regions=64):
     p, c = ctx.shape[0], ctx.shape[1]
     hip_ops.check_host_indices(pairs, 0, num_regions, "region_pair_list")
     hip_ops.check_host_indices(ctx, 0, num_regions, "context_list")
-    one = np.uint64(1)
-    if ctx.shape[2] > 0:
-        s = np.bitwise_or.reduce(np.left_shift(one, ctx.astype(np.uint64)), axis=2)  # (P,C)
-    else:
-        s = np.zeros((p, c), dtype=np.uint64)
-    bi = np.left_shift(one, pairs[:, 0].astype(np.uint64))[:, None]
-    bj = np.left_shift(one, pairs[:, 1].astype(np.uint64))[:, None]
-    out = np.stack([s | bi | bj, s | bi, s | bj, s], axis=2)  # (P,C,4)
-    return out.reshape(-1)
+    s = hip_ops.region_words(ctx, num_regions)[..., 0]                    # (P,C)
+    bi, bj = hip_ops.region_words(pairs[:, :1], num_regions), hip_ops.region_words(pairs[:, 1:], num_regions)   # (P,1)
+    return np.stack([s | bi | bj, s | bi, s | bj, s], axis=2).reshape(-1)  # (P,C,4)
 
 
 def compute_order_interaction_logits(model, data_disturb, region_id, region_pair_list, context_list, args):
@@ -91,33 +85,45 @@ def _selected(args):
     return MODELNET_INTER_SELECTED_SAMPLE if args.dataset == "modelnet10" else SHAPENET_INTER_SELECTED_SAMPLE
 
 
+def _region_folders(single):
+    if not os.path.isdir(single):
+        return []
+    return [single + d + "/" for d in sorted(os.listdir(single)) if os.path.isdir(single + d)]
+
+
+def selected_clouds(args):
+    """The walk the interaction drivers share: for every cloud of the dataset's interaction selection (within
+    ``args.cloud_subset``) -> (pc_idx, name, data, lbl, base_folder, interaction_folder, single_folders), the tensors on the
+    device; ``single_folders``: the normal/ folders of the most pose-sensitive region (rank 01) under <mode>_adv_single_region/
+    (final_point_binary_interaction_logits.py:125-135).  Ends after the last cloud that is wanted."""
+    folder_name_list = get_folder_name_list(args)
+    wanted = [i for i in _selected(args) if iqdist.cloud_selected(args, i)]
+    for pc_idx, (data, lbl) in enumerate(data_loader(args)):
+        if not wanted or pc_idx > max(wanted):
+            break
+        if pc_idx not in wanted:
+            continue
+        name = folder_name_list[pc_idx]
+        print("======= sample %s =========" % name)
+        base_folder = args.exp_folder + "%s/" % name
+        interaction_folder = base_folder + "interaction_seed%d/" % args.gen_pair_seed
+        single = [f + "normal/" for f in _region_folders(interaction_folder + "%s_adv_single_region/" % args.mode)
+                  if int(os.path.basename(f[:-1])[10:12]) == 1]
+        yield pc_idx, name, data.to(args.device), lbl.to(args.device), base_folder, interaction_folder, single
+
+
 def save_logits(args, disturb_fn):
     """final_point_binary_interaction_logits.py:83-135."""
     model = load_model(args)
-    folder_name_list = get_folder_name_list(args)
     with torch.no_grad():
-        for pc_idx, (data, lbl) in enumerate(data_loader(args)):
-            if pc_idx not in _selected(args) or not iqdist.cloud_selected(args, pc_idx):
-                continue
-            name = folder_name_list[pc_idx]
-            print("======= sample %s =========" % name)
-            data = data.to(args.device)
-            base_folder = args.exp_folder + "%s/" % name
-            interaction_folder = base_folder + "interaction_seed%d/" % args.gen_pair_seed
-            single_region_folder = interaction_folder + "%s_adv_single_region/" % args.mode
+        for _, _, data, _, base_folder, interaction_folder, single_folders in selected_clouds(args):
             region_id = np.load(base_folder + "region_id.npy")
             save_logits_all_orders(model, data, region_id, interaction_folder + "normal/", args)
             params = np.load(interaction_folder + "%s_adv/transform_params.npy" % args.mode).astype(np.float32)
             data_disturb = disturb_fn(data, torch.from_numpy(params).to(args.device))
             save_logits_all_orders(model, data_disturb, region_id, interaction_folder + "%s_adv/" % args.mode, args)
-            if not os.path.isdir(single_region_folder):
-                continue
-            for region_folder_name in sorted(os.listdir(single_region_folder)):
-                if not os.path.isdir(single_region_folder + region_folder_name):
-                    continue
-                if int(region_folder_name[10:12]) != 1:  # only the most rotation-sensitive region, :129-131
-                    continue
-                save_logits_all_orders(model, data, region_id, single_region_folder + region_folder_name + "/normal/", args)
+            for folder in single_folders:
+                save_logits_all_orders(model, data, region_id, folder, args)
 
 
 def compute_order_interaction(all_logits, lbl, args):
@@ -144,17 +150,8 @@ def cal_interaction_all_orders(lbl, save_path, args):
 
 def cal_interaction(args):
     """final_cal_interactions.py:49-99."""
-    folder_name_list = get_folder_name_list(args)
     with torch.no_grad():
-        for pc_idx, (data, lbl) in enumerate(data_loader(args)):
-            if pc_idx not in _selected(args) or not iqdist.cloud_selected(args, pc_idx):
-                continue
-            name = folder_name_list[pc_idx]
-            print("======= sample %s =========" % name)
-            lbl = lbl.to(args.device)
-            base_folder = args.exp_folder + "%s/" % name
-            interaction_folder = base_folder + "interaction_seed%d/" % args.gen_pair_seed
-            single_region_folder = interaction_folder + "%s_adv_single_region/" % args.mode
+        for _, _, _, lbl, _, interaction_folder, single_folders in selected_clouds(args):
             print("##### normal pose")
             cal_interaction_all_orders(lbl, interaction_folder + "normal/", args)
             print("##### max attacking utility pose")
@@ -162,14 +159,8 @@ def cal_interaction(args):
             pred = torch.tensor([pred_class], dtype=torch.long, device=args.device)
             use = lbl if args.output_type == "gt" else pred
             cal_interaction_all_orders(use, interaction_folder + "%s_adv/" % args.mode, args)
-            if not os.path.isdir(single_region_folder):
-                continue
-            for region_folder_name in sorted(os.listdir(single_region_folder)):
-                if not os.path.isdir(single_region_folder + region_folder_name):
-                    continue
-                if int(region_folder_name[10:12]) != 1:
-                    continue
-                cal_interaction_all_orders(lbl, single_region_folder + region_folder_name + "/normal/", args)
+            for folder in single_folders:
+                cal_interaction_all_orders(lbl, folder, args)
 
 
 def build_parser(with_cal_flags):

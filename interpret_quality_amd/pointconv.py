@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, hip_ops
-from .engine import CoalitionModel, Engine, Packer, fold, ptr, stream
+from .engine import CoalitionModel, Engine, Packer, check_cloud_of, fold, ptr, stream
 
 SA = [dict(npoint=512, nsample=32, in_channel=3, mlp=[64, 64, 128], bandwidth=0.1),          # models/pointconv.py:403
       dict(npoint=128, nsample=64, in_channel=128 + 3, mlp=[128, 128, 256], bandwidth=0.2),  # :404
@@ -166,6 +166,7 @@ class PointConvDensityClsSsg(CoalitionModel, nn.Module):
         if clouds.shape[1] < 64:
             raise _lib.IqError("PointConv needs at least 64 points per cloud (sa2 groups 64 neighbours), got %d" % clouds.shape[1])
         if clouds.shape[1] > 1024:   # beyond the library's coalition entry: mask kernel + forward, source cloud by source cloud
+            check_cloud_of(clouds, keep, cloud_of)
             which = cloud_of if cloud_of is not None else (torch.zeros(b, dtype=torch.int32, device=keep.device) if nc == 1
                                                           else torch.arange(b, dtype=torch.int32, device=keep.device))
             out = torch.empty((b, self.output_channels), dtype=torch.float32, device=keep.device)

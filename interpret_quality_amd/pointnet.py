@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, hip_ops, workspace
-from .engine import Engine, EngineOwner, Packer, check_coalition_args, fold, ptr, stream
+from .engine import Engine, EngineOwner, Packer, check_coalition_args, fold, ptr, split_launches, stream
 
 
 class PackedWeights(Packer):
@@ -115,10 +115,9 @@ class PointNetEngine(Engine):
         channel_first and trans_feat_packed; no wide caller needs them), and centers and keep are required: the dense forward
         goes through the narrow entry."""
         r = int(num_regions)
-        w = hip_ops.wide_words(r)
+        hip_ops.wide_words(r)
         check_coalition_args(clouds, centers, region_id, keep, cloud_of)
-        if keep.dim() != 2 or keep.shape[1] != w:
-            raise _lib.IqError("keep must be (B, %d) for %d regions, got %s" % (w, r, tuple(keep.shape)))
+        hip_ops.wide_keep(keep, r)
         nc, n, b = clouds.shape[0], clouds.shape[1], keep.shape[0]
         logits = self.new_logits(b)
         ws = workspace.ensure(self, self.wide_bytes(b, nc, n, r))
@@ -188,24 +187,13 @@ class PointNetCls(EngineOwner, nn.Module):
     def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None, validate=True):
         """Logits of B WIDE coalitions: ``keep`` (B, ceil(num_regions / 64)) int64 rows, num_regions up to
         hip_ops.MAX_WIDE_REGIONS (one region per point included).  Launches of at most ``max_wide_per_call`` coalitions, fewer when
-        the free memory asks for it (workspace.run_in_steps, as CoalitionModel.split_launches does for the other families: only
+        the free memory asks for it (engine.split_launches, which the other families' CoalitionModel.split_launches calls too: only
         ``keep`` and ``cloud_of`` are sliced); a coalition's logits do not depend on what else is in its launch."""
         r = int(num_regions)
         hip_ops.wide_words(r)
         if validate:
             hip_ops.check_index_range(region_id, 0, r, "region_id")
         eng = self.engine()
-        nc, n, b = clouds.shape[0], clouds.shape[1], keep.shape[0]
-        if cloud_of is None and nc not in (1, b):
-            raise _lib.IqError("cloud_of is required when 1 < number of clouds != number of coalitions")
-        names = cloud_of
-
-        def call(lo, hi):
-            nonlocal names
-            if (lo, hi) == (0, b):
-                return eng.coalition_logits_wide(clouds, centers, region_id, keep, cloud_of, num_regions=r)
-            if names is None and nc == b:
-                names = torch.arange(b, dtype=torch.int32, device=keep.device)
-            return eng.coalition_logits_wide(clouds, centers, region_id, keep[lo:hi].contiguous(),
-                                             names[lo:hi].contiguous() if names is not None else None, num_regions=r)
-        return workspace.run_in_steps(eng, b, self.max_wide_per_call, lambda k: eng.wide_bytes(k, nc, n, r), call)
+        nc, n = clouds.shape[0], clouds.shape[1]
+        return split_launches(eng, lambda k, names: eng.coalition_logits_wide(clouds, centers, region_id, k, names, num_regions=r),
+                              lambda k: eng.wide_bytes(k, nc, n, r), self.max_wide_per_call, clouds, keep, cloud_of)

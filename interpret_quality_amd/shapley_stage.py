@@ -123,32 +123,40 @@ def shapley_all_orders(model, data, lbl, region_id, all_orders, args):
         return final_common.get_reward(logits, lbl, args).reshape(hi - lo, args.num_regions + 1)
 
     v = iqdist.sharded_rows(s, rewards).reshape(-1)  # one gather per cloud
-    counts = [c for c in SAMPLE_NUMS if c <= s]
-    total, rows, snaps = hip_ops.shapley_accum(v.contiguous(), hip_ops.as_i32(all_orders, v.device), snap_counts=counts)
-    snaps = snaps.cpu().numpy() if snaps is not None else np.zeros((0, args.num_regions))
-    return {c: snaps[k] for k, c in enumerate(counts)}, rows.cpu().numpy(), total.cpu().numpy()
+    return hip_ops.shapley_snapshots(v.contiguous(), hip_ops.as_i32(all_orders, v.device), SAMPLE_NUMS)
+
+
+def selected_clouds(args, folder_name_list, skip_draw, dataloader=None):
+    """The per-cloud loop of the Shapley drivers (this stage, wide_stage.py, exact_stage.py): yields (i, name, result_path,
+    data, lbl, fps_index) for every cloud of ``args.cloud_subset`` (None: all), the folder made and the tensors on the device.
+    The FPS file is written first if it is absent.  The random streams run on from cloud to cloud, so for a cloud that is not
+    selected ``skip_draw(result_path, args, save=False)`` draws what the cloud would have drawn and nothing is computed; after
+    the last selected cloud nothing in this call reads the streams and the loop ends."""
+    if not os.path.exists(fps_index_path(args)):
+        save_fps(args)
+    fps_indices = np.load(fps_index_path(args))
+    subset = getattr(args, "cloud_subset", None)
+    for i, (data, lbl) in enumerate(dataloader if dataloader is not None else data_loader(args)):
+        if subset is not None and i > max(subset):
+            break
+        result_path = args.exp_folder + "%s/" % folder_name_list[i]
+        if not iqdist.cloud_selected(args, i):
+            skip_draw(result_path, args, save=False)
+            continue
+        mkdir(result_path)
+        yield i, folder_name_list[i], result_path, data.to(args.device), lbl.to(args.device), fps_indices[i]
 
 
 def shap_sampling(model, dataloader, args, folder_name_list):
     """final_shapley_value.py:110-156."""
     with torch.no_grad():
-        fps_indices = np.load(fps_index_path(args))
-        subset = getattr(args, "cloud_subset", None)
-        for i, (data, lbl) in enumerate(dataloader):
-            if subset is not None and i > max(subset):
-                break      # nothing later in this call reads the stream: no need to draw the remaining clouds' permutations
-            result_path = args.exp_folder + "%s/" % folder_name_list[i]
-            if not iqdist.cloud_selected(args, i):
-                generate_all_orders(result_path, args, save=False)  # the stream runs on from cloud to cloud: draw, do not compute
-                continue
-            mkdir(result_path)
-            data, lbl = data.to(args.device), lbl.to(args.device)
+        for i, name, result_path, data, lbl, fps_index in selected_clouds(args, folder_name_list, generate_all_orders, dataloader):
             write = iqdist.rank() == 0
-            region_id = cal_region_id(data, fps_indices[i], result_path, save=write)
+            region_id = cal_region_id(data, fps_index, result_path, save=write)
             center = torch.mean(data, dim=1).squeeze()
             cal_norm_factor(model, data, lbl, center, result_path, args, save=write)
             all_orders = generate_all_orders(result_path, args, save=write)  # same RNG stream on every rank
-            print("pointcloud:%s, index:%d, samples:%d" % (folder_name_list[i], i, len(all_orders)))
+            print("pointcloud:%s, index:%d, samples:%d" % (name, i, len(all_orders)))
             snaps, region_sv_all, _ = shapley_all_orders(model, data, lbl, region_id, all_orders, args)
             if write:
                 for count, running in snaps.items():
@@ -218,11 +226,29 @@ def finish_args(args):
     return args
 
 
+def parse_game_args(parser, argv, default_regions=NUM_REGIONS, lo=None, hi=None, message=None, samples=True):
+    """Adds the additive flags --num_samples_save (``samples``) and --num_regions to a stage's parser and parses; a region count
+    outside [lo, hi] is a parser error that ends with the stage's own ``message``."""
+    if samples:
+        parser.add_argument("--num_samples_save", type=int, default=NUM_SAMPLES_SAVE)
+    parser.add_argument("--num_regions", type=int, default=default_regions)
+    args = parser.parse_args(argv)
+    if message is not None and not lo <= args.num_regions <= hi:
+        parser.error("--num_regions %d: %s" % (args.num_regions, message))
+    return args
+
+
+def rank0_only(run, args, what):
+    """A single-process stage under several ranks: rank 0 does the work and the others wait, so no two ranks write the same files."""
+    if iqdist.rank() == 0:
+        run(args)
+    else:
+        print("rank %d: the %s stage runs on rank 0 only; waiting" % (iqdist.rank(), what))
+    iqdist.barrier()
+
+
 def make_args(argv=None):
-    parser = build_parser()
-    parser.add_argument("--num_samples_save", type=int, default=NUM_SAMPLES_SAVE)  # additive
-    parser.add_argument("--num_regions", type=int, default=NUM_REGIONS)            # additive
-    return parser.parse_args(argv)
+    return parse_game_args(build_parser(), argv)
 
 
 @iqdist.record

@@ -6,16 +6,13 @@ for any region count up to the number of points.  Here a WIDE coalition is a row
 (r & 63) of word (r >> 6) set = region r kept - for 1 <= R <= MAX_REGIONS (include/iq.h, "Wide coalitions").
 
 PointNet evaluates wide coalitions fused (iq_pointnet_coalitions_wide: no masked cloud is ever written).  Every other family
-runs iq_mask_coalitions_wide in batches into its own dense forward, the route final_common.materialised_logits takes: correct,
+runs iq_mask_coalitions_wide in batches into its own dense forward (final_common.dense_logits, the narrow route too): correct,
 at dense-forward speed.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
 and the multi-order interactions of sampled (pair, context) coalitions (``gen_context``, ``interaction_logits``, ``interactions``,
 wide_interaction_stage.py).  The smoothness and pose stages have none.
 """
-import itertools
-
 import numpy as np
 import torch
-from scipy.special import comb
 
 from . import dist as iqdist
 from . import final_common, gen_pair, hip_ops, interaction, work
@@ -33,51 +30,28 @@ def prefix_keep_masks(orders, num_regions):
     orders = np.asarray(orders, dtype=np.int64)
     if orders.ndim != 2 or orders.shape[1] != r:
         raise IqError("orders must be (S, %d), got %s" % (r, orders.shape))
-    s = orders.shape[0]
-    valid = (orders >= 0) & (orders < r)
-    word = np.where(valid, orders >> 6, -1)
-    bit = np.left_shift(np.uint64(1), (orders & 63).astype(np.uint64))
-    out = np.zeros((s, r + 1, w), dtype=np.uint64)
-    for k in range(w):
-        out[:, 1:, k] = np.bitwise_or.accumulate(np.where(word == k, bit, np.uint64(0)), axis=1)
-    return out.reshape(s * (r + 1), w)
-
-
-def _keep_rows(keep, num_regions, device):
-    if isinstance(keep, np.ndarray):
-        keep = hip_ops.wide_masks_to_tensor(keep, device)
-    w = hip_ops.wide_words(num_regions)
-    if keep.dim() != 2 or keep.shape[1] != w:
-        raise IqError("keep must be (B, %d) for %d regions, got %s" % (w, int(num_regions), tuple(keep.shape)))
-    return keep.contiguous()
+    return hip_ops.region_words(orders, r, prefixes=True).reshape(-1, w)
 
 
 def coalition_logits(model, data, region_id, keep, args):
     """Logits of the wide coalitions ``keep`` ((B,W) int64-typed device tensor or uint64 ndarray) of one cloud ``data`` (1,N,3);
     every masked point collapses onto the mean of the cloud (tools/final_common.py:80).  ``args``: model, num_regions."""
     r = int(args.num_regions)
-    return _logits(model, data, hip_ops.region_ids(region_id, data.device, r), _keep_rows(keep, r, data.device), r)
+    keep = (hip_ops.wide_masks_to_tensor(keep, data.device) if isinstance(keep, np.ndarray) else keep).contiguous()
+    hip_ops.wide_keep(keep, r)
+    return _logits(model, data, hip_ops.region_ids(region_id, data.device, r), keep, r)
 
 
 def _logits(model, data, rid, keep, r):
     """coalition_logits on validated region ids (int32 device tensor) and a (B,W) device tensor."""
-    dev = data.device
     center = torch.mean(data, dim=1)
     work.add(keep.shape[0])
     if hasattr(model, "coalition_logits_wide"):
         return model.coalition_logits_wide(data.contiguous(), center.reshape(1, 3).contiguous(), rid.reshape(1, -1), keep, None,
                                            num_regions=r, validate=False)
-    points_api = hasattr(model, "forward_points")     # consumes (B,N,3) directly: no transpose
-    bs = max(DENSE_BATCH, getattr(model, "preferred_clouds_per_call", 0))
     cloud, c3 = data[0].contiguous(), center.reshape(3).contiguous()
-    chunks = []
-    for i in range(0, keep.shape[0], bs):
-        x = hip_ops.mask_coalitions_wide(cloud, rid, keep[i:i + bs].contiguous(), c3, r, channel_first=not points_api)
-        out = model.forward_points(x) if points_api else model(x)
-        chunks.append(out[0] if isinstance(out, tuple) else out)
-    if not chunks:
-        return torch.empty((0, 0), dtype=torch.float32, device=dev)
-    return torch.cat(chunks, dim=0)
+    return final_common.dense_logits(model, keep, max(DENSE_BATCH, getattr(model, "preferred_clouds_per_call", 0)),
+                                     lambda k, cf: hip_ops.mask_coalitions_wide(cloud, rid, k, c3, r, channel_first=cf))
 
 
 def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None):
@@ -104,10 +78,7 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
             keep = hip_ops.prefix_keep_masks_wide(orders_dev[lo:hi].contiguous())
             logits = _logits(model, data, rid, keep, r)
             v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
-    counts = [int(c) for c in (snap_counts or []) if c <= s]
-    total, rows, snaps = hip_ops.shapley_accum_wide(v, orders_dev, snap_counts=counts)
-    snaps = snaps.cpu().numpy() if snaps is not None else np.zeros((0, r))
-    return {c: snaps[k] for k, c in enumerate(counts)}, rows.cpu().numpy(), total.cpu().numpy()
+    return hip_ops.shapley_snapshots(v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
 
 
 # ---- multi-order interactions: final_gen_pair.py, final_point_binary_interaction_logits.py and final_cal_interactions.py ---------
@@ -118,24 +89,10 @@ interactions = interaction.compute_order_interaction  # final_cal_interactions.p
 
 def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=np.int64):
     """``gen_context`` one ratio at a time: a generator of (P, C, m) arrays of ``dtype`` (at R = 1024 one ratio's contexts are up
-    to 30 000 x 1022 entries: a caller that saves them need not hold thirteen of them)."""
-    r, cmax = int(num_regions), int(num_save_context_max)
-    hip_ops.wide_words(r)
-    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    regions = np.arange(r)
-    for ratio in ratios:
-        m = int((r - 2) * ratio)
-        sampled = comb(r - 2, m) > cmax
-        per_pair = []
-        for i, j in pairs:
-            rest = regions[(regions != i) & (regions != j)]        # ascending, as the reference's all_S
-            if sampled:
-                # np.random.choice(rest, m, replace=False) on the legacy generator: the head of a fresh permutation
-                per_pair.append(np.array([rest[np.random.permutation(rest.size)[:m]] for _ in range(cmax)], dtype=dtype).reshape(cmax, m))
-            else:
-                listed = list(itertools.combinations(rest.tolist(), m))
-                per_pair.append(np.array(listed, dtype=dtype).reshape(len(listed), m))
-        yield np.stack(per_pair) if per_pair else np.zeros((0, 0, m), dtype=dtype)
+    to 30 000 x 1022 entries: a caller that saves them need not hold thirteen of them).  The draws are gen_pair.iter_contexts's,
+    the host loop of the narrow stage."""
+    hip_ops.wide_words(num_regions)
+    yield from gen_pair.iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype)
 
 
 def gen_context(pairs, num_regions, ratios, num_save_context_max):
@@ -164,20 +121,8 @@ def context_keep_masks(pairs, contexts, num_regions):
     w = hip_ops.wide_words(r)
     pairs, ctx = _pairs_contexts(pairs, contexts, r)
     p, c = ctx.shape[0], ctx.shape[1]
-    ctx = ctx.astype(np.int64)
-
-    def words(idx):     # (..., k) region ids -> (..., W) words of the set
-        valid = (idx >= 0) & (idx < r)
-        word = np.where(valid, idx >> 6, -1)
-        bit = np.left_shift(np.uint64(1), (idx & 63).astype(np.uint64))
-        out = np.zeros(idx.shape[:-1] + (w,), dtype=np.uint64)
-        if idx.shape[-1]:
-            for k in range(w):
-                out[..., k] = np.bitwise_or.reduce(np.where(word == k, bit, np.uint64(0)), axis=-1)
-        return out
-
-    s = words(ctx)                                        # (P,C,W)
-    bi, bj = words(pairs[:, :1])[:, None, :], words(pairs[:, 1:])[:, None, :]
+    s = hip_ops.region_words(ctx, r)                      # (P,C,W)
+    bi, bj = hip_ops.region_words(pairs[:, None, :1], r), hip_ops.region_words(pairs[:, None, 1:], r)
     return np.stack([s | bi | bj, s | bi, s | bj, s], axis=2).reshape(4 * p * c, w)
 
 

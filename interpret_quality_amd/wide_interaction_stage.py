@@ -29,7 +29,7 @@ from . import dist as iqdist
 from . import gen_pair, interaction, wide
 from .final_util import get_folder_name_list, load_model, mkdir, set_random
 from .pose_sweep import rotate_xyz, translate_pc
-from .shapley_stage import data_loader, finish_args
+from .shapley_stage import finish_args, parse_game_args, rank0_only
 from .wide_stage import DEFAULT_REGIONS, MIN_REGIONS
 
 CONTEXT_DTYPE = np.int16      # holds every region id of a wide game (wide.MAX_REGIONS = 1024)
@@ -88,15 +88,8 @@ def run(args):
     set_random(args.gen_pair_seed)        # final_gen_pair.py --seed <k> writes interaction_seed<k>/
     draw(args, names, wanted)
     with torch.no_grad():
-        for i, (data, lbl) in enumerate(data_loader(args)):
-            if i > max(wanted):
-                break
-            if i not in wanted:
-                continue
-            print("======= sample %s =========" % names[i])
-            data, lbl = data.to(args.device), lbl.to(args.device)
-            folder = _folder(args, names[i])
-            region_id = np.load(args.exp_folder + "%s/region_id.npy" % names[i])
+        for _, _, data, lbl, base_folder, folder, _ in interaction.selected_clouds(args):
+            region_id = np.load(base_folder + "region_id.npy")
             print("##### normal pose")
             evaluate(model, data, lbl, region_id, folder, folder + "normal/", args)
             if params is None:
@@ -114,13 +107,11 @@ def run(args):
 def make_args(argv=None):
     parser = interaction.build_parser(with_cal_flags=True)
     parser.set_defaults(device_id=0)
-    parser.add_argument("--num_regions", type=int, default=DEFAULT_REGIONS)     # additive
     parser.add_argument("--transform_params", type=str, default=None, metavar="FILE.npy",
                         help="the --mode parameters of one pose: the same pairs and contexts are also evaluated there")
-    args = parser.parse_args(argv)
-    if not MIN_REGIONS <= args.num_regions <= wide.MAX_REGIONS:
-        parser.error("--num_regions %d: the wide stage takes %d .. %d regions (final_gen_pair.py and "
-                     "final_point_binary_interaction_logits.py: up to 64)" % (args.num_regions, MIN_REGIONS, wide.MAX_REGIONS))
+    args = parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
+                           "the wide stage takes %d .. %d regions (final_gen_pair.py and final_point_binary_interaction_logits.py: "
+                           "up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS), samples=False)
     if args.mode not in ("rotate", "trans"):
         parser.error("--mode %s: rotate or trans" % args.mode)
     if args.num_save_context_max < 1 or args.num_pairs_random < 1:
@@ -134,11 +125,7 @@ def main(argv=None):
     finish_args(args)
     if args.num_regions > args.num_points:
         raise SystemExit("--num_regions %d exceeds the %d points of a cloud" % (args.num_regions, args.num_points))
-    if iqdist.rank() == 0:
-        run(args)
-    else:
-        print("rank %d: the wide stage runs on rank 0 only; waiting" % iqdist.rank())
-    iqdist.barrier()
+    rank0_only(run, args, "wide")
 
 
 if __name__ == "__main__":

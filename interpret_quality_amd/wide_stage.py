@@ -12,15 +12,13 @@ fps_<dataset>_<N>_<R>_index_final30.npy.  Single process: under several ranks ra
 multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py).  The smoothness and pose
 stages have no wide form.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import dist as iqdist
 from . import hip_ops, wide
 from . import shapley_stage as stage1
-from .final_util import NUM_SAMPLES_SAVE, get_folder_name_list, load_model, mkdir
+from .final_util import get_folder_name_list, load_model
 
 DEFAULT_REGIONS = 128
 MIN_REGIONS = 65          # up to 64 regions: final_shapley_value.py
@@ -46,26 +44,13 @@ def cal_region_id(data, fps_index, result_path, save=True):
 
 def run(args):
     model = load_model(args)
-    folder_name_list = get_folder_name_list(args)
-    if not os.path.exists(stage1.fps_index_path(args)):
-        stage1.save_fps(args)
-    fps_indices = np.load(stage1.fps_index_path(args))
-    subset = getattr(args, "cloud_subset", None)
     with torch.no_grad():
-        for i, (data, lbl) in enumerate(stage1.data_loader(args)):
-            if subset is not None and i > max(subset):
-                break
-            result_path = args.exp_folder + "%s/" % folder_name_list[i]
-            if not iqdist.cloud_selected(args, i):
-                generate_all_orders(result_path, args, save=False)   # the stream runs on from cloud to cloud: draw, do not compute
-                continue
-            mkdir(result_path)
-            data, lbl = data.to(args.device), lbl.to(args.device)
-            region_id = cal_region_id(data, fps_indices[i], result_path)
+        for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), generate_all_orders):
+            region_id = cal_region_id(data, fps_index, result_path)
             center = torch.mean(data, dim=1).squeeze()
             stage1.cal_norm_factor(model, data, lbl, center, result_path, args)
             all_orders = generate_all_orders(result_path, args)
-            print("pointcloud:%s, index:%d, regions:%d, samples:%d" % (folder_name_list[i], i, args.num_regions, len(all_orders)))
+            print("pointcloud:%s, index:%d, regions:%d, samples:%d" % (name, i, args.num_regions, len(all_orders)))
             snaps, region_sv_all, _ = wide.shapley(model, data, lbl, region_id, all_orders, args, snap_counts=stage1.SAMPLE_NUMS)
             for count, running in snaps.items():
                 stage1.save_shapley(running, i, count, result_path, region_id, args)
@@ -73,14 +58,8 @@ def run(args):
 
 
 def make_args(argv=None):
-    parser = stage1.build_parser()
-    parser.add_argument("--num_samples_save", type=int, default=NUM_SAMPLES_SAVE)   # additive, as in stage 1
-    parser.add_argument("--num_regions", type=int, default=DEFAULT_REGIONS)         # additive
-    args = parser.parse_args(argv)
-    if not MIN_REGIONS <= args.num_regions <= wide.MAX_REGIONS:
-        parser.error("--num_regions %d: the wide stage takes %d .. %d regions (final_shapley_value.py: up to 64)"
-                     % (args.num_regions, MIN_REGIONS, wide.MAX_REGIONS))
-    return args
+    return stage1.parse_game_args(stage1.build_parser(), argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
+                                  "the wide stage takes %d .. %d regions (final_shapley_value.py: up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS))
 
 
 @iqdist.record
@@ -89,11 +68,7 @@ def main(argv=None):
     stage1.finish_args(args)
     if args.num_regions > args.num_points:
         raise SystemExit("--num_regions %d exceeds the %d points of a cloud" % (args.num_regions, args.num_points))
-    if iqdist.rank() == 0:
-        run(args)
-    else:
-        print("rank %d: the wide stage runs on rank 0 only; waiting" % iqdist.rank())
-    iqdist.barrier()
+    stage1.rank0_only(run, args, "wide")
 
 
 if __name__ == "__main__":

@@ -118,6 +118,19 @@ def test_abi_error_reporting(model):
         model.coalition_logits(clouds.cpu(), None, rid, None, None, num_regions=1)
 
 
+@pytest.mark.parametrize("accum", [hip_ops.shapley_accum, hip_ops.shapley_accum_wide])
+def test_shapley_accum_refuses_a_reward_vector_of_the_wrong_length(accum):
+    """S = 2 permutations of R = 3 regions need 8 rewards: one short would be read out of bounds, so nothing is launched."""
+    d = dev()
+    orders = torch.tensor([[0, 1, 2], [2, 0, 1]], dtype=torch.int32, device=d)
+    v = torch.arange(8, dtype=torch.float32, device=d)
+    with pytest.raises(_lib.IqError, match="v holds 7 rewards for 2 permutations of 3 regions"):
+        accum(v[:7].contiguous(), orders, snap_counts=[1])
+    phi, rows, snaps = accum(v, orders, snap_counts=[1])
+    assert rows.shape == (2, 3) and torch.equal(phi, rows.sum(0)) and torch.equal(snaps[0], rows[0])
+    assert rows[0].tolist() == [1.0, 1.0, 1.0] and rows[1].tolist() == [1.0, 1.0, 1.0]      # v[i+1] - v[i], credited to orders[o][i]
+
+
 def test_fps_more_samples_than_distinct_points():
     d = dev()
     x = torch.zeros((2, 64, 3), device=d)
