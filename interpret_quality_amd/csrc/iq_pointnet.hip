@@ -7,7 +7,7 @@
 //   * the feature-STN and trunk chains run only over a coalition's DISTINCT points.
 // Both are exact with respect to evaluating the same kernels on the materialised cloud.
 //
-// chain kernel: one workgroup (4 waves) per coalition, 64-row chunks:
+// chain kernel: one workgroup (4 waves) per coalition, 64-row chunks (96 in the product instantiations, below):
 //   stage0 (VALU)  x -> x.trans -> conv1(3->64)+bn+relu                      -> LDS act0
 //   L1  (MFMA)     64->64   (fstn.conv1 | per-coalition trans_feat product)  -> LDS act1
 //   L2  (MFMA)     64->128  conv2+bn+relu                                    -> LDS act2
@@ -18,7 +18,14 @@
 // L3V = 3 (the product path of the feature-STN and trunk chains): layers 2-3 as six exact bf16 products per float32 product on
 // v_mfma_f32_16x16x32_bf16 (iq_bf3.h; DESIGN.md 5a: the kernel is power-bound and this shape holds a 10 % higher clock than
 // 32x32x16), activations as three swizzled bf16 planes in LDS.  LDS = 74.8 KB, <= 256 VGPRs -> 2 workgroups/CU.
+// The two product instantiations (<kFstn | kTrunk, 3, false>) work on 96-ROW chunks: a layer-3 weight fragment then feeds six
+// 16-row m-tiles instead of four, a third less weight streaming out of L2 per row.  Two workgroups still fit a CU because act0,
+// act1 and act2 share ONE 72 KB image (act0 bytes 0 - 25.5 K, act1 36 - 72 K, act2 all of it: layer 2 keeps its 96 x 32 outputs per
+// wave in registers until every wave has read act1, one more barrier per chunk): LDS = 73.5 KB, 254-256 VGPRs, no scratch.  Every
+// row's arithmetic is the 64-row kernels', which stay as they are (pre-pool, fp32 twins, arg-max, twin kTwinChainL3Single) and are the
+// 96-row kernel's bitwise reference.  Row lists are padded for both chunk sizes (padded_rows).
 #include <algorithm>
+#include <type_traits>
 
 #include "iq_common.h"
 #include "iq_profile.h"
@@ -29,12 +36,16 @@
 namespace {
 
 constexpr int kFeat = IQ_NUM_FEAT;
-constexpr int kMC = 64;        // rows per chunk
+constexpr int kMC = 64;        // rows per chunk (the product instantiations of the chain kernel: kMC96)
+constexpr int kMC96 = 96;
 constexpr int kMaxN = 4096;    // points per cloud supported by the chain kernel (= IQ_MAX_POINTS; row lists are uint16)
 constexpr int kThreads = 256;
 constexpr int kRowCap = kMaxN + kMC;  // row-list stride per item (uint16)
 
-enum ChainMode { kPrepool = 0, kFstn = 1, kTrunk = 2 };
+// kFstn64 / kTrunk64: the same two bf16x3 chains in 64-row chunks, one n-tile per pass (twin kTwinChainL3Single, the bitwise reference
+// of the product instantiations <kFstn | kTrunk, 3, false>, which keep their names and work on 96-row chunks).  The chunk size rides
+// in the mode because the kernel keeps its three template arguments <mode, L3V, ARGMAX> (tests/test_isa_cpu.py pins them).
+enum ChainMode { kPrepool = 0, kFstn = 1, kTrunk = 2, kFstn64 = 3, kTrunk64 = 4 };
 
 // LDS activation images are row-major [row][k] with the row stride padded by 4 floats (68 / 132):
 // a 16-lane ds_read_b128 group reads 16 different rows at one k, i.e. bank offsets 4*row mod 64 ->
@@ -64,7 +75,7 @@ struct ChainArgs {
     int32_t* argrow;           // (items,1024) point index of the row that attains each column maximum, or null [ARGMAX trunk only]
     int N, R, items, nclouds, with_centre;
     int tail16;                  // last m-tile of an item on 16x16x4 MFMAs when it holds at most 16 rows (l3_tail16)
-    int l3_single;               // bf16x3 layer 3 one n-tile per pass (twin kTwinChainL3Single: A/B against two per pass)
+    int l3_single;               // twin kTwinChainL3Single: the 64-row bf16x3 kernel, one n-tile per pass (launch_chain; the 96-row kernel's reference)
 };
 
 // ---- L3: 128 -> 1024 for one 64-row chunk; wave `wave` owns the n-tiles q*4 + wave ------------
@@ -189,11 +200,12 @@ __device__ __forceinline__ void l3_pool16(const f32x4 (&acc)[MT], bool take, flo
         m = fmaxf(fmaxf(m, acc[0][3]), acc[1][0]);
         m = fmaxf(fmaxf(m, acc[1][1]), acc[1][2]);
         m = fmaxf(m, acc[1][3]);
-        if (MT == 4) {
-            float n = fmaxf(fmaxf(acc[2][0], acc[2][1]), acc[2][2]);
-            n = fmaxf(fmaxf(n, acc[2][3]), acc[3][0]);
-            n = fmaxf(fmaxf(n, acc[3][1]), acc[3][2]);
-            m = fmaxf(fmaxf(m, n), acc[3][3]);
+#pragma unroll
+        for (int p = 2; p < MT; p += 2) {      // a further pair of m-tiles
+            float n = fmaxf(fmaxf(acc[p][0], acc[p][1]), acc[p][2]);
+            n = fmaxf(fmaxf(n, acc[p][3]), acc[p + 1][0]);
+            n = fmaxf(fmaxf(n, acc[p + 1][1]), acc[p + 1][2]);
+            m = fmaxf(fmaxf(m, n), acc[p + 1][3]);
         }
         runmax = take ? fmaxf(runmax, m) : runmax;
     }
@@ -243,16 +255,19 @@ __device__ __forceinline__ void l3_pass_bf3(const __amdgpu_buffer_rsrc_t& rs, in
     }
 }
 
-// The same layer with TWO n-tiles per pass (n-tiles (2 qp) 4 + wave and (2 qp + 1) 4 + wave: 4 x 4 tiles of 16 x 16, the 64 x 64
-// wave tile and the 64 accumulator registers of the former 32x32x16 form): the A terms of a k-step are read from LDS once for all
-// four column tiles.  Every tile sees the same products in the same order, so the maxima are bit-identical to l3_pass_bf3's.  The
-// 96 MFMAs of a k-step go column-tile-major; ring.r[jj] = fragment of column tile jj (n-tile jj >> 1, half jj & 1) of the CURRENT
-// k-step, refilled with the next k-step's as soon as its 6 MT MFMAs are issued: the ring is three quarters of a k-step (1 152
-// matrix cycles) ahead and rolls over pass and chunk boundaries.
-template <int MTS>
+// The same layer with TWO n-tiles per pass (n-tiles (2 qp) 4 + wave and (2 qp + 1) 4 + wave: 4 column tiles of 16) over the 96-row
+// chunks of the product instantiations: MT = 2, 4 or 6 m-tiles of 16 rows, a 96 x 64 wave tile, 96 accumulator registers.  Every
+// tile sees the same products in the same order, so the maxima are bit-identical to l3_pass_bf3's.  A weight fragment feeds up to
+// six m-tiles (a third less weight streaming per row than with 64-row chunks).  Six m-tiles go as two halves of three, one after
+// the other: the A terms of a half (36 registers; all six would be 72 and do not fit beside 96 + 48) are read from LDS once for
+// all four column tiles, then the half's 72 MFMAs go column-tile-major.  ring.r[jj] = fragment of column tile jj (n-tile jj >> 1,
+// half jj & 1) of the CURRENT k-step, refilled with the next k-step's as soon as the LAST half's MFMAs of that column tile are
+// issued: a refilled slot is next read 3 x 6 x (MT / NH) MFMAs later (the other three column tiles, one half each; 54 MFMAs = 864 matrix
+// cycles at MT = 6, 1 152 at MT = 4 as with 64-row chunks, 576 at MT = 2) and the ring rolls over pass and chunk boundaries.
+template <int MTS, int PLANEB>
 __device__ __forceinline__ void l3_pass_bf3_2x2(const __amdgpu_buffer_rsrc_t& rs, int voff, const unsigned char* abase, int aoff,
                                                 int wave_s, float (&runmax)[16], B3Ring& ring) {
-    constexpr int MT = 2 * MTS;
+    constexpr int MT = 2 * MTS, NH = MTS == 3 ? 2 : 1, HT = MT / NH;
     int noarg = 0;
 #pragma unroll 1
     for (int qp = 0; qp < 4; ++qp) {
@@ -263,23 +278,28 @@ __device__ __forceinline__ void l3_pass_bf3_2x2(const __amdgpu_buffer_rsrc_t& rs
             for (int i = 0; i < MT; ++i) acc[j][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            bf16x8 af[MT][3];
 #pragma unroll
-            for (int i = 0; i < MT; ++i) a16_load<kLdB, kPlaneB>(af[i], abase, aoff, i, t);
+            for (int h = 0; h < NH; ++h) {
+                bf16x8 af[HT][3];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const B3 b = ring.r[j];
-                mfma16_bf3_col<MT>(af, b, acc[j]);
-                // k-step t + 1 of this pair of n-tiles, or k-step 0 of the next pair
-                ring.r[j] = b3_load16(rs, voff, (t + 1 < 4 ? 2 * qp : 2 * qp + 2) + (j >> 1), (t + 1) & 3, j & 1, wave_s);
+                for (int i = 0; i < HT; ++i) a16_load<kLdB, PLANEB>(af[i], abase, aoff, h * HT + i, t);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const B3 b = ring.r[j];
+                    mfma16_bf3_col<HT>(af, b, reinterpret_cast<f32x4(&)[HT]>(acc[j][h * HT]));
+                    // k-step t + 1 of this pair of n-tiles, or k-step 0 of the next pair
+                    if (h == NH - 1)
+                        ring.r[j] = b3_load16(rs, voff, (t + 1 < 4 ? 2 * qp : 2 * qp + 2) + (j >> 1), (t + 1) & 3, j & 1, wave_s);
+                }
+                // issue order (as l3_pass_bf3): the half's A reads, then per column tile its MFMAs and - last half - its refill
+                __builtin_amdgcn_sched_group_barrier(0x100, 3 * HT, 0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 6 * HT, 0);
+                    if (h == NH - 1) __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_sched_group_barrier(0x100, 3 * MT, 0);     // as l3_pass_bf3
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 6 * MT, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 3, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -344,12 +364,17 @@ __device__ __forceinline__ void l3_tail16(const WBuf& w3, const float* act2, int
     }
 }
 
-template <int MODE, int L3V, bool ARGMAX = false>
+// CM = ChainMode; MODE = the chain it names, MC = rows per chunk: 96 in the two product instantiations <kFstn | kTrunk, 3, false>, else 64
+template <int CM, int L3V, bool ARGMAX = false>
 __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(ChainArgs a) {
-    // act0 (ld 68) then act2: float image (ld 132), or - L3V = 3 - three bf16 planes of 272-byte rows
-    __shared__ __attribute__((aligned(16))) float bufA[L3V == 3 ? 3 * kPlaneB / 4 : kMC * kLd2];
-    __shared__ __attribute__((aligned(16))) float bufB[L3V == 3 ? 3 * kPlane1B / 4 : kMC * kLd1];  // act1 (L3V = 3: three bf16 planes)
-    __shared__ __attribute__((aligned(16))) float xs[kMC * 4];       // transformed inputs of the chunk (x,y,z,-)
+    constexpr int MODE = CM >= kFstn64 ? CM - kFstn64 + kFstn : CM;
+    constexpr int MC = (CM == kFstn || CM == kTrunk) && L3V == 3 && !ARGMAX ? kMC96 : kMC;
+    static_assert(CM < kFstn64 || (L3V == 3 && !ARGMAX), "kFstn64 / kTrunk64: the 64-row twins of the product instantiations only");
+    // act0 (ld 68) then act2: float image (ld 132), or - L3V = 3 - three bf16 planes of 256-byte rows.  MC = 96: the ONE image
+    // that act0, act1 and act2 share (kAct1Off); bufB is then a placeholder for the 64-row bases below and takes no LDS
+    __shared__ __attribute__((aligned(16))) float bufA[L3V == 3 ? 3 * MC * kLdB / 4 : kMC * kLd2];
+    __shared__ __attribute__((aligned(16))) float bufB[MC == kMC96 ? 4 : (L3V == 3 ? 3 * kPlane1B / 4 : kMC * kLd1)];  // act1 (L3V = 3: three bf16 planes)
+    __shared__ __attribute__((aligned(16))) float xs[MC * 4];        // transformed inputs of the chunk (x,y,z,-)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int item = a.item_order ? a.item_order[blockIdx.x] : blockIdx.x;
@@ -364,8 +389,9 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         for (int c = tid; c < kFeat; c += kThreads) outp[c] = -INFINITY;
         return;
     }
-    const int nchunks = (nrows + kMC - 1) / kMC;
+    const int nchunks = (nrows + MC - 1) / MC;
 
+    // (64-row chunks: stage 0b's channel and row group, the fp32 weight images and the per-lane bases; the 96-row body derives its own)
     const int c0 = tid & 63, rg = tid >> 6;
     const f32x4 win = *reinterpret_cast<const f32x4*>(a.w_in + c0 * 4);
     const int wave_s = uniform(wave);
@@ -387,11 +413,11 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
 #pragma unroll
     for (int q = 0; q < NRUN; ++q) { runmax[q] = -INFINITY; runarg[q] = 0; }
 
-    // Input points travel ahead in registers: lanes 0..15 of each wave own 16 rows of a chunk.  The
+    // Input points travel ahead in registers: lanes 0..15 (23) of each wave own 16 (24) rows of a chunk.  The
     // row index of chunk c+2 and the coordinates of chunk c+1 are requested while chunk c computes, so
     // neither of the two dependent global loads is ever waited for.
-    const bool fetcher = lane < 16;
-    const int frow = wave * 16 + lane;
+    const bool fetcher = lane < MC / 4;
+    const int frow = wave * (MC / 4) + lane;
     const uint16_t* rowp = a.rows + (size_t)item * kRowCap + frow;
     float px = 0.f, py = 0.f, pz = 0.f;
     auto load_point = [&](int p) {
@@ -405,7 +431,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     int pnext = 0;
     if (fetcher) {
         load_point(rowp[0]);
-        if (nchunks > 1) pnext = rowp[kMC];
+        if (nchunks > 1) pnext = rowp[MC];
     }
 
     BRing ring;
@@ -418,14 +444,145 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     if (L3V == 3) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {  // l3_pass_bf3: k-steps 0..1 of n-tile 0, both halves; l3_pass_bf3_2x2: k-step 0 of n-tiles 0 and 1
-            const bool single = ARGMAX || a.l3_single;
+            const bool single = MC == kMC;   // 64-row chunks: the arg-max instantiation and twin kTwinChainL3Single
             ring3.r[i] = b3_load16(w3rs, b16_lane_off(lane), single ? 0 : i >> 1, single ? i >> 1 : 0, i & 1, wave_s);
         }
     }
+    if constexpr (MC == kMC96) {
+        // One 96-row chunk of MTS 32-row m-tiles.  Every chunk but an item's last is full, so the chunk loop holds the MTS = 3 body
+        // alone and the last chunk picks its own: with the three layer-3 loops inside one chunk loop the compiler keeps the weight
+        // ring and the running maxima in registers twice (before and inside each loop) and spills.
+        auto chunk = [&](auto mtc, const int ch) {
+            constexpr int mts = decltype(mtc)::value;
+            // ---- 96-row chunk: act0 (fp32, bytes 0 - 25.5 K), act1 (bf16 planes, bytes 36 K - 72 K) and act2 (bf16 planes, all 72 K)
+            //      in ONE image, five barriers.  Every row's arithmetic is the 64-row body's. ---------------------------------------
+            constexpr int kPlane96 = kMC96 * kLdB, kPlane96_1 = kMC96 * kLd1B, kAct1Off = 3 * kPlane96 - 3 * kPlane96_1;
+            static_assert(kMC96 * kLd1 * 4 <= kAct1Off, "act0 and act1 are disjoint");
+            unsigned char* const img = reinterpret_cast<unsigned char*>(bufA);
+            unsigned char* const act1 = img + kAct1Off;
+            // Every per-lane address below derives from `ln`, a copy of the lane index the compiler cannot see through: it otherwise
+            // hoists some eighty loop-invariant addresses out of the chunk loop and keeps them in registers across layer 3, whose
+            // 96 + 48 + 36 registers leave no room for them (they cost a few VALU instructions per chunk instead).
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int fl = ln & 31, fh = ln >> 5, l15 = ln & 15, kq = ln >> 4;
+            const f32x4 wi = *reinterpret_cast<const f32x4*>(a.w_in + ln * 4);   // per chunk, ahead of the barrier: four registers fewer across layer 3
+            // stage 0a: input transform
+            if (fetcher) {
+                float x = px, y = py, z = pz;
+                const float* t9 = a.trans + (size_t)item * 9;  // uniform -> scalar loads
+                const float x2 = fmaf(z, t9[6], fmaf(y, t9[3], x * t9[0]));
+                const float y2 = fmaf(z, t9[7], fmaf(y, t9[4], x * t9[1]));
+                const float z2 = fmaf(z, t9[8], fmaf(y, t9[5], x * t9[2]));
+                *reinterpret_cast<f32x4*>(xs + frow * 4) = (f32x4){x2, y2, z2, 0.f};
+            }
+            __syncthreads();  // also orders the previous chunk's L3 reads of the image before stage 0b and layer 1 rewrite it
+            if (fetcher && ch + 1 < nchunks) {
+                load_point(pnext);
+                if (ch + 2 < nchunks) pnext = rowp[(ch + 2) * MC];
+            }
+            // stage 0b: 3 -> 64 (+bn, relu), thread = (channel lane, the wave's 24 rows)
+            {
+                float* dst = bufA + wave_s * 24 * kLd1 + ln;
+#pragma unroll 4
+                for (int i = 0; i < 24; ++i) {
+                    const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + (wave_s * 24 + i) * 4);
+                    const float f = fmaf(wi[2], xv[2], fmaf(wi[1], xv[1], wi[0] * xv[0])) + wi[3];
+                    dst[i * kLd1] = fmaxf(f, 0.f);
+                }
+            }
+            // L1: 64 -> 64, 3 x 2 tiles of 32 x 32 (transposed): wave = (m-tile parity, n-tile); the even waves also take m-tile 2
+            {
+                const int nt = wave_s >> 1;
+                const int wq = (wave_s >> 1) * 8 * kFragBytes;
+                f32x4 bw[8];  // weight fragments are requested before the barrier, consumed after it
+#pragma unroll
+                for (int kb = 0; kb < 8; ++kb) bw[kb] = wbuf_load(w1b, wq + kb * kFragBytes);
+                f32x4 bq[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+                if (MODE == kFstn) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b1 + nt * 32 + 8 * g + 4 * fh);
+                }
+                __syncthreads();
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int mt = (wave_s & 1) + 2 * s;
+                    if (mt < mts) {
+                        f32x16 acc = {0};
+#pragma unroll
+                        for (int kb = 0; kb < 8; ++kb) {
+                            acc = mfma4(bw[kb], lds_frag<kLd1>(bufA + (mt * 32 + fl) * kLd1 + 4 * fh, 0, kb), acc);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        ct_tile_to_planes_swz<kLd1B, kPlane96_1>(act1, mt * 32 + fl, nt * 4, ln, [&](int r) {
+                            const float v = acc[r] + bq[r >> 2][r & 3];
+                            return (MODE == kFstn) ? fmaxf(v, 0.f) : v;
+                        });
+                    }
+                }
+            }
+            // L2: 64 -> 128 (+bn, relu) on v_mfma_f32_16x16x32_bf16, transposed tiles: wave w = the 32 channels of n-tile w for every
+            // m-tile, so its four weight fragments (2 k-steps x 2 halves, requested before the barrier) are loaded once per chunk.  The
+            // 96 x 32 outputs stay in registers until every wave has read act1, which act2 overwrites.
+            {
+                const int boff = b16_lane_off(ln), a1off = a16_lane_off<kLd1B>(ln);
+                B3 bw[4];
+#pragma unroll
+                for (int f = 0; f < 4; ++f) bw[f] = b3_load16_l2(w2rs, boff, wave_s, f >> 1, f & 1);   // fragment f = (k-step, half)
+                f32x4 acc[2][3][2];
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int mt = 0; mt < 3; ++mt) { acc[hf][mt][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[hf][mt][1] = acc[hf][mt][0]; }
+                __syncthreads();
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                    for (int mt = 0; mt < 3; ++mt) {
+                        if (mt < mts) {
+                            bf16x8 af[2][3];
+#pragma unroll
+                            for (int pi = 0; pi < 2; ++pi) a16_load<kLd1B, kPlane96_1>(af[pi], act1, a1off, 2 * mt + pi, t);
+#pragma unroll
+                            for (int hf = 0; hf < 2; ++hf) mfma16_bf3_col_tr<2>(bw[2 * t + hf], af, acc[hf][mt]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                __syncthreads();   // act1 is read: act2 may take its place
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf) {
+                    const int c = wave_s * 32 + 16 * hf;
+                    const f32x4 bq = *reinterpret_cast<const f32x4*>(a.b2 + c + 4 * kq);
+#pragma unroll
+                    for (int mt = 0; mt < 3; ++mt) {
+                        if (mt < mts) {
+#pragma unroll
+                            for (int pi = 0; pi < 2; ++pi) {
+                                const f32x4 v = {fmaxf(acc[hf][mt][pi][0] + bq[0], 0.f), fmaxf(acc[hf][mt][pi][1] + bq[1], 0.f),
+                                                 fmaxf(acc[hf][mt][pi][2] + bq[2], 0.f), fmaxf(acc[hf][mt][pi][3] + bq[3], 0.f)};
+                                c16_tile_to_planes_swz<kLdB, kPlane96>(img, mt * 32 + 16 * pi + l15, c / 8, ln, v);
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            // L3: 128 -> 1024, running column max
+            {
+                const int aoff = a16_lane_off<kLdB>(ln), boff = b16_lane_off(ln);
+                l3_pass_bf3_2x2<mts, kPlane96>(w3rs, boff, img, aoff, wave_s, runmax, ring3);
+            }
+        };
+        for (int ch = 0; ch + 1 < nchunks; ++ch) chunk(std::integral_constant<int, 3>{}, ch);
+        const int rows_last = nrows - (nchunks - 1) * MC;
+        if (rows_last > 64)      chunk(std::integral_constant<int, 3>{}, nchunks - 1);
+        else if (rows_last > 32) chunk(std::integral_constant<int, 2>{}, nchunks - 1);
+        else                     chunk(std::integral_constant<int, 1>{}, nchunks - 1);
+    } else   // 64-row chunks: the loop below
     for (int ch = 0; ch < nchunks; ++ch) {
         const int rows_here = min(kMC, nrows - ch * kMC);
         const int mts = rows_here > 32 ? 2 : 1;
-
         // ---- stage 0a: input transform (models/pointnet.py:67-69) --------------------------
         if (fetcher) {
             float x = px, y = py, z = pz;
@@ -441,7 +598,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         __syncthreads();  // also orders the previous chunk's L3 reads of bufA before stage 0b rewrites it
         if (fetcher && ch + 1 < nchunks) {
             load_point(pnext);
-            if (ch + 2 < nchunks) pnext = rowp[(ch + 2) * kMC];
+            if (ch + 2 < nchunks) pnext = rowp[(ch + 2) * MC];
         }
         // ---- stage 0b: 3 -> 64 (+bn, relu), thread = (channel c0, 16 rows) -----------------
         {
@@ -574,12 +731,9 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
                 const int row0 = ch * kMC + 4 * (lane >> 4);
                 if (mts == 2) l3_pass_bf3<2, true>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg, row0);
                 else          l3_pass_bf3<1, true>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg, row0);
-            } else if (a.l3_single) {
+            } else {   // twin kTwinChainL3Single (launch_chain): one n-tile per pass, the bitwise reference of the 96-row kernel
                 if (mts == 2) l3_pass_bf3<2>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg);
                 else          l3_pass_bf3<1>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3, runarg);
-            } else {
-                if (mts == 2) l3_pass_bf3_2x2<2>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3);
-                else          l3_pass_bf3_2x2<1>(w3rs, boff, ab3, aoff, wave_s, runmax, ring3);
             }
         } else {
             const bool tail = !ARGMAX && a.tail16 && rows_here - 32 * (mts - 1) <= 16;   // (uniform) the last m-tile holds <= 16 rows
@@ -668,8 +822,13 @@ __global__ __launch_bounds__(kThreads) void pn_prepare_kernel(const int32_t* __r
 // ---- compacted row list of every work item (one wave per item) --------------------------------
 // Coalition items: keep[item] (null = everything), centre appended iff a point is masked.
 // Pre-pool items (prepool != 0): item = cloud*(R+with_centre) + r; r < R keeps region r only (no
-// centre), r == R is the centre alone.  The list is padded to a multiple of kMC with replicas of a
-// valid row (duplicates never change a max).
+// centre), r == R is the centre alone.  The list is padded with replicas of a valid row (duplicates
+// never change a max) to a multiple of the chunk size of either chain kernel, whichever ends later:
+// the 96-row kernel's fetch lanes read whole chunks (at most 43 x 96 = 4128 <= kRowCap entries).
+__device__ __forceinline__ int padded_rows(int nrows) {
+    static_assert((kMaxN + kMC96 - 1) / kMC96 * kMC96 <= kRowCap, "a padded row list fits its stride");
+    return max((nrows + kMC - 1) / kMC * kMC, (nrows + kMC96 - 1) / kMC96 * kMC96);
+}
 __global__ __launch_bounds__(64) void pn_rows_kernel(const uint16_t* __restrict__ sorted_all,
                                                      const int32_t* __restrict__ roff_all,
                                                      const uint64_t* __restrict__ keep_all,
@@ -719,7 +878,7 @@ __global__ __launch_bounds__(64) void pn_rows_kernel(const uint16_t* __restrict_
         const int rl = __ffsll((long long)last) - 1;
         padval = sorted_pts[roff[rl + 1] - 1];
     }
-    const int npad = (nrows + kMC - 1) / kMC * kMC;
+    const int npad = padded_rows(nrows);
     for (int i = nkept + lane; i < npad; i += 64) rows[i] = (uint16_t)padval;
     if (lane == 0) nrows_all[item] = nrows | (add_centre ? (1 << 16) : 0);
 }
@@ -823,7 +982,7 @@ __global__ __launch_bounds__(64) void pn_rows_wide_kernel(const uint16_t* __rest
         if (!add_centre && nkept > 0) padval = sorted_pts[roff[last_r + 1] - 1];   // padding: the centre if present, else the last kept point
     }
     const int nrows = nkept + (add_centre ? 1 : 0);
-    const int npad = (nrows + kMC - 1) / kMC * kMC;
+    const int npad = padded_rows(nrows);
     for (int i = nkept + lane; i < npad; i += 64) rows[i] = (uint16_t)padval;
     if (lane == 0) nrows_all[item] = nrows | (add_centre ? (1 << 16) : 0);
 }
@@ -961,14 +1120,22 @@ template <int MODE>
 void launch_chain(const ChainArgs& a, hipStream_t st) {
     // twins kTwinChainL3Fp32 / kTwinChainL3Fp32NoTail16: layer 3 on the fp32 MFMA (round 3's kernel; A/B and tests)
     const bool fp32_l3 = iq::twin() == iq::kTwinChainL3Fp32 || iq::twin() == iq::kTwinChainL3Fp32NoTail16;
-    if (MODE == kTrunk && a.argrow && a.w3_bf3 && a.w2_bf3 && !fp32_l3)
-        hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 3, true>), dim3(a.items), dim3(kThreads), 0, st, a);
-    else if (MODE == kTrunk && a.argrow)
-        hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 2, true>), dim3(a.items), dim3(kThreads), 0, st, a);
-    else if (MODE != kPrepool && a.w3_bf3 && a.w2_bf3 && !fp32_l3)
-        hipLaunchKernelGGL((pn_chain_kernel<MODE, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
-    else
-        hipLaunchKernelGGL((pn_chain_kernel<MODE, 2>), dim3(a.items), dim3(kThreads), 0, st, a);
+    const bool bf3 = a.w3_bf3 && a.w2_bf3 && !fp32_l3;
+    if constexpr (MODE == kTrunk) {
+        if (a.argrow) {
+            if (bf3) hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 3, true>), dim3(a.items), dim3(kThreads), 0, st, a);
+            else     hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 2, true>), dim3(a.items), dim3(kThreads), 0, st, a);
+            return;
+        }
+    }
+    if constexpr (MODE != kPrepool) {
+        if (bf3) {   // the product path: 96-row chunks; twin kTwinChainL3Single: 64-row chunks, one n-tile per pass (its bitwise reference)
+            if (a.l3_single) hipLaunchKernelGGL((pn_chain_kernel<MODE - kFstn + kFstn64, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
+            else             hipLaunchKernelGGL((pn_chain_kernel<MODE, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((pn_chain_kernel<MODE, 2>), dim3(a.items), dim3(kThreads), 0, st, a);
 }
 
 }  // namespace
