@@ -145,12 +145,14 @@ def _fc(x, sd, name):
     return F.linear(x, sd[name + ".weight"], sd[name + ".bias"])
 
 
-def _stn(x, sd, p, k):
-    """models/pointnet.py:29-47 - STNkd.forward."""
+def _stn(x, sd, p, k, aux=None):
+    """models/pointnet.py:29-47 - STNkd.forward.  ``aux``: a dict that receives the pooled layer as "<stn|fstn>_pool"."""
     h = F.relu(_bn(_conv(x, sd, p + ".conv1"), sd, p + ".bn1"))
     h = F.relu(_bn(_conv(h, sd, p + ".conv2"), sd, p + ".bn2"))
     h = F.relu(_bn(_conv(h, sd, p + ".conv3"), sd, p + ".bn3"))
     h = torch.max(h, 2, keepdim=True)[0].reshape(-1, 1024)
+    if aux is not None:
+        aux[p.rsplit(".", 1)[-1] + "_pool"] = h
     h = F.relu(_bn(_fc(h, sd, p + ".fc1"), sd, p + ".bn4"))
     h = F.relu(_bn(_fc(h, sd, p + ".fc2"), sd, p + ".bn5"))
     h = _fc(h, sd, p + ".fc3")
@@ -158,15 +160,18 @@ def _stn(x, sd, p, k):
     return h.reshape(-1, k, k)
 
 
-def pointnet_forward(sd, x):
+def pointnet_forward(sd, x, return_aux=False):
     """models/pointnet.py:64-89,109-115 - eval-mode PointNetCls.  x (B,3,N) float32 ->
-    (logits (B,10), trans_feat (B,64,64), crt_points (B,1024) int64)."""
-    trans = _stn(x, sd, "feat.stn", 3)
+    (logits (B,10), trans_feat (B,64,64), crt_points (B,1024) int64).  Runs in the dtype of ``sd`` and ``x`` (float64 too).
+    ``return_aux``: a fourth entry {"trunk": the pre-pool activations (B,1024,N) that crt_points indexes, "stn_pool" /
+    "fstn_pool": the two STNs' pooled (post-ReLU) layers (B,1024)}."""
+    aux = {}
+    trans = _stn(x, sd, "feat.stn", 3, aux)
     h = torch.bmm(x.transpose(2, 1), trans).transpose(2, 1)
     h = F.relu(_bn(_conv(h, sd, "feat.conv1"), sd, "feat.bn1"))
     trans_feat = None
     if "feat.fstn.conv1.weight" in sd:   # feature_transform (models/pointnet.py:72-78); None without it
-        trans_feat = _stn(h, sd, "feat.fstn", 64)
+        trans_feat = _stn(h, sd, "feat.fstn", 64, aux)
         h = torch.bmm(h.transpose(2, 1), trans_feat).transpose(2, 1)
     h = F.relu(_bn(_conv(h, sd, "feat.conv2"), sd, "feat.bn2"))
     h = _bn(_conv(h, sd, "feat.conv3"), sd, "feat.bn3")
@@ -174,6 +179,9 @@ def pointnet_forward(sd, x):
     g = g.reshape(-1, 1024)
     g = F.relu(_bn(_fc(g, sd, "fc1"), sd, "bn1"))
     g = F.relu(_bn(_fc(g, sd, "fc2"), sd, "bn2"))  # dropout is identity in eval mode
+    if return_aux:
+        aux["trunk"] = h
+        return _fc(g, sd, "fc3"), trans_feat, crt, aux
     return _fc(g, sd, "fc3"), trans_feat, crt
 
 

@@ -69,9 +69,11 @@ def coalition_inputs(case):
 _MODELS = {}
 
 
-def coalition_model(family, device):
-    """(HIP model, state dict) of a family with the synthetic weights of seed 0, built once per process."""
-    if family not in _MODELS:
+def coalition_model(family, device, variant=None):
+    """(HIP model, state dict) of a family with the synthetic weights of seed 0, built once per process.  ``variant``: a name
+    tests/weight_variants.py's ``variant`` knows ("dead", "rescaled12", ...): that state dict instead, cached beside the base."""
+    key = family if variant is None else (family, variant)
+    if key not in _MODELS:
         from interpret_quality_amd import synth
         from interpret_quality_amd.dgcnn import DGCNN_cls, GCNN_cls
         from interpret_quality_amd.pointconv import PointConvDensityClsSsg
@@ -80,11 +82,15 @@ def coalition_model(family, device):
         cls, sdf = {"pointnet": (PointNetCls, synth.pointnet_state_dict), "pointnet2": (PointNet2ClsMsg, synth.pointnet2_state_dict),
                     "pointconv": (PointConvDensityClsSsg, synth.pointconv_state_dict), "dgcnn": (DGCNN_cls, synth.dgcnn_state_dict),
                     "gcnn": (GCNN_cls, synth.dgcnn_state_dict)}[family]
-        sd = synth.to_torch(sdf(0))
+        if variant is None:
+            sd = synth.to_torch(sdf(0))
+        else:
+            import weight_variants
+            sd = synth.to_torch(weight_variants.variant(family, variant))
         m = cls(argparse.Namespace(dataset="modelnet10", k=20) if "cnn" in family else None)
         m.load_state_dict(sd)
-        _MODELS[family] = (m.to(device).eval(), sd)
-    return _MODELS[family]
+        _MODELS[key] = (m.to(device).eval(), sd)
+    return _MODELS[key]
 
 
 def _first(o):
@@ -106,12 +112,12 @@ def oracle_logits(family, sd, masked_bn3):
         return O.dgcnn_forward(sd, x, 20, family == "gcnn").numpy()
 
 
-def run_coalition_case(case, device, oracle_cap=None):
+def run_coalition_case(case, device, oracle_cap=None, variant=None):
     """-> (coalition logits, dense HIP logits of the materialised masked clouds, oracle logits or None, masked clouds).
-    The oracle runs when the case holds at most `oracle_cap` points in all (None: always)."""
+    The oracle runs when the case holds at most `oracle_cap` points in all (None: always).  ``variant``: as coalition_model's."""
     import torch
     from interpret_quality_amd import hip_ops
-    m, sd = coalition_model(case.family, device)
+    m, sd = coalition_model(case.family, device, variant)
     clouds_h, rid_h, keep, cloud_of = coalition_inputs(case)
     clouds = torch.from_numpy(clouds_h).to(device)
     centers = clouds.mean(dim=1)
