@@ -1,4 +1,4 @@
-// bf16x3 building blocks (gfx950, v_mfma_f32_32x32x16_bf16; the 16x16x32 forms at the end are the PointNet chain kernel's layer 3):
+// bf16x3 building blocks (gfx950, v_mfma_f32_32x32x16_bf16; the 16x16x32 forms at the end are the PointNet chain kernel's layers 1-3):
 // float32 GEMMs on the bf16 matrix pipe, float32-exact.
 // A float32 is three bf16 terms, x = h + m + l (round to nearest, residuals exact); a product is the six largest of the nine
 // term products, each exact, accumulated in float32 (small terms first).  See DESIGN.md 5a and iq_pack_weight_bf3 (iq_linear.hip)
@@ -141,7 +141,7 @@ __device__ __forceinline__ void mfma_bf3_block(const bf16x8 (&a)[MT][3], const B
     mfma_term_block<0, 0, MT, NT>(a, b, acc);
 }
 
-// ---- v_mfma_f32_16x16x32_bf16 forms (PointNet chain kernel, layer 3) ---------------------------------------------------
+// ---- v_mfma_f32_16x16x32_bf16 forms (PointNet chain kernel, layers 1-3) ---------------------------------------------------
 // Operands (lane l: c = l & 15, kq = l >> 4): A = row c, channels 8 kq .. 8 kq + 7 of the 32-channel k-step; B = column c, the same
 // channels; C = rows 4 kq + i (register i < 4) of column c.
 //
@@ -157,8 +157,8 @@ __device__ __forceinline__ int b16_lane_off(int lane) {
 // whose 16-byte pieces are stored XOR-swizzled by the row: piece p of row r lies at ROWB r + 16 (p ^ swz(r)), swz(r) = r & 15
 // (256-byte rows) or (r >> 1) & 7 (128-byte rows: two rows share a 256-byte bank line).  The 16x16x32 read (row c, piece 4 t + kq)
 // is then conflict-free: a ds_read_b128 lane group holds rows {0-3, 12-15} of one kq and rows {4-11} of the next, the XOR maps both
-// sets onto disjoint sixteen-byte bank groups (with padded rows that pattern is 2-way conflicted).  The planes' only writers are the
-// epilogues of layers 1 and 2 (ct_tile_to_planes_swz, c16_tile_to_planes_swz).  a16_lane_off: the per-lane byte offset of k-step
+// sets onto disjoint sixteen-byte bank groups (with padded rows that pattern is 2-way conflicted).  The planes' only writers are
+// stage 0b (act0: stage0b_planes, iq_pointnet.hip) and the epilogues of layers 1 and 2 (c16_tile_to_planes_swz).  a16_lane_off: the per-lane byte offset of k-step
 // 0; k-step t is that offset ^ (64 t).
 template <int ROWB>
 __device__ __forceinline__ int swz_of_row(int row) {
@@ -204,6 +204,16 @@ __device__ __forceinline__ void c16_tile_to_planes_swz(unsigned char* plane0, in
     *reinterpret_cast<u32x2*>(o) = h;
     *reinterpret_cast<u32x2*>(o + PLANEB) = m;
     *reinterpret_cast<u32x2*>(o + 2 * PLANEB) = l;
+}
+
+// A 16x16x32 weight fragment split in registers (PointNet chain kernel, layer 1): the lane's eight consecutive float32 k values
+// (two float4s of a 32x32x2 fragment image, iq_mfma.h) -> their three bf16 terms
+__device__ __forceinline__ B3 b3_split8(f32x4 lo, f32x4 hi) {
+    u32x2 h0, m0, l0, h1, m1, l1;
+    split4(lo, h0, m0, l0);
+    split4(hi, h1, m1, l1);
+    return B3{__builtin_bit_cast(bf16x8, u32x4{h0[0], h0[1], h1[0], h1[1]}), __builtin_bit_cast(bf16x8, u32x4{m0[0], m0[1], m1[0], m1[1]}),
+              __builtin_bit_cast(bf16x8, u32x4{l0[0], l0[1], l1[0], l1[1]})};
 }
 
 // MT m-tiles x ONE 16-column n-tile of one 32-channel k-step: the six products of mfma_bf3 in the same order (small terms first),

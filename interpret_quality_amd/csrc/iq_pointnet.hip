@@ -15,15 +15,19 @@
 // L3V = 2: v_mfma_f32_32x32x2_f32 throughout (exact fp32 fma chains).  A operands come from LDS (row stride padded by 4 floats:
 // conflict-free ds_read_b128), B operands (weights) stream from L2 in a pre-packed fragment order (1 KiB contiguous per wave-load).
 // LDS = 52 KB -> 3 workgroups/CU.
-// L3V = 3 (the product path of the feature-STN and trunk chains): layers 2-3 as six exact bf16 products per float32 product on
+// L3V = 3 (the product path of the feature-STN and trunk chains): layers 1-3 as six exact bf16 products per float32 product on
 // v_mfma_f32_16x16x32_bf16 (iq_bf3.h; DESIGN.md 5a: the kernel is power-bound and this shape holds a 10 % higher clock than
-// 32x32x16), activations as three swizzled bf16 planes in LDS.  LDS = 74.8 KB, <= 256 VGPRs -> 2 workgroups/CU.
+// 32x32x16), activations - act0 included, split by stage 0b - as three swizzled bf16 planes in LDS.  Layer 1 reads its weights out
+// of the SAME fp32 images as the fp32 kernels (the packed fstn.conv1, the per-coalition transform) and splits them into bf16 terms
+// in registers, four b128 loads per wave and chunk (l1_raw_load, l1_bf3): wave w = the 16 channels of n-tile w for every 16-row
+// m-tile.  No v_mfma_f32_32x32x2_f32 is left in these kernels (tests/test_isa_chain_l1_cpu.py).  LDS = 74.8 KB, <= 256 VGPRs ->
+// 2 workgroups/CU.
 // The two product instantiations (<kFstn | kTrunk, 3, false>) work on 96-ROW chunks: a layer-3 weight fragment then feeds six
 // 16-row m-tiles instead of four, a third less weight streaming out of L2 per row.  Two workgroups still fit a CU because act0,
-// act1 and act2 share ONE 72 KB image (act0 bytes 0 - 25.5 K, act1 36 - 72 K, act2 all of it: layer 2 keeps its 96 x 32 outputs per
-// wave in registers until every wave has read act1, one more barrier per chunk): LDS = 73.5 KB, 254-256 VGPRs, no scratch.  Every
-// row's arithmetic is the 64-row kernels', which stay as they are (pre-pool, fp32 twins, arg-max, twin kTwinChainL3Single) and are the
-// 96-row kernel's bitwise reference.  Row lists are padded for both chunk sizes (padded_rows).
+// act1 and act2 share ONE 72 KB image (act0 bytes 0 - 36 K, act1 36 - 72 K, act2 all of it: layer 2 keeps its 96 x 32 outputs per
+// wave in registers until every wave has read act1, one more barrier per chunk): LDS = 73.5 KB, 252 VGPRs, no scratch.  Every
+// row's arithmetic is the 64-row kernels', which stay as they are from layer 2 on (pre-pool, fp32 twins, arg-max, twin
+// kTwinChainL3Single) and are the 96-row kernel's bitwise reference.  Row lists are padded for both chunk sizes (padded_rows).
 #include <algorithm>
 #include <type_traits>
 
@@ -364,13 +368,80 @@ __device__ __forceinline__ void l3_tail16(const WBuf& w3, const float* act2, int
     }
 }
 
+// ---- stage 0b and layer 1 of the bf16x3 kernels (L3V = 3): act0 as three bf16 planes, layer 1 on v_mfma_f32_16x16x32_bf16 --------
+// act0 has act1's format: three planes of unpadded, XOR-swizzled 128-byte rows (iq_bf3.h), read with a16_load<kLd1B, ...>.
+// stage 0b, 3 -> 64 (+bn, relu): thread t = (channel quad t & 15, rows (t >> 4) + 16 i), so a lane splits four consecutive channels
+// of a row into one 8-byte store per plane and a wave's store covers four whole rows (512 contiguous bytes: conflict-free).
+// wi[j] = the folded 3 -> 64 layer's row of channel 4 (t & 15) + j.
+template <int ROWS, int PLANEB>
+__device__ __forceinline__ void stage0b_planes(unsigned char* act0, const float* xs, const f32x4 (&wi)[4], int t) {
+    const int cq = t & 15;
+#pragma unroll
+    for (int i = 0; i < ROWS / 16; ++i) {
+        const int row = (t >> 4) + 16 * i;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + row * 4);
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = fmaxf(fmaf(wi[j][2], xv[2], fmaf(wi[j][1], xv[1], wi[j][0] * xv[0])) + wi[j][3], 0.f);
+        row4_to_planes<PLANEB>(act0 + row * kLd1B + 16 * ((cq >> 1) ^ swz_of_row<kLd1B>(row)) + 8 * (cq & 1), v);
+    }
+}
+
+// Layer 1's weights come out of the fp32 image that the fp32 kernels read (32x32x2 fragment order, iq_mfma.h: fragment (n-tile,
+// k-block kb of 8) = 1 KiB, lane (n & 31) + 32 h holds k = 8 kb + 4 h + 0..3 of column n).  Wave w owns the 16 output channels
+// n = 16 w + c; the 16x16x32 operand of lane (c, kq) at k-step t is k = 32 t + 8 kq + 0..7 = the two float4s of lanes (n & 31) and
+// 32 + (n & 31) of fragment (w >> 1, 4 t + kq): four b128 loads per chunk, split into bf16 terms in registers after the barrier.
+struct L1Raw { f32x4 r[2][2]; };   // [k-step][half of the eight k values]
+__device__ __forceinline__ L1Raw l1_raw_load(const __amdgpu_buffer_rsrc_t& rs, int ln, int wave_s) {
+    const int voff = ((ln >> 4) * 64 + 16 * (wave_s & 1) + (ln & 15)) * 16;
+    L1Raw w;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            w.r[t][h] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 512 * h, ((wave_s >> 1) * 8 + 4 * t) * kFragBytes, 0));
+    return w;
+}
+// 64 -> 64 over MT 16-row m-tiles, transposed tiles as layer 2 has them (the weight fragment is the A operand: lane (row l & 15 of
+// the m-tile, kq) holds channels 16 w + 4 kq + 0..3), two k-steps of 32 channels, the six products of mfma16_bf3_col_tr per k-step.
+// The m-tiles go G at a time; a tile's accumulation chain is the same whatever G, m-tile or chunk, so a row's result does not depend
+// on where it sits.  bq: b1 of the lane's four channels (RELU: the feature STN; the trunk's product has neither bias nor relu).
+template <int MT, int PLANEB, bool RELU>
+__device__ __forceinline__ void l1_bf3(const unsigned char* act0, unsigned char* act1, const L1Raw& raw, f32x4 bq, int ln, int wave_s) {
+    constexpr int G = MT % 3 == 0 ? 3 : 2;
+    static_assert(MT % G == 0, "m-tiles go G at a time");
+    const int a0off = a16_lane_off<kLd1B>(ln), l15 = ln & 15;
+    const B3 w[2] = {b3_split8(raw.r[0][0], raw.r[0][1]), b3_split8(raw.r[1][0], raw.r[1][1])};
+#pragma unroll
+    for (int p = 0; p < MT; p += G) {
+        f32x4 acc[G];
+#pragma unroll
+        for (int i = 0; i < G; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            bf16x8 af[G][3];
+#pragma unroll
+            for (int i = 0; i < G; ++i) a16_load<kLd1B, PLANEB>(af[i], act0, a0off, p + i, t);
+            mfma16_bf3_col_tr<G>(w[t], af, acc);
+        }
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            f32x4 v = acc[i];
+            if (RELU) v = (f32x4){fmaxf(v[0] + bq[0], 0.f), fmaxf(v[1] + bq[1], 0.f), fmaxf(v[2] + bq[2], 0.f), fmaxf(v[3] + bq[3], 0.f)};
+            c16_tile_to_planes_swz<kLd1B, PLANEB>(act1, 16 * (p + i) + l15, 2 * wave_s, ln, v);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // CM = ChainMode; MODE = the chain it names, MC = rows per chunk: 96 in the two product instantiations <kFstn | kTrunk, 3, false>, else 64
 template <int CM, int L3V, bool ARGMAX = false>
 __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(ChainArgs a) {
     constexpr int MODE = CM >= kFstn64 ? CM - kFstn64 + kFstn : CM;
     constexpr int MC = (CM == kFstn || CM == kTrunk) && L3V == 3 && !ARGMAX ? kMC96 : kMC;
     static_assert(CM < kFstn64 || (L3V == 3 && !ARGMAX), "kFstn64 / kTrunk64: the 64-row twins of the product instantiations only");
-    // act0 (ld 68) then act2: float image (ld 132), or - L3V = 3 - three bf16 planes of 256-byte rows.  MC = 96: the ONE image
+    // act0 (ld 68) then act2: float image (ld 132), or - L3V = 3 - act0 as three bf16 planes of 128-byte rows (24 KB), then act2
+    // as three bf16 planes of 256-byte rows.  MC = 96: the ONE image
     // that act0, act1 and act2 share (kAct1Off); bufB is then a placeholder for the 64-row bases below and takes no LDS
     __shared__ __attribute__((aligned(16))) float bufA[L3V == 3 ? 3 * MC * kLdB / 4 : kMC * kLd2];
     __shared__ __attribute__((aligned(16))) float bufB[MC == kMC96 ? 4 : (L3V == 3 ? 3 * kPlane1B / 4 : kMC * kLd1)];  // act1 (L3V = 3: three bf16 planes)
@@ -454,10 +525,10 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
         // ring and the running maxima in registers twice (before and inside each loop) and spills.
         auto chunk = [&](auto mtc, const int ch) {
             constexpr int mts = decltype(mtc)::value;
-            // ---- 96-row chunk: act0 (fp32, bytes 0 - 25.5 K), act1 (bf16 planes, bytes 36 K - 72 K) and act2 (bf16 planes, all 72 K)
+            // ---- 96-row chunk: act0 (bf16 planes, bytes 0 - 36 K), act1 (bf16 planes, bytes 36 K - 72 K) and act2 (bf16 planes, all 72 K)
             //      in ONE image, five barriers.  Every row's arithmetic is the 64-row body's. ---------------------------------------
             constexpr int kPlane96 = kMC96 * kLdB, kPlane96_1 = kMC96 * kLd1B, kAct1Off = 3 * kPlane96 - 3 * kPlane96_1;
-            static_assert(kMC96 * kLd1 * 4 <= kAct1Off, "act0 and act1 are disjoint");
+            static_assert(3 * kPlane96_1 <= kAct1Off, "act0 and act1 are disjoint");
             unsigned char* const img = reinterpret_cast<unsigned char*>(bufA);
             unsigned char* const act1 = img + kAct1Off;
             // Every per-lane address below derives from `ln`, a copy of the lane index the compiler cannot see through: it otherwise
@@ -465,8 +536,10 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             // 96 + 48 + 36 registers leave no room for them (they cost a few VALU instructions per chunk instead).
             int ln = lane;
             asm volatile("" : "+v"(ln));
-            const int fl = ln & 31, fh = ln >> 5, l15 = ln & 15, kq = ln >> 4;
-            const f32x4 wi = *reinterpret_cast<const f32x4*>(a.w_in + ln * 4);   // per chunk, ahead of the barrier: four registers fewer across layer 3
+            const int l15 = ln & 15, kq = ln >> 4;
+            f32x4 wi[4];   // per chunk, ahead of the barrier: no registers for them across layer 3
+#pragma unroll
+            for (int j = 0; j < 4; ++j) wi[j] = *reinterpret_cast<const f32x4*>(a.w_in + ((ln & 15) * 4 + j) * 4);
             // stage 0a: input transform
             if (fetcher) {
                 float x = px, y = py, z = pz;
@@ -481,45 +554,15 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
                 load_point(pnext);
                 if (ch + 2 < nchunks) pnext = rowp[(ch + 2) * MC];
             }
-            // stage 0b: 3 -> 64 (+bn, relu), thread = (channel lane, the wave's 24 rows)
+            // stage 0b: 3 -> 64 (+bn, relu) -> act0 as three bf16 planes
+            stage0b_planes<kMC96, kPlane96_1>(img, xs, wi, wave_s * 64 + ln);
+            // L1: 64 -> 64 on v_mfma_f32_16x16x32_bf16, transposed tiles: wave w = the 16 channels of n-tile w for every m-tile
             {
-                float* dst = bufA + wave_s * 24 * kLd1 + ln;
-#pragma unroll 4
-                for (int i = 0; i < 24; ++i) {
-                    const f32x4 xv = *reinterpret_cast<const f32x4*>(xs + (wave_s * 24 + i) * 4);
-                    const float f = fmaf(wi[2], xv[2], fmaf(wi[1], xv[1], wi[0] * xv[0])) + wi[3];
-                    dst[i * kLd1] = fmaxf(f, 0.f);
-                }
-            }
-            // L1: 64 -> 64, 3 x 2 tiles of 32 x 32 (transposed): wave = (m-tile parity, n-tile); the even waves also take m-tile 2
-            {
-                const int nt = wave_s >> 1;
-                const int wq = (wave_s >> 1) * 8 * kFragBytes;
-                f32x4 bw[8];  // weight fragments are requested before the barrier, consumed after it
-#pragma unroll
-                for (int kb = 0; kb < 8; ++kb) bw[kb] = wbuf_load(w1b, wq + kb * kFragBytes);
-                f32x4 bq[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                if (MODE == kFstn) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b1 + nt * 32 + 8 * g + 4 * fh);
-                }
+                const L1Raw raw = l1_raw_load(w1b.rsrc, ln, wave_s);   // requested before the barrier, split and consumed after it
+                f32x4 bq = {0.f, 0.f, 0.f, 0.f};
+                if (MODE == kFstn) bq = *reinterpret_cast<const f32x4*>(a.b1 + 16 * wave_s + 4 * kq);
                 __syncthreads();
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const int mt = (wave_s & 1) + 2 * s;
-                    if (mt < mts) {
-                        f32x16 acc = {0};
-#pragma unroll
-                        for (int kb = 0; kb < 8; ++kb) {
-                            acc = mfma4(bw[kb], lds_frag<kLd1>(bufA + (mt * 32 + fl) * kLd1 + 4 * fh, 0, kb), acc);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        ct_tile_to_planes_swz<kLd1B, kPlane96_1>(act1, mt * 32 + fl, nt * 4, ln, [&](int r) {
-                            const float v = acc[r] + bq[r >> 2][r & 3];
-                            return (MODE == kFstn) ? fmaxf(v, 0.f) : v;
-                        });
-                    }
-                }
+                l1_bf3<2 * mts, kPlane96_1, MODE == kFstn>(img, act1, raw, bq, ln, wave_s);
             }
             // L2: 64 -> 128 (+bn, relu) on v_mfma_f32_16x16x32_bf16, transposed tiles: wave w = the 32 channels of n-tile w for every
             // m-tile, so its four weight fragments (2 k-steps x 2 halves, requested before the barrier) are loaded once per chunk.  The
@@ -583,6 +626,16 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     for (int ch = 0; ch < nchunks; ++ch) {
         const int rows_here = min(kMC, nrows - ch * kMC);
         const int mts = rows_here > 32 ? 2 : 1;
+        // (L3V = 3) the per-lane addresses of stage 0b and layer 1 derive from `tq`, a copy of the thread index the compiler cannot see
+        // through, and the folded 3 -> 64 rows of the lane's four channels are loaded per chunk, ahead of the barrier: loop-invariant,
+        // they would otherwise sit in registers across layer 3, which has none to spare
+        [[maybe_unused]] int tq = tid;
+        [[maybe_unused]] f32x4 wi[4];
+        if constexpr (L3V == 3) {
+            asm volatile("" : "+v"(tq));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) wi[j] = *reinterpret_cast<const f32x4*>(a.w_in + ((tq & 15) * 4 + j) * 4);
+        }
         // ---- stage 0a: input transform (models/pointnet.py:67-69) --------------------------
         if (fetcher) {
             float x = px, y = py, z = pz;
@@ -600,8 +653,10 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             load_point(pnext);
             if (ch + 2 < nchunks) pnext = rowp[(ch + 2) * MC];
         }
-        // ---- stage 0b: 3 -> 64 (+bn, relu), thread = (channel c0, 16 rows) -----------------
-        {
+        // ---- stage 0b: 3 -> 64 (+bn, relu), thread = (channel c0, 16 rows); L3V = 3: act0 as three bf16 planes in bufA ----
+        if constexpr (L3V == 3) {
+            stage0b_planes<kMC, kPlane1B>(reinterpret_cast<unsigned char*>(bufA), xs, wi, tq);
+        } else {
             float* dst = ((MODE == kPrepool) ? bufB : bufA) + rg * 16 * kLd1 + c0;
 #pragma unroll 4
             for (int i = 0; i < 16; ++i) {
@@ -611,7 +666,17 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
             }
         }
         // ---- L1: 64 -> 64 ------------------------------------------------------------------
-        if (MODE != kPrepool) {
+        if constexpr (L3V == 3) {   // on v_mfma_f32_16x16x32_bf16 (l1_bf3): wave w = the 16 channels of n-tile w for every m-tile
+            const int ln = tq & 63;
+            const L1Raw raw = l1_raw_load(w1b.rsrc, ln, wave_s);   // requested before the barrier, split and consumed after it
+            f32x4 bq = {0.f, 0.f, 0.f, 0.f};
+            if (MODE == kFstn) bq = *reinterpret_cast<const f32x4*>(a.b1 + 16 * wave_s + 4 * (ln >> 4));
+            __syncthreads();
+            unsigned char* const act0 = reinterpret_cast<unsigned char*>(bufA);
+            unsigned char* const act1 = reinterpret_cast<unsigned char*>(bufB);
+            if (mts == 2) l1_bf3<4, kPlane1B, MODE == kFstn>(act0, act1, raw, bq, ln, wave_s);
+            else          l1_bf3<2, kPlane1B, MODE == kFstn>(act0, act1, raw, bq, ln, wave_s);
+        } else if (MODE != kPrepool) {
             const int mt = wave & 1, nt = wave >> 1;
             const int wq = (wave_s >> 1) * 8 * kFragBytes;
             f32x4 bw[8];  // weight fragments are requested before the barrier, consumed after it
@@ -622,31 +687,16 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
                 f32x16 acc = {0};
 #pragma unroll
                 for (int kb = 0; kb < 8; ++kb) {
-                    // L3V = 3: TRANSPOSED tile (the weight fragment as the A operand: iq_bf3.h, ct_tile_to_planes) - the same products in
-                    // the same order, the lane then holds its row's channels in register quads and act1 needs no two-lane trade
-                    if (L3V == 3) acc = mfma4(bw[kb], lds_frag<kLd1>(a1base_A + mt * 32 * kLd1, 0, kb), acc);
-                    else acc = mfma4(lds_frag<kLd1>(a1base_A + mt * 32 * kLd1, 0, kb), bw[kb], acc);
+                    acc = mfma4(lds_frag<kLd1>(a1base_A + mt * 32 * kLd1, 0, kb), bw[kb], acc);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                const float bias = (MODE == kFstn && L3V != 3) ? a.b1[nt * 32 + frag_lane] : 0.f;
-                if (L3V == 3) {   // act1 as three bf16 planes for layer 2; register r = channel c_row_i(r) + 4 frag_h of the n-tile
-                    f32x4 bq[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-                    if (MODE == kFstn) {
+                const float bias = (MODE == kFstn) ? a.b1[nt * 32 + frag_lane] : 0.f;
+                float* dst = c1base + mt * 32 * kLd1 + nt * 32;
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b1 + nt * 32 + 8 * g + 4 * frag_h);
-                    }
-                    ct_tile_to_planes_swz<kLd1B, kPlane1B>(reinterpret_cast<unsigned char*>(bufB), mt * 32 + frag_lane, nt * 4, lane, [&](int r) {
-                        const float v = acc[r] + bq[r >> 2][r & 3];
-                        return (MODE == kFstn) ? fmaxf(v, 0.f) : v;
-                    });
-                } else {
-                    float* dst = c1base + mt * 32 * kLd1 + nt * 32;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        float v = acc[i] + bias;
-                        if (MODE == kFstn) v = fmaxf(v, 0.f);
-                        dst[c_row_i(i) * kLd1] = v;
-                    }
+                for (int i = 0; i < 16; ++i) {
+                    float v = acc[i] + bias;
+                    if (MODE == kFstn) v = fmaxf(v, 0.f);
+                    dst[c_row_i(i) * kLd1] = v;
                 }
             }
         }
