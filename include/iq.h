@@ -56,8 +56,9 @@ enum {
  * 103: new entry points, no layout change (the standalone geometric ops: iq_index_points .. iq_density).
  * 104: new entry points, no layout change (exact games by full enumeration: iq_enum_keep_masks .. iq_exact_scratch_bytes).
  * 105: new entry points, no layout change (wide coalitions: iq_prefix_keep_masks_wide .. iq_pointnet_coalitions_wide).
- * 106: new entry point, no layout change (iq_context_keep_masks_wide: the interaction stage of wide games). */
-#define IQ_ABI_VERSION 106
+ * 106: new entry point, no layout change (iq_context_keep_masks_wide: the interaction stage of wide games).
+ * 107: new entry point, no layout change (iq_pointnet_prefix_coalitions_wide: prefix coalitions straight from permutations). */
+#define IQ_ABI_VERSION 107
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -603,6 +604,21 @@ int iq_pointnet_coalitions_wide(const iq_pointnet_weights* w, const float* cloud
                                 const int32_t* region_id, const uint64_t* keep /*B,W*/, const int32_t* cloud_of, float* logits,
                                 float* trans_feat_packed, void* workspace, size_t workspace_bytes, int B, int nclouds, int N,
                                 int R, int channel_first, iq_stream_t stream);
+
+/* The prefix coalitions of S permutations without keep rows: item o*(R+1) + i keeps orders[o][0..i-1], with the set semantics
+ * of iq_prefix_keep_masks_wide (an entry outside [0, R) is ignored, a region named twice counts once).  The row list of an item
+ * is a prefix of the permutation-ordered point list and its pooled input-STN feature the running maximum along the permutation
+ * (R rows of the pre-pool per permutation, not R^2 / 2); a row list holds the points of iq_pointnet_coalitions_wide's in another
+ * order and every pooling is an exact maximum, so logits and trans_feat_packed are that entry's on
+ * iq_prefix_keep_masks_wide(orders), bit for bit.  cloud_of[o] is the cloud of PERMUTATION o (required when 1 < nclouds != S);
+ * centers is required; clouds are channel-last.  1 <= R <= IQ_MAX_WIDE_REGIONS (for R <= 64 the bits are the narrow entry's).
+ * Workspace: iq_pointnet_wide_workspace_bytes(S*(R+1), nclouds, N, R). */
+int iq_pointnet_prefix_coalitions_wide(const iq_pointnet_weights* w, const float* clouds /*nclouds,N,3*/,
+                                       const float* centers /*nclouds,3*/, const int32_t* region_id /*nclouds,N*/,
+                                       const int32_t* orders /*S,R*/, const int32_t* cloud_of /*S or NULL*/,
+                                       float* logits /*S*(R+1),C*/, float* trans_feat_packed /*S*(R+1),4096 or NULL*/,
+                                       void* workspace, size_t workspace_bytes, int S, int nclouds, int N, int R,
+                                       iq_stream_t stream);
 
 /* The diagnostic entry points (HIP-event profiler, experiment knobs, debug counters) are NOT part of the drop-in surface:
  * they are declared in iq_debug.h. */

@@ -141,6 +141,8 @@ SIGNATURES = {
     "iq_pointnet_wide_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "iq_pointnet_coalitions_wide": (_I, [ctypes.POINTER(PointNetWeights), _P, _P, _P, _P, _P, _P, _P, _P, _SZ,
                                          _I, _I, _I, _I, _I, _P]),
+    "iq_pointnet_prefix_coalitions_wide": (_I, [ctypes.POINTER(PointNetWeights), _P, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                                _I, _I, _I, _I, _P]),
     "iq_profile_enable": (_I, [_I]),
     "iq_set_tuning": (_I, [_I, _I]),
     "iq_profile_read_work": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -151,7 +153,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 106   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 107   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -1037,6 +1037,115 @@ __global__ __launch_bounds__(64) void pn_rows_wide_kernel(const uint16_t* __rest
     if (lane == 0) nrows_all[item] = nrows | (add_centre ? (1 << 16) : 0);
 }
 
+// ---- prefix coalitions straight from permutations (iq_pointnet_prefix_coalitions_wide): no keep rows ---------------------------
+// Item o * (R + 1) + i keeps orders[o][0 .. i-1] with the set semantics of iq_prefix_keep_masks_wide: an entry outside [0, R) adds
+// nothing, and neither does a region that an earlier entry of the same permutation named.  The "seen" set is kept as the position
+// of every region's FIRST occurrence (atomicMin over the entries: the same table whatever the schedule), so all entries are
+// classified at once: entry i counts iff first_s[ord[i]] == i.  A region therefore counts once and a row list never exceeds N.
+static_assert(IQ_MAX_WIDE_REGIONS <= 4 * kThreads, "pn_rows_prefix_kernel: a thread scans four entries of a permutation");
+
+__device__ __forceinline__ void prefix_first_seen(const int32_t* __restrict__ ord, int R, int* first_s) {
+    for (int r = threadIdx.x; r < R; r += blockDim.x) first_s[r] = R;
+    __syncthreads();
+    for (int i = threadIdx.x; i < R; i += blockDim.x) {
+        const int r = ord[i];
+        if ((unsigned)r < (unsigned)R) atomicMin(&first_s[r], i);
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ int prefix_entry_region(const int32_t* __restrict__ ord, int R, const int* first_s, int i) {
+    const int r = ord[i];
+    return ((unsigned)r < (unsigned)R && first_s[r] == i) ? r : -1;   // -1: the entry adds nothing
+}
+
+// One workgroup per permutation.  P = the points of the counting entries in permutation order (LDS), pos[i] = points after i
+// entries (a scan over the R entry sizes); the row list of item i is P[0 : pos[i]], then the centre and the padding by the rules of
+// pn_rows_wide_kernel.  A wave writes an item, eight entries (16 bytes) per lane: kRowCap and every padded length are multiples of 8.
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+static_assert(kRowCap % 8 == 0 && kMC % 8 == 0 && kMC96 % 8 == 0, "row lists are written 8 entries at a time");
+
+__global__ __launch_bounds__(kThreads) void pn_rows_prefix_kernel(const uint16_t* __restrict__ sorted_all,
+                                                                  const int32_t* __restrict__ roff_all,
+                                                                  const int32_t* __restrict__ orders,
+                                                                  const int32_t* __restrict__ cloud_of, uint16_t* __restrict__ rows_all,
+                                                                  int32_t* __restrict__ nrows_all, int N, int R, int nclouds,
+                                                                  int with_centre) {
+    __shared__ __attribute__((aligned(16))) uint16_t P[kMaxN + 8];
+    __shared__ int first_s[IQ_MAX_WIDE_REGIONS];
+    __shared__ int src_s[IQ_MAX_WIDE_REGIONS];       // region of entry i, -1 = adds nothing
+    __shared__ int pos_s[IQ_MAX_WIDE_REGIONS + 1];
+    __shared__ int wsum_s[kThreads / 64];
+    const int o = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cloud = cloud_of ? cloud_of[o] : (nclouds == 1 ? 0 : o);
+    const int32_t* ord = orders + (size_t)o * R;
+    const int32_t* roff = roff_all + (size_t)cloud * (R + 1);
+    const uint16_t* sorted_pts = sorted_all + (size_t)cloud * N;
+    prefix_first_seen(ord, R, first_s);
+
+    // exclusive scan of the entry sizes: four consecutive entries per thread, the wave, then the four waves
+    int sz[4], tot = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = 4 * tid + k;
+        int r = -1;
+        if (i < R) src_s[i] = r = prefix_entry_region(ord, R, first_s, i);
+        sz[k] = r >= 0 ? roff[r + 1] - roff[r] : 0;
+        tot += sz[k];
+    }
+    int inc = tot;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off);
+        if (lane >= off) inc += t;
+    }
+    if (lane == 63) wsum_s[wave] = inc;
+    __syncthreads();
+    int run = inc - tot;
+    for (int w = 0; w < wave; ++w) run += wsum_s[w];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = 4 * tid + k;
+        if (i < R) {
+            pos_s[i] = run;
+            run += sz[k];
+            if (i == R - 1) pos_s[R] = run;
+        }
+    }
+    __syncthreads();
+
+    // P: slot p belongs to the entry i with pos[i] <= p < pos[i+1] (binary search; entries that add nothing have pos[i] == pos[i+1])
+    const int total = pos_s[R];   // <= N: every region counts once
+    for (int p = tid; p < total; p += kThreads) {
+        int lo = 0, hi = R - 1;   // the first entry whose end pos[i+1] exceeds p; pos[R] = total > p
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (pos_s[mid + 1] > p) hi = mid; else lo = mid + 1;
+        }
+        P[p] = sorted_pts[roff[src_s[lo]] + p - pos_s[lo]];
+    }
+    __syncthreads();
+
+    for (int i = wave; i <= R; i += kThreads / 64) {
+        const int nkept = pos_s[i];
+        const bool add_centre = with_centre && nkept < N;
+        const int nrows = nkept + (add_centre ? 1 : 0);
+        const unsigned short padval = (unsigned short)((add_centre || nkept == 0) ? N : P[nkept - 1]);   // the centre, else the last kept point
+        const size_t item = (size_t)o * (R + 1) + i;
+        uint16_t* rows = rows_all + item * kRowCap;
+        const int npad = padded_rows(nrows);
+        for (int j = lane * 8; j < npad; j += 64 * 8) {
+            u16x8 v = {padval, padval, padval, padval, padval, padval, padval, padval};
+            if (j < nkept) {      // j + 7 <= nkept + 6 < kMaxN + 8
+                const u16x8 p8 = *reinterpret_cast<const u16x8*>(&P[j]);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = j + k < nkept ? p8[k] : padval;
+            }
+            *reinterpret_cast<u16x8*>(&rows[j]) = v;
+        }
+        if (lane == 0) nrows_all[item] = nrows | (add_centre ? (1 << 16) : 0);
+    }
+}
+
 // ---- launch order: largest coalitions first (LPT), a counting sort on the chunk count ---------
 constexpr int kBins = kMaxN / kMC + 2;
 
@@ -1159,6 +1268,57 @@ __global__ __launch_bounds__(kThreads) void pn_stn_gather_wide_kernel(const floa
     reinterpret_cast<f32x4*>(out)[(size_t)item * (kFeat / 4) + threadIdx.x] = m;
 }
 
+// The same for the prefix coalitions of a permutation: the pooled feature of item i is the running maximum of the rows of G along
+// the permutation, R rows per permutation instead of R^2 / 2.  kFeat / 256 workgroups of one wave per permutation (a float4 of
+// channels per lane), kPrefixRows rows of G in flight.  max is exact and order-independent, so the bits are the gather's.  The wave
+// that owns channels 0 .. 255 also writes every item's cloud for the chain kernels (item_cloud, null for one cloud: they take a
+// cloud per ITEM, this entry a cloud per permutation).
+constexpr int kPrefixRows = 8;
+
+__global__ __launch_bounds__(64) void pn_stn_prefix_kernel(const float* __restrict__ G, const int32_t* __restrict__ nrows_all,
+                                                           const int32_t* __restrict__ orders,
+                                                           const int32_t* __restrict__ cloud_of, float* __restrict__ out,
+                                                           int32_t* __restrict__ item_cloud, int R, int nclouds, int with_centre) {
+    __shared__ int first_s[IQ_MAX_WIDE_REGIONS];
+    __shared__ int src_s[IQ_MAX_WIDE_REGIONS];
+    __shared__ unsigned char flag_s[IQ_MAX_WIDE_REGIONS + 1];
+    const int o = blockIdx.x, part = blockIdx.y, lane = threadIdx.x;
+    const int cloud = cloud_of ? cloud_of[o] : (nclouds == 1 ? 0 : o);
+    const int32_t* ord = orders + (size_t)o * R;
+    const size_t item0 = (size_t)o * (R + 1);
+    prefix_first_seen(ord, R, first_s);
+    for (int i = lane; i < R; i += 64) src_s[i] = prefix_entry_region(ord, R, first_s, i);
+    for (int i = lane; i <= R; i += 64) {
+        flag_s[i] = (unsigned char)(nrows_all[item0 + i] >> 16);   // a centre row exists (something was masked)
+        if (item_cloud && part == 0) item_cloud[item0 + i] = cloud;
+    }
+    __syncthreads();
+    const int per = R + with_centre;
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(G) + (size_t)cloud * per * (kFeat / 4) + part * 64 + lane;
+    f32x4* o4 = reinterpret_cast<f32x4*>(out) + item0 * (kFeat / 4) + part * 64 + lane;
+    const f32x4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    const f32x4 c = with_centre ? g4[(size_t)R * (kFeat / 4)] : ninf;
+    f32x4 m = ninf;
+    for (int i0 = 0; i0 <= R; i0 += kPrefixRows) {
+        f32x4 v[kPrefixRows];
+#pragma unroll
+        for (int q = 0; q < kPrefixRows; ++q) {
+            const int i = i0 + q;
+            const int r = __builtin_amdgcn_readfirstlane(i < R ? src_s[i] : -1);   // the same for every lane
+            v[q] = r >= 0 ? g4[(size_t)r * (kFeat / 4)] : ninf;
+        }
+#pragma unroll
+        for (int q = 0; q < kPrefixRows; ++q) {
+            const int i = i0 + q;
+            if (i > R) break;
+            f32x4 w = m;
+            if (flag_s[i]) { w[0] = fmaxf(w[0], c[0]); w[1] = fmaxf(w[1], c[1]); w[2] = fmaxf(w[2], c[2]); w[3] = fmaxf(w[3], c[3]); }
+            o4[(size_t)i * (kFeat / 4)] = w;
+            m[0] = fmaxf(m[0], v[q][0]); m[1] = fmaxf(m[1], v[q][1]); m[2] = fmaxf(m[2], v[q][2]); m[3] = fmaxf(m[3], v[q][3]);
+        }
+    }
+}
+
 // every item's 64 x 64 transform := one packed image (4096 floats), float4 per thread
 __global__ __launch_bounds__(kThreads) void pn_fill_rows_kernel(float* __restrict__ out, const float* __restrict__ image, int B) {
     const size_t t = (size_t)blockIdx.x * kThreads + threadIdx.x;
@@ -1267,22 +1427,25 @@ extern "C" int iq_pointnet_coalitions(const iq_pointnet_weights* w, const float*
 
 namespace {
 
-// The forward behind iq_pointnet_coalitions[_crt] (wide_words = 0: keep (B) masks, R <= IQ_MAX_REGIONS) and behind
-// iq_pointnet_coalitions_wide (wide_words = W: keep (B,W) rows).  Only the three kernels that read a mask differ; the chains, the
-// launch order and the heads are the same launches.
+// The forward behind iq_pointnet_coalitions[_crt] (wide_words = 0: keep (B) masks, R <= IQ_MAX_REGIONS), behind
+// iq_pointnet_coalitions_wide (wide_words = W: keep (B,W) rows) and behind iq_pointnet_prefix_coalitions_wide (wide_words = W and
+// orders (B / (R+1), R): item o*(R+1)+i keeps orders[o][:i], no keep rows; cloud_of then names a cloud per PERMUTATION).  Only the
+// kernels that fill rows, nrows and gbuf differ; the chains, the launch order and the heads are the same launches.
 int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const float* centers, const int32_t* region_id,
-                        const uint64_t* keep, int wide_words, const int32_t* cloud_of, float* logits, float* trans_feat_packed,
-                        int32_t* crt_points, void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int R,
-                        int channel_first, iq_stream_t stream) {
-    const char* who = wide_words ? "iq_pointnet_coalitions_wide" : "iq_pointnet_coalitions";   // the entry point a message names
+                        const uint64_t* keep, int wide_words, const int32_t* orders, const int32_t* cloud_of, float* logits,
+                        float* trans_feat_packed, int32_t* crt_points, void* workspace, size_t workspace_bytes, int B, int nclouds,
+                        int N, int R, int channel_first, iq_stream_t stream) {
+    const char* who = orders ? "iq_pointnet_prefix_coalitions_wide"                           // the entry point a message names
+                             : wide_words ? "iq_pointnet_coalitions_wide" : "iq_pointnet_coalitions";
     IQ_REQUIRE(B >= 0 && nclouds >= 1, "%s: B=%d nclouds=%d", who, B, nclouds);
     IQ_REQUIRE(w && clouds && region_id && (logits || B == 0), "%s: null pointer", who);
     IQ_REQUIRE(N >= 1 && N <= kMaxN, "%s: N=%d not in [1,%d]", who, N, kMaxN);
     const int max_regions = wide_words ? IQ_MAX_WIDE_REGIONS : IQ_MAX_REGIONS;
     IQ_REQUIRE(R >= 1 && R <= max_regions, "%s: R=%d not in [1,%d]", who, R, max_regions);
-    IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == B, "%s: cloud_of required when 1 < nclouds != B", who);
+    const int groups = orders ? B / (R + 1) : B;   // what cloud_of names a cloud for: a permutation, else a coalition
+    IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == groups, "%s: cloud_of required when 1 < nclouds != %s", who, orders ? "S" : "B");
     const int with_centre = centers ? 1 : 0;  // no centre = dense mode (nothing is ever masked)
-    IQ_REQUIRE(centers || !keep, "%s: keep masks need centers", who);
+    IQ_REQUIRE(centers || !(keep || orders), "%s: %s need centers", who, orders ? "prefix coalitions" : "keep masks");
     if (B == 0) return IQ_OK;
     const size_t need = wide_words ? iq_pointnet_wide_workspace_bytes(B, nclouds, N, R) : iq_pointnet_workspace_bytes(B, nclouds, N, R);
     if (!workspace || workspace_bytes < need)
@@ -1293,14 +1456,24 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     iq::ProfileSpan call_span(iq::kSlotCall, st);
 
     const int pre_items = nclouds * (R + with_centre);
+    // the chain kernels take a cloud per item: the prefix route writes one (pn_stn_prefix_kernel) where the launch order kept its
+    // bins, which nothing reads once the order is scattered
+    const int32_t* item_cloud = orders ? (nclouds > 1 ? ws.bin_of : nullptr) : cloud_of;
     if (wide_words) {
         hipLaunchKernelGGL(pn_prepare_wide_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
         if ((rc = iq::check_launch("pn_prepare_wide_kernel"))) return rc;
         hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
                            ws.rows_pre, ws.nrows_pre, N, R, wide_words, nclouds, with_centre, 1);
-        hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
-                           ws.nrows, N, R, wide_words, nclouds, with_centre, 0);
         if ((rc = iq::check_launch("pn_rows_wide_kernel"))) return rc;
+        if (orders) {
+            hipLaunchKernelGGL(pn_rows_prefix_kernel, dim3(groups), dim3(kThreads), 0, st, ws.sorted_pts, ws.roff, orders, cloud_of,
+                               ws.rows, ws.nrows, N, R, nclouds, with_centre);
+            if ((rc = iq::check_launch("pn_rows_prefix_kernel"))) return rc;
+        } else {
+            hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
+                               ws.nrows, N, R, wide_words, nclouds, with_centre, 0);
+            if ((rc = iq::check_launch("pn_rows_wide_kernel"))) return rc;
+        }
     } else {
         hipLaunchKernelGGL(pn_prepare_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
         if ((rc = iq::check_launch("pn_prepare_kernel"))) return rc;
@@ -1347,19 +1520,23 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     }
     if ((rc = iq::check_launch("pn_chain_kernel<prepool>"))) return rc;
 
-    if (wide_words)
+    if (orders)
+        hipLaunchKernelGGL(pn_stn_prefix_kernel, dim3(groups, kFeat / 256), dim3(64), 0, st, ws.G, ws.nrows, orders, cloud_of, ws.gbuf,
+                           item_cloud ? ws.bin_of : nullptr, R, nclouds, with_centre);
+    else if (wide_words)
         hipLaunchKernelGGL(pn_stn_gather_wide_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
                            R, wide_words, nclouds, with_centre);
     else
         hipLaunchKernelGGL(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
                            R, nclouds, with_centre);
-    if ((rc = iq::check_launch(wide_words ? "pn_stn_gather_wide_kernel" : "pn_stn_gather_kernel"))) return rc;
+    if ((rc = iq::check_launch(orders ? "pn_stn_prefix_kernel" : wide_words ? "pn_stn_gather_wide_kernel" : "pn_stn_gather_kernel")))
+        return rc;
     if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st))) return rc;
     if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st))) return rc;
     if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st))) return rc;
 
     // 2. feature-STN chain over each coalition's distinct points
-    a.cloud_of = cloud_of; a.trans = ws.trans;
+    a.cloud_of = item_cloud; a.trans = ws.trans;
     a.rows = ws.rows; a.nrows = ws.nrows;
     a.item_order = ws.order;
     a.w_in = w->feat_in;
@@ -1412,7 +1589,7 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
                                           float* logits, float* trans_feat_packed, int32_t* crt_points, void* workspace,
                                           size_t workspace_bytes, int B, int nclouds, int N, int R,
                                           int channel_first, iq_stream_t stream) {
-    return pointnet_coalitions(w, clouds, centers, region_id, keep, 0, cloud_of, logits, trans_feat_packed, crt_points, workspace,
+    return pointnet_coalitions(w, clouds, centers, region_id, keep, 0, nullptr, cloud_of, logits, trans_feat_packed, crt_points, workspace,
                                workspace_bytes, B, nclouds, N, R, channel_first, stream);
 }
 
@@ -1426,8 +1603,19 @@ extern "C" int iq_pointnet_coalitions_wide(const iq_pointnet_weights* w, const f
                                            float* logits, float* trans_feat_packed, void* workspace, size_t workspace_bytes,
                                            int B, int nclouds, int N, int R, int channel_first, iq_stream_t stream) {
     IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_pointnet_coalitions_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
-    return pointnet_coalitions(w, clouds, centers, region_id, keep, (R + 63) / 64, cloud_of, logits, trans_feat_packed, nullptr,
-                               workspace, workspace_bytes, B, nclouds, N, R, channel_first, stream);
+    return pointnet_coalitions(w, clouds, centers, region_id, keep, (R + 63) / 64, nullptr, cloud_of, logits, trans_feat_packed,
+                               nullptr, workspace, workspace_bytes, B, nclouds, N, R, channel_first, stream);
+}
+
+extern "C" int iq_pointnet_prefix_coalitions_wide(const iq_pointnet_weights* w, const float* clouds, const float* centers,
+                                                  const int32_t* region_id, const int32_t* orders, const int32_t* cloud_of,
+                                                  float* logits, float* trans_feat_packed, void* workspace, size_t workspace_bytes,
+                                                  int S, int nclouds, int N, int R, iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_pointnet_prefix_coalitions_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
+    IQ_REQUIRE(S >= 0 && S <= 0x7fffffff / (R + 1), "iq_pointnet_prefix_coalitions_wide: S=%d (R=%d)", S, R);
+    IQ_REQUIRE(centers && (orders || S == 0), "iq_pointnet_prefix_coalitions_wide: null pointer");
+    return pointnet_coalitions(w, clouds, centers, region_id, nullptr, (R + 63) / 64, orders, cloud_of, logits, trans_feat_packed,
+                               nullptr, workspace, workspace_bytes, S * (R + 1), nclouds, N, R, 0, stream);
 }
 
 // ---- host-side packing of the feature-STN output layer (generic packing: iq_linear.hip) ------------

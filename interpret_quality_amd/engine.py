@@ -191,7 +191,9 @@ def split_launches(eng, launch_fn, bytes_fn, cap, clouds, keep, cloud_of):
     """``launch_fn(keep, cloud_of) -> logits`` in one engine launch if the workspace fits, several otherwise: the launch size
     comes from the memory that is free now (workspace.run_in_steps, ``bytes_fn(coalitions)``), at most ``cap``.  Only ``keep`` and
     ``cloud_of`` are sliced - ``launch_fn`` passes the caller's own ``clouds``, ``centers`` and ``region_id`` tensors on every launch
-    (an engine may key a cache on their identity)."""
+    (an engine may key a cache on their identity).  ``keep`` is whatever has one row per unit of ``cap``, ``bytes_fn`` and
+    ``cloud_of``: keep masks or rows (a unit is a coalition) or permutations (PointNet's prefix route: a unit is a permutation,
+    and a launch returns R + 1 rows for each)."""
     check_cloud_of(clouds, keep, cloud_of)
     nc, b = clouds.shape[0], keep.shape[0]
     names = cloud_of

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, hip_ops, workspace
-from .engine import Engine, EngineOwner, Packer, check_coalition_args, fold, ptr, split_launches, stream
+from .engine import Engine, EngineOwner, Packer, check_cloud_of, check_coalition_args, fold, ptr, split_launches, stream
 
 
 class PackedWeights(Packer):
@@ -108,24 +108,50 @@ class PointNetEngine(Engine):
     def wide_bytes(self, b, nc, n, r):
         return self.lib.iq_pointnet_wide_workspace_bytes(b, nc, n, r)
 
-    def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None):
+    def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None, return_trans_feat=False):
         """One iq_pointnet_coalitions_wide launch: clouds (nc,N,3), centers (nc,3), region_id (nc,N) int32, keep (B,W) int64 rows of
-        W = ceil(num_regions / 64) words, cloud_of (B,) int32 or None -> logits (B, num_classes).  Unlike ``coalition_logits`` it
-        takes channel-last clouds only and returns neither the packed trans_feat nor crt_points (the C entry point has
-        channel_first and trans_feat_packed; no wide caller needs them), and centers and keep are required: the dense forward
-        goes through the narrow entry."""
+        W = ceil(num_regions / 64) words, cloud_of (B,) int32 or None -> logits (B, num_classes) [, packed trans_feat (B,4096)].
+        Unlike ``coalition_logits`` it takes channel-last clouds only and returns no crt_points (the C entry point has
+        channel_first; no wide caller needs it), and centers and keep are required: the dense forward goes through the narrow
+        entry."""
         r = int(num_regions)
         hip_ops.wide_words(r)
         check_coalition_args(clouds, centers, region_id, keep, cloud_of)
         hip_ops.wide_keep(keep, r)
         nc, n, b = clouds.shape[0], clouds.shape[1], keep.shape[0]
         logits = self.new_logits(b)
+        tfp = torch.empty((b, 4096), dtype=torch.float32, device=self.device) if return_trans_feat else None
         ws = workspace.ensure(self, self.wide_bytes(b, nc, n, r))
         rc = self.lib.iq_pointnet_coalitions_wide(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id),
-                                                  ptr(keep), ptr(cloud_of), ptr(logits), ptr(None), ptr(ws), ws.numel(),
+                                                  ptr(keep), ptr(cloud_of), ptr(logits), ptr(tfp), ptr(ws), ws.numel(),
                                                   b, nc, n, r, 0, stream())
         _lib.check(rc, "iq_pointnet_coalitions_wide")
-        return logits
+        return (logits, tfp) if return_trans_feat else logits
+
+    def prefix_logits_wide(self, clouds, centers, region_id, orders, cloud_of=None, num_regions=None, return_trans_feat=False):
+        """One iq_pointnet_prefix_coalitions_wide launch: the prefix coalitions of the permutations ``orders`` (S,R) int32 without
+        keep rows - row o*(R+1)+i of the result keeps orders[o][:i] - bit for bit ``coalition_logits_wide`` on
+        hip_ops.prefix_keep_masks_wide(orders).  clouds (nc,N,3), centers (nc,3), region_id (nc,N) int32; cloud_of (S,) int32 names
+        the cloud of each PERMUTATION (required when 1 < nc != S) -> logits (S*(R+1), num_classes) [, packed trans_feat]."""
+        r = int(num_regions)
+        hip_ops.wide_words(r)
+        check_coalition_args(clouds, centers, region_id, None, cloud_of, masked=False)
+        if centers is None:
+            raise _lib.IqError("centers must be a contiguous %s GPU tensor" % torch.float32)
+        if orders.dim() != 2 or orders.shape[1] != r:
+            raise _lib.IqError("orders must be (S, %d), got %s" % (r, tuple(orders.shape)))
+        op = hip_ops._dev(orders, torch.int32, "orders")
+        check_cloud_of(clouds, orders, cloud_of)
+        nc, n, s = clouds.shape[0], clouds.shape[1], orders.shape[0]
+        b = s * (r + 1)
+        logits = self.new_logits(b)
+        tfp = torch.empty((b, 4096), dtype=torch.float32, device=self.device) if return_trans_feat else None
+        ws = workspace.ensure(self, self.wide_bytes(b, nc, n, r))
+        rc = self.lib.iq_pointnet_prefix_coalitions_wide(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers),
+                                                         ptr(region_id), op, ptr(cloud_of), ptr(logits), ptr(tfp), ptr(ws),
+                                                         ws.numel(), s, nc, n, r, stream())
+        _lib.check(rc, "iq_pointnet_prefix_coalitions_wide")
+        return (logits, tfp) if return_trans_feat else logits
 
     def forward(self, x):
         """Dense forward, x (B,3,N) -> (logits, trans_feat (B,64,64), crt_points (B,1024) int64)."""
@@ -197,3 +223,19 @@ class PointNetCls(EngineOwner, nn.Module):
         nc, n = clouds.shape[0], clouds.shape[1]
         return split_launches(eng, lambda k, names: eng.coalition_logits_wide(clouds, centers, region_id, k, names, num_regions=r),
                               lambda k: eng.wide_bytes(k, nc, n, r), self.max_wide_per_call, clouds, keep, cloud_of)
+
+    def prefix_logits_wide(self, clouds, centers, region_id, orders, cloud_of=None, num_regions=None, validate=True):
+        """Logits of the prefix coalitions of the permutations ``orders`` (S, num_regions) int32, straight from the permutations:
+        row o*(R+1)+i keeps orders[o][:i], ``cloud_of`` (S,) names each permutation's cloud.  Bit for bit
+        ``coalition_logits_wide`` on hip_ops.prefix_keep_masks_wide(orders), without the keep rows and with one pass over the
+        pre-pooled rows per permutation.  Launches of whole permutations, at most ``max_wide_per_call // (R+1)`` of them (at least
+        one), fewer when the free memory asks for it (engine.split_launches slices ``orders`` and ``cloud_of``)."""
+        r = int(num_regions)
+        hip_ops.wide_words(r)
+        if validate:
+            hip_ops.check_index_range(region_id, 0, r, "region_id")
+        eng = self.engine()
+        nc, n = clouds.shape[0], clouds.shape[1]
+        return split_launches(eng, lambda o, names: eng.prefix_logits_wide(clouds, centers, region_id, o, names, num_regions=r),
+                              lambda k: eng.wide_bytes(k * (r + 1), nc, n, r), max(1, self.max_wide_per_call // (r + 1)), clouds,
+                              orders, cloud_of)

@@ -5,7 +5,9 @@ NUM_REGIONS is a constant one edits (tools/final_util.py:20-22) and mask_data_ba
 for any region count up to the number of points.  Here a WIDE coalition is a row of W = ceil(R / 64) uint64 words - bit
 (r & 63) of word (r >> 6) set = region r kept - for 1 <= R <= MAX_REGIONS (include/iq.h, "Wide coalitions").
 
-PointNet evaluates wide coalitions fused (iq_pointnet_coalitions_wide: no masked cloud is ever written).  Every other family
+PointNet evaluates wide coalitions fused (iq_pointnet_coalitions_wide: no masked cloud is ever written), and the prefix
+coalitions of permutations - all that the sampled Shapley values need - straight from the permutations
+(iq_pointnet_prefix_coalitions_wide, ``prefix_logits``: no keep rows either, the same bits).  Every other family
 runs iq_mask_coalitions_wide in batches into its own dense forward (final_common.dense_logits, the narrow route too): correct,
 at dense-forward speed.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
 and the multi-order interactions of sampled (pair, context) coalitions (``gen_context``, ``interaction_logits``, ``interactions``,
@@ -20,6 +22,8 @@ from ._lib import IqError
 
 MAX_REGIONS = hip_ops.MAX_WIDE_REGIONS
 DENSE_BATCH = 256     # materialised clouds per dense forward of the families without a wide coalition path
+ROUTES = ("prefix", "keep")   # how ``shapley`` evaluates prefix coalitions: from the permutations, or through keep rows
+DEFAULT_ROUTE = "prefix"      # what route=None means for a model with ``prefix_logits_wide`` (the measured rule)
 
 
 def prefix_keep_masks(orders, num_regions):
@@ -54,12 +58,49 @@ def _logits(model, data, rid, keep, r):
                                      lambda k, cf: hip_ops.mask_coalitions_wide(cloud, rid, k, c3, r, channel_first=cf))
 
 
-def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None):
+def _pick_route(model, route):
+    """``route`` of ``shapley`` -> "prefix" or "keep"; None = DEFAULT_ROUTE where the model has the prefix entry, else "keep"."""
+    if route is not None and route not in ROUTES:
+        raise IqError("route must be one of %s or None, got %r" % (ROUTES, route))
+    fused = hasattr(model, "prefix_logits_wide")
+    if route == "prefix" and not fused:
+        raise IqError("route='prefix' needs a model with prefix_logits_wide (PointNet); %s has none" % type(model).__name__)
+    return route or (DEFAULT_ROUTE if fused else "keep")
+
+
+def _prefix_logits(model, data, rid, orders_dev, r):
+    """prefix_logits on validated region ids and an (S,R) int32 device tensor of permutations."""
+    if not hasattr(model, "prefix_logits_wide"):
+        return _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(orders_dev), r)
+    center = torch.mean(data, dim=1)
+    work.add(orders_dev.shape[0] * (r + 1))
+    return model.prefix_logits_wide(data.contiguous(), center.reshape(1, 3).contiguous(), rid.reshape(1, -1), orders_dev, None,
+                                    num_regions=r, validate=False)
+
+
+def prefix_logits(model, data, region_id, orders, args):
+    """Logits of the prefix coalitions of the permutations ``orders`` ((S,R) ndarray or int32 device tensor) of one cloud ``data``
+    (1,N,3): row o*(R+1)+i keeps orders[o][:i] (tools/final_common.py:56-60) - ``coalition_logits`` on
+    hip_ops.prefix_keep_masks_wide(orders), bit for bit.  PointNet evaluates them straight from the permutations; a family
+    without ``prefix_logits_wide`` goes through the keep rows.  ``args``: model, num_regions."""
+    r = int(args.num_regions)
+    hip_ops.wide_words(r)
+    if isinstance(orders, np.ndarray):
+        orders = hip_ops.as_i32(orders, data.device)
+    if orders.dim() != 2 or orders.shape[1] != r:
+        raise IqError("orders must be (S, %d), got %s" % (r, tuple(orders.shape)))
+    return _prefix_logits(model, data, hip_ops.region_ids(region_id, data.device, r), orders.contiguous(), r)
+
+
+def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None, route=None):
     """The sampling loop of final_shapley_value.py:138-156 for one cloud ``data`` (1,N,3) and the permutations ``orders`` ((S,R)
     ndarray): -> (running sums {count: (R,) float64} at ``snap_counts``, per-permutation rows (S,R) float64, total (R,)), shaped
-    like shapley_stage.shapley_all_orders.  The prefix masks are built on the device, ``perms_per_step`` permutations at a time
-    (default: about 2^17 coalitions), so the keep rows and logits of 1000 x 1025 coalitions are never resident at once.  Prefix
-    sets of different permutations almost never coincide at these region counts: no de-duplication."""
+    like shapley_stage.shapley_all_orders.  ``perms_per_step`` permutations at a time (default: about 2^17 coalitions), so the
+    logits of 1000 x 1025 coalitions are never resident at once.  ``route``: "prefix" evaluates a step straight from its
+    permutations (``prefix_logits``; IqError for a model without that entry), "keep" builds the prefix masks on the device and
+    evaluates them as arbitrary coalitions, None takes "prefix" where the model has it - the values are the same bits either
+    way.  Prefix sets of different permutations almost never coincide at these region counts: no de-duplication."""
+    route = _pick_route(model, route)
     dev = data.device
     r = int(args.num_regions)
     hip_ops.wide_words(r)
@@ -75,8 +116,11 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
     with torch.no_grad():
         for lo in range(0, s, step):
             hi = min(lo + step, s)
-            keep = hip_ops.prefix_keep_masks_wide(orders_dev[lo:hi].contiguous())
-            logits = _logits(model, data, rid, keep, r)
+            step_orders = orders_dev[lo:hi].contiguous()
+            if route == "prefix":
+                logits = _prefix_logits(model, data, rid, step_orders, r)
+            else:
+                logits = _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(step_orders), r)
             v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
     return hip_ops.shapley_snapshots(v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
 

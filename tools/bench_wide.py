@@ -2,7 +2,8 @@
 """Times the wide coalition path of PointNet (not the flagship workload: that is bench.py).
 
     python tools/bench_wide.py [--out profiles/wide_regions.json] [--repeats 5] [--perms 1000] [--regions 128 256 1024]
-    python tools/bench_wide.py --profile-step 1024      # one warmed step only: the program for rocprofv3 --kernel-trace --stats
+    python tools/bench_wide.py --profile-step 1024 [--route keep|prefix]   # one warmed step only: the program for rocprofv3 --kernel-trace --stats
+    python tools/bench_wide.py --prefix                 # wide.shapley, keep route against prefix route, into the "prefix" key of --out
     python tools/bench_wide.py --interaction            # the interaction stage only, into the "interaction" key of --out
 
 1. Wide against narrow at R = 32 (the headline's workload: 1000 permutations, 33 000 coalitions) and R = 64: the SAME coalitions
@@ -18,6 +19,12 @@
    (interaction.compute_order_interaction_logits: untouched code) on identical pairs and contexts at R = 64, alternated in one
    process, ratio and spread as in 1.  Both routes hand the chain kernels the same row lists, so the expectation is a ratio inside
    the spread (the narrow route also de-duplicates on the host; sampled contexts of 31 regions out of 62 do not repeat).
+
+4. ``--prefix``: wide.shapley on one synthetic cloud at R = 128, 256 and 1024 (N = 1024), route="keep" (the yardstick: the parent's
+   code path, untouched) against route="prefix" (iq_pointnet_prefix_coalitions_wide), alternated in one process after a warm-up of
+   both, ``repeats`` runs each (at least five), with as many whole steps of permutations as make a run about a second.  Reported per
+   R: seconds and coalitions/s of every run, median and spread of each route, the ratio of the medians, whether the Shapley rows are
+   the same bits, and ``prefix_slower_beyond_spread`` - the one condition under which wide.DEFAULT_ROUTE must be "keep".
 
 Times are host clocks around work that ends in a device synchronise.  Kernel shares come from a separate run under the profiler
 (--profile-step): tracing slows the host, so no rate is taken there."""
@@ -89,8 +96,9 @@ def wide_vs_narrow(model, r, perms, repeats, dev):
     return out
 
 
-def _wide_step(model, r, perms, dev):
-    """One cloud's coalitions as wide.shapley issues them: masks on the device, about 2^17 coalitions per step."""
+def _wide_step(model, r, perms, dev, route="keep"):
+    """One cloud's coalitions as wide.shapley issues them, about 2^17 coalitions per step: masks on the device and arbitrary wide
+    coalitions (``route`` "keep"), or straight from the permutations ("prefix")."""
     clouds, centers, rid = _setup(r, dev)
     orders = _orders(perms, r, dev)
     step = max(1, (1 << 17) // (r + 1))
@@ -98,8 +106,12 @@ def _wide_step(model, r, perms, dev):
     def run():
         last = None
         for lo in range(0, perms, step):
-            keep = hip_ops.prefix_keep_masks_wide(orders[lo:lo + step].contiguous())
-            last = model.coalition_logits_wide(clouds, centers, rid, keep, None, num_regions=r, validate=False)
+            o = orders[lo:lo + step].contiguous()
+            if route == "prefix":
+                last = model.prefix_logits_wide(clouds, centers, rid, o, None, num_regions=r, validate=False)
+            else:
+                last = model.coalition_logits_wide(clouds, centers, rid, hip_ops.prefix_keep_masks_wide(o), None, num_regions=r,
+                                                   validate=False)
         return last
     return run, perms * (r + 1)
 
@@ -110,6 +122,37 @@ def wide_rate(model, r, perms, repeats, dev):
     times = [_clock(run)[0] for _ in range(repeats)]
     out = {"regions": r, "permutations": perms, "coalitions": b, "seconds_per_cloud": statistics.median(times)}
     out.update(_summary([b / t for t in times]))
+    return out
+
+
+def prefix_vs_keep(model, r, repeats, dev, min_seconds=1.0):
+    """wide.shapley on one cloud, route "keep" against route "prefix", alternated; see the module docstring, 4."""
+    import math
+    from interpret_quality_amd import wide
+    data, _, rid = _setup(r, dev)
+    rid_np = rid[0].cpu().numpy().astype(np.int64)
+    lbl = torch.zeros((1,), dtype=torch.int64, device=dev)
+    args = argparse.Namespace(model="pointnet", softmax_type="modified", num_points=1024, num_regions=r, verbose=False)
+    step = max(1, (1 << 17) // (r + 1))
+    run = lambda route, orders: wide.shapley(model, data, lbl, rid_np, orders, args, route=route)      # noqa: E731
+    one = synth.make_orders(step, r, seed=1)
+    for route in wide.ROUTES:                      # warm-up of both at the step's shape
+        run(route, one)
+    t_step = min(_clock(lambda: run(route, one))[0] for route in wide.ROUTES)
+    perms = step * max(1, math.ceil(min_seconds / t_step))       # whole steps, about a second for the faster route
+    orders = synth.make_orders(perms, r, seed=1)
+    same = bool(np.array_equal(run("keep", orders)[1], run("prefix", orders)[1]))     # second warm-up; the results must not differ
+    times = {route: [] for route in wide.ROUTES}
+    for _ in range(max(5, repeats)):
+        for route in ("keep", "prefix"):
+            times[route].append(_clock(lambda: run(route, orders))[0])
+    b = perms * (r + 1)
+    out = {"regions": r, "permutations": perms, "coalitions": b, "rows_bitwise_equal": same}
+    for route in wide.ROUTES:
+        out[route] = dict(_summary([b / t for t in times[route]]), seconds=times[route], median_seconds=statistics.median(times[route]))
+    keep, prefix = out["keep"], out["prefix"]
+    out["ratio_prefix_over_keep"] = prefix["median"] / keep["median"]
+    out["prefix_slower_beyond_spread"] = (keep["median"] - prefix["median"]) / keep["median"] > max(keep["spread"], prefix["spread"])
     return out
 
 
@@ -185,6 +228,9 @@ def main(argv=None):
     ap.add_argument("--regions", type=int, nargs="+", default=[128, 256, 1024])
     ap.add_argument("--profile-step", type=int, default=0, metavar="R",
                     help="run one warmed step at R regions and exit (the program to put under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--route", choices=["keep", "prefix"], default="keep", help="the route of --profile-step")
+    ap.add_argument("--prefix", action="store_true",
+                    help="time wide.shapley, keep route against prefix route (leg 4), and put it under \"prefix\" in --out, keeping what is there")
     ap.add_argument("--interaction", action="store_true",
                     help="time the interaction stage only (legs 3a, 3b) and put it under \"interaction\" in --out, keeping what is there")
     args = ap.parse_args(argv)
@@ -193,10 +239,20 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     model = _model(dev)
     if args.profile_step:
-        run, b = _wide_step(model, args.profile_step, args.perms, dev)
+        run, b = _wide_step(model, args.profile_step, args.perms, dev, args.route)
         run()
         t, _ = _clock(run)
-        print(json.dumps({"profile_step_regions": args.profile_step, "coalitions": b, "runs": 2, "seconds_under_profiler": t}))
+        print(json.dumps({"profile_step_regions": args.profile_step, "route": args.route, "coalitions": b, "runs": 2,
+                          "seconds_under_profiler": t}))
+        return
+    if args.prefix:
+        from interpret_quality_amd import wide
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        legs = [prefix_vs_keep(model, r, args.repeats, dev) for r in args.regions]
+        res["prefix"] = {"device": torch.cuda.get_device_name(0), "repeats": max(5, args.repeats), "by_regions": legs,
+                         "default_route_by_the_rule": "keep" if any(l["prefix_slower_beyond_spread"] for l in legs) else "prefix",
+                         "default_route_in_this_build": wide.DEFAULT_ROUTE}
+        _write(args.out, res)
         return
     if args.interaction:
         res = json.load(open(args.out)) if os.path.exists(args.out) else {}
