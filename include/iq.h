@@ -57,8 +57,10 @@ enum {
  * 104: new entry points, no layout change (exact games by full enumeration: iq_enum_keep_masks .. iq_exact_scratch_bytes).
  * 105: new entry points, no layout change (wide coalitions: iq_prefix_keep_masks_wide .. iq_pointnet_coalitions_wide).
  * 106: new entry point, no layout change (iq_context_keep_masks_wide: the interaction stage of wide games).
- * 107: new entry point, no layout change (iq_pointnet_prefix_coalitions_wide: prefix coalitions straight from permutations). */
-#define IQ_ABI_VERSION 107
+ * 107: new entry point, no layout change (iq_pointnet_prefix_coalitions_wide: prefix coalitions straight from permutations).
+ * 108: new entry points, no layout change (the other families' compact coalition paths for wide keep rows:
+ * iq_dgcnn_coalitions_wide, iq_pointnet2_coalitions_wide, iq_pointconv_coalitions_wide, iq_pointconv_coalitions_cached_wide). */
+#define IQ_ABI_VERSION 108
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -565,8 +567,10 @@ int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
  * and the contexts of its interaction stage are drawn on the host (final_shapley_value.py:59-72, final_gen_pair.py:18-43 as
  * they stand: NumPy's global generator) - iq_sample_permutations stays narrow.  The multi-order interactions of a wide game need
  * one wide entry point only, iq_context_keep_masks_wide: iq_reward and iq_interaction_reduce never see a mask.
- * The smoothness and pose stages and the compact coalition paths of PointNet++ / DGCNN / PointConv have no wide form: those
- * families evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.
+ * Every family's coalition entry has a wide form (the compact paths of PointNet++ / DGCNN / GCNN / PointConv: the few small kernels
+ * that turn a mask into a coalition's kept points, csrc/iq_common.h WaveKeep; everything behind them works on points); those
+ * families can also evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.  The smoothness and pose stages
+ * have no wide form.
  * ------------------------------------------------------------------------------------------- */
 
 /* tools/final_common.py:56-60 as wide masks: row s*(R+1) + i of keep keeps orders[s][0..i-1]; an entry outside [0, R) is ignored. */
@@ -619,6 +623,29 @@ int iq_pointnet_prefix_coalitions_wide(const iq_pointnet_weights* w, const float
                                        float* logits /*S*(R+1),C*/, float* trans_feat_packed /*S*(R+1),4096 or NULL*/,
                                        void* workspace, size_t workspace_bytes, int S, int nclouds, int N, int R,
                                        iq_stream_t stream);
+
+/* iq_dgcnn_coalitions, iq_pointnet2_coalitions, iq_pointconv_coalitions and iq_pointconv_coalitions_cached for wide keep rows
+ * (B,W): the arguments of the narrow twin plus R, 1 <= R <= IQ_MAX_WIDE_REGIONS; a point whose region id lies outside [0, R) is
+ * masked, bits at or above R change nothing.  The same workspace functions as the twins (iq_dgcnn_workspace_bytes,
+ * iq_pointnet2_coalitions_workspace_bytes, iq_pointconv_coalitions_workspace_bytes / iq_pointconv_tables_bytes) and the same
+ * limits on N, except PointNet++: N <= 1024 (its wide form takes "kept" from the coalition's 1024-point bitmap).  Only the
+ * kernels that read a mask differ, so a coalition's logits are the narrow entry's on the same kept points, bit for bit - for
+ * R <= 64 on the same mask.  PointNet++ runs sa1 without the region-reduced tables (they hold 64 regions): the member walk,
+ * the same bits.  PointConv's per-cloud tables do not depend on the mask: `tables_state` and the tables at the head of the
+ * workspace are shared with the narrow entry. */
+int iq_dgcnn_coalitions_wide(const iq_dgcnn_weights* w, const float* clouds, const float* centers, const int32_t* region_id,
+                             const uint64_t* keep /*B,W*/, const int32_t* cloud_of, float* logits, void* workspace,
+                             size_t workspace_bytes, int B, int nclouds, int N, int fixed_graph, int R, iq_stream_t stream);
+int iq_pointnet2_coalitions_wide(const iq_pointnet2_weights* w, const float* clouds, const float* centers,
+                                 const int32_t* region_id, const uint64_t* keep /*B,W*/, const int32_t* cloud_of, float* logits,
+                                 void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int R, iq_stream_t stream);
+int iq_pointconv_coalitions_wide(const iq_pointconv_weights* w, const float* clouds, const float* centers,
+                                 const int32_t* region_id, const uint64_t* keep /*B,W*/, const int32_t* cloud_of, float* logits,
+                                 void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int R, iq_stream_t stream);
+int iq_pointconv_coalitions_cached_wide(const iq_pointconv_weights* w, const float* clouds, const float* centers,
+                                        const int32_t* region_id, const uint64_t* keep /*B,W*/, const int32_t* cloud_of,
+                                        float* logits, void* workspace, size_t workspace_bytes, int B, int nclouds, int N,
+                                        int* tables_state, int R, iq_stream_t stream);
 
 /* The diagnostic entry points (HIP-event profiler, experiment knobs, debug counters) are NOT part of the drop-in surface:
  * they are declared in iq_debug.h. */

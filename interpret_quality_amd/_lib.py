@@ -143,6 +143,11 @@ SIGNATURES = {
                                          _I, _I, _I, _I, _I, _P]),
     "iq_pointnet_prefix_coalitions_wide": (_I, [ctypes.POINTER(PointNetWeights), _P, _P, _P, _P, _P, _P, _P, _P, _SZ,
                                                 _I, _I, _I, _I, _P]),
+    "iq_dgcnn_coalitions_wide": (_I, [ctypes.POINTER(DgcnnWeights), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P]),
+    "iq_pointnet2_coalitions_wide": (_I, [ctypes.POINTER(PointNet2Weights), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
+    "iq_pointconv_coalitions_wide": (_I, [ctypes.POINTER(PointConvWeights), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
+    "iq_pointconv_coalitions_cached_wide": (_I, [ctypes.POINTER(PointConvWeights), _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I,
+                                               ctypes.POINTER(ctypes.c_int), _I, _P]),
     "iq_profile_enable": (_I, [_I]),
     "iq_set_tuning": (_I, [_I, _I]),
     "iq_profile_read_work": (_I, [_I, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -153,7 +158,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 107   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 108   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -38,6 +38,47 @@ __host__ __device__ inline bool keep_bit(unsigned long long keep, int rid) {
     return (unsigned)rid < 64u && ((keep >> rid) & 1ull);
 }
 
+// ---- wide coalitions (include/iq.h, "Wide coalitions"): a row of W = ceil(R / 64) words ------------------------------------------
+constexpr int kMaxKeepWords = IQ_MAX_WIDE_REGIONS / 64;
+
+__host__ __device__ inline int keep_words(int R) { return (R + 63) >> 6; }
+
+// bit `rid` of a wide keep row; a region id outside [0, R) is never kept (keep_bit's rule)
+__device__ __forceinline__ bool keep_bit_wide(const uint64_t* keep, int rid, int R) {
+    return (unsigned)rid < (unsigned)R && ((keep[rid >> 6] >> (rid & 63)) & 1ull);
+}
+
+// The coalition of ONE WAVE, for the small kernels of the compact coalition paths that turn a coalition's mask into its kept
+// points (a wave per coalition).  The switch between the two kinds of game is this template argument, so a narrow kernel holds
+// no trace of the wide form:
+//   WIDE = false: keep[b] is the uint64 mask, held in a register and tested with keep_bit - R, W and `strip` are not looked at;
+//   WIDE = true:  keep is (B, W); lane l < W loads word l of row b into `strip` (the wave's own kMaxKeepWords words of LDS), once,
+//                 and every test afterwards is an LDS read - no global read per point.  The fences and the wave barrier make the
+//                 W lanes' words visible to all 64 (LDS is coherent within a workgroup; they keep the compiler from moving the
+//                 reads above the writes).  Every lane of the wave must construct it (no divergent return before).
+template <bool WIDE>
+struct WaveKeep {
+    unsigned long long k = 0;
+    const uint64_t* row = nullptr;
+    int R = 64;
+    __device__ __forceinline__ WaveKeep(const uint64_t* keep, int b, int R_, int W, int lane, uint64_t* strip) {
+        if constexpr (WIDE) {
+            if (lane < W) strip[lane] = keep[(size_t)b * W + lane];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            row = strip;
+            R = R_;
+        } else {
+            k = keep[b];
+        }
+    }
+    __device__ __forceinline__ bool operator()(int rid) const {
+        if constexpr (WIDE) return keep_bit_wide(row, rid, R);
+        else return keep_bit(k, rid);
+    }
+};
+
 // The cloud a workgroup of an XCD-aware grid works on.  Workgroups go round-robin over the 8 XCDs (blockIdx & 7); all
 // workgroups of a cloud sit on one XCD (they share its rows through one L2), clouds c = 8 k + xcd.  A batch whose work has
 // period 4 in the cloud index - the four masked clouds S+{i,j}, S+{i}, S+{j}, S of every interaction context, largest first

@@ -71,15 +71,20 @@ __global__ void dg_dense_layout_kernel(int32_t* __restrict__ roff, int32_t* __re
 }
 
 // coalitions: kept points of coalition b = points whose region bit is set in keep[b]
+// WIDE (the three kernels that read a mask: count, compact, walk): keep is (B, W) rows of an R-region game, iq::WaveKeep<true>
+// (iq_common.h) - a compile-time switch, the narrow instantiations are the kernels as they were; R and W are theirs to ignore.
+template <bool WIDE>
 __global__ __launch_bounds__(64) void dg_count_kernel(const int32_t* __restrict__ region_id, const uint64_t* __restrict__ keep,
                                                       const int32_t* __restrict__ cloud_of, int32_t* __restrict__ nkept,
-                                                      int32_t* __restrict__ ncopy, int32_t* __restrict__ dpad, int N, int nclouds) {
+                                                      int32_t* __restrict__ ncopy, int32_t* __restrict__ dpad, int N, int nclouds,
+                                                      int R, int W) {
+    __shared__ uint64_t strip[WIDE ? iq::kMaxKeepWords : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int c = cloud_of ? cloud_of[b] : (nclouds == 1 ? 0 : b);
-    const uint64_t k = keep[b];
+    const iq::WaveKeep<WIDE> k(keep, b, R, W, lane, strip);
     const int32_t* rid = region_id + (size_t)c * N;
     int n = 0;
-    for (int i = lane; i < N; i += 64) n += (int)iq::keep_bit(k, rid[i]);
+    for (int i = lane; i < N; i += 64) n += (int)k(rid[i]);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) n += __shfl_xor(n, o, 64);
     if (lane == 0) {
@@ -112,16 +117,19 @@ __global__ __launch_bounds__(1024) void dg_scan_kernel(const int32_t* __restrict
 }
 
 // rows of coalition b: kept points in index order, then the centre (once), then dead rows; (.,8) padded xyz
+template <bool WIDE>
 __global__ __launch_bounds__(64) void dg_compact_kernel(const float* __restrict__ clouds, const float* __restrict__ centers,
                                                         const int32_t* __restrict__ region_id, const uint64_t* __restrict__ keep,
                                                         const int32_t* __restrict__ cloud_of, const int32_t* __restrict__ roff,
                                                         const int32_t* __restrict__ nkept, const int32_t* __restrict__ ncopy,
                                                         float* __restrict__ x0, int32_t* __restrict__ row_cloud,
                                                         float* __restrict__ row_w, int N, int nclouds,
-                                                        int16_t* __restrict__ src /*(B,Np) source point of a row, or null*/, int Np) {
+                                                        int16_t* __restrict__ src /*(B,Np) source point of a row, or null*/, int Np,
+                                                        int R, int W) {
+    __shared__ uint64_t strip[WIDE ? iq::kMaxKeepWords : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int c = cloud_of ? cloud_of[b] : (nclouds == 1 ? 0 : b);
-    const uint64_t k = keep[b];
+    const iq::WaveKeep<WIDE> k(keep, b, R, W, lane, strip);
     const int32_t* rid = region_id + (size_t)c * N;
     const float* xyz = clouds + (size_t)c * N * 3;
     const int base = roff[b], end = roff[b + 1];
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(64) void dg_compact_kernel(const float* __restrict_
     int pos = 0;
     for (int i0 = 0; i0 < N; i0 += 64) {
         const int i = i0 + lane;
-        const bool kept = i < N && iq::keep_bit(k, rid[i]);
+        const bool kept = i < N && k(rid[i]);
         const unsigned long long m = __ballot(kept);
         if (kept) {
             const int row = base + pos + __popcll(m & ((1ull << lane) - 1ull));
@@ -224,21 +232,23 @@ __global__ __launch_bounds__(kThreads) void rownorm_kernel(const float* __restri
 // coalition.  The wave first builds the coalition's kept-point bitmap (N bits) and the prefix counts of its 32-bit words in
 // LDS, so that "is point p kept" and "which compact row is it" (= the number of kept points before p) are two LDS reads
 // and a popcount; the only global reads of the walk are the list entries themselves, eight per 16-byte load.
+template <bool WIDE>
 __global__ __launch_bounds__(64) void dg_walk_kernel(const int16_t* __restrict__ sorted, const int16_t* __restrict__ src,
                                                      const int32_t* __restrict__ region_id, const uint64_t* __restrict__ keep,
                                                      const int32_t* __restrict__ cloud_of, int16_t* __restrict__ idx, Ragged rg,
-                                                     int N, int Np, int Nsl, int nclouds, int as_addr) {
+                                                     int N, int Np, int Nsl, int nclouds, int as_addr, int R, int W) {
+    __shared__ uint64_t strip[WIDE ? iq::kMaxKeepWords : 1];
     __shared__ unsigned bits[kWalkMaxN / 32];
     __shared__ int pre[kWalkMaxN / 32];
     const int b = blockIdx.y, lane = threadIdx.x, r = blockIdx.x * 64 + lane;
     const int base = rg.roff[b], D = rg.roff[b + 1] - base;
     if (blockIdx.x * 64 >= D) return;                 // wave-uniform
     const int c = cloud_of ? cloud_of[b] : (nclouds == 1 ? 0 : b);
-    const uint64_t k = keep[b];
+    const iq::WaveKeep<WIDE> k(keep, b, R, W, lane, strip);
     const int32_t* rid = region_id + (size_t)c * N;
     for (int i0 = 0; i0 < kWalkMaxN; i0 += 64) {      // kept bitmap, 64 points per step
         const int i = i0 + lane;
-        const unsigned long long m = __ballot(i < N && iq::keep_bit(k, rid[min(i, N - 1)]));
+        const unsigned long long m = __ballot(i < N && k(rid[min(i, N - 1)]));
         if (lane == 0) { bits[i0 >> 5] = (unsigned)m; bits[(i0 >> 5) + 1] = (unsigned)(m >> 32); }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1193,6 +1203,7 @@ struct WalkCtx {
     const uint64_t* keep;
     const int32_t* cloud_of;
     int nclouds, Nsl;
+    int R, W;                // wide game: keep is (B, W) rows over R regions; W = 0: uint64 masks
 };
 
 // does run_network take the fused EdgeConv path?  (the walk tables live in the P/Q buffer that only the other path uses)
@@ -1224,8 +1235,9 @@ int run_network(const iq_dgcnn_weights* w, const WsD& s, float* logits, int B, i
         IQ_REQUIRE(w->pq[l].cin == cin, "iq_dgcnn: layer %d expects %d inputs, got %d", l, cin, w->pq[l].cin);
         if (l == 0 && walk) {
             iq::ProfileSpan span(iq::kSlotPrepool, st);
-            hipLaunchKernelGGL(dg_walk_kernel, dim3((Np + 63) / 64, B), dim3(64), 0, st, walk->sorted, walk->src, walk->region_id,
-                               walk->keep, walk->cloud_of, s.idx, rg, N, Np, walk->Nsl, walk->nclouds, fused ? 1 : 0);
+            hipLaunchKernelGGL((walk->W ? dg_walk_kernel<true> : dg_walk_kernel<false>), dim3((Np + 63) / 64, B), dim3(64), 0, st,
+                               walk->sorted, walk->src, walk->region_id, walk->keep, walk->cloud_of, s.idx, rg, N, Np, walk->Nsl,
+                               walk->nclouds, fused ? 1 : 0, walk->R, walk->W);
             if ((rc = iq::check_launch("dg_walk_kernel"))) return rc;
         } else if (l == 0 || !fixed_graph) {
             iq::ProfileSpan span(iq::kSlotPrepool, st);
@@ -1319,19 +1331,22 @@ extern "C" int iq_dgcnn_forward(const iq_dgcnn_weights* w, const float* xyz, flo
     return run_network(w, s, logits, B, N, rows, fixed_graph, st);
 }
 
-extern "C" int iq_dgcnn_coalitions(const iq_dgcnn_weights* w, const float* clouds, const float* centers,
-                                   const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
-                                   void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int fixed_graph,
-                                   iq_stream_t stream) {
-    IQ_REQUIRE(B >= 0 && nclouds >= 1, "iq_dgcnn_coalitions: B=%d nclouds=%d", B, nclouds);
-    IQ_REQUIRE(w && clouds && centers && region_id && (B == 0 || (keep && logits)), "iq_dgcnn_coalitions: null pointer");
-    IQ_REQUIRE(N >= kK && N <= 32767, "iq_dgcnn_coalitions: N=%d not in [%d, 32767]", N, kK);
-    IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == B, "iq_dgcnn_coalitions: cloud_of required when 1 < nclouds != B");
-    IQ_REQUIRE(w->k == kK, "iq_dgcnn_coalitions: k=%d (only 20)", w->k);
+namespace {
+
+// iq_dgcnn_coalitions (W = 0: keep holds B uint64 masks) and iq_dgcnn_coalitions_wide (keep holds (B, W) rows of an R-region game):
+// the count, the compaction and the walk's bitmap read the coalition, everything after them works on its rows
+int dgcnn_coalitions(const char* name, const iq_dgcnn_weights* w, const float* clouds, const float* centers, const int32_t* region_id,
+                     const uint64_t* keep, const int32_t* cloud_of, float* logits, void* workspace, size_t workspace_bytes, int B,
+                     int nclouds, int N, int fixed_graph, int R, int W, iq_stream_t stream) {
+    IQ_REQUIRE(B >= 0 && nclouds >= 1, "%s: B=%d nclouds=%d", name, B, nclouds);
+    IQ_REQUIRE(w && clouds && centers && region_id && (B == 0 || (keep && logits)), "%s: null pointer", name);
+    IQ_REQUIRE(N >= kK && N <= 32767, "%s: N=%d not in [%d, 32767]", name, N, kK);
+    IQ_REQUIRE(cloud_of || nclouds == 1 || nclouds == B, "%s: cloud_of required when 1 < nclouds != B", name);
+    IQ_REQUIRE(w->k == kK, "%s: k=%d (only 20)", name, w->k);
     if (B == 0) return IQ_OK;
     const size_t need = carve_d(nullptr, B, N).bytes;
     if (!workspace || workspace_bytes < need)
-        return iq::fail(IQ_EWORKSPACE, "iq_dgcnn_coalitions: workspace %zu < %zu bytes", workspace_bytes, need);
+        return iq::fail(IQ_EWORKSPACE, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
     WsD s = carve_d(workspace, B, N);
     hipStream_t st = iq::as_stream(stream);
     int rc;
@@ -1356,13 +1371,34 @@ extern "C" int iq_dgcnn_coalitions(const iq_dgcnn_weights* w, const float* cloud
             hipLaunchKernelGGL(sl_dist_kernel<0>, dim3(Nsp / 32, nclouds), dim3(64), 0, st, xs, xxs, dmat, Nsp);
             hipLaunchKernelGGL(sl_sort_kernel, dim3(N + 1, nclouds), dim3(256), 0, st, dmat, sorted, N, Nsp, Nsl);
             if ((rc = iq::check_launch("sl_sort_kernel"))) return rc;
-            walk = WalkCtx{sorted, srcrow, region_id, keep, cloud_of, nclouds, Nsl};
+            walk = WalkCtx{sorted, srcrow, region_id, keep, cloud_of, nclouds, Nsl, R, W};
         }
     }
-    hipLaunchKernelGGL(dg_count_kernel, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, s.nkept, s.ncopy, s.dpad, N, nclouds);
+    hipLaunchKernelGGL((W ? dg_count_kernel<true> : dg_count_kernel<false>), dim3(B), dim3(64), 0, st, region_id, keep, cloud_of,
+                       s.nkept, s.ncopy, s.dpad, N, nclouds, R, W);
     hipLaunchKernelGGL(dg_scan_kernel, dim3(1), dim3(1024), 0, st, s.dpad, s.roff, B);
-    hipLaunchKernelGGL(dg_compact_kernel, dim3(B), dim3(64), 0, st, clouds, centers, region_id, keep, cloud_of, s.roff, s.nkept,
-                       s.ncopy, s.x0, s.row_cloud, s.row_w, N, nclouds, use_walk ? const_cast<int16_t*>(walk.src) : (int16_t*)nullptr, Np);
+    hipLaunchKernelGGL((W ? dg_compact_kernel<true> : dg_compact_kernel<false>), dim3(B), dim3(64), 0, st, clouds, centers, region_id,
+                       keep, cloud_of, s.roff, s.nkept, s.ncopy, s.x0, s.row_cloud, s.row_w, N, nclouds,
+                       use_walk ? const_cast<int16_t*>(walk.src) : (int16_t*)nullptr, Np, R, W);
     if ((rc = iq::check_launch("dg_compact_kernel"))) return rc;
     return run_network(w, s, logits, B, N, B * Np, fixed_graph, st, use_walk ? &walk : nullptr);
+}
+
+}  // namespace
+
+extern "C" int iq_dgcnn_coalitions(const iq_dgcnn_weights* w, const float* clouds, const float* centers,
+                                   const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
+                                   void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int fixed_graph,
+                                   iq_stream_t stream) {
+    return dgcnn_coalitions("iq_dgcnn_coalitions", w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B,
+                            nclouds, N, fixed_graph, 64, 0, stream);
+}
+
+extern "C" int iq_dgcnn_coalitions_wide(const iq_dgcnn_weights* w, const float* clouds, const float* centers,
+                                        const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
+                                        void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int fixed_graph, int R,
+                                        iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_dgcnn_coalitions_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
+    return dgcnn_coalitions("iq_dgcnn_coalitions_wide", w, clouds, centers, region_id, keep, cloud_of, logits, workspace,
+                            workspace_bytes, B, nclouds, N, fixed_graph, R, iq::keep_words(R), stream);
 }

@@ -646,20 +646,24 @@ __global__ void pc_fill_dup_rows_kernel(float* __restrict__ out, int S, int C, c
 //       position 0 also owns the 512 - n_unique duplicate positions that FPS returns once the distinct locations are used up.
 // The distances are pc_knn_kernel's own (sl_dist_kernel<1>), so the groups are the same point sets up to ties.
 
-// per coalition: kept-point bitmap (32 words), the first 64 masked point indices and their number
+// per coalition: kept-point bitmap (32 words), the first 64 masked point indices and their number.  The one kernel of this file
+// that reads a coalition's mask; WIDE: keep is (B, W) rows of an R-region game (iq::WaveKeep<true>, iq_common.h) - a compile-time
+// switch, the narrow instantiation is the kernel as it was and ignores R and W.
+template <bool WIDE>
 __global__ __launch_bounds__(64) void pc_coal_prep_kernel(const int32_t* __restrict__ region_id, const uint64_t* __restrict__ keep,
                                                           const int32_t* __restrict__ cloud_of, uint32_t* __restrict__ kept,
                                                           int16_t* __restrict__ mfirst, int32_t* __restrict__ mcount, int N,
-                                                          int nclouds) {
+                                                          int nclouds, int R, int W) {
+    __shared__ uint64_t strip[WIDE ? iq::kMaxKeepWords : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int c = cloud_of ? cloud_of[b] : (nclouds == 1 ? 0 : b);
-    const uint64_t k = keep[b];
+    const iq::WaveKeep<WIDE> k(keep, b, R, W, lane, strip);
     const int32_t* rid = region_id + (size_t)c * N;
     int nm = 0;
     for (int i0 = 0; i0 < kWalkMaxN; i0 += 64) {
         const int i = i0 + lane;
         const bool in = i < N;
-        const bool kp = in && iq::keep_bit(k, rid[min(i, N - 1)]);
+        const bool kp = in && k(rid[min(i, N - 1)]);
         const unsigned long long m = __ballot(kp), mm = __ballot(in && !kp);
         if (lane == 0) { kept[(size_t)b * 32 + (i0 >> 5)] = (uint32_t)m; kept[(size_t)b * 32 + (i0 >> 5) + 1] = (uint32_t)(m >> 32); }
         if (in && !kp) {
@@ -1306,10 +1310,11 @@ extern "C" int iq_pointconv_coalitions(const iq_pointconv_weights* w, const floa
 // iq_pointconv_tables_bytes(nclouds, N) bytes of `workspace` already hold - bit 0 the sorted neighbour lists, bit 1 the sa1 pair
 // tables - for exactly these clouds, centres, nclouds and N (the caller's promise: same workspace base, contents untouched);
 // what is missing is built and the bits are set.  Round 3 rebuilt both on every call (~1 GB of writes per source cloud).
-extern "C" int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, const float* clouds, const float* centers,
-                                              const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
-                                              void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int* tables_state,
-                                              iq_stream_t stream) {
+// W = 0: keep holds B uint64 masks (iq_pointconv_coalitions, _cached); otherwise (B, W) rows of an R-region game (the _wide entries).
+// pc_coal_prep_kernel alone reads the coalition; the per-cloud tables do not depend on it, so both kinds of game share them.
+static int pointconv_coalitions(const iq_pointconv_weights* w, const float* clouds, const float* centers, const int32_t* region_id,
+                                const uint64_t* keep, const int32_t* cloud_of, float* logits, void* workspace, size_t workspace_bytes,
+                                int B, int nclouds, int N, int* tables_state, int R, int W, iq_stream_t stream) {
     IQ_REQUIRE(B >= 0 && nclouds >= 1, "iq_pointconv_coalitions: B=%d nclouds=%d", B, nclouds);
     IQ_REQUIRE(w && clouds && centers && region_id && (B == 0 || (keep && logits)), "iq_pointconv_coalitions: null pointer");
     IQ_REQUIRE(N >= 64 && N <= kWalkMaxN, "iq_pointconv_coalitions: N=%d not in [64, %d]", N, kWalkMaxN);
@@ -1330,7 +1335,8 @@ extern "C" int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, con
     int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
     const int Nsp = (N + 1 + 31) / 32 * 32, Nsl = (N + 1 + 7) / 8 * 8;
-    hipLaunchKernelGGL(pc_coal_prep_kernel, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept, t.mfirst, t.mcount, N, nclouds);
+    hipLaunchKernelGGL((W ? pc_coal_prep_kernel<true> : pc_coal_prep_kernel<false>), dim3(B), dim3(64), 0, st, region_id, keep, cloud_of,
+                       t.kept, t.mfirst, t.mcount, N, nclouds, R, W);
     hipLaunchKernelGGL(pc_mask_kernel, dim3((unsigned)(((size_t)B * N + 255) / 256)), dim3(256), 0, st, clouds, centers, t.kept, cloud_of,
                        t.X, N, B, nclouds);
     if ((rc = iq::check_launch("pc_mask_kernel"))) return rc;
@@ -1368,4 +1374,31 @@ extern "C" int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, con
     }
     if (tables_state) *tables_state = have | (force << 2);
     return run_pointconv(w, t.X, logits, s, B, N, st, use_walk ? &walk : nullptr);
+}
+
+extern "C" int iq_pointconv_coalitions_cached(const iq_pointconv_weights* w, const float* clouds, const float* centers,
+                                              const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
+                                              void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int* tables_state,
+                                              iq_stream_t stream) {
+    return pointconv_coalitions(w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B, nclouds, N,
+                                tables_state, 64, 0, stream);
+}
+
+// The two entries for wide keep rows (B, W), W = ceil(R / 64): same workspace, same tables, same `tables_state` - a workspace
+// whose tables a narrow call built serves a wide call on the same clouds, and the other way round.
+extern "C" int iq_pointconv_coalitions_cached_wide(const iq_pointconv_weights* w, const float* clouds, const float* centers,
+                                                   const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of,
+                                                   float* logits, void* workspace, size_t workspace_bytes, int B, int nclouds, int N,
+                                                   int* tables_state, int R, iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_pointconv_coalitions_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
+    return pointconv_coalitions(w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B, nclouds, N,
+                                tables_state, R, iq::keep_words(R), stream);
+}
+
+extern "C" int iq_pointconv_coalitions_wide(const iq_pointconv_weights* w, const float* clouds, const float* centers,
+                                            const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
+                                            void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int R,
+                                            iq_stream_t stream) {
+    return iq_pointconv_coalitions_cached_wide(w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B,
+                                               nclouds, N, nullptr, R, stream);
 }

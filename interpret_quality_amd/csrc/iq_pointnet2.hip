@@ -749,16 +749,20 @@ __global__ __launch_bounds__(64) void pt_bits_kernel(const int32_t* __restrict__
 }
 
 // kept[b][w]: bit j = point 32 w + j of coalition b's cloud is kept (N <= 1024)
+// WIDE: keep is (B, W) rows of an R-region game (iq::WaveKeep<true>, iq_common.h) - a compile-time switch, the narrow
+// instantiation is the kernel as it was and ignores R and W.
+template <bool WIDE>
 __global__ __launch_bounds__(64) void pn2_kept_bits_kernel(const int32_t* __restrict__ region_id, const uint64_t* __restrict__ keep,
                                                            const int32_t* __restrict__ cloud_of, uint32_t* __restrict__ kept, int N,
-                                                           int nclouds) {
+                                                           int nclouds, int R, int W) {
+    __shared__ uint64_t strip[WIDE ? iq::kMaxKeepWords : 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const int c = cloud_of ? cloud_of[b] : (nclouds == 1 ? 0 : b);
-    const uint64_t k = keep[b];
+    const iq::WaveKeep<WIDE> k(keep, b, R, W, lane, strip);
     const int32_t* rid = region_id + (size_t)c * N;
     for (int i0 = 0; i0 < 1024; i0 += 64) {
         const int i = i0 + lane;
-        const unsigned long long m = __ballot(i < N && iq::keep_bit(k, rid[min(i, N - 1)]));
+        const unsigned long long m = __ballot(i < N && k(rid[min(i, N - 1)]));
         if (lane == 0) { kept[(size_t)b * 32 + (i0 >> 5)] = (uint32_t)m; kept[(size_t)b * 32 + (i0 >> 5) + 1] = (uint32_t)(m >> 32); }
     }
 }
@@ -819,6 +823,30 @@ __global__ void pn2_mask_kernel(const float* __restrict__ clouds, const float* _
     const bool kept = iq::keep_bit(keep[b], region_id[(size_t)c * N + i]);
     const float* src = kept ? clouds + ((size_t)c * N + i) * 3 : centers + (size_t)c * 3;
     out[(size_t)t * 3] = src[0]; out[(size_t)t * 3 + 1] = src[1]; out[(size_t)t * 3 + 2] = src[2];
+}
+
+// pn2_mask_kernel for wide keep rows (B, W): a wave per coalition (four to a workgroup), its row in LDS, the lanes over the points
+constexpr int kMaskWideWaves = 4;
+
+__global__ __launch_bounds__(64 * kMaskWideWaves) void pn2_mask_wide_kernel(const float* __restrict__ clouds,
+                                                                            const float* __restrict__ centers,
+                                                                            const int32_t* __restrict__ region_id,
+                                                                            const uint64_t* __restrict__ keep,
+                                                                            const int32_t* __restrict__ cloud_of, float* __restrict__ out,
+                                                                            int N, int B, int nclouds, int R, int W) {
+    __shared__ uint64_t strip[kMaskWideWaves][iq::kMaxKeepWords];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = blockIdx.x * kMaskWideWaves + wave;
+    if (b >= B) return;                                   // wave-uniform; no workgroup barrier below
+    const int c = cloud_of ? cloud_of[b] : (nclouds == 1 ? 0 : b);
+    const iq::WaveKeep<true> k(keep, b, R, W, lane, strip[wave]);
+    const int32_t* rid = region_id + (size_t)c * N;
+    const float* ctr = centers + (size_t)c * 3;
+    float* o = out + (size_t)b * N * 3;
+    for (int i = lane; i < N; i += 64) {
+        const float* src = k(rid[i]) ? clouds + ((size_t)c * N + i) * 3 : ctr;
+        o[(size_t)i * 3] = src[0]; o[(size_t)i * 3 + 1] = src[1]; o[(size_t)i * 3 + 2] = src[2];
+    }
 }
 
 // points of source cloud c: P[0..N-1] = cloud, P[N] = centre  -> (nc, N+1, 4) padded
@@ -923,7 +951,8 @@ struct GatherArgs {
     const int32_t* cnt;        // (B,S)
     const int32_t* n_unique;   // (B)
     const int32_t* region_id;  // (nc,N)
-    const uint64_t* keep;      // (B)
+    const uint64_t* keep;      // (B); a wide game: null
+    const uint32_t* kept_bits; // (B,32) a wide game: the kept points of a coalition (pn2_kept_bits_kernel), instead of its mask
     const int32_t* cloud_of;   // (B) or null
     const int32_t* map;        // (nc,N+1,N+1)
     const float* feat;         // (rows,C3)
@@ -986,6 +1015,9 @@ __global__ __launch_bounds__(kThreads) void pt_regtab_kernel(const float* __rest
 // members are all the same point (the centre), whose row is appended once.  Pass 2: every lane walks the compact list
 // with eight row loads in flight.  (The single loop - index, bit, map, row per member, one member at a time - was bound by
 // the latency of that chain: 8.2 ms per 3300-coalition step for the three scales.)
+// WIDE (a game of up to 1024 regions, N <= 1024): whether the centroid and a member are kept comes from the coalition's kept-point
+// bitmap, not from its mask, and there are no region-reduced tables (they hold kRegSlots regions): the member walk, the same bits.
+template <bool WIDE>
 __global__ __launch_bounds__(kThreads) void pt_gather_kernel(GatherArgs a) {
     __shared__ int32_t rows[kThreads / 16][128 + 4];   // per group: compact row list (K <= 128), padded to a multiple of 4
     const int per = a.C3 / 4;                       // float4 lanes per group (16 or 32)
@@ -999,14 +1031,21 @@ __global__ __launch_bounds__(kThreads) void pt_gather_kernel(GatherArgs a) {
     const int s = (slot % wgs_per_cloud) * gpb + gl;
     if (s >= a.S || s >= a.n_unique[b]) return;     // duplicate centroids are filled from group 0 afterwards
     const int c = a.cloud_of ? a.cloud_of[b] : (a.nclouds == 1 ? 0 : b);
-    const uint64_t k = a.keep[b];
+    uint64_t k = 0;
     const int32_t* rid = a.region_id + (size_t)c * a.N;
+    const uint32_t* kb = nullptr;
+    if constexpr (WIDE) kb = a.kept_bits + (size_t)b * 32;
+    else k = a.keep[b];
+    auto is_kept = [&](int i) -> bool {
+        if constexpr (WIDE) return (kb[i >> 5] >> (i & 31)) & 1u;
+        else return iq::keep_bit(k, rid[i]);
+    };
     const int pi = a.fps[(size_t)b * a.S + s];
-    const int p = iq::keep_bit(k, rid[pi]) ? pi : a.N;
+    const int p = is_kept(pi) ? pi : a.N;
     const f32x4* F = reinterpret_cast<const f32x4*>(a.feat);
     f32x4 m = {0.f, 0.f, 0.f, 0.f};                 // rows are post-ReLU (>= 0) and every group has >= 1 member
     constexpr int U = 8;
-    if (a.touch) {                                  // a simple ball: one row per kept region that reaches into it
+    if (!WIDE && a.touch) {                         // a simple ball: one row per kept region that reaches into it
         unsigned long long regs = a.touch[(size_t)c * (a.N + 1) + p] & k;
         if (regs) {
             const f32x4* T = reinterpret_cast<const f32x4*>(a.regtab) + ((size_t)c * (a.N + 1) + p) * kRegSlots * per + c4;
@@ -1043,7 +1082,7 @@ __global__ __launch_bounds__(kThreads) void pt_gather_kernel(GatherArgs a) {
         int row = -1;
         if (j < n) {
             const int qi = mem[j];
-            kept = iq::keep_bit(k, rid[qi]);
+            kept = is_kept(qi);
             masked = masked || !kept;
             if (kept) row = mrow[qi];
         }
@@ -1185,7 +1224,8 @@ int run_pn2(const iq_pointnet2_weights* w, const float* xyz, float* logits, cons
             g.out = s.l1 + col; g.ldo = F1; g.N = N; g.S = S1; g.K = w->sa1[q].nsample; g.B = B;
             const int gpb = kThreads / (g.C3 / 4);
             iq::ProfileSpan span(iq::kSlotPrepool, st);
-            hipLaunchKernelGGL(pt_gather_kernel, dim3((unsigned)((B + 7) / 8 * 8 * ((S1 + gpb - 1) / gpb))), dim3(kThreads), 0, st, g);
+            hipLaunchKernelGGL((g.kept_bits ? pt_gather_kernel<true> : pt_gather_kernel<false>),
+                               dim3((unsigned)((B + 7) / 8 * 8 * ((S1 + gpb - 1) / gpb))), dim3(kThreads), 0, st, g);
             if ((rc = iq::check_launch("pt_gather_kernel"))) return rc;
             col += w->sa1[q].l3.cout;
             continue;
@@ -1314,10 +1354,11 @@ extern "C" size_t iq_pointnet2_coalitions_workspace_bytes(int B, int nclouds, in
     return iq::align_up(carve2(nullptr, B, nullptr).bytes, 256) + carve_c(nullptr, B, nclouds, N).bytes;
 }
 
-extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const float* clouds, const float* centers,
-                                       const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of,
-                                       float* logits, void* workspace, size_t workspace_bytes, int B, int nclouds, int N,
-                                       iq_stream_t stream) {
+// W = 0: keep holds B uint64 masks (iq_pointnet2_coalitions); otherwise (B, W) rows of an R-region game (iq_pointnet2_coalitions_wide,
+// which has checked N <= 1024: every coalition gets its kept-point bitmap, and the gather kernel reads that instead of the mask).
+static int pointnet2_coalitions(const iq_pointnet2_weights* w, const float* clouds, const float* centers, const int32_t* region_id,
+                                const uint64_t* keep, const int32_t* cloud_of, float* logits, void* workspace, size_t workspace_bytes,
+                                int B, int nclouds, int N, int R, int W, iq_stream_t stream) {
     IQ_REQUIRE(B >= 0 && nclouds >= 1 && nclouds <= 64, "iq_pointnet2_coalitions: B=%d nclouds=%d", B, nclouds);
     IQ_REQUIRE(w && clouds && centers && region_id && (B == 0 || (keep && logits)), "iq_pointnet2_coalitions: null pointer");
     IQ_REQUIRE(N >= 1 && N <= 4096, "iq_pointnet2_coalitions: N=%d", N);
@@ -1334,8 +1375,12 @@ extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const floa
     iq::ProfileSpan call_span(iq::kSlotCall, st);
     const int n1 = N + 1;
 
-    hipLaunchKernelGGL(pn2_mask_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, clouds, centers, region_id, keep, cloud_of,
-                       t.X, N, B, nclouds);
+    if (W)
+        hipLaunchKernelGGL(pn2_mask_wide_kernel, dim3((B + kMaskWideWaves - 1) / kMaskWideWaves), dim3(64 * kMaskWideWaves), 0, st,
+                           clouds, centers, region_id, keep, cloud_of, t.X, N, B, nclouds, R, W);
+    else
+        hipLaunchKernelGGL(pn2_mask_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, clouds, centers, region_id, keep, cloud_of,
+                           t.X, N, B, nclouds);
     hipLaunchKernelGGL(pt_points_kernel, dim3((nclouds * n1 + 255) / 256), dim3(256), 0, st, clouds, centers, t.P, N, nclouds);
     float r2[3];
     for (int q = 0; q < 3; ++q) r2[q] = (float)((double)w->sa1[q].radius * (double)w->sa1[q].radius);
@@ -1374,7 +1419,8 @@ extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const floa
             if ((rc = iq::launch_linear(t.h1, sc.l2.cin, sc.l2, t.h2, sc.l2.cout, row0, 1, st))) return rc;
             if ((rc = iq::launch_linear(t.h2, sc.l2.cout, sc.l3, t.feat[q], sc.l3.cout, row0, 1, st))) return rc;
         }
-        if (iq::twin() != iq::kTwinPn2MemberWalk) {   // region-reduced rows of this scale (the twin: member walk only, A/B and tests)
+        // region-reduced rows of this scale (the twin: member walk only, A/B and tests; a wide game: the tables hold 64 regions)
+        if (iq::twin() != iq::kTwinPn2MemberWalk && !W) {
             int r0c = 0;
             for (int c = 0; c < nclouds; ++c) {
                 hipLaunchKernelGGL(pt_regtab_kernel, dim3(n1), dim3(kThreads), (size_t)kRegSlots * sc.l3.cout * 4, st, t.feat[q], t.pairs,
@@ -1392,11 +1438,37 @@ extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const floa
             hipLaunchKernelGGL(pt_bits_kernel, dim3(n1, nclouds), dim3(64), 0, st, t.map[q], t.ball_bits[q], n1);
             tab.ball_bits[q] = t.ball_bits[q];
         }
-        hipLaunchKernelGGL(pn2_kept_bits_kernel, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N, nclouds);
-        if ((rc = iq::check_launch("pn2_kept_bits_kernel"))) return rc;
+        if (!W) {
+            hipLaunchKernelGGL(pn2_kept_bits_kernel<false>, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N,
+                               nclouds, 64, 0);
+            if ((rc = iq::check_launch("pn2_kept_bits_kernel"))) return rc;
+        }
         tab.kept_bits = t.kept_bits;
     }
     GatherArgs g{};
     g.region_id = region_id; g.keep = keep; g.cloud_of = cloud_of; g.nclouds = nclouds;
+    if (W) {   // the bitmap whatever the scales run on: the gather kernel of a wide game takes "kept" from it
+        hipLaunchKernelGGL(pn2_kept_bits_kernel<true>, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N, nclouds, R, W);
+        if ((rc = iq::check_launch("pn2_kept_bits_kernel"))) return rc;
+        g.keep = nullptr; g.kept_bits = t.kept_bits;
+    }
     return run_pn2(w, t.X, logits, s, B, N, st, &tab, &g);
+}
+
+extern "C" int iq_pointnet2_coalitions(const iq_pointnet2_weights* w, const float* clouds, const float* centers,
+                                       const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of,
+                                       float* logits, void* workspace, size_t workspace_bytes, int B, int nclouds, int N,
+                                       iq_stream_t stream) {
+    return pointnet2_coalitions(w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B, nclouds, N, 64, 0,
+                                stream);
+}
+
+extern "C" int iq_pointnet2_coalitions_wide(const iq_pointnet2_weights* w, const float* clouds, const float* centers,
+                                            const int32_t* region_id, const uint64_t* keep, const int32_t* cloud_of, float* logits,
+                                            void* workspace, size_t workspace_bytes, int B, int nclouds, int N, int R,
+                                            iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_pointnet2_coalitions_wide: R=%d not in [1,%d]", R, IQ_MAX_WIDE_REGIONS);
+    IQ_REQUIRE(N >= 1 && N <= 1024, "iq_pointnet2_coalitions_wide: N=%d not in [1, 1024] (the kept-point bitmap holds 1024 points)", N);
+    return pointnet2_coalitions(w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B, nclouds, N, R,
+                                iq::keep_words(R), stream);
 }

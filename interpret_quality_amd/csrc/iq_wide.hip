@@ -14,14 +14,11 @@
 
 namespace {
 
-constexpr int kMaxW = IQ_MAX_WIDE_REGIONS / 64;
+constexpr int kMaxW = iq::kMaxKeepWords;
 
-__host__ __device__ inline int words_of(int R) { return (R + 63) >> 6; }
+__host__ __device__ inline int words_of(int R) { return iq::keep_words(R); }
 
-// bit `rid` of a wide keep row; a region id outside [0, R) is never kept (iq::keep_bit's rule)
-__device__ __forceinline__ bool keep_bit_wide(const uint64_t* keep, int rid, int R) {
-    return (unsigned)rid < (unsigned)R && ((keep[rid >> 6] >> (rid & 63)) & 1ull);
-}
+using iq::keep_bit_wide;   // iq_common.h: shared with the compact coalition paths' wide forms
 
 // ---- prefix masks: one lane per (permutation, word), running OR over the entries that fall into its word ----------------------
 __global__ __launch_bounds__(256) void prefix_keep_wide_kernel(const int32_t* __restrict__ orders, uint64_t* __restrict__ keep,

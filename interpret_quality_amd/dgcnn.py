@@ -73,6 +73,11 @@ class DgcnnEngine(Engine):
         return self.lib.iq_dgcnn_coalitions(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id), ptr(keep),
                                             ptr(cloud_of), ptr(logits), ptr(ws), ws.numel(), b, nc, n, self.fixed_graph, stream())
 
+    def _coalitions_wide(self, clouds, centers, region_id, keep, cloud_of, logits, ws, b, nc, n, r):
+        return self.lib.iq_dgcnn_coalitions_wide(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id),
+                                                 ptr(keep), ptr(cloud_of), ptr(logits), ptr(ws), ws.numel(), b, nc, n,
+                                                 self.fixed_graph, r, stream())
+
 
 class _GraphCnn(CoalitionModel, nn.Module):
     fixed_graph = False

@@ -129,6 +129,21 @@ class Engine:
         _lib.check(self._coalitions(clouds, centers, region_id, keep, cloud_of, logits, ws, b, nc, n, *extra), self.coalitions_name)
         return logits
 
+    def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None, *extra):
+        """``coalition_logits`` for a game of up to hip_ops.MAX_WIDE_REGIONS regions: keep (B,W) int64 rows, W = ceil(R / 64), bit
+        (r & 63) of word (r >> 6) = region r kept - one launch of the family's ``_coalitions_wide``.  The same workspace as the
+        narrow launch: only the kernels that read a mask differ (include/iq.h, "Wide coalitions")."""
+        check_coalition_args(clouds, centers, region_id, keep, cloud_of)
+        r = int(num_regions)
+        hip_ops.wide_keep(keep, r)
+        nc, n, _ = clouds.shape
+        b = keep.shape[0]
+        ws = workspace.ensure(self, self.coalition_bytes(b, nc, n))
+        logits = self.new_logits(b)
+        _lib.check(self._coalitions_wide(clouds, centers, region_id, keep, cloud_of, logits, ws, b, nc, n, r, *extra),
+                   self.coalitions_name + "_wide")
+        return logits
+
 
 class EngineOwner:
     """``nn.Module`` mixin: the engine (packed image of the parameters) is built on first use and dropped on any parameter change.
@@ -179,6 +194,22 @@ class CoalitionModel(EngineOwner):
         same ``extra``."""
         nc, n = clouds.shape[0], clouds.shape[1]
         return split_launches(eng, lambda k, names: eng.coalition_logits(clouds, centers, region_id, k, names, *extra),
+                              lambda k: eng.coalition_bytes(k, nc, n), self.max_clouds_per_call, clouds, keep, cloud_of)
+
+    def coalition_logits_wide(self, clouds, centers, region_id, keep, cloud_of=None, num_regions=None, validate=True):
+        """``coalition_logits`` for wide coalitions: keep (B,W) int64 rows over ``num_regions`` <= hip_ops.MAX_WIDE_REGIONS regions
+        (one region per point included), through the family's compact path.  For 64 regions and fewer the logits are
+        ``coalition_logits``'s on the same masks, bit for bit; above, they are its bits on the same kept points."""
+        r = int(num_regions)
+        hip_ops.wide_keep(keep, r)
+        if validate:
+            hip_ops.check_index_range(region_id, 0, r, "region_id")
+        return self.split_launches_wide(self.engine(), clouds, centers, region_id, keep, cloud_of, r)
+
+    def split_launches_wide(self, eng, clouds, centers, region_id, keep, cloud_of, r, *extra):
+        """``split_launches`` over eng.coalition_logits_wide: the same cap and the same workspace sizes as the narrow launches."""
+        nc, n = clouds.shape[0], clouds.shape[1]
+        return split_launches(eng, lambda k, names: eng.coalition_logits_wide(clouds, centers, region_id, k, names, r, *extra),
                               lambda k: eng.coalition_bytes(k, nc, n), self.max_clouds_per_call, clouds, keep, cloud_of)
 
 

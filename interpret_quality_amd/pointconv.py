@@ -93,6 +93,16 @@ class PointConvEngine(Engine):
             self._tab["state"] = state.value & 3
         return rc
 
+    def _coalitions_wide(self, clouds, centers, region_id, keep, cloud_of, logits, ws, b, nc, n, r, walk=None):
+        """``_coalitions`` for wide keep rows: the same cached tables (they belong to the source clouds, not to the masks)."""
+        state = ctypes.c_int(self._tables_state(clouds, centers, nc, n) | (0 if walk is None else (4 if walk else 8)))
+        rc = self.lib.iq_pointconv_coalitions_cached_wide(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id),
+                                                          ptr(keep), ptr(cloud_of), ptr(logits), ptr(ws), ws.numel(), b, nc, n,
+                                                          ctypes.byref(state), r, stream())
+        if rc == 0:
+            self._tab["state"] = state.value & 3
+        return rc
+
     def _tables_state(self, clouds, centers, nc, n):
         """Which per-cloud structures (sorted lists, sa1 pair tables) the head of the workspace still holds for THESE clouds:
         the same workspace allocation, the same (nc, N), and the same `clouds` / `centers` TENSORS at the same version (torch
@@ -180,3 +190,11 @@ class PointConvDensityClsSsg(CoalitionModel, nn.Module):
         # how groups are formed is decided ONCE, from the whole batch (the library's own rule, iq.h): a memory-tight run that splits
         # the batch - or its short last launch - must not switch to the other summation order
         return super().split_launches(eng, clouds, centers, region_id, keep, cloud_of, nc <= 8 or nc * 8 <= b)
+
+    def split_launches_wide(self, eng, clouds, centers, region_id, keep, cloud_of, r):
+        """The compact path takes clouds of 64 to 1024 points; there is no dense detour here (wide.py's "dense" route is one).  How
+        groups are formed is decided once from the whole batch, as in ``split_launches``."""
+        nc, b, n = clouds.shape[0], keep.shape[0], clouds.shape[1]
+        if not 64 <= n <= 1024:
+            raise _lib.IqError("PointConv's compact coalition path takes clouds of 64 to 1024 points, got %d" % n)
+        return super().split_launches_wide(eng, clouds, centers, region_id, keep, cloud_of, r, nc <= 8 or nc * 8 <= b)

@@ -83,6 +83,11 @@ class PointNet2Engine(Engine):
         return self.lib.iq_pointnet2_coalitions(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id), ptr(keep),
                                                 ptr(cloud_of), ptr(logits), ptr(ws), ws.numel(), b, nc, n, stream())
 
+    def _coalitions_wide(self, clouds, centers, region_id, keep, cloud_of, logits, ws, b, nc, n, r):
+        """sa1 from the per-cloud pair tables by the member walk; clouds of at most 1024 points"""
+        return self.lib.iq_pointnet2_coalitions_wide(ctypes.byref(self.weights.struct), ptr(clouds), ptr(centers), ptr(region_id),
+                                                     ptr(keep), ptr(cloud_of), ptr(logits), ptr(ws), ws.numel(), b, nc, n, r, stream())
+
 
 def _holder_msg(cfg):
     m = nn.Module()

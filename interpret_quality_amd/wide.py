@@ -7,9 +7,12 @@ for any region count up to the number of points.  Here a WIDE coalition is a row
 
 PointNet evaluates wide coalitions fused (iq_pointnet_coalitions_wide: no masked cloud is ever written), and the prefix
 coalitions of permutations - all that the sampled Shapley values need - straight from the permutations
-(iq_pointnet_prefix_coalitions_wide, ``prefix_logits``: no keep rows either, the same bits).  Every other family
-runs iq_mask_coalitions_wide in batches into its own dense forward (final_common.dense_logits, the narrow route too): correct,
-at dense-forward speed.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
+(iq_pointnet_prefix_coalitions_wide, ``prefix_logits``: no keep rows either, the same bits).  Every other family has two ways,
+named by the ``coalitions`` argument of the functions below: "dense" (the default, and what None means) runs
+iq_mask_coalitions_wide in batches into the family's dense forward (final_common.dense_logits, the narrow route too) - correct,
+at dense-forward speed; "compact" takes the family's compact coalition path through its wide entry (``coalition_logits_wide``:
+a coalition's distinct rows only, per-source-cloud tables), whose logits agree with the dense forward's to rounding, bitwise only
+where the summation order is the same.  For PointNet both names mean its fused path.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
 and the multi-order interactions of sampled (pair, context) coalitions (``gen_context``, ``interaction_logits``, ``interactions``,
 wide_interaction_stage.py).  The smoothness and pose stages have none.
 """
@@ -24,6 +27,16 @@ MAX_REGIONS = hip_ops.MAX_WIDE_REGIONS
 DENSE_BATCH = 256     # materialised clouds per dense forward of the families without a wide coalition path
 ROUTES = ("prefix", "keep")   # how ``shapley`` evaluates prefix coalitions: from the permutations, or through keep rows
 DEFAULT_ROUTE = "prefix"      # what route=None means for a model with ``prefix_logits_wide`` (the measured rule)
+COALITIONS = ("dense", "compact")   # how a family other than PointNet evaluates wide coalitions; None = "dense"
+
+
+def _pick_coalitions(coalitions, data):
+    """``coalitions`` -> "dense" or "compact"; "compact" has no CPU form."""
+    if coalitions is not None and coalitions not in COALITIONS:
+        raise IqError("coalitions must be one of %s or None, got %r" % (COALITIONS, coalitions))
+    if coalitions == "compact" and not data.is_cuda:
+        raise IqError("coalitions='compact' needs the cloud on a GPU (no CPU fallback)")
+    return coalitions or "dense"
 
 
 def prefix_keep_masks(orders, num_regions):
@@ -37,20 +50,28 @@ def prefix_keep_masks(orders, num_regions):
     return hip_ops.region_words(orders, r, prefixes=True).reshape(-1, w)
 
 
-def coalition_logits(model, data, region_id, keep, args):
+def coalition_logits(model, data, region_id, keep, args, coalitions=None):
     """Logits of the wide coalitions ``keep`` ((B,W) int64-typed device tensor or uint64 ndarray) of one cloud ``data`` (1,N,3);
-    every masked point collapses onto the mean of the cloud (tools/final_common.py:80).  ``args``: model, num_regions."""
+    every masked point collapses onto the mean of the cloud (tools/final_common.py:80).  ``args``: model, num_regions.
+    ``coalitions``: None / "dense" - a family other than PointNet runs its dense forward on materialised clouds - or "compact" -
+    its compact coalition path (IqError for a cloud that path does not take: PointNet++ and PointConv above 1024 points)."""
+    mode = _pick_coalitions(coalitions, data)
     r = int(args.num_regions)
     keep = (hip_ops.wide_masks_to_tensor(keep, data.device) if isinstance(keep, np.ndarray) else keep).contiguous()
     hip_ops.wide_keep(keep, r)
-    return _logits(model, data, hip_ops.region_ids(region_id, data.device, r), keep, r)
+    return _logits(model, data, hip_ops.region_ids(region_id, data.device, r), keep, r, mode)
 
 
-def _logits(model, data, rid, keep, r):
-    """coalition_logits on validated region ids (int32 device tensor) and a (B,W) device tensor."""
+def _fused(model):
+    """PointNet: one fused wide path, whatever ``coalitions`` says."""
+    return hasattr(model, "prefix_logits_wide")
+
+
+def _logits(model, data, rid, keep, r, mode="dense"):
+    """coalition_logits on validated region ids (int32 device tensor) and a (B,W) device tensor; ``mode`` "dense" or "compact"."""
     center = torch.mean(data, dim=1)
     work.add(keep.shape[0])
-    if hasattr(model, "coalition_logits_wide"):
+    if mode == "compact" or _fused(model):
         return model.coalition_logits_wide(data.contiguous(), center.reshape(1, 3).contiguous(), rid.reshape(1, -1), keep, None,
                                            num_regions=r, validate=False)
     cloud, c3 = data[0].contiguous(), center.reshape(3).contiguous()
@@ -68,39 +89,43 @@ def _pick_route(model, route):
     return route or (DEFAULT_ROUTE if fused else "keep")
 
 
-def _prefix_logits(model, data, rid, orders_dev, r):
+def _prefix_logits(model, data, rid, orders_dev, r, mode="dense"):
     """prefix_logits on validated region ids and an (S,R) int32 device tensor of permutations."""
     if not hasattr(model, "prefix_logits_wide"):
-        return _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(orders_dev), r)
+        return _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(orders_dev), r, mode)
     center = torch.mean(data, dim=1)
     work.add(orders_dev.shape[0] * (r + 1))
     return model.prefix_logits_wide(data.contiguous(), center.reshape(1, 3).contiguous(), rid.reshape(1, -1), orders_dev, None,
                                     num_regions=r, validate=False)
 
 
-def prefix_logits(model, data, region_id, orders, args):
+def prefix_logits(model, data, region_id, orders, args, coalitions=None):
     """Logits of the prefix coalitions of the permutations ``orders`` ((S,R) ndarray or int32 device tensor) of one cloud ``data``
     (1,N,3): row o*(R+1)+i keeps orders[o][:i] (tools/final_common.py:56-60) - ``coalition_logits`` on
     hip_ops.prefix_keep_masks_wide(orders), bit for bit.  PointNet evaluates them straight from the permutations; a family
-    without ``prefix_logits_wide`` goes through the keep rows.  ``args``: model, num_regions."""
+    without ``prefix_logits_wide`` goes through the keep rows, evaluated as ``coalitions`` says (``coalition_logits``).
+    ``args``: model, num_regions."""
+    mode = _pick_coalitions(coalitions, data)
     r = int(args.num_regions)
     hip_ops.wide_words(r)
     if isinstance(orders, np.ndarray):
         orders = hip_ops.as_i32(orders, data.device)
     if orders.dim() != 2 or orders.shape[1] != r:
         raise IqError("orders must be (S, %d), got %s" % (r, tuple(orders.shape)))
-    return _prefix_logits(model, data, hip_ops.region_ids(region_id, data.device, r), orders.contiguous(), r)
+    return _prefix_logits(model, data, hip_ops.region_ids(region_id, data.device, r), orders.contiguous(), r, mode)
 
 
-def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None, route=None):
+def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None, route=None, coalitions=None):
     """The sampling loop of final_shapley_value.py:138-156 for one cloud ``data`` (1,N,3) and the permutations ``orders`` ((S,R)
     ndarray): -> (running sums {count: (R,) float64} at ``snap_counts``, per-permutation rows (S,R) float64, total (R,)), shaped
     like shapley_stage.shapley_all_orders.  ``perms_per_step`` permutations at a time (default: about 2^17 coalitions), so the
     logits of 1000 x 1025 coalitions are never resident at once.  ``route``: "prefix" evaluates a step straight from its
     permutations (``prefix_logits``; IqError for a model without that entry), "keep" builds the prefix masks on the device and
     evaluates them as arbitrary coalitions, None takes "prefix" where the model has it - the values are the same bits either
-    way.  Prefix sets of different permutations almost never coincide at these region counts: no de-duplication."""
+    way.  ``coalitions``: how a family other than PointNet evaluates the keep rows (``coalition_logits``).  Prefix sets of
+    different permutations almost never coincide at these region counts: no de-duplication."""
     route = _pick_route(model, route)
+    mode = _pick_coalitions(coalitions, data)
     dev = data.device
     r = int(args.num_regions)
     hip_ops.wide_words(r)
@@ -118,9 +143,9 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
             hi = min(lo + step, s)
             step_orders = orders_dev[lo:hi].contiguous()
             if route == "prefix":
-                logits = _prefix_logits(model, data, rid, step_orders, r)
+                logits = _prefix_logits(model, data, rid, step_orders, r, mode)
             else:
-                logits = _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(step_orders), r)
+                logits = _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(step_orders), r, mode)
             v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
     return hip_ops.shapley_snapshots(v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
 
@@ -170,14 +195,16 @@ def context_keep_masks(pairs, contexts, num_regions):
     return np.stack([s | bi | bj, s | bi, s | bj, s], axis=2).reshape(4 * p * c, w)
 
 
-def interaction_logits(model, data, region_id, pairs, contexts, args):
+def interaction_logits(model, data, region_id, pairs, contexts, args, coalitions=None):
     """final_point_binary_interaction_logits.py:15-70 for a wide game: the logits of the four coalitions S+{i,j}, S+{i}, S+{j}, S
     of every (pair, context) of ONE ratio on one cloud ``data`` (1,N,3), perturbed or not (masked points collapse onto
     torch.mean(data, dim=1)) -> (P, 4C, K) float32.  ``pairs`` (P,2), ``contexts`` (P,C,m) host arrays of any integer type;
     ``args``: model, num_regions.  The contexts go to the device as int32 (at most about 110 MB at R = 1024), the keep rows are
     built there (iq_context_keep_masks_wide) and evaluated as ``coalition_logits`` evaluates them: PointNet fused, in launches of
-    at most 2^16 coalitions, every other family through its dense forward.  Sampled contexts of more than 64 regions do not
+    at most 2^16 coalitions, every other family through its dense forward or, with ``coalitions="compact"``, its compact
+    path.  Sampled contexts of more than 64 regions do not
     coincide: no de-duplication (interaction.compute_order_interaction_logits, the narrow stage, evaluates distinct sets once)."""
+    mode = _pick_coalitions(coalitions, data)
     dev = data.device
     r = int(args.num_regions)
     hip_ops.wide_words(r)
@@ -190,5 +217,5 @@ def interaction_logits(model, data, region_id, pairs, contexts, args):
     rid = hip_ops.region_ids(region_id, dev, r)
     with torch.no_grad():
         keep = hip_ops.context_keep_masks_wide(hip_ops.as_i32(pairs, dev), hip_ops.as_i32(ctx, dev), r)
-        logits = _logits(model, data, rid, keep, r)
+        logits = _logits(model, data, rid, keep, r, mode)
     return logits.reshape(p, 4 * c, -1)

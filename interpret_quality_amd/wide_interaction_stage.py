@@ -67,7 +67,8 @@ def evaluate(model, data, lbl, region_id, folder, save_path, args):
     for ratio in args.ratio:
         tag = int(ratio * 100)
         context_list = np.load(folder + "ratio%d_context_list.npy" % tag)
-        all_logits = wide.interaction_logits(model, data, region_id, pairs, context_list, args)
+        all_logits = wide.interaction_logits(model, data, region_id, pairs, context_list, args,
+                                             coalitions=getattr(args, "coalitions", None))
         torch.save(all_logits, save_path + "ratio%d_all_logits.pt" % tag)
         np.save(save_path + "ratio%d_%s_interaction.npy" % (tag, args.output_type), wide.interactions(all_logits, lbl, args))
         print("\tratio: %f, logits %s" % (ratio, tuple(all_logits.shape)))
@@ -109,6 +110,9 @@ def make_args(argv=None):
     parser.set_defaults(device_id=0)
     parser.add_argument("--transform_params", type=str, default=None, metavar="FILE.npy",
                         help="the --mode parameters of one pose: the same pairs and contexts are also evaluated there")
+    parser.add_argument("--coalitions", choices=wide.COALITIONS, default=None,
+                        help="how a family other than PointNet evaluates the coalitions: dense = its dense forward on materialised "
+                             "clouds (the default), compact = its compact coalition path; the same artefacts, equal to rounding")
     args = parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
                            "the wide stage takes %d .. %d regions (final_gen_pair.py and final_point_binary_interaction_logits.py: "
                            "up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS), samples=False)

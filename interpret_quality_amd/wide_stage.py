@@ -9,7 +9,7 @@ derives from ``--num_regions`` - so a run never overwrites a 32-region run:
 The permutations come from NumPy's global generator on the host, exactly as the reference's generate_all_orders draws them
 (final_shapley_value.py:59-72); the device sampler of stage 1 stays a 64-region kernel.  The FPS centres go to their own
 fps_<dataset>_<N>_<R>_index_final30.npy.  ``--route prefix|keep`` picks how ``wide.shapley`` evaluates the prefix coalitions (the
-same bits either way).  Single process: under several ranks rank 0 does the work and the others wait.  The
+same bits either way), ``--coalitions dense|compact`` how a family other than PointNet evaluates them (wide.py).  Single process: under several ranks rank 0 does the work and the others wait.  The
 multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py).  The smoothness and pose
 stages have no wide form.
 """
@@ -53,7 +53,7 @@ def run(args):
             all_orders = generate_all_orders(result_path, args)
             print("pointcloud:%s, index:%d, regions:%d, samples:%d" % (name, i, args.num_regions, len(all_orders)))
             snaps, region_sv_all, _ = wide.shapley(model, data, lbl, region_id, all_orders, args, snap_counts=stage1.SAMPLE_NUMS,
-                                                   route=args.route)
+                                                   route=args.route, coalitions=getattr(args, "coalitions", None))
             for count, running in snaps.items():
                 stage1.save_shapley(running, i, count, result_path, region_id, args)
             np.save(result_path + "region_sv_all.npy", region_sv_all)
@@ -64,6 +64,9 @@ def make_args(argv=None):
     parser.add_argument("--route", choices=wide.ROUTES, default=None,
                         help="how the prefix coalitions are evaluated: prefix = straight from the permutations (PointNet), keep = "
                              "through keep rows; the same bits either way (default: prefix where the model has it)")
+    parser.add_argument("--coalitions", choices=wide.COALITIONS, default=None,
+                        help="how a family other than PointNet evaluates the coalitions: dense = its dense forward on materialised "
+                             "clouds (the default), compact = its compact coalition path; the same artefacts, equal to rounding")
     return stage1.parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
                                   "the wide stage takes %d .. %d regions (final_shapley_value.py: up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS))
 

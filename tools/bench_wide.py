@@ -5,6 +5,7 @@
     python tools/bench_wide.py --profile-step 1024 [--route keep|prefix]   # one warmed step only: the program for rocprofv3 --kernel-trace --stats
     python tools/bench_wide.py --prefix                 # wide.shapley, keep route against prefix route, into the "prefix" key of --out
     python tools/bench_wide.py --interaction            # the interaction stage only, into the "interaction" key of --out
+    python tools/bench_wide.py --compact                # the other families, dense against compact, into the "compact" key of --out
 
 1. Wide against narrow at R = 32 (the headline's workload: 1000 permutations, 33 000 coalitions) and R = 64: the SAME coalitions
    through iq_pointnet_coalitions (the yardstick: untouched code) and iq_pointnet_coalitions_wide, alternated in one process,
@@ -25,6 +26,13 @@
    both, ``repeats`` runs each (at least five), with as many whole steps of permutations as make a run about a second.  Reported per
    R: seconds and coalitions/s of every run, median and spread of each route, the ratio of the medians, whether the Shapley rows are
    the same bits, and ``prefix_slower_beyond_spread`` - the one condition under which wide.DEFAULT_ROUTE must be "keep".
+
+5. ``--compact``: the other families (pointnet2, dgcnn, gcnn, pointconv; ``--families``) - wide.shapley on one synthetic cloud,
+   N = 1024, at R = 128 and R = 1024, coalitions="dense" (the yardstick: the parent's code path, untouched - masked clouds into the
+   dense forward) against coalitions="compact" (the iq_*_coalitions_wide entries), alternated in one process after one warm-up of
+   both, five runs each, with as many whole permutations as make a dense run about a second.  Reported per family and R: seconds
+   and coalitions/s of every run, median and spread of each route, the ratio of the medians, ``compact_faster_beyond_spread`` and
+   the norm-wise difference of the Shapley rows.  Into the "compact" key of --out.  No threshold hangs on these numbers.
 
 Times are host clocks around work that ends in a device synchronise.  Kernel shares come from a separate run under the profiler
 (--profile-step): tracing slows the host, so no rate is taken there."""
@@ -156,6 +164,54 @@ def prefix_vs_keep(model, r, repeats, dev, min_seconds=1.0):
     return out
 
 
+COMPACT_FAMILIES = ("pointnet2", "dgcnn", "gcnn", "pointconv")
+
+
+def _family_model(family, dev):
+    ns = argparse.Namespace(dataset="modelnet10", k=20)
+    if family == "pointnet2":
+        from interpret_quality_amd.pointnet2 import PointNet2ClsMsg
+        model, sd = PointNet2ClsMsg(None), synth.pointnet2_state_dict(0)
+    elif family == "pointconv":
+        from interpret_quality_amd.pointconv import PointConvDensityClsSsg
+        model, sd = PointConvDensityClsSsg(None), synth.pointconv_state_dict(0)
+    else:
+        from interpret_quality_amd.dgcnn import DGCNN_cls, GCNN_cls
+        model, sd = (DGCNN_cls if family == "dgcnn" else GCNN_cls)(ns), synth.dgcnn_state_dict(0)
+    model.load_state_dict(synth.to_torch(sd))
+    return model.to(dev).eval()
+
+
+def compact_vs_dense(family, model, r, repeats, dev, min_seconds=1.0):
+    """wide.shapley on one cloud, coalitions "dense" against "compact", alternated; see the module docstring, 5."""
+    import math
+    from interpret_quality_amd import wide
+    data, _, rid = _setup(r, dev)
+    rid_np = rid[0].cpu().numpy().astype(np.int64)
+    lbl = torch.zeros((1,), dtype=torch.int64, device=dev)
+    args = argparse.Namespace(model=family, softmax_type="modified", num_points=1024, num_regions=r, verbose=False)
+    run = lambda mode, orders: wide.shapley(model, data, lbl, rid_np, orders, args, coalitions=mode)      # noqa: E731
+    one = synth.make_orders(1, r, seed=1)
+    run("dense", one)                              # sizing: a warmed dense run of one permutation
+    t_perm = _clock(lambda: run("dense", one))[0]
+    perms = max(1, math.ceil(min_seconds / t_perm))
+    orders = synth.make_orders(perms, r, seed=1)
+    rows = {mode: run(mode, orders)[1] for mode in wide.COALITIONS}      # the one warm-up of both routes at the run's shape
+    diff = float(np.linalg.norm(rows["compact"] - rows["dense"]) / max(np.linalg.norm(rows["dense"]), 1e-300))
+    times = {mode: [] for mode in wide.COALITIONS}
+    for _ in range(repeats):
+        for mode in wide.COALITIONS:
+            times[mode].append(_clock(lambda: run(mode, orders))[0])
+    b = perms * (r + 1)
+    out = {"family": family, "regions": r, "points": 1024, "permutations": perms, "coalitions": b, "rows_rel_norm_diff": diff}
+    for mode in wide.COALITIONS:
+        out[mode] = dict(_summary([b / t for t in times[mode]]), seconds=times[mode], median_seconds=statistics.median(times[mode]))
+    dense, compact = out["dense"], out["compact"]
+    out["ratio_compact_over_dense"] = compact["median"] / dense["median"]
+    out["compact_faster_beyond_spread"] = (compact["median"] - dense["median"]) / dense["median"] > max(dense["spread"], compact["spread"])
+    return out
+
+
 def _interaction_inputs(r, pairs_n, ctx_n, ratio):
     from interpret_quality_amd import wide
     np.random.seed(1)
@@ -233,10 +289,27 @@ def main(argv=None):
                     help="time wide.shapley, keep route against prefix route (leg 4), and put it under \"prefix\" in --out, keeping what is there")
     ap.add_argument("--interaction", action="store_true",
                     help="time the interaction stage only (legs 3a, 3b) and put it under \"interaction\" in --out, keeping what is there")
+    ap.add_argument("--compact", action="store_true",
+                    help="time wide.shapley of the other families, dense against compact coalitions (leg 5), and put it under "
+                         "\"compact\" in --out, keeping what is there")
+    ap.add_argument("--families", nargs="+", choices=COMPACT_FAMILIES, default=list(COMPACT_FAMILIES), help="the families of --compact")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("bench_wide.py needs a GPU: a time taken elsewhere says nothing about the MI355X")
     dev = torch.device("cuda:0")
+    if args.compact:
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        legs = res.get("compact", {}).get("legs", [])
+        for family in args.families:
+            model = _family_model(family, dev)
+            for r in (128, 1024):
+                leg = compact_vs_dense(family, model, r, 5, dev)
+                legs = [l for l in legs if (l["family"], l["regions"]) != (family, r)] + [leg]
+            del model
+            torch.cuda.empty_cache()
+        res["compact"] = {"device": torch.cuda.get_device_name(0), "repeats": 5, "legs": legs}
+        _write(args.out, res)
+        return
     model = _model(dev)
     if args.profile_step:
         run, b = _wide_step(model, args.profile_step, args.perms, dev, args.route)
