@@ -59,8 +59,10 @@ enum {
  * 106: new entry point, no layout change (iq_context_keep_masks_wide: the interaction stage of wide games).
  * 107: new entry point, no layout change (iq_pointnet_prefix_coalitions_wide: prefix coalitions straight from permutations).
  * 108: new entry points, no layout change (the other families' compact coalition paths for wide keep rows:
- * iq_dgcnn_coalitions_wide, iq_pointnet2_coalitions_wide, iq_pointconv_coalitions_wide, iq_pointconv_coalitions_cached_wide). */
-#define IQ_ABI_VERSION 108
+ * iq_dgcnn_coalitions_wide, iq_pointnet2_coalitions_wide, iq_pointconv_coalitions_wide, iq_pointconv_coalitions_cached_wide).
+ * 109: new entry points, no layout change (iq_split_packed_weight_bf3, iq_split_packed_weight_bf3_host); the PointNet workspaces
+ * grew by the bf16x3 image of fstn.fc3 (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes). */
+#define IQ_ABI_VERSION 109
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -241,6 +243,12 @@ int iq_pack_weight(const float* w_host /*cout,cin*/, float* out_host, int cout, 
  * k range is cin rounded up to a multiple of 32, zero beyond cin (the dense layer never reads A's columns there). */
 size_t iq_packed_bf3_elems(int cout, int cin);
 int iq_pack_weight_bf3(const float* w_host /*cout,cin*/, unsigned short* out_host, int cout, int cin);
+/* The same image derived from the layer's float32 image (iq_pack_weight order) ON THE DEVICE: packed_w and out_bf3 are device
+ * pointers (iq_packed_floats and iq_packed_bf3_elems elements), byte for byte what iq_pack_weight_bf3 gives for the weight that
+ * packed_w was packed from.  iq_pointnet_coalitions derives fstn.fc3's bf16x3 image this way, once per call, into its workspace.
+ * _host: the same maps and split in a host loop over host pointers (for checks without a device). */
+int iq_split_packed_weight_bf3(const float* packed_w, unsigned short* out_bf3, int cout, int cin, iq_stream_t stream);
+int iq_split_packed_weight_bf3_host(const float* packed_w_host, unsigned short* out_host, int cout, int cin);
 /* feat.fstn.fc3 (4096 x 256): permutes the output rows so that the layer's output vector IS the
  * packed B-fragment image of trans_feat for the trunk's per-coalition 64x64 product, and adds the
  * identity (models/pointnet.py:42-45) into the bias.  out_w has iq_packed_floats(4096,256)

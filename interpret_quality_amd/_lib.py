@@ -99,6 +99,8 @@ SIGNATURES = {
     "iq_pack_weight": (_I, [_P, _P, _I, _I]),
     "iq_packed_bf3_elems": (_SZ, [_I, _I]),
     "iq_pack_weight_bf3": (_I, [_P, _P, _I, _I]),
+    "iq_split_packed_weight_bf3": (_I, [_P, _P, _I, _I, _P]),
+    "iq_split_packed_weight_bf3_host": (_I, [_P, _P, _I, _I]),
     "iq_pack_fstn_fc3": (_I, [_P, _P, _P, _P, _P]),
     "iq_pointnet_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "iq_pointnet_coalitions": (_I, [ctypes.POINTER(PointNetWeights), _P, _P, _P, _P, _P, _P, _P, _P, _SZ,
@@ -158,7 +160,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 108   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 109   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

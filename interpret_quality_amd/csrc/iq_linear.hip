@@ -1,7 +1,9 @@
 // The dense layer every model shares: out = act(A W^T + b) on weights pre-packed in MFMA B-fragment order
 // (iq_pack_weight).  Two kernels with bit-identical results (same MFMA order over k), a split-K form for few rows x very
-// long K, and a form whose epilogue does the first stage of a pooling layer.  fp32 MFMA (v_mfma_f32_32x32x2_f32) only.
+// long K, and a form whose epilogue does the first stage of a pooling layer, on the fp32 MFMA (v_mfma_f32_32x32x2_f32); below them the same layer as bf16x3 on the
+// bf16 matrix pipe (gemm_bf3_tile), the weight packers and the device split of a float32 weight image into its bf16x3 image.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 
 #include "iq_common.h"
@@ -318,7 +320,7 @@ __global__ __launch_bounds__(kThreads, 2) void pn_gemm_lds_kernel(const float* _
 // 16 k cost 6 x 32 = 192 matrix cycles instead of 8 x 64 = 512.
 //   * weights: split and packed once on the host (iq_pack_weight_bf3): [term][n-tile][k-step of 16][lane][8 bf16], 1 KB per
 //     fragment, streamed through a ring of the four n-tiles' fragments one k-step (1 536 matrix cycles) ahead;
-//   * activations: read ONCE as float32 (128 rows x 32 k per chunk, full-line coalesced), split in registers while they are
+//   * activations: read ONCE as float32 (128 rows x 32 k per chunk - 32 MT rows in gemm_bf3_tile<.., MT> -, full-line coalesced), split in registers while they are
 //     staged, three bf16 planes in LDS (row stride 80 bytes: conflict-free ds_read_b128), double-buffered;
 //   * tile, epilogue and output exactly those of pn_gemm_lds_kernel<4, true>: 128 rows x 256 columns per workgroup, per 32-row
 //     tile the column maxima and weighted sums.
@@ -328,33 +330,35 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // POOL = false: the plain dense layer out (M, ldo) = act(A W^T + b) on the same tiles (launch_linear, for layers that carry
 // iq_dense_layer.w_bf3); tile_nu / rows_per_cloud as in pn_gemm_lds_kernel.
-template <bool POOL, int NW = 4, bool RAGGED = false, bool SPLITK = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(const float* __restrict__ A, int lda,
-                                                                  const unsigned short* __restrict__ w3,
-                                                                  const float* __restrict__ bias, float* __restrict__ out, int ldo,
-                                                                  int M, int K, int Nout, int relu,
-                                                                  const int32_t* __restrict__ m_dev,
-                                                                  const float* __restrict__ row_w, int col_blocks,
-                                                                  const int32_t* __restrict__ tile_nu, int rows_per_cloud, int Kreal,
-                                                                  int chunks_per_split) {
+// MT = m-tiles of 32 rows per workgroup (4: the 128-row tile above).  2 and 1 are launch_linear's short tiles for launches that
+// would leave the chip part empty at 128 rows: fewer accumulators and a smaller LDS image, so that three (MT = 2) or four
+// (MT = 1) workgroups share a CU; a row's sums take the same MFMAs in the same order over k whatever MT is - bit-identical.
+template <bool POOL, int NW, bool RAGGED, bool SPLITK, int MT>
+__device__ __forceinline__ void gemm_bf3_tile(const float* __restrict__ A, int lda, const unsigned short* __restrict__ w3,
+                                              const float* __restrict__ bias, float* __restrict__ out, int ldo, int M, int K, int Nout,
+                                              int relu, const int32_t* __restrict__ m_dev, const float* __restrict__ row_w,
+                                              int col_blocks, const int32_t* __restrict__ tile_nu, int rows_per_cloud, int Kreal,
+                                              int chunks_per_split) {
     // SPLITK (few rows, very long K: launch_linear_splitk): workgroup row blockIdx.y takes chunks_per_split 32-k chunks and writes
     // its RAW partial sums to out + blockIdx.y * M * ldo; bias and activation belong to splitk_reduce_kernel.
     // K = the layer's inputs rounded up to a multiple of 32 (the weight image is zero there, iq_pack_weight_bf3), Kreal = the
     // columns A really has (a multiple of 8).  RAGGED (Kreal < K; its own instantiation - the few registers it needs would spill
     // in the others): the last chunk's columns beyond Kreal are taken as zero.
-    // wave tile: ALL 128 rows (MT = 4 m-tiles) x 64 columns (NT = 2): a weight fragment feeds four m-tiles - with 64 x 128 wave
+    // wave tile: ALL rows of the workgroup (128: MT = 4 m-tiles) x 64 columns (NT = 2): a weight fragment feeds four m-tiles - with 64 x 128 wave
     // tiles (two m-tiles per fragment) the weight stream alone asked the L2 for 19 TB/s at full matrix rate
-    constexpr int MT = 4, NT = 2, KC = 32, ROWB = 80, PLANE = 128 * ROWB;      // bytes
-    constexpr int NTH = 64 * NW, NLD = 1024 / NTH;    // threads; (row, 4 k) items per thread and chunk
+    constexpr int ROWS = 32 * MT, NT = 2, KC = 32, ROWB = 80, PLANE = ROWS * ROWB;      // bytes
+    constexpr int NTH = 64 * NW, NLD = ROWS * 8 / NTH;    // threads; (row, 4 k) items per thread and chunk
+    static_assert(MT == 4 || (MT >= 1 && NW == 4 && !POOL && !SPLITK), "short tiles: the plain dense layer only");
+    static_assert(NLD * NTH == ROWS * 8, "chunk items per thread");
     __shared__ __attribute__((aligned(16))) unsigned char As[2][3 * PLANE];
     __shared__ float wrow[POOL ? 128 : 1];
-    const int row_tiles = (M + 127) / 128;
+    const int row_tiles = (M + ROWS - 1) / ROWS;
     const int per = 8 * col_blocks, grp = blockIdx.x / per, rr = blockIdx.x - grp * per;
     const int bx = grp * 8 + (rr & 7), by = rr >> 3;                   // column blocks of a row tile side by side on one XCD
     if (bx >= row_tiles) return;
     if (m_dev) M = min(M, *m_dev);
-    int m0 = bx * 128;
-    if (!POOL && tile_nu) {   // as pn_gemm_lds_kernel: cloud-fastest walk, tiles beyond a cloud's live rows skipped
+    int m0 = bx * ROWS;
+    if (!POOL && MT == 4 && tile_nu) {   // as pn_gemm_lds_kernel: cloud-fastest walk, tiles beyond a cloud's live rows skipped
         const int ntc = rows_per_cloud / 128, nc = row_tiles / ntc;
         if (nc * ntc == row_tiles) m0 = ((bx % nc) * ntc + bx / nc) * 128;
         if (m0 >= M) return;
@@ -375,7 +379,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(c
     const int NTT = (Nout + 31) >> 5;
     const int nt0 = (by * NW + wave) * NT;
 
-    // activations: thread t owns (row, 4 k) = (e >> 3, (e & 7) * 4) for e = t + 256 i
+    // activations: thread t owns (row, 4 k) = (e >> 3, (e & 7) * 4) for e = t + NTH i, i < NLD = 32 MT * 8 / NTH
     // A's resource ends with the last row's last real column, so that the partial last chunk of a layer whose inputs are no
     // multiple of 32 reads zeros there, not memory behind the matrix (rows are clamped to M - 1 below)
     WBuf ab = wbuf_make(A + (size_t)m0 * lda, lane);
@@ -463,7 +467,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(c
             for (int j = 0; j < NT; ++j) {
                 const B3 b = ring[s][j];                            // (k-step parity = s: two steps per chunk)
                 ring[s][j] = wfrag(j, ks + 2);
-                // four accumulation chains interleaved (a dependent MFMA waits for its predecessor); small terms first
+                // MT accumulation chains interleaved (a dependent MFMA waits for its predecessor); small terms first.  (MT = 1: the six
+                // MFMAs of an n-tile are ONE dependent chain, and only the other n-tile and the CU's other waves fill its waits - the
+                // likely reason 32-row tiles lose where a launch has many rounds, 256 -> 4096: 509 us against 445.)
 #pragma unroll
                 for (int i = 0; i < MT; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b.h, acc[i][j], 0, 0, 0);
 #pragma unroll
@@ -545,10 +551,109 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(c
     }
 }
 
+#define IQ_GEMM_BF3_PARAMS                                                                                                          \
+    const float *__restrict__ A, int lda, const unsigned short *__restrict__ w3, const float *__restrict__ bias,                     \
+        float *__restrict__ out, int ldo, int M, int K, int Nout, int relu, const int32_t *__restrict__ m_dev,                       \
+        const float *__restrict__ row_w, int col_blocks, const int32_t *__restrict__ tile_nu, int rows_per_cloud, int Kreal,         \
+        int chunks_per_split
+#define IQ_GEMM_BF3_ARGS A, lda, w3, bias, out, ldo, M, K, Nout, relu, m_dev, row_w, col_blocks, tile_nu, rows_per_cloud, Kreal, chunks_per_split
+
+// the 128-row tile: two workgroups per CU
+template <bool POOL, int NW = 4, bool RAGGED = false, bool SPLITK = false>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void pn_gemm_bf3_kernel(IQ_GEMM_BF3_PARAMS) {
+    gemm_bf3_tile<POOL, NW, RAGGED, SPLITK, 4>(IQ_GEMM_BF3_ARGS);
+}
+
+// the plain dense layer on short tiles, MT = 2 / 1 (64 / 32 rows): three / four workgroups per CU
+template <int MT, bool RAGGED>
+__global__ __launch_bounds__(kThreads, MT == 2 ? 3 : 4) void pn_gemm_bf3_short_kernel(IQ_GEMM_BF3_PARAMS) {
+    gemm_bf3_tile<false, 4, RAGGED, false, MT>(IQ_GEMM_BF3_ARGS);
+}
+#undef IQ_GEMM_BF3_PARAMS
+#undef IQ_GEMM_BF3_ARGS
+
+}  // namespace
+
+namespace {
+
+// multiprocessors of the CURRENT device, asked once per device.  (A stream of another device would get this device's count: the
+// tile heights would be chosen for the wrong chip, the results not touched - they do not depend on the tiles.)
+int cu_count() {
+    constexpr int kMaxDev = 64;
+    static std::atomic<int> cached[kMaxDev];
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (dev >= 0 && dev < kMaxDev && (n = cached[dev].load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return 0;
+    if (dev >= 0 && dev < kMaxDev) cached[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+// one grid of pn_gemm_bf3_kernel<false> (MT = 4) or pn_gemm_bf3_short_kernel with MT m-tiles per workgroup over rows [0, M) and the first gy column blocks of 256
+template <int MT>
+void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
+                     const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy) {
+    const int Kp = (L.cin + 31) & ~31;     // the bf16x3 image's k range (iq_pack_weight_bf3 pads with zero columns)
+    const int gx = (M + 32 * MT - 1) / (32 * MT);
+    const dim3 grid((unsigned)((gx + 7) / 8 * 8 * gy));
+    const unsigned short* w3 = reinterpret_cast<const unsigned short*>(L.w_bf3);
+    const bool ragged = Kp != L.cin;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, A, lda, w3, L.b, out, ldo, M, Kp, L.cout, relu, m_dev,
+                           static_cast<const float*>(nullptr), gy, tile_nu, rows_per_cloud, L.cin, 0);
+    };
+    if constexpr (MT == 4) {
+        if (ragged) launch(pn_gemm_bf3_kernel<false, 4, true>);
+        else launch(pn_gemm_bf3_kernel<false>);
+    } else {
+        if (ragged) launch(pn_gemm_bf3_short_kernel<MT, true>);
+        else launch(pn_gemm_bf3_short_kernel<MT, false>);
+    }
+}
+
+// The plain bf16x3 dense layer.  128-row workgroups sit two to a CU, in rounds of 2 x CUs; 64-row ones three, 32-row ones four to
+// a CU.  A grid of fewer than 2 x CUs workgroups leaves every SIMD a single wave, which does not feed the matrix pipe, and a grid a
+// few workgroups over a whole number of rounds pays nearly a round for them.  Measured at 33 000 rows on 256 CUs
+// (profiles/heads_profile.txt; 128-row tiles -> the choice below):
+//   * fewer than one round at 128 rows: 32-row tiles throughout           (512 -> 256: 258 workgroups, 80 -> 60 us; 64-row tiles 64)
+//   * fewer than two rounds: 64-row tiles throughout                      (1024 -> 512: 516 workgroups, 221 -> 188 us; 128-row
+//     tiles for the whole round and 32-row ones for the 232 rows left: 195; 32-row tiles throughout: 196)
+//   * from two rounds on: 128-row tiles, and where the last round is at most a quarter / a half full its rows go to a second grid
+//     of 32- / 64-row tiles behind the whole rounds                       (256 -> 4096: 8.06 rounds, 447 -> 445 us, nothing; 64-row
+//     tiles throughout 433, 32-row ones 509 - the short tiles' weight stream is 2 x / 4 x per row)
+//   * without fit_tiles (the other families' launches, not re-measured), with rows that only the device knows (m_dev), with
+//     tile_nu and under twin kTwinDenseTile128: 128-row tiles only, the former launch.
+// Which tile a row falls in changes nothing in its result (gemm_bf3_tile: MT), so the result stays independent of M.
+int launch_bf3(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
+               const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, bool fit_tiles) {
+    if (!fit_tiles || m_dev || tile_nu || iq::twin() == iq::kTwinDenseTile128) {
+        launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy);
+        return iq::check_launch("pn_gemm_bf3_kernel");
+    }
+    const int cus = cu_count();
+    if (cus <= 0) return iq::fail(IQ_ELAUNCH, "dense layer: cannot read the device's multiprocessor count");
+    const long long round = 2LL * cus, tiles = (M + 127) / 128, wgs = tiles * gy;
+    const int m_full = (int)(wgs / round * round / gy) * 128;     // rows of the whole rounds
+    if (wgs < round) {
+        launch_bf3_rows<1>(A, lda, L, out, ldo, M, relu, st, nullptr, nullptr, 0, gy);
+    } else if (wgs < 2 * round) {
+        launch_bf3_rows<2>(A, lda, L, out, ldo, M, relu, st, nullptr, nullptr, 0, gy);
+    } else if (wgs % round == 0 || wgs % round > round / 2 || m_full <= 0 || m_full >= M) {
+        launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, nullptr, nullptr, 0, gy);
+    } else {
+        launch_bf3_rows<4>(A, lda, L, out, ldo, m_full, relu, st, nullptr, nullptr, 0, gy);
+        const float* At = A + (size_t)m_full * lda;
+        float* ot = out + (size_t)m_full * ldo;
+        if (wgs % round <= round / 4) launch_bf3_rows<1>(At, lda, L, ot, ldo, M - m_full, relu, st, nullptr, nullptr, 0, gy);
+        else launch_bf3_rows<2>(At, lda, L, ot, ldo, M - m_full, relu, st, nullptr, nullptr, 0, gy);
+    }
+    return iq::check_launch("pn_gemm_bf3_kernel");
+}
+
 }  // namespace
 
 int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu,
-                      hipStream_t st, const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud) {
+                      hipStream_t st, const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, bool fit_tiles) {
     if (M == 0) return IQ_OK;
     IQ_REQUIRE(L.w && L.b && L.cin % 8 == 0 && L.cout >= 1, "dense layer: bad descriptor (cin=%d cout=%d)", L.cin, L.cout);
     const int ntiles = (L.cout + 31) / 32;
@@ -558,39 +663,20 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
     // (column blocks of 256: 320 outputs would leave the second block a quarter full, and lose to the NT = 5 fp32 tiling - so the
     // whole blocks of such a layer go to the bf16 pipe and its last 64 columns to the fp32 MFMA as a layer of their own; which
     // columns take which arithmetic depends on the layer only, never on M)
-    const int Kp = (L.cin + 31) & ~31;     // the bf16x3 image's k range (iq_pack_weight_bf3 pads with zero columns)
     const bool fp32 = iq::twin() == iq::kTwinDenseFp32;
     if (L.w_bf3 && L.cout > 256 && L.cout % 256 == 64 && L.cin >= 32 && !fp32) {
-        const int gx = (M + 127) / 128, gy = L.cout / 256;
-        if (Kp != L.cin)
-            hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                               reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy,
-                               tile_nu, rows_per_cloud, L.cin, 0);
-        else
-            hipLaunchKernelGGL(pn_gemm_bf3_kernel<false>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                               reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy,
-                               tile_nu, rows_per_cloud, L.cin, 0);
-        int rc = iq::check_launch("pn_gemm_bf3_kernel");
+        const int gy = L.cout / 256;
+        int rc = launch_bf3(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy, fit_tiles);
         if (rc) return rc;
         iq_dense_layer rest = L;                       // n-tiles 8 gy, 8 gy + 1 of the fp32 image (n-tile-major, cin / 8 fragments each)
         rest.w = L.w + (size_t)(8 * gy) * (L.cin / 8) * (kFragBytes / 4);
         rest.b = L.b + 256 * gy;
         rest.cout = 64;
         rest.w_bf3 = nullptr;
-        return launch_linear(A, lda, rest, out + 256 * gy, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud);
+        return launch_linear(A, lda, rest, out + 256 * gy, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, fit_tiles);
     }
-    if (L.w_bf3 && L.cout % 256 == 0 && L.cin >= 32 && !fp32) {
-        const int gx = (M + 127) / 128, gy = (L.cout + 255) / 256;
-        if (Kp != L.cin)
-            hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                               reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy,
-                               tile_nu, rows_per_cloud, L.cin, 0);
-        else
-            hipLaunchKernelGGL(pn_gemm_bf3_kernel<false>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                               reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy,
-                               tile_nu, rows_per_cloud, L.cin, 0);
-        return iq::check_launch("pn_gemm_bf3_kernel");
-    }
+    if (L.w_bf3 && L.cout % 256 == 0 && L.cin >= 32 && !fp32)
+        return launch_bf3(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, L.cout / 256, fit_tiles);
     if (M >= 2048 && (ntiles >= 4 || (ntiles == 2 && (M + 255) / 256 >= 2048)) && L.cin % 32 == 0 && !iq::no_lds_gemm()) {
         if (ntiles % 10 == 0 && (long long)((M + 127) / 128) * (ntiles / 10) >= 2048) {
             // 320 / 640 ... outputs: column blocks of exactly 10 tiles (NT = 5), nothing padded
@@ -706,7 +792,7 @@ extern "C" int iq_linear(const float* A, int lda, const iq_dense_layer* L, float
     IQ_REQUIRE(A && L && out, "iq_linear: null pointer");
     IQ_REQUIRE(M >= 0 && act >= 0 && act <= 2 && lda >= L->cin && ldo >= L->cout, "iq_linear: M=%d act=%d lda=%d ldo=%d", M,
                act, lda, ldo);
-    return iq::launch_linear(A, lda, *L, out, ldo, M, act, iq::as_stream(stream));
+    return iq::launch_linear(A, lda, *L, out, ldo, M, act, iq::as_stream(stream), nullptr, nullptr, 0, true);
 }
 
 // ---- host-side weight packing ---------------------------------------------------------------
@@ -714,22 +800,62 @@ extern "C" int iq_padded_cout(int cout) { return (cout + 31) / 32 * 32; }
 
 extern "C" size_t iq_packed_floats(int cout, int cin) { return (size_t)iq_padded_cout(cout) * cin; }
 
-// bf16 (round to nearest even) of a finite float, as v_cvt_pk_bf16_f32 rounds
-static inline unsigned short iq_bf16_of(float f) {
-    unsigned u;
-    memcpy(&u, &f, 4);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static inline float iq_float_of_bf16(unsigned short h) {
-    const unsigned u = (unsigned)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
 extern "C" size_t iq_packed_bf3_elems(int cout, int cin) { return (size_t)3 * iq_padded_cout(cout) * ((cin + 31) & ~31); }
 
-// [term][n-tile][k-step of 16][lane][8]: lane (n & 31) + 32 ((k >> 3) & 1) holds k-aligned-8 elements of column n
+// ---- the bf16x3 image: what the host packer, the device split and its host twin share ------------------------------------------
+namespace {
+// bf16 (round to nearest even) of a finite float, as v_cvt_pk_bf16_f32 rounds
+__host__ __device__ inline unsigned short bf16_of(float f) {
+    const unsigned u = __builtin_bit_cast(unsigned, f);
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+__host__ __device__ inline float float_of_bf16(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
+
+// v = h + m + l exactly: h = bf16(v), m = bf16(v - h), l = bf16(v - h - m), the residuals exact in float32
+__host__ __device__ inline void bf3_split(float v, unsigned short& h, unsigned short& m, unsigned short& l) {
+    h = bf16_of(v);
+    const float r1 = v - float_of_bf16(h);
+    m = bf16_of(r1);
+    l = bf16_of(r1 - float_of_bf16(m));
+}
+
+// [term][n-tile][k-step of 16][lane][8]: lane (n & 31) + 32 ((k >> 3) & 1) holds k-aligned-8 elements of column n.
+// Element j of `lane` in fragment (nt, ks) is weight (n, k0 + j); its place in a term of KS k-steps per n-tile is bf3_pos + j.
+__host__ __device__ inline int bf3_n(int nt, int lane) { return nt * 32 + (lane & 31); }
+__host__ __device__ inline int bf3_k0(int ks, int lane) { return 16 * ks + 8 * (lane >> 5); }
+__host__ __device__ inline size_t bf3_pos(int nt, int ks, int lane, int KS) { return (((size_t)nt * KS + ks) * 64 + lane) * 8; }
+// place of weight (n, k) in the float32 image of iq_pack_weight: lane (n & 31) + 32 ((k >> 2) & 1) of fragment (n / 32, k / 8)
+// holds four consecutive k
+__host__ __device__ inline size_t packed_pos(int n, int k, int cin) {
+    return ((((size_t)(n >> 5) * (cin >> 3) + (k >> 3)) * 64 + (n & 31) + 32 * ((k >> 2) & 1)) << 2) + (k & 3);
+}
+
+// one thread per (n-tile, k-step, lane): eight weights of the float32 image (two float4) -> their place in the three terms
+__global__ void split_packed_bf3_kernel(const float* __restrict__ packed, unsigned short* __restrict__ out, int ntiles, int KS, int cin) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)ntiles * KS * 64) return;
+    const int lane = (int)(t & 63), ks = (int)((t >> 6) % KS), nt = (int)((t >> 6) / KS);
+    const int n = bf3_n(nt, lane), k0 = bf3_k0(ks, lane);
+    const size_t term = (size_t)ntiles * KS * 512, o = bf3_pos(nt, ks, lane, KS);
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    u16x8 h, m, l;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};       // the image's k range beyond cin (cin % 8 == 0: eight weights lie inside or outside)
+        if (k0 < cin) v = *reinterpret_cast<const f32x4*>(packed + packed_pos(n, k0 + 4 * half, cin));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unsigned short a, b, c;
+            bf3_split(v[j], a, b, c);
+            h[4 * half + j] = a; m[4 * half + j] = b; l[4 * half + j] = c;
+        }
+    }
+    *reinterpret_cast<u16x8*>(out + o) = h;
+    *reinterpret_cast<u16x8*>(out + term + o) = m;
+    *reinterpret_cast<u16x8*>(out + 2 * term + o) = l;
+}
+}  // namespace
+
 extern "C" int iq_pack_weight_bf3(const float* w, unsigned short* out, int cout, int cin) {
     IQ_REQUIRE(w && out && cout >= 1 && cin >= 8 && cin % 8 == 0, "iq_pack_weight_bf3: cout=%d cin=%d", cout, cin);
     const int KS = ((cin + 31) & ~31) / 16, ntiles = iq_padded_cout(cout) / 32;   // k padded to a multiple of 32 with zero columns
@@ -738,14 +864,39 @@ extern "C" int iq_pack_weight_bf3(const float* w, unsigned short* out, int cout,
         for (int ks = 0; ks < KS; ++ks)
             for (int lane = 0; lane < 64; ++lane)
                 for (int j = 0; j < 8; ++j) {
-                    const int n = nt * 32 + (lane & 31), k = 16 * ks + 8 * (lane >> 5) + j;
-                    const float v = n < cout && k < cin ? w[(size_t)n * cin + k] : 0.f;
-                    const unsigned short h = iq_bf16_of(v);
-                    const float r1 = v - iq_float_of_bf16(h);
-                    const unsigned short m = iq_bf16_of(r1);
-                    const unsigned short l = iq_bf16_of(r1 - iq_float_of_bf16(m));
-                    const size_t o = (((size_t)nt * KS + ks) * 64 + lane) * 8 + j;
-                    out[o] = h; out[term + o] = m; out[2 * term + o] = l;
+                    const int n = bf3_n(nt, lane), k = bf3_k0(ks, lane) + j;
+                    const size_t o = bf3_pos(nt, ks, lane, KS) + j;
+                    bf3_split(n < cout && k < cin ? w[(size_t)n * cin + k] : 0.f, out[o], out[term + o], out[2 * term + o]);
+                }
+    return IQ_OK;
+}
+
+// The same image from the layer's float32 image (iq_pack_weight order) instead of the plain weight: for a layer whose bf16x3
+// image the caller does not hold (PointNet's fstn.fc3: iq_pointnet_coalitions).  Rows beyond cout are zero in both images.
+int iq::launch_split_bf3(const float* packed_w, unsigned short* out_bf3, int cout, int cin, hipStream_t st) {
+    IQ_REQUIRE(packed_w && out_bf3 && cout >= 1 && cin >= 8 && cin % 8 == 0, "iq_split_packed_weight_bf3: cout=%d cin=%d", cout, cin);
+    const int KS = ((cin + 31) & ~31) / 16, ntiles = iq_padded_cout(cout) / 32;
+    const size_t threads = (size_t)ntiles * KS * 64;
+    hipLaunchKernelGGL(split_packed_bf3_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, packed_w, out_bf3, ntiles, KS, cin);
+    return iq::check_launch("split_packed_bf3_kernel");
+}
+
+extern "C" int iq_split_packed_weight_bf3(const float* packed_w, unsigned short* out_bf3, int cout, int cin, iq_stream_t stream) {
+    return iq::launch_split_bf3(packed_w, out_bf3, cout, cin, iq::as_stream(stream));
+}
+
+// the host twin: the same two maps and the same split in a loop, so that they can be checked without a device
+extern "C" int iq_split_packed_weight_bf3_host(const float* packed_w, unsigned short* out_bf3, int cout, int cin) {
+    IQ_REQUIRE(packed_w && out_bf3 && cout >= 1 && cin >= 8 && cin % 8 == 0, "iq_split_packed_weight_bf3_host: cout=%d cin=%d", cout, cin);
+    const int KS = ((cin + 31) & ~31) / 16, ntiles = iq_padded_cout(cout) / 32;
+    const size_t term = (size_t)ntiles * KS * 512;
+    for (int nt = 0; nt < ntiles; ++nt)
+        for (int ks = 0; ks < KS; ++ks)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int n = bf3_n(nt, lane), k = bf3_k0(ks, lane) + j;
+                    const size_t o = bf3_pos(nt, ks, lane, KS) + j;
+                    bf3_split(k < cin ? packed_w[packed_pos(n, k, cin)] : 0.f, out_bf3[o], out_bf3[term + o], out_bf3[2 * term + o]);
                 }
     return IQ_OK;
 }

@@ -115,8 +115,12 @@ namespace iq {
 // known on the device (ragged batches); M is then the upper bound the grid is sized for.
 // tile_nu / rows_per_cloud (optional): rows are rows_per_cloud consecutive rows per cloud, of which only the first
 // tile_nu[cloud] are wanted - 128-row tiles that lie entirely beyond are skipped (their outputs are left untouched).
+// fit_tiles: a bf16x3 layer may take 64- / 32-row workgroup tiles where 128-row ones would leave the chip part empty (launch_bf3 in
+// iq_linear.hip; bit-identical results).  Asked for by PointNet's heads and by iq_linear, where it is measured; the other families'
+// launches keep the 128-row tiling their steps were measured with.
 int launch_linear(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu,
-                  hipStream_t st, const int32_t* m_dev = nullptr, const int32_t* tile_nu = nullptr, int rows_per_cloud = 0);
+                  hipStream_t st, const int32_t* m_dev = nullptr, const int32_t* tile_nu = nullptr, int rows_per_cloud = 0,
+                  bool fit_tiles = false);
 // Same layer for few rows and a very long K: K is split over workgroups in slices of 512 (independent of M), partial
 // sums pass through `scratch` (cin/512 x M x cout floats) and are added in a fixed order.
 int launch_linear_splitk(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, float* scratch,
@@ -128,6 +132,9 @@ int launch_linear_splitk(const float* A, int lda, const iq_dense_layer& L, float
 // matrix pipe, float32-exact (pn_gemm_bf3_kernel<pool>).
 int launch_linear_pool(const float* A, int lda, const iq_dense_layer& L, float* partial, int M, int relu,
                        const float* row_w, hipStream_t st, const int32_t* m_dev = nullptr, const void* w_bf3 = nullptr);
+// The bf16x3 image (iq_pack_weight_bf3 order, iq_packed_bf3_elems(cout, cin) elements) of a layer from its float32 image in
+// iq_pack_weight order, on the device (iq_linear.hip: split_packed_bf3_kernel).
+int launch_split_bf3(const float* packed_w, unsigned short* out_bf3, int cout, int cin, hipStream_t st);
 // Farthest point sampling (iq_geom.hip); n_unique may be null.
 int launch_fps(const float* xyz, int32_t* idx, int32_t* n_unique, int B, int N, int S, hipStream_t st);
 }  // namespace iq

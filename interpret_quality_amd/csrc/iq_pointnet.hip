@@ -1351,7 +1351,7 @@ void launch_chain(const ChainArgs& a, hipStream_t st) {
 }  // namespace
 
 namespace {
-using iq::launch_linear;
+using iq::launch_linear;   // (the heads pass fit_tiles = true: tile heights that fill the chip, iq_mfma.h)
 
 struct Workspace {
     uint16_t* sorted_pts;
@@ -1369,6 +1369,7 @@ struct Workspace {
     float* h2;
     float* trans;
     float* tfp;
+    uint16_t* fc3_bf3;   // fstn.fc3's weights as three bf16 terms, derived per call from the float32 image (pointnet_coalitions)
     size_t bytes;
 };
 
@@ -1396,6 +1397,7 @@ Workspace carve(void* base, int B, int nclouds, int N, int R, int roff_entries =
     w.h2 = reinterpret_cast<float*>(take((size_t)B * 256 * sizeof(float)));
     w.trans = reinterpret_cast<float*>(take((size_t)B * 9 * sizeof(float)));
     w.tfp = reinterpret_cast<float*>(take((size_t)B * 4096 * sizeof(float)));
+    w.fc3_bf3 = reinterpret_cast<uint16_t*>(take(iq_packed_bf3_elems(4096, 256) * sizeof(uint16_t)));
     w.bytes = off;
     return w;
 }
@@ -1531,9 +1533,9 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
                            R, nclouds, with_centre);
     if ((rc = iq::check_launch(orders ? "pn_stn_prefix_kernel" : wide_words ? "pn_stn_gather_wide_kernel" : "pn_stn_gather_kernel")))
         return rc;
-    if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st))) return rc;
-    if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st))) return rc;
-    if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st))) return rc;
+    if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st, nullptr, nullptr, 0, true))) return rc;
 
     // 2. feature-STN chain over each coalition's distinct points
     a.cloud_of = item_cloud; a.trans = ws.trans;
@@ -1553,9 +1555,19 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
             launch_chain<kFstn>(a, st);
         }
         if ((rc = iq::check_launch("pn_chain_kernel<fstn>"))) return rc;
-        if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st))) return rc;
-        if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st))) return rc;
-        if ((rc = launch_linear(ws.h2, 256, w->fstn_fc3, tfp, 4096, B, 0, st))) return rc;
+        if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+        if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+        // fstn.fc3 (256 -> 4096, 70 % of the heads' FLOP) on the bf16 matrix pipe like the other wide layers.  The descriptor brings
+        // no bf16x3 image of it (its rows are permuted by iq_pack_fstn_fc3; the packed weight set is what it has always been), so the
+        // image is split off the float32 one here, per call: 1 M weights, a few microseconds, and nothing to go stale when a
+        // caller reuses a pointer for other weights.  Twin kTwinDenseFp32: no split, the fp32-MFMA kernel.
+        iq_dense_layer fc3 = w->fstn_fc3;
+        IQ_REQUIRE(fc3.cin == 256 && fc3.cout == 4096, "%s: fstn_fc3 is %d -> %d, not 256 -> 4096", who, fc3.cin, fc3.cout);
+        if (!fc3.w_bf3 && iq::twin() != iq::kTwinDenseFp32) {
+            if ((rc = iq::launch_split_bf3(fc3.w, ws.fc3_bf3, 4096, 256, st))) return rc;
+            fc3.w_bf3 = ws.fc3_bf3;
+        }
+        if ((rc = launch_linear(ws.h2, 256, fc3, tfp, 4096, B, 0, st, nullptr, nullptr, 0, true))) return rc;
     } else {
         // feature_transform = False (models/pointnet.py:62-63,72-78): no feature STN.  The trunk multiplies by the packed
         // IDENTITY instead (fstn_fc3.b = iq_pack_fstn_fc3 of a zero layer): sum_k f[k] I[k][n] = f[n] + zeros, exact.
@@ -1576,9 +1588,9 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         launch_chain<kTrunk>(a, st);
     }
     if ((rc = iq::check_launch("pn_chain_kernel<trunk>"))) return rc;
-    if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st))) return rc;
-    if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st))) return rc;
-    if ((rc = launch_linear(ws.h2, 256, w->cls_fc3, logits, w->cls_fc3.cout, B, 0, st))) return rc;
+    if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h2, 256, w->cls_fc3, logits, w->cls_fc3.cout, B, 0, st, nullptr, nullptr, 0, true))) return rc;
     return IQ_OK;
 }
 
