@@ -61,8 +61,9 @@ enum {
  * 108: new entry points, no layout change (the other families' compact coalition paths for wide keep rows:
  * iq_dgcnn_coalitions_wide, iq_pointnet2_coalitions_wide, iq_pointconv_coalitions_wide, iq_pointconv_coalitions_cached_wide).
  * 109: new entry points, no layout change (iq_split_packed_weight_bf3, iq_split_packed_weight_bf3_host); the PointNet workspaces
- * grew by the bf16x3 image of fstn.fc3 (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes). */
-#define IQ_ABI_VERSION 109
+ * grew by the bf16x3 image of fstn.fc3 (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes).
+ * 110: one new entry point, no layout change (iq_smoothness_enum_wide: the smoothness enumeration of a wide game). */
+#define IQ_ABI_VERSION 110
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -191,6 +192,13 @@ typedef struct iq_smoothness_params {
 int iq_smoothness_enum(const float* cloud /*N,3*/, const float* origin /*N,3 or NULL*/, const int32_t* region_id /*N*/, int N, int R, int mode,
                        int objective, const iq_smoothness_params* prm, float* data_out, float* smooth_out,
                        float* var_out, float* orig_out, int32_t* stop_epoch, iq_stream_t stream);
+/* The same enumeration for a wide game ("Wide coalitions" below): the same arguments and outputs, 1 <= R <= IQ_MAX_WIDE_REGIONS.
+ * Both entry points take 1 <= N <= 1024 - a region's points live in the kernel's LDS arrays - and launch the same kernel, one
+ * wave per region; a region's trajectory reads only that region's points, so for R <= 64 the five outputs are
+ * iq_smoothness_enum's bit for bit.  Above a few hundred regions many regions hold fewer than two points: stop_epoch -1, NaN. */
+int iq_smoothness_enum_wide(const float* cloud /*N,3*/, const float* origin /*N,3 or NULL*/, const int32_t* region_id /*N*/, int N, int R,
+                            int mode, int objective, const iq_smoothness_params* prm, float* data_out, float* smooth_out,
+                            float* var_out, float* orig_out, int32_t* stop_epoch, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PointNet (models/pointnet.py:11-115) - fused fp32-MFMA forward over coalitions
@@ -577,8 +585,9 @@ int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
  * one wide entry point only, iq_context_keep_masks_wide: iq_reward and iq_interaction_reduce never see a mask.
  * Every family's coalition entry has a wide form (the compact paths of PointNet++ / DGCNN / GCNN / PointConv: the few small kernels
  * that turn a mask into a coalition's kept points, csrc/iq_common.h WaveKeep; everything behind them works on points); those
- * families can also evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.  The smoothness and pose stages
- * have no wide form.
+ * families can also evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.  The pose sweeps of a wide
+ * game need no entry point of their own - every pose of a cloud goes through the coalition entries below - and its smoothness
+ * stage needs one, iq_smoothness_enum_wide (declared beside iq_smoothness_enum above: the same kernel, N <= 1024).
  * ------------------------------------------------------------------------------------------- */
 
 /* tools/final_common.py:56-60 as wide masks: row s*(R+1) + i of keep keeps orders[s][0..i-1]; an entry outside [0, R) is ignored. */

@@ -315,18 +315,33 @@ __global__ __launch_bounds__(kWave) void smooth_enum_kernel(
 
 }  // namespace
 
-extern "C" int iq_smoothness_enum(const float* cloud, const float* origin, const int32_t* region_id, int N, int R, int mode, int objective,
-                                  const iq_smoothness_params* prm, float* data_out, float* smooth_out, float* var_out,
-                                  float* orig_out, int32_t* stop_epoch, iq_stream_t stream) {
-    IQ_REQUIRE(cloud && region_id && prm && data_out && smooth_out && var_out && orig_out && stop_epoch,
-               "iq_smoothness_enum: null pointer");
-    IQ_REQUIRE(N >= 1 && N <= kMaxRegionPoints, "iq_smoothness_enum: N=%d not in [1,%d]", N, kMaxRegionPoints);
-    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_REGIONS, "iq_smoothness_enum: R=%d not in [1,%d]", R, IQ_MAX_REGIONS);
-    IQ_REQUIRE(mode >= 0 && mode <= 2, "iq_smoothness_enum: mode %d (0 linearity, 1 planarity, 2 scattering)", mode);
-    IQ_REQUIRE(objective == 1 || objective == -1, "iq_smoothness_enum: objective %d (+1 inc, -1 dec)", objective);
-    IQ_REQUIRE(prm->epochs >= 1 && prm->epochs <= 4096 && prm->max_iteration >= 0,
-               "iq_smoothness_enum: epochs=%d max_iteration=%d", prm->epochs, prm->max_iteration);
+// Both entry points launch the one kernel above, one wave per region (grid = R); they differ in the region count they admit.
+// N keeps one limit: a region's points live in the kernel's LDS arrays.
+static int launch_smooth_enum(const char* name, int max_regions, const float* cloud, const float* origin, const int32_t* region_id,
+                              int N, int R, int mode, int objective, const iq_smoothness_params* prm, float* data_out,
+                              float* smooth_out, float* var_out, float* orig_out, int32_t* stop_epoch, iq_stream_t stream) {
+    IQ_REQUIRE(cloud && region_id && prm && data_out && smooth_out && var_out && orig_out && stop_epoch, "%s: null pointer", name);
+    IQ_REQUIRE(N >= 1 && N <= kMaxRegionPoints, "%s: N=%d not in [1,%d]", name, N, kMaxRegionPoints);
+    IQ_REQUIRE(R >= 1 && R <= max_regions, "%s: R=%d not in [1,%d]", name, R, max_regions);
+    IQ_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d (0 linearity, 1 planarity, 2 scattering)", name, mode);
+    IQ_REQUIRE(objective == 1 || objective == -1, "%s: objective %d (+1 inc, -1 dec)", name, objective);
+    IQ_REQUIRE(prm->epochs >= 1 && prm->epochs <= 4096 && prm->max_iteration >= 0, "%s: epochs=%d max_iteration=%d", name,
+               prm->epochs, prm->max_iteration);
     hipLaunchKernelGGL(smooth_enum_kernel, dim3(R), dim3(kWave), 0, iq::as_stream(stream), cloud,
                        origin ? origin : cloud, region_id, N, R, mode, objective, *prm, data_out, smooth_out, var_out, orig_out, stop_epoch);
     return iq::check_launch("smooth_enum_kernel");
+}
+
+extern "C" int iq_smoothness_enum(const float* cloud, const float* origin, const int32_t* region_id, int N, int R, int mode, int objective,
+                                  const iq_smoothness_params* prm, float* data_out, float* smooth_out, float* var_out,
+                                  float* orig_out, int32_t* stop_epoch, iq_stream_t stream) {
+    return launch_smooth_enum("iq_smoothness_enum", IQ_MAX_REGIONS, cloud, origin, region_id, N, R, mode, objective, prm, data_out,
+                              smooth_out, var_out, orig_out, stop_epoch, stream);
+}
+
+extern "C" int iq_smoothness_enum_wide(const float* cloud, const float* origin, const int32_t* region_id, int N, int R, int mode,
+                                       int objective, const iq_smoothness_params* prm, float* data_out, float* smooth_out,
+                                       float* var_out, float* orig_out, int32_t* stop_epoch, iq_stream_t stream) {
+    return launch_smooth_enum("iq_smoothness_enum_wide", IQ_MAX_WIDE_REGIONS, cloud, origin, region_id, N, R, mode, objective, prm,
+                              data_out, smooth_out, var_out, orig_out, stop_epoch, stream);
 }

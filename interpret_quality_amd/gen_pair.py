@@ -119,6 +119,17 @@ def _dense_logits(model, clouds_cf, args):
     return out[0] if args.model == "pointnet" else out
 
 
+def lowest_reward_pose(model, data, lbl, params, disturb_fn, args):
+    """The rule of check_adv_success (final_gen_pair.py:245-276) for one cloud: one dense forward over the poses ``params`` (P,3) of
+    ``data`` (1,N,3); -> the index of the pose with the lowest reward on the true class.  Shared with the wide interaction stage."""
+    poses = torch.cat([disturb_fn(data, torch.from_numpy(params[i]).to(args.device)) for i in range(params.shape[0])], dim=0)
+    logits = _dense_logits(model, poses.permute(0, 2, 1).contiguous(), args)
+    pred = torch.argmax(logits, dim=1)
+    print("%d poses are misclassified" % int((pred != lbl[0].item()).sum()))
+    v = final_common.get_reward(logits, lbl, args)
+    return torch.argmin(v).item()
+
+
 def check_adv_success(args, disturb_fn, folder_name_list):
     """final_gen_pair.py:221-286: one dense forward over all poses of each cloud; saves the pose with the
     lowest reward on the true class (max attacking utility)."""
@@ -130,12 +141,7 @@ def check_adv_success(args, disturb_fn, folder_name_list):
             base_folder = args.exp_folder + "%s/" % name
             mode_folder = base_folder + "%s_all/" % args.mode
             params = np.load(mode_folder + ("trans_vector.npy" if args.mode == "trans" else "angle_tuple.npy"))
-            poses = torch.cat([disturb_fn(data, torch.from_numpy(params[i]).to(args.device)) for i in range(params.shape[0])], dim=0)
-            logits = _dense_logits(model, poses.permute(0, 2, 1).contiguous(), args)
-            pred = torch.argmax(logits, dim=1)
-            print("%d poses are misclassified" % int((pred != lbl[0].item()).sum()))
-            v = final_common.get_reward(logits, lbl, args)
-            pose_idx = torch.argmin(v).item()
+            pose_idx = lowest_reward_pose(model, data, lbl, params, disturb_fn, args)
             folder = _interaction_folder(args, name) + "%s_adv/" % args.mode
             np.save(folder + "pose_idx.npy", pose_idx)
             np.save(folder + "transform_params.npy", params[pose_idx])

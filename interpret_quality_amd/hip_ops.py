@@ -576,7 +576,8 @@ SMOOTHNESS_MODES = ("linearity", "planarity", "scattering")
 
 
 def smoothness_enum(cloud, region_id, num_regions, mode, objective, step=1e-3, enum_step=0.05, var_threshold=0.003,
-                    dist_threshold=0.03, stop_ratio=0.5, epochs=50, max_iteration=100, origin=None, project_to_bound=False):
+                    dist_threshold=0.03, stop_ratio=0.5, epochs=50, max_iteration=100, origin=None, project_to_bound=False,
+                    entry="iq_smoothness_enum"):
     """final_smoothness_center_enum_all.py:183-242,303-335 for all regions and epochs in one launch.
     cloud (N,3) f32, region_id (N,) i32 -> dict(data (E,N,3) f32, smoothness (E,R) f32, var (E,R,3) f32,
     orig (R,4) f32, stop_epoch (R,) i32); see include/iq.h.  ``origin`` (N,3): restart from a deformed ``cloud``."""
@@ -592,11 +593,24 @@ def smoothness_enum(cloud, region_id, num_regions, mode, objective, step=1e-3, e
     if mode not in SMOOTHNESS_MODES or objective not in ("inc", "dec"):
         raise _lib.IqError("smoothness_enum: mode %r / objective %r" % (mode, objective))
     org = _dev(origin, torch.float32, "origin") if origin is not None else ctypes.c_void_p(0)
-    _lib.check(lib.iq_smoothness_enum(_dev(cloud, torch.float32, "cloud"), org, _dev(region_id, torch.int32, "region_id"), n, r,
-                                      SMOOTHNESS_MODES.index(mode), 1 if objective == "inc" else -1, ctypes.byref(prm),
-                                      _p(out["data"]), _p(out["smoothness"]), _p(out["var"]), _p(out["orig"]),
-                                      _p(out["stop_epoch"]), _stream()), "iq_smoothness_enum")
+    _lib.check(getattr(lib, entry)(_dev(cloud, torch.float32, "cloud"), org, _dev(region_id, torch.int32, "region_id"), n, r,
+                                   SMOOTHNESS_MODES.index(mode), 1 if objective == "inc" else -1, ctypes.byref(prm),
+                                   _p(out["data"]), _p(out["smoothness"]), _p(out["var"]), _p(out["orig"]),
+                                   _p(out["stop_epoch"]), _stream()), entry)
     return out
+
+
+MAX_SMOOTHNESS_POINTS = 1024    # iq_smoothness_enum, iq_smoothness_enum_wide: a region's points live in the kernel's LDS arrays
+
+
+def smoothness_enum_wide(cloud, region_id, num_regions, mode, objective, **kw):
+    """``smoothness_enum`` for a wide game, 1 <= num_regions <= MAX_WIDE_REGIONS (iq_smoothness_enum_wide: the same kernel, one
+    wave per region; for num_regions <= 64 the same bits).  The cloud keeps the narrow limit of MAX_SMOOTHNESS_POINTS points.
+    A region without points leaves no trace in ``data``: every point of the cloud belongs to a region that writes it."""
+    wide_words(num_regions)
+    if not 1 <= cloud.shape[0] <= MAX_SMOOTHNESS_POINTS:
+        raise _lib.IqError("smoothness_enum_wide: N=%d points, the enumeration takes 1 .. %d" % (cloud.shape[0], MAX_SMOOTHNESS_POINTS))
+    return smoothness_enum(cloud, region_id, num_regions, mode, objective, entry="iq_smoothness_enum_wide", **kw)
 
 
 class PackedLinear:

@@ -40,14 +40,17 @@ STOP_RATIO = 0.5
 MAX_ITERATION = 100
 
 
-def enumerate_smoothness(data, region_id, args, objective):
+def enumerate_smoothness(data, region_id, args, objective, wide=False):
     """The epoch loop of test_all_region (:303-335) without its Shapley calls.  data (1,N,3) GPU tensor ->
-    (poses (P,N,3) f32 GPU tensor, smoothness (P,R) f64 ndarray, raw kernel outputs)."""
+    (poses (P,N,3) f32 GPU tensor, smoothness (P,R) f64 ndarray, raw kernel outputs).  ``wide``: the enumerator of a wide game
+    (hip_ops.smoothness_enum_wide: up to hip_ops.MAX_WIDE_REGIONS regions, the same kernel); the region ids stay the original
+    cloud's either way.  When no region can move (every region holds fewer than two points) the result is one pose, the input."""
     dev = data.device
-    res = hip_ops.smoothness_enum(data[0].contiguous(), hip_ops.region_ids(region_id, dev, args.num_regions), args.num_regions, args.mode, objective,
-                                  step=args.step, enum_step=args.enum_step, var_threshold=args.var_threshold,
-                                  dist_threshold=args.dist_threshold, stop_ratio=args.stop_ratio, epochs=args.epoch,
-                                  max_iteration=args.max_iteration)
+    enum = hip_ops.smoothness_enum_wide if wide else hip_ops.smoothness_enum
+    res = enum(data[0].contiguous(), hip_ops.region_ids(region_id, dev, args.num_regions), args.num_regions, args.mode, objective,
+               step=args.step, enum_step=args.enum_step, var_threshold=args.var_threshold,
+               dist_threshold=args.dist_threshold, stop_ratio=args.stop_ratio, epochs=args.epoch,
+               max_iteration=args.max_iteration)
     stop = res["stop_epoch"].cpu().numpy()                       # the one sync of the enumeration
     n_epochs = max(1, min(int(args.epoch), int(stop.max()) + 1))  # break once every indicator is False (:333-334)
     res["stop_epoch_host"] = stop

@@ -14,7 +14,9 @@ at dense-forward speed; "compact" takes the family's compact coalition path thro
 a coalition's distinct rows only, per-source-cloud tables), whose logits agree with the dense forward's to rounding, bitwise only
 where the summation order is the same.  For PointNet both names mean its fused path.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
 and the multi-order interactions of sampled (pair, context) coalitions (``gen_context``, ``interaction_logits``, ``interactions``,
-wide_interaction_stage.py).  The smoothness and pose stages have none.
+wide_interaction_stage.py), and so do the stages that move the cloud: the pose sweeps (``shapley_over_poses``, ``sharded_shapley``,
+wide_pose_stage.py) and the smoothness enumeration (smoothness.enumerate_smoothness with ``wide=True``, wide_smoothness_stage.py;
+clouds of at most 1024 points).  Not wide: the single-region folders of final_gen_pair.py.
 """
 import numpy as np
 import torch
@@ -148,6 +150,71 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
                 logits = _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(step_orders), r, mode)
             v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
     return hip_ops.shapley_snapshots(v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
+
+
+def shapley_over_poses(model, poses, lbl, region_id, orders, args, route=None, coalitions=None):
+    """Region Shapley values of several perturbed copies ``poses`` (P,N,3) of one cloud under the permutations ``orders`` ((S,R)
+    ndarray): -> phi (P,R) float64 device tensor, the wide twin of pose_sweep.shapley_over_poses without its logits.  phi[p] is
+    ``total / S`` of ``shapley(model, poses[p:p+1], lbl, region_id, orders, args, route=route, coalitions=coalitions)``, bit for bit:
+    the same kernels on the same rows (``_prefix_logits`` / ``_logits``, ``get_reward``, ``shapley_accum_wide``).  What does not
+    depend on the pose is done once per call: the checks, the permutations and region ids on the device and, on the keep route,
+    the keep rows.  The centre of a pose is torch.mean of that one (1,N,3) cloud, never of a batch of poses
+    (pose_sweep.shapley_over_poses records what a batched mean did to sharding).  Every route goes pose by pose: poses do not share
+    launches (DESIGN.md 5e has the rule and why).
+    ``route`` and ``coalitions`` as in ``shapley``."""
+    route = _pick_route(model, route)
+    mode = _pick_coalitions(coalitions, poses)
+    dev = poses.device
+    r = int(args.num_regions)
+    hip_ops.wide_words(r)
+    orders = np.asarray(orders)
+    if orders.ndim != 2 or orders.shape[1] != r:
+        raise IqError("orders must be (S, %d), got %s" % (r, orders.shape))
+    if poses.dim() != 3 or poses.shape[2] != 3:
+        raise IqError("poses must be (P, N, 3), got %s" % (tuple(poses.shape),))
+    hip_ops.check_host_indices(orders, 0, r, "orders")
+    s, p = orders.shape[0], poses.shape[0]
+    phi = torch.zeros((p, r), dtype=torch.float64, device=dev)
+    if p == 0:          # an empty shard still agrees with the others on the trailing shape of the gather
+        return phi
+    if s == 0:
+        raise IqError("orders holds no permutation")
+    per = s * (r + 1)
+    orders_dev = hip_ops.as_i32(orders, dev)
+    rid = hip_ops.region_ids(region_id, dev, r)
+    poses = poses.contiguous()
+    with torch.no_grad():
+        step = max(1, (1 << 17) // (r + 1))           # ``shapley``'s launches
+        steps = [(lo, min(lo + step, s)) for lo in range(0, s, step)]
+        step_orders = [orders_dev[lo:hi].contiguous() for lo, hi in steps]
+        keep = [hip_ops.prefix_keep_masks_wide(o) for o in step_orders] if route == "keep" else None
+        v = torch.empty((p * per,), dtype=torch.float32, device=dev)
+        for k in range(p):
+            for j, (lo, hi) in enumerate(steps):
+                if route == "prefix":
+                    logits = _prefix_logits(model, poses[k:k + 1], rid, step_orders[j], r, mode)
+                else:
+                    logits = _logits(model, poses[k:k + 1], rid, keep[j], r, mode)
+                v[k * per + lo * (r + 1):k * per + hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
+        for k in range(p):
+            total, _, _ = hip_ops.shapley_accum_wide(v[k * per:(k + 1) * per], orders_dev)
+            # a true float64 division, as ``total / S`` on the host: a tensor divided by a Python number is multiplied by its
+            # reciprocal on the device, one rounding more (the values differ in the last bit for S = 3)
+            phi[k] = torch.div(total, torch.full_like(total, float(s)))
+    return phi
+
+
+def sharded_shapley(model, data, poses, lbl, region_id, orders, args, route=None, coalitions=None):
+    """The wide twin of pose_sweep.sharded_shapley: region Shapley values of the original cloud ``data`` (1,N,3) and of its
+    perturbed copies ``poses`` (P,N,3), the P + 1 clouds sharded over the ranks (the original travels as pose 0) and gathered
+    once -> (orig (R,) float64 ndarray, phi (P,R) float64 tensor), the same on every rank whatever the rank count.  One
+    all_gather_rows of phi per call; no logits, no other collective."""
+    allp = torch.cat([data.reshape(1, -1, 3), poses.reshape(-1, data.shape[1], 3)], dim=0)
+    n = allp.shape[0]
+    lo, hi = iqdist.shard_range(n)
+    phi = shapley_over_poses(model, allp[lo:hi].contiguous(), lbl, region_id, orders, args, route=route, coalitions=coalitions)
+    phi = iqdist.all_gather_rows(phi, n)
+    return phi[0].cpu().numpy(), phi[1:]
 
 
 # ---- multi-order interactions: final_gen_pair.py, final_point_binary_interaction_logits.py and final_cal_interactions.py ---------

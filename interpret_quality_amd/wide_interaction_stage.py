@@ -11,14 +11,18 @@ final_wide_shapley.py wrote for ``--num_regions`` and writes, under the referenc
 
 and, with ``--transform_params FILE.npy`` (the angle tuple or translation vector of ``--mode``), the same pairs and contexts on the
 perturbed cloud into ``interaction_seed<k>/<mode>_adv/`` (with transform_params.npy and pred_labels.npy, as final_gen_pair.py
-leaves them there) - how the normal pose is compared with an adversarial one until the pose sweeps have a wide form.
+leaves them there).  ``--adv_pose sweep`` finds that pose itself: for each selected cloud it reads the parameter file that
+final_wide_pose.py --mode <mode> wrote (``<mode>_all/trans_vector.npy`` | ``angle_tuple.npy``), picks the pose with the lowest reward
+on the true class by one dense forward over all poses (gen_pair.lowest_reward_pose: check_adv_success's rule and code), writes
+``pose_idx.npy`` and ``transform_params.npy`` into ``<mode>_adv/`` and evaluates that pose exactly as ``--transform_params`` with that
+row would.  The two flags exclude each other.
 
 Deviations from the reference, both for size: the context lists are saved in the narrowest integer type that holds R (int16; at
 R = 1024 the reference's int64 would be 1.4 GB per cloud - nothing but this driver reads these files), and pairs and contexts are
 saved for the selected clouds only.  The random stream is final_gen_pair.py's for ``--seed <k>``: NumPy's global generator, seeded
 with ``--gen_pair_seed``, draws the pairs of ALL clouds first and then the contexts of all clouds, selected or not.  Not here
-(DESIGN.md 5e): check_adv_success and the single-region folders (they need the wide pose sweeps), sharding over ranks - under
-several ranks rank 0 does the work and the others wait.
+(DESIGN.md 5e): the single-region folders of final_gen_pair.py (at R = 128 there are 128 of them, each with its own contexts) and
+sharding over ranks - under several ranks rank 0 does the work and the others wait.
 """
 import os
 
@@ -59,6 +63,11 @@ def draw(args, names, wanted):
                 np.save(folder + "ratio%d_context_list.npy" % int(ratio * 100), context_list)
 
 
+def _sweep_params_path(args, base_folder):
+    """The parameter file of the cloud's wide pose sweep of ``args.mode`` (wide_pose_stage.py)."""
+    return base_folder + "%s_all/" % args.mode + ("trans_vector.npy" if args.mode == "trans" else "angle_tuple.npy")
+
+
 def evaluate(model, data, lbl, region_id, folder, save_path, args):
     """save_logits_all_orders + cal_interaction_all_orders (final_point_binary_interaction_logits.py:73-80,
     final_cal_interactions.py:40-46) for one pose of one cloud."""
@@ -83,6 +92,9 @@ def run(args):
         path = args.exp_folder + "%s/region_id.npy" % names[i]
         if not os.path.exists(path):
             raise SystemExit("%s not found: run final_wide_shapley.py --num_regions %d first" % (path, args.num_regions))
+        path = _sweep_params_path(args, args.exp_folder + "%s/" % names[i])
+        if getattr(args, "adv_pose", None) == "sweep" and not os.path.exists(path):
+            raise SystemExit("%s not found: run final_wide_pose.py --mode %s --num_regions %d first" % (path, args.mode, args.num_regions))
     model = load_model(args)
     disturb_fn = translate_pc if args.mode == "trans" else rotate_xyz
     params = np.load(args.transform_params) if args.transform_params else None
@@ -93,10 +105,17 @@ def run(args):
             region_id = np.load(base_folder + "region_id.npy")
             print("##### normal pose")
             evaluate(model, data, lbl, region_id, folder, folder + "normal/", args)
+            adv = folder + "%s_adv/" % args.mode
+            if getattr(args, "adv_pose", None) == "sweep":
+                sweep = np.load(_sweep_params_path(args, base_folder))
+                pose_idx = gen_pair.lowest_reward_pose(model, data, lbl, sweep, disturb_fn, args)
+                print("Pose idx with max attacking utility: %d" % pose_idx)
+                mkdir(adv)
+                np.save(adv + "pose_idx.npy", pose_idx)
+                params = sweep[pose_idx]
             if params is None:
                 continue
-            print("##### %s pose of --transform_params" % args.mode)
-            adv = folder + "%s_adv/" % args.mode
+            print("##### %s pose of %s" % (args.mode, "the sweep" if getattr(args, "adv_pose", None) else "--transform_params"))
             mkdir(adv)
             np.save(adv + "transform_params.npy", params)
             gen_pair.gen_pred_label(model, data, lbl, disturb_fn, adv, args)
@@ -110,12 +129,17 @@ def make_args(argv=None):
     parser.set_defaults(device_id=0)
     parser.add_argument("--transform_params", type=str, default=None, metavar="FILE.npy",
                         help="the --mode parameters of one pose: the same pairs and contexts are also evaluated there")
+    parser.add_argument("--adv_pose", choices=("sweep",), default=None,
+                        help="sweep: take the adversarial pose from the wide pose sweep of --mode (the pose with the lowest reward "
+                             "on the true class) instead of --transform_params")
     parser.add_argument("--coalitions", choices=wide.COALITIONS, default=None,
                         help="how a family other than PointNet evaluates the coalitions: dense = its dense forward on materialised "
                              "clouds (the default), compact = its compact coalition path; the same artefacts, equal to rounding")
     args = parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
                            "the wide stage takes %d .. %d regions (final_gen_pair.py and final_point_binary_interaction_logits.py: "
                            "up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS), samples=False)
+    if args.adv_pose and args.transform_params:
+        parser.error("--adv_pose sweep finds the pose itself: it cannot be combined with --transform_params")
     if args.mode not in ("rotate", "trans"):
         parser.error("--mode %s: rotate or trans" % args.mode)
     if args.num_save_context_max < 1 or args.num_pairs_random < 1:

@@ -10,8 +10,9 @@ The permutations come from NumPy's global generator on the host, exactly as the 
 (final_shapley_value.py:59-72); the device sampler of stage 1 stays a 64-region kernel.  The FPS centres go to their own
 fps_<dataset>_<N>_<R>_index_final30.npy.  ``--route prefix|keep`` picks how ``wide.shapley`` evaluates the prefix coalitions (the
 same bits either way), ``--coalitions dense|compact`` how a family other than PointNet evaluates them (wide.py).  Single process: under several ranks rank 0 does the work and the others wait.  The
-multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py).  The smoothness and pose
-stages have no wide form.
+multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py); the pose sweeps and the
+smoothness stage on these region ids and permutations: final_wide_pose.py (wide_pose_stage.py) and final_wide_smoothness.py
+(wide_smoothness_stage.py), sharded over the ranks.
 """
 import numpy as np
 import torch

@@ -6,6 +6,7 @@
     python tools/bench_wide.py --prefix                 # wide.shapley, keep route against prefix route, into the "prefix" key of --out
     python tools/bench_wide.py --interaction            # the interaction stage only, into the "interaction" key of --out
     python tools/bench_wide.py --compact                # the other families, dense against compact, into the "compact" key of --out
+    python tools/bench_wide.py --poses                  # a pose sweep, one wide.shapley per pose against wide.shapley_over_poses, into "poses"
 
 1. Wide against narrow at R = 32 (the headline's workload: 1000 permutations, 33 000 coalitions) and R = 64: the SAME coalitions
    through iq_pointnet_coalitions (the yardstick: untouched code) and iq_pointnet_coalitions_wide, alternated in one process,
@@ -33,6 +34,14 @@
    both, five runs each, with as many whole permutations as make a dense run about a second.  Reported per family and R: seconds
    and coalitions/s of every run, median and spread of each route, the ratio of the medians, ``compact_faster_beyond_spread`` and
    the norm-wise difference of the Shapley rows.  Into the "compact" key of --out.  No threshold hangs on these numbers.
+
+6. ``--poses``: PointNet, N = 1024, R = 128 and R = 1024, S = 100 permutations, P = 32 rotations of one synthetic cloud (6.6 k to
+   102 k coalitions a pose: the shape of final_wide_pose.py).  Arm (a), the yardstick: P separate calls of wide.shapley - the
+   parent's code path, not the code under test.  Arm (b): wide.shapley_over_poses.
+   Alternated in one process after a warm-up of both, five runs each.  Reported per R: seconds and coalitions/s of every run,
+   median and spread of each arm, whether the values are the same bits, and ``batched_slower_beyond_spread`` /
+   ``batched_faster`` - batching poses across launches stays only if it is slower beyond the larger spread at neither region
+   count and faster at one of them (``batching_stays_by_the_rule``).  Into the "poses" key of --out.
 
 Times are host clocks around work that ends in a device synchronise.  Kernel shares come from a separate run under the profiler
 (--profile-step): tracing slows the host, so no rate is taken there."""
@@ -164,6 +173,35 @@ def prefix_vs_keep(model, r, repeats, dev, min_seconds=1.0):
     return out
 
 
+def poses_batched_vs_looped(model, r, dev, perms=100, n_poses=32, repeats=5):
+    """A pose sweep, one wide.shapley call per pose against wide.shapley_over_poses, alternated; see the module docstring, 6."""
+    from interpret_quality_amd import pose_sweep, wide
+    data, _, rid = _setup(r, dev)
+    rid_np = rid[0].cpu().numpy().astype(np.int64)
+    lbl = torch.zeros((1,), dtype=torch.int64, device=dev)
+    args = argparse.Namespace(model="pointnet", softmax_type="modified", num_points=1024, num_regions=r, verbose=False,
+                              angle_threshold=pose_sweep.ANGLE_THRESHOLD, num_grid_enum_rotate=pose_sweep.NUM_GRID_ENUM_ROTATE)
+    angles = pose_sweep.generate_rotate_angle(args, dev)[:n_poses]
+    poses = torch.cat([pose_sweep.rotate_xyz(data, angles[i]) for i in range(n_poses)], dim=0).contiguous()
+    orders = synth.make_orders(perms, r, seed=1)
+    looped = lambda: np.stack([wide.shapley(model, poses[k:k + 1], lbl, rid_np, orders, args)[2] / perms for k in range(n_poses)])  # noqa: E731
+    batched = lambda: wide.shapley_over_poses(model, poses, lbl, rid_np, orders, args).cpu().numpy()                                # noqa: E731
+    same = bool(np.array_equal(looped(), batched()))      # warm-up of both, and the results must not differ
+    times = {"looped": [], "batched": []}
+    for _ in range(repeats):
+        times["looped"].append(_clock(looped)[0])
+        times["batched"].append(_clock(batched)[0])
+    b = n_poses * perms * (r + 1)
+    out = {"regions": r, "poses": n_poses, "permutations": perms, "coalitions": b, "values_bitwise_equal": same}
+    for arm in times:
+        out[arm] = dict(_summary([b / t for t in times[arm]]), seconds=times[arm], median_seconds=statistics.median(times[arm]))
+    a, bt = out["looped"], out["batched"]
+    out["ratio_batched_over_looped"] = bt["median"] / a["median"]
+    out["batched_slower_beyond_spread"] = (a["median"] - bt["median"]) / a["median"] > max(a["spread"], bt["spread"])
+    out["batched_faster"] = bt["median"] > a["median"]
+    return out
+
+
 COMPACT_FAMILIES = ("pointnet2", "dgcnn", "gcnn", "pointconv")
 
 
@@ -292,6 +330,9 @@ def main(argv=None):
     ap.add_argument("--compact", action="store_true",
                     help="time wide.shapley of the other families, dense against compact coalitions (leg 5), and put it under "
                          "\"compact\" in --out, keeping what is there")
+    ap.add_argument("--poses", action="store_true",
+                    help="time a pose sweep, one wide.shapley per pose against wide.shapley_over_poses (leg 6), and put it under "
+                         "\"poses\" in --out, keeping what is there")
     ap.add_argument("--families", nargs="+", choices=COMPACT_FAMILIES, default=list(COMPACT_FAMILIES), help="the families of --compact")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -325,6 +366,14 @@ def main(argv=None):
         res["prefix"] = {"device": torch.cuda.get_device_name(0), "repeats": max(5, args.repeats), "by_regions": legs,
                          "default_route_by_the_rule": "keep" if any(l["prefix_slower_beyond_spread"] for l in legs) else "prefix",
                          "default_route_in_this_build": wide.DEFAULT_ROUTE}
+        _write(args.out, res)
+        return
+    if args.poses:
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        legs = [poses_batched_vs_looped(model, r, dev) for r in (128, 1024)]
+        res["poses"] = {"device": torch.cuda.get_device_name(0), "repeats": 5, "by_regions": legs,
+                        "batching_stays_by_the_rule": not any(l["batched_slower_beyond_spread"] for l in legs)
+                        and any(l["batched_faster"] for l in legs)}
         _write(args.out, res)
         return
     if args.interaction:
