@@ -6,7 +6,7 @@ wrote for the same --num_regions (65 .. 1024, default 128).  Flags of final_wide
 Thin driver: all logic lives in interpret_quality_amd/, all arithmetic in libiq_hip.so."""
 from interpret_quality_amd.wide_pose_stage import main
 
-from interpret_quality_amd.wide_pose_stage import make_args, run, test  # noqa: F401,E402
+from interpret_quality_amd.wide_pose_stage import make_args, run  # noqa: F401,E402
 
 if __name__ == "__main__":
     main()

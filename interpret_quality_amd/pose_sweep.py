@@ -7,7 +7,12 @@ the ranks and each rank evaluates ``pose_batch`` poses per fused launch (coaliti
 perturbed clouds in one grid via ``cloud_of``); rank 0 gathers once per cloud and writes the same
 artefacts: orig_shapley_value.npy, region_shapley_value.npy (P,R), all_logits.pt (P,S*(R+1),C),
 trans_vector.npy | angle_tuple.npy | scale.npy, log.txt.
+
+The per-cloud loop (``test``, ``selected_clouds``) and the sharding (``sharded_over_poses``) serve every region count: what differs
+between the game of up to 64 regions and the wide one - which clouds, which permutations, the Shapley call - is a ``Game`` that
+the caller passes in (``GAME`` here, wide_stage.GAME for final_wide_pose.py); all_logits.pt is written when the call returns logits.
 """
+import collections
 import math
 import time
 
@@ -157,30 +162,59 @@ def shapley_over_poses(model, poses, lbl, region_id, orders, args, pose_batch=8)
     return torch.stack(phis, dim=0), torch.cat(all_logits, dim=0)
 
 
-def sharded_shapley(model, data, poses, lbl, region_id, orders, args):
-    """Region Shapley values of the original cloud ``data`` (1,N,3) and of its perturbed copies ``poses`` (P,N,3), the
-    P + 1 clouds sharded over the ranks (the original pose travels as pose 0 of the batch, so no rank repeats it) and
-    gathered once.  Returns (orig (R,) float64 ndarray, phi (P,R) float64 tensor, logits (P, S*(R+1), C)), the same on
-    every rank.  A cloud's values do not depend on the batch or shard it travels in (tested bitwise)."""
+def sharded_over_poses(data, poses, over_poses):
+    """What every game's sharded call does around its own Shapley function: the original cloud ``data`` (1,N,3) travels as pose 0
+    in front of its perturbed copies ``poses`` (P,N,3), so no rank repeats it; ``over_poses`` maps this rank's share of the
+    P + 1 clouds to a tuple of tensors with one row per cloud, and each of them is gathered once, in that order.  Returns the
+    gathered (P + 1, ...) tensors, the same on every rank."""
     allp = torch.cat([data.reshape(1, -1, 3), poses.reshape(-1, data.shape[1], 3)], dim=0)
     n = allp.shape[0]
     lo, hi = iqdist.shard_range(n)
-    phi, logits = shapley_over_poses(model, allp[lo:hi].contiguous(), lbl, region_id, orders, args)
-    phi = iqdist.all_gather_rows(phi, n)          # one gather per cloud
-    logits = iqdist.all_gather_rows(logits, n)
+    return [iqdist.all_gather_rows(t, n) for t in over_poses(allp[lo:hi].contiguous())]   # one gather per cloud and tensor
+
+
+def sharded_shapley(model, data, poses, lbl, region_id, orders, args):
+    """Region Shapley values of the original cloud ``data`` (1,N,3) and of its perturbed copies ``poses`` (P,N,3), the
+    P + 1 clouds sharded over the ranks and gathered once (``sharded_over_poses``).  Returns (orig (R,) float64 ndarray,
+    phi (P,R) float64 tensor, logits (P, S*(R+1), C)), the same on every rank.  A cloud's values do not depend on the batch
+    or shard it travels in (tested bitwise)."""
+    phi, logits = sharded_over_poses(data, poses, lambda clouds: shapley_over_poses(model, clouds, lbl, region_id, orders, args))
     return phi[0].cpu().numpy(), phi[1:], logits[1:]
 
 
-def test(args, get_transform_params_fn, disturb_fn, print_info_fn, save_info_fn):
-    """tools/final_common.py:107-174."""
-    model = load_model(args)
-    folder_name_list = get_folder_name_list(args)
-    write = iqdist.rank() == 0
+# ---- the per-cloud loop, for narrow and wide games -------------------------------------------------
+def selected_folders(args, names):
+    """(index, base folder) of the clouds this call computes; their files are not looked at."""
+    return [(i, args.exp_folder + "%s/" % name) for i, name in enumerate(names) if iqdist.cloud_selected(args, i)]
+
+
+def load_orders(base_folder, args):
+    """The whole all_orders.npy of a cloud; ``shapley_over_poses`` trims it to ``args.num_samples``."""
+    return np.load(base_folder + "all_orders.npy")
+
+
+# A game, as the per-cloud loops here and in smoothness.py see it.  ``folders``: which clouds to visit, (args, names) -> [(index,
+# base folder)].  ``orders``: which permutations to read, (base folder, args) -> (S,R) ndarray.  ``shapley``: the Shapley call,
+# (model, data, poses, lbl, region_id, orders, args) -> (orig, phi, logits or None).  The wide game: wide_stage.GAME.
+Game = collections.namedtuple("Game", "folders orders shapley")
+GAME = Game(selected_folders, load_orders, sharded_shapley)
+
+
+def selected_clouds(args, game):
+    """The clouds of ``game`` that this call computes, on the device and with stage 1's files read: yields (data, lbl, base
+    folder, region_id, orders).  The folders are resolved - and, where the game checks them, checked - before the loader starts."""
+    folders = dict(game.folders(args, get_folder_name_list(args)))
     for pc_index, (data, lbl) in enumerate(data_loader(args)):
-        if not iqdist.cloud_selected(args, pc_index):
-            continue
-        data, lbl = data.to(args.device), lbl.to(args.device)
-        base_folder = args.exp_folder + "%s/" % folder_name_list[pc_index]
+        if pc_index in folders:
+            base_folder = folders[pc_index]
+            yield data.to(args.device), lbl.to(args.device), base_folder, np.load(base_folder + "region_id.npy"), game.orders(base_folder, args)
+
+
+def test(args, get_transform_params_fn, disturb_fn, print_info_fn, save_info_fn, game=GAME):
+    """tools/final_common.py:107-174, for the clouds, permutations and Shapley call of ``game``."""
+    model = load_model(args)
+    write = iqdist.rank() == 0
+    for data, lbl, base_folder, region_id, orders in selected_clouds(args, game):
         mode_folder = base_folder + "%s_all/" % args.mode
         io = None
         if write:
@@ -188,15 +222,13 @@ def test(args, get_transform_params_fn, disturb_fn, print_info_fn, save_info_fn)
             io = IOStream(mode_folder + "log.txt")
             io.cprint(str(args))
             io.cprint("norm factor: %f" % np.load(base_folder + "norm_factor.npy"))
-        region_id = np.load(base_folder + "region_id.npy")
-        load_order_list = np.load(base_folder + "all_orders.npy")
 
         t_start = time.time()
         with torch.no_grad():
             all_params = get_transform_params_fn(args, data.device)
             n_pose = all_params.size()[0]
             poses = torch.cat([disturb_fn(data, all_params[i]) for i in range(n_pose)], dim=0)
-            orig, phi, logits = sharded_shapley(model, data, poses, lbl, region_id, load_order_list, args)
+            orig, phi, logits = game.shapley(model, data, poses, lbl, region_id, orders, args)
         if write:
             io.cprint("origin region shapley: %s" % str(orig))
             np.save(mode_folder + "orig_shapley_value.npy", orig)
@@ -204,10 +236,24 @@ def test(args, get_transform_params_fn, disturb_fn, print_info_fn, save_info_fn)
             for i in range(n_pose):
                 print_info_fn(io, all_params[i], phi_np[i], i)
             np.save(mode_folder + "region_shapley_value.npy", phi_np)
-            torch.save(logits, mode_folder + "all_logits.pt")
+            if logits is not None:
+                torch.save(logits, mode_folder + "all_logits.pt")
             save_info_fn(all_params, mode_folder)
             io.cprint("time: %f" % (time.time() - t_start))
             io.close()
+
+
+MODES = {"trans": (generate_trans_vector, translate_pc, print_trans_info, save_trans_info),
+         "rotate": (generate_rotate_angle, rotate_xyz, print_rotate_info, save_rotate_info),
+         "scale": (generate_scale, scale_pc, print_scale_info, save_scale_info)}
+
+
+def set_grid_args(args):
+    """The grids of the three sweeps (final_{rotate,trans,scale}_center_enum_all.py's constants) onto ``args``."""
+    args.angle_threshold, args.num_grid_enum_rotate = ANGLE_THRESHOLD, NUM_GRID_ENUM_ROTATE
+    args.trans_dist_threshold, args.num_grid_enum_trans = TRANS_DIST_THRESHOLD, NUM_GRID_ENUM_TRANS
+    args.scale_upper, args.scale_lower, args.num_grid_enum_scale = SCALE_UPPER, SCALE_LOWER, NUM_GRID_ENUM_SCALE
+    return args
 
 
 def make_args(mode, argv=None):
@@ -215,19 +261,13 @@ def make_args(mode, argv=None):
     args = build_parser(default_model).parse_args(argv)
     args.num_samples = NUM_SAMPLES
     args.mode = mode
-    args.angle_threshold, args.num_grid_enum_rotate = ANGLE_THRESHOLD, NUM_GRID_ENUM_ROTATE
-    args.trans_dist_threshold, args.num_grid_enum_trans = TRANS_DIST_THRESHOLD, NUM_GRID_ENUM_TRANS
-    args.scale_upper, args.scale_lower, args.num_grid_enum_scale = SCALE_UPPER, SCALE_LOWER, NUM_GRID_ENUM_SCALE
-    return args
+    return set_grid_args(args)
 
 
 def run(args):
     """The body of the three sweep scripts after argument handling (final_*_center_enum_all.py mains)."""
     set_shapley_batch_size(args)
-    fns = {"trans": (generate_trans_vector, translate_pc, print_trans_info, save_trans_info),
-           "rotate": (generate_rotate_angle, rotate_xyz, print_rotate_info, save_rotate_info),
-           "scale": (generate_scale, scale_pc, print_scale_info, save_scale_info)}[args.mode]
-    test(args, *fns)
+    test(args, *MODES[args.mode])
 
 
 @iqdist.record

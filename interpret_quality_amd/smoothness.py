@@ -19,6 +19,10 @@ Deviations, on purpose: (1) torch.symeig is gone from current torch; the 3x3 eig
 kernel (fp64 Jacobi).  (2) On a CPU tensor the reference's ``data_list`` aliases the working cloud, so every saved
 epoch shows the final state; on a GPU (how the experiment is run) each epoch is a snapshot - that is what is written
 here.  (3) A region with fewer than two points (which makes the reference fail) is left untouched, smoothness NaN.
+
+The loops (``run_modes``, ``test_smoothness``, ``test_all_region``) serve every region count: the game (pose_sweep.Game: clouds,
+permutations, Shapley call) and the enumerator are passed in - pose_sweep.GAME and ``enumerate_smoothness`` here, wide_stage.GAME
+and the wide enumerator for final_wide_smoothness.py; all_logits.pt is written when the Shapley call returns logits.
 """
 import time
 
@@ -26,10 +30,9 @@ import numpy as np
 import torch
 
 from . import dist as iqdist
-from . import final_common, hip_ops
-from .final_util import NUM_SAMPLES, IOStream, get_folder_name_list, load_model, mkdir, set_shapley_batch_size
-from .pose_sweep import sharded_shapley
-from .shapley_stage import build_parser, data_loader, finish_args
+from . import hip_ops, pose_sweep
+from .final_util import NUM_SAMPLES, IOStream, load_model, mkdir, set_shapley_batch_size
+from .shapley_stage import build_parser, finish_args
 
 STEP = 1e-3            # final_smoothness_center_enum_all.py:13-19
 ENUM_STEP = 0.05
@@ -78,8 +81,9 @@ def _log_enumeration(io, res, n_epochs, args, objective):
                 io.cprint("curr smoothness: %.8f" % sm[e, r])
 
 
-def test_all_region(model, data, lbl, load_order_list, region_id, mode_folder, args, objective):
-    """final_smoothness_center_enum_all.py:280-356."""
+def test_all_region(model, data, lbl, load_order_list, region_id, mode_folder, args, objective, shapley=pose_sweep.sharded_shapley,
+                    enumerate_fn=enumerate_smoothness):
+    """final_smoothness_center_enum_all.py:280-356, with the Shapley call of a game (pose_sweep.Game) and its enumerator."""
     assert objective in ["inc", "dec"]
     t_start = time.time()
     write = iqdist.rank() == 0
@@ -90,9 +94,9 @@ def test_all_region(model, data, lbl, load_order_list, region_id, mode_folder, a
         io = IOStream(result_path + "log.txt")
         io.cprint(str(args))
     with torch.no_grad():
-        poses, smoothness_list, res = enumerate_smoothness(data, region_id, args, objective)
+        poses, smoothness_list, res = enumerate_fn(data, region_id, args, objective)
         n_pose = poses.shape[0]
-        orig_shap_value, phi, logits = sharded_shapley(model, data, poses, lbl, region_id, load_order_list, args)
+        orig_shap_value, phi, logits = shapley(model, data, poses, lbl, region_id, load_order_list, args)
     if write:
         io.cprint("origin shapley of this region: %s" % str(orig_shap_value))
         np.save(result_path + "orig_shapley_value.npy", orig_shap_value)
@@ -101,43 +105,48 @@ def test_all_region(model, data, lbl, load_order_list, region_id, mode_folder, a
         for e in range(n_pose):
             io.cprint("epoch %d region shapley value: %s" % (e, str(phi_np[e])))
         np.save(result_path + "region_shapley_value.npy", phi_np)             # (num_poses, num_regions)
-        torch.save(logits, result_path + "all_logits.pt")                      # (num_poses, S*(R+1), C)
+        if logits is not None:
+            torch.save(logits, result_path + "all_logits.pt")                  # (num_poses, S*(R+1), C)
         np.save(result_path + "%s.npy" % args.mode, smoothness_list)           # (num_poses, num_regions)
         np.save(result_path + "data_smoothness.npy", poses.unsqueeze(1).cpu().numpy())  # (num_poses,1,N,3)
         io.cprint("time: %f" % (time.time() - t_start))
         io.close()
 
 
-def test_smoothness(args):
-    """final_smoothness_center_enum_all.py:360-390."""
-    model = load_model(args)
-    folder_name_list = get_folder_name_list(args)
-    for pc_index, (data, lbl) in enumerate(data_loader(args)):
-        if not iqdist.cloud_selected(args, pc_index):
-            continue
-        data, lbl = data.to(args.device), lbl.to(args.device)
-        base_folder = args.exp_folder + "%s/" % folder_name_list[pc_index]
+def test_smoothness(args, model, game=pose_sweep.GAME, enumerate_fn=enumerate_smoothness):
+    """final_smoothness_center_enum_all.py:360-390, for the clouds, permutations and Shapley call of ``game``."""
+    for data, lbl, base_folder, region_id, orders in pose_sweep.selected_clouds(args, game):
         mode_folder = base_folder + "%s_all/" % args.mode
-        region_id = np.load(base_folder + "region_id.npy")
-        load_order_list = np.load(base_folder + "all_orders.npy")
-        test_all_region(model, data, lbl, load_order_list, region_id, mode_folder, args, objective="inc")
-        test_all_region(model, data, lbl, load_order_list, region_id, mode_folder, args, objective="dec")
+        for objective in ("inc", "dec"):
+            test_all_region(model, data, lbl, orders, region_id, mode_folder, args, objective, game.shapley, enumerate_fn)
 
 
-def make_args(argv=None):
-    args = build_parser("pointnet").parse_args(argv)
-    args.num_samples = NUM_SAMPLES
+def set_enum_args(args):
+    """The constants of the enumeration (final_smoothness_center_enum_all.py:13-19) onto ``args``."""
     args.step, args.enum_step, args.epoch = STEP, ENUM_STEP, EPOCH
     args.var_threshold, args.dist_threshold = VAR_THRESHOLD, DIST_THRESHOLD
     args.stop_ratio, args.max_iteration = STOP_RATIO, MAX_ITERATION
     return args
 
 
+def make_args(argv=None):
+    args = build_parser("pointnet").parse_args(argv)
+    args.num_samples = NUM_SAMPLES
+    return set_enum_args(args)
+
+
+def run_modes(args, game=pose_sweep.GAME, enumerate_fn=enumerate_smoothness):
+    """The three modes of one game on one model (final_smoothness_center_enum_all.py:413-418; the reference rebuilds the model per
+    mode - the same weights)."""
+    model = load_model(args)
+    for mode in hip_ops.SMOOTHNESS_MODES:
+        args.mode = mode
+        test_smoothness(args, model, game, enumerate_fn)
+
+
 def run(args):
     set_shapley_batch_size(args)
-    for mode in ("linearity", "planarity", "scattering"):   # :413-418
-        args.mode = mode
-        test_smoothness(args)
+    run_modes(args)
 
 
 @iqdist.record

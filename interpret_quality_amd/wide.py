@@ -14,7 +14,8 @@ at dense-forward speed; "compact" takes the family's compact coalition path thro
 a coalition's distinct rows only, per-source-cloud tables), whose logits agree with the dense forward's to rounding, bitwise only
 where the summation order is the same.  For PointNet both names mean its fused path.  Both halves of the project have a wide form: the sampled Shapley values (``shapley``, wide_stage.py)
 and the multi-order interactions of sampled (pair, context) coalitions (``gen_context``, ``interaction_logits``, ``interactions``,
-wide_interaction_stage.py), and so do the stages that move the cloud: the pose sweeps (``shapley_over_poses``, ``sharded_shapley``,
+wide_interaction_stage.py), and so do the stages that move the cloud: the pose sweeps (``shapley_over_poses`` - ``shapley``'s checks,
+launches and reward loop run per pose: ``_game``, ``_steps``, ``_rewards`` - and ``sharded_shapley``,
 wide_pose_stage.py) and the smoothness enumeration (smoothness.enumerate_smoothness with ``wide=True``, wide_smoothness_stage.py;
 clouds of at most 1024 points).  Not wide: the single-region folders of final_gen_pair.py.
 """
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from . import dist as iqdist
-from . import final_common, gen_pair, hip_ops, interaction, work
+from . import final_common, gen_pair, hip_ops, interaction, pose_sweep, work
 from ._lib import IqError
 
 MAX_REGIONS = hip_ops.MAX_WIDE_REGIONS
@@ -117,6 +118,40 @@ def prefix_logits(model, data, region_id, orders, args, coalitions=None):
     return _prefix_logits(model, data, hip_ops.region_ids(region_id, data.device, r), orders.contiguous(), r, mode)
 
 
+def _game(model, clouds, orders, args, route, coalitions):
+    """What ``shapley`` and ``shapley_over_poses`` check before anything reaches a device -> (route, mode, R, ``orders`` as an (S,R)
+    ndarray); the route first, before any other argument is touched."""
+    route = _pick_route(model, route)
+    mode = _pick_coalitions(coalitions, clouds)
+    r = int(args.num_regions)
+    hip_ops.wide_words(r)
+    orders = np.asarray(orders)
+    if orders.ndim != 2 or orders.shape[1] != r:
+        raise IqError("orders must be (S, %d), got %s" % (r, orders.shape))
+    hip_ops.check_host_indices(orders, 0, r, "orders")
+    return route, mode, r, orders
+
+
+def _steps(orders_dev, r, perms_per_step=None):
+    """The launches of a game: [(lo, hi, orders_dev[lo:hi])], ``perms_per_step`` permutations at a time (default: about 2^17
+    coalitions)."""
+    s = orders_dev.shape[0]
+    step = int(perms_per_step) if perms_per_step else max(1, (1 << 17) // (r + 1))
+    return [(lo, min(lo + step, s), orders_dev[lo:lo + step].contiguous()) for lo in range(0, s, step)]
+
+
+def _rewards(model, data, lbl, rid, steps, keep, v, r, mode, args):
+    """The rewards of the prefix coalitions of one cloud ``data`` (1,N,3) into ``v`` (S*(R+1),), one step of ``_steps`` at a
+    time.  ``keep``: None on the prefix route - a step is evaluated straight from its permutations - else step index -> the
+    step's keep rows, evaluated as arbitrary coalitions."""
+    for j, (lo, hi, step_orders) in enumerate(steps):
+        if keep is None:
+            logits = _prefix_logits(model, data, rid, step_orders, r, mode)
+        else:
+            logits = _logits(model, data, rid, keep(j), r, mode)
+        v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
+
+
 def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None, route=None, coalitions=None):
     """The sampling loop of final_shapley_value.py:138-156 for one cloud ``data`` (1,N,3) and the permutations ``orders`` ((S,R)
     ndarray): -> (running sums {count: (R,) float64} at ``snap_counts``, per-permutation rows (S,R) float64, total (R,)), shaped
@@ -126,29 +161,16 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
     evaluates them as arbitrary coalitions, None takes "prefix" where the model has it - the values are the same bits either
     way.  ``coalitions``: how a family other than PointNet evaluates the keep rows (``coalition_logits``).  Prefix sets of
     different permutations almost never coincide at these region counts: no de-duplication."""
-    route = _pick_route(model, route)
-    mode = _pick_coalitions(coalitions, data)
+    route, mode, r, orders = _game(model, data, orders, args, route, coalitions)
     dev = data.device
-    r = int(args.num_regions)
-    hip_ops.wide_words(r)
-    orders = np.asarray(orders)
-    if orders.ndim != 2 or orders.shape[1] != r:
-        raise IqError("orders must be (S, %d), got %s" % (r, orders.shape))
-    hip_ops.check_host_indices(orders, 0, r, "orders")
-    s = orders.shape[0]
-    step = int(perms_per_step) if perms_per_step else max(1, (1 << 17) // (r + 1))
     orders_dev = hip_ops.as_i32(orders, dev)
     rid = hip_ops.region_ids(region_id, dev, r)
-    v = torch.empty((s * (r + 1),), dtype=torch.float32, device=dev)
+    steps = _steps(orders_dev, r, perms_per_step)
+    # the keep rows of one step at a time: at R = 1024 and 1000 permutations all of them would be about 130 MB
+    keep = None if route == "prefix" else lambda j: hip_ops.prefix_keep_masks_wide(steps[j][2])
+    v = torch.empty((orders.shape[0] * (r + 1),), dtype=torch.float32, device=dev)
     with torch.no_grad():
-        for lo in range(0, s, step):
-            hi = min(lo + step, s)
-            step_orders = orders_dev[lo:hi].contiguous()
-            if route == "prefix":
-                logits = _prefix_logits(model, data, rid, step_orders, r, mode)
-            else:
-                logits = _logits(model, data, rid, hip_ops.prefix_keep_masks_wide(step_orders), r, mode)
-            v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
+        _rewards(model, data, lbl, rid, steps, keep, v, r, mode, args)
     return hip_ops.shapley_snapshots(v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
 
 
@@ -156,23 +178,16 @@ def shapley_over_poses(model, poses, lbl, region_id, orders, args, route=None, c
     """Region Shapley values of several perturbed copies ``poses`` (P,N,3) of one cloud under the permutations ``orders`` ((S,R)
     ndarray): -> phi (P,R) float64 device tensor, the wide twin of pose_sweep.shapley_over_poses without its logits.  phi[p] is
     ``total / S`` of ``shapley(model, poses[p:p+1], lbl, region_id, orders, args, route=route, coalitions=coalitions)``, bit for bit:
-    the same kernels on the same rows (``_prefix_logits`` / ``_logits``, ``get_reward``, ``shapley_accum_wide``).  What does not
-    depend on the pose is done once per call: the checks, the permutations and region ids on the device and, on the keep route,
-    the keep rows.  The centre of a pose is torch.mean of that one (1,N,3) cloud, never of a batch of poses
+    ``shapley``'s checks, launches and reward loop (``_game``, ``_steps``, ``_rewards``) run per pose, then ``shapley_accum_wide``.
+    What does not depend on the pose is done once per call: the checks, the permutations and region ids on the device and, on the
+    keep route, the keep rows.  The centre of a pose is torch.mean of that one (1,N,3) cloud, never of a batch of poses
     (pose_sweep.shapley_over_poses records what a batched mean did to sharding).  Every route goes pose by pose: poses do not share
     launches (DESIGN.md 5e has the rule and why).
     ``route`` and ``coalitions`` as in ``shapley``."""
-    route = _pick_route(model, route)
-    mode = _pick_coalitions(coalitions, poses)
-    dev = poses.device
-    r = int(args.num_regions)
-    hip_ops.wide_words(r)
-    orders = np.asarray(orders)
-    if orders.ndim != 2 or orders.shape[1] != r:
-        raise IqError("orders must be (S, %d), got %s" % (r, orders.shape))
+    route, mode, r, orders = _game(model, poses, orders, args, route, coalitions)
     if poses.dim() != 3 or poses.shape[2] != 3:
         raise IqError("poses must be (P, N, 3), got %s" % (tuple(poses.shape),))
-    hip_ops.check_host_indices(orders, 0, r, "orders")
+    dev = poses.device
     s, p = orders.shape[0], poses.shape[0]
     phi = torch.zeros((p, r), dtype=torch.float64, device=dev)
     if p == 0:          # an empty shard still agrees with the others on the trailing shape of the gather
@@ -184,18 +199,12 @@ def shapley_over_poses(model, poses, lbl, region_id, orders, args, route=None, c
     rid = hip_ops.region_ids(region_id, dev, r)
     poses = poses.contiguous()
     with torch.no_grad():
-        step = max(1, (1 << 17) // (r + 1))           # ``shapley``'s launches
-        steps = [(lo, min(lo + step, s)) for lo in range(0, s, step)]
-        step_orders = [orders_dev[lo:hi].contiguous() for lo, hi in steps]
-        keep = [hip_ops.prefix_keep_masks_wide(o) for o in step_orders] if route == "keep" else None
+        steps = _steps(orders_dev, r)                 # ``shapley``'s launches
+        rows = [hip_ops.prefix_keep_masks_wide(o) for _, _, o in steps] if route == "keep" else None   # once per call, not per pose
+        keep = None if rows is None else rows.__getitem__
         v = torch.empty((p * per,), dtype=torch.float32, device=dev)
         for k in range(p):
-            for j, (lo, hi) in enumerate(steps):
-                if route == "prefix":
-                    logits = _prefix_logits(model, poses[k:k + 1], rid, step_orders[j], r, mode)
-                else:
-                    logits = _logits(model, poses[k:k + 1], rid, keep[j], r, mode)
-                v[k * per + lo * (r + 1):k * per + hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
+            _rewards(model, poses[k:k + 1], lbl, rid, steps, keep, v[k * per:(k + 1) * per], r, mode, args)
         for k in range(p):
             total, _, _ = hip_ops.shapley_accum_wide(v[k * per:(k + 1) * per], orders_dev)
             # a true float64 division, as ``total / S`` on the host: a tensor divided by a Python number is multiplied by its
@@ -205,15 +214,11 @@ def shapley_over_poses(model, poses, lbl, region_id, orders, args, route=None, c
 
 
 def sharded_shapley(model, data, poses, lbl, region_id, orders, args, route=None, coalitions=None):
-    """The wide twin of pose_sweep.sharded_shapley: region Shapley values of the original cloud ``data`` (1,N,3) and of its
-    perturbed copies ``poses`` (P,N,3), the P + 1 clouds sharded over the ranks (the original travels as pose 0) and gathered
-    once -> (orig (R,) float64 ndarray, phi (P,R) float64 tensor), the same on every rank whatever the rank count.  One
+    """The wide twin of pose_sweep.sharded_shapley, on its helper (pose_sweep.sharded_over_poses: the original travels as pose 0)
+    -> (orig (R,) float64 ndarray, phi (P,R) float64 tensor), the same on every rank whatever the rank count.  One
     all_gather_rows of phi per call; no logits, no other collective."""
-    allp = torch.cat([data.reshape(1, -1, 3), poses.reshape(-1, data.shape[1], 3)], dim=0)
-    n = allp.shape[0]
-    lo, hi = iqdist.shard_range(n)
-    phi = shapley_over_poses(model, allp[lo:hi].contiguous(), lbl, region_id, orders, args, route=route, coalitions=coalitions)
-    phi = iqdist.all_gather_rows(phi, n)
+    phi, = pose_sweep.sharded_over_poses(data, poses, lambda clouds: (
+        shapley_over_poses(model, clouds, lbl, region_id, orders, args, route=route, coalitions=coalitions),))
     return phi[0].cpu().numpy(), phi[1:]
 
 

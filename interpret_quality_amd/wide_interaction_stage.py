@@ -24,8 +24,6 @@ with ``--gen_pair_seed``, draws the pairs of ALL clouds first and then the conte
 (DESIGN.md 5e): the single-region folders of final_gen_pair.py (at R = 128 there are 128 of them, each with its own contexts) and
 sharding over ranks - under several ranks rank 0 does the work and the others wait.
 """
-import os
-
 import numpy as np
 import torch
 
@@ -33,8 +31,8 @@ from . import dist as iqdist
 from . import gen_pair, interaction, wide
 from .final_util import get_folder_name_list, load_model, mkdir, set_random
 from .pose_sweep import rotate_xyz, translate_pc
-from .shapley_stage import finish_args, parse_game_args, rank0_only
-from .wide_stage import DEFAULT_REGIONS, MIN_REGIONS
+from .shapley_stage import finish_args, rank0_only
+from .wide_stage import add_wide_flags, check_points, parse_wide_args, require
 
 CONTEXT_DTYPE = np.int16      # holds every region id of a wide game (wide.MAX_REGIONS = 1024)
 
@@ -77,7 +75,7 @@ def evaluate(model, data, lbl, region_id, folder, save_path, args):
         tag = int(ratio * 100)
         context_list = np.load(folder + "ratio%d_context_list.npy" % tag)
         all_logits = wide.interaction_logits(model, data, region_id, pairs, context_list, args,
-                                             coalitions=getattr(args, "coalitions", None))
+                                             coalitions=args.coalitions)
         torch.save(all_logits, save_path + "ratio%d_all_logits.pt" % tag)
         np.save(save_path + "ratio%d_%s_interaction.npy" % (tag, args.output_type), wide.interactions(all_logits, lbl, args))
         print("\tratio: %f, logits %s" % (ratio, tuple(all_logits.shape)))
@@ -89,12 +87,9 @@ def run(args):
     if not wanted:
         return
     for i in wanted:
-        path = args.exp_folder + "%s/region_id.npy" % names[i]
-        if not os.path.exists(path):
-            raise SystemExit("%s not found: run final_wide_shapley.py --num_regions %d first" % (path, args.num_regions))
-        path = _sweep_params_path(args, args.exp_folder + "%s/" % names[i])
-        if getattr(args, "adv_pose", None) == "sweep" and not os.path.exists(path):
-            raise SystemExit("%s not found: run final_wide_pose.py --mode %s --num_regions %d first" % (path, args.mode, args.num_regions))
+        require(args.exp_folder + "%s/region_id.npy" % names[i], args)
+        if args.adv_pose == "sweep":
+            require(_sweep_params_path(args, args.exp_folder + "%s/" % names[i]), args, "final_wide_pose.py --mode %s" % args.mode)
     model = load_model(args)
     disturb_fn = translate_pc if args.mode == "trans" else rotate_xyz
     params = np.load(args.transform_params) if args.transform_params else None
@@ -106,7 +101,7 @@ def run(args):
             print("##### normal pose")
             evaluate(model, data, lbl, region_id, folder, folder + "normal/", args)
             adv = folder + "%s_adv/" % args.mode
-            if getattr(args, "adv_pose", None) == "sweep":
+            if args.adv_pose == "sweep":
                 sweep = np.load(_sweep_params_path(args, base_folder))
                 pose_idx = gen_pair.lowest_reward_pose(model, data, lbl, sweep, disturb_fn, args)
                 print("Pose idx with max attacking utility: %d" % pose_idx)
@@ -115,7 +110,7 @@ def run(args):
                 params = sweep[pose_idx]
             if params is None:
                 continue
-            print("##### %s pose of %s" % (args.mode, "the sweep" if getattr(args, "adv_pose", None) else "--transform_params"))
+            print("##### %s pose of %s" % (args.mode, "the sweep" if args.adv_pose else "--transform_params"))
             mkdir(adv)
             np.save(adv + "transform_params.npy", params)
             gen_pair.gen_pred_label(model, data, lbl, disturb_fn, adv, args)
@@ -132,12 +127,8 @@ def make_args(argv=None):
     parser.add_argument("--adv_pose", choices=("sweep",), default=None,
                         help="sweep: take the adversarial pose from the wide pose sweep of --mode (the pose with the lowest reward "
                              "on the true class) instead of --transform_params")
-    parser.add_argument("--coalitions", choices=wide.COALITIONS, default=None,
-                        help="how a family other than PointNet evaluates the coalitions: dense = its dense forward on materialised "
-                             "clouds (the default), compact = its compact coalition path; the same artefacts, equal to rounding")
-    args = parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
-                           "the wide stage takes %d .. %d regions (final_gen_pair.py and final_point_binary_interaction_logits.py: "
-                           "up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS), samples=False)
+    add_wide_flags(parser, route=False)
+    args = parse_wide_args(parser, argv, "final_gen_pair.py and final_point_binary_interaction_logits.py", samples=False)
     if args.adv_pose and args.transform_params:
         parser.error("--adv_pose sweep finds the pose itself: it cannot be combined with --transform_params")
     if args.mode not in ("rotate", "trans"):
@@ -151,8 +142,7 @@ def make_args(argv=None):
 def main(argv=None):
     args = make_args(argv)
     finish_args(args)
-    if args.num_regions > args.num_points:
-        raise SystemExit("--num_regions %d exceeds the %d points of a cloud" % (args.num_regions, args.num_points))
+    check_points(args)
     rank0_only(run, args, "wide")
 
 

@@ -13,17 +13,90 @@ same bits either way), ``--coalitions dense|compact`` how a family other than Po
 multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py); the pose sweeps and the
 smoothness stage on these region ids and permutations: final_wide_pose.py (wide_pose_stage.py) and final_wide_smoothness.py
 (wide_smoothness_stage.py), sharded over the ranks.
+
+What the four wide stages share lives here too: the --route / --coalitions / --num_samples flags, the region-count message, the
+checks after finish_args, the "not found: run ... first" check of an earlier stage's files, and ``GAME`` - the wide game that the
+pose and smoothness stages pass to pose_sweep's and smoothness's per-cloud loops.
 """
+import os
+
 import numpy as np
 import torch
 
 from . import dist as iqdist
-from . import hip_ops, wide
+from . import hip_ops, pose_sweep, wide
 from . import shapley_stage as stage1
-from .final_util import get_folder_name_list, load_model
+from .final_util import NUM_SAMPLES, get_folder_name_list, load_model
 
 DEFAULT_REGIONS = 128
 MIN_REGIONS = 65          # up to 64 regions: final_shapley_value.py
+
+
+# ---- what the four wide stages share: flags, checks, stage 1's files -------------------------------
+def add_wide_flags(parser, route=True, num_samples=False):
+    """--coalitions, and where the stage has them --route and --num_samples."""
+    if route:
+        parser.add_argument("--route", choices=wide.ROUTES, default=None,
+                            help="how the prefix coalitions are evaluated: prefix = straight from the permutations (PointNet), keep = "
+                                 "through keep rows; the same bits either way (default: prefix where the model has it)")
+    parser.add_argument("--coalitions", choices=wide.COALITIONS, default=None,
+                        help="how a family other than PointNet evaluates the coalitions: dense = its dense forward on materialised "
+                             "clouds (the default), compact = its compact coalition path; the same artefacts, equal to rounding")
+    if num_samples:
+        parser.add_argument("--num_samples", type=int, default=NUM_SAMPLES,
+                            help="permutations per pose: the first rows of the all_orders.npy that final_wide_shapley.py wrote")
+
+
+def parse_wide_args(parser, argv, narrow_scripts, samples=True):
+    """shapley_stage.parse_game_args for MIN_REGIONS .. wide.MAX_REGIONS regions; ``narrow_scripts``: where fewer regions go."""
+    return stage1.parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
+                                  "the wide stage takes %d .. %d regions (%s: up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS, narrow_scripts),
+                                  samples=samples)
+
+
+def check_points(args):
+    """What every wide stage refuses after finish_args: more regions than points."""
+    if args.num_regions > args.num_points:
+        raise SystemExit("--num_regions %d exceeds the %d points of a cloud" % (args.num_regions, args.num_points))
+
+
+def check_wide_args(args):
+    """``check_points``, and for the stages with --num_samples: fewer than one permutation."""
+    check_points(args)
+    if args.num_samples < 1:
+        raise SystemExit("--num_samples %d: at least one permutation" % args.num_samples)
+
+
+def require(path, args, first="final_wide_shapley.py"):
+    """SystemExit naming the stage that writes ``path`` when it is not there."""
+    if not os.path.exists(path):
+        raise SystemExit("%s not found: run %s --num_regions %d first" % (path, first, args.num_regions))
+
+
+def selected_folders(args, names):
+    """pose_sweep.selected_folders; SystemExit (``require``) when stage 1 has not written a cloud's region ids or permutations."""
+    out = pose_sweep.selected_folders(args, names)
+    for _, base in out:
+        for f in ("region_id.npy", "all_orders.npy"):
+            require(base + f, args)
+    return out
+
+
+def load_orders(base_folder, args):
+    """The first ``--num_samples`` rows of the cloud's all_orders.npy; more than the file holds is an error."""
+    orders = np.load(base_folder + "all_orders.npy")
+    if args.num_samples > orders.shape[0]:
+        raise SystemExit("--num_samples %d exceeds the %d permutations of %sall_orders.npy (final_wide_shapley.py "
+                         "--num_samples_save)" % (args.num_samples, orders.shape[0], base_folder))
+    return orders[:args.num_samples]
+
+
+def sharded_shapley(model, data, poses, lbl, region_id, orders, args):
+    """wide.sharded_shapley as the per-cloud loops call it: route and coalitions from the flags, and no logits."""
+    return wide.sharded_shapley(model, data, poses, lbl, region_id, orders, args, route=args.route, coalitions=args.coalitions) + (None,)
+
+
+GAME = pose_sweep.Game(selected_folders, load_orders, sharded_shapley)   # the wide game of the pose and smoothness stages
 
 
 def generate_all_orders(result_path, args, save=True):
@@ -54,7 +127,7 @@ def run(args):
             all_orders = generate_all_orders(result_path, args)
             print("pointcloud:%s, index:%d, regions:%d, samples:%d" % (name, i, args.num_regions, len(all_orders)))
             snaps, region_sv_all, _ = wide.shapley(model, data, lbl, region_id, all_orders, args, snap_counts=stage1.SAMPLE_NUMS,
-                                                   route=args.route, coalitions=getattr(args, "coalitions", None))
+                                                   route=args.route, coalitions=args.coalitions)
             for count, running in snaps.items():
                 stage1.save_shapley(running, i, count, result_path, region_id, args)
             np.save(result_path + "region_sv_all.npy", region_sv_all)
@@ -62,22 +135,15 @@ def run(args):
 
 def make_args(argv=None):
     parser = stage1.build_parser()
-    parser.add_argument("--route", choices=wide.ROUTES, default=None,
-                        help="how the prefix coalitions are evaluated: prefix = straight from the permutations (PointNet), keep = "
-                             "through keep rows; the same bits either way (default: prefix where the model has it)")
-    parser.add_argument("--coalitions", choices=wide.COALITIONS, default=None,
-                        help="how a family other than PointNet evaluates the coalitions: dense = its dense forward on materialised "
-                             "clouds (the default), compact = its compact coalition path; the same artefacts, equal to rounding")
-    return stage1.parse_game_args(parser, argv, DEFAULT_REGIONS, MIN_REGIONS, wide.MAX_REGIONS,
-                                  "the wide stage takes %d .. %d regions (final_shapley_value.py: up to 64)" % (MIN_REGIONS, wide.MAX_REGIONS))
+    add_wide_flags(parser)
+    return parse_wide_args(parser, argv, "final_shapley_value.py")
 
 
 @iqdist.record
 def main(argv=None):
     args = make_args(argv)
     stage1.finish_args(args)
-    if args.num_regions > args.num_points:
-        raise SystemExit("--num_regions %d exceeds the %d points of a cloud" % (args.num_regions, args.num_points))
+    check_points(args)
     stage1.rank0_only(run, args, "wide")
 
 
