@@ -63,7 +63,7 @@ enum {
  * 109: new entry points, no layout change (iq_split_packed_weight_bf3, iq_split_packed_weight_bf3_host); the PointNet workspaces
  * grew by the bf16x3 image of fstn.fc3 (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes).
  * 110: one new entry point, no layout change (iq_smoothness_enum_wide: the smoothness enumeration of a wide game). */
-#define IQ_ABI_VERSION 110
+#define IQ_ABI_VERSION 111
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -112,8 +112,19 @@ int iq_check_index_range(const int32_t* idx, size_t count, int lo, int hi, uint3
  * ON THE DEVICE: mt_state is the generator's state as np.random.get_state() returns it - 624 key words followed by the
  * position (625 uint32, device memory) - and is advanced in place, so permutations and every later host draw (after
  * np.random.set_state with the returned words) are bit-identical to the reference's stream for the same seed.
- * One workgroup (the stream is sequential); ~0.2 ms for 1000 permutations of 32 regions. */
+ * One workgroup (the stream is sequential); 0.40 ms for 1000 permutations of 32 regions. */
 int iq_sample_permutations(uint32_t* mt_state /*625*/, int32_t* orders /*S,R*/, int S, int R, iq_stream_t stream);
+
+/* The same draw, same bits in orders and mt_state, spread over many workgroups: only the twist of the generator is sequential.
+ * The library allocates nothing, so the caller lends a workspace (device memory, 8-byte aligned, contents irrelevant before and
+ * after); iq_sample_workspace_bytes(S, R) is the size at which the wide kernels expect to draw everything.  The number of words
+ * a draw consumes is random, the size an estimate: with a smaller workspace (any size, none included) or an unlucky draw the
+ * one-workgroup kernel of iq_sample_permutations, which always runs last, draws the rest.  No host synchronisation;
+ * 0.075 ms for 1000 permutations of 32 regions (five launches; a call that fits one batch of the one-workgroup kernel, about
+ * 100 permutations of 32 regions, stays on it, and iq_sample_workspace_bytes answers 0 for it). */
+size_t iq_sample_workspace_bytes(int S, int R);
+int iq_sample_permutations_ws(uint32_t* mt_state /*625*/, int32_t* orders /*S,R*/, int S, int R, void* workspace,
+                              size_t workspace_bytes, iq_stream_t stream);
 
 /* tools/final_common.py:56-60 as bit masks: keep[s*(R+1) + i] = the regions orders[s][0..i-1]
  * (row 0 = nothing kept = all-centre cloud, row R = the unmodified cloud). */

@@ -85,6 +85,8 @@ SIGNATURES = {
     "iq_mask_coalitions": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "iq_check_index_range": (_I, [_P, _SZ, _I, _I, _P, _P]),
     "iq_sample_permutations": (_I, [_P, _P, _I, _I, _P]),
+    "iq_sample_workspace_bytes": (_SZ, [_I, _I]),
+    "iq_sample_permutations_ws": (_I, [_P, _P, _I, _I, _P, _SZ, _P]),
     "iq_prefix_keep_masks": (_I, [_P, _P, _I, _I, _P]),
     "iq_context_keep_masks": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "iq_reward": (_I, [_P, _I, _I, _P, _I, _I, _P]),
@@ -161,7 +163,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 110   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 111   # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

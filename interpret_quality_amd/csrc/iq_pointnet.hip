@@ -838,35 +838,83 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
 }
 
 // ---- per-cloud region tables: points grouped by region (counting sort) ------------------------
-__global__ __launch_bounds__(kThreads) void pn_prepare_kernel(const int32_t* __restrict__ region_id,
-                                                              uint16_t* __restrict__ sorted_pts,
-                                                              int32_t* __restrict__ roff, int N, int R) {
+// sorted_pts: the points of region 0, 1, .. R-1 in ascending point order; roff[r]: where region r starts (roff[R]: the end).
+// A stable counting sort on kThreads / 64 waves: wave w owns the w-th quarter of the points.  Counts per (wave, region), one
+// scan over the regions that turns them into the first slot of each wave in each region, then every wave walks its points 64
+// at a time: the lanes of one region find each other by ballot, a lane's rank among them is a population count, and the slot
+// table is read and moved once per 64 points.  (The rank used to be a loop over all earlier points, per point.)  MAXR: IQ_MAX_REGIONS or IQ_MAX_WIDE_REGIONS, the size of the tables.
+template <int MAXR>
+__device__ __forceinline__ void pn_prepare_body(const int32_t* __restrict__ region_id, uint16_t* __restrict__ sorted_pts,
+                                                int32_t* __restrict__ roff, int N, int R) {
+    constexpr int kWaves = kThreads / 64;
     __shared__ int16_t rid[kMaxN];
-    __shared__ int cnt[IQ_MAX_REGIONS + 1];
-    const int cloud = blockIdx.x;
-    if (threadIdx.x <= IQ_MAX_REGIONS) cnt[threadIdx.x] = 0;
-    for (int p = threadIdx.x; p < N; p += kThreads) {
+    __shared__ int cnt[kWaves][MAXR + 1];          // points of (wave, region); after the scan: the next free slot of that wave there
+    const int cloud = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int r = tid; r <= R; r += kThreads)
+        for (int w = 0; w < kWaves; ++w) cnt[w][r] = 0;
+    for (int p = tid; p < N; p += kThreads) {
         // an id outside [0,R) (rejected by iq_check_index_range; never produced by iq_region_assign) goes to bucket R,
         // which no coalition keeps: the point counts as masked instead of indexing LDS / the workspace out of bounds
         const int r = region_id[(size_t)cloud * N + p];
         rid[p] = (int16_t)((unsigned)r < (unsigned)R ? r : R);
     }
     __syncthreads();
-    for (int p = threadIdx.x; p < N; p += kThreads) atomicAdd(&cnt[rid[p]], 1);
+    const int per = (N + kThreads - 1) / kThreads * 64;          // points per wave, whole steps of 64
+    const int begin = min(wave * per, N), end = min(begin + per, N);
+    for (int p = begin + lane; p < end; p += 64) atomicAdd(&cnt[wave][rid[p]], 1);
     __syncthreads();
-    if (threadIdx.x == 0) {  // exclusive scan, R <= 64
-        int run = 0;
-        for (int r = 0; r <= R; ++r) { const int c = r < R ? cnt[r] : 0; cnt[r] = run; run += c; }
+    if (wave == 0) {                               // exclusive scan over (region, wave), 64 regions at a time; bucket R holds nothing
+        int carry = 0;
+        for (int r0 = 0; r0 <= R; r0 += 64) {
+            const int r = r0 + lane;
+            int c[kWaves], tot = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) { c[w] = r < R ? cnt[w][r] : 0; tot += c[w]; }
+            int inc = tot;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(inc, off);
+                if (lane >= off) inc += t;
+            }
+            int slot = carry + inc - tot;
+            if (r <= R) {
+                roff[(size_t)cloud * (R + 1) + r] = slot;
+#pragma unroll
+                for (int w = 0; w < kWaves; ++w) { cnt[w][r] = slot; slot += c[w]; }
+            }
+            carry += __shfl(inc, 63);
+        }
     }
     __syncthreads();
-    if (threadIdx.x <= R) roff[(size_t)cloud * (R + 1) + threadIdx.x] = cnt[threadIdx.x];
-    for (int p = threadIdx.x; p < N; p += kThreads) {
-        const int r = rid[p];
-        if (r >= R) continue;
-        int k = 0;
-        for (int q = 0; q < p; ++q) k += (rid[q] == r);   // rank inside the region: ascending point index
-        sorted_pts[(size_t)cloud * N + cnt[r] + k] = (uint16_t)p;
+    for (int p0 = begin; p0 < end; p0 += 64) {
+        const int p = p0 + lane;
+        const int r = p < end ? rid[p] : R;
+        const bool placed = r < R;
+        int rank = 0, total = 0;                   // this lane among the lanes of its region, and how many they are
+        unsigned long long pending = __ballot(placed);
+        while (pending) {                          // one trip per region present among the 64 points, registers only
+            const int rl = __builtin_amdgcn_readlane(r, __builtin_amdgcn_readfirstlane(__ffsll((long long)pending) - 1));
+            const unsigned long long same = __ballot(placed && r == rl);
+            if (placed && r == rl) {
+                rank = __popcll(same & ((1ull << lane) - 1));
+                total = __popcll(same);
+            }
+            pending &= ~same;
+        }
+        const int slot = cnt[wave][r];             // (bucket R: read, never used)
+        if (placed) sorted_pts[(size_t)cloud * N + slot + rank] = (uint16_t)p;
+        __builtin_amdgcn_wave_barrier();           // every lane has read its slot before the first of a region moves it
+        if (placed && rank == 0) cnt[wave][r] = slot + total;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+}
+
+__global__ __launch_bounds__(kThreads) void pn_prepare_kernel(const int32_t* __restrict__ region_id,
+                                                              uint16_t* __restrict__ sorted_pts,
+                                                              int32_t* __restrict__ roff, int N, int R) {
+    pn_prepare_body<IQ_MAX_REGIONS>(region_id, sorted_pts, roff, N, R);
 }
 
 // ---- compacted row list of every work item (one wave per item) --------------------------------
@@ -941,30 +989,7 @@ constexpr int kMaxW = IQ_MAX_WIDE_REGIONS / 64;
 __global__ __launch_bounds__(kThreads) void pn_prepare_wide_kernel(const int32_t* __restrict__ region_id,
                                                                    uint16_t* __restrict__ sorted_pts,
                                                                    int32_t* __restrict__ roff, int N, int R) {
-    __shared__ int16_t rid[kMaxN];
-    __shared__ int cnt[IQ_MAX_WIDE_REGIONS + 1];
-    const int cloud = blockIdx.x;
-    for (int r = threadIdx.x; r <= R; r += kThreads) cnt[r] = 0;
-    for (int p = threadIdx.x; p < N; p += kThreads) {
-        const int r = region_id[(size_t)cloud * N + p];          // outside [0,R): bucket R, which no coalition keeps
-        rid[p] = (int16_t)((unsigned)r < (unsigned)R ? r : R);
-    }
-    __syncthreads();
-    for (int p = threadIdx.x; p < N; p += kThreads) atomicAdd(&cnt[rid[p]], 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {  // exclusive scan; once per cloud and launch
-        int run = 0;
-        for (int r = 0; r <= R; ++r) { const int c = r < R ? cnt[r] : 0; cnt[r] = run; run += c; }
-    }
-    __syncthreads();
-    for (int r = threadIdx.x; r <= R; r += kThreads) roff[(size_t)cloud * (R + 1) + r] = cnt[r];
-    for (int p = threadIdx.x; p < N; p += kThreads) {
-        const int r = rid[p];
-        if (r >= R) continue;
-        int k = 0;
-        for (int q = 0; q < p; ++q) k += (rid[q] == r);   // rank inside the region: ascending point index
-        sorted_pts[(size_t)cloud * N + cnt[r] + k] = (uint16_t)p;
-    }
+    pn_prepare_body<IQ_MAX_WIDE_REGIONS>(region_id, sorted_pts, roff, N, R);
 }
 
 // One wave per item.  The start of every kept region in the row list comes from a scan over the regions, 64 at a time.  A region of
@@ -1191,6 +1216,51 @@ __global__ __launch_bounds__(kThreads) void pn_order_scatter_kernel(const int32_
     if (threadIdx.x < kBins && lh[threadIdx.x]) base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], lh[threadIdx.x]);
     __syncthreads();
     if (item < B) order[base[bin] + pos] = item;
+}
+
+// The four steps above in one launch for a batch that one workgroup covers (a pose of a sweep: 3 300 coalitions): the clear, the
+// histogram and the scan stay in LDS, and an item keeps its position inside its bin in a register.  Above kOrderFusedMax items a
+// single workgroup would take longer than the four launches' grids, so those stay.  pointnet.ORDER_FUSED_MAX (Python) repeats
+// kOrderFusedMax for the tests that probe both sides of the bound: the two move together.
+constexpr int kOrderThreads = 1024, kOrderPer = 4, kOrderFusedMax = kOrderThreads * kOrderPer;
+
+__global__ __launch_bounds__(kOrderThreads) void pn_order_fused_kernel(const int32_t* __restrict__ nrows_all,
+                                                                       int32_t* __restrict__ order, int B) {
+    __shared__ int lh[kBins];
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < kBins) lh[tid] = 0;
+    __syncthreads();
+    int bin[kOrderPer], pos[kOrderPer];
+#pragma unroll
+    for (int j = 0; j < kOrderPer; ++j) {
+        const int item = tid + j * kOrderThreads;
+        if (item < B) {
+            const int rows = nrows_all[item] & 0xffff;
+            bin[j] = kBins - 1 - min(kBins - 1, (rows + kMC - 1) / kMC);  // bin 0 = most chunks
+            pos[j] = atomicAdd(&lh[bin[j]], 1);
+        }
+    }
+    __syncthreads();
+    if (tid < 64) {                                // exclusive scan, 64 bins at a time
+        int carry = 0;
+        for (int b0 = 0; b0 < kBins; b0 += 64) {
+            const int b = b0 + lane, c = b < kBins ? lh[b] : 0;
+            int inc = c;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int t = __shfl_up(inc, off);
+                if (lane >= off) inc += t;
+            }
+            if (b < kBins) lh[b] = carry + inc - c;
+            carry += __shfl(inc, 63);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kOrderPer; ++j) {
+        const int item = tid + j * kOrderThreads;
+        if (item < B) order[lh[bin[j]] + pos[j]] = item;
+    }
 }
 
 // ---- pooled input-STN feature of a coalition: max over kept regions (+ centre) -------------
@@ -1486,13 +1556,17 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         if ((rc = iq::check_launch("pn_rows_kernel"))) return rc;
     }
     // launch order of the coalition chains: most rows first, so the grid drains evenly
-    if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "%s: memset failed", who);
-    hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
-                       ws.bin_of, ws.hist, B);
-    hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
-    hipLaunchKernelGGL(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                       ws.bin_of, ws.hist, ws.order, B);
+    if (B <= kOrderFusedMax) {
+        hipLaunchKernelGGL(pn_order_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.order, B);
+    } else {
+        if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
+            return iq::fail(IQ_ELAUNCH, "%s: memset failed", who);
+        hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
+                           ws.bin_of, ws.hist, B);
+        hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
+        hipLaunchKernelGGL(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+                           ws.bin_of, ws.hist, ws.order, B);
+    }
     if ((rc = iq::check_launch("pn_order kernels"))) return rc;
 
     ChainArgs a{};

@@ -1,6 +1,7 @@
 // Reward (K3), per-region Shapley accumulation (K4) and interaction reduction (K5).
-// All tiny next to the forward; written for bit-stability (fixed summation order), not speed.
+// All tiny next to the forward; written for bit-stability (fixed summation order) first.
 #include "iq_common.h"
+#include "iq_shapley_sum.h"
 
 namespace {
 
@@ -38,33 +39,11 @@ __global__ void shapley_scatter_kernel(const float* __restrict__ v, const int32_
 }
 
 // Sum over permutations in permutation order, one lane per region: the same sequence of float64
-// adds the reference's host loop performs, hence bit-identical for identical v.
-__global__ void shapley_sum_kernel(const double* __restrict__ sv_rows, double* __restrict__ phi_sum,
-                                   const int32_t* __restrict__ snap_counts, int n_snap,
-                                   double* __restrict__ snaps, int R, int S) {
-    const int r = threadIdx.x;
-    if (r >= R) return;
-    double acc = 0.0;
-    int k = 0;
-    // the adds stay strictly in permutation order; the loads run 8 rows ahead of them (a plain loop paid one memory
-    // latency per permutation: 260 us for 1000 permutations)
-    constexpr int U = 8;
-    int o = 0;
-    for (; o + U <= S; o += U) {
-        double v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = sv_rows[(size_t)(o + u) * R + r];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            acc += v[u];
-            while (k < n_snap && snap_counts[k] == o + u + 1) { snaps[(size_t)k * R + r] = acc; ++k; }
-        }
-    }
-    for (; o < S; ++o) {
-        acc += sv_rows[(size_t)o * R + r];
-        while (k < n_snap && snap_counts[k] == o + 1) { snaps[(size_t)k * R + r] = acc; ++k; }
-    }
-    phi_sum[r] = acc;
+// adds the reference's host loop performs, hence bit-identical for identical v (iq_shapley_sum.h).
+__global__ __launch_bounds__(iq::kSumThreads) void shapley_sum_kernel(const double* __restrict__ sv_rows, double* __restrict__ phi_sum,
+                                                                      const int32_t* __restrict__ snap_counts, int n_snap,
+                                                                      double* __restrict__ snaps, int R, int S) {
+    iq::shapley_sum_rows(sv_rows, phi_sum, snap_counts, n_snap, snaps, R, S, 0);
 }
 
 __global__ void interaction_reduce_kernel(const float* __restrict__ v, float* __restrict__ out, int n) {
@@ -102,7 +81,7 @@ extern "C" int iq_shapley_accum(const float* v, const int32_t* orders, double* s
         int rc = iq::check_launch("shapley_scatter_kernel");
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(shapley_sum_kernel, dim3(1), dim3(64), 0, st, sv_rows, phi_sum, snap_counts,
+    hipLaunchKernelGGL(shapley_sum_kernel, dim3(1), dim3(iq::kSumThreads), 0, st, sv_rows, phi_sum, snap_counts,
                        n_snap, snaps, R, S);
     return iq::check_launch("shapley_sum_kernel");
 }

@@ -7,6 +7,7 @@
 // R <= 64 the results are the twins' bits.  The (pair, context) masks of the interaction stage have the twin's rows and another
 // kernel shape: one wave per context.  The fused PointNet path for wide masks is in iq_pointnet.hip.
 #include "iq_common.h"
+#include "iq_shapley_sum.h"
 #include "iq_sqdist.h"
 
 // iq_region_assign_wide is index-valued: individually rounded operations, as in iq_geom.hip
@@ -171,31 +172,11 @@ __global__ void shapley_scatter_wide_kernel(const float* __restrict__ v, const i
     if ((unsigned)r < (unsigned)R) sv_rows[o * R + r] = (double)dv;
 }
 
-// one lane per region, adds strictly in permutation order (shapley_sum_kernel's sequence), loads 8 rows ahead
-__global__ __launch_bounds__(64) void shapley_sum_wide_kernel(const double* __restrict__ sv_rows, double* __restrict__ phi_sum,
-                                                              const int32_t* __restrict__ snap_counts, int n_snap,
-                                                              double* __restrict__ snaps, int R, int S) {
-    const int r = blockIdx.x * 64 + threadIdx.x;
-    if (r >= R) return;
-    double acc = 0.0;
-    int k = 0;
-    constexpr int U = 8;
-    int o = 0;
-    for (; o + U <= S; o += U) {
-        double v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = sv_rows[(size_t)(o + u) * R + r];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            acc += v[u];
-            while (k < n_snap && snap_counts[k] == o + u + 1) { snaps[(size_t)k * R + r] = acc; ++k; }
-        }
-    }
-    for (; o < S; ++o) {
-        acc += sv_rows[(size_t)o * R + r];
-        while (k < n_snap && snap_counts[k] == o + 1) { snaps[(size_t)k * R + r] = acc; ++k; }
-    }
-    phi_sum[r] = acc;
+// shapley_sum_kernel's body (iq_shapley_sum.h) on one workgroup per 64 regions
+__global__ __launch_bounds__(iq::kSumThreads) void shapley_sum_wide_kernel(const double* __restrict__ sv_rows, double* __restrict__ phi_sum,
+                                                                           const int32_t* __restrict__ snap_counts, int n_snap,
+                                                                           double* __restrict__ snaps, int R, int S) {
+    iq::shapley_sum_rows(sv_rows, phi_sum, snap_counts, n_snap, snaps, R, S, blockIdx.x * 64);
 }
 
 }  // namespace
@@ -262,7 +243,7 @@ extern "C" int iq_shapley_accum_wide(const float* v, const int32_t* orders, doub
         int rc = iq::check_launch("shapley_scatter_wide_kernel");
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(shapley_sum_wide_kernel, dim3((R + 63) / 64), dim3(64), 0, st, sv_rows, phi_sum, snap_counts, n_snap, snaps,
+    hipLaunchKernelGGL(shapley_sum_wide_kernel, dim3((R + 63) / 64), dim3(iq::kSumThreads), 0, st, sv_rows, phi_sum, snap_counts, n_snap, snaps,
                        R, S);
     return iq::check_launch("shapley_sum_wide_kernel");
 }

@@ -106,12 +106,26 @@ def mt_state_to_host(mt_state, set_global=True):
     return st
 
 
-def sample_permutations(mt_state, num_samples, num_regions):
-    """iq_sample_permutations: (S,R) int32 permutations continuing the generator ``mt_state`` (advanced in place, no sync)."""
+_sample_ws = {}       # device -> uint8 scratch tensor of the sampler, grown on demand
+SAMPLE_WS_CAP = 32 << 20    # bytes kept per device at most (16 per estimated word: 50 000 permutations of 32 regions); beyond it
+#                             the library's finishing kernel draws what the wide kernels could not
+
+
+def sample_permutations(mt_state, num_samples, num_regions, workspace_bytes=None):
+    """iq_sample_permutations_ws: (S,R) int32 permutations continuing the generator ``mt_state`` (advanced in place, no sync).
+    ``workspace_bytes``: lend the library that much scratch instead of what iq_sample_workspace_bytes asks for (the result does
+    not depend on it; 0 = the one-workgroup kernel alone).  The scratch tensor is one per device: calls on one device are
+    expected on one stream, like the engines' workspaces."""
     lib = _lib.load()
-    orders = torch.empty((int(num_samples), int(num_regions)), dtype=torch.int32, device=mt_state.device)
-    _lib.check(lib.iq_sample_permutations(_dev(mt_state, torch.int32, "mt_state"), _p(orders), int(num_samples), int(num_regions),
-                                          _stream()), "iq_sample_permutations")
+    s, r = int(num_samples), int(num_regions)
+    orders = torch.empty((s, r), dtype=torch.int32, device=mt_state.device)
+    state = _dev(mt_state, torch.int32, "mt_state")
+    nbytes = min(lib.iq_sample_workspace_bytes(s, r), SAMPLE_WS_CAP) if workspace_bytes is None else int(workspace_bytes)
+    ws = _sample_ws.get(mt_state.device)
+    if nbytes and (ws is None or ws.numel() < nbytes):
+        ws = _sample_ws[mt_state.device] = torch.empty((nbytes,), dtype=torch.uint8, device=mt_state.device)
+    _lib.check(lib.iq_sample_permutations_ws(state, _p(orders), s, r, _p(ws) if nbytes else ctypes.c_void_p(0), nbytes, _stream()),
+               "iq_sample_permutations_ws")
     return orders
 
 

@@ -79,6 +79,9 @@ class PackedWeights(Packer):
         self.num_classes = int(sd["fc3.weight"].shape[0])
 
 
+ORDER_FUSED_MAX = 4096      # kOrderFusedMax of csrc/iq_pointnet.hip: up to here one kernel sorts a batch's launch order, above it four
+
+
 class PointNetEngine(Engine):
     """Owns packed weights and a growable workspace; issues iq_pointnet_coalitions."""
     packed = PackedWeights
