@@ -233,10 +233,87 @@ struct PcGroupArgs {
     const int32_t* n_unique;   // (B) or null: groups s >= n_unique[b] are copies of group 0 and are not computed
 };
 
+// ---- what pc_group_kernel and pc_group_bf3_kernel share ---------------------------------------------------------------------
+static_assert(kThreads == kGroupThreads, "iq_group_mlp.h deals rows and channels over this workgroup");
+constexpr int kLdsSw = kMC + 2;   // swT row stride 66: conflict-free dword reads
+
+// The 64-member chunks [ch0, ch0 + nchunks) of cloud b that a workgroup computes.  1-D grid; workgroups go round-robin over the
+// 8 XCDs: keep all workgroups of a cloud on one XCD (one L2 holds its U rows and member records).
+struct ChunkRange {
+    int b, ch0, nchunks;
+    size_t member0;   // first member record of this cloud
+};
+// false: nothing to do for this workgroup
+__device__ __forceinline__ bool chunk_range(const PcGroupArgs& a, ChunkRange& w) {
+    const int slot = blockIdx.x >> 3;
+    w.b = iq::xcd_cloud(blockIdx.x, a.wgs_per_cloud, a.B);
+    if (w.b >= a.B) return false;
+    const int live_groups = a.n_unique ? min(a.S, a.n_unique[w.b]) : a.S;
+    const int chunks_total = (live_groups * a.K + kMC - 1) / kMC;
+    w.ch0 = (slot % a.wgs_per_cloud) * a.chunks_per_wg;
+    if (w.ch0 >= chunks_total) return false;
+    w.nchunks = min(a.chunks_per_wg, chunks_total - w.ch0);
+    w.member0 = (size_t)w.b * a.S * a.K;
+    return true;
+}
+
+// Stage 0a of chunk ch: the members' rel rows into relbuf, their sw rows transposed into swbuf ([w][member])
+__device__ __forceinline__ void pc_stage0a(const PcGroupArgs& a, const ChunkRange& w, int ch, float* relbuf, float* swbuf, int tid) {
+    const size_t m = w.member0 + (size_t)(w.ch0 + ch) * kMC;
+    if (tid < kMC) *reinterpret_cast<f32x4*>(relbuf + tid * 4) = *reinterpret_cast<const f32x4*>(a.mrel + (m + tid) * 4);
+    const int mem = tid >> 2, q4 = tid & 3;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(a.msw + (m + mem) * 16 + q4 * 4);
+    float* dst = swbuf + (q4 * 4) * kLdsSw + mem;
+    dst[0] = v[0]; dst[kLdsSw] = v[1]; dst[2 * kLdsSw] = v[2]; dst[3 * kLdsSw] = v[3];
+}
+
+// B operand of the contraction: lane (w = lane & 15, k = lane >> 4) reads sw of member base + (k & 1) + 4 (k >> 1)
+__device__ __forceinline__ const float* pc_sw_lane(const float* swbuf, int lane) {
+    return swbuf + (lane & 15) * kLdsSw + ((lane >> 4) & 1) + 4 * (lane >> 5);
+}
+
+// The contraction of one n-tile (described above pc_group_kernel): acc0 / acc1 = the layer-3 tiles of m-tiles 0 / 1 before bias and
+// ReLU, swc = pc_sw_lane of the chunk's swT, dst = out[first group of the chunk][first channel of the n-tile][0].
+template <int C3>
+__device__ __forceinline__ void pc_contract_tile(const f32x16& acc0, const f32x16& acc1, float bias, const float* swc, float* dst,
+                                                 int K, int lane) {
+    // d[mt][half]: 16x16 tiles (channels 16 half + 4 (lane >> 4) + j of the n-tile, w = lane & 15) of m-tile mt
+    f32x4 d00 = {0, 0, 0, 0}, d01 = d00, d10 = d00, d11 = d00;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {      // accumulator registers 2 p, 2 p + 1: members c_row_i(2 p) + {0, 1, 4, 5}
+        const int m = c_row_i(2 * p);
+        const float s0 = swc[m], s1 = swc[32 + m];
+        const auto a0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(fmaxf(acc0[2 * p] + bias, 0.f)),
+                                                         __float_as_uint(fmaxf(acc0[2 * p + 1] + bias, 0.f)), false, false);
+        const auto a1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(fmaxf(acc1[2 * p] + bias, 0.f)),
+                                                         __float_as_uint(fmaxf(acc1[2 * p + 1] + bias, 0.f)), false, false);
+        d00 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a0[0]), s0, d00, 0, 0, 0);
+        d01 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a0[1]), s0, d01, 0, 0, 0);
+        d10 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a1[0]), s1, d10, 0, 0, 0);
+        d11 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a1[1]), s1, d11, 0, 0, 0);
+    }
+    dst += (size_t)(4 * (lane >> 4)) * 16 + (lane & 15);
+    if (K == 64) {        // one group: both m-tiles
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            dst[j * 16] = d00[j] + d10[j];
+            dst[(16 + j) * 16] = d01[j] + d11[j];
+        }
+    } else {              // K == 32: m-tile 0 = the chunk's first group, m-tile 1 = the next
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            dst[j * 16] = d00[j];
+            dst[(16 + j) * 16] = d01[j];
+            dst[C3 * 16 + j * 16] = d10[j];
+            dst[C3 * 16 + (16 + j) * 16] = d11[j];
+        }
+    }
+}
+
 // One workgroup = `chunks_per_wg` consecutive 64-member chunks of one cloud (K = 32: two groups per chunk, K = 64: one).
 //   stage 0a  members' rel / sw rows -> LDS (sw transposed: swT[w][member], row 16 = zeros)      [coalesced, one chunk ahead]
 //   stage 0b  layer 1 (VALU, 4 channels per thread) + U[p] rows by 16-byte buffer loads -> act1
-//   L2, L3    fp32 MFMA as in pn2_group_kernel
+//   L2, L3    fp32 MFMA (layer 2: group_layer2_f32, iq_group_mlp.h, shared with pn2_group_kernel)
 //   contraction out[c][w] = sum_k h[k][c] sw[k][w] ON THE MFMA (v_mfma_f32_16x16x4_f32, all 16 columns = the 16 WeightNet
 //             outputs): two neighbouring accumulator registers of an L3 tile (bias + ReLU applied) hold, per 16-lane row,
 //             h[member][c] for members m, m+1 (rows 0/1: channels 0-15 / 16-31) and m+4, m+5 (rows 2/3); ONE
@@ -247,123 +324,51 @@ struct PcGroupArgs {
 //             chunk's gather travel behind the L3 MFMAs.
 template <int C1, int C2, int C3>
 __global__ __launch_bounds__(kThreads, 2) void pc_group_kernel(PcGroupArgs a) {
-    constexpr int LD1 = C1 + 4, LD2 = C2 + 4, LDS_SW = kMC + 2;   // swT row stride 66: conflict-free dword reads
+    constexpr int LD1 = C1 + 4, LD2 = C2 + 4;
     constexpr int KB1 = C1 / 8, KB2 = C2 / 8, NT2 = C2 / 32, NT3 = C3 / 32;
     static_assert(NT3 >= 4, "C3 >= 128");
-    constexpr int Q1 = C1 / 4, NR = kMC * Q1 / kThreads;
     __shared__ __attribute__((aligned(16))) float act1[kMC * LD1];
     __shared__ __attribute__((aligned(16))) float act2[kMC * LD2];
     __shared__ __attribute__((aligned(16))) float rel[2 * kMC * 4];          // dx,dy,dz, member index (bits); double-buffered
-    __shared__ __attribute__((aligned(16))) float swT[2 * 16 * LDS_SW];      // [buf][w][member]
+    __shared__ __attribute__((aligned(16))) float swT[2 * 16 * kLdsSw];      // [buf][w][member]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // 1-D grid; workgroups go round-robin over the 8 XCDs: keep all workgroups of a cloud on one XCD (one L2 holds its
-    // U rows and member records)
-    const int slot = blockIdx.x >> 3;
-    const int b = iq::xcd_cloud(blockIdx.x, a.wgs_per_cloud, a.B);
-    if (b >= a.B) return;
+    ChunkRange w;
+    if (!chunk_range(a, w)) return;
     const int K = a.K;                                   // 32 or 64
-    const int live_groups = a.n_unique ? min(a.S, a.n_unique[b]) : a.S;
-    const int chunks_total = (live_groups * K + kMC - 1) / kMC;
-    const int ch0 = (slot % a.wgs_per_cloud) * a.chunks_per_wg;
-    if (ch0 >= chunks_total) return;
-    const int nchunks = min(a.chunks_per_wg, chunks_total - ch0);
     const int fl = lane & 31, fh = lane >> 5;
     const float* a1base = act1 + fl * LD1 + 4 * fh;
     const float* a2base = act2 + fl * LD2 + 4 * fh;
     float* c2base = act2 + (4 * fh) * LD2 + fl;
     const int wave_s = uniform(wave);
     const WBuf w2b = wbuf_make(a.w2, lane), w3b = wbuf_make(a.w3, lane);
-    const size_t member0 = (size_t)b * a.S * K;          // first member record of this cloud
 
-    // B operand of the contraction: lane (w = lane & 15, k = lane >> 4) reads sw of member base + (k & 1) + 4 (k >> 1)
-    const float* swlane = swT + (lane & 15) * LDS_SW + ((lane >> 4) & 1) + 4 * (lane >> 5);
-
-    const int c4 = tid % Q1, rsub = tid / Q1;
-    f32x4 w1[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w1[e] = *reinterpret_cast<const f32x4*>(a.w1x + (c4 * 4 + e) * 4);
-    const __amdgpu_buffer_rsrc_t ursrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.U ? a.U + (size_t)b * a.N * a.ldu : a.w1x), 0, 0x7fffffff, 0x00020000);
-    f32x4 ureg[NR];
-    auto stage0a = [&](int ch, int buf) {
-        const size_t m = member0 + (size_t)(ch0 + ch) * kMC;
-        if (tid < kMC) *reinterpret_cast<f32x4*>(rel + (buf * kMC + tid) * 4) = *reinterpret_cast<const f32x4*>(a.mrel + (m + tid) * 4);
-        const int mem = tid >> 2, q4 = tid & 3;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(a.msw + (m + mem) * 16 + q4 * 4);
-        float* dst = swT + buf * 16 * LDS_SW + (q4 * 4) * LDS_SW + mem;
-        dst[0] = v[0]; dst[LDS_SW] = v[1]; dst[2 * LDS_SW] = v[2]; dst[3 * LDS_SW] = v[3];
-    };
-    auto gather_u = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const int p = __float_as_int(rel[(buf * kMC + r) * 4 + 3]);
-            if (a.U) ureg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (p * a.ldu + c4 * 4) * 4, 0, 0));
-            else ureg[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    stage0a(0, 0);
+    Stage0b<C1, kMC> s0(a.w1x, a.U, a.ldu, w.b, a.N, tid, a.U != nullptr);
+    pc_stage0a(a, w, 0, rel, swT, tid);
     __syncthreads();
-    gather_u(0);
+    s0.gather(rel);
+    const float* swlane = pc_sw_lane(swT, lane);
 
     WRing ring2, ring3;
-    for (int ch = 0; ch < nchunks; ++ch) {
+    for (int ch = 0; ch < w.nchunks; ++ch) {
         const int cur = ch & 1, nxt = cur ^ 1;
         if (NT2 >= 4) wring_prime(ring2, w2b, wave_s * KB1 * kFragBytes);   // in flight across stage 0b
         // ---- stage 0b: layer 1 -> act1 ----------------------------------------------------------------------------
 #pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4);
-            f32x4 h;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = fmaf(w1[e][2], v[2], fmaf(w1[e][1], v[1], w1[e][0] * v[0])) + w1[e][3];
-                if (a.U) t += ureg[i][e];
-                h[e] = fmaxf(t, 0.f);
-            }
-            *reinterpret_cast<f32x4*>(act1 + r * LD1 + c4 * 4) = h;
+        for (int i = 0; i < s0.NR; ++i) {
+            const int r = s0.r(i);
+            *reinterpret_cast<f32x4*>(act1 + r * LD1 + s0.c4 * 4) = s0.row(i, *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4));
         }
         __syncthreads();  // act1 complete; every wave has finished L3 of the previous chunk (act2, swT[nxt], rel[nxt] are free)
         // ---- layer 2 -------------------------------------------------------------------------------------------------
-        if (NT2 >= 4) {
-#pragma unroll
-            for (int q = 0; q < NT2 / 4; ++q) {
-                const int nt = q * 4 + wave, nts = q * 4 + wave_s;
-                f32x16 acc0 = {0}, acc1 = {0};
-                const int wq = nts * KB1 * kFragBytes;
-                const int wn = (q + 1 < NT2 / 4 ? nts + 4 : nts) * KB1 * kFragBytes;
-                mfma_ntile<LD1, KB1, 2>(a1base, w2b, wq, wn, ring2, acc0, acc1);
-                const float bias = a.b2[nt * 32 + fl];
-                float* dst = c2base + nt * 32;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    dst[c_row_i(i) * LD2] = fmaxf(acc0[i] + bias, 0.f);
-                    dst[(32 + c_row_i(i)) * LD2] = fmaxf(acc1[i] + bias, 0.f);
-                }
-            }
-        } else {
-            for (int t = wave; t < 2 * NT2; t += 4) {
-                const int mt = t / NT2, nt = t - mt * NT2;
-                f32x16 acc = {0};
-                const int wq = uniform(nt) * KB1 * kFragBytes;
-#pragma unroll 4
-                for (int kb = 0; kb < KB1; ++kb)
-                    acc = mfma4(lds_frag<LD1>(a1base + mt * 32 * LD1, 0, kb), wbuf_load(w2b, wq + kb * kFragBytes), acc);
-                const float bias = a.b2[nt * 32 + fl];
-                float* dst = c2base + mt * 32 * LD2 + nt * 32;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dst[c_row_i(i) * LD2] = fmaxf(acc[i] + bias, 0.f);
-            }
-        }
+        group_layer2_f32<C1, C2, kMC>(a1base, c2base, w2b, ring2, a.b2, wave, wave_s, fl, 2);
         wring_prime(ring3, w3b, wave_s * KB2 * kFragBytes);                 // in flight across the barrier
-        if (ch + 1 < nchunks) stage0a(ch + 1, nxt);
+        if (ch + 1 < w.nchunks) pc_stage0a(a, w, ch + 1, rel + nxt * kMC * 4, swT + nxt * 16 * kLdsSw, tid);
         __syncthreads();  // act2 complete; rel[nxt] / swT[nxt] visible
-        if (ch + 1 < nchunks) gather_u(nxt);                                // consumed after L3
+        if (ch + 1 < w.nchunks) s0.gather(rel + nxt * kMC * 4);             // consumed after L3
         // ---- layer 3 + contraction over the members (MFMA) -------------------------------------------------------------
-        const float* swc = swlane + cur * 16 * LDS_SW;
-        const int g_first = (ch0 + ch) * (kMC / K);                         // first group of this chunk
+        const float* swc = swlane + cur * 16 * kLdsSw;
+        float* og = a.out + ((size_t)w.b * a.S + (w.ch0 + ch) * (kMC / K)) * (C3 * 16);   // first group of this chunk
 #pragma unroll
         for (int q = 0; q < NT3 / 4; ++q) {
             const int nt = q * 4 + wave, nts = q * 4 + wave_s;
@@ -371,39 +376,7 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_kernel(PcGroupArgs a) {
             const int wq = nts * KB2 * kFragBytes;
             const int wn = (q + 1 < NT3 / 4 ? nts + 4 : nts) * KB2 * kFragBytes;
             mfma_ntile<LD2, KB2, 2>(a2base, w3b, wq, wn, ring3, acc0, acc1);
-            const float bias = a.b3[nt * 32 + fl];
-            // d[mt][half]: 16x16 tiles (channels nt*32 + 16 half + 4 (lane >> 4) + j, w = lane & 15) of m-tile mt
-            f32x4 d00 = {0, 0, 0, 0}, d01 = d00, d10 = d00, d11 = d00;
-#pragma unroll
-            for (int p = 0; p < 8; ++p) {      // accumulator registers 2 p, 2 p + 1: members c_row_i(2 p) + {0, 1, 4, 5}
-                const int m = c_row_i(2 * p);
-                const float s0 = swc[m], s1 = swc[32 + m];
-                const auto a0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(fmaxf(acc0[2 * p] + bias, 0.f)),
-                                                                 __float_as_uint(fmaxf(acc0[2 * p + 1] + bias, 0.f)), false, false);
-                const auto a1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(fmaxf(acc1[2 * p] + bias, 0.f)),
-                                                                 __float_as_uint(fmaxf(acc1[2 * p + 1] + bias, 0.f)), false, false);
-                d00 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a0[0]), s0, d00, 0, 0, 0);
-                d01 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a0[1]), s0, d01, 0, 0, 0);
-                d10 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a1[0]), s1, d10, 0, 0, 0);
-                d11 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a1[1]), s1, d11, 0, 0, 0);
-            }
-            const int w = lane & 15, cq = 4 * (lane >> 4);
-            float* dst = a.out + ((size_t)b * a.S + g_first) * (C3 * 16) + (size_t)(nt * 32 + cq) * 16 + w;
-            if (K == 64) {        // one group: both m-tiles
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dst[j * 16] = d00[j] + d10[j];
-                    dst[(16 + j) * 16] = d01[j] + d11[j];
-                }
-            } else {              // K == 32: m-tile 0 = group g_first, m-tile 1 = g_first + 1
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dst[j * 16] = d00[j];
-                    dst[(16 + j) * 16] = d01[j];
-                    dst[C3 * 16 + j * 16] = d10[j];
-                    dst[C3 * 16 + (16 + j) * 16] = d11[j];
-                }
-            }
+            pc_contract_tile<C3>(acc0, acc1, a.b3[nt * 32 + fl], swc, og + (size_t)(nt * 32) * 16, K, lane);
         }
     }
 }
@@ -414,138 +387,57 @@ __global__ __launch_bounds__(kThreads, 2) void pc_group_kernel(PcGroupArgs a) {
 // 2 x 2 tiles per wave.  The contraction over the members stays on v_mfma_f32_16x16x4_f32 (float32 operands straight out of the
 // accumulators).
 __global__ __launch_bounds__(kThreads, 2) void pc_group_bf3_kernel(PcGroupArgs a) {
-    constexpr int C1 = 128, C3 = 256, ROWB = 272, PLANEB = kMC * ROWB, LDS_SW = kMC + 2;
-    constexpr int Q1 = C1 / 4, NR = kMC * Q1 / kThreads;
+    constexpr int C1 = 128, C3 = 256, ROWB = 272, PLANEB = kMC * ROWB;
     __shared__ __attribute__((aligned(16))) unsigned char planes[3 * PLANEB];   // act1, then act2: three bf16 planes [64][136]
     __shared__ __attribute__((aligned(16))) float rel[2 * kMC * 4];
-    __shared__ __attribute__((aligned(16))) float swT[2 * 16 * LDS_SW];
+    __shared__ __attribute__((aligned(16))) float swT[2 * 16 * kLdsSw];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int slot = blockIdx.x >> 3;
-    const int b = iq::xcd_cloud(blockIdx.x, a.wgs_per_cloud, a.B);
-    if (b >= a.B) return;
+    ChunkRange w;
+    if (!chunk_range(a, w)) return;
     const int K = a.K;
-    const int live_groups = a.n_unique ? min(a.S, a.n_unique[b]) : a.S;
-    const int chunks_total = (live_groups * K + kMC - 1) / kMC;
-    const int ch0 = (slot % a.wgs_per_cloud) * a.chunks_per_wg;
-    if (ch0 >= chunks_total) return;
-    const int nchunks = min(a.chunks_per_wg, chunks_total - ch0);
     const int fl = lane & 31, fh = lane >> 5;
     const unsigned char* abase = planes + fl * ROWB + 16 * fh;
     const int wave_s = uniform(wave), voff = lane * 16;
     const __amdgpu_buffer_rsrc_t w2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w2_bf3), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t w3rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w3_bf3), 0, 0x7fffffff, 0x00020000);
-    const size_t member0 = (size_t)b * a.S * K;
-    const float* swlane = swT + (lane & 15) * LDS_SW + ((lane >> 4) & 1) + 4 * (lane >> 5);
 
-    const int c4 = tid % Q1, rsub = tid / Q1;
-    f32x4 w1[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w1[e] = *reinterpret_cast<const f32x4*>(a.w1x + (c4 * 4 + e) * 4);
-    const __amdgpu_buffer_rsrc_t ursrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.U ? a.U + (size_t)b * a.N * a.ldu : a.w1x), 0, 0x7fffffff, 0x00020000);
-    f32x4 ureg[NR];
-    auto stage0a = [&](int ch, int buf) {   // as pc_group_kernel
-        const size_t m = member0 + (size_t)(ch0 + ch) * kMC;
-        if (tid < kMC) *reinterpret_cast<f32x4*>(rel + (buf * kMC + tid) * 4) = *reinterpret_cast<const f32x4*>(a.mrel + (m + tid) * 4);
-        const int mem = tid >> 2, q4 = tid & 3;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(a.msw + (m + mem) * 16 + q4 * 4);
-        float* dst = swT + buf * 16 * LDS_SW + (q4 * 4) * LDS_SW + mem;
-        dst[0] = v[0]; dst[LDS_SW] = v[1]; dst[2 * LDS_SW] = v[2]; dst[3 * LDS_SW] = v[3];
-    };
-    auto gather_u = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const int p = __float_as_int(rel[(buf * kMC + r) * 4 + 3]);
-            if (a.U) ureg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (p * a.ldu + c4 * 4) * 4, 0, 0));
-            else ureg[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    stage0a(0, 0);
+    Stage0b<C1, kMC> s0(a.w1x, a.U, a.ldu, w.b, a.N, tid, a.U != nullptr);
+    pc_stage0a(a, w, 0, rel, swT, tid);
     __syncthreads();
-    gather_u(0);
+    s0.gather(rel);
+    const float* swlane = pc_sw_lane(swT, lane);
 
-    for (int ch = 0; ch < nchunks; ++ch) {
+    for (int ch = 0; ch < w.nchunks; ++ch) {
         const int cur = ch & 1, nxt = cur ^ 1;
-        B3 ring2[4];                                 // layer 2's weights (n-tile = wave), in flight across stage 0b
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ring2[i] = b3_load_at(w2rs, voff, (wave_s * 8 + i) * 1024, 4 * 8 * 1024);
+        B3 ring2[4];                                 // in flight across stage 0b
+        gb_ring2_prime(ring2, w2rs, voff, wave_s);
         // ---- stage 0b: layer 1 -> act1 (three planes) ------------------------------------------------------------------
 #pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4);
-            f32x4 h;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float t = fmaf(w1[e][2], v[2], fmaf(w1[e][1], v[1], w1[e][0] * v[0])) + w1[e][3];
-                if (a.U) t += ureg[i][e];
-                h[e] = fmaxf(t, 0.f);
-            }
-            row4_to_planes<PLANEB>(planes + r * ROWB + c4 * 8, h);
+        for (int i = 0; i < s0.NR; ++i) {
+            const int r = s0.r(i);
+            row4_to_planes<PLANEB>(planes + r * ROWB + s0.c4 * 8, s0.row(i, *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4)));
         }
         __syncthreads();  // act1 complete
         // ---- layer 2: tiles (m-tile 0..1, n-tile = wave) kept in registers ---------------------------------------------------
         f32x16 acc2[2][1] = {{{0}}, {{0}}};
         gb_layer2<2>(abase, w2rs, voff, wave_s, ring2, acc2);
-        B3x2 ring3[2];                               // layer 3's weights (n-tiles wave, wave + 4), in flight across the epilogue
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            ring3[i].b[0] = b3_load_at(w3rs, voff, (wave_s * 8 + i) * 1024, 8 * 8 * 1024);
-            ring3[i].b[1] = b3_load_at(w3rs, voff, ((wave_s + 4) * 8 + i) * 1024, 8 * 8 * 1024);
-        }
-        if (ch + 1 < nchunks) stage0a(ch + 1, nxt);
+        B3x2 ring3[2];                               // in flight across the epilogue
+        gb_ring3_prime(ring3, w3rs, voff, wave_s);
+        if (ch + 1 < w.nchunks) pc_stage0a(a, w, ch + 1, rel + nxt * kMC * 4, swT + nxt * 16 * kLdsSw, tid);
         __syncthreads();  // every wave has read act1: the image is free
-        {   // register r = channel c_row_i(r) + 4 fh of this wave's n-tile
-            f32x4 bq[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave * 32 + 8 * g + 4 * fh);
-            ct_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int r) { return fmaxf(acc2[0][0][r] + bq[r >> 2][r & 3], 0.f); });
-            ct_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane, [&](int r) { return fmaxf(acc2[1][0][r] + bq[r >> 2][r & 3], 0.f); });
-        }
+        gb_act2_store<2>(planes, a.b2, wave, lane, acc2);
         __syncthreads();  // act2 complete; rel[nxt] / swT[nxt] visible
-        if (ch + 1 < nchunks) gather_u(nxt);                                // consumed after layer 3
-        // ---- layer 3 (2 x 2 tiles per wave) + contraction over the members (fp32 MFMA, as pc_group_kernel) -------------------
+        if (ch + 1 < w.nchunks) s0.gather(rel + nxt * kMC * 4);             // consumed after layer 3
+        // ---- layer 3 (2 x 2 tiles per wave) + contraction over the members (fp32 MFMA) ---------------------------------------
         f32x16 acc3[2][2] = {{{0}, {0}}, {{0}, {0}}};
         gb_layer3<2>(abase, w3rs, voff, wave_s, ring3, acc3);
-        const float* swc = swlane + cur * 16 * LDS_SW;
-        const int g_first = (ch0 + ch) * (kMC / K);
+        const float* swc = swlane + cur * 16 * kLdsSw;
+        float* og = a.out + ((size_t)w.b * a.S + (w.ch0 + ch) * (kMC / K)) * (C3 * 16);   // first group of this chunk
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int nt = q * 4 + wave;
-            const float bias = a.b3[nt * 32 + fl];
-            f32x4 d00 = {0, 0, 0, 0}, d01 = d00, d10 = d00, d11 = d00;
-#pragma unroll
-            for (int p = 0; p < 8; ++p) {
-                const int m = c_row_i(2 * p);
-                const float s0 = swc[m], s1 = swc[32 + m];
-                const auto a0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(fmaxf(acc3[0][q][2 * p] + bias, 0.f)),
-                                                                 __float_as_uint(fmaxf(acc3[0][q][2 * p + 1] + bias, 0.f)), false, false);
-                const auto a1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(fmaxf(acc3[1][q][2 * p] + bias, 0.f)),
-                                                                 __float_as_uint(fmaxf(acc3[1][q][2 * p + 1] + bias, 0.f)), false, false);
-                d00 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a0[0]), s0, d00, 0, 0, 0);
-                d01 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a0[1]), s0, d01, 0, 0, 0);
-                d10 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a1[0]), s1, d10, 0, 0, 0);
-                d11 = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a1[1]), s1, d11, 0, 0, 0);
-            }
-            const int w = lane & 15, cq = 4 * (lane >> 4);
-            float* dst = a.out + ((size_t)b * a.S + g_first) * (C3 * 16) + (size_t)(nt * 32 + cq) * 16 + w;
-            if (K == 64) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dst[j * 16] = d00[j] + d10[j];
-                    dst[(16 + j) * 16] = d01[j] + d11[j];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    dst[j * 16] = d00[j];
-                    dst[(16 + j) * 16] = d01[j];
-                    dst[C3 * 16 + j * 16] = d10[j];
-                    dst[C3 * 16 + (16 + j) * 16] = d11[j];
-                }
-            }
+            pc_contract_tile<C3>(acc3[0][q], acc3[1][q], a.b3[nt * 32 + fl], swc, og + (size_t)(nt * 32) * 16, K, lane);
         }
         __syncthreads();  // every wave has read act2 and swT[cur]: the next chunk's stage 0b may overwrite the image
     }

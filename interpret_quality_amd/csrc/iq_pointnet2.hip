@@ -215,6 +215,93 @@ __device__ __forceinline__ void emit_tile(f32x16 acc, float bias, const int* g, 
     if (run >= 0) merge_max(orow + (size_t)run * ldo, v);
 }
 
+// ---- what pn2_group_kernel and pn2_group_bf3_kernel share ------------------------------------------------------------------
+static_assert(kThreads == kGroupThreads, "iq_group_mlp.h deals rows and channels over this workgroup");
+// The 8-row blocks [j0, jend) of cloud b that a workgroup computes.  1-D grid, workgroups round-robin over the 8 XCDs: all
+// workgroups of a cloud on one XCD (its U rows, coordinates and indices are then fetched into one L2).
+struct BlockRange {
+    int b, j0, jend;
+    const int32_t* bstart;   // this cloud's block_start
+    const uint16_t* bmap;    // this cloud's blockmap
+};
+// false: nothing to do for this workgroup
+__device__ __forceinline__ bool block_range(const GroupArgs& a, BlockRange& w) {
+    const int slot = blockIdx.x >> 3;
+    w.b = iq::xcd_cloud(blockIdx.x, a.wgs_per_cloud, a.B);
+    if (w.b >= a.B) return false;
+    w.bstart = a.block_start + (size_t)w.b * (a.S + 1);
+    const int nblocks = w.bstart[a.S];
+    w.j0 = (slot % a.wgs_per_cloud) * a.blocks_per_wg;
+    if (w.j0 >= nblocks) return false;
+    w.jend = min(nblocks, w.j0 + a.blocks_per_wg);
+    w.bmap = a.blockmap + (size_t)w.b * a.maxblocks;
+    return true;
+}
+
+// Stage 0a of chunk ch (MC rows): member -> relative coordinates + member index into relbuf, owner group of each block into
+// groupbuf (-1 = none)
+template <int MC>
+__device__ __forceinline__ void pn2_stage0a(const GroupArgs& a, const BlockRange& w, int ch, float* relbuf, int* groupbuf, int tid) {
+    if (tid < MC) {
+        int j = w.j0 + ch * (MC / kBlk) + tid / kBlk;
+        const bool live = j < w.jend;
+        if (!live) j = w.jend - 1;                   // padding blocks replicate a valid one (never emitted)
+        const int g = w.bmap[j];
+        int m = (j - w.bstart[g]) * kBlk + (tid % kBlk);
+        if (m >= a.cnt[(size_t)w.b * a.S + g]) m = 0;  // tail of the last block: copies of the first hit
+        const int p = a.idx[((size_t)w.b * a.S + g) * a.K + m];
+        const float* x = a.xyz + ((size_t)w.b * a.N + p) * a.ldx;
+        const float* c = a.new_xyz + ((size_t)w.b * a.S + g) * a.ldc;
+        f32x4 v;
+        v[0] = x[0] - c[0]; v[1] = x[1] - c[1]; v[2] = x[2] - c[2];  // rounded like the reference's `-=`
+        v[3] = __int_as_float(p);
+        *reinterpret_cast<f32x4*>(relbuf + tid * 4) = v;
+        if (tid % kBlk == 0) groupbuf[tid / kBlk] = live ? g : -1;
+    }
+}
+
+// Block maxima are not sent to memory one by one: the blocks of a group are consecutive, so each wave keeps, per n-tile
+// (slot q = n-tile q * 4 + wave), the running maximum of the group it is in and writes it when the group changes - a plain store
+// if all of the group's blocks belong to this workgroup, an atomic max only for a group that straddles a workgroup boundary.  One
+// store per group instead of one atomic per 16-row block (8x fewer for K = 128), and no atomic is in flight when stage 0b waits
+// for the gathered U rows (memory operations retire in order).
+template <int NQ>
+struct GroupMax {
+    const GroupArgs& a;
+    const BlockRange& w;
+    int lane, wave;
+    int run_g[NQ];
+    float run_v[NQ];
+    __device__ __forceinline__ GroupMax(const GroupArgs& a_, const BlockRange& w_, int lane_, int wave_)
+        : a(a_), w(w_), lane(lane_), wave(wave_) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) { run_g[q] = -1; run_v[q] = 0.f; }
+    }
+    __device__ __forceinline__ void flush(int q) const {
+        const int g = run_g[q];
+        if (g < 0 || (lane >> 5) != 0) return;
+        float* dst = a.out + ((size_t)w.b * a.S + g) * a.ldo + (q * 4 + wave) * 32 + (lane & 31);
+        if (w.bstart[g] >= w.j0 && w.bstart[g + 1] <= w.jend) *dst = run_v[q];   // sole owner (out is zero-initialised, values >= 0)
+        else merge_max(dst, run_v[q]);
+    }
+    // the maximum v of one block of group g (wave-uniform, -1 = none) for slot q
+    __device__ __forceinline__ void feed(int q, int g, float v) {
+        if (g < 0) return;
+        if (g != run_g[q]) {
+            flush(q);
+            run_g[q] = g;
+            run_v[q] = v;
+        } else {
+            run_v[q] = fmaxf(run_v[q], v);
+        }
+    }
+    // the four 8-row quarters of one accumulator tile, owned by groups g[0..3]
+    __device__ __forceinline__ void feed_tile(int q, const int* g, const TileMax& m) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) feed(q, g[i], m.v[i]);
+    }
+};
+
 // MC = rows per chunk: 64 (two 32-row MFMA tiles per weight fragment) or 32 (one tile: half the LDS and far fewer
 // registers, so twice the workgroups per CU hide each other's barriers and stage-0 phases; each weight fragment then
 // feeds 4 MFMAs instead of 8).
@@ -224,25 +311,16 @@ __global__ __launch_bounds__(kThreads, WPS) void pn2_group_kernel(GroupArgs a) {
     static_assert(MC == 64 || MC == 32, "chunk rows");
     constexpr int LD1 = C1 + 4, LD2 = C2 + 4;
     constexpr int KB1 = C1 / 8, KB2 = C2 / 8, NT2 = C2 / 32, NT3 = C3 / 32;
+    constexpr int BPC = kMC / kBlk;                                  // 8-row blocks per chunk (4 per MFMA tile)
     __shared__ __attribute__((aligned(16))) float act1[kMC * LD1];
     __shared__ __attribute__((aligned(16))) float act2[kMC * LD2];
     __shared__ __attribute__((aligned(16))) float rel[2 * kMC * 4];  // dx,dy,dz, member index (bits); double-buffered
-    __shared__ int blk_group[2 * (kMC / kBlk)];                      // owner group of a chunk's blocks (-1 = none)
+    __shared__ int blk_group[2 * BPC];                               // owner group of a chunk's blocks (-1 = none)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // 1-D grid, workgroups round-robin over the 8 XCDs: all workgroups of a cloud on one XCD (its U rows, coordinates and
-    // indices are then fetched into one L2)
-    const int slot = blockIdx.x >> 3;
-    const int b = iq::xcd_cloud(blockIdx.x, a.wgs_per_cloud, a.B);
-    if (b >= a.B) return;
-    const int K = a.K;
-    const int32_t* bstart = a.block_start + (size_t)b * (a.S + 1);
-    const int nblocks = bstart[a.S];
-    const int j0 = (slot % a.wgs_per_cloud) * a.blocks_per_wg;
-    if (j0 >= nblocks) return;
-    const int jend = min(nblocks, j0 + a.blocks_per_wg);
-    const int nchunks = (jend - j0 + (kMC / kBlk) - 1) / (kMC / kBlk);
-    const uint16_t* bmap = a.blockmap + (size_t)b * a.maxblocks;
+    BlockRange w;
+    if (!block_range(a, w)) return;
+    const int nchunks = (w.jend - w.j0 + BPC - 1) / BPC;
 
     const int fl = lane & 31, fh = lane >> 5;
     const float* a1base = act1 + fl * LD1 + 4 * fh;
@@ -252,135 +330,36 @@ __global__ __launch_bounds__(kThreads, WPS) void pn2_group_kernel(GroupArgs a) {
     // Stage 0a (member -> relative coordinates) of chunk c+1 runs before the barrier that precedes L3
     // of chunk c, and the per-point layer-1 rows U[p] of chunk c+1 are requested right after that
     // barrier, so the gather latency hides behind the L3 MFMAs.  rel / blk_group are double-buffered.
-    // stage 0b: a thread owns 4 consecutive channels (c4) of NR rows; the per-point layer-1 rows U[p] arrive as 16-byte raw
-    // buffer loads (resource on this cloud's U rows, 32-bit per-lane offsets): 4x fewer vector-memory instructions and
-    // no 64-bit address arithmetic next to the MFMAs
-    constexpr int Q1 = C1 / 4;                   // channel quads per row
-    constexpr int NR = kMC * Q1 / kThreads;      // rows per thread in stage 0b
-    const int c4 = tid % Q1, rsub = tid / Q1;
-    f32x4 w1[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w1[e] = *reinterpret_cast<const f32x4*>(a.w1x + (c4 * 4 + e) * 4);
-    const __amdgpu_buffer_rsrc_t ursrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.U ? a.U + (size_t)b * a.N * a.ldu : a.w1x), 0, 0x7fffffff, 0x00020000);
-    f32x4 ureg[NR];
-    auto stage0a = [&](int ch, int buf) {
-        if (tid < kMC) {
-            int j = j0 + ch * (kMC / kBlk) + tid / kBlk;
-            const bool live = j < jend;
-            if (!live) j = jend - 1;                 // padding blocks replicate a valid one (never emitted)
-            const int g = bmap[j];
-            int m = (j - bstart[g]) * kBlk + (tid % kBlk);
-            if (m >= a.cnt[(size_t)b * a.S + g]) m = 0;  // tail of the last block: copies of the first hit
-            const int p = a.idx[((size_t)b * a.S + g) * K + m];
-            const float* x = a.xyz + ((size_t)b * a.N + p) * a.ldx;
-            const float* c = a.new_xyz + ((size_t)b * a.S + g) * a.ldc;
-            f32x4 v;
-            v[0] = x[0] - c[0]; v[1] = x[1] - c[1]; v[2] = x[2] - c[2];  // rounded like the reference's `-=`
-            v[3] = __int_as_float(p);
-            *reinterpret_cast<f32x4*>(rel + (buf * kMC + tid) * 4) = v;
-            if (tid % kBlk == 0) blk_group[buf * (kMC / kBlk) + tid / kBlk] = live ? g : -1;
-        }
-    };
-    auto gather_u = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const int p = __float_as_int(rel[(buf * kMC + r) * 4 + 3]);
-            if (a.U) ureg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (p * a.ldu + c4 * 4) * 4, 0, 0));
-            else ureg[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    stage0a(0, 0);
+    Stage0b<C1, kMC> s0(a.w1x, a.U, a.ldu, w.b, a.N, tid, true);
+    pn2_stage0a<kMC>(a, w, 0, rel, blk_group, tid);
     __syncthreads();
-    gather_u(0);
+    s0.gather(rel);
 
-    // Block maxima are not sent to memory one by one: the blocks of a group are consecutive, so each wave keeps, per n-tile,
-    // the running maximum of the group it is in and writes it when the group changes - a plain store if all of the
-    // group's blocks belong to this workgroup, an atomic max only for a group that straddles a workgroup boundary.  One
-    // store per group instead of one atomic per 16-row block (8x fewer for K = 128), and no atomic is in flight when
-    // stage 0b waits for the gathered U rows (memory operations retire in order).
     constexpr int NQ = NT3 >= 4 ? NT3 / 4 : 1;
-    int run_g[NQ];
-    float run_v[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) { run_g[q] = -1; run_v[q] = 0.f; }
-    auto flush_group = [&](int q) {
-        const int g = run_g[q];
-        if (g < 0 || fh != 0) return;
-        float* dst = a.out + ((size_t)b * a.S + g) * a.ldo + (q * 4 + wave) * 32 + fl;
-        if (bstart[g] >= j0 && bstart[g + 1] <= jend) *dst = run_v[q];   // sole owner (out is zero-initialised, values >= 0)
-        else merge_max(dst, run_v[q]);
-    };
-    auto feed = [&](int q, int g, float v) {   // g is wave-uniform
-        if (g < 0) return;
-        if (g != run_g[q]) {
-            flush_group(q);
-            run_g[q] = g;
-            run_v[q] = v;
-        } else {
-            run_v[q] = fmaxf(run_v[q], v);
-        }
-    };
+    GroupMax<NQ> gmax(a, w, lane, wave);
     WRing ring2, ring3;
     const int wave_s = uniform(wave);
     const WBuf w2b = wbuf_make(a.w2, lane), w3b = wbuf_make(a.w3, lane);
     for (int ch = 0; ch < nchunks; ++ch) {
         const int cur = ch & 1, nxt = cur ^ 1;
-        constexpr int BPC = kMC / kBlk;            // 8-row blocks per chunk (4 per MFMA tile)
-        const int mts = (MC == 64 && (jend - (j0 + ch * BPC)) > BPC / 2) ? 2 : 1;  // second m-tile holds live blocks?
+        const int mts = (MC == 64 && (w.jend - (w.j0 + ch * BPC)) > BPC / 2) ? 2 : 1;  // second m-tile holds live blocks?
         int gq[BPC];                               // owner groups of the chunk's blocks (wave-uniform)
 #pragma unroll
         for (int i = 0; i < BPC; ++i) gq[i] = blk_group[cur * BPC + i];
         if (NT2 >= 4) wring_prime(ring2, w2b, wave_s * KB1 * kFragBytes);  // in flight across stage 0b
         // ---- stage 0b: layer 1 -> act1 -------------------------------------------------------------
 #pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4);
-            f32x4 h;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                h[e] = fmaxf(fmaf(w1[e][2], v[2], fmaf(w1[e][1], v[1], w1[e][0] * v[0])) + w1[e][3] + ureg[i][e], 0.f);
-            *reinterpret_cast<f32x4*>(act1 + r * LD1 + c4 * 4) = h;
+        for (int i = 0; i < s0.NR; ++i) {
+            const int r = s0.r(i);
+            *reinterpret_cast<f32x4*>(act1 + r * LD1 + s0.c4 * 4) = s0.row(i, *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4));
         }
         __syncthreads();  // act1 complete; every wave has finished L3 of the previous chunk (act2 is free)
         // ---- layer 2: C1 -> C2 (+bn, relu) -> act2 -------------------------------------------------
-        if (NT2 >= 4) {
-#pragma unroll
-            for (int q = 0; q < NT2 / 4; ++q) {
-                const int nt = q * 4 + wave, nts = q * 4 + wave_s;
-                f32x16 acc0 = {0}, acc1 = {0};
-                const int wq = nts * KB1 * kFragBytes;
-                const int wn = (q + 1 < NT2 / 4 ? nts + 4 : nts) * KB1 * kFragBytes;
-                if (MC == 64 && mts == 2) mfma_ntile<LD1, KB1, 2>(a1base, w2b, wq, wn, ring2, acc0, acc1);
-                else                      mfma_ntile<LD1, KB1, 1>(a1base, w2b, wq, wn, ring2, acc0, acc1);
-                const float bias = a.b2[nt * 32 + fl];
-                float* dst = c2base + nt * 32;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    dst[c_row_i(i) * LD2] = fmaxf(acc0[i] + bias, 0.f);
-                    if (MC == 64) dst[(32 + c_row_i(i)) * LD2] = fmaxf(acc1[i] + bias, 0.f);
-                }
-            }
-        } else {
-            for (int t = wave; t < mts * NT2; t += 4) {
-                const int mt = t / NT2, nt = t - mt * NT2;
-                f32x16 acc = {0};
-                const int wq = uniform(nt) * KB1 * kFragBytes;
-#pragma unroll 4
-                for (int kb = 0; kb < KB1; ++kb)
-                    acc = mfma4(lds_frag<LD1>(a1base + mt * 32 * LD1, 0, kb), wbuf_load(w2b, wq + kb * kFragBytes), acc);
-                const float bias = a.b2[nt * 32 + fl];
-                float* dst = c2base + mt * 32 * LD2 + nt * 32;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dst[c_row_i(i) * LD2] = fmaxf(acc[i] + bias, 0.f);
-            }
-        }
+        group_layer2_f32<C1, C2, MC>(a1base, c2base, w2b, ring2, a.b2, wave, wave_s, fl, mts);
         if (NT3 >= 4) wring_prime(ring3, w3b, wave_s * KB2 * kFragBytes);  // in flight across the barrier
-        if (ch + 1 < nchunks) stage0a(ch + 1, nxt);
+        if (ch + 1 < nchunks) pn2_stage0a<kMC>(a, w, ch + 1, rel + nxt * kMC * 4, blk_group + nxt * BPC, tid);
         __syncthreads();  // act2 complete; rel[nxt] visible
-        if (ch + 1 < nchunks) gather_u(nxt);  // consumed after L3
+        if (ch + 1 < nchunks) s0.gather(rel + nxt * kMC * 4);  // consumed after L3
         // ---- layer 3: C2 -> C3 (+bn, relu), block maxima merged into the owning groups ---------------
         if (NT3 >= 4) {
 #pragma unroll
@@ -392,14 +371,8 @@ __global__ __launch_bounds__(kThreads, WPS) void pn2_group_kernel(GroupArgs a) {
                 if (MC == 64 && mts == 2) mfma_ntile<LD2, KB2, 2>(a2base, w3b, wq, wn, ring3, acc0, acc1);
                 else                      mfma_ntile<LD2, KB2, 1>(a2base, w3b, wq, wn, ring3, acc0, acc1);
                 const float bias = a.b3[nt * 32 + fl];
-                const TileMax m0 = reduce_tile(acc0, bias);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) feed(q, gq[i], m0.v[i]);
-                if (MC == 64 && mts == 2) {
-                    const TileMax m1 = reduce_tile(acc1, bias);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) feed(q, gq[(BPC - 4) + i], m1.v[i]);
-                }
+                gmax.feed_tile(q, gq, reduce_tile(acc0, bias));
+                if (MC == 64 && mts == 2) gmax.feed_tile(q, gq + (BPC - 4), reduce_tile(acc1, bias));
             }
         } else {
             for (int t = wave; t < mts * NT3; t += 4) {
@@ -410,13 +383,13 @@ __global__ __launch_bounds__(kThreads, WPS) void pn2_group_kernel(GroupArgs a) {
                 for (int kb = 0; kb < KB2; ++kb)
                     acc = mfma4(lds_frag<LD2>(a2base + mt * 32 * LD2, 0, kb), wbuf_load(w3b, wq + kb * kFragBytes), acc);
                 const float bias = a.b3[nt * 32 + fl];
-                float* orow = a.out + (size_t)b * a.S * a.ldo + nt * 32 + fl;
+                float* orow = a.out + (size_t)w.b * a.S * a.ldo + nt * 32 + fl;
                 emit_tile(acc, bias, gq + (mt == 0 ? 0 : BPC - 4), orow, a.ldo, fh);
             }
         }
     }
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) flush_group(q);
+    for (int q = 0; q < NQ; ++q) gmax.flush(q);
 }
 
 // ---- the 128-128-256 scale on the bf16 matrix pipe: bf16x3, float32-exact (iq_bf3.h) ---------------------------
@@ -430,17 +403,9 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
     __shared__ int blk_group[2 * BPC];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int slot = blockIdx.x >> 3;
-    const int b = iq::xcd_cloud(blockIdx.x, a.wgs_per_cloud, a.B);
-    if (b >= a.B) return;
-    const int K = a.K;
-    const int32_t* bstart = a.block_start + (size_t)b * (a.S + 1);
-    const int nblocks = bstart[a.S];
-    const int j0 = (slot % a.wgs_per_cloud) * a.blocks_per_wg;
-    if (j0 >= nblocks) return;
-    const int jend = min(nblocks, j0 + a.blocks_per_wg);
-    const int nchunks = (jend - j0 + BPC - 1) / BPC;
-    const uint16_t* bmap = a.blockmap + (size_t)b * a.maxblocks;
+    BlockRange w;
+    if (!block_range(a, w)) return;
+    const int nchunks = (w.jend - w.j0 + BPC - 1) / BPC;
 
     const int fl = lane & 31, fh = lane >> 5;
     const unsigned char* abase = planes + fl * ROWB + 16 * fh;
@@ -449,86 +414,28 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
     // chunk = 33 400, of which the 288 MFMAs need 9 200: the other wave of the SIMD does the same, and its VALU phases do not hide
     // under this wave's MFMAs (the two share the SIMD's issue and register ports) - 0.55 MFMA-busy.
 
-    constexpr int Q1 = C1 / 4, NR = kMC * Q1 / kThreads;   // stage 0b: a thread owns 4 consecutive channels of NR rows
-    const int c4 = tid % Q1, rsub = tid / Q1;
-    f32x4 w1[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w1[e] = *reinterpret_cast<const f32x4*>(a.w1x + (c4 * 4 + e) * 4);
-    const __amdgpu_buffer_rsrc_t ursrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.U ? a.U + (size_t)b * a.N * a.ldu : a.w1x), 0, 0x7fffffff, 0x00020000);
-    f32x4 ureg[NR];
-    auto stage0a = [&](int ch, int buf) {   // as pn2_group_kernel
-        if (tid < kMC) {
-            int j = j0 + ch * BPC + tid / kBlk;
-            const bool live = j < jend;
-            if (!live) j = jend - 1;
-            const int g = bmap[j];
-            int m = (j - bstart[g]) * kBlk + (tid % kBlk);
-            if (m >= a.cnt[(size_t)b * a.S + g]) m = 0;
-            const int p = a.idx[((size_t)b * a.S + g) * K + m];
-            const float* x = a.xyz + ((size_t)b * a.N + p) * a.ldx;
-            const float* c = a.new_xyz + ((size_t)b * a.S + g) * a.ldc;
-            f32x4 v;
-            v[0] = x[0] - c[0]; v[1] = x[1] - c[1]; v[2] = x[2] - c[2];
-            v[3] = __int_as_float(p);
-            *reinterpret_cast<f32x4*>(rel + (buf * kMC + tid) * 4) = v;
-            if (tid % kBlk == 0) blk_group[buf * BPC + tid / kBlk] = live ? g : -1;
-        }
-    };
-    auto gather_u = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const int p = __float_as_int(rel[(buf * kMC + r) * 4 + 3]);
-            if (a.U) ureg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ursrc, (p * a.ldu + c4 * 4) * 4, 0, 0));
-            else ureg[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    stage0a(0, 0);
+    Stage0b<C1, kMC> s0(a.w1x, a.U, a.ldu, w.b, a.N, tid, true);
+    pn2_stage0a<kMC>(a, w, 0, rel, blk_group, tid);
     __syncthreads();
-    gather_u(0);
+    s0.gather(rel);
 
-    int run_g[2] = {-1, -1};
-    float run_v[2] = {0.f, 0.f};
-    auto flush_group = [&](int q) {   // as pn2_group_kernel: one store per group, an atomic max only across workgroups
-        const int g = run_g[q];
-        if (g < 0 || fh != 0) return;
-        float* dst = a.out + ((size_t)b * a.S + g) * a.ldo + (q * 4 + wave) * 32 + fl;
-        if (bstart[g] >= j0 && bstart[g + 1] <= jend) *dst = run_v[q];
-        else merge_max(dst, run_v[q]);
-    };
-    auto feed = [&](int q, int g, float v) {
-        if (g < 0) return;
-        if (g != run_g[q]) {
-            flush_group(q);
-            run_g[q] = g;
-            run_v[q] = v;
-        } else {
-            run_v[q] = fmaxf(run_v[q], v);
-        }
-    };
+    GroupMax<2> gmax(a, w, lane, wave);
     const int wave_s = uniform(wave), voff = lane * 16;
     const __amdgpu_buffer_rsrc_t w2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w2_bf3), 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t w3rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(a.w3_bf3), 0, 0x7fffffff, 0x00020000);
     for (int ch = 0; ch < nchunks; ++ch) {
         const int cur = ch & 1, nxt = cur ^ 1;
-        const int mts = (jend - (j0 + ch * BPC)) > BPC / 2 ? 2 : 1;
+        const int mts = (w.jend - (w.j0 + ch * BPC)) > BPC / 2 ? 2 : 1;
         int gq[BPC];
 #pragma unroll
         for (int i = 0; i < BPC; ++i) gq[i] = blk_group[cur * BPC + i];
-        B3 ring2[4];                                 // layer 2's weights (n-tile = wave), in flight across stage 0b
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ring2[i] = b3_load_at(w2rs, voff, (wave_s * 8 + i) * 1024, 4 * 8 * 1024);
+        B3 ring2[4];                                 // in flight across stage 0b
+        gb_ring2_prime(ring2, w2rs, voff, wave_s);
         // ---- stage 0b: layer 1 -> act1 (three planes) ----------------------------------------------------
 #pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const int r = rsub + i * (kThreads / Q1);
-            const f32x4 v = *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4);
-            f32x4 h;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                h[e] = fmaxf(fmaf(w1[e][2], v[2], fmaf(w1[e][1], v[1], w1[e][0] * v[0])) + w1[e][3] + ureg[i][e], 0.f);
-            row4_to_planes<PLANEB>(planes + r * ROWB + c4 * 8, h);
+        for (int i = 0; i < s0.NR; ++i) {
+            const int r = s0.r(i);
+            row4_to_planes<PLANEB>(planes + r * ROWB + s0.c4 * 8, s0.row(i, *reinterpret_cast<const f32x4*>(rel + (cur * kMC + r) * 4)));
         }
         __syncthreads();  // act1 complete
         // ---- layer 2: 128 -> 128, tiles (m-tile 0..1, n-tile = wave) kept in registers -------------------
@@ -540,54 +447,35 @@ __global__ __launch_bounds__(kThreads, 2) void pn2_group_bf3_kernel(GroupArgs a)
             gb_layer2<1>(abase, w2rs, voff, wave_s, ring2, one);
             acc2[0][0] = one[0][0];
         }
-        B3x2 ring3[2];                               // layer 3's weights (n-tiles wave, wave + 4), in flight across the epilogue
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            ring3[i].b[0] = b3_load_at(w3rs, voff, (wave_s * 8 + i) * 1024, 8 * 8 * 1024);
-            ring3[i].b[1] = b3_load_at(w3rs, voff, ((wave_s + 4) * 8 + i) * 1024, 8 * 8 * 1024);
-        }
-        if (ch + 1 < nchunks) stage0a(ch + 1, nxt);
+        B3x2 ring3[2];                               // in flight across the epilogue
+        gb_ring3_prime(ring3, w3rs, voff, wave_s);
+        if (ch + 1 < nchunks) pn2_stage0a<kMC>(a, w, ch + 1, rel + nxt * kMC * 4, blk_group + nxt * BPC, tid);
         __syncthreads();  // every wave has read act1: the image is free
-        {   // register r = channel c_row_i(r) + 4 fh of this wave's n-tile: the biases of the lane's 16 channels
-            f32x4 bq[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave * 32 + 8 * g + 4 * fh);
-            ct_tile_to_planes<ROWB, PLANEB>(planes + wave * 64, lane, [&](int r) { return fmaxf(acc2[0][0][r] + bq[r >> 2][r & 3], 0.f); });
-            if (mts == 2)
-                ct_tile_to_planes<ROWB, PLANEB>(planes + 32 * ROWB + wave * 64, lane,
-                                                [&](int r) { return fmaxf(acc2[1][0][r] + bq[r >> 2][r & 3], 0.f); });
-        }
+        if (mts == 2) gb_act2_store<2>(planes, a.b2, wave, lane, acc2);
+        else          gb_act2_store<1>(planes, a.b2, wave, lane, acc2);
         __syncthreads();  // act2 complete; rel[nxt] visible
-        if (ch + 1 < nchunks) gather_u(nxt);  // consumed after layer 3
+        if (ch + 1 < nchunks) s0.gather(rel + nxt * kMC * 4);  // consumed after layer 3
         // ---- layer 3: 128 -> 256, 2 x 2 tiles per wave, block maxima merged into the owning groups -------
         if (mts == 2) {
             f32x16 acc3[2][2] = {{{0}, {0}}, {{0}, {0}}};
-                gb_layer3<2>(abase, w3rs, voff, wave_s, ring3, acc3);
-    #pragma unroll
+            gb_layer3<2>(abase, w3rs, voff, wave_s, ring3, acc3);
+#pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const float bias = a.b3[(q * 4 + wave) * 32 + fl];
-                const TileMax m0 = reduce_tile(acc3[0][q], bias);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) feed(q, gq[i], m0.v[i]);
-                const TileMax m1 = reduce_tile(acc3[1][q], bias);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) feed(q, gq[(BPC - 4) + i], m1.v[i]);
+                gmax.feed_tile(q, gq, reduce_tile(acc3[0][q], bias));
+                gmax.feed_tile(q, gq + (BPC - 4), reduce_tile(acc3[1][q], bias));
             }
         } else {
             f32x16 acc3[1][2] = {{{0}, {0}}};
-                gb_layer3<1>(abase, w3rs, voff, wave_s, ring3, acc3);
-    #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float bias = a.b3[(q * 4 + wave) * 32 + fl];
-                const TileMax m0 = reduce_tile(acc3[0][q], bias);
+            gb_layer3<1>(abase, w3rs, voff, wave_s, ring3, acc3);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) feed(q, gq[i], m0.v[i]);
-            }
+            for (int q = 0; q < 2; ++q)
+                gmax.feed_tile(q, gq, reduce_tile(acc3[0][q], a.b3[(q * 4 + wave) * 32 + fl]));
         }
         __syncthreads();  // every wave has read act2: the next chunk's stage 0b may overwrite the image
     }
-    flush_group(0);
-    flush_group(1);
+    gmax.flush(0);
+    gmax.flush(1);
 }
 
 // rows s >= n_unique[b] := row 0 (duplicate centroids), columns [c0, c0+ncols)
