@@ -43,7 +43,9 @@ int iq_profile_read_work(int slot, double* total_ms, int* launches, double* tota
  *   5    54, 55, 58  PointNet chain layer 3 on the fp32 MFMA (55: without the 16-row tail tiles) / one n-tile per pass
  *   5    56, 64      fp32-MFMA grouped kernels (32- / 64-row chunks; PointConv: 56)
  *   5    57          dense layers on the fp32 MFMA
- *   5    59          bf16x3 dense layers with 128-row tiles only (the launch before the short tiles; bit-identical results) */
+ *   5    59          bf16x3 dense layers with 128-row tiles only (the launch before the short tiles; bit-identical results)
+ *   5    60          PointNet coalition chains run every repeated full / empty set of a batch instead of copying the first one's
+ *                    rows (pn_dup_copy_kernel; bit-identical results) */
 int iq_set_tuning(int key, int value);
 int iq_profile_read(int slot, double* total_ms, int* launches);
 

@@ -56,7 +56,8 @@ extern "C" int iq_set_tuning(int key, int value) {
             case 0: case iq::kTwinEdgeGemmL2: case iq::kTwinEdgeGemmLds: case iq::kTwinKnnCompact: case iq::kTwinPcKnn:
             case iq::kTwinPcGroupedMlp: case iq::kTwinKnnFp32Rank: case iq::kTwinPn2MemberWalk: case iq::kTwinKnnFp32Mfma:
             case iq::kTwinPcTwoKernel: case iq::kTwinChainL3Fp32: case iq::kTwinChainL3Fp32NoTail16: case iq::kTwinGroupFp32:
-            case iq::kTwinDenseFp32: case iq::kTwinChainL3Single: case iq::kTwinDenseTile128: case iq::kTwinGroupFp32Chunk64:
+            case iq::kTwinDenseFp32: case iq::kTwinChainL3Single: case iq::kTwinDenseTile128: case iq::kTwinChainNoDedup:
+            case iq::kTwinGroupFp32Chunk64:
                 iq::ts().twin = value;
                 return IQ_OK;
         }

@@ -30,7 +30,7 @@ inline int check_launch(const char* what) {
 
 inline hipStream_t as_stream(iq_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+constexpr size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Bit `rid` of a coalition's keep mask; a region id outside [0, 64) (which iq_check_index_range rejects) is never kept,
 // so an unvalidated id gives a defined result instead of an undefined shift.

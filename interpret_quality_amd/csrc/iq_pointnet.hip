@@ -77,6 +77,8 @@ struct ChainArgs {
     const unsigned short* w2_bf3;   // layer 2's, likewise (L3V = 3 needs both)
     float* out;                // (items,1024)
     int32_t* argrow;           // (items,1024) point index of the row that attains each column maximum, or null [ARGMAX trunk only]
+    const int32_t* dup_rep;    // [2] first full-set / first empty-set item of the batch, or null: the other such items are copies of
+                               // it and leave at once (pn_dup_rep_kernel, pn_dup_copy_kernel)              [kFstn/kTrunk]
     int N, R, items, nclouds, with_centre;
     int tail16;                  // last m-tile of an item on 16x16x4 MFMAs when it holds at most 16 rows (l3_tail16)
     int l3_single;               // twin kTwinChainL3Single: the 64-row bf16x3 kernel, one n-tile per pass (launch_chain; the 96-row kernel's reference)
@@ -434,6 +436,11 @@ __device__ __forceinline__ void l1_bf3(const unsigned char* act0, unsigned char*
     }
 }
 
+// Coalitions that recur in a batch: every permutation of a Shapley sample contributes the full set (prefix R) and the empty set
+// (prefix 0), 2 of its R + 1 coalitions, and all full sets of a cloud are the same rows under the same transforms.  nrows tells
+// both: all N points and no centre row (nothing masked) -> 0, the centre row alone -> 1, anything else -> -1.
+__device__ __forceinline__ int dup_kind(int nrows_word, int N) { return nrows_word == N ? 0 : nrows_word == ((1 << 16) | 1) ? 1 : -1; }
+
 // CM = ChainMode; MODE = the chain it names, MC = rows per chunk: 96 in the two product instantiations <kFstn | kTrunk, 3, false>, else 64
 template <int CM, int L3V, bool ARGMAX = false>
 __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(ChainArgs a) {
@@ -455,6 +462,10 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     else cloud = a.cloud_of ? a.cloud_of[item] : (a.nclouds == 1 ? 0 : item);
 
     const int nrows = a.nrows[item] & 0xffff;
+    if (MODE != kPrepool && a.dup_rep) {   // a repeated full or empty set: pn_dup_copy_kernel fills its row from the first one's
+        const int kind = dup_kind(a.nrows[item], N);
+        if (kind >= 0 && a.dup_rep[kind] != item) return;
+    }
     float* outp = a.out + (size_t)item * kFeat;
     if (nrows == 0) {  // empty region in the pre-pool: identity of max
         for (int c = tid; c < kFeat; c += kThreads) outp[c] = -INFINITY;
@@ -1263,6 +1274,39 @@ __global__ __launch_bounds__(kOrderThreads) void pn_order_fused_kernel(const int
     }
 }
 
+// ---- repeated full and empty sets (one cloud per call): the first of each kind is computed, the others copy its chain output ----
+constexpr int kDupRepOff = kBins;   // rep[2] lives in the padding behind the launch-order histogram: workspace sizes stay what they were
+static_assert(iq::align_up((kBins + 2) * sizeof(int32_t), 256) == iq::align_up(kBins * sizeof(int32_t), 256), "room behind hist");
+
+__global__ __launch_bounds__(kOrderThreads) void pn_dup_rep_kernel(const int32_t* __restrict__ nrows_all, int32_t* __restrict__ rep,
+                                                                   int B, int N) {
+    __shared__ int first[2];
+    if (threadIdx.x < 2) first[threadIdx.x] = B;
+    __syncthreads();
+    for (int item = threadIdx.x; item < B; item += kOrderThreads) {
+        const int kind = dup_kind(nrows_all[item], N);
+        if (kind >= 0) atomicMin(&first[kind], item);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) rep[threadIdx.x] = first[threadIdx.x];
+}
+
+// after a chain launch: row `item` of out (and of argrow, if any) = the row of the first item of its kind
+__global__ __launch_bounds__(kThreads) void pn_dup_copy_kernel(const int32_t* __restrict__ nrows_all, const int32_t* __restrict__ rep,
+                                                               float* __restrict__ out, int32_t* __restrict__ argrow, int N) {
+    const int item = blockIdx.x;
+    const int kind = dup_kind(nrows_all[item], N);
+    if (kind < 0) return;
+    const int src = rep[kind];
+    if (src == item) return;
+    static_assert(kFeat == 4 * kThreads, "one float4 per thread");
+    reinterpret_cast<f32x4*>(out + (size_t)item * kFeat)[threadIdx.x] = reinterpret_cast<const f32x4*>(out + (size_t)src * kFeat)[threadIdx.x];
+    if (argrow) {
+        const int4 v = reinterpret_cast<const int4*>(argrow + (size_t)src * kFeat)[threadIdx.x];
+        reinterpret_cast<int4*>(argrow + (size_t)item * kFeat)[threadIdx.x] = v;
+    }
+}
+
 // ---- pooled input-STN feature of a coalition: max over kept regions (+ centre) -------------
 __global__ __launch_bounds__(kThreads) void pn_stn_gather_kernel(const float* __restrict__ G,
                                                                  const int32_t* __restrict__ nrows_all,
@@ -1460,7 +1504,7 @@ Workspace carve(void* base, int B, int nclouds, int N, int R, int roff_entries =
     w.nrows = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
     w.order = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
     w.bin_of = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-    w.hist = reinterpret_cast<int32_t*>(take((size_t)kBins * sizeof(int32_t)));
+    w.hist = reinterpret_cast<int32_t*>(take((size_t)(kBins + 2) * sizeof(int32_t)));   // + pn_dup_rep_kernel's two
     w.G = reinterpret_cast<float*>(take((size_t)nclouds * (R + 1) * kFeat * sizeof(float)));
     w.gbuf = reinterpret_cast<float*>(take((size_t)B * kFeat * sizeof(float)));
     w.h1 = reinterpret_cast<float*>(take((size_t)B * 512 * sizeof(float)));
@@ -1568,6 +1612,13 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
                            ws.bin_of, ws.hist, ws.order, B);
     }
     if ((rc = iq::check_launch("pn_order kernels"))) return rc;
+    // repeated full / empty sets: one cloud and keep masks in table order only (a prefix route's row lists follow its permutations)
+    const int32_t* dup_rep = nullptr;
+    if (nclouds == 1 && !wide_words && B > 1 && iq::twin() != iq::kTwinChainNoDedup) {
+        hipLaunchKernelGGL(pn_dup_rep_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.hist + kDupRepOff, B, N);
+        if ((rc = iq::check_launch("pn_dup_rep_kernel"))) return rc;
+        dup_rep = ws.hist + kDupRepOff;
+    }
 
     ChainArgs a{};
     a.clouds = clouds;
@@ -1615,6 +1666,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     a.cloud_of = item_cloud; a.trans = ws.trans;
     a.rows = ws.rows; a.nrows = ws.nrows;
     a.item_order = ws.order;
+    a.dup_rep = dup_rep;
     a.w_in = w->feat_in;
     a.items = B;
     a.out = ws.gbuf;
@@ -1628,6 +1680,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
             iq::ProfileSpan span(iq::kSlotFstn, st);
             launch_chain<kFstn>(a, st);
         }
+        if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, ws.nrows, dup_rep, ws.gbuf, nullptr, N);
         if ((rc = iq::check_launch("pn_chain_kernel<fstn>"))) return rc;
         if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
         if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
@@ -1661,6 +1714,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         iq::ProfileSpan span(iq::kSlotTrunk, st);
         launch_chain<kTrunk>(a, st);
     }
+    if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, ws.nrows, dup_rep, ws.gbuf, crt_points, N);
     if ((rc = iq::check_launch("pn_chain_kernel<trunk>"))) return rc;
     if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
     if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
