@@ -158,7 +158,7 @@ __device__ __forceinline__ int b16_lane_off(int lane) {
 // (256-byte rows) or (r >> 1) & 7 (128-byte rows: two rows share a 256-byte bank line).  The 16x16x32 read (row c, piece 4 t + kq)
 // is then conflict-free: a ds_read_b128 lane group holds rows {0-3, 12-15} of one kq and rows {4-11} of the next, the XOR maps both
 // sets onto disjoint sixteen-byte bank groups (with padded rows that pattern is 2-way conflicted).  The planes' only writers are
-// stage 0b (act0: stage0b_planes, iq_pointnet.hip) and the epilogues of layers 1 and 2 (c16_tile_to_planes_swz).  a16_lane_off: the per-lane byte offset of k-step
+// stage 0b (act0: stage0b_planes, iq_pointnet_chain.h) and the epilogues of layers 1 and 2 (c16_tile_to_planes_swz).  a16_lane_off: the per-lane byte offset of k-step
 // 0; k-step t is that offset ^ (64 t).
 template <int ROWB>
 __device__ __forceinline__ int swz_of_row(int row) {

@@ -1,4 +1,5 @@
-"""GPU: the 96-row chunks of the PointNet chain kernel's product instantiations (csrc/iq_pointnet.hip, kFstn96 / kTrunk96).
+"""GPU: the 96-row chunks of the PointNet chain kernel's product instantiations (csrc/iq_pointnet_chain.h, chain_bf3_96:
+pn_chain_kernel<kFstn | kTrunk, 3, false>; the 64-row twins are the modes kFstn64 / kTrunk64).
 
 The cases are coalitions whose row counts sit on every edge of the 32-row m-tiles and of the 96-row chunks: 1, 31, 32, 33, 63, 64,
 65, 95, 96, 97, 127, 128, 129, 159, 160, 161, 191, 192, 193 rows and the full cloud (1024 rows: ten full chunks and a 64-row
@@ -100,6 +101,36 @@ def test_dense_forward_equals_the_coalition_path(model, case, batch):
     logits = model(dense)[0]                                            # (B,3,1024) materialised clouds, 64-row arg-max kernel
     for i, r in enumerate(case["rows"]):
         assert torch.equal(logits[i], batch[0][i]), "coalition %d (%d rows)" % (i, r)
+
+
+def test_argmax_trunks_equal_their_plain_twins_and_name_kept_points(model, case, batch):
+    """The arg-max trunks against the trunks without arg-max, logits bit for bit: pn_chain_kernel<kTrunk, 2, true> against
+    <kTrunk, 2, false> with its 16-row tails (tuning 5 = 54, documented bit-identical), and in the product path <kTrunk, 3, true>
+    (64-row chunks) against <kTrunk, 3, false> (96-row chunks).  Every arg-max index is a kept point of its coalition, or N (the
+    centre) in a coalition that has a centre row; the coalition of the centre alone names nothing else."""
+    from interpret_quality_amd import _lib
+    eng = model.engine()
+    run = lambda **kw: eng.coalition_logits(case["data"], case["center"], case["rid"], case["keep_t"], None, num_regions=case["nreg"], **kw)
+    lib = _lib.load()
+    try:
+        lib.iq_set_tuning(5, 54)
+        f32 = run()
+        f32_arg, crt_f32 = run(return_crt=True)
+    finally:
+        lib.iq_set_tuning(5, 0)
+    bf3_arg, crt_bf3 = run(return_crt=True)
+    assert torch.equal(f32_arg, f32)
+    assert torch.equal(bf3_arg, batch[0])
+    assert not torch.equal(f32, batch[0])                             # two different pairs of kernels did run
+    n, rid = case["data"].shape[1], case["rid"][0].long()
+    for name, crt in (("fp32", crt_f32), ("bf16x3", crt_bf3)):
+        for i, k in enumerate(case["keep"]):
+            in_k = torch.tensor([(k >> r) & 1 for r in range(case["nreg"])], dtype=torch.bool, device=rid.device)
+            allowed = torch.cat([in_k[rid], torch.tensor([bool(case["rows"][i] < n)], device=rid.device)])   # entry N: the centre row
+            idx = crt[i].long()
+            assert ((idx >= 0) & (idx <= n)).all(), "%s, coalition %d (%d rows)" % (name, i, case["rows"][i])
+            assert allowed[idx].all(), "%s, coalition %d (%d rows)" % (name, i, case["rows"][i])
+        assert (crt[0] == n).all(), name                              # coalition 0 keeps nothing: the centre alone
 
 
 def _cloud(seed, n):

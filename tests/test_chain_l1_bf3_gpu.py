@@ -1,4 +1,4 @@
-"""GPU: layer 1 of the PointNet chain kernel's bf16x3 instantiations on v_mfma_f32_16x16x32_bf16 (csrc/iq_pointnet.hip: l1_bf3,
+"""GPU: layer 1 of the PointNet chain kernel's bf16x3 instantiations on v_mfma_f32_16x16x32_bf16 (csrc/iq_pointnet_chain.h: l1_bf3,
 stage0b_planes; every pn_chain_kernel<*, 3, *>).  One 200-point cloud, five regions (tests/chain_l1_cases.py).
 
 (a) Wide-range layer-1 weights, seeds chain_l1_cases.SEEDS (0, 1, 2: every seed tried was kept): feat.fstn.conv1 with per-entry

@@ -1,4 +1,4 @@
-"""GPU: layer 3 of the PointNet chain kernel on v_mfma_f32_16x16x32_bf16 (csrc/iq_pointnet.hip, l3_pass_bf3 / l3_pass_bf3_2x2).
+"""GPU: layer 3 of the PointNet chain kernel on v_mfma_f32_16x16x32_bf16 (csrc/iq_pointnet_chain.h, l3_pass_bf3 / l3_pass_bf3_2x2).
 
 The m-tiles are 16 rows now and a column's rows are spread over four lane groups, so the cases are coalitions whose row counts
 cover every residue mod 16 and the chunk edges: 1, 15, 16, 17, 31, 32, 33, 63, 64, 65 rows (and 2 .. 14), and the full cloud
