@@ -62,8 +62,9 @@ enum {
  * iq_dgcnn_coalitions_wide, iq_pointnet2_coalitions_wide, iq_pointconv_coalitions_wide, iq_pointconv_coalitions_cached_wide).
  * 109: new entry points, no layout change (iq_split_packed_weight_bf3, iq_split_packed_weight_bf3_host); the PointNet workspaces
  * grew by the bf16x3 image of fstn.fc3 (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes).
- * 110: one new entry point, no layout change (iq_smoothness_enum_wide: the smoothness enumeration of a wide game). */
-#define IQ_ABI_VERSION 111
+ * 110: one new entry point, no layout change (iq_smoothness_enum_wide: the smoothness enumeration of a wide game).
+ * 112: one new diagnostic entry point, no layout change and no workspace size changed (iq_debug.h: iq_debug_pointnet_reps). */
+#define IQ_ABI_VERSION 112
 int iq_version(void);
 const char* iq_last_error(void);
 

@@ -44,8 +44,8 @@ int iq_profile_read_work(int slot, double* total_ms, int* launches, double* tota
  *   5    56, 64      fp32-MFMA grouped kernels (32- / 64-row chunks; PointConv: 56)
  *   5    57          dense layers on the fp32 MFMA
  *   5    59          bf16x3 dense layers with 128-row tiles only (the launch before the short tiles; bit-identical results)
- *   5    60          PointNet coalition chains run every repeated full / empty set of a batch instead of copying the first one's
- *                    rows (pn_dup_copy_kernel; bit-identical results) */
+ *   5    60          PointNet coalition chains run every repeated coalition of a batch instead of copying the first one's rows
+ *                    (no representatives are sought, pn_dup_copy_kernel does not run; bit-identical results) */
 int iq_set_tuning(int key, int value);
 int iq_profile_read(int slot, double* total_ms, int* launches);
 
@@ -62,6 +62,15 @@ int iq_debug_mfma_sustained(double seconds, float* scratch /*device*/, size_t sc
  * draw different power per FLOP: tools/chain_shape_probe.py alternates them.  Any other shape: IQ_EINVAL. */
 int iq_debug_mfma_sustained_shape(int shape, double seconds, float* scratch /*device*/, size_t scratch_floats, double* tflops /*host*/,
                                   double* clock_ghz /*host or NULL*/, iq_stream_t stream);
+
+/* Diagnostic: the representatives iq_pointnet_coalitions finds in a batch of keep masks before its chains run - the same launches
+ * from the same launcher, with the caller's scratch in place of the workspace.  rep_out[i] = the lowest j <= i with
+ * cloud_of[j] == cloud_of[i] (NULL: one cloud, nclouds must be 1) and (keep[j] ^ keep[i]) clear in its low R bits; items with
+ * rep_out[i] != i are the ones whose chain output the forward copies from row rep_out[i].  keep (B) uint64, cloud_of (B) int32 or
+ * NULL, rep_out (B) int32: device.  scratch: device, 4 bytes times the smallest power of two >= max(4, 2 B) - 16 * max(B, 1) bytes
+ * always suffice; less is IQ_EWORKSPACE.  No synchronisation. */
+int iq_debug_pointnet_reps(const uint64_t* keep /*device*/, const int32_t* cloud_of /*device or NULL*/, int B, int nclouds, int R,
+                           int32_t* rep_out /*device*/, void* scratch /*device*/, size_t scratch_bytes, iq_stream_t stream);
 
 #ifdef __cplusplus
 }

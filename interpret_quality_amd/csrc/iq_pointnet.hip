@@ -440,30 +440,90 @@ __global__ __launch_bounds__(kOrderThreads) void pn_order_fused_kernel(const int
     }
 }
 
-// ---- repeated full and empty sets (one cloud per call): the first of each kind is computed, the others copy its chain output ----
-constexpr int kDupRepOff = kBins;   // rep[2] lives in the padding behind the launch-order histogram: workspace sizes stay what they were
-static_assert(iq::align_up((kBins + 2) * sizeof(int32_t), 256) == iq::align_up(kBins * sizeof(int32_t), 256), "room behind hist");
-
-__global__ __launch_bounds__(kOrderThreads) void pn_dup_rep_kernel(const int32_t* __restrict__ nrows_all, int32_t* __restrict__ rep,
-                                                                   int B, int N) {
-    __shared__ int first[2];
-    if (threadIdx.x < 2) first[threadIdx.x] = B;
-    __syncthreads();
-    for (int item = threadIdx.x; item < B; item += kOrderThreads) {
-        const int kind = dup_kind(nrows_all[item], N);
-        if (kind >= 0) atomicMin(&first[kind], item);
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) rep[threadIdx.x] = first[threadIdx.x];
+// ---- repeated coalitions of a batch: the first item of every (cloud, keep mask) is computed, the others copy its chain output ----
+// rep[i] = the lowest item j <= i on i's cloud with the same kept regions (the mask's low R bits, as pn_stn_gather_kernel forms them):
+// the same row list in table order under the same transforms, so whichever member computes, the row is the same; the lowest makes rep
+// independent of timing and rep[rep[i]] == rep[i].  An open-addressing table of item indices, cleared to -1, at most half full:
+// pn_rep_insert_kernel claims a slot per distinct key (atomicCAS; a slot always holds SOME member of its group, so a later item
+// compares keys through it and probes on if they differ) and keeps the group's lowest index there (atomicMin); it leaves each
+// item's slot in rep, and pn_rep_write_kernel replaces the slot by what it holds.  The launch boundary orders the two phases.
+__host__ __device__ inline size_t rep_slots(int B) {   // a power of two >= 2 B
+    size_t s = 4;
+    while (s < 2 * (size_t)B) s <<= 1;
+    return s;
 }
 
-// after a chain launch: row `item` of out (and of argrow, if any) = the row of the first item of its kind
-__global__ __launch_bounds__(kThreads) void pn_dup_copy_kernel(const int32_t* __restrict__ nrows_all, const int32_t* __restrict__ rep,
-                                                               float* __restrict__ out, int32_t* __restrict__ argrow, int N) {
+__device__ __forceinline__ uint32_t rep_hash(uint64_t k, int cloud) {
+    uint64_t x = k * 0x9E3779B97F4A7C15ull + (uint64_t)(uint32_t)cloud * 0xC2B2AE3D27D4EB4Full;
+    x ^= x >> 29;
+    x *= 0xBF58476D1CE4E5B9ull;
+    return (uint32_t)(x >> 32);
+}
+
+__global__ __launch_bounds__(kThreads) void pn_rep_insert_kernel(const uint64_t* __restrict__ keep, const int32_t* __restrict__ cloud_of,
+                                                                 int32_t* table, int32_t* __restrict__ rep, int B, int R,
+                                                                 uint32_t slot_mask) {
+    const int item = blockIdx.x * kThreads + threadIdx.x, lane = threadIdx.x & 63;
+    const bool live = item < B;
+    const uint64_t full = R >= 64 ? ~0ull : ((1ull << R) - 1);
+    const uint64_t k = live ? keep[item] & full : 0;
+    const int cloud = live && cloud_of ? cloud_of[item] : 0;
+    // equal keys inside a wave go through their lowest lane (= lowest item): a batch of B copies of one mask then costs B / 64
+    // atomics on its slot instead of B.  A Shapley batch has close to 64 keys per wave, hence 64 rounds: l is wave-uniform, so
+    // the leader's key comes by v_readlane, not through the LDS crossbar of __shfl
+    const int k_lo = (int)(uint32_t)k, k_hi = (int)(uint32_t)(k >> 32);
+    int leader = lane;
+    for (uint64_t todo = __ballot(live); todo;) {
+        const int l = __ffsll((unsigned long long)todo) - 1;
+        const bool same = live && k_lo == __builtin_amdgcn_readlane(k_lo, l) && k_hi == __builtin_amdgcn_readlane(k_hi, l) &&
+                          cloud == __builtin_amdgcn_readlane(cloud, l);
+        if (same) leader = l;
+        todo &= ~__ballot(same);
+    }
+    int slot = 0;
+    if (live && leader == lane) {
+        uint32_t h = rep_hash(k, cloud) & slot_mask;
+        for (;;) {   // at most B of >= 2 B slots are ever claimed: an empty one is always ahead
+            // a plain look first: a slot only ever goes from -1 to a member of one group and then down inside it, so whatever
+            // the load returns, however old, is still a valid witness - and a lower member there needs no atomic at all (the
+            // full and the empty set of a Shapley sample would otherwise queue two atomics per wave on two addresses)
+            int old = __atomic_load_n(&table[h], __ATOMIC_RELAXED);
+            if (old == -1) old = atomicCAS(&table[h], -1, item);
+            if (old == -1) break;
+            if ((keep[old] & full) == k && (cloud_of ? cloud_of[old] : 0) == cloud) {
+                if (item < old) atomicMin(&table[h], item);
+                break;
+            }
+            h = (h + 1) & slot_mask;
+        }
+        slot = (int)h;
+    }
+    slot = __shfl(slot, leader);
+    if (live) rep[item] = slot;
+}
+
+__global__ __launch_bounds__(kThreads) void pn_rep_write_kernel(const int32_t* __restrict__ table, int32_t* __restrict__ rep, int B) {
+    const int item = blockIdx.x * kThreads + threadIdx.x;
+    if (item < B) rep[item] = table[rep[item]];
+}
+
+// rep (B) from keep (B) and cloud_of (B, or null: one cloud); table: rep_slots(B) int32 of scratch.  The same three launches for
+// every B: one workgroup with the table in LDS took 40 us on a pose-sized batch against 26 us for these (profiles/chain_repeats_ab.txt)
+int launch_reps(const uint64_t* keep, const int32_t* cloud_of, int B, int R, int32_t* rep, int32_t* table, hipStream_t st) {
+    const size_t slots = rep_slots(B);
+    if (hipMemsetAsync(table, 0xff, slots * sizeof(int32_t), st) != hipSuccess)
+        return iq::fail(IQ_ELAUNCH, "pn_rep kernels: memset failed");
+    const dim3 grid((B + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(pn_rep_insert_kernel, grid, dim3(kThreads), 0, st, keep, cloud_of, table, rep, B, R, (uint32_t)(slots - 1));
+    hipLaunchKernelGGL(pn_rep_write_kernel, grid, dim3(kThreads), 0, st, table, rep, B);
+    return iq::check_launch("pn_rep kernels");
+}
+
+// after a chain launch: row `item` of out (and of argrow, if any) = the row of its representative
+__global__ __launch_bounds__(kThreads) void pn_dup_copy_kernel(const int32_t* __restrict__ rep, float* __restrict__ out,
+                                                               int32_t* __restrict__ argrow) {
     const int item = blockIdx.x;
-    const int kind = dup_kind(nrows_all[item], N);
-    if (kind < 0) return;
-    const int src = rep[kind];
+    const int src = rep[item];
     if (src == item) return;
     static_assert(kFeat == 4 * kThreads, "one float4 per thread");
     reinterpret_cast<f32x4*>(out + (size_t)item * kFeat)[threadIdx.x] = reinterpret_cast<const f32x4*>(out + (size_t)src * kFeat)[threadIdx.x];
@@ -616,11 +676,13 @@ struct Workspace {
     uint16_t* rows;      // (B, kRowCap)
     int32_t* nrows;      // (B)
     int32_t* order;    // (B) launch order
-    int32_t* bin_of;   // (B)
+    int32_t* bin_of;   // (B) launch-order bins until the order is scattered (above kOrderFusedMax items only); afterwards, on the narrow
+                       // keep-mask route, every item's representative (launch_reps) - on the prefix route a cloud per item instead
     int32_t* hist;     // (kBins)
     float* G;
     float* gbuf;
-    float* h1;
+    float* h1;         // (B,512) the heads' first hidden layer; before the input-STN head writes it, the table of launch_reps
+                       // (rep_slots(B) int32 < 4 B of them)
     float* h2;
     float* trans;
     float* tfp;
@@ -645,7 +707,7 @@ Workspace carve(void* base, int B, int nclouds, int N, int R, int roff_entries =
     w.nrows = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
     w.order = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
     w.bin_of = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-    w.hist = reinterpret_cast<int32_t*>(take((size_t)(kBins + 2) * sizeof(int32_t)));   // + pn_dup_rep_kernel's two
+    w.hist = reinterpret_cast<int32_t*>(take((size_t)kBins * sizeof(int32_t)));
     w.G = reinterpret_cast<float*>(take((size_t)nclouds * (R + 1) * kFeat * sizeof(float)));
     w.gbuf = reinterpret_cast<float*>(take((size_t)B * kFeat * sizeof(float)));
     w.h1 = reinterpret_cast<float*>(take((size_t)B * 512 * sizeof(float)));
@@ -753,12 +815,14 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
                            ws.bin_of, ws.hist, ws.order, B);
     }
     if ((rc = iq::check_launch("pn_order kernels"))) return rc;
-    // repeated full / empty sets: one cloud and keep masks in table order only (a prefix route's row lists follow its permutations)
+    // repeated coalitions: narrow keep masks in table order only (a prefix route's row lists follow its permutations), and a cloud
+    // per item that is known - without cloud_of and with several clouds every item has its own.  rep takes the place of the launch
+    // order's bins and the table that of h1, both idle from here to the heads (Workspace).
     const int32_t* dup_rep = nullptr;
-    if (nclouds == 1 && !wide_words && B > 1 && iq::twin() != iq::kTwinChainNoDedup) {
-        hipLaunchKernelGGL(pn_dup_rep_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.hist + kDupRepOff, B, N);
-        if ((rc = iq::check_launch("pn_dup_rep_kernel"))) return rc;
-        dup_rep = ws.hist + kDupRepOff;
+    if (!wide_words && !orders && keep && B > 1 && (cloud_of || nclouds == 1) && iq::twin() != iq::kTwinChainNoDedup) {
+        static_assert(sizeof(int32_t) * 4 <= sizeof(float) * 512, "rep_slots(B) < 4 B int32 inside h1's (B,512) floats");
+        if ((rc = launch_reps(keep, cloud_of, B, R, ws.bin_of, reinterpret_cast<int32_t*>(ws.h1), st))) return rc;
+        dup_rep = ws.bin_of;
     }
 
     ChainArgs a{};
@@ -821,7 +885,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
             iq::ProfileSpan span(iq::kSlotFstn, st);
             launch_chain<kFstn>(a, st);
         }
-        if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, ws.nrows, dup_rep, ws.gbuf, nullptr, N);
+        if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, dup_rep, ws.gbuf, nullptr);
         if ((rc = iq::check_launch("pn_chain_kernel<fstn>"))) return rc;
         if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
         if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
@@ -855,7 +919,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         iq::ProfileSpan span(iq::kSlotTrunk, st);
         launch_chain<kTrunk>(a, st);
     }
-    if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, ws.nrows, dup_rep, ws.gbuf, crt_points, N);
+    if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, dup_rep, ws.gbuf, crt_points);
     if ((rc = iq::check_launch("pn_chain_kernel<trunk>"))) return rc;
     if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
     if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
@@ -872,6 +936,20 @@ extern "C" int iq_pointnet_coalitions_crt(const iq_pointnet_weights* w, const fl
                                           int channel_first, iq_stream_t stream) {
     return pointnet_coalitions(w, clouds, centers, region_id, keep, 0, nullptr, cloud_of, logits, trans_feat_packed, crt_points, workspace,
                                workspace_bytes, B, nclouds, N, R, channel_first, stream);
+}
+
+// include/iq_debug.h: the representatives alone, from the launcher the forward uses, with the caller's scratch for the table
+extern "C" int iq_debug_pointnet_reps(const uint64_t* keep, const int32_t* cloud_of, int B, int nclouds, int R, int32_t* rep_out,
+                                      void* scratch, size_t scratch_bytes, iq_stream_t stream) {
+    IQ_REQUIRE(B >= 0 && nclouds >= 1, "iq_debug_pointnet_reps: B=%d nclouds=%d", B, nclouds);
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_REGIONS, "iq_debug_pointnet_reps: R=%d not in [1,%d]", R, IQ_MAX_REGIONS);
+    IQ_REQUIRE(cloud_of || nclouds == 1, "iq_debug_pointnet_reps: cloud_of required when nclouds > 1");
+    if (B == 0) return IQ_OK;
+    IQ_REQUIRE(keep && rep_out, "iq_debug_pointnet_reps: null pointer");
+    const size_t need = rep_slots(B) * sizeof(int32_t);
+    if (!scratch || scratch_bytes < need)
+        return iq::fail(IQ_EWORKSPACE, "iq_debug_pointnet_reps: scratch %zu < %zu bytes", scratch_bytes, need);
+    return launch_reps(keep, cloud_of, B, R, rep_out, reinterpret_cast<int32_t*>(scratch), iq::as_stream(stream));
 }
 
 extern "C" size_t iq_pointnet_wide_workspace_bytes(int B, int nclouds, int N, int R) {

@@ -72,8 +72,8 @@ struct ChainArgs {
     const unsigned short* w2_bf3;   // layer 2's, likewise (L3V = 3 needs both)
     float* out;                // (items,1024)
     int32_t* argrow;           // (items,1024) point index of the row that attains each column maximum, or null [ARGMAX trunk only]
-    const int32_t* dup_rep;    // [2] first full-set / first empty-set item of the batch, or null: the other such items are copies of
-                               // it and leave at once (pn_dup_rep_kernel, pn_dup_copy_kernel)              [kFstn/kTrunk]
+    const int32_t* dup_rep;    // (items) the first item of the batch with this item's cloud and kept regions, or null: every other
+                               // item is a copy of that one and leaves at once (launch_reps, pn_dup_copy_kernel)   [kFstn/kTrunk]
     int N, R, items, nclouds, with_centre;
     int tail16;                  // last m-tile of an item on 16x16x4 MFMAs when it holds at most 16 rows (l3_tail16)
     int l3_single;               // twin kTwinChainL3Single: the 64-row bf16x3 kernel, one n-tile per pass (launch_chain; the 96-row kernel's reference)
@@ -435,11 +435,6 @@ __device__ __forceinline__ void l1_bf3(const unsigned char* act0, unsigned char*
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-
-// Coalitions that recur in a batch: every permutation of a Shapley sample contributes the full set (prefix R) and the empty set
-// (prefix 0), 2 of its R + 1 coalitions, and all full sets of a cloud are the same rows under the same transforms.  nrows tells
-// both: all N points and no centre row (nothing masked) -> 0, the centre row alone -> 1, anything else -> -1.
-__device__ __forceinline__ int dup_kind(int nrows_word, int N) { return nrows_word == N ? 0 : nrows_word == ((1 << 16) | 1) ? 1 : -1; }
 
 // ---- what the three bodies share: buffer resources, the point fetcher (stage 0a), layer 2's store, the two epilogues ---------------
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t chain_rsrc(const void* base) {   // raw buffer over a wave-uniform base (iq_mfma.h: wbuf_make)
@@ -883,10 +878,7 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
     else cloud = a.cloud_of ? a.cloud_of[item] : (a.nclouds == 1 ? 0 : item);
 
     const int nrows = a.nrows[item] & 0xffff;
-    if (MODE != kPrepool && a.dup_rep) {   // a repeated full or empty set: pn_dup_copy_kernel fills its row from the first one's
-        const int kind = dup_kind(a.nrows[item], a.N);
-        if (kind >= 0 && a.dup_rep[kind] != item) return;
-    }
+    if (MODE != kPrepool && a.dup_rep && a.dup_rep[item] != item) return;   // a repeated coalition: pn_dup_copy_kernel fills its row
     if (nrows == 0) {  // empty region in the pre-pool: identity of max
         float* outp = a.out + (size_t)item * kFeat;
         for (int c = threadIdx.x; c < kFeat; c += kThreads) outp[c] = -INFINITY;

@@ -30,7 +30,7 @@ enum Twin {                                           // key 5
     kTwinDenseFp32 = 57,             // dense layers on the fp32 MFMA
     kTwinChainL3Single = 58,         // bf16x3 chain layer 3 with one n-tile per pass
     kTwinDenseTile128 = 59,          // bf16x3 dense layers with 128-row tiles only, the former launch
-    kTwinChainNoDedup = 60,          // PointNet coalition chains compute every repeated full / empty set of a batch
+    kTwinChainNoDedup = 60,          // PointNet coalition chains compute every repeated coalition of a batch
     kTwinGroupFp32Chunk64 = 64,      // PointNet++ fp32-MFMA grouped kernel with 64-row chunks
 };
 bool no_lds_gemm();   // the calling thread's key 3

@@ -647,3 +647,18 @@ def linear(x, layer, act=0):
     _lib.check(lib.iq_linear(_dev(x, torch.float32, "x"), x.shape[1], ctypes.byref(layer.struct), _p(out), layer.cout, m, int(act),
                              _stream()), "iq_linear")
     return out
+
+
+def pointnet_reps(keep, cloud_of=None, num_regions=64, nclouds=1, scratch_bytes=None):
+    """Diagnostic (iq_debug_pointnet_reps; no product path calls it): keep (B,) int64-typed masks, cloud_of (B,) int32 or None
+    -> (B,) int32, for every coalition the lowest item of the batch on the same cloud with the same kept regions - the items the
+    PointNet chains compute; the others copy their rows.  ``scratch_bytes``: lend the table that much instead of what it needs."""
+    lib = _lib.load()
+    b = keep.shape[0]
+    rep = torch.empty((b,), dtype=torch.int32, device=keep.device)
+    nbytes = 16 * max(b, 1) if scratch_bytes is None else int(scratch_bytes)
+    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=keep.device)
+    _lib.check(lib.iq_debug_pointnet_reps(_dev(keep, torch.int64, "keep"), _dev(cloud_of, torch.int32, "cloud_of") if cloud_of is not None
+                                          else ctypes.c_void_p(0), b, int(nclouds), int(num_regions), _p(rep), _p(scratch), nbytes,
+                                          _stream()), "iq_debug_pointnet_reps")
+    return rep
