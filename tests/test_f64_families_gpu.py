@@ -1,0 +1,165 @@
+"""GPU: every coalition route of PointNet++, PointConv and GCNN against a float64 run of the CPU oracle (tests/f64_cases.py).
+
+With e(x) = max |x - float64| / max |float64| over the logits of a case, every route must satisfy
+    e(route) <= min(FACTOR e(float32 CPU oracle) + 1e-7, 1e-4),   FACTOR = 4,
+the bar of tests/test_stress_weights_gpu.py (a).  tests/test_f64_families_cpu.py shows what this relies on: both oracle precisions
+make the same discrete choices on every case, the 1e-4 clamp is never the active bar, and weights that lost their third bf16 term
+fail it.  The last test here shows the same loss on the device.
+
+Routes, one printed row each (name, e_hip, e_ref, e_hip / e_ref, bar), per (family, case, variant):
+  all       the dense forward on the uploaded host-masked clouds; the coalition entry (``coalition_logits`` with ``cloud_of``; the
+            ``wide`` case: ``coalition_logits_wide`` at R = 128); both again under every twin of the family (tuning key 5)
+  pointnet2 twins 21 (member walk), 56 / 64 (fp32-MFMA grouped kernels), 57 (dense layers on the fp32 MFMA).  Case ``overflow``:
+            256 points shrunk to a diameter of 0.3, so all 257^2 ordered pairs of (points + centre) lie within sa1's radius 0.4 and
+            exceed the pair table's 192 x 257 rows: that scale runs the grouped MLP inside the coalition entry.  Known from the count
+            alone (the library decides by `rows <= cap`, csrc/iq_pointnet2.hip); tests/test_f64_families_cpu.py repeats the count
+            on the host and shows that no other case overflows.
+  pointconv twins 14 (kNN per coalition), 15 (grouped MLP instead of the pair table), 31 (two-kernel contraction), 56, 57; the engine's
+            ``walk`` argument forced on and off.  Cases of at most 8 source clouds build pair tables (``tables_state`` 3 after
+            the call); case ``nc9`` has 9 and must not (bit 1 clear).  Every call gets fresh cloud tensors, so no route reads
+            tables another route built.
+  gcnn      twins 7 / 8 (EdgeConv as GEMM + gather), 12 (no neighbour-list walk), 57.  Case ``walk`` (nc * 8 <= b) takes the
+            layer-1 graph from the neighbour-list walk; the others from knn_kernel.
+iq_mask_coalitions (_wide) with the host's float32 centre reproduces the host-masked clouds bit for bit, so the CPU test and
+this one see the same bytes.
+
+Measured e_hip / e_ref, smallest .. largest over the family's ten (case, variant) pairs, from one run of this file on an MI355X
+(gfx950; the 33 ids in 36 s; e_ref there 3.9e-07 .. 2.0e-06).  Routes on one line gave the same figures to three digits.
+Nothing was above the bar, the worst route used 0.66 of it, so FACTOR is 4 on every route and no kernel was changed.
+  pointnet2  forward_points = coalition entry = 5 = 21 (either entry)                      1.01 .. 2.70  (stress, negshift)
+             5 = 56 = 5 = 64 (either entry)                                                1.07 .. 2.23  (wide)
+             5 = 57 (either entry)                                                         0.96 .. 1.98  (stress, negshift)
+  pointconv  forward_points (also under 5 = 14, 15, 31), entry under 5 = 14 = walk off     0.68 .. 2.58  (stress, negshift)
+             coalition entry = 5 = 31 = walk on (list walk and pair tables)                0.63 .. 2.52  (stress, seed1)
+             coalition entry, 5 = 15 (list walk, grouped MLP)                              0.61 .. 1.92  (stress, negshift)
+             5 = 56: forward_points 0.74 .. 2.75 (stress, negshift), coalition entry 0.70 .. 2.07 (min)
+             5 = 57: forward_points 0.59 .. 1.81 (stress, seed1), coalition entry 0.67 .. 2.09 (stress, negshift)
+  gcnn       every route, every twin                                                       1.04 .. 2.74  (walk)
+             (5 = 57 changes nothing in GCNN: its heads carry no bf16 image and run on the fp32 MFMA whatever the key, and
+             conv5's pooled GEMM has no fp32 twin; the key stays in the list so that a head moved to the bf16 pipe is covered)
+  weights with 16 significant bits on the device (last test): 17 (pointnet2), 21 - 22 (pointconv), 23 (gcnn) x e_ref, i.e. 4.2,
+  5.1 - 5.2 and 5.7 x the bar.
+"""
+import argparse
+
+import numpy as np
+import pytest
+import torch
+
+import f64_cases as F
+import probes
+import weight_variants as V
+from interpret_quality_amd import _lib, hip_ops, synth
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+TWINS = {"pointnet2": (21, 56, 64, 57), "pointconv": (14, 15, 31, 56, 57), "gcnn": (7, 8, 12, 57)}
+# per route, where it is not f64_cases.FACTOR: (factor, measured ratio, reason) - none so far
+FACTORS = {}
+
+
+def tuned(key, fn):
+    lib = _lib.load()
+    try:
+        lib.iq_set_tuning(5, key)
+        return fn()
+    finally:
+        lib.iq_set_tuning(5, 0)
+
+
+_DEVICE = {}
+
+
+def device_inputs(case):
+    if case not in _DEVICE:
+        i, s = F.inputs(case), case.spec
+        up = lambda k: torch.from_numpy(np.ascontiguousarray(i[k])).to(DEV)
+        d = {k: up(k) for k in ("clouds", "centers", "rid", "cloud_of", "masked")}
+        d["keep"] = hip_ops.wide_masks_to_tensor(i["keep"], DEV) if case.wide else hip_ops.masks_to_tensor(i["keep"], DEV)
+        for c in range(s.nc):                       # the mask kernel with the host's centre writes the host's bytes
+            sel = np.flatnonzero(i["cloud_of"] == c)
+            if not len(sel):
+                continue
+            keep = d["keep"][torch.from_numpy(sel).to(DEV)].contiguous()
+            args = (d["clouds"][c].contiguous(), d["rid"][c].contiguous(), keep, d["centers"][c].contiguous())
+            got = hip_ops.mask_coalitions_wide(*args, s.r) if case.wide else hip_ops.mask_coalitions(*args)
+            assert probes.bitwise_equal(got.cpu().numpy(), i["masked"][sel]), (case.id, c)
+        _DEVICE[case] = d
+    return _DEVICE[case]
+
+
+def model_of(family, sd):
+    """A HIP model of ``family`` with the numpy state dict ``sd`` (probes.coalition_model for weights that have no variant name)."""
+    from interpret_quality_amd.dgcnn import GCNN_cls
+    from interpret_quality_amd.pointconv import PointConvDensityClsSsg
+    from interpret_quality_amd.pointnet2 import PointNet2ClsMsg
+    cls = {"pointnet2": PointNet2ClsMsg, "pointconv": PointConvDensityClsSsg, "gcnn": GCNN_cls}[family]
+    m = cls(argparse.Namespace(dataset="modelnet10", k=20) if family == "gcnn" else None)
+    m.load_state_dict(synth.to_torch(sd))
+    return m.to(DEV).eval()
+
+
+def routes(family, case, model):
+    """[(name, callable -> logits tensor)]"""
+    d, s = device_inputs(case), case.spec
+    fresh = lambda: (d["clouds"].clone(), d["centers"].clone())       # PointConv keys its cached tables on these tensors
+    dense = lambda: model.forward_points(d["masked"])
+    if case.wide:
+        entry = "coalition_logits_wide"
+        coal = lambda: model.coalition_logits_wide(*fresh(), d["rid"], d["keep"], d["cloud_of"], num_regions=s.r)
+        forced = lambda walk: model.engine().coalition_logits_wide(*fresh(), d["rid"], d["keep"], d["cloud_of"], s.r, walk)
+    else:
+        entry = "coalition_logits"
+        coal = lambda: model.coalition_logits(*fresh(), d["rid"], d["keep"], d["cloud_of"], num_regions=s.r)
+        forced = lambda walk: model.engine().coalition_logits(*fresh(), d["rid"], d["keep"], d["cloud_of"], walk)
+    out = [("forward_points", dense), (entry, coal)]
+    for key in TWINS[family]:
+        out.append(("forward_points, 5 = %d" % key, lambda key=key: tuned(key, dense)))
+        out.append(("%s, 5 = %d" % (entry, key), lambda key=key: tuned(key, coal)))
+    if family == "pointconv":
+        out += [("%s, walk off" % entry, lambda: forced(False)), ("%s, walk on" % entry, lambda: forced(True))]
+    return out
+
+
+def measure(tag, rows, run):
+    """Runs every route, prints its row, -> [(name, e_hip, bar)]."""
+    out = []
+    for name, fn in rows:
+        got = fn().cpu().numpy()
+        assert got.shape == run["f64"].shape and np.isfinite(got).all(), (tag, name)
+        e_hip, e_ref = F.rel_err(got, run["f64"]), run["e_ref"]
+        bar = F.bar(e_ref, FACTORS.get(name, (F.FACTOR,))[0])
+        print("%-44s %-34s e_hip %.3g  e_ref %.3g  e_hip / e_ref %.2f  (bar %.3g)" % (tag, name, e_hip, e_ref, e_hip / e_ref, bar))
+        out.append((name, e_hip, bar))
+    return out
+
+
+@pytest.mark.parametrize("pair", F.PAIRS, ids=F.pair_id)
+def test_every_route_is_within_the_float64_bar(pair):
+    family, case, variant = pair
+    model, _ = probes.coalition_model(family, DEV, variant)
+    run = F.oracle_run(family, case, variant)
+    assert not F.choice_mismatches(run)
+    if family == "pointnet2":
+        rows, cap = F.pn2_pair_rows(case)
+        assert (rows > cap) == (case.name == "overflow")
+    got = measure(F.pair_id(pair), routes(family, case, model), run)
+    if family == "pointconv":           # the last route ran the list walk on fresh tensors: what it built is what the engine remembers
+        state = model.engine()._tab.get("state")
+        assert state == (3 if case.spec.nc <= 8 else 1), state
+    above = ["%s: e_hip %.3g above %.3g" % r for r in got if not r[1] <= r[2]]
+    assert not above, above
+
+
+@pytest.mark.parametrize("family", F.FAMILIES)
+def test_a_lost_bf16_term_is_above_the_bar_on_the_device(family):
+    """The HIP model loaded with weights of 16 significant bits on the layers that run on the bf16 pipe (grouped layers and heads),
+    against float64 of the TRUE weights: the dense and the coalition route are both above the bar, as the float32 oracle is in
+    tests/test_f64_families_cpu.py.  So the bar resolves, on the device, the loss it is meant to catch."""
+    case = F.stress_base(family)
+    run = F.oracle_run(family, case, "base")
+    sd = F.trunc16(V.variant(family, "base"), F.BF16_GROUP_LAYERS[family] + F.BF16_HEAD_LAYERS[family])
+    got = measure("trunc16 " + case.id, routes(family, case, model_of(family, sd))[:2], run)
+    assert len(got) == 2
+    for name, e_hip, bar in got:
+        assert e_hip > bar, (family, name, e_hip, bar)
