@@ -32,6 +32,27 @@ inline hipStream_t as_stream(iq_stream_t s) { return reinterpret_cast<hipStream_
 
 constexpr size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Arrays carved one after the other out of a workspace, each starting on a 256-byte boundary.  A null base only measures.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* b) : base(reinterpret_cast<char*>(b)) {}
+    template <class T> T* take(size_t count) {
+        T* p = reinterpret_cast<T*>(base + off);
+        off = align_up(off + count * sizeof(T), 256);
+        return p;
+    }
+    size_t bytes() const { return off; }
+};
+
+// The lanes of ONE wave exchange data through LDS: what every lane wrote before is visible to every lane after (LDS is coherent
+// within a workgroup; the fences keep the compiler from moving reads above the writes, the barrier keeps the lanes together).
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Bit `rid` of a coalition's keep mask; a region id outside [0, 64) (which iq_check_index_range rejects) is never kept,
 // so an unvalidated id gives a defined result instead of an undefined shift.
 __host__ __device__ inline bool keep_bit(unsigned long long keep, int rid) {
@@ -64,9 +85,7 @@ struct WaveKeep {
     __device__ __forceinline__ WaveKeep(const uint64_t* keep, int b, int R_, int W, int lane, uint64_t* strip) {
         if constexpr (WIDE) {
             if (lane < W) strip[lane] = keep[(size_t)b * W + lane];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             row = strip;
             R = R_;
         } else {

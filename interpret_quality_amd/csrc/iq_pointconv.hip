@@ -897,26 +897,21 @@ struct WsC {
 
 WsC carve_c(void* base, int B, int N) {
     WsC s{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = iq::align_up(off + bytes, 256);
-        return reinterpret_cast<char*>(base) + o;
-    };
+    iq::Carver c(base);
     const size_t b = (size_t)B;
-    s.inv1 = (float*)take(b * N * 4); s.inv2 = (float*)take(b * 512 * 4); s.inv3 = (float*)take(b * 128 * 4);
-    s.fps1 = (int32_t*)take(b * 512 * 4); s.fps2 = (int32_t*)take(b * 128 * 4); s.nu1 = (int32_t*)take(b * 4);
-    s.nx1 = (float*)take(b * 512 * 3 * 4); s.nx2 = (float*)take(b * 128 * 3 * 4);
+    s.inv1 = c.take<float>(b * N); s.inv2 = c.take<float>(b * 512); s.inv3 = c.take<float>(b * 128);
+    s.fps1 = c.take<int32_t>(b * 512); s.fps2 = c.take<int32_t>(b * 128); s.nu1 = c.take<int32_t>(b);
+    s.nx1 = c.take<float>(b * 512 * 3); s.nx2 = c.take<float>(b * 128 * 3);
     // k8 holds the keys of both kNN launches: the N points (sa1) and the 512 sa1 centroids (sa2) - the larger of the two
-    s.k8 = (float*)take(b * (size_t)std::max((N + 31) / 32 * 32, 512) * 8 * 4); s.q8 = (float*)take(b * 512 * 8 * 4);
-    s.idx1 = (int16_t*)take(b * 512 * 32 * 2); s.idx2 = (int16_t*)take(b * 128 * 64 * 2);
-    s.g1 = (float*)take(b * 512 * 2048 * 4); s.l1 = (float*)take(b * 512 * 128 * 4);
-    s.u2 = (float*)take(b * 512 * 128 * 4); s.g2 = (float*)take(b * 128 * 4096 * 4); s.l2 = (float*)take(b * 128 * 256 * 4);
-    s.u3 = (float*)take(b * 128 * 256 * 4); s.h1 = (float*)take(b * 128 * 256 * 4); s.h2 = (float*)take(b * 128 * 512 * 4);
-    s.h3 = (float*)take(b * 128 * 1024 * 4); s.sw3 = (float*)take(b * 128 * 16 * 4); s.g3 = (float*)take(b * 16384 * 4);
-    s.l3 = (float*)take(b * 1024 * 4); s.f1 = (float*)take(b * 512 * 4); s.f2 = (float*)take(b * 256 * 4);
-    s.mrel = (float*)take(b * 16384 * 4 * 4); s.msw = (float*)take(b * 16384 * 16 * 4);
-    s.bytes = off;
+    s.k8 = c.take<float>(b * (size_t)std::max((N + 31) / 32 * 32, 512) * 8); s.q8 = c.take<float>(b * 512 * 8);
+    s.idx1 = c.take<int16_t>(b * 512 * 32); s.idx2 = c.take<int16_t>(b * 128 * 64);
+    s.g1 = c.take<float>(b * 512 * 2048); s.l1 = c.take<float>(b * 512 * 128);
+    s.u2 = c.take<float>(b * 512 * 128); s.g2 = c.take<float>(b * 128 * 4096); s.l2 = c.take<float>(b * 128 * 256);
+    s.u3 = c.take<float>(b * 128 * 256); s.h1 = c.take<float>(b * 128 * 256); s.h2 = c.take<float>(b * 128 * 512);
+    s.h3 = c.take<float>(b * 128 * 1024); s.sw3 = c.take<float>(b * 128 * 16); s.g3 = c.take<float>(b * 16384);
+    s.l3 = c.take<float>(b * 1024); s.f1 = c.take<float>(b * 512); s.f2 = c.take<float>(b * 256);
+    s.mrel = c.take<float>(b * 16384 * 4); s.msw = c.take<float>(b * 16384 * 16);
+    s.bytes = c.bytes();
     return s;
 }
 
@@ -1116,41 +1111,31 @@ constexpr int kTabClouds = 8;
 // chunk of coalitions of the same clouds can have it kept (iq_pointconv_coalitions_cached).  `rest` = per-coalition arrays and
 // the scratch of the table build; it follows the forward's own workspace.
 size_t carve_w_cloud(WsW& s, void* base, int nc, int N) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = iq::align_up(off + bytes, 256);
-        return reinterpret_cast<char*>(base) + o;
-    };
+    iq::Carver c(base);
     const size_t Nsp = (size_t)(N + 1 + 31) / 32 * 32, Nsl = (size_t)(N + 1 + 7) / 8 * 8;
-    s.xs = (float*)take((size_t)nc * Nsp * 8 * 4);
-    s.xxs = (float*)take((size_t)nc * Nsp * 4);
-    s.sorted = (int16_t*)take((size_t)nc * (N + 1) * Nsl * 2);
-    if (nc <= kTabClouds) s.feat = (float*)take((size_t)nc * (size_t)(N + 1) * (N + 1) * 128 * 4);
-    return off;
+    s.xs = c.take<float>((size_t)nc * Nsp * 8);
+    s.xxs = c.take<float>((size_t)nc * Nsp);
+    s.sorted = c.take<int16_t>((size_t)nc * (N + 1) * Nsl);
+    if (nc <= kTabClouds) s.feat = c.take<float>((size_t)nc * (size_t)(N + 1) * (N + 1) * 128);
+    return c.bytes();
 }
 
 size_t carve_w_rest(WsW& s, void* base, int B, int nc, int N) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = iq::align_up(off + bytes, 256);
-        return reinterpret_cast<char*>(base) + o;
-    };
+    iq::Carver c(base);
     const size_t Nsp = (size_t)(N + 1 + 31) / 32 * 32, Nsl = (size_t)(N + 1 + 7) / 8 * 8;
-    s.X = (float*)take((size_t)B * N * 3 * 4);
-    s.dmat = (float*)take((size_t)nc * Nsp * Nsp * 4);
-    s.kept = (uint32_t*)take((size_t)B * 32 * 4);
-    s.mfirst = (int16_t*)take((size_t)B * 64 * 2);
-    s.mcount = (int32_t*)take((size_t)B * 4);
-    s.src1 = (int16_t*)take((size_t)B * 512 * 2);
-    s.pos = (int16_t*)take((size_t)B * Nsl * 2);
+    s.X = c.take<float>((size_t)B * N * 3);
+    s.dmat = c.take<float>((size_t)nc * Nsp * Nsp);
+    s.kept = c.take<uint32_t>((size_t)B * 32);
+    s.mfirst = c.take<int16_t>((size_t)B * 64);
+    s.mcount = c.take<int32_t>((size_t)B);
+    s.src1 = c.take<int16_t>((size_t)B * 512);
+    s.pos = c.take<int16_t>((size_t)B * Nsl);
     if (nc <= kTabClouds) {
         const size_t rows = (size_t)(N + 1) * (N + 1);
-        s.th1 = (float*)take(rows * 64 * 4);
-        s.th2 = (float*)take(rows * 64 * 4);
+        s.th1 = c.take<float>(rows * 64);
+        s.th2 = c.take<float>(rows * 64);
     }
-    return off;
+    return c.bytes();
 }
 
 }  // namespace

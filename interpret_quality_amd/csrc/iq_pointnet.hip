@@ -693,29 +693,25 @@ struct Workspace {
 // roff_entries: offsets per cloud - IQ_MAX_REGIONS + 1 for the narrow entry points (their layout since ABI 100), R + 1 for the wide one
 Workspace carve(void* base, int B, int nclouds, int N, int R, int roff_entries = IQ_MAX_REGIONS + 1) {
     Workspace w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = iq::align_up(off + bytes, 256);
-        return reinterpret_cast<char*>(base) + o;
-    };
-    w.sorted_pts = reinterpret_cast<uint16_t*>(take((size_t)nclouds * N * sizeof(uint16_t)));
-    w.roff = reinterpret_cast<int32_t*>(take((size_t)nclouds * roff_entries * sizeof(int32_t)));
-    w.rows_pre = reinterpret_cast<uint16_t*>(take((size_t)nclouds * (R + 1) * kRowCap * sizeof(uint16_t)));
-    w.nrows_pre = reinterpret_cast<int32_t*>(take((size_t)nclouds * (R + 1) * sizeof(int32_t)));
-    w.rows = reinterpret_cast<uint16_t*>(take((size_t)B * kRowCap * sizeof(uint16_t)));
-    w.nrows = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-    w.order = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-    w.bin_of = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-    w.hist = reinterpret_cast<int32_t*>(take((size_t)kBins * sizeof(int32_t)));
-    w.G = reinterpret_cast<float*>(take((size_t)nclouds * (R + 1) * kFeat * sizeof(float)));
-    w.gbuf = reinterpret_cast<float*>(take((size_t)B * kFeat * sizeof(float)));
-    w.h1 = reinterpret_cast<float*>(take((size_t)B * 512 * sizeof(float)));
-    w.h2 = reinterpret_cast<float*>(take((size_t)B * 256 * sizeof(float)));
-    w.trans = reinterpret_cast<float*>(take((size_t)B * 9 * sizeof(float)));
-    w.tfp = reinterpret_cast<float*>(take((size_t)B * 4096 * sizeof(float)));
-    w.fc3_bf3 = reinterpret_cast<uint16_t*>(take(iq_packed_bf3_elems(4096, 256) * sizeof(uint16_t)));
-    w.bytes = off;
+    iq::Carver c(base);
+    const size_t b = (size_t)B, nc = (size_t)nclouds;
+    w.sorted_pts = c.take<uint16_t>(nc * N);
+    w.roff = c.take<int32_t>(nc * roff_entries);
+    w.rows_pre = c.take<uint16_t>(nc * (R + 1) * kRowCap);
+    w.nrows_pre = c.take<int32_t>(nc * (R + 1));
+    w.rows = c.take<uint16_t>(b * kRowCap);
+    w.nrows = c.take<int32_t>(b);
+    w.order = c.take<int32_t>(b);
+    w.bin_of = c.take<int32_t>(b);
+    w.hist = c.take<int32_t>((size_t)kBins);
+    w.G = c.take<float>(nc * (R + 1) * kFeat);
+    w.gbuf = c.take<float>(b * kFeat);
+    w.h1 = c.take<float>(b * 512);
+    w.h2 = c.take<float>(b * 256);
+    w.trans = c.take<float>(b * 9);
+    w.tfp = c.take<float>(b * 4096);
+    w.fc3_bf3 = c.take<uint16_t>(iq_packed_bf3_elems(4096, 256));
+    w.bytes = c.bytes();
     return w;
 }
 

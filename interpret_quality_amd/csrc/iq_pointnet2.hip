@@ -1026,29 +1026,24 @@ struct Ws2 {
 
 Ws2 carve2(void* base, int B, const iq_pointnet2_weights* w) {
     Ws2 s{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = iq::align_up(off + bytes, 256);
-        return reinterpret_cast<char*>(base) + o;
-    };
+    iq::Carver c(base);
     const size_t b = (size_t)B;
-    s.fps1 = (int32_t*)take(b * 512 * 4); s.nu1 = (int32_t*)take(b * 4);
-    s.fps2 = (int32_t*)take(b * 128 * 4); s.nu2 = (int32_t*)take(b * 4);
-    s.nx1 = (float*)take(b * 512 * 3 * 4);
-    for (int q = 0; q < 3; ++q) s.idx1[q] = (int16_t*)take(b * 512 * (w ? w->sa1[q].nsample : 128) * 2);
-    for (int q = 0; q < 3; ++q) { s.cnt1[q] = (int32_t*)take(b * 512 * 4); s.cnt2[q] = (int32_t*)take(b * 128 * 4); }
-    s.bstart = (int32_t*)take(b * 513 * 4);
-    s.bmap = (uint16_t*)take(b * 8192 * 2);
-    s.l1 = (float*)take(b * 512 * 320 * 4);
-    s.U = (float*)take(b * 512 * 320 * 4);
-    for (int q = 0; q < 3; ++q) s.idx2[q] = (int16_t*)take(b * 128 * (w ? w->sa2[q].nsample : 128) * 2);
-    s.a3 = (float*)take(b * 128 * 648 * 4);
-    s.h1 = (float*)take(b * 128 * 256 * 4);
-    s.h2 = (float*)take(b * 128 * 512 * 4);
-    s.h3 = (float*)take(b * 128 * 1024 * 4);
-    s.g = (float*)take(b * 1024 * 4); s.f1 = (float*)take(b * 512 * 4); s.f2 = (float*)take(b * 256 * 4);
-    s.bytes = off;
+    s.fps1 = c.take<int32_t>(b * 512); s.nu1 = c.take<int32_t>(b);
+    s.fps2 = c.take<int32_t>(b * 128); s.nu2 = c.take<int32_t>(b);
+    s.nx1 = c.take<float>(b * 512 * 3);
+    for (int q = 0; q < 3; ++q) s.idx1[q] = c.take<int16_t>(b * 512 * (w ? w->sa1[q].nsample : 128));
+    for (int q = 0; q < 3; ++q) { s.cnt1[q] = c.take<int32_t>(b * 512); s.cnt2[q] = c.take<int32_t>(b * 128); }
+    s.bstart = c.take<int32_t>(b * 513);
+    s.bmap = c.take<uint16_t>(b * 8192);
+    s.l1 = c.take<float>(b * 512 * 320);
+    s.U = c.take<float>(b * 512 * 320);
+    for (int q = 0; q < 3; ++q) s.idx2[q] = c.take<int16_t>(b * 128 * (w ? w->sa2[q].nsample : 128));
+    s.a3 = c.take<float>(b * 128 * 648);
+    s.h1 = c.take<float>(b * 128 * 256);
+    s.h2 = c.take<float>(b * 128 * 512);
+    s.h3 = c.take<float>(b * 128 * 1024);
+    s.g = c.take<float>(b * 1024); s.f1 = c.take<float>(b * 512); s.f2 = c.take<float>(b * 256);
+    s.bytes = c.bytes();
     return s;
 }
 
@@ -1209,29 +1204,24 @@ struct WsC {
 
 WsC carve_c(void* base, int B, int nc, int N) {
     WsC s{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = iq::align_up(off + bytes, 256);
-        return reinterpret_cast<char*>(base) + o;
-    };
+    iq::Carver c(base);
     const size_t n1 = (size_t)N + 1, cap = (size_t)nc * kPairFan * n1;
-    s.X = (float*)take((size_t)B * N * 3 * 4);
-    s.P = (float*)take((size_t)nc * n1 * 4 * 4);
-    s.cntp = (int32_t*)take((size_t)nc * 3 * n1 * 4);
-    s.off = (int32_t*)take((size_t)nc * 3 * n1 * 4);
-    s.total = (int32_t*)take((size_t)nc * 3 * 4);
-    for (int q = 0; q < 3; ++q) s.map[q] = (int32_t*)take((size_t)nc * n1 * n1 * 4);
-    s.pairs = (uint32_t*)take(cap * 4);
-    s.h1 = (float*)take(cap * 64 * 4);
-    s.h2 = (float*)take(cap * 96 * 4);
+    s.X = c.take<float>((size_t)B * N * 3);
+    s.P = c.take<float>((size_t)nc * n1 * 4);
+    s.cntp = c.take<int32_t>((size_t)nc * 3 * n1);
+    s.off = c.take<int32_t>((size_t)nc * 3 * n1);
+    s.total = c.take<int32_t>((size_t)nc * 3);
+    for (int q = 0; q < 3; ++q) s.map[q] = c.take<int32_t>((size_t)nc * n1 * n1);
+    s.pairs = c.take<uint32_t>(cap);
+    s.h1 = c.take<float>(cap * 64);
+    s.h2 = c.take<float>(cap * 96);
     const int c3[3] = {64, 128, 128};
-    for (int q = 0; q < 3; ++q) s.feat[q] = (float*)take(cap * c3[q] * 4);
-    for (int q = 0; q < 3; ++q) s.ball_bits[q] = (uint32_t*)take((size_t)nc * n1 * kBallWords * 4);
-    s.kept_bits = (uint32_t*)take((size_t)B * 32 * 4);
-    for (int q = 0; q < 3; ++q) s.regtab[q] = (float*)take((size_t)nc * n1 * kRegSlots * c3[q] * 4);
-    for (int q = 0; q < 3; ++q) s.touch[q] = (uint64_t*)take((size_t)nc * n1 * 8);
-    s.bytes = off;
+    for (int q = 0; q < 3; ++q) s.feat[q] = c.take<float>(cap * c3[q]);
+    for (int q = 0; q < 3; ++q) s.ball_bits[q] = c.take<uint32_t>((size_t)nc * n1 * kBallWords);
+    s.kept_bits = c.take<uint32_t>((size_t)B * 32);
+    for (int q = 0; q < 3; ++q) s.regtab[q] = c.take<float>((size_t)nc * n1 * kRegSlots * c3[q]);
+    for (int q = 0; q < 3; ++q) s.touch[q] = c.take<uint64_t>((size_t)nc * n1);
+    s.bytes = c.bytes();
     return s;
 }
 

@@ -31,7 +31,7 @@ __global__ void sl_rows_kernel(const float* __restrict__ clouds, const float* __
 }
 
 // dmat[c][q][k] = the consumer's distance value (larger = nearer) of query row q and key row k, by its own expression on the
-// same MFMA inner products (one wave = 32 queries, all key tiles).  FORM 0: knn_kernel<8> of iq_dgcnn.hip, (2 q.k - |k|^2) - |q|^2;
+// same MFMA inner products (one wave = 32 queries, all key tiles).  FORM 0: knn_kernel<8> of iq_dgcnn_knn.h, (2 q.k - |k|^2) - |q|^2;
 // FORM 1: pc_knn_kernel of iq_pointconv.hip, -(((-2 q.k) + |q|^2) + |k|^2).
 template <int FORM>
 __global__ __launch_bounds__(64) void sl_dist_kernel(const float* __restrict__ xs, const float* __restrict__ xxs,

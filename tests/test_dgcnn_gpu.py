@@ -62,7 +62,7 @@ def knn_set_mismatches(got, want, x_cf):
                 dw = np.sort(dist[b, i, list(sw - sg)])
                 scale = max(1.0, float(np.abs(dist[b, i]).max()))
                 # float32 noise of the expanded form, plus the band inside which knn_refine_kernel ranks by exact distances
-                # (csrc/iq_dgcnn.hip kNearTie: 1e-5 of 2 (|q|^2 + |q - k|^2))
+                # (csrc/iq_dgcnn_knn.h kNearTie: 1e-5 of 2 (|q|^2 + |q - k|^2))
                 band = 2e-5 * (float(xx[b, 0, i]) + float(np.abs(dw).max()))
                 assert np.allclose(dg, dw, rtol=0, atol=2e-6 * scale + band), (b, i, dg, dw)
                 bad += 1
