@@ -63,8 +63,10 @@ enum {
  * 109: new entry points, no layout change (iq_split_packed_weight_bf3, iq_split_packed_weight_bf3_host); the PointNet workspaces
  * grew by the bf16x3 image of fstn.fc3 (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes).
  * 110: one new entry point, no layout change (iq_smoothness_enum_wide: the smoothness enumeration of a wide game).
- * 112: one new diagnostic entry point, no layout change and no workspace size changed (iq_debug.h: iq_debug_pointnet_reps). */
-#define IQ_ABI_VERSION 112
+ * 112: one new diagnostic entry point, no layout change and no workspace size changed (iq_debug.h: iq_debug_pointnet_reps).
+ * 113: new entry points, no layout change (the device sampler for wide games: iq_sample_wide_workspace_bytes,
+ * iq_sample_permutations_wide, iq_context_regions_wide). */
+#define IQ_ABI_VERSION 113
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -591,16 +593,39 @@ int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
  * cal_region_id (final_shapley_value.py:20-35) and the sampling loop (:138-156) work for any region count up to the number of
  * points.  A WIDE coalition is a row of W = ceil(R / 64) uint64 words: bit (r & 63) of word (r >> 6) set = region r kept; bits
  * at or above R are ignored.  1 <= R <= IQ_MAX_WIDE_REGIONS.  Every entry point above keeps its R <= 64 check and its code;
- * for R <= 64 (W = 1) the entry points below give the same bits as their narrow twins.  The permutations of a wide game are
- * and the contexts of its interaction stage are drawn on the host (final_shapley_value.py:59-72, final_gen_pair.py:18-43 as
- * they stand: NumPy's global generator) - iq_sample_permutations stays narrow.  The multi-order interactions of a wide game need
- * one wide entry point only, iq_context_keep_masks_wide: iq_reward and iq_interaction_reduce never see a mask.
+ * for R <= 64 (W = 1) the entry points below give the same bits as their narrow twins.  The permutations of a wide game and
+ * the contexts of its interaction stage (final_shapley_value.py:59-72, final_gen_pair.py:18-43: NumPy's global generator) are
+ * drawn on the host or, the same bits, on the device: iq_sample_permutations_wide is iq_sample_permutations_ws's kernels with
+ * 16-bit rows and longer windows, and iq_context_regions_wide turns the head of a permutation into a context.  The multi-order
+ * interactions of a wide game need one more wide entry point only, iq_context_keep_masks_wide: iq_reward and
+ * iq_interaction_reduce never see a mask.
  * Every family's coalition entry has a wide form (the compact paths of PointNet++ / DGCNN / GCNN / PointConv: the few small kernels
  * that turn a mask into a coalition's kept points, csrc/iq_common.h WaveKeep; everything behind them works on points); those
  * families can also evaluate wide coalitions with iq_mask_coalitions_wide + their iq_*_forward.  The pose sweeps of a wide
  * game need no entry point of their own - every pose of a cloud goes through the coalition entries below - and its smoothness
  * stage needs one, iq_smoothness_enum_wide (declared beside iq_smoothness_enum above: the same kernel, N <= 1024).
  * ------------------------------------------------------------------------------------------- */
+
+/* iq_sample_permutations_ws for 1 <= R <= IQ_MAX_WIDE_REGIONS: the same draw as NumPy's legacy RandomState.permutation(R), S
+ * times, and the same state handed back; for R <= 64 the rows are iq_sample_permutations's.  Of every permutation the first
+ * `head` entries are written (0 <= head <= R), rows of `head`: a sampled context is the head of a permutation
+ * (final_gen_pair.py:29: np.random.choice(rest, m, replace=False)), and at R = 1024 the full rows of one ratio of the interaction
+ * stage would be 123 MB.  head = 0 or orders = NULL: the draw advances the state and writes nothing (the contexts of a cloud that
+ * is not selected).  The conventions of iq_sample_permutations_ws hold: nothing is allocated and the host is never synchronised;
+ * iq_sample_wide_workspace_bytes(S, R) - 16 bytes per estimated word, 0 for a refused argument or a draw that one batch of the
+ * one-workgroup kernel covers, never smaller for a larger S - is the size at which the spread kernels expect to draw everything,
+ * and with any smaller workspace, none included, or an unlucky draw the one-workgroup kernel, which runs last, draws the rest:
+ * rows and state never depend on the workspace or on how a draw is cut into calls.  A malformed or poisoned state gives rows
+ * of -1 and stays poisoned. */
+size_t iq_sample_wide_workspace_bytes(int S, int R);
+int iq_sample_permutations_wide(uint32_t* mt_state /*625*/, int32_t* orders /*S,head or NULL*/, int S, int R, int head,
+                                void* workspace, size_t workspace_bytes, iq_stream_t stream);
+
+/* final_gen_pair.py:25-29: heads of permutations of R - 2 -> context regions, in place.  Entry k becomes rest[k] for the ascending
+ * list `rest` of the regions outside pair p = (i, j): k + (k >= lo) + (k + 1 >= hi) with lo < hi the pair.  One coalesced pass;
+ * 0 <= m <= R - 2.  The pair is not checked here (i == j or an entry outside [0, R): the caller refuses it). */
+int iq_context_regions_wide(const int32_t* pairs /*P,2*/, int32_t* heads /*P,C,m: in place -> contexts*/, int P, int C, int m, int R,
+                            iq_stream_t stream);
 
 /* tools/final_common.py:56-60 as wide masks: row s*(R+1) + i of keep keeps orders[s][0..i-1]; an entry outside [0, R) is ignored. */
 int iq_prefix_keep_masks_wide(const int32_t* orders /*S,R*/, uint64_t* keep /*S*(R+1),W*/, int S, int R, iq_stream_t stream);

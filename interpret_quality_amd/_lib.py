@@ -140,6 +140,9 @@ SIGNATURES = {
     "iq_moebius": (_I, [_P, _I, _P, _P]),
     "iq_prefix_keep_masks_wide": (_I, [_P, _P, _I, _I, _P]),
     "iq_context_keep_masks_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "iq_sample_wide_workspace_bytes": (_SZ, [_I, _I]),
+    "iq_sample_permutations_wide": (_I, [_P, _P, _I, _I, _I, _P, _SZ, _P]),
+    "iq_context_regions_wide": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "iq_mask_coalitions_wide": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_region_assign_wide": (_I, [_P, _P, _P, _I, _I, _P]),
     "iq_shapley_accum_wide": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
@@ -164,7 +167,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 112  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 113  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

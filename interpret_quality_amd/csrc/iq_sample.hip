@@ -73,10 +73,28 @@ __device__ inline int perm_end(Word word, int limit, int R, int o) {
     return fail ? -1 : p;
 }
 
-// The same draws with the swaps: row (R bytes) becomes the permutation that starts at offset p; its words all lie below `limit`
-template <class Word>
-__device__ inline void perm_replay(Word word, int limit, int R, int p, uint8_t* row) {
-    for (int j = 0; j < R; ++j) row[j] = (uint8_t)j;
+// What depends on the region count, as parameters of ONE body per kernel below.  Row: the element of a permutation row in LDS
+// (a byte cannot hold an id above 255).  kNextTail: words behind its 256 offsets that a workgroup of mt_next_kernel keeps in LDS,
+// kReplayTail: words behind a segment that mt_replay_kernel keeps - a permutation of 1024 regions draws about 1413 words, one of
+// 64 about 90; beyond the tail the words come from memory, so the tails are a matter of speed only.  The 16-bit offsets of the
+// narrow kernels (nxt[] and start[] of a batch of 4992 words, start[] relative to a segment of 4096) count words, not regions:
+// they fit at any R.
+struct MtNarrow {
+    using Row = uint8_t;
+    static constexpr int kNextTail = 256, kReplayTail = 1024;
+    static int next_tail(int) { return kNextTail; }
+};
+struct MtWide {
+    using Row = uint16_t;
+    static constexpr int kNextTail = 2048, kReplayTail = 2048;
+    // 1.39 R words on average at worst (R = 2^k), sigma about sqrt(R): 1.5 R + 64 covers all but a rare lane
+    static int next_tail(int R) { const int t = ((3 * R / 2 + 64) + 255) / 256 * 256; return t < kNextTail ? t : kNextTail; }
+};
+
+// The same draws with the swaps: row (R entries) becomes the permutation that starts at offset p; its words all lie below `limit`
+template <class Word, class Row>
+__device__ inline void perm_replay(Word word, int limit, int R, int p, Row* row) {
+    for (int j = 0; j < R; ++j) row[j] = (Row)j;
     int i = R - 1;
     while (i >= 1) {
         uint32_t w[4];
@@ -88,7 +106,7 @@ __device__ inline void perm_replay(Word word, int limit, int R, int p, uint8_t* 
                 const uint32_t v = w[u] & interval_mask(i);
                 ++p;
                 if (v <= (uint32_t)i) {
-                    const uint8_t a_i = row[i], a_v = row[v];
+                    const Row a_i = row[i], a_v = row[v];
                     row[i] = a_v;
                     row[v] = a_i;
                     --i;
@@ -101,9 +119,13 @@ __device__ inline void perm_replay(Word word, int limit, int R, int p, uint8_t* 
 // The whole draw on one workgroup.  iq_sample_permutations launches it alone (keys == nullptr: the state comes from `state`).  The
 // workspace route launches it LAST: keys / reached are what the wide kernels below left - reached[0] permutations written,
 // reached[1] the word offset behind them in keys[] - and it draws whatever is missing (normally nothing) and hands the state back.
+// Of every permutation the first `head` entries are written, rows of `head` (head = R: the whole permutation; 0: the draw only
+// advances the state and `orders` is never touched).
+template <class Cfg>
 __global__ __launch_bounds__(kMtThreads) void mt_permutations_kernel(uint32_t* __restrict__ state, int32_t* __restrict__ orders, int S, int R,
-                                                                     const uint32_t* __restrict__ keys, const int* __restrict__ reached,
-                                                                     int nblk) {
+                                                                     int head, const uint32_t* __restrict__ keys,
+                                                                     const int* __restrict__ reached, int nblk) {
+    using Row = typename Cfg::Row;
     __shared__ uint32_t key[kMtBlocks][kMtN];      // block 0: the carried generator state; block k = twist of block k - 1
     __shared__ uint32_t word[kMtWords];            // tempered outputs of the batch
     __shared__ uint16_t nxt[kMtWords + 1];         // offset behind a permutation that starts at offset o (kMtInvalid: runs out of the batch)
@@ -124,7 +146,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_permutations_kernel(uint32_t* _
     if ((unsigned)pos > (unsigned)kMtN) {
         // a malformed state (np.random.set_state accepts any position) or one a failed call poisoned: draw nothing, write rows
         // that every range check rejects, keep the state poisoned so that the host sees it (hip_ops.mt_state_to_host raises)
-        for (int e = tid; e < S * R; e += kMtThreads) orders[e] = -1;
+        for (size_t e = tid; e < (size_t)S * head; e += kMtThreads) orders[e] = -1;
         if (tid == 0) state[kMtN] = kMtPoison;
         return;
     }
@@ -166,12 +188,25 @@ __global__ __launch_bounds__(kMtThreads) void mt_permutations_kernel(uint32_t* _
         }
         __syncthreads();
         const int n = ctl[0], cur = ctl[1];
-        // (4) replay with the swaps: one lane per permutation, its row as bytes in nxt[]'s storage (free once the chain is
-        // known; n rows of R bytes never exceed it: n <= 4992 / (R - 1) + 1), then one coalesced copy to global memory
-        uint8_t* rowbytes = reinterpret_cast<uint8_t*>(nxt);
-        for (int s = tid; s < n; s += kMtThreads) perm_replay(lds_word, kMtWords, R, start[s], rowbytes + s * R);
-        __syncthreads();
-        for (int e = tid; e < n * R; e += kMtThreads) orders[(size_t)done * R + e] = rowbytes[e];
+        // (4) replay with the swaps: one lane per permutation, its row in nxt[]'s storage (free once the chain is known), then
+        // one coalesced copy to global memory.  n rows of R bytes never exceed that storage (n <= 4992 / (R - 1) + 1); rows of
+        // 16-bit entries can, and are then replayed as many at a time as it holds (four of 1024 regions)
+        if (head > 0) {
+            Row* rows = reinterpret_cast<Row*>(nxt);
+            const int cap = (int)(sizeof(nxt) / (R * sizeof(Row)));
+            for (int r0 = 0; r0 < n; r0 += cap) {
+                const int nr = min(cap, n - r0);
+                for (int s = tid; s < nr; s += kMtThreads) perm_replay(lds_word, kMtWords, R, start[r0 + s], rows + s * R);
+                __syncthreads();
+                int32_t* out = orders + (size_t)(done + r0) * head;
+                if (head == R) {
+                    for (int e = tid; e < nr * R; e += kMtThreads) out[e] = rows[e];
+                } else {
+                    for (int e = tid; e < nr * head; e += kMtThreads) { const int s = e / head; out[e] = rows[s * R + (e - s * head)]; }
+                }
+                if (r0 + cap < n) __syncthreads();
+            }
+        }
         // carry the state: the block that holds `cur` becomes block 0 (cur == 624 k stays at the END of block k - 1, as NumPy
         // leaves its position at 624 until the next draw)
         const int kb = cur == 0 ? 0 : min((cur - 1) / kMtN, kMtBlocks - 1);
@@ -188,7 +223,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_permutations_kernel(uint32_t* _
     }
     for (int k = tid; k < kMtN; k += kMtThreads) state[k] = key[0][k];
     if (done < S) {                     // gave up: the rows not drawn are marked, and so is the state (see the entry check)
-        for (int e = done * R + tid; e < S * R; e += kMtThreads) orders[e] = -1;
+        for (size_t e = (size_t)done * head + tid; e < (size_t)S * head; e += kMtThreads) orders[e] = -1;
         pos = (int)kMtPoison;
     }
     if (tid == 0) state[kMtN] = (uint32_t)pos;
@@ -201,11 +236,11 @@ __global__ __launch_bounds__(kMtThreads) void mt_permutations_kernel(uint32_t* _
 // permutations, so that the chain of REAL starts is one hop per segment instead of one per permutation; mt_replay_kernel (one
 // workgroup per segment) takes those hops to its own segment, walks it, replays its permutations with the swaps and writes their
 // rows.  How many words S permutations draw is only known afterwards: nblk is an estimate, and mt_permutations_kernel runs last
-// and draws what the estimate missed.
+// and draws what the estimate missed.  iq_sample_permutations_wide (up to 1024 regions, `head` entries of a permutation, skip mode)
+// is the same kernels with MtWide for MtNarrow; mt_words_kernel and mt_jump_kernel do not depend on R.
 constexpr int kMtSeg = 4096;                       // word offsets per segment
 constexpr int kMtSegThreads = 1024;
 constexpr int kMtSegPer = kMtSeg / kMtSegThreads + 1;   // offsets per lane (the last segment also holds offset W)
-constexpr int kMtTail = 1024;                      // words behind a segment that mt_replay_kernel keeps in LDS (beyond: global reads)
 constexpr int kMtCtl = 16;                         // control words in front of the workspace
 constexpr uint32_t kMtNone = 0xffffffffu;          // next[]: the permutation runs out of the words
 
@@ -238,17 +273,19 @@ __global__ __launch_bounds__(256) void mt_words_kernel(const uint32_t* __restric
 }
 
 // next[o], o = 0..W: the offset behind a permutation that starts at offset o.  A workgroup keeps its 256 offsets' words and the
-// 256 behind them in LDS; a permutation that draws more reads the rest from memory.
+// `tail` (<= Cfg::kNextTail, a multiple of 256) behind them in LDS - the lanes of a wave start at consecutive offsets and read
+// nearly the same words; a permutation that draws more reads the rest from memory.
+template <class Cfg>
 __global__ __launch_bounds__(256) void mt_next_kernel(const uint32_t* __restrict__ keys, const int* __restrict__ ctl,
-                                                      uint32_t* __restrict__ next, int W, int R) {
-    __shared__ uint32_t win[512];
+                                                      uint32_t* __restrict__ next, int W, int R, int tail) {
+    __shared__ uint32_t win[256 + Cfg::kNextTail];
     if (ctl[2] == (int)kMtPoison) return;
-    const int base = blockIdx.x * 256, tid = threadIdx.x;
-    for (int k = tid; k < 512; k += 256) win[k] = base + k < W ? mt_temper(keys[base + k]) : 0u;
+    const int base = blockIdx.x * 256, tid = threadIdx.x, held = 256 + tail;
+    for (int k = tid; k < held; k += 256) win[k] = base + k < W ? mt_temper(keys[base + k]) : 0u;
     __syncthreads();
     const int o = base + tid;
     if (o > W) return;
-    const int p = perm_end([&](int k) { return k >= base && k < base + 512 ? win[k - base] : mt_temper(keys[k]); }, W, R, o);   // (k < base: o == W)
+    const int p = perm_end([&](int k) { return k >= base && k < base + held ? win[k - base] : mt_temper(keys[k]); }, W, R, o);   // (k < base: o == W)
     next[o] = p < 0 ? kMtNone : (uint32_t)p;
 }
 
@@ -293,11 +330,14 @@ __global__ __launch_bounds__(kMtSegThreads) void mt_jump_kernel(const uint32_t* 
     for (int k = tid; k < n; k += kMtSegThreads) hop[lo + k] = make_uint2(to[k], cnt[k]);
 }
 
+template <class Cfg>
 __global__ __launch_bounds__(kMtSegThreads) void mt_replay_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ next,
                                                                   const uint2* __restrict__ hop, int* __restrict__ ctl,
-                                                                  int32_t* __restrict__ orders, int S, int R, int W, int nseg) {
-    __shared__ uint32_t nx[kMtSeg + 1];            // next[] of the segment, later the rows as bytes
-    __shared__ uint32_t word[kMtSeg + kMtTail];
+                                                                  int32_t* __restrict__ orders, int S, int R, int head, int W, int nseg) {
+    using Row = typename Cfg::Row;
+    constexpr int kHeld = kMtSeg + Cfg::kReplayTail;   // words of the segment and behind it in LDS (beyond: global reads)
+    __shared__ uint32_t nx[kMtSeg + 1];            // next[] of the segment, later the rows
+    __shared__ uint32_t word[kHeld];
     __shared__ uint16_t start[kMtSeg + 1];         // real starts, relative to the segment
     __shared__ int sh[3];                          // first real start of the segment (-1: none), permutations before it, found here
     const int start_pos = ctl[2];
@@ -322,7 +362,8 @@ __global__ __launch_bounds__(kMtSegThreads) void mt_replay_kernel(const uint32_t
     const int entry = sh[0], before = sh[1];
     if (entry < 0) return;
     for (int k = tid; k < n_off; k += kMtSegThreads) nx[k] = next[lo + k];
-    for (int k = tid; k < kMtSeg + kMtTail; k += kMtSegThreads) word[k] = lo + k < W ? mt_temper(keys[lo + k]) : 0u;
+    if (head > 0)
+        for (int k = tid; k < kHeld; k += kMtSegThreads) word[k] = lo + k < W ? mt_temper(keys[lo + k]) : 0u;
     __syncthreads();
     if (tid == 0) {
         int x = entry, n = 0;
@@ -335,12 +376,19 @@ __global__ __launch_bounds__(kMtSegThreads) void mt_replay_kernel(const uint32_t
     }
     __syncthreads();
     const int n = sh[2];
-    // n rows of R bytes fit next[]'s storage: n <= kMtSeg / (R - 1) + 1
-    uint8_t* rowbytes = reinterpret_cast<uint8_t*>(nx);
-    const auto lds_word = [&](int k) { return k < lo + kMtSeg + kMtTail ? word[k - lo] : mt_temper(keys[k]); };
-    for (int s = tid; s < n; s += kMtSegThreads) perm_replay(lds_word, W, R, lo + start[s], rowbytes + s * R);
+    if (head == 0) return;                         // the draw only advances the state
+    // n rows fit next[]'s storage: n <= (kMtSeg - 1) / (R - 1) + 1 starts in a segment, of R bytes or R 16-bit entries each
+    // (R = 2: 4096 rows of 4 bytes; from there the product falls)
+    Row* rows = reinterpret_cast<Row*>(nx);
+    const auto lds_word = [&](int k) { return k < lo + kHeld ? word[k - lo] : mt_temper(keys[k]); };
+    for (int s = tid; s < n; s += kMtSegThreads) perm_replay(lds_word, W, R, lo + start[s], rows + s * R);
     __syncthreads();
-    for (int e = tid; e < n * R; e += kMtSegThreads) orders[(size_t)before * R + e] = rowbytes[e];
+    int32_t* out = orders + (size_t)before * head;
+    if (head == R) {
+        for (int e = tid; e < n * R; e += kMtSegThreads) out[e] = rows[e];
+    } else {
+        for (int e = tid; e < n * head; e += kMtSegThreads) { const int s = e / head; out[e] = rows[s * R + (e - s * head)]; }
+    }
 }
 
 // Blocks to twist ahead for S permutations of R regions: the words they draw - mean + 8 standard deviations - the 624 a start
@@ -406,19 +454,65 @@ __global__ __launch_bounds__(256) void context_keep_kernel(const int32_t* __rest
     out[3] = sset;
 }
 
+// The one-workgroup kernel alone.  `what`: the entry point's name for messages
+template <class Cfg>
+int mt_sample_one(const char* what, uint32_t* mt_state, int32_t* orders, int S, int R, int head, hipStream_t st) {
+    if (S == 0) return IQ_OK;
+    IQ_REQUIRE(mt_state && (orders || head == 0), "%s: null pointer", what);
+    if (R == 1) {                                  // nothing is drawn; a row is the one region
+        if (head == 0) return IQ_OK;
+        hipLaunchKernelGGL(zero_orders_kernel, dim3((S + 255) / 256), dim3(256), 0, st, orders, S);
+        return iq::check_launch("zero_orders_kernel");
+    }
+    hipLaunchKernelGGL(mt_permutations_kernel<Cfg>, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, head, nullptr, nullptr, 0);
+    return iq::check_launch("mt_permutations_kernel");
+}
+
+// The spread kernels over as many blocks as the workspace holds, then the one-workgroup kernel for what is left
+template <class Cfg>
+int mt_sample_ws(const char* what, uint32_t* mt_state, int32_t* orders, int S, int R, int head, void* workspace, size_t workspace_bytes,
+                 hipStream_t st) {
+    IQ_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+    // as many blocks ahead as the workspace holds, at most the estimate; under two there is nothing to spread
+    int nblk = 0;
+    if (workspace && S > 0 && R >= 2) {
+        nblk = mt_blocks_estimate(S, R);
+        while (nblk >= 2 && mt_workspace_bytes(nblk) > workspace_bytes)
+            nblk = (int)fmin(nblk - 1, (double)(workspace_bytes / (16 * kMtN)));
+    }
+    if (nblk < 2) return mt_sample_one<Cfg>(what, mt_state, orders, S, R, head, st);
+    IQ_REQUIRE(mt_state && (orders || head == 0), "%s: null pointer", what);
+    const int W = nblk * kMtN, nseg = (W + kMtSeg - 1) / kMtSeg;
+    int* ctl = static_cast<int*>(workspace);
+    uint32_t* keys = static_cast<uint32_t*>(workspace) + kMtCtl;
+    uint32_t* next = keys + W;
+    uint2* hop = reinterpret_cast<uint2*>(next + W + 2);
+    hipLaunchKernelGGL(mt_words_kernel, dim3(1), dim3(256), 0, st, mt_state, keys, ctl, nblk);
+    hipLaunchKernelGGL(mt_next_kernel<Cfg>, dim3(W / 256 + 1), dim3(256), 0, st, keys, ctl, next, W, R, Cfg::next_tail(R));
+    hipLaunchKernelGGL(mt_jump_kernel, dim3(nseg), dim3(kMtSegThreads), 0, st, next, ctl, hop, W, nseg);
+    hipLaunchKernelGGL(mt_replay_kernel<Cfg>, dim3(nseg), dim3(kMtSegThreads), 0, st, keys, next, hop, ctl, orders, S, R, head, W, nseg);
+    int rc = iq::check_launch("mt_words / mt_next / mt_jump / mt_replay kernels");
+    if (rc) return rc;
+    hipLaunchKernelGGL(mt_permutations_kernel<Cfg>, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, head, keys, ctl, nblk);
+    return iq::check_launch("mt_permutations_kernel");
+}
+
+// heads (P,C,m) of permutations of R - 2 -> region ids: entry k of the ascending list of the regions outside the pair
+__global__ __launch_bounds__(256) void context_regions_kernel(const int32_t* __restrict__ pairs, int32_t* __restrict__ heads, size_t total,
+                                                              int per_pair) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    const int p = (int)(t / (size_t)per_pair);
+    const int a = pairs[2 * p], b = pairs[2 * p + 1], lo = min(a, b), hi = max(a, b);
+    const int k = heads[t];
+    heads[t] = k + (k >= lo ? 1 : 0) + (k + 1 >= hi ? 1 : 0);
+}
+
 }  // namespace
 
 extern "C" int iq_sample_permutations(uint32_t* mt_state, int32_t* orders, int S, int R, iq_stream_t stream) {
     IQ_REQUIRE(S >= 0 && R >= 1 && R <= IQ_MAX_REGIONS, "iq_sample_permutations: S=%d R=%d", S, R);
-    if (S == 0) return IQ_OK;
-    IQ_REQUIRE(mt_state && orders, "iq_sample_permutations: null pointer");
-    hipStream_t st = iq::as_stream(stream);
-    if (R == 1) {
-        hipLaunchKernelGGL(zero_orders_kernel, dim3((S + 255) / 256), dim3(256), 0, st, orders, S);
-        return iq::check_launch("zero_orders_kernel");
-    }
-    hipLaunchKernelGGL(mt_permutations_kernel, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, nullptr, nullptr, 0);
-    return iq::check_launch("mt_permutations_kernel");
+    return mt_sample_one<MtNarrow>("iq_sample_permutations", mt_state, orders, S, R, R, iq::as_stream(stream));
 }
 
 extern "C" size_t iq_sample_workspace_bytes(int S, int R) {
@@ -429,30 +523,32 @@ extern "C" size_t iq_sample_workspace_bytes(int S, int R) {
 extern "C" int iq_sample_permutations_ws(uint32_t* mt_state, int32_t* orders, int S, int R, void* workspace, size_t workspace_bytes,
                                          iq_stream_t stream) {
     IQ_REQUIRE(S >= 0 && R >= 1 && R <= IQ_MAX_REGIONS, "iq_sample_permutations_ws: S=%d R=%d", S, R);
-    IQ_REQUIRE(((uintptr_t)workspace & 7) == 0, "iq_sample_permutations_ws: workspace must be 8-byte aligned");
-    // as many blocks ahead as the workspace holds, at most the estimate; under two there is nothing to spread
-    int nblk = 0;
-    if (workspace && S > 0 && R >= 2) {
-        nblk = mt_blocks_estimate(S, R);
-        while (nblk >= 2 && mt_workspace_bytes(nblk) > workspace_bytes)
-            nblk = (int)fmin(nblk - 1, (double)(workspace_bytes / (16 * kMtN)));
-    }
-    if (nblk < 2) return iq_sample_permutations(mt_state, orders, S, R, stream);
-    IQ_REQUIRE(mt_state && orders, "iq_sample_permutations_ws: null pointer");
-    hipStream_t st = iq::as_stream(stream);
-    const int W = nblk * kMtN, nseg = (W + kMtSeg - 1) / kMtSeg;
-    int* ctl = static_cast<int*>(workspace);
-    uint32_t* keys = static_cast<uint32_t*>(workspace) + kMtCtl;
-    uint32_t* next = keys + W;
-    uint2* hop = reinterpret_cast<uint2*>(next + W + 2);
-    hipLaunchKernelGGL(mt_words_kernel, dim3(1), dim3(256), 0, st, mt_state, keys, ctl, nblk);
-    hipLaunchKernelGGL(mt_next_kernel, dim3(W / 256 + 1), dim3(256), 0, st, keys, ctl, next, W, R);
-    hipLaunchKernelGGL(mt_jump_kernel, dim3(nseg), dim3(kMtSegThreads), 0, st, next, ctl, hop, W, nseg);
-    hipLaunchKernelGGL(mt_replay_kernel, dim3(nseg), dim3(kMtSegThreads), 0, st, keys, next, hop, ctl, orders, S, R, W, nseg);
-    int rc = iq::check_launch("mt_words / mt_next / mt_jump / mt_replay kernels");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mt_permutations_kernel, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, keys, ctl, nblk);
-    return iq::check_launch("mt_permutations_kernel");
+    return mt_sample_ws<MtNarrow>("iq_sample_permutations_ws", mt_state, orders, S, R, R, workspace, workspace_bytes, iq::as_stream(stream));
+}
+
+extern "C" size_t iq_sample_wide_workspace_bytes(int S, int R) {
+    if (S <= 0 || R < 2 || R > IQ_MAX_WIDE_REGIONS || mt_blocks_estimate(S, R) == 0) return 0;
+    return mt_workspace_bytes(mt_blocks_estimate(S, R));
+}
+
+extern "C" int iq_sample_permutations_wide(uint32_t* mt_state, int32_t* orders, int S, int R, int head, void* workspace,
+                                           size_t workspace_bytes, iq_stream_t stream) {
+    IQ_REQUIRE(S >= 0 && R >= 1 && R <= IQ_MAX_WIDE_REGIONS && head >= 0 && head <= R, "iq_sample_permutations_wide: S=%d R=%d head=%d", S,
+               R, head);
+    if (!orders) head = 0;                         // skip mode: the draw advances the state and writes nothing
+    return mt_sample_ws<MtWide>("iq_sample_permutations_wide", mt_state, orders, S, R, head, workspace, workspace_bytes,
+                                iq::as_stream(stream));
+}
+
+extern "C" int iq_context_regions_wide(const int32_t* pairs, int32_t* heads, int P, int C, int m, int R, iq_stream_t stream) {
+    IQ_REQUIRE(P >= 0 && C >= 0 && R >= 2 && R <= IQ_MAX_WIDE_REGIONS && m >= 0 && m <= R - 2, "iq_context_regions_wide: P=%d C=%d m=%d R=%d",
+               P, C, m, R);
+    const size_t total = (size_t)P * C * m;
+    if (total == 0) return IQ_OK;
+    IQ_REQUIRE(pairs && heads, "iq_context_regions_wide: null pointer");
+    hipLaunchKernelGGL(context_regions_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, iq::as_stream(stream), pairs, heads, total,
+                       C * m);
+    return iq::check_launch("context_regions_kernel");
 }
 
 extern "C" int iq_prefix_keep_masks(const int32_t* orders, uint64_t* keep, int S, int R, iq_stream_t stream) {

@@ -41,6 +41,18 @@ def gen_context(region_pair_list, save_path, args):
         np.save(save_path + "ratio%d_context_list.npy" % int(ratio * 100), context_list)
 
 
+def _rest(pairs, num_regions):
+    """(P, R-2): per pair the regions outside it, ascending, as the reference's all_S."""
+    regions = np.arange(int(num_regions))
+    return [regions[(regions != i) & (regions != j)] for i, j in pairs]
+
+
+def _enumerated(rest, m, dtype):
+    """All C(R-2, m) contexts of one pair, in itertools' order."""
+    listed = list(itertools.combinations(rest.tolist(), m))
+    return np.array(listed, dtype=dtype).reshape(len(listed), m)
+
+
 def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=None):
     """The reference's host loop (final_gen_pair.py:18-43), one ratio at a time: a generator of (P, C, m) arrays, drawn from
     NumPy's GLOBAL generator in the reference's order (ratio, pair, context).  ``dtype`` None: what the reference's
@@ -48,41 +60,59 @@ def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=None):
     wide.MAX_REGIONS regions."""
     r, cmax = int(num_regions), int(num_save_context_max)
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    regions = np.arange(r)
     for ratio in ratios:
         m = int((r - 2) * ratio)
         sampled = comb(r - 2, m) > cmax
         per_pair = []
-        for i, j in pairs:
-            rest = regions[(regions != i) & (regions != j)]        # ascending, as the reference's all_S
+        for rest in _rest(pairs, r):
             if sampled:
                 # np.random.choice(rest, m, replace=False) on the legacy generator: the head of a fresh permutation
                 per_pair.append(np.array([rest[np.random.permutation(rest.size)[:m]] for _ in range(cmax)], dtype=dtype).reshape(cmax, m))
             else:
-                listed = list(itertools.combinations(rest.tolist(), m))
-                per_pair.append(np.array(listed, dtype=dtype).reshape(len(listed), m))
+                per_pair.append(_enumerated(rest, m, dtype))
         yield np.stack(per_pair) if per_pair else np.zeros((0, 0, m), dtype=dtype)
+
+
+def iter_contexts_device(pairs, num_regions, ratios, num_save_context_max, dev, draw, dtype=None, skip=False):
+    """``iter_contexts`` with the sampled ratios drawn on the device, the one loop of the narrow and the wide stage: NumPy's global
+    generator goes to the device once before the ratios, runs through the sampled ones in the reference's order and comes back
+    once after the last of them (one sync), so that whatever the host draws next continues the reference's stream.
+    ``draw(state, pairs, m)`` -> the (P, C, m) host array of one sampled ratio's contexts (the sampler call and the ``rest``
+    mapping: what differs between narrow and wide).  The enumerated ratios come from itertools.combinations as on the host.
+    ``skip``: the caller only passes the stream over - ``draw`` returns None, and nothing is enumerated either."""
+    from . import hip_ops
+    r, cmax = int(num_regions), int(num_save_context_max)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    ms = [int((r - 2) * ratio) for ratio in ratios]
+    sampled = [comb(r - 2, m) > cmax for m in ms]
+    left = sum(sampled)
+    state = hip_ops.mt_state_to_device(dev) if left else None
+    rest = None
+    for m, is_sampled in zip(ms, sampled):
+        if is_sampled:
+            out = draw(state, pairs, m)
+            left -= 1
+            if left == 0:
+                hip_ops.mt_state_to_host(state, set_global=True)
+        elif skip:
+            out = None
+        else:
+            rest = _rest(pairs, r) if rest is None else rest
+            out = np.stack([_enumerated(row, m, dtype) for row in rest])
+        yield out
 
 
 def _gen_context_device(pairs, save_path, args, dev):
     from . import hip_ops
     n_rest, cmax, p = args.num_regions - 2, args.num_save_context_max, pairs.shape[0]
-    regions = np.arange(args.num_regions)
-    rest = np.stack([regions[(regions != i) & (regions != j)] for i, j in pairs])          # (P, R-2) ascending, as the reference's list
-    state = hip_ops.mt_state_to_device(dev)
-    drawn = {}
-    for ratio in args.ratio:            # the generator runs through the sampled ratios in the reference's order
-        m = int(n_rest * ratio)
-        if comb(n_rest, m) > cmax:
-            drawn[ratio] = hip_ops.sample_permutations(state, p * cmax, n_rest)
-    hip_ops.mt_state_to_host(state, set_global=True)                                        # one sync; NumPy goes on from here
-    for ratio in args.ratio:
-        m = int(n_rest * ratio)
-        if ratio in drawn:
-            first = drawn[ratio].cpu().numpy().astype(np.int64).reshape(p, cmax, n_rest)[:, :, :m]
-            context_list = np.take_along_axis(rest[:, None, :], first, axis=2)             # rest[perm[:m]]
-        else:
-            context_list = np.array([list(itertools.combinations(row.tolist(), m)) for row in rest])
+    rest = np.stack(_rest(pairs, args.num_regions))                                         # (P, R-2)
+
+    def draw(state, pairs, m):
+        first = hip_ops.sample_permutations(state, p * cmax, n_rest).cpu().numpy().astype(np.int64).reshape(p, cmax, n_rest)[:, :, :m]
+        return np.take_along_axis(rest[:, None, :], first, axis=2)                          # rest[perm[:m]]
+
+    contexts = iter_contexts_device(pairs, args.num_regions, args.ratio, cmax, dev, draw)
+    for ratio, context_list in zip(args.ratio, contexts):
         print(context_list.shape)
         np.save(save_path + "ratio%d_context_list.npy" % int(ratio * 100), context_list)
 

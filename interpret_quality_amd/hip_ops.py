@@ -415,6 +415,70 @@ def context_keep_masks_wide(pairs, contexts, num_regions):
     return keep
 
 
+SAMPLE_WIDE_WS_CAP = 128 << 20   # bytes of sampler scratch per device that sample_permutations_wide asks for at most
+
+
+def _wide_sample_call_size(lib, s, r, cap):
+    """The most permutations of ``r`` regions, at most ``s``, whose queried workspace stays within ``cap`` bytes (at least 1)."""
+    if lib.iq_sample_wide_workspace_bytes(s, r) <= cap:
+        return s
+    lo, hi = 1, s                      # the query never shrinks as S grows: lo fits (or is 1), hi does not
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if lib.iq_sample_wide_workspace_bytes(mid, r) <= cap else (lo, mid)
+    return lo
+
+
+def sample_permutations_wide(mt_state, num_samples, num_regions, head=None, skip=False, workspace_bytes=None):
+    """iq_sample_permutations_wide: the first ``head`` entries (None: all R) of S permutations of 1 <= R <= MAX_WIDE_REGIONS regions
+    continuing the generator ``mt_state`` (advanced in place, no sync) -> (S, head) int32.  ``skip``: draw, advance the state, write
+    and return nothing.  The scratch is iq_sample_wide_workspace_bytes's 16 bytes per estimated word (the key, next[] and an 8-byte
+    hop per word offset; about 1413 words per permutation of 1024 regions), and a large draw is cut into calls so that the scratch
+    tensor - one per device, shared with ``sample_permutations`` - stays under SAMPLE_WIDE_WS_CAP = 128 MiB: about 5900 permutations
+    of 1024 regions per call.  Rows and state do not depend on the cut.  ``workspace_bytes``: one call that lends the library
+    exactly that much instead (0 = the one-workgroup kernel alone; the result does not depend on it either)."""
+    lib = _lib.load()
+    s, r = int(num_samples), int(num_regions)
+    h = 0 if skip else r if head is None else int(head)
+    state = _dev(mt_state, torch.int32, "mt_state")
+    dev = mt_state.device
+    orders = None if skip else torch.empty((max(s, 0), max(h, 0)), dtype=torch.int32, device=dev)
+    per_call = s if workspace_bytes is not None or s <= 0 else _wide_sample_call_size(lib, s, r, SAMPLE_WIDE_WS_CAP)
+    done = 0
+    while True:
+        n = min(per_call, s - done)
+        nbytes = lib.iq_sample_wide_workspace_bytes(n, r) if workspace_bytes is None else int(workspace_bytes)
+        ws = _sample_ws.get(dev)
+        if nbytes and (ws is None or ws.numel() < nbytes):
+            ws = _sample_ws[dev] = None        # release the old tensor before the larger one is made
+            ws = _sample_ws[dev] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        out = ctypes.c_void_p(0) if orders is None or orders.numel() == 0 else ctypes.c_void_p(orders.data_ptr() + 4 * done * h)
+        _lib.check(lib.iq_sample_permutations_wide(state, out, n, r, h, _p(ws) if nbytes else ctypes.c_void_p(0), nbytes, _stream()),
+                   "iq_sample_permutations_wide")
+        done += n
+        if done >= s:
+            return orders
+
+
+def context_regions_wide(pairs, heads, num_regions):
+    """iq_context_regions_wide: ``heads`` (P,C,m) i32 device tensor, heads of permutations of R - 2, becomes IN PLACE the context
+    regions rest[heads] - rest the ascending regions outside the pair (final_gen_pair.py:25-29) - and is returned.  ``pairs``
+    (P,2): a host array (checked here: i != j, both in [0, R)) ."""
+    lib = _lib.load()
+    r = int(num_regions)
+    wide_words(r)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    check_host_indices(pairs, 0, r, "pairs")
+    if (pairs[:, 0] == pairs[:, 1]).any():
+        raise _lib.IqError("pairs: pair %d names one region twice" % int(np.flatnonzero(pairs[:, 0] == pairs[:, 1])[0]))
+    p, c, m = _shape(heads, "heads", pairs.shape[0], None, None)
+    if m > r - 2:
+        raise _lib.IqError("a context of %d regions does not fit beside a pair in %d" % (m, r))
+    _lib.check(lib.iq_context_regions_wide(_p(as_i32(pairs, heads.device)), _dev(heads, torch.int32, "heads"), p, c, m, r, _stream()),
+               "iq_context_regions_wide")
+    return heads
+
+
 def mask_coalitions_wide(cloud, region_id, keep, center, num_regions, channel_first=False):
     """cloud (N,3) f32, region_id (N,) i32, keep (B,W) i64, center (3,) f32 -> (B,N,3) or (B,3,N) (iq_mask_coalitions_wide)."""
     lib = _lib.load()

@@ -17,7 +17,9 @@ and the multi-order interactions of sampled (pair, context) coalitions (``gen_co
 wide_interaction_stage.py), and so do the stages that move the cloud: the pose sweeps (``shapley_over_poses`` - ``shapley``'s checks,
 launches and reward loop run per pose: ``_game``, ``_steps``, ``_rewards`` - and ``sharded_shapley``,
 wide_pose_stage.py) and the smoothness enumeration (smoothness.enumerate_smoothness with ``wide=True``, wide_smoothness_stage.py;
-clouds of at most 1024 points).  Not wide: the single-region folders of final_gen_pair.py.
+clouds of at most 1024 points).  The random draws - permutations and sampled contexts - come from NumPy's global generator on
+the host or, the same stream, from the device sampler (``gen_context`` / ``iter_contexts`` with ``device``, ``skip_contexts``;
+hip_ops.sample_permutations_wide).  Not wide: the single-region folders of final_gen_pair.py.
 """
 import numpy as np
 import torch
@@ -228,22 +230,62 @@ gen_pair_random = gen_pair.gen_pair_random            # final_gen_pair.py:288-30
 interactions = interaction.compute_order_interaction  # final_cal_interactions.py:14-37: reward and reduction never see a mask
 
 
-def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=np.int64):
+_DEVICE_DTYPES = {np.dtype(np.int16): torch.int16, np.dtype(np.int32): torch.int32, np.dtype(np.int64): torch.int64}
+
+
+def _device_draw(num_regions, cmax, dtype, skip=False):
+    """The ``draw`` of gen_pair.iter_contexts_device for a wide game: the heads of P * cmax permutations of R - 2
+    (hip_ops.sample_permutations_wide, head = m), mapped to regions on the device (hip_ops.context_regions_wide) and brought to
+    the host in ``dtype``; ``skip``: the draw only advances the generator."""
+    r = int(num_regions)
+
+    def draw(state, pairs, m):
+        p = pairs.shape[0]
+        heads = hip_ops.sample_permutations_wide(state, p * cmax, r - 2, head=m, skip=skip)
+        if skip:
+            return None
+        ctx = hip_ops.context_regions_wide(pairs, heads.reshape(p, cmax, m), r)
+        on_device = _DEVICE_DTYPES.get(np.dtype(dtype))
+        return (ctx if on_device is None else ctx.to(on_device)).cpu().numpy().astype(dtype, copy=False)
+    return draw
+
+
+def iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype=np.int64, device=None):
     """``gen_context`` one ratio at a time: a generator of (P, C, m) arrays of ``dtype`` (at R = 1024 one ratio's contexts are up
     to 30 000 x 1022 entries: a caller that saves them need not hold thirteen of them).  The draws are gen_pair.iter_contexts's,
-    the host loop of the narrow stage."""
+    the host loop of the narrow stage - or, with ``device`` (a GPU), the same draws from the device sampler
+    (gen_pair.iter_contexts_device: the loop of the narrow stage's device route), host arrays all the same."""
     hip_ops.wide_words(num_regions)
-    yield from gen_pair.iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype)
+    if device is not None and len(pairs) > 0:
+        hip_ops.check_host_indices(np.asarray(pairs), 0, int(num_regions), "pairs")
+        yield from gen_pair.iter_contexts_device(pairs, num_regions, ratios, num_save_context_max, device,
+                                                 _device_draw(num_regions, int(num_save_context_max), dtype), dtype)
+    else:
+        yield from gen_pair.iter_contexts(pairs, num_regions, ratios, num_save_context_max, dtype)
 
 
-def gen_context(pairs, num_regions, ratios, num_save_context_max):
+def skip_contexts(num_pairs, num_regions, ratios, num_save_context_max, device):
+    """Advance NumPy's GLOBAL generator past the contexts of one cloud with ``num_pairs`` pairs, as ``gen_context`` would leave it,
+    on the device and without writing anything (iq_sample_permutations_wide's skip mode): the contexts of a cloud that is not
+    selected.  How many words a draw consumes does not depend on the pairs."""
+    hip_ops.wide_words(num_regions)
+    pairs = np.zeros((int(num_pairs), 2), dtype=np.int64)
+    draw = _device_draw(num_regions, int(num_save_context_max), np.int64, skip=True)
+    if int(num_pairs) > 0:
+        for _ in gen_pair.iter_contexts_device(pairs, num_regions, ratios, num_save_context_max, device, draw, skip=True):
+            pass
+
+
+def gen_context(pairs, num_regions, ratios, num_save_context_max, device=None):
     """final_gen_pair.py:18-43 for any region count: for each ratio (in order) the (P, C, m) int64 contexts of the (P,2) ``pairs``,
     m = int((R-2)*ratio) regions out of the R-2 that are not in the pair - ``num_save_context_max`` sampled ones per pair when
-    C(R-2, m) exceeds that number, otherwise all combinations.  The draws come from NumPy's GLOBAL generator on the host in the
+    C(R-2, m) exceeds that number, otherwise all combinations.  The draws come from NumPy's GLOBAL generator in the
     reference's order (ratio, pair, context), each as rest[np.random.permutation(R-2)[:m]] - what the reference's
     np.random.choice(rest, m, replace=False) does on the legacy generator, without its per-call overhead: 390 000 draws at
-    R = 1024 take seconds.  The device sampler (gen_pair.gen_context with ``args.device``) stays a 64-region kernel."""
-    return list(iter_contexts(pairs, num_regions, ratios, num_save_context_max))
+    R = 1024 take seconds on the host.  With ``device`` (a GPU) the generator is continued there for the sampled ratios
+    (iq_sample_permutations_wide: the narrow stage's sampler for up to MAX_REGIONS regions) and handed back: the same arrays, and
+    the same generator state afterwards."""
+    return list(iter_contexts(pairs, num_regions, ratios, num_save_context_max, device=device))
 
 
 def _pairs_contexts(pairs, contexts, r):

@@ -20,7 +20,9 @@ row would.  The two flags exclude each other.
 Deviations from the reference, both for size: the context lists are saved in the narrowest integer type that holds R (int16; at
 R = 1024 the reference's int64 would be 1.4 GB per cloud - nothing but this driver reads these files), and pairs and contexts are
 saved for the selected clouds only.  The random stream is final_gen_pair.py's for ``--seed <k>``: NumPy's global generator, seeded
-with ``--gen_pair_seed``, draws the pairs of ALL clouds first and then the contexts of all clouds, selected or not.  Not here
+with ``--gen_pair_seed``, draws the pairs of ALL clouds first and then the contexts of all clouds, selected or not - on the host,
+or with ``--sampler device`` the pairs on the host and the contexts on the GPU (wide.iter_contexts with a device: the same stream,
+the same files byte for byte; the contexts of a cloud that is not selected are passed over without being written).  Not here
 (DESIGN.md 5e): the single-region folders of final_gen_pair.py (at R = 128 there are 128 of them, each with its own contexts) and
 sharding over ranks - under several ranks rank 0 does the work and the others wait.
 """
@@ -50,12 +52,17 @@ def draw(args, names, wanted):
     """The pairs of all clouds, then the contexts of all clouds (gen_pair.run's order); saved for the clouds of ``wanted``."""
     pairs = [wide.gen_pair_random(args) for _ in names]
     last = max(wanted)           # nothing later in this call reads the stream: the contexts of the clouds after it are not drawn
+    dev = args.device if getattr(args, "sampler", "host") == "device" else None     # --sampler device: the same stream on the GPU
     for i in range(last + 1):
         folder = _folder(args, names[i])
         if i in wanted:
             mkdir(folder + "normal/")
             np.save(folder + "region_pair_list.npy", pairs[i])
-        contexts = wide.iter_contexts(pairs[i], args.num_regions, args.ratio, args.num_save_context_max, dtype=CONTEXT_DTYPE)
+        elif dev is not None:    # passed over in the sampler's skip mode: nothing is written, nothing comes to the host
+            wide.skip_contexts(len(pairs[i]), args.num_regions, args.ratio, args.num_save_context_max, dev)
+            continue
+        contexts = wide.iter_contexts(pairs[i], args.num_regions, args.ratio, args.num_save_context_max, dtype=CONTEXT_DTYPE,
+                                      device=dev)
         for ratio, context_list in zip(args.ratio, contexts):      # one ratio resident at a time
             if i in wanted:
                 np.save(folder + "ratio%d_context_list.npy" % int(ratio * 100), context_list)

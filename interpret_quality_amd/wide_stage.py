@@ -6,15 +6,16 @@ derives from ``--num_regions`` - so a run never overwrites a 32-region run:
 
     region_id.npy  norm_factor.npy  all_orders.npy  shapley/<i>_<count>.npy  region_shapley/<i>_<count>.npy  region_sv_all.npy
 
-The permutations come from NumPy's global generator on the host, exactly as the reference's generate_all_orders draws them
-(final_shapley_value.py:59-72); the device sampler of stage 1 stays a 64-region kernel.  The FPS centres go to their own
+The permutations come from NumPy's global generator, exactly as the reference's generate_all_orders draws them
+(final_shapley_value.py:59-72): on the host, or with ``--sampler device`` the same stream continued on the GPU (stage 1's device
+sampler in its wide form, iq_sample_permutations_wide; the same all_orders.npy byte for byte).  The FPS centres go to their own
 fps_<dataset>_<N>_<R>_index_final30.npy.  ``--route prefix|keep`` picks how ``wide.shapley`` evaluates the prefix coalitions (the
 same bits either way), ``--coalitions dense|compact`` how a family other than PointNet evaluates them (wide.py).  Single process: under several ranks rank 0 does the work and the others wait.  The
 multi-order interactions on these region ids: final_wide_interaction.py (wide_interaction_stage.py); the pose sweeps and the
 smoothness stage on these region ids and permutations: final_wide_pose.py (wide_pose_stage.py) and final_wide_smoothness.py
 (wide_smoothness_stage.py), sharded over the ranks.
 
-What the four wide stages share lives here too: the --route / --coalitions / --num_samples flags, the region-count message, the
+What the four wide stages share lives here too: the --route / --coalitions / --num_samples / --sampler flags, the region-count message, the
 checks after finish_args, the "not found: run ... first" check of an earlier stage's files, and ``GAME`` - the wide game that the
 pose and smoothness stages pass to pose_sweep's and smoothness's per-cloud loops.
 """
@@ -33,8 +34,16 @@ MIN_REGIONS = 65          # up to 64 regions: final_shapley_value.py
 
 
 # ---- what the four wide stages share: flags, checks, stage 1's files -------------------------------
+SAMPLERS = ("host", "device")
+
+
 def add_wide_flags(parser, route=True, num_samples=False):
-    """--coalitions, and where the stage has them --route and --num_samples."""
+    """--coalitions and --sampler, and where the stage has them --route and --num_samples."""
+    parser.add_argument("--sampler", choices=SAMPLERS, default="host",
+                        help="where final_wide_shapley.py draws the permutations and final_wide_interaction.py the sampled contexts: host = "
+                             "NumPy's global generator, device = the same stream continued on the GPU (iq_sample_permutations_wide); the "
+                             "same artefacts, byte for byte.  The stages that draw nothing take the flag and ignore it (scripts/exp_wide.sh "
+                             "passes one EXTRA to all of them)")
     if route:
         parser.add_argument("--route", choices=wide.ROUTES, default=None,
                             help="how the prefix coalitions are evaluated: prefix = straight from the permutations (PointNet), keep = "
@@ -99,10 +108,31 @@ def sharded_shapley(model, data, poses, lbl, region_id, orders, args):
 GAME = pose_sweep.Game(selected_folders, load_orders, sharded_shapley)   # the wide game of the pose and smoothness stages
 
 
+def _device_orders(args, skip=False):
+    """``num_samples_save`` permutations from NumPy's GLOBAL generator, continued on the device and handed back (one sync)."""
+    state = hip_ops.mt_state_to_device(args.device)
+    orders = hip_ops.sample_permutations_wide(state, args.num_samples_save, args.num_regions, skip=skip)
+    hip_ops.mt_state_to_host(state, set_global=True)
+    return None if skip else orders.cpu().numpy().astype(np.int64)
+
+
+def skip_all_orders(result_path, args, save=False):
+    """What ``generate_all_orders`` draws, drawn and dropped: the permutations of a cloud that is not selected.  With
+    ``--sampler device`` the device sampler's skip mode: nothing is written anywhere."""
+    if getattr(args, "sampler", "host") == "device":
+        _device_orders(args, skip=True)
+    else:
+        generate_all_orders(result_path, args, save=False)
+
+
 def generate_all_orders(result_path, args, save=True):
-    """final_shapley_value.py:59-72 as it stands: ``num_samples_save`` permutations of 0..R-1 from NumPy's GLOBAL generator."""
-    rows = [np.random.permutation(np.arange(0, args.num_regions, 1)).reshape((1, -1)) for _ in range(args.num_samples_save)]
-    all_orders = np.concatenate(rows, axis=0)
+    """final_shapley_value.py:59-72 as it stands: ``num_samples_save`` permutations of 0..R-1 from NumPy's GLOBAL generator - on the
+    host, or with ``--sampler device`` the same stream on the device (the same int64 array, the same generator state afterwards)."""
+    if getattr(args, "sampler", "host") == "device":
+        all_orders = _device_orders(args)
+    else:
+        rows = [np.random.permutation(np.arange(0, args.num_regions, 1)).reshape((1, -1)) for _ in range(args.num_samples_save)]
+        all_orders = np.concatenate(rows, axis=0)
     if save:
         np.save(result_path + "all_orders.npy", all_orders)
     return all_orders
@@ -120,7 +150,7 @@ def cal_region_id(data, fps_index, result_path, save=True):
 def run(args):
     model = load_model(args)
     with torch.no_grad():
-        for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), generate_all_orders):
+        for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), skip_all_orders):
             region_id = cal_region_id(data, fps_index, result_path)
             center = torch.mean(data, dim=1).squeeze()
             stage1.cal_norm_factor(model, data, lbl, center, result_path, args)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The wide pipeline (65 .. 1024 regions): stage 1, the three pose sweeps, the smoothness stage and the multi-order interactions
-# at the sweep's adversarial pose.  Variables as in scripts/exp_shapley.sh: pass --synthetic / --num_regions R through EXTRA;
+# at the sweep's adversarial pose.  Variables as in scripts/exp_shapley.sh: pass --synthetic / --num_regions R / --sampler device through EXTRA;
 # prefix with "torchrun --nproc-per-node N" via LAUNCH to shard the pose and smoothness stages over N GPUs (stage 1 and the
 # interaction stage run on rank 0).
 model="pointnet";

@@ -7,6 +7,8 @@
     python tools/bench_wide.py --interaction            # the interaction stage only, into the "interaction" key of --out
     python tools/bench_wide.py --compact                # the other families, dense against compact, into the "compact" key of --out
     python tools/bench_wide.py --poses                  # a pose sweep, one wide.shapley per pose against wide.shapley_over_poses, into "poses"
+    python tools/bench_wide.py --sampler                # the draws of a wide game, host against device, into the "sampler" key of --out
+    python tools/bench_wide.py --profile-sampler 1024   # one warmed device draw of one ratio only: the program for rocprofv3 --kernel-trace --stats
 
 1. Wide against narrow at R = 32 (the headline's workload: 1000 permutations, 33 000 coalitions) and R = 64: the SAME coalitions
    through iq_pointnet_coalitions (the yardstick: untouched code) and iq_pointnet_coalitions_wide, alternated in one process,
@@ -42,6 +44,16 @@
    median and spread of each arm, whether the values are the same bits, and ``batched_slower_beyond_spread`` /
    ``batched_faster`` - batching poses across launches stays only if it is slower beyond the larger spread at neither region
    count and faster at one of them (``batching_stays_by_the_rule``).  Into the "poses" key of --out.
+
+7. ``--sampler``: the random draws of a wide game, NumPy's global generator on the host (the yardstick: the parent's code path,
+   untouched) against the same stream on the device (iq_sample_permutations_wide), alternated in one process after a warm-up of
+   both, five runs each, every side up to and including the host array the driver saves.  (a) One ratio of the interaction
+   driver's default job - 300 pairs x 100 contexts at ratio 0.5, an int16 array - at R = 128 and R = 1024 through
+   wide.iter_contexts; (b) the same ratio passed over, as for a cloud that is not selected: the host has no way to pass a draw
+   over but to draw it, the device runs wide.skip_contexts; (c) stage 1's 1000 permutations at R = 1024 through
+   wide_stage.generate_all_orders (an int64 array).  Reported per leg: seconds of every run, median and spread of each side, the
+   ratio of the medians, ``device_faster_beyond_spread`` and whether both sides gave the same bits from the same seed.  Into the
+   "sampler" key of --out.  No threshold hangs on these numbers and the drivers' default stays ``--sampler host``.
 
 Times are host clocks around work that ends in a device synchronise.  Kernel shares come from a separate run under the profiler
 (--profile-step): tracing slows the host, so no rate is taken there."""
@@ -307,6 +319,64 @@ def interaction_wide_vs_narrow(model, repeats, dev, r=64, pairs_n=300, ctx_n=100
     return out
 
 
+def _seconds(ts):
+    med = statistics.median(ts)
+    return {"seconds": ts, "median": med, "spread": (max(ts) - min(ts)) / med}
+
+
+def _host_vs_device(name, host, device, repeats, same):
+    """``host`` and ``device`` alternated after a warm-up of both; ``same(a, b)``: the two results from one seed are the same bits."""
+    np.random.seed(1)
+    a = host()
+    np.random.seed(1)
+    b = device()
+    th, td = [], []
+    for _ in range(repeats):
+        th.append(_clock(host)[0])
+        td.append(_clock(device)[0])
+    out = {"leg": name, "host": _seconds(th), "device": _seconds(td), "same_bits": bool(same(a, b))}
+    out["ratio_host_over_device"] = out["host"]["median"] / out["device"]["median"]
+    out["device_faster_beyond_spread"] = out["ratio_host_over_device"] - 1.0 > max(out["host"]["spread"], out["device"]["spread"])
+    return out
+
+
+def _sampler_ratio(r, dev, pairs_n=300, ctx_n=100, ratio=0.5):
+    """One ratio of final_wide_interaction.py's default draw at R regions -> (host, device, device skip) callables."""
+    from interpret_quality_amd import wide
+    from interpret_quality_amd.wide_interaction_stage import CONTEXT_DTYPE
+    np.random.seed(0)
+    pairs = wide.gen_pair_random(argparse.Namespace(num_regions=r, num_pairs_random=pairs_n))
+
+    def draw(device):
+        return next(iter(wide.iter_contexts(pairs, r, [ratio], ctx_n, dtype=CONTEXT_DTYPE, device=device)))
+    return (lambda: draw(None)), (lambda: draw(dev)), (lambda: wide.skip_contexts(pairs_n, r, [ratio], ctx_n, dev))
+
+
+def sampler_host_vs_device(repeats, dev, regions=(128, 1024), perms=1000):
+    from interpret_quality_amd import wide_stage
+    legs = []
+    for r in regions:
+        host, device, skip = _sampler_ratio(r, dev)
+        leg = _host_vs_device("one ratio: 300 pairs x 100 contexts, ratio 0.5", host, device, repeats,
+                              lambda a, b: a.dtype == b.dtype and np.array_equal(a, b))
+        legs.append(dict(leg, regions=r, permutations=30000))
+
+        def state_after(fn):
+            fn()
+            st = np.random.get_state()
+            return st[1].copy(), st[2]
+        leg = _host_vs_device("the same ratio passed over", lambda: state_after(host), lambda: state_after(skip), repeats,
+                              lambda a, b: np.array_equal(a[0], b[0]) and a[1] == b[1])
+        legs.append(dict(leg, regions=r, permutations=30000))
+    r = max(regions)
+    ns = {s: argparse.Namespace(num_regions=r, num_samples_save=perms, sampler=s, device=dev) for s in ("host", "device")}
+    leg = _host_vs_device("stage 1: all_orders", lambda: wide_stage.generate_all_orders(None, ns["host"], save=False),
+                          lambda: wide_stage.generate_all_orders(None, ns["device"], save=False), repeats,
+                          lambda a, b: a.dtype == b.dtype and np.array_equal(a, b))
+    legs.append(dict(leg, regions=r, permutations=perms))
+    return legs
+
+
 def _write(path, res):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
@@ -333,6 +403,12 @@ def main(argv=None):
     ap.add_argument("--poses", action="store_true",
                     help="time a pose sweep, one wide.shapley per pose against wide.shapley_over_poses (leg 6), and put it under "
                          "\"poses\" in --out, keeping what is there")
+    ap.add_argument("--sampler", action="store_true",
+                    help="time the draws of a wide game, host against device (leg 7), and put it under \"sampler\" in --out, keeping what "
+                         "is there")
+    ap.add_argument("--profile-sampler", type=int, default=0, metavar="R",
+                    help="run one warmed device draw of one ratio at R regions and exit (the program to put under rocprofv3 "
+                         "--kernel-trace --stats)")
     ap.add_argument("--families", nargs="+", choices=COMPACT_FAMILIES, default=list(COMPACT_FAMILIES), help="the families of --compact")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -350,6 +426,18 @@ def main(argv=None):
             torch.cuda.empty_cache()
         res["compact"] = {"device": torch.cuda.get_device_name(0), "repeats": 5, "legs": legs}
         _write(args.out, res)
+        return
+    if args.sampler:
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        res["sampler"] = dict(res.get("sampler", {}), device=torch.cuda.get_device_name(0), repeats=max(5, args.repeats),
+                              legs=sampler_host_vs_device(max(5, args.repeats), dev))
+        _write(args.out, res)
+        return
+    if args.profile_sampler:
+        _, device, _ = _sampler_ratio(args.profile_sampler, dev)
+        device()
+        t, _ = _clock(device)
+        print(json.dumps({"profile_sampler_regions": args.profile_sampler, "permutations": 30000, "runs": 2, "seconds_under_profiler": t}))
         return
     model = _model(dev)
     if args.profile_step:
