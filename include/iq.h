@@ -65,8 +65,9 @@ enum {
  * 110: one new entry point, no layout change (iq_smoothness_enum_wide: the smoothness enumeration of a wide game).
  * 112: one new diagnostic entry point, no layout change and no workspace size changed (iq_debug.h: iq_debug_pointnet_reps).
  * 113: new entry points, no layout change (the device sampler for wide games: iq_sample_wide_workspace_bytes,
- * iq_sample_permutations_wide, iq_context_regions_wide). */
-#define IQ_ABI_VERSION 113
+ * iq_sample_permutations_wide, iq_context_regions_wide).
+ * 114: new entry points, no layout change (the regression estimator of Shapley values: iq_kshap_keep_masks .. iq_kshap_solve). */
+#define IQ_ABI_VERSION 114
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -585,6 +586,45 @@ int iq_exact_interactions(const float* v, int n, const int32_t* pairs /*P,2*/, i
  * Ties the two reductions above down: phi_k = sum over {c with bit k} of a[c] / |c|, and the interaction term of context S is
  * the sum of a[T + {i,j}] over the subsets T of S. */
 int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The regression (KernelSHAP) estimator of Shapley values (csrc/iq_kshap.hip)
+ *
+ * The reference estimates Shapley values from sampled permutations only (final_shapley_value.py:138-156).  The weighted
+ * least-squares estimator takes M coalition rows z_m in {0,1}^n of a game of 2 <= n <= IQ_MAX_REGIONS regions, weights w_m (all 1
+ * when the rows are sampled from the Shapley kernel), rewards v(z_m), v0 = v(empty) and delta = v(all) - v(empty):
+ *     A = (1/W) sum w_m z_m z_m^T,   b = (1/W) sum w_m z_m ((double)v(z_m) - v0),   W = sum w_m,
+ *     x = A^-1 b,  y = A^-1 1,  phi = x - y (1^T x - delta) / (1^T y)          (so sum(phi) = delta by construction).
+ * With all 2^n - 2 proper coalitions and w(S) = (n-1) / (C(n,|S|) |S| (n-|S|)) phi is the exact Shapley vector.  The three entry
+ * points below build the rows, reduce them to the RAW sums (the caller divides by W) and solve.  All float64 sums are taken in an
+ * order that depends on (M, n, G) only - no floating-point atomics - so two calls give the same bits; G games that share the
+ * rows (the poses of a sweep) give per game the bits of a call with G = 1.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Row m of a sampled game: the regions orders[m][0 .. sizes[m]-1] of permutation m (iq_sample_permutations) as a keep mask.
+ * paired != 0: keep[2m] = that set, keep[2m+1] = its complement within the n bits (keep holds 2S masks); else keep[m] (S masks).
+ * status (1 int32, device, zeroed by the caller) becomes 1 if a size lies outside 1 .. n-1 and 2 if an order entry lies outside
+ * [0, n); such a row is written as 0, nothing is read out of bounds, and the caller reads status when it needs the verdict. */
+int iq_kshap_keep_masks(const int32_t* orders /*S,n*/, const int32_t* sizes /*S*/, uint64_t* keep /*M*/, int S, int n, int paired,
+                        int32_t* status /*1, device*/, iq_stream_t stream);
+
+/* Scratch (bytes) of iq_kshap_accum; 0 for arguments out of range (M outside 1 .. 2^30, n outside 2 .. 64, G outside 1 .. 65535). */
+size_t iq_kshap_scratch_bytes(int M, int n, int G);
+
+/* The raw moments of M rows shared by G games: A[i][j] = sum w_m z_mi z_mj (n,n), b[g][i] = sum w_m z_mi ((double)v[g][m] - v0[g])
+ * (G,n), wsum = sum w_m; bit i of keep[m] is z_mi (every bit 0 .. 63 alike).  weights == NULL: w_m = 1, A holds co-occurrence
+ * counts accumulated in integers (exact, order-free) and wsum = M.  Rows are summed in row order within a chunk of rows and the
+ * chunks in chunk order by a second kernel; the chunking is a function of M alone. */
+int iq_kshap_accum(const uint64_t* keep /*M*/, const float* v /*G,M*/, const double* v0 /*G*/, const double* weights /*M or NULL*/,
+                   int M, int n, int G, double* A /*n,n*/, double* b /*G,n*/, double* wsum /*1*/, void* scratch, size_t scratch_bytes,
+                   iq_stream_t stream);
+
+/* phi[g] = x - y (1^T x - delta[g]) / (1^T y) with x = A^-1 b[g], y = A^-1 1: one workgroup, float64 Cholesky of A in LDS and two
+ * triangular solves per right-hand side.  A (n,n) symmetric (the lower triangle is read), any positive scale common to A and b
+ * aside.  status (1 int32, device) becomes 0, or 1 when a pivot is <= n 2^-52 max_i A_ii (or NaN): the rows do not determine
+ * the regression, phi is left unwritten. */
+int iq_kshap_solve(const double* A /*n,n*/, const double* b /*G,n*/, const double* delta /*G*/, double* phi /*G,n*/,
+                   int32_t* status /*1, device*/, int n, int G, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

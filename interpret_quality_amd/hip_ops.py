@@ -327,6 +327,84 @@ def moebius(v):
     return a
 
 
+MAX_KSHAP_REGIONS = 64      # IQ_MAX_REGIONS: the regression estimator's rows are one uint64 each
+
+
+class KshapSingular(_lib.IqError):
+    """kshap_solve: the rows behind A do not determine the regression."""
+
+
+def kshap_regions(n):
+    """The region count of a game the regression estimator takes, as an int (IqError outside 2 .. 64)."""
+    n = int(n)
+    if not 2 <= n <= MAX_KSHAP_REGIONS:
+        raise _lib.IqError("the regression estimator takes 2 .. %d regions, got %d" % (MAX_KSHAP_REGIONS, n))
+    return n
+
+
+def kshap_keep_masks(orders, sizes, paired=True):
+    """orders (S,n) i32 permutations, sizes (S,) i32 in 1 .. n-1 -> int64-typed keep masks (iq_kshap_keep_masks): the first
+    sizes[m] entries of permutation m; ``paired``: (2S,) with every set followed by its complement within the n bits, else (S,).
+    A size outside 1 .. n-1 or an order entry outside [0, n) raises IqError (one 4-byte read back)."""
+    lib = _lib.load()
+    _dev(orders, torch.int32, "orders")
+    s, n = _shape(orders, "orders", None, None)
+    n = kshap_regions(n)
+    _shape(sizes, "sizes", s)
+    keep = torch.empty((2 * s if paired else s,), dtype=torch.int64, device=orders.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=orders.device)
+    _lib.check(lib.iq_kshap_keep_masks(_p(orders), _dev(sizes, torch.int32, "sizes"), _p(keep), s, n, int(bool(paired)), _p(status),
+                                       _stream()), "iq_kshap_keep_masks")
+    verdict = int(status.item()) if s else 0
+    if verdict:
+        raise _lib.IqError("kshap_keep_masks: " + ("a size lies outside 1 .. %d" % (n - 1) if verdict == 1
+                                                   else "an order entry lies outside [0, %d)" % n))
+    return keep
+
+
+def kshap_accum(keep, v, v0, n, weights=None):
+    """keep (M,) int64-typed rows, v (G,M) f32 rewards of G games on those rows, v0 (G,) f64, weights (M,) f64 or None (all 1) ->
+    (A (n,n) f64, b (G,n) f64, wsum (1,) f64): the RAW sums A = sum w z z^T, b[g] = sum w z (v[g] - v0[g]), wsum = sum w
+    (iq_kshap_accum: float64 in a fixed order, bitwise repeatable; without weights A holds exact counts and wsum = M)."""
+    lib = _lib.load()
+    n = kshap_regions(n)
+    m, = _shape(keep, "keep", None)
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    if weights is not None:
+        _shape(weights, "weights", m)
+    dev = keep.device
+    nbytes = lib.iq_kshap_scratch_bytes(m, n, g)
+    if nbytes == 0:
+        raise _lib.IqError("kshap_accum: M=%d rows, n=%d regions, G=%d games is out of range" % (m, n, g))
+    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    a = torch.empty((n, n), dtype=torch.float64, device=dev)
+    b = torch.empty((g, n), dtype=torch.float64, device=dev)
+    wsum = torch.empty((1,), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_accum(_dev(keep, torch.int64, "keep"), _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"),
+                                  _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0), m, n, g,
+                                  _p(a), _p(b), _p(wsum), _p(scratch), nbytes, _stream()), "iq_kshap_accum")
+    return a, b, wsum
+
+
+def kshap_solve(a, b, delta):
+    """a (n,n) f64 symmetric positive definite, b (G,n) f64, delta (G,) f64 -> phi (G,n) f64 with a phi[g] + lambda 1 = b[g] and
+    sum(phi[g]) = delta[g] (iq_kshap_solve: one workgroup, Cholesky in LDS).  IqError when the rows behind ``a`` do not
+    determine the regression (a status word read back, not a fault)."""
+    lib = _lib.load()
+    n = kshap_regions(_shape(a, "a", None, None)[0])
+    _shape(a, "a", n, n)
+    g, _ = _shape(b, "b", None, n)
+    _shape(delta, "delta", g)
+    phi = torch.empty((g, n), dtype=torch.float64, device=a.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=a.device)
+    _lib.check(lib.iq_kshap_solve(_dev(a, torch.float64, "a"), _dev(b, torch.float64, "b"), _dev(delta, torch.float64, "delta"),
+                                  _p(phi), _p(status), n, g, _stream()), "iq_kshap_solve")
+    if int(status.item()):
+        raise KshapSingular("the sampled coalitions do not determine the regression: draw more samples or use gram='analytic'")
+    return phi
+
+
 def region_assign(cloud, fps_idx):
     lib = _lib.load()
     n = cloud.shape[0]

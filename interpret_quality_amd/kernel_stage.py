@@ -1,0 +1,135 @@
+"""final_kernel_shapley.py - region Shapley values by the regression (KernelSHAP) estimator (kernelshap.py; the reference has
+none: it only walks sampled permutations, shapley_stage.py).
+
+Per selected cloud, under the experiment folder that ``exp_folder`` derives from ``--num_regions`` (2 to 64, default 32):
+
+    kernelshap/coalitions.npy                     (M,) uint64    the sampled rows, bit r = region r kept
+    kernelshap/rewards.npy                        (M,) float32   their rewards
+    kernelshap/region_shapley_value.npy           (n,) float64   the estimate from all M rows
+    kernelshap/running_counts.npy                 (k,) int64     row counts c (n + 1), c in stage 1's sample counts, <= M
+    kernelshap/running_region_shapley_value.npy   (k, n) float64 the estimate from the first count rows
+    kernelshap/sampling_error.json                with --compare_exact (at most 24 regions): per count the max and RMS error, in
+                                                  reward units, of this estimator and of stage 1's permutation estimate at the same
+                                                  number of model evaluations, against exact.shapley of the same cloud; the last row
+                                                  is the largest budget both have
+
+``--samples`` is the number of rows M (model evaluations; default 1000 (n + 1), stage 1's budget; ``all``: the enumerated game).
+With --compare_exact both estimates are read off ONE exact value table, not run through the network again; the permutations are
+the ones stage 1 would draw at this point of the stream, and the generator is put back afterwards, so the flag does not change
+what any cloud draws.  Single process: under several ranks rank 0 does the work and the others wait at the end.
+"""
+import json
+
+import numpy as np
+import torch
+
+from . import dist as iqdist
+from . import exact, hip_ops, kernelshap
+from . import shapley_stage as stage1
+from .final_util import NUM_REGIONS, get_folder_name_list, load_model, mkdir
+
+
+def _errors(est, phi):
+    err = np.asarray(est) - phi
+    return {"max_abs_error": float(np.abs(err).max()), "rms_error": float(np.sqrt((err ** 2).mean()))}
+
+
+def compare_exact(model, data, lbl, region_id, keep, args):
+    """-> (exact phi, rows of sampling_error.json): for every sample count c of stage 1 whose c (n + 1) evaluations both
+    estimators have, and for the largest number of permutations both have, the errors of the permutation estimate of c
+    permutations and of this estimator's first c (n + 1) rows."""
+    n = args.num_regions
+    v = exact.value_table(model, data, lbl, region_id, args)
+    phi, _, _ = exact.shapley(model, data, lbl, region_id, args, v=v)
+    if args.samples == "all":       # the enumerated rows are no sample: only the final estimate is compared
+        return phi, []
+    state = np.random.get_state()
+    all_orders = stage1.generate_all_orders(None, args, save=False)
+    np.random.set_state(state)
+    most = min(len(all_orders), keep.numel() // (n + 1))
+    budgets = sorted({c for c in stage1.SAMPLE_NUMS if c <= most} | ({most} if most else set()))
+    snaps, _ = exact.sampled_from_table(v, all_orders, budgets)
+    rows = []
+    for c in budgets:
+        count = kernelshap.running_counts(n, keep.numel(), not args.unpaired, [c * (n + 1)])[0]
+        try:
+            est = kernelshap.from_table(v, keep[:count].contiguous(), gram=args.gram)
+        except hip_ops.KshapSingular:
+            continue
+        rows.append({"samples": int(c), "evaluations": int(c * (n + 1)), "permutation": _errors(snaps[c] / c, phi),
+                     "kernelshap": dict(rows=int(count), **_errors(est, phi))})
+    return phi, rows
+
+
+def kernel_one_cloud(model, data, lbl, region_id, args):
+    """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact)."""
+    n = args.num_regions
+    g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram)
+    keep, running = g["keep"], g["running"]
+    out = {"coalitions": keep.cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
+           "running_counts": np.array(sorted(running), dtype=np.int64),
+           "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), n),
+           "v_full": g["v_full"], "v_empty": g["v_empty"]}
+    if args.compare_exact:
+        out["exact"], out["sampling_error"] = compare_exact(model, data, lbl, region_id, keep, args)
+    return out
+
+
+def _skip_draw(result_path, args, save=False):
+    """What a cloud that is not selected draws: the same sizes and permutations, nothing computed."""
+    if args.samples != "all":
+        kernelshap.draw(args.num_regions, args.samples or kernelshap.default_samples(args.num_regions), not args.unpaired, args.device)
+
+
+def run(args):
+    model = load_model(args)
+    with torch.no_grad():
+        for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), _skip_draw):
+            mkdir(result_path + "kernelshap/")
+            region_id = stage1.cal_region_id(data, fps_index, result_path, save=False)
+            out = kernel_one_cloud(model, data, lbl, region_id, args)
+            for key in ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value"):
+                np.save(result_path + "kernelshap/%s.npy" % key, out[key])
+            line = "pointcloud:%s, index:%d, rows:%d, sum(phi)=%.6f, v_full - v_empty=%.6f" % (
+                name, i, out["coalitions"].size, out["region_shapley_value"].sum(), out["v_full"] - out["v_empty"])
+            if args.compare_exact:
+                with open(result_path + "kernelshap/sampling_error.json", "w") as f:
+                    json.dump({"num_regions": args.num_regions, "gram": args.gram, "paired": not args.unpaired, "v_full": out["v_full"], "v_empty": out["v_empty"],
+                               "final": _errors(out["region_shapley_value"], out["exact"]), "sample_counts": out["sampling_error"]},
+                              f, indent=1)
+                if out["sampling_error"]:
+                    last = out["sampling_error"][-1]
+                    line += ", %d evaluations: rms error %.4g (kernelshap, %s) against %.4g (%d permutations)" % (
+                        last["evaluations"], last["kernelshap"]["rms_error"], args.gram, last["permutation"]["rms_error"], last["samples"])
+            print(line)
+
+
+def make_args(argv=None):
+    parser = stage1.build_parser()
+    parser.add_argument("--samples", type=str, default=None,
+                        help="coalition rows (model evaluations) per cloud; default 1000 (num_regions + 1); 'all': every proper coalition")
+    parser.add_argument("--unpaired", action="store_true", help="do not follow every sampled coalition with its complement")
+    parser.add_argument("--gram", type=str, default="sampled", choices=list(kernelshap.GRAMS))
+    parser.add_argument("--compare_exact", action="store_true",
+                        help="also enumerate the game (at most %d regions) and write sampling_error.json" % exact.MAX_PLAYERS)
+    args = stage1.parse_game_args(parser, argv, NUM_REGIONS, 2, kernelshap.MAX_REGIONS,
+                                  "the regression estimator takes 2 to 64 regions (final_wide_shapley.py samples wider games)")
+    if args.samples is not None and args.samples != "all":
+        if not args.samples.isdigit() or int(args.samples) < 2:
+            parser.error("--samples %s: a count of at least 2, or 'all'" % args.samples)
+        args.samples = int(args.samples)
+    if (args.compare_exact or args.samples == "all") and args.num_regions > exact.MAX_PLAYERS:
+        parser.error("--num_regions %d: --compare_exact and --samples all enumerate 2^num_regions coalitions; at most %d regions"
+                     % (args.num_regions, exact.MAX_PLAYERS))
+    return args
+
+
+@iqdist.record
+def main(argv=None):
+    args = make_args(argv)
+    stage1.finish_args(args)
+    stage1.rank0_only(run, args, "kernelshap")
+
+
+if __name__ == "__main__":
+    main()

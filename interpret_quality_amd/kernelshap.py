@@ -1,0 +1,203 @@
+"""The regression (KernelSHAP) estimator of region Shapley values, for games of 2 .. 64 regions.
+
+Stage 1 (shapley_stage.py) estimates Shapley values as the reference does, by walking sampled permutations.  This module is the
+weighted least-squares estimator with paired sampling on the same coalition engines: sample coalitions from the Shapley kernel,
+regress their rewards on their membership rows under the constraint sum(phi) = v(all) - v(empty).  The contract (include/iq.h,
+"The regression (KernelSHAP) estimator", has the formulas; DESIGN.md 5f the reasoning):
+
+* sizes: p(s) ~ 1 / (s (n - s)), s = 1 .. n-1, drawn by inverse CDF from ONE ``np.random.random_sample(S)`` on NumPy's global
+  legacy generator; members: the first s_m entries of permutation m, the S permutations drawn after the sizes on the device from
+  the same stream exactly as stage 1 draws its own (``hip_ops.sample_permutations``), the state handed back to the host;
+* pairing (default): row 2m is S_m, row 2m+1 its complement, M = 2S rows;
+* ``gram="sampled"``: A from the rows (the original KernelSHAP); ``gram="analytic"``: A is its expectation under the size law,
+  only b comes from the rows (the unbiased variant of Covert & Lee);
+* all 2^n - 2 proper coalitions with the weights of ``enumerated`` give the exact Shapley vector.
+
+The moments and the solve run in libiq_hip.so (csrc/iq_kshap.hip): float64, fixed order, bitwise repeatable.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import final_common, hip_ops, work
+from ._lib import IqError
+
+MAX_REGIONS = hip_ops.MAX_KSHAP_REGIONS
+GRAMS = ("sampled", "analytic")
+
+
+_regions = hip_ops.kshap_regions
+
+
+def size_cdf(n):
+    """(n-1,) float64: entry s-1 = P(size <= s) under p(s) = (1 / (s (n - s))) / Z; the last entry is exactly 1.0."""
+    n = _regions(n)
+    s = np.arange(1, n, dtype=np.float64)
+    p = 1.0 / (s * (n - s))
+    cdf = np.cumsum(p / p.sum())
+    cdf[-1] = 1.0
+    return cdf
+
+
+def analytic_gram(n):
+    """(n,n) float64: E[z z^T] under the size law - 1/2 on the diagonal, 1/2 - 1 / (2 H_{n-1}) off it."""
+    n = _regions(n)
+    h = math.fsum(1.0 / k for k in range(1, n))
+    a = np.full((n, n), 0.5 - 1.0 / (2.0 * h))
+    np.fill_diagonal(a, 0.5)
+    return a
+
+
+def draw_sizes(n, count):
+    """``count`` coalition sizes by the contract: one random_sample call on NumPy's global generator -> (count,) int32."""
+    u = np.random.random_sample(int(count))
+    return np.minimum(n - 1, 1 + np.searchsorted(size_cdf(n), u, side="right")).astype(np.int32)
+
+
+def draw(n, samples, paired=True, device="cuda"):
+    """One cloud's draw of ``samples`` rows (paired: rounded down to even, half of them drawn) -> (keep (M,) int64-typed device
+    tensor, sizes (S,) int32 ndarray).  S doubles on the host, then S permutations on the device; NumPy's global generator is
+    left where the reference's stream stands after both."""
+    n = _regions(n)
+    s = int(samples) // 2 if paired else int(samples)
+    if s < 1:
+        raise IqError("samples=%d leaves no coalition to draw" % int(samples))
+    sizes = draw_sizes(n, s)
+    state = hip_ops.mt_state_to_device(device)
+    orders = hip_ops.sample_permutations(state, s, n)
+    hip_ops.mt_state_to_host(state, set_global=True)
+    return hip_ops.kshap_keep_masks(orders, torch.from_numpy(sizes).to(orders.device), paired), sizes
+
+
+def enumeration_weights(n):
+    """(n+1,) float64: entry s = w(S) of a coalition of s regions, (n-1) / (C(n,s) s (n-s)); 0 for the empty and the full set."""
+    w = np.zeros(n + 1)
+    for s in range(1, n):
+        w[s] = (n - 1) / (math.comb(n, s) * s * (n - s))
+    return w
+
+
+def enumerated(n, device):
+    """-> (keep (2^n - 2,) int64-typed, weights (2^n - 2,) float64), both on the device: every proper coalition of regions 0 .. n-1
+    with the weight under which the regression returns the exact Shapley vector."""
+    n = _regions(n)
+    if n > hip_ops.MAX_EXACT_PLAYERS:
+        raise IqError("an enumerated game has 2^n rows: n=%d is above the limit of %d" % (n, hip_ops.MAX_EXACT_PLAYERS))
+    count = (1 << n) - 2
+    keep = hip_ops.enum_keep_masks(1, count, n, device)
+    c = np.arange(1, count + 1, dtype=np.int64)
+    size = np.zeros(count, dtype=np.int64)
+    for k in range(n):
+        size += (c >> k) & 1
+    return keep, torch.from_numpy(enumeration_weights(n)[size]).to(keep.device)
+
+
+def _f64(x, g, dev, what):
+    t = torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64).reshape(-1))
+    if t.numel() != g:
+        raise IqError("%s holds %d values for %d games" % (what, t.numel(), g))
+    return t.to(dev)
+
+
+def estimate(keep, v, v_empty, v_full, n, weights=None, gram="sampled"):
+    """phi of the rows ``keep`` (M,) with rewards ``v`` ((M,) float32 device tensor, or (G,M) for G games on the same rows;
+    v_empty, v_full: scalars or (G,)) -> float64 ndarray (n,) or (G,n).  IqError (hip_ops.KshapSingular) if the rows leave the
+    sampled A singular."""
+    n = _regions(n)
+    if gram not in GRAMS:
+        raise IqError("gram must be one of %s, got %r" % (GRAMS, gram))
+    if not isinstance(v, torch.Tensor) or v.dim() not in (1, 2):
+        raise IqError("v must be a (M,) or (G,M) tensor")
+    v2 = v.reshape(1, -1) if v.dim() == 1 else v
+    g, dev = v2.shape[0], keep.device
+    v0, v1 = _f64(v_empty, g, dev, "v_empty"), _f64(v_full, g, dev, "v_full")
+    a, b, wsum = hip_ops.kshap_accum(keep, v2.contiguous(), v0, n, weights)
+    a = a / wsum if gram == "sampled" else torch.from_numpy(analytic_gram(n)).to(dev)
+    phi = hip_ops.kshap_solve(a.contiguous(), (b / wsum).contiguous(), v1 - v0).cpu().numpy()
+    return phi[0] if v.dim() == 1 else phi
+
+
+def default_samples(n):
+    """Stage 1's budget of model evaluations: 1000 permutations of n + 1 prefix coalitions, rounded down to even."""
+    return 1000 * (n + 1) // 2 * 2
+
+
+def running_counts(n, rows, paired=True, counts=None):
+    """The row counts at which ``shapley`` reports a running estimate: c (n + 1) for c in shapley_stage.SAMPLE_NUMS (the model
+    evaluations of c permutations), rounded down to even when paired, that do not exceed ``rows``."""
+    if counts is None:
+        from .shapley_stage import SAMPLE_NUMS
+        counts = [c * (n + 1) for c in SAMPLE_NUMS]
+    counts = [int(c) // 2 * 2 if paired else int(c) for c in counts]
+    return [c for c in counts if 1 <= c <= rows]
+
+
+def rewards(model, data, lbl, region_id, args, keep, chunk=1 << 16):
+    """Rewards of the coalitions ``keep`` of one cloud ``data`` (1,N,3), obtained as exact.value_table obtains them, with the
+    full and the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty)."""
+    if not hasattr(model, "coalition_logits"):
+        raise IqError("%s has no coalition entry point" % type(model).__name__)
+    dev = data.device
+    r = _regions(args.num_regions)
+    rid = hip_ops.region_ids(region_id, dev, r).reshape(1, -1)
+    clouds = data.contiguous()
+    centers = torch.mean(data, dim=1).reshape(1, 3).contiguous()
+    rows = torch.cat([keep, hip_ops.masks_to_tensor([(1 << r) - 1, 0], dev)])
+    v = torch.empty((rows.numel(),), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for first in range(0, rows.numel(), max(1, int(chunk))):
+            part = rows[first:first + chunk].contiguous()
+            work.add(part.numel())
+            logits = model.coalition_logits(clouds, centers, rid, part, None, num_regions=r, validate=False)
+            v[first:first + part.numel()] = final_common.get_reward(logits, lbl, args)
+    ends = v[-2:].cpu().numpy()
+    return v[:-2].contiguous(), float(ends[0]), float(ends[1])
+
+
+def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled"):
+    """{count: phi of the first ``count`` rows}; a count whose rows leave A singular is left out."""
+    out = {}
+    for c in counts:
+        try:
+            out[c] = estimate(keep[:c].contiguous(), v[:c].contiguous(), v_empty, v_full, n, None, gram)
+        except hip_ops.KshapSingular:
+            pass
+    return out
+
+
+def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):
+    """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
+    sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows}."""
+    n = _regions(args.num_regions)
+    weights = None
+    if isinstance(samples, str):
+        if samples != "all":
+            raise IqError("samples must be a count, None or 'all', got %r" % (samples,))
+        keep, weights = enumerated(n, data.device)
+    else:
+        keep, _ = draw(n, default_samples(n) if samples is None else samples, paired, data.device)
+    v, v_full, v_empty = rewards(model, data, lbl, region_id, args, keep)
+    phi = estimate(keep, v, v_empty, v_full, n, weights, gram)
+    running = {}
+    if weights is None:
+        running = running_estimates(keep, v, v_empty, v_full, n, running_counts(n, keep.numel(), paired, counts), gram)
+    return {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
+
+
+def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):
+    """-> (phi (n,) float64 ndarray, v_full, v_empty, running {count: (n,) phi of the first ``count`` rows}) of one cloud.
+    ``samples``: rows to draw (None: default_samples(n)), or "all": the enumerated game, exact up to rounding (no running
+    estimates)."""
+    g = game(model, data, lbl, region_id, args, samples, paired, gram, counts)
+    return g["phi"], g["v_full"], g["v_empty"], g["running"]
+
+
+def from_table(v_table, keep, weights=None, gram="sampled"):
+    """The estimate of the rows ``keep`` with rewards read off an exact value table (exact.value_table; players are regions
+    0 .. n-1, so a coalition's reward is v_table[keep]) - the counterpart of exact.sampled_from_table -> (n,) float64 ndarray."""
+    n = int(v_table.numel()).bit_length() - 1
+    if v_table.dim() != 1 or v_table.numel() != 1 << n:
+        raise IqError("v_table must be a (2^n,) table, got shape %s" % (tuple(v_table.shape),))
+    ends = v_table[[0, v_table.numel() - 1]].cpu().numpy()
+    return estimate(keep, v_table.index_select(0, keep).contiguous(), float(ends[0]), float(ends[1]), n, weights, gram)
