@@ -190,7 +190,10 @@ int iq_fps(const float* xyz, int32_t* idx, int B, int N, int S, iq_stream_t stre
  *                            the reference cannot process such a region)
  * The caller evaluates epochs 0 .. min(epochs, max_r stop_epoch + 1) - 1, as the break at :333-334 does.
  * `origin` (optional) restarts the enumeration from an already deformed `cloud`: orientations, variance
- * bounds, the distance bound and the first target are taken from `origin` (NULL: from `cloud`). */
+ * bounds, the distance bound and the first target are taken from `origin` (NULL: from `cloud`).
+ * Every region_id[i] must lie in [0, R); neither entry point checks it (iq_check_index_range does, and hip_ops.smoothness_enum
+ * calls it before the launch).  A point with an id outside [0, R) belongs to no region: it takes no part in any region's
+ * covariance or step, the launch copies its row of `cloud` into every epoch of data_out, and rc is still 0. */
 typedef struct iq_smoothness_params {
     double step;           /* STEP = 1e-3 */
     double enum_step;      /* ENUM_STEP = 0.05 */

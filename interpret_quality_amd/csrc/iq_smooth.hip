@@ -313,6 +313,19 @@ __global__ __launch_bounds__(kWave) void smooth_enum_kernel(
     if (lane == 0) stop_epoch[r] = stop;
 }
 
+// A point whose region id lies outside [0, R) belongs to no region's point list, so the kernel above never writes its rows of
+// data_out.  The contract (include/iq.h) asks for ids in [0, R); a caller that breaks it gets such a point back where it was,
+// in every epoch, instead of whatever the output buffer held.
+__global__ __launch_bounds__(kWave) void smooth_passthrough_kernel(const float* __restrict__ cloud, const int32_t* __restrict__ region_id,
+                                                                   int N, int R, int E, float* __restrict__ data_out) {
+    const int i = blockIdx.x * kWave + threadIdx.x;
+    if (i >= N) return;
+    const int32_t id = region_id[i];
+    if (id >= 0 && id < R) return;
+    for (int e = 0; e < E; ++e)
+        for (int c = 0; c < 3; ++c) data_out[((size_t)e * N + i) * 3 + c] = cloud[(size_t)i * 3 + c];
+}
+
 }  // namespace
 
 // Both entry points launch the one kernel above, one wave per region (grid = R); they differ in the region count they admit.
@@ -327,6 +340,8 @@ static int launch_smooth_enum(const char* name, int max_regions, const float* cl
     IQ_REQUIRE(objective == 1 || objective == -1, "%s: objective %d (+1 inc, -1 dec)", name, objective);
     IQ_REQUIRE(prm->epochs >= 1 && prm->epochs <= 4096 && prm->max_iteration >= 0, "%s: epochs=%d max_iteration=%d", name,
                prm->epochs, prm->max_iteration);
+    hipLaunchKernelGGL(smooth_passthrough_kernel, dim3((N + kWave - 1) / kWave), dim3(kWave), 0, iq::as_stream(stream), cloud, region_id,
+                       N, R, prm->epochs, data_out);
     hipLaunchKernelGGL(smooth_enum_kernel, dim3(R), dim3(kWave), 0, iq::as_stream(stream), cloud,
                        origin ? origin : cloud, region_id, N, R, mode, objective, *prm, data_out, smooth_out, var_out, orig_out, stop_epoch);
     return iq::check_launch("smooth_enum_kernel");

@@ -736,10 +736,13 @@ def smoothness_enum(cloud, region_id, num_regions, mode, objective, step=1e-3, e
                     entry="iq_smoothness_enum"):
     """final_smoothness_center_enum_all.py:183-242,303-335 for all regions and epochs in one launch.
     cloud (N,3) f32, region_id (N,) i32 -> dict(data (E,N,3) f32, smoothness (E,R) f32, var (E,R,3) f32,
-    orig (R,4) f32, stop_epoch (R,) i32); see include/iq.h.  ``origin`` (N,3): restart from a deformed ``cloud``."""
+    orig (R,4) f32, stop_epoch (R,) i32); see include/iq.h.  ``origin`` (N,3): restart from a deformed ``cloud``.
+    Every region id must lie in [0, num_regions): an IqError otherwise (check_index_range), before anything is launched."""
     lib = _lib.load()
     n, r, e = cloud.shape[0], int(num_regions), int(epochs)
     dev = cloud.device
+    _dev(region_id, torch.int32, "region_id")
+    check_index_range(region_id, 0, r, "region_id")
     out = {"data": torch.empty((e, n, 3), dtype=torch.float32, device=dev),
            "smoothness": torch.empty((e, r), dtype=torch.float32, device=dev),
            "var": torch.empty((e, r, 3), dtype=torch.float32, device=dev),

@@ -620,9 +620,11 @@ def _smoothness_value(mode, var):
     return s_min / s_max, (s_max, s_min)
 
 
-def smoothness_enumerate(data, region_id, num_regions, mode, objective, start=None, **overrides):
+def smoothness_enumerate(data, region_id, num_regions, mode, objective, start=None, trace=None, **overrides):
     """test_all_region's epoch loop (:303-335) without the Shapley evaluations: returns
-    (data_list (P,1,N,3), smoothness_list (P,R), orig (R,4) = var1..3 and smoothness of the untouched regions)."""
+    (data_list (P,1,N,3), smoothness_list (P,R), orig (R,4) = var1..3 and smoothness of the untouched regions).
+    ``trace``: a dict that receives the discrete decisions, {region: dict(iters [steps taken per epoch], stop (epoch, or None),
+    steps [(order of the variances (3,), which variances kept their gradient (3,), distance count)])}; the return is unchanged."""
     prm = dict(SMOOTH_DEFAULTS, **overrides)
     region_id = np.asarray(region_id)
     cur = (data if start is None else start).clone().detach()  # start: resume from a deformed cloud (test hook)
@@ -637,15 +639,17 @@ def smoothness_enumerate(data, region_id, num_regions, mode, objective, start=No
                          lb=[v - prm["var_threshold"] for v in var0], smooth=sm0, var0=[v.item() for v in var0], sm0=sm0))
     live = [True] * num_regions
     data_list, smooth_list = [], []
-    for _ in range(prm["epoch"]):
+    if trace is not None:
+        trace.update({r: dict(iters=[], stop=None, steps=[]) for r in range(num_regions)})
+    for ep in range(prm["epoch"]):
         row = []
         for r in range(num_regions):
             reg = info[r]
+            it = 0
             if live[r]:  # update_region (:183-242)
                 sel = region_id == r
                 smooth = reg["smooth"]
                 target = smooth + prm["enum_step"] if objective == "inc" else smooth - prm["enum_step"]
-                it = 0
                 while (smooth < target) if objective == "inc" else (smooth > target):
                     x = cur[:, sel, :].squeeze().clone().detach().requires_grad_(True)
                     var = projected_variances(x, reg["orient"])
@@ -672,10 +676,17 @@ def smoothness_enumerate(data, region_id, num_regions, mode, objective, start=No
                                 x[i].data = reg["org"][i].data + prm["dist_threshold"] * diff[i] / dist[i]
                     cur[:, sel, :] = x.unsqueeze(0).data
                     it += 1
+                    if trace is not None:
+                        order = np.argsort(np.array([v.item() for v in var])).tolist()
+                        trace[r]["steps"].append((tuple(order), tuple(bool(v.requires_grad) for v in var), count))
                     if count / x.shape[0] > prm["stop_ratio"] or grad_none or it > prm["max_iteration"]:
                         live[r] = False
+                        if trace is not None:
+                            trace[r]["stop"] = ep
                         break
                 reg["smooth"] = smooth
+            if trace is not None:
+                trace[r]["iters"].append(it)
             row.append(reg["smooth"])
         smooth_list.append(row)
         data_list.append(cur.numpy().copy())
