@@ -66,8 +66,10 @@ enum {
  * 112: one new diagnostic entry point, no layout change and no workspace size changed (iq_debug.h: iq_debug_pointnet_reps).
  * 113: new entry points, no layout change (the device sampler for wide games: iq_sample_wide_workspace_bytes,
  * iq_sample_permutations_wide, iq_context_regions_wide).
- * 114: new entry points, no layout change (the regression estimator of Shapley values: iq_kshap_keep_masks .. iq_kshap_solve). */
-#define IQ_ABI_VERSION 114
+ * 114: new entry points, no layout change (the regression estimator of Shapley values: iq_kshap_keep_masks .. iq_kshap_solve).
+ * 115: new entry points, no layout change (the regression estimator of wide games: iq_kshap_keep_masks_wide,
+ * iq_kshap_scratch_bytes_wide, iq_kshap_moment_wide, iq_kshap_phi_analytic). */
+#define IQ_ABI_VERSION 115
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -602,6 +604,14 @@ int iq_moebius(const float* v, int n, double* a, iq_stream_t stream);
  * points below build the rows, reduce them to the RAW sums (the caller divides by W) and solve.  All float64 sums are taken in an
  * order that depends on (M, n, G) only - no floating-point atomics - so two calls give the same bits; G games that share the
  * rows (the poses of a sweep) give per game the bits of a call with G = 1.
+ *
+ * Wide games (65 .. IQ_MAX_WIDE_REGIONS regions, rows in the format of "Wide coalitions" below; csrc/iq_kshap_wide.hip) have the
+ * estimator with the ANALYTIC A only: A = E[z z^T] under the size law p(s) ~ 1 / (s (R - s)) is alpha I + c 1 1^T with
+ * alpha = 1 / (2 H_{R-1}), c = 1/2 - alpha, H_{R-1} = sum_{k<R} 1/k, so y = A^-1 1 is a multiple of 1 and the formula above becomes
+ *     phi_i = 2 H_{R-1} (b_i - mean(b)) + delta / R:
+ * no matrix, no factorisation, no singular case, sum(phi) = delta by construction, and with the enumerated rows and weights still
+ * the exact Shapley vector.  The three wide entry points after iq_kshap_solve build the rows, reduce them to the raw b and W, and
+ * evaluate that formula.  The A of sampled rows above 64 regions is not built.
  * ------------------------------------------------------------------------------------------- */
 
 /* Row m of a sampled game: the regions orders[m][0 .. sizes[m]-1] of permutation m (iq_sample_permutations) as a keep mask.
@@ -628,6 +638,35 @@ int iq_kshap_accum(const uint64_t* keep /*M*/, const float* v /*G,M*/, const dou
  * the regression, phi is left unwritten. */
 int iq_kshap_solve(const double* A /*n,n*/, const double* b /*G,n*/, const double* delta /*G*/, double* phi /*G,n*/,
                    int32_t* status /*1, device*/, int n, int G, iq_stream_t stream);
+
+/* iq_kshap_keep_masks for wide rows, 2 <= R <= IQ_MAX_WIDE_REGIONS, W = ceil(R / 64): row m (paired: row 2m) holds the first
+ * sizes[m] entries of permutation m, bit (r & 63) of word (r >> 6); paired: row 2m+1 is its complement within the R bits, the bits
+ * at or above R of the last word 0 in both.  status as in the narrow entry (1 = a size outside 1 .. R-1, 2 = an entry outside
+ * [0, R)): the row and its complement are written as 0, nothing is read out of bounds.  One wave per sample.  For R <= 64 the
+ * words are iq_kshap_keep_masks's. */
+int iq_kshap_keep_masks_wide(const int32_t* orders /*S,R*/, const int32_t* sizes /*S*/, uint64_t* keep /*M,W*/, int S, int R, int paired,
+                             int32_t* status /*1, device*/, iq_stream_t stream);
+
+/* Scratch (bytes) of iq_kshap_moment_wide; 0 for arguments out of range (M outside 1 .. 2^30, R outside 2 .. IQ_MAX_WIDE_REGIONS,
+ * G outside 1 .. 65535). */
+size_t iq_kshap_scratch_bytes_wide(int M, int R, int G);
+
+/* The raw moment of M wide rows shared by G games: b[g][i] = sum w_m z_mi ((double)v[g][m] - v0[g]) (G,R) and wsum = sum w_m (M
+ * when weights == NULL).  The summation order per region is iq_kshap_accum's - rows cut into chunks of whole 256-row tiles by the
+ * same function of M, within a chunk wave q of four adds rows 64 q .. 64 q + 63 of every tile in row order, the waves added as
+ * ((0 + 1) + 2) + 3, the chunks in chunk order by a second kernel; wsum by the narrow rule - so for R <= 64 b and wsum are that
+ * entry's bits, two calls give the same bits, and G games give per game the bits of a call with G = 1. */
+int iq_kshap_moment_wide(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/,
+                         const double* weights /*M or NULL*/, int M, int R, int G, double* b /*G,R*/, double* wsum /*1*/,
+                         void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* phi[g][i] = 2 H_{R-1} (x_i - mean(x)) + delta[g] / R with x = b[g] / wsum (b and wsum RAW, as iq_kshap_moment_wide leaves them on
+ * the device: no host round trip), 2 <= R <= IQ_MAX_WIDE_REGIONS.  H_{R-1} is summed in float64 in ascending k on the host, inside this
+ * call, and passed to the kernel by value.  Per game, in this order, every operation rounded on its own: x_i = b_i / wsum;
+ * c = (x_0 + x_1 + ...) / R in index order; y_i = x_i - c; d = (y_0 + y_1 + ...) / R in index order (the mean of the centred
+ * values: 0 but for the rounding of c); phi_i = (2 H) (y_i - d) + delta / R.  No status word: there is no singular case. */
+int iq_kshap_phi_analytic(const double* b /*G,R raw*/, const double* wsum /*1, device*/, const double* delta /*G*/,
+                          double* phi /*G,R*/, int R, int G, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

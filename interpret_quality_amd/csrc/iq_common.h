@@ -69,6 +69,19 @@ __device__ __forceinline__ bool keep_bit_wide(const uint64_t* keep, int rid, int
     return (unsigned)rid < (unsigned)R && ((keep[rid >> 6] >> (rid & 63)) & 1ull);
 }
 
+// The 64 lanes of ONE WAVE stride over `count` region ids (row-contiguous: coalesced) and OR their bits into the wave's own row
+// `set` of LDS words (zeroed before, and read only after a barrier).  OR is order-independent: the words do not depend on the
+// schedule.  An id outside [0, R) sets nothing; the return value says whether this lane met one.
+__device__ __forceinline__ bool wave_or_regions(const int32_t* __restrict__ ids, int count, int R, int lane, unsigned long long* set) {
+    bool outside = false;
+    for (int j = lane; j < count; j += 64) {
+        const int r = ids[j];
+        if ((unsigned)r < (unsigned)R) atomicOr(&set[r >> 6], 1ull << (r & 63));
+        else outside = true;
+    }
+    return outside;
+}
+
 // The coalition of ONE WAVE, for the small kernels of the compact coalition paths that turn a coalition's mask into its kept
 // points (a wave per coalition).  The switch between the two kinds of game is this template argument, so a narrow kernel holds
 // no trace of the wide form:

@@ -7,22 +7,18 @@
 // kMaxChunks chunks, so the scratch stays bounded when M is the 2^24 rows of an enumerated game.  Without weights A holds
 // co-occurrence counts: the same kernel with integer accumulators, exact and order-free.
 #include "iq_common.h"
+#include "iq_kshap_order.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 256;          // rows staged per step: one per thread
-constexpr int kMaxChunks = 256;
+// iq_kshap_order.h: the cut into chunks, the moment of a chunk and the folds, shared with the wide form (iq_kshap_wide.hip)
+using iq::kshap::Chunks;
+using iq::kshap::chunks_of;
+using iq::kshap::kThreads;
+using iq::kshap::kTile;
+
 constexpr int kMaxN = IQ_MAX_REGIONS;
 constexpr int kCols = 16;           // entries of a row of A per thread: 256 threads x 16 = 64 x 64
-
-struct Chunks { int count, tiles_per; };
-
-__host__ __device__ inline Chunks chunks_of(long long M) {
-    const long long tiles = (M + kTile - 1) / kTile;
-    const long long per = (tiles + kMaxChunks - 1) / kMaxChunks;
-    return {(int)((tiles + per - 1) / per), (int)per};
-}
 
 // One thread per sample: the first sizes[m] entries of permutation m as a bit mask; paired: its complement within n bits beside it.
 // status: 1 = a size outside 1 .. n-1, 2 = an order entry outside [0, n) (the row is written as 0 either way).
@@ -94,42 +90,19 @@ __global__ __launch_bounds__(kThreads) void kshap_gram_kernel(const unsigned lon
             if (j0 + c < n) partA[((size_t)blockIdx.x * n + i) * n + j0 + c] = acc[c];
     }
     if (partW) {
-        sh_w[t] = wacc;
-        __syncthreads();
-        if (t == 0) {
-            T s = T(0);
-            for (int u = 0; u < kThreads; ++u) s += sh_w[u];
-            partW[blockIdx.x] = (double)s;
-        }
+        const T s = iq::kshap::sum_threads_in_order(sh_w, wacc);
+        if (t == 0) partW[blockIdx.x] = (double)s;
     }
 }
 
 // partB[(g * nchunk + chunk) * n + i] = the chunk's sum of w_m z_mi ((double)v[g][m] - v0[g]): lane i of wave q adds rows
-// 64 q .. 64 q + 63 of every tile in row order, then the four waves are added in wave order.
+// 64 q .. 64 q + 63 of every tile in row order, then the four waves are added in wave order (iq::kshap::moment_chunk).
 __global__ __launch_bounds__(kThreads) void kshap_moment_kernel(const unsigned long long* __restrict__ keep, const float* __restrict__ v,
                                                                 const double* __restrict__ v0, const double* __restrict__ weights,
                                                                 long long M, int n, int tiles_per, double* __restrict__ partB) {
-    __shared__ unsigned long long sh_keep[kTile];
-    __shared__ double sh_d[kTile];
-    __shared__ double sh_fold[4][64];
-    const int t = threadIdx.x, lane = t & 63, q = t >> 6, g = blockIdx.y;
-    const long long row0 = (long long)blockIdx.x * tiles_per * kTile;
-    const double base = v0[g];
-    const float* vg = v + (size_t)g * M;
-    double acc = 0.0;
-    for (int tile = 0; tile < tiles_per; ++tile) {
-        const long long m = row0 + (long long)tile * kTile + t;
-        const bool live = m < M;
-        sh_keep[t] = live ? keep[m] : 0ull;
-        sh_d[t] = live ? (weights ? weights[m] : 1.0) * ((double)vg[m] - base) : 0.0;
-        __syncthreads();
-#pragma unroll 8
-        for (int r = q * 64; r < q * 64 + 64; ++r) acc += (sh_keep[r] >> lane) & 1ull ? sh_d[r] : 0.0;
-        __syncthreads();
-    }
-    sh_fold[q][lane] = acc;
-    __syncthreads();
-    if (t < n) partB[((size_t)g * gridDim.x + blockIdx.x) * n + t] = ((sh_fold[0][t] + sh_fold[1][t]) + sh_fold[2][t]) + sh_fold[3][t];
+    const int g = blockIdx.y;
+    iq::kshap::moment_chunk(keep, 1, 0, v + (size_t)g * M, v0[g], weights, M, tiles_per, blockIdx.x,
+                            partB + ((size_t)g * gridDim.x + blockIdx.x) * n, n, nullptr);
 }
 
 // One thread per output: the chunks' partials added in chunk order.  Entries [0, n^2): A; then G n of b; the last one wsum.
@@ -140,10 +113,7 @@ __global__ __launch_bounds__(kThreads) void kshap_fold_kernel(const void* __rest
     const int e = blockIdx.x * kThreads + threadIdx.x, nn = n * n;
     if (e < nn) {
         if (weighted) {
-            const double* p = static_cast<const double*>(partA);
-            double s = 0.0;
-            for (int c = 0; c < nchunk; ++c) s += p[(size_t)c * nn + e];
-            A[e] = s;
+            A[e] = iq::kshap::fold_chunks(static_cast<const double*>(partA) + e, nn, nchunk);
         } else {
             const unsigned long long* p = static_cast<const unsigned long long*>(partA);
             unsigned long long s = 0;
@@ -152,16 +122,9 @@ __global__ __launch_bounds__(kThreads) void kshap_fold_kernel(const void* __rest
         }
     } else if (e < nn + G * n) {
         const int g = (e - nn) / n, i = (e - nn) % n;
-        double s = 0.0;
-        for (int c = 0; c < nchunk; ++c) s += partB[((size_t)g * nchunk + c) * n + i];
-        b[e - nn] = s;
+        b[e - nn] = iq::kshap::fold_chunks(partB + (size_t)g * nchunk * n + i, n, nchunk);
     } else if (e == nn + G * n) {
-        double s = (double)M;
-        if (weighted) {
-            s = 0.0;
-            for (int c = 0; c < nchunk; ++c) s += partW[c];
-        }
-        *wsum = s;
+        *wsum = iq::kshap::fold_wsum(partW, weighted, M, nchunk);
     }
 }
 

@@ -55,13 +55,7 @@ __global__ __launch_bounds__(64 * kCtxPerWg) void context_keep_wide_kernel(const
     const bool live = t < PC;                                   // no early return: every wave reaches both barriers
     if (lane < W) set_s[wave][lane] = 0ull;
     __syncthreads();
-    if (live) {
-        const int32_t* row = ctx + t * m;
-        for (int j = lane; j < m; j += 64) {
-            const int r = row[j];
-            if ((unsigned)r < (unsigned)R) atomicOr(&set_s[wave][r >> 6], 1ull << (r & 63));   // an out-of-range entry is ignored
-        }
-    }
+    if (live) iq::wave_or_regions(ctx + t * m, m, R, lane, set_s[wave]);   // an out-of-range entry is ignored
     __syncthreads();
     if (live && lane < 4 * W) {
         const int q = lane / W, w = lane - q * W;               // row q of the four, word w of the row

@@ -589,6 +589,74 @@ def shapley_accum_wide(v, orders, snap_counts=None):
     return _shapley_accum("iq_shapley_accum_wide", v, orders, snap_counts)
 
 
+def kshap_regions_wide(r):
+    """The region count of a game the wide regression estimator's entry points take, as an int (IqError outside 2 .. 1024)."""
+    r = int(r)
+    if not 2 <= r <= MAX_WIDE_REGIONS:
+        raise _lib.IqError("the wide regression estimator takes 2 .. %d regions, got %d" % (MAX_WIDE_REGIONS, r))
+    return r
+
+
+def kshap_keep_masks_wide(orders, sizes, paired=True):
+    """``kshap_keep_masks`` for wide rows: orders (S,R) i32 permutations, sizes (S,) i32 in 1 .. R-1 -> (2S or S, W) int64-typed
+    keep rows (iq_kshap_keep_masks_wide), every set followed by its complement within the R bits when ``paired``.  A size outside
+    1 .. R-1 or an order entry outside [0, R) raises IqError (one 4-byte read back)."""
+    lib = _lib.load()
+    _dev(orders, torch.int32, "orders")
+    s, r = _shape(orders, "orders", None, None)
+    r = kshap_regions_wide(r)
+    _shape(sizes, "sizes", s)
+    keep = torch.empty((2 * s if paired else s, wide_words(r)), dtype=torch.int64, device=orders.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=orders.device)
+    _lib.check(lib.iq_kshap_keep_masks_wide(_p(orders), _dev(sizes, torch.int32, "sizes"), _p(keep), s, r, int(bool(paired)),
+                                            _p(status), _stream()), "iq_kshap_keep_masks_wide")
+    verdict = int(status.item()) if s else 0
+    if verdict:
+        raise _lib.IqError("kshap_keep_masks_wide: " + ("a size lies outside 1 .. %d" % (r - 1) if verdict == 1
+                                                        else "an order entry lies outside [0, %d)" % r))
+    return keep
+
+
+def kshap_moment_wide(keep, v, v0, num_regions, weights=None):
+    """keep (M,W) int64-typed wide rows, v (G,M) f32 rewards of G games on those rows, v0 (G,) f64, weights (M,) f64 or None (all 1)
+    -> (b (G,R) f64, wsum (1,) f64): the RAW sums b[g] = sum w z (v[g] - v0[g]) and wsum = sum w (iq_kshap_moment_wide: float64 in
+    ``kshap_accum``'s order, for R <= 64 its bits; bitwise repeatable)."""
+    lib = _lib.load()
+    r = kshap_regions_wide(num_regions)
+    kp = wide_keep(keep, r)
+    m = keep.shape[0]
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    if weights is not None:
+        _shape(weights, "weights", m)
+    dev = keep.device
+    nbytes = lib.iq_kshap_scratch_bytes_wide(m, r, g)
+    if nbytes == 0:
+        raise _lib.IqError("kshap_moment_wide: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
+    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    b = torch.empty((g, r), dtype=torch.float64, device=dev)
+    wsum = torch.empty((1,), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_moment_wide(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"),
+                                        _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0), m, r, g,
+                                        _p(b), _p(wsum), _p(scratch), nbytes, _stream()), "iq_kshap_moment_wide")
+    return b, wsum
+
+
+def kshap_phi_analytic(b, wsum, delta):
+    """b (G,R) f64 and wsum (1,) f64 RAW as ``kshap_moment_wide`` returns them, delta (G,) f64 -> phi (G,R) f64 =
+    2 H_{R-1} (b / wsum - mean(b / wsum)) + delta / R, the regression under the analytic Gram matrix in closed form
+    (iq_kshap_phi_analytic: sum(phi[g]) = delta[g]; no singular case, nothing is read back)."""
+    lib = _lib.load()
+    g, r = _shape(b, "b", None, None)
+    r = kshap_regions_wide(r)
+    _shape(wsum, "wsum", 1)
+    _shape(delta, "delta", g)
+    phi = torch.empty((g, r), dtype=torch.float64, device=b.device)
+    _lib.check(lib.iq_kshap_phi_analytic(_dev(b, torch.float64, "b"), _dev(wsum, torch.float64, "wsum"),
+                                         _dev(delta, torch.float64, "delta"), _p(phi), r, g, _stream()), "iq_kshap_phi_analytic")
+    return phi
+
+
 def fps(xyz, npoint):
     """xyz (B,N,3) f32 -> (B,npoint) i32."""
     lib = _lib.load()

@@ -113,7 +113,7 @@ def make_args(argv=None):
     parser.add_argument("--compare_exact", action="store_true",
                         help="also enumerate the game (at most %d regions) and write sampling_error.json" % exact.MAX_PLAYERS)
     args = stage1.parse_game_args(parser, argv, NUM_REGIONS, 2, kernelshap.MAX_REGIONS,
-                                  "the regression estimator takes 2 to 64 regions (final_wide_shapley.py samples wider games)")
+                                  "the regression estimator takes 2 to 64 regions (final_wide_kernel_shapley.py: 65 to 1024)")
     if args.samples is not None and args.samples != "all":
         if not args.samples.isdigit() or int(args.samples) < 2:
             parser.error("--samples %s: a count of at least 2, or 'all'" % args.samples)

@@ -14,6 +14,7 @@ regress their rewards on their membership rows under the constraint sum(phi) = v
 * all 2^n - 2 proper coalitions with the weights of ``enumerated`` give the exact Shapley vector.
 
 The moments and the solve run in libiq_hip.so (csrc/iq_kshap.hip): float64, fixed order, bitwise repeatable.
+Games of 65 .. 1024 regions: wide_kernelshap.py (the analytic variant in closed form, on wide keep rows).
 """
 import math
 
@@ -30,14 +31,24 @@ GRAMS = ("sampled", "analytic")
 _regions = hip_ops.kshap_regions
 
 
-def size_cdf(n):
-    """(n-1,) float64: entry s-1 = P(size <= s) under p(s) = (1 / (s (n - s))) / Z; the last entry is exactly 1.0."""
-    n = _regions(n)
+def _size_cdf(n):
+    """``size_cdf`` of any n >= 2, unchecked: shared with wide_kernelshap.py, whose range is another."""
     s = np.arange(1, n, dtype=np.float64)
     p = 1.0 / (s * (n - s))
     cdf = np.cumsum(p / p.sum())
     cdf[-1] = 1.0
     return cdf
+
+
+def _draw_sizes(n, count):
+    """``draw_sizes`` of any n >= 2, unchecked (wide_kernelshap.py)."""
+    u = np.random.random_sample(int(count))
+    return np.minimum(n - 1, 1 + np.searchsorted(_size_cdf(n), u, side="right")).astype(np.int32)
+
+
+def size_cdf(n):
+    """(n-1,) float64: entry s-1 = P(size <= s) under p(s) = (1 / (s (n - s))) / Z; the last entry is exactly 1.0."""
+    return _size_cdf(_regions(n))
 
 
 def analytic_gram(n):
@@ -51,8 +62,7 @@ def analytic_gram(n):
 
 def draw_sizes(n, count):
     """``count`` coalition sizes by the contract: one random_sample call on NumPy's global generator -> (count,) int32."""
-    u = np.random.random_sample(int(count))
-    return np.minimum(n - 1, 1 + np.searchsorted(size_cdf(n), u, side="right")).astype(np.int32)
+    return _draw_sizes(_regions(n), count)
 
 
 def draw(n, samples, paired=True, device="cuda"):

@@ -1,0 +1,104 @@
+"""final_wide_kernel_shapley.py - region Shapley values of a wide game (65 .. 1024 regions) by the regression (KernelSHAP) estimator
+with the analytic Gram matrix (wide_kernelshap.py); kernel_stage.py is the stage for 2 .. 64 regions.
+
+Per selected cloud, under the wide experiment folder of that region count (``exp_folder``; the folder final_wide_shapley.py uses):
+
+    kernelshap/coalitions.npy                     (M, W) uint64  the sampled rows, bit (r & 63) of word (r >> 6) = region r kept
+    kernelshap/rewards.npy                        (M,) float32   their rewards
+    kernelshap/region_shapley_value.npy           (R,) float64   the estimate from all M rows
+    kernelshap/running_counts.npy                 (k,) int64     row counts c (R + 1), c in stage 1's sample counts, <= M
+    kernelshap/running_region_shapley_value.npy   (k, R) float64 the estimate from the first count rows
+
+``--samples`` is the number of rows M (model evaluations; default 1000 (R + 1), stage 1's budget).  The clouds, the FPS centres and
+the region ids are final_wide_shapley.py's (wide_stage.cal_region_id).  The draws after the sizes come from the device sampler
+whatever ``--sampler`` says (the contract of DESIGN.md 5f; the flag is taken because the wide stages share one set of flags), and
+a cloud that is not selected performs the same draws, so what a cloud gets does not depend on which others are selected.  There is no exact
+value at these region counts: where stage 1 has written the cloud's permutation estimate (region_shapley/<i>_<count>.npy), the
+cloud's line gives the max and RMS difference to the one of the most permutations - a cross-check, not an error.  Single process:
+under several ranks rank 0 does the work and the others wait at the end.
+"""
+import glob
+import os
+
+import numpy as np
+import torch
+
+from . import dist as iqdist
+from . import shapley_stage as stage1
+from . import wide_kernelshap, wide_stage
+from .final_util import get_folder_name_list, load_model, mkdir
+
+FILES = ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value")
+
+
+def kernel_one_cloud(model, data, lbl, region_id, args):
+    """-> dict of one cloud's artefacts (ndarrays) plus v_full and v_empty."""
+    r = args.num_regions
+    g = wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, coalitions=args.coalitions)
+    running = g["running"]
+    return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
+            "running_counts": np.array(sorted(running), dtype=np.int64),
+            "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), r),
+            "v_full": g["v_full"], "v_empty": g["v_empty"]}
+
+
+def stage1_estimate(result_path, i):
+    """Stage 1's region_shapley/<i>_<count>.npy of the largest count there is -> (count, (R,) array), or None."""
+    found = {}
+    for path in glob.glob(result_path + "region_shapley/%d_*.npy" % i):
+        count = os.path.basename(path)[:-4].split("_")[-1]
+        if count.isdigit():
+            found[int(count)] = path
+    if not found:
+        return None
+    return max(found), np.load(found[max(found)])
+
+
+def _skip_draw(result_path, args, save=False):
+    """What a cloud that is not selected draws: the same sizes and permutations, nothing written."""
+    samples = args.samples or wide_kernelshap.default_samples(args.num_regions)
+    wide_kernelshap.draw(args.num_regions, samples, not args.unpaired, args.device, skip=True)
+
+
+def run(args):
+    model = load_model(args)
+    with torch.no_grad():
+        for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), _skip_draw):
+            mkdir(result_path + "kernelshap/")
+            region_id = wide_stage.cal_region_id(data, fps_index, result_path, save=False)
+            out = kernel_one_cloud(model, data, lbl, region_id, args)
+            for key in FILES:
+                np.save(result_path + "kernelshap/%s.npy" % key, out[key])
+            phi = out["region_shapley_value"]
+            line = "pointcloud:%s, index:%d, regions:%d, rows:%d, sum(phi)=%.6f, v_full - v_empty=%.6f" % (
+                name, i, args.num_regions, out["coalitions"].shape[0], phi.sum(), out["v_full"] - out["v_empty"])
+            other = stage1_estimate(result_path, i)
+            if other is not None and other[1].shape == phi.shape:
+                diff = phi - other[1]
+                line += ", against %d permutations: max difference %.4g, rms %.4g" % (
+                    other[0], np.abs(diff).max(), np.sqrt((diff ** 2).mean()))
+            print(line)
+
+
+def make_args(argv=None):
+    parser = stage1.build_parser()
+    wide_stage.add_wide_flags(parser, route=False)
+    parser.add_argument("--samples", type=int, default=None,
+                        help="coalition rows (model evaluations) per cloud; default 1000 (num_regions + 1)")
+    parser.add_argument("--unpaired", action="store_true", help="do not follow every sampled coalition with its complement")
+    args = wide_stage.parse_wide_args(parser, argv, "final_kernel_shapley.py", samples=False)
+    if args.samples is not None and args.samples < 2:
+        parser.error("--samples %d: a count of at least 2" % args.samples)
+    return args
+
+
+@iqdist.record
+def main(argv=None):
+    args = make_args(argv)
+    stage1.finish_args(args)
+    wide_stage.check_points(args)
+    stage1.rank0_only(run, args, "wide kernelshap")
+
+
+if __name__ == "__main__":
+    main()
