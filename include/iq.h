@@ -68,8 +68,9 @@ enum {
  * iq_sample_permutations_wide, iq_context_regions_wide).
  * 114: new entry points, no layout change (the regression estimator of Shapley values: iq_kshap_keep_masks .. iq_kshap_solve).
  * 115: new entry points, no layout change (the regression estimator of wide games: iq_kshap_keep_masks_wide,
- * iq_kshap_scratch_bytes_wide, iq_kshap_moment_wide, iq_kshap_phi_analytic). */
-#define IQ_ABI_VERSION 115
+ * iq_kshap_scratch_bytes_wide, iq_kshap_moment_wide, iq_kshap_phi_analytic).
+ * 116: new entry point, no layout change (the counter-based draw of a wide game's rows: iq_kshap_draw_counter). */
+#define IQ_ABI_VERSION 116
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -667,6 +668,34 @@ int iq_kshap_moment_wide(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, c
  * values: 0 but for the rounding of c); phi_i = (2 H) (y_i - d) + delta / R.  No status word: there is no singular case. */
 int iq_kshap_phi_analytic(const double* b /*G,R raw*/, const double* wsum /*1, device*/, const double* delta /*G*/,
                           double* phi /*G,R*/, int R, int G, iq_stream_t stream);
+
+/* The COUNTER-BASED draw of a wide game's rows (csrc/iq_kshap_draw.hip): sizes and members of samples first .. first + S - 1 of one
+ * cloud in one launch, each a pure function of (seed, stream, m, R) - no generator state, no sequential part, any range of rows
+ * drawn alone, the chunking without influence.  Another contract than the MT19937 stream of iq_kshap_keep_masks_wide's callers,
+ * which stays the default; the estimator needs a size under p(s) ~ 1 / (s (R - s)), a uniform s-subset and repeatability only.
+ *
+ * Generator: Philox4x32-10.  Multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85 after every round
+ * but the last; ten rounds of (c0,c1,c2,c3) -> (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)).
+ * Known answers: counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; all ffffffff -> 408f276d 41c83b0e a20bc7c6 6d5451fd;
+ * counter 243f6a88 85a308d3 13198a2e 03707344, key a4093822 299f31d0 -> d16cfe09 94fdcceb 5001e420 24126ea1.
+ * Key: (seed & 0xffffffff, stream & 0xffffffff); the drivers pass --seed and the cloud's index.  m: the 64-bit sample index
+ * within the cloud, from 0, as (m_lo, m_hi).
+ *
+ * Size of sample m: words w0 .. w3 of the block with counter (m_lo, m_hi, 0, 1); u = ((w0 >> 5) 2^26 + (w1 >> 6)) / 2^53 (NumPy's
+ * random_sample construction); s = min(R - 1, 1 + #{k : cdf[k] <= u}) (searchsorted, side = "right").  cdf: R - 1 float64 on the
+ * device, the host's table of P(size <= k + 1); the device divides nothing, so host and device agree bit for bit.
+ * Members of sample m: region i has the 32-bit key u_i = word (i & 3) of the block with counter (m_lo, m_hi, i >> 2, 0) and the
+ * composite key (u_i << 10) | i - 42 bits, no two regions share one; S_m = the s regions of the smallest composite keys.  That is
+ * the random-keys construction of a uniform s-subset, exact except where the s-th and (s+1)-th 32-bit keys are equal: there the
+ * lower index wins.  A row holds two equal 32-bit keys AT ALL with probability below R^2 / 2^33, and they must also be the s-th and
+ * (s+1)-th: at most a fraction R / 2^32 of the rows (2.4e-7 at R = 1024) can be affected.
+ * Rows: unpaired, row j of keep is S_{first + j}; paired, row 2j is S_{first + j} and row 2j + 1 its complement within the R bits;
+ * bits at or above R are 0; keep is (rows, W), W = ceil(R / 64), in the format of "Wide coalitions" below.  sizes[j] = s of sample
+ * first + j (NULL: not written).
+ * Checks: 2 <= R <= IQ_MAX_WIDE_REGIONS; 0 <= S <= 2^29; first >= 0 and first + S <= 2^62; S == 0 is IQ_OK and nothing is read;
+ * otherwise cdf and keep must not be NULL.  One wave per sample, no atomics, nothing read back. */
+int iq_kshap_draw_counter(uint64_t seed, uint64_t stream, int64_t first, int S, int R, const double* cdf /*R-1, device*/, int paired,
+                          uint64_t* keep /*rows,W*/, int32_t* sizes /*S or NULL*/, iq_stream_t queue);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

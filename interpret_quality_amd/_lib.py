@@ -146,6 +146,7 @@ SIGNATURES = {
     "iq_kshap_scratch_bytes_wide": (_SZ, [_I, _I, _I]),
     "iq_kshap_moment_wide": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "iq_kshap_phi_analytic": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "iq_kshap_draw_counter": (_I, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, _I, _I, _P, _I, _P, _P, _P]),
     "iq_prefix_keep_masks_wide": (_I, [_P, _P, _I, _I, _P]),
     "iq_context_keep_masks_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "iq_sample_wide_workspace_bytes": (_SZ, [_I, _I]),
@@ -175,7 +176,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 115  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 116  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -657,6 +657,32 @@ def kshap_phi_analytic(b, wsum, delta):
     return phi
 
 
+def kshap_draw_counter(seed, stream, first, count, r, cdf=None, paired=True, device="cuda"):
+    """The counter-based draw of samples ``first .. first + count - 1`` of one cloud (iq_kshap_draw_counter: Philox4x32-10 keyed by
+    (seed, stream), each sample a pure function of (seed, stream, index, r)) -> (keep (2 count or count, W) int64-typed wide rows,
+    every set followed by its complement within the R bits when ``paired``; sizes (count,) int32), both on ``device``.  ``cdf``:
+    (r-1,) float64 table of P(size <= k + 1), ndarray or device tensor; None: ``kernelshap._size_cdf(r)``.  One launch."""
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    first, count = int(first), int(count)
+    if count < 0 or count > 1 << 29 or first < 0 or first + count > 1 << 62:
+        raise _lib.IqError("kshap_draw_counter: first=%d, count=%d (0 <= count <= 2^29, 0 <= first, first + count <= 2^62)" % (first, count))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.IqError("kshap_draw_counter: device must be a CUDA/HIP device (the HIP path has no CPU fallback)")
+    if cdf is None:
+        from . import kernelshap
+        cdf = kernelshap._size_cdf(r)
+    if isinstance(cdf, np.ndarray):
+        cdf = torch.from_numpy(np.ascontiguousarray(cdf, dtype=np.float64)).to(device)
+    _shape(cdf, "cdf", r - 1)
+    keep = torch.empty((2 * count if paired else count, wide_words(r)), dtype=torch.int64, device=cdf.device)
+    sizes = torch.empty((count,), dtype=torch.int32, device=cdf.device)
+    _lib.check(lib.iq_kshap_draw_counter(int(seed) & 0xFFFFFFFF, int(stream) & 0xFFFFFFFF, first, count, r, _dev(cdf, torch.float64, "cdf"),
+                                         int(bool(paired)), _p(keep), _p(sizes), _stream()), "iq_kshap_draw_counter")
+    return keep, sizes
+
+
 def fps(xyz, npoint):
     """xyz (B,N,3) f32 -> (B,npoint) i32."""
     lib = _lib.load()

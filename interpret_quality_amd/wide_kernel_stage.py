@@ -8,6 +8,7 @@ Per selected cloud, under the wide experiment folder of that region count (``exp
     kernelshap/region_shapley_value.npy           (R,) float64   the estimate from all M rows
     kernelshap/running_counts.npy                 (k,) int64     row counts c (R + 1), c in stage 1's sample counts, <= M
     kernelshap/running_region_shapley_value.npy   (k, R) float64 the estimate from the first count rows
+    kernelshap/draw.json                          {"draw", "seed", "stream"}: the contract that made the rows
 
 ``--samples`` is the number of rows M (model evaluations; default 1000 (R + 1), stage 1's budget).  The clouds, the FPS centres and
 the region ids are final_wide_shapley.py's (wide_stage.cal_region_id).  The draws after the sizes come from the device sampler
@@ -16,8 +17,13 @@ a cloud that is not selected performs the same draws, so what a cloud gets does 
 value at these region counts: where stage 1 has written the cloud's permutation estimate (region_shapley/<i>_<count>.npy), the
 cloud's line gives the max and RMS difference to the one of the most permutations - a cross-check, not an error.  Single process:
 under several ranks rank 0 does the work and the others wait at the end.
+
+``--draw counter`` (default ``stream``, all of the above) draws the rows by the counter-based contract instead: row
+m of cloud i is a function of (--seed, i, m, R) alone, so a cloud that is not selected draws nothing and NumPy's generator is not
+touched.  draw.json's "stream" is the cloud's index under ``counter`` and null under ``stream``.
 """
 import glob
+import json
 import os
 
 import numpy as np
@@ -31,10 +37,12 @@ from .final_util import get_folder_name_list, load_model, mkdir
 FILES = ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value")
 
 
-def kernel_one_cloud(model, data, lbl, region_id, args):
-    """-> dict of one cloud's artefacts (ndarrays) plus v_full and v_empty."""
+def kernel_one_cloud(model, data, lbl, region_id, args, cloud=0):
+    """-> dict of one cloud's artefacts (ndarrays) plus v_full and v_empty.  ``cloud``: its index, the key's second word under
+    ``--draw counter``."""
     r = args.num_regions
-    g = wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, coalitions=args.coalitions)
+    g = wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, coalitions=args.coalitions,
+                             draw=args.draw, seed=args.seed, stream=cloud)
     running = g["running"]
     return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
             "running_counts": np.array(sorted(running), dtype=np.int64),
@@ -55,7 +63,10 @@ def stage1_estimate(result_path, i):
 
 
 def _skip_draw(result_path, args, save=False):
-    """What a cloud that is not selected draws: the same sizes and permutations, nothing written."""
+    """What a cloud that is not selected draws: the same sizes and permutations, nothing written; under ``--draw counter``
+    nothing at all."""
+    if args.draw == "counter":
+        return
     samples = args.samples or wide_kernelshap.default_samples(args.num_regions)
     wide_kernelshap.draw(args.num_regions, samples, not args.unpaired, args.device, skip=True)
 
@@ -66,9 +77,11 @@ def run(args):
         for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), _skip_draw):
             mkdir(result_path + "kernelshap/")
             region_id = wide_stage.cal_region_id(data, fps_index, result_path, save=False)
-            out = kernel_one_cloud(model, data, lbl, region_id, args)
+            out = kernel_one_cloud(model, data, lbl, region_id, args, i)
             for key in FILES:
                 np.save(result_path + "kernelshap/%s.npy" % key, out[key])
+            with open(result_path + "kernelshap/draw.json", "w") as f:
+                json.dump({"draw": args.draw, "seed": int(args.seed), "stream": i if args.draw == "counter" else None}, f)
             phi = out["region_shapley_value"]
             line = "pointcloud:%s, index:%d, regions:%d, rows:%d, sum(phi)=%.6f, v_full - v_empty=%.6f" % (
                 name, i, args.num_regions, out["coalitions"].shape[0], phi.sum(), out["v_full"] - out["v_empty"])
@@ -86,6 +99,9 @@ def make_args(argv=None):
     parser.add_argument("--samples", type=int, default=None,
                         help="coalition rows (model evaluations) per cloud; default 1000 (num_regions + 1)")
     parser.add_argument("--unpaired", action="store_true", help="do not follow every sampled coalition with its complement")
+    parser.add_argument("--draw", choices=wide_kernelshap.DRAWS, default="stream",
+                        help="how the rows are drawn: from NumPy's MT19937 stream (default), or counter-based (Philox keyed by "
+                             "--seed and the cloud's index): any cloud alone, no skip draws")
     args = wide_stage.parse_wide_args(parser, argv, "final_kernel_shapley.py", samples=False)
     if args.samples is not None and args.samples < 2:
         parser.error("--samples %d: a count of at least 2" % args.samples)

@@ -8,6 +8,8 @@ estimator"):
   generator; members: the first s_m entries of permutation m, the S permutations drawn after the sizes on the device from the same
   stream (``hip_ops.sample_permutations_wide``), a chunk of samples at a time - the full permutations of 512 k samples of 1024
   regions would be 2 GB - each chunk turned into keep rows before the next is drawn; the state is handed back to the host;
+* or, ``draw="counter"``, sizes and members by the counter-based contract (``draw_counter``; include/iq.h, "The COUNTER-BASED
+  draw"): Philox4x32-10 keyed by (seed, stream), row m a function of (seed, stream, m, R) alone, one launch, no generator state;
 * pairing (default): row 2m is S_m, row 2m+1 its complement, M = 2S rows;
 * A is the expectation of z z^T under the size law, alpha I + c 1 1^T, so the constrained solve is the closed form
   ``phi_i = 2 H_{R-1} (b_i - mean(b)) + delta / R`` with b = (1/W) sum w z (v - v0): no matrix, no factorisation, no singular case,
@@ -26,6 +28,7 @@ from ._lib import IqError
 
 MAX_REGIONS = hip_ops.MAX_WIDE_REGIONS
 GRAMS = ("analytic",)
+DRAWS = ("stream", "counter")   # the contract the rows are drawn by: NumPy's MT19937 stream (the default), or Philox by (seed, stream, row)
 DRAW_CHUNK = 4096      # samples drawn per step of ``draw``: 16 MB of permutations at 1024 regions
 SAMPLED_REFUSAL = ("the wide estimator has gram='analytic' only: the sampled Gram matrix of more than 64 regions needs an R x R "
                    "float64 factorisation over several workgroups and more rows than regions before it is regular, and on the one "
@@ -80,6 +83,28 @@ def draw(r, samples, paired=True, device="cuda", chunk=DRAW_CHUNK, skip=False):
     return keep, sizes
 
 
+_draw_stream = draw      # ``game`` and ``shapley`` have an argument of that name
+
+
+def _draw_kind(kind):
+    if kind not in DRAWS:
+        raise IqError("draw must be one of %s, got %r" % (DRAWS, kind))
+    return kind
+
+
+def draw_counter(r, samples, seed, stream=0, paired=True, device="cuda", first=0):
+    """One cloud's COUNTER-BASED draw of ``samples`` rows (paired: rounded down to even, half of them drawn) -> (keep (M,W)
+    int64-typed device tensor, sizes (S,) int32 ndarray): samples ``first .. first + S - 1`` of the cloud ``stream`` under ``seed``
+    (include/iq.h, "The COUNTER-BASED draw"), each a pure function of (seed, stream, index, r).  One launch, no
+    chunks, no generator state: NumPy's global generator is not touched and a cloud that is not selected draws nothing."""
+    r = _regions(r)
+    s = int(samples) // 2 if paired else int(samples)
+    if s < 1:
+        raise IqError("samples=%d leaves no coalition to draw" % int(samples))
+    keep, sizes = hip_ops.kshap_draw_counter(seed, stream, first, s, r, size_cdf(r), paired, device)
+    return keep, sizes.cpu().numpy()
+
+
 def enumerated(r, device):
     """``kernelshap.enumerated`` with the rows widened to (2^R - 2, 1): every proper coalition of at most exact.MAX_PLAYERS regions
     and the weight under which the regression returns the exact Shapley vector."""
@@ -132,19 +157,26 @@ def running_estimates(keep, v, v_empty, v_full, r, counts, gram="analytic"):
     return {c: estimate(keep[:c].contiguous(), v[:c].contiguous(), v_empty, v_full, r, None, gram) for c in counts}
 
 
-def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None):
+def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",
+         seed=1, stream=0):
     """One cloud's sampled (or, at most exact.MAX_PLAYERS regions, enumerated) game with everything the driver stores: dict of
     keep (M,W), weights (None when sampled), v (M,) float32 rewards, v_full, v_empty, phi (R,) and running {count: phi of the
-    first ``count`` rows}."""
+    first ``count`` rows}.  ``draw``: "stream" - ``draw`` on NumPy's global generator - or "counter" - ``draw_counter`` keyed by
+    (``seed``, ``stream``), which the other kind ignores."""
     r = _regions(args.num_regions)
     _gram(gram)
+    _draw_kind(draw)
     weights = None
     if isinstance(samples, str):
         if samples != "all":
             raise IqError("samples must be a count, None or 'all', got %r" % (samples,))
         keep, weights = enumerated(r, data.device)
     else:
-        keep, _ = draw(r, default_samples(r) if samples is None else samples, paired, data.device)
+        samples = default_samples(r) if samples is None else samples
+        if draw == "counter":
+            keep, _ = draw_counter(r, samples, seed, stream, paired, data.device)
+        else:
+            keep, _ = _draw_stream(r, samples, paired, data.device)
     v, v_full, v_empty = rewards(model, data, lbl, region_id, args, keep, coalitions)
     phi = estimate(keep, v, v_empty, v_full, r, weights, gram)
     running = {}
@@ -153,7 +185,8 @@ def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="ana
     return {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
 
 
-def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None):
+def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",
+            seed=1, stream=0):
     """-> (phi (R,) float64 ndarray, v_full, v_empty, running {count: (R,) phi of the first ``count`` rows}) of one cloud."""
-    g = game(model, data, lbl, region_id, args, samples, paired, gram, counts, coalitions)
+    g = game(model, data, lbl, region_id, args, samples, paired, gram, counts, coalitions, draw, seed, stream)
     return g["phi"], g["v_full"], g["v_empty"], g["running"]
