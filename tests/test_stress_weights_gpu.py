@@ -15,6 +15,7 @@
 (c) PointNet++, PointConv, GCNN and DGCNN with dead channels and the negative shift: the bars of tests/test_fuzz_gpu.py against
     the dense HIP forward and the float32 oracle; PointNet++'s member-walk twin (5 = 21) bit for bit.  These run the `>= +0`
     assumptions of the integer maxima of csrc/iq_pointnet2.hip on rows that are exactly 0 and on a bias of -0.0.
+    (DGCNN's 1e-2 here stays; tests/test_dgcnn_f64_gpu.py holds the same weights to the float64 bar on clouds with decidable graphs.)
 
 Row counts of the PointNet coalitions: 1, 33, 65, 96, 97, 129, 193 and 200 (both sides of the 32 / 64 / 96 chunk edges, the empty and
 the full coalition) among 16.  No four region sizes give all eight counts (exhaustive search), so the cloud has five regions of
