@@ -69,8 +69,9 @@ enum {
  * 114: new entry points, no layout change (the regression estimator of Shapley values: iq_kshap_keep_masks .. iq_kshap_solve).
  * 115: new entry points, no layout change (the regression estimator of wide games: iq_kshap_keep_masks_wide,
  * iq_kshap_scratch_bytes_wide, iq_kshap_moment_wide, iq_kshap_phi_analytic).
- * 116: new entry point, no layout change (the counter-based draw of a wide game's rows: iq_kshap_draw_counter). */
-#define IQ_ABI_VERSION 116
+ * 116: new entry point, no layout change (the counter-based draw of a wide game's rows: iq_kshap_draw_counter).
+ * 117: new entry point, no layout change (the fused PointConv path's inverse density on its own: iq_pointconv_inverse_density). */
+#define IQ_ABI_VERSION 117
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -549,6 +550,11 @@ int iq_sort_neighbours(const float* q, const float* keys, int32_t* idx, int B, i
  * d = square_distance(xyz, xyz) - the density itself (the fused PointConv path keeps its inverse).
  * Within 2e-6 relative of the reference.  xyz (B,N,3) -> out (B,N); B <= 65535. */
 int iq_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream);
+
+/* The kernel the fused PointConv path (iq_pointconv_forward, iq_pointconv_coalitions) runs in front of each DensityNet, on its own:
+ * out[b,i] = 1 / iq_density's value, the sum taken as exp2(d * k) on the hardware exponential with one division at the end.  The
+ * bandwidth is rounded to float32, as the weights hold it.  xyz (B,N,3) -> out (B,N); B <= 65535, N <= 3072. */
+int iq_pointconv_inverse_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Exact games by full enumeration (csrc/iq_lattice.hip)

@@ -133,6 +133,7 @@ SIGNATURES = {
     "iq_knn_point": (_I, [_P, _P, _I, _P, _P, _SZ, _I, _I, _I, _P]),
     "iq_sort_neighbours": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "iq_density": (_I, [_P, ctypes.c_double, _P, _I, _I, _P]),
+    "iq_pointconv_inverse_density": (_I, [_P, ctypes.c_double, _P, _I, _I, _P]),
     "iq_enum_keep_masks": (_I, [_P, ctypes.c_uint64, _SZ, _P, _I, ctypes.c_uint64, _P]),
     "iq_exact_scratch_bytes": (_SZ, [_I, _I]),
     "iq_exact_shapley": (_I, [_P, _I, _P, _P, _SZ, _P]),
@@ -176,7 +177,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 116  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 117  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -55,24 +55,37 @@ __global__ __launch_bounds__(kThreads) void pc_density_kernel(const float* __res
     const f32x4 q = *reinterpret_cast<const f32x4*>(pts + i * 4);
     // exp(-d / c0) / c1 summed as exp2(d * k) with the division by c1 once at the end: the N^2 loop is 3 fma + 2 add + 1 mul +
     // v_exp_f32 per pair instead of a full-precision expf and two divisions (the density only feeds DensityNet, a smooth
-    // function; agreement with the reference stays at the 1e-6 level)
+    // function).  Against float64 the kernel is within 4 x the float32 reference's own error + 1e-7 at unit scale and at the
+    // ends of the pose sweeps' grids (iq_pointconv_inverse_density, tests/test_pose_f64_gpu.py).
     const float c0 = 2.0f * bw * bw, c1 = 2.5f * bw;
     const float k2 = -1.4426950408889634f / c0;
-    float s0 = 0.f, s1 = 0.f;
+    auto term = [&](int j) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(pts + j * 4);
+        return __builtin_amdgcn_exp2f(((-2.f * fmaf(q[2], v[2], fmaf(q[1], v[1], q[0] * v[0])) + q[3]) + v[3]) * k2);
+    };
+    // Summed in blocks of kBlock terms, two accumulators to a block, the block sums added up: at a bandwidth as wide as the cloud
+    // every term is near 1, and one running float32 sum over N / 2 of them loses sqrt(N) ulps - 1.7e-6 at N = 511 against the
+    // float32 reference's 2e-7 (measured against float64, tests/test_pose_f64_gpu.py), which was the whole error of this kernel.
+    constexpr int kBlock = 32;
+    float sum = 0.f;
     int j = 0;
+    for (; j + kBlock <= N; j += kBlock) {
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll 4
+        for (int t = 0; t < kBlock; t += 2) {
+            s0 += term(j + t);
+            s1 += term(j + t + 1);
+        }
+        sum += s0 + s1;
+    }
+    float s0 = 0.f, s1 = 0.f;
     for (; j + 1 < N; j += 2) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(pts + j * 4);
-        const f32x4 u = *reinterpret_cast<const f32x4*>(pts + j * 4 + 4);
-        const float d0 = (-2.f * fmaf(q[2], v[2], fmaf(q[1], v[1], q[0] * v[0])) + q[3]) + v[3];
-        const float d1 = (-2.f * fmaf(q[2], u[2], fmaf(q[1], u[1], q[0] * u[0])) + q[3]) + u[3];
-        s0 += __builtin_amdgcn_exp2f(d0 * k2);
-        s1 += __builtin_amdgcn_exp2f(d1 * k2);
+        s0 += term(j);
+        s1 += term(j + 1);
     }
-    if (j < N) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(pts + j * 4);
-        s0 += __builtin_amdgcn_exp2f(((-2.f * fmaf(q[2], v[2], fmaf(q[1], v[1], q[0] * v[0])) + q[3]) + v[3]) * k2);
-    }
-    inv_density[(size_t)b * N + i] = 1.0f / (((s0 + s1) / c1) / (float)N);
+    if (j < N) s0 += term(j);
+    sum += s0 + s1;
+    inv_density[(size_t)b * N + i] = 1.0f / ((sum / c1) / (float)N);
 }
 
 // ---- K nearest points (models/pointconv.py:103-114): queries on the lanes, keys on the accumulator rows ----
@@ -1278,4 +1291,16 @@ extern "C" int iq_pointconv_coalitions_wide(const iq_pointconv_weights* w, const
                                             iq_stream_t stream) {
     return iq_pointconv_coalitions_cached_wide(w, clouds, centers, region_id, keep, cloud_of, logits, workspace, workspace_bytes, B,
                                                nclouds, N, nullptr, R, stream);
+}
+
+// pc_density_kernel on its own: what sa1 - sa3 of the network feed their DensityNets, for tests that hold the kernel itself (and not
+// only the logits behind the DensityNet) to the reference's density.  N * 16 bytes of LDS: the default dynamic limit of 48 KB.
+extern "C" int iq_pointconv_inverse_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream) {
+    IQ_REQUIRE(B >= 0 && B <= 65535 && N >= 1 && N <= 3072, "iq_pointconv_inverse_density: B=%d N=%d (N <= 3072)", B, N);
+    IQ_REQUIRE(bandwidth > 0.0, "iq_pointconv_inverse_density: bandwidth %g must be positive", bandwidth);
+    if (B == 0) return IQ_OK;
+    IQ_REQUIRE(xyz && out, "iq_pointconv_inverse_density: null pointer");
+    hipLaunchKernelGGL(pc_density_kernel, dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)N * 16, iq::as_stream(stream),
+                       xyz, (float)bandwidth, out, N);
+    return iq::check_launch("pc_density_kernel");
 }

@@ -822,6 +822,17 @@ def density(xyz, bandwidth):
     return out
 
 
+def pointconv_inverse_density(xyz, bandwidth):
+    """xyz (B,N,3) f32, N <= 3072 -> (B,N) f32: the inverse density as the fused PointConv path computes it in front of its
+    DensityNets (iq_pointconv_inverse_density); 1 / ``density`` up to that kernel's rounding."""
+    lib = _lib.load()
+    b, n, _ = _shape(xyz, "xyz", None, None, 3)
+    out = torch.empty((b, n), dtype=torch.float32, device=xyz.device)
+    _lib.check(lib.iq_pointconv_inverse_density(_dev(xyz, torch.float32, "xyz"), float(bandwidth), _p(out), b, n, _stream()),
+               "iq_pointconv_inverse_density")
+    return out
+
+
 SMOOTHNESS_MODES = ("linearity", "planarity", "scattering")
 
 

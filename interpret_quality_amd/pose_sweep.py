@@ -177,7 +177,9 @@ def sharded_shapley(model, data, poses, lbl, region_id, orders, args):
     """Region Shapley values of the original cloud ``data`` (1,N,3) and of its perturbed copies ``poses`` (P,N,3), the
     P + 1 clouds sharded over the ranks and gathered once (``sharded_over_poses``).  Returns (orig (R,) float64 ndarray,
     phi (P,R) float64 tensor, logits (P, S*(R+1), C)), the same on every rank.  A cloud's values do not depend on the batch
-    or shard it travels in (tested bitwise)."""
+    or shard it travels in: tested bitwise by tests/test_pose_f64_gpu.py (a cloud alone against the same cloud beside one that moves
+    the launch across PointNet++'s pair-table capacity, and ``pose_batch`` 8 against 1 on such a sweep) and by the two-rank
+    sweeps of tests/test_dist_gpu.py."""
     phi, logits = sharded_over_poses(data, poses, lambda clouds: shapley_over_poses(model, clouds, lbl, region_id, orders, args))
     return phi[0].cpu().numpy(), phi[1:], logits[1:]
 

@@ -16,6 +16,10 @@ straddle the 20 | 21 boundary, what decides the set is the gap between the centr
 and both must meet ``MARGIN`` (stricter than exempting the exact tie alone: a kept row that changes sides with the centre enters
 or leaves the list).
 
+Poses.  The stress shape also runs with base weights under scale 0.5, scale 2.0 and the translation 0.5 (1,1,1) / sqrt 3 (``POSE``,
+f64_cases.POSES: the ends of the pose sweeps' grids), masked with the posed cloud's centre.  Each pose has a seed of its own from the
+same ``find_seed`` under the same MARGIN and SEARCH_LIMIT; all three were found at 40 points (tries 1, 12 and 14).
+
 Sizes left out: 1024 points and beyond - the N > 1024 L2-gather EdgeConv path among them - stay with the golden and oracle tests of
 tests/test_dgcnn_gpu.py.  With thousands of queries per cloud and layer no seed meets the condition.
 
@@ -56,7 +60,12 @@ SHAPES = {
     "walk": ((40, 8, 1, 8), False),        # nc * 8 <= b: the layer-1 graph comes from the neighbour-list walk
     "wide": ((40, 128, 2, 8), True),       # the wide entry
     "n128": ((128, 8, 1, 2), False),       # four pads; the largest size at which the condition is still cheap to meet
+    # the stress shape under the ends of the pose sweeps' grids (``POSE``; f64_cases.POSES), masked with the posed cloud's centre
+    "scale_lo": ((40, 8, 2, 8), False),
+    "scale_hi": ((40, 8, 2, 8), False),
+    "shift": ((40, 8, 2, 8), False),
 }
+POSE = {"scale_lo": "s0.5", "scale_hi": "s2.0", "shift": "t+"}
 SEARCH_START = {name: 9000 + 1000 * i for i, name in enumerate(SHAPES)}
 # The stress size has a seed per variant.  Under the margin above (the centre's copies as one row, gaps on both sides) about one seed
 # in twelve qualifies for ONE variant at this size, and the walk from 9000 found none for all five at once within SEARCH_LIMIT
@@ -78,12 +87,15 @@ SEEDS = {
     ("walk", "base"): 14002,         # try 3
     ("wide", "base"): 15029,         # try 30
     ("n128", "base"): 16079,         # try 80
+    ("scale_lo", "base"): 17000,     # try 1
+    ("scale_hi", "base"): 18011,     # try 12
+    ("shift", "base"): 19013,        # try 14
 }
 
 
 def make_case(name, seed):
     (n, r, nc, b), wide = SHAPES[name]
-    return F.Case(name, probes.CoalitionCase("dgcnn", n, r, nc, b, seed), wide=wide)
+    return F.Case(name, probes.CoalitionCase("dgcnn", n, r, nc, b, seed), wide=wide, pose=POSE.get(name))
 
 
 def pairs():

@@ -25,6 +25,10 @@ route and no kernel was changed.
              the same graphs on these clouds, and 57 changes nothing in DGCNN, whose heads run on the fp32 MFMA whatever the key)
   centre multiplicity (M = 20 and the empty coalition), either entry, alone and under 5 = 12, 20           1.41
   weights with 16 significant bits on the device (last test): every route 39 x e_ref, i.e. 9.5 x the bar
+Since then the stress shape also runs under scale 0.5, scale 2.0 and a translation of 0.5 (cases ``scale_lo``, ``scale_hi``, ``shift``:
+fifteen pairs, 32 ids, 180 graph comparisons, still no query with another neighbour set).  On these three, e_ref 9.0e-07 .. 1.1e-06:
+forward_points and its twins 2.11 (shift) .. 2.90 (scale_hi), the coalition entry and its twins 2.01 (shift) .. 2.60 (scale_hi);
+the worst used 0.70 of the bar.
 Checked once by hand: a library in which the centre row weighs M + 1 in the mean pool (dg_compact_kernel's row_w) fails the coalition
 entry of all twelve pairs and the multiplicity test, at 1e-3 to 3e-3 of max |logit| - below the 1e-2 that DGCNN is held to elsewhere.
 """

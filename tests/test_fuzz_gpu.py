@@ -1,8 +1,9 @@
 """A seeded slice of the randomised probes (tests/fuzz_sizes.py, tests/fuzz_hotpath.py) and of the standalone geometric ops at
 the sizes where their kernels change shape: coalition paths of the five families against the dense HIP forward and the CPU
 oracle, the PointNet hot path against the oracle's loop, and iq_knn_point / iq_density / iq_sort_neighbours / the gathers /
-iq_fps / iq_ball_query against plain float64 or indexing references.  The case lists are built at collection time from fixed
-seeds plus explicit boundary cases; every id reruns alone with -k <id>."""
+iq_fps / iq_ball_query against plain float64 or indexing references, and those ops again on clouds at the ends of the pose sweeps'
+grids.  The case lists are built at collection time from fixed seeds plus explicit boundary cases; every id reruns alone with
+-k <id>."""
 import numpy as np
 import pytest
 import torch
@@ -259,3 +260,46 @@ def test_ball_query_random_shapes(b, n, s, nsample):
         assert want.max() < n                                                 # no empty ball
         assert got.shape == want.shape
         assert probes.ball_mismatch(got, want, X, Q, radius, O) <= max(1, b * s // 100)
+
+
+# ---- (d) the geometric ops at the ends of the pose sweeps' grids -------------------------------------------------------------
+
+POSED_GEOM = [(n, pose) for n in (100, 513) for pose in ("s0.5", "s2.0", "t+")]
+
+
+@pytest.mark.parametrize("n,pose", POSED_GEOM, ids=["geom-N%d-%s" % c for c in POSED_GEOM])
+def test_geometric_ops_under_sweep_poses(n, pose):
+    """One synthetic cloud scaled by 0.5 and 2.0 and translated by 0.5 (f64_cases.POSES): the ops whose float32 expanded-form
+    distances carry a larger |x|^2 there - and whose fixed radii and bandwidths meet another point density - under the checkers and
+    tolerances of the cases above."""
+    import f64_cases as F
+    from interpret_quality_amd import synth
+    from oracle import ref_cpu as O
+    x = F.apply_pose(synth.make_cloud(60 + n, n)[0][None], pose)
+    X, xd = torch.from_numpy(x), torch.from_numpy(x).to(dev())
+    for bw in (0.1, 0.4):
+        got = hip_ops.density(xd, bw).cpu().numpy()
+        want32, want64 = O.compute_density(X, bw).numpy(), probes.density64(x, bw)
+        e = lambda w: (np.abs(got - w) / np.maximum(np.abs(w), probes.DENSITY_FLOOR)).max()
+        print("N=%d %s density h=%g: vs oracle %.3g, vs float64 %.3g (the oracle vs float64 %.3g)" % (
+            n, pose, bw, e(want32), e(want64), (np.abs(want32 - want64) / np.abs(want64)).max()))
+        problems = probes.density_problems(got, want32, want64)
+        assert not problems, (bw, problems)
+    s = min(n, 128)
+    fps = hip_ops.fps(xd, s)
+    want_fps = O.farthest_point_sample(X, s)
+    assert np.array_equal(fps.cpu().numpy(), want_fps.numpy())
+    new_xyz = x[:, want_fps[0].numpy()]
+    Q, qd = torch.from_numpy(new_xyz), torch.from_numpy(new_xyz).to(dev())
+    for k in (1, 20, min(n, 128)):
+        nbad = probes.check_knn(hip_ops.knn_point(xd, qd, k).cpu().numpy(), x, new_xyz, k)
+        assert nbad <= max(2, s // 100), (k, nbad)
+    for radius, nsample in ((0.1, 16), (0.2, 32), (0.4, min(n, 128))):      # sa1 of PointNet++ (the reference needs nsample <= N)
+        got = hip_ops.ball_query(xd, qd, radius, nsample).cpu().numpy()
+        want = O.query_ball_point(radius, nsample, X, Q).numpy()
+        assert want.max() < n and got.shape == want.shape
+        assert probes.ball_mismatch(got, want, X, Q, radius, O) <= max(1, s // 100), radius
+    for r in (8, 32):
+        rid = hip_ops.region_assign(xd[0].contiguous(), fps[0, :r].contiguous()).cpu().numpy()
+        want_rid = np.asarray(O.cal_region_id(X, want_fps[0, :r]))
+        assert rid.shape == (n,) and (rid != want_rid).mean() <= probes.REGION_NEAR_TIE_FRACTION, r
