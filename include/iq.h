@@ -70,8 +70,10 @@ enum {
  * 115: new entry points, no layout change (the regression estimator of wide games: iq_kshap_keep_masks_wide,
  * iq_kshap_scratch_bytes_wide, iq_kshap_moment_wide, iq_kshap_phi_analytic).
  * 116: new entry point, no layout change (the counter-based draw of a wide game's rows: iq_kshap_draw_counter).
- * 117: new entry point, no layout change (the fused PointConv path's inverse density on its own: iq_pointconv_inverse_density). */
-#define IQ_ABI_VERSION 117
+ * 117: new entry point, no layout change (the fused PointConv path's inverse density on its own: iq_pointconv_inverse_density).
+ * 118: new entry points, no layout change (all-class games on shared coalitions: iq_reward_classes, iq_shapley_games_scratch_bytes,
+ * iq_shapley_accum_games). */
+#define IQ_ABI_VERSION 118
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -162,6 +164,32 @@ int iq_reward(const float* logits /*B,C*/, int label, int modified, float* v /*B
 int iq_shapley_accum(const float* v /*S*(R+1)*/, const int32_t* orders /*S,R*/,
                      double* sv_rows, double* phi_sum, const int32_t* snap_counts, int n_snap,
                      double* snaps, int R, int S, iq_stream_t stream);
+
+/* iq_reward for G labels of the same logits - the G games a forward has already paid for: v[g*ldv + b] is what
+ * iq_reward(logits, labels[g], modified, ...) writes to v[b], bit for bit (the same maximum and sum over c ascending with the
+ * label skipped when modified, the same |m| == inf rule and final association; in normal mode maximum and sum do not depend
+ * on the label and are taken once per row).  labels: HOST pointer to G labels in [0, C), in any order, repeats allowed; they
+ * travel by value in the kernel arguments.  NULL = the labels 0 .. C-1, and G must equal C.  v: G rows of ldv >= B floats; the
+ * floats b >= B of a row are not touched, so a (G, M) table is filled one chunk of coalitions at a time (v + first, ldv = M).
+ * A row of logits is staged once in LDS for its G labels; stores are coalesced along b.
+ * Checks (IQ_EINVAL, nothing launched): 2 <= C <= 64, 1 <= G <= 64, every label in [0, C), ldv >= B.  B == 0 is IQ_OK. */
+int iq_reward_classes(const float* logits /*B,C*/, const int32_t* labels /*HOST: G, or NULL*/, int G, int modified,
+                      float* v /*G rows of ldv*/, size_t ldv, int B, int C, iq_stream_t stream);
+
+/* iq_shapley_accum / iq_shapley_accum_wide for G games on the same permutations: game g's rewards are v + g*ldv
+ * (ldv >= S*(R+1): the (G, M) table iq_reward_classes fills), its outputs phi_sum + g*R and snaps + g*n_snap*R, and they carry
+ * the bits iq_shapley_accum_wide gives for v + g*ldv alone - for R <= 64 also iq_shapley_accum's: float32 differences, widened
+ * to float64, added per region strictly in permutation order.  1 <= R <= IQ_MAX_WIDE_REGIONS (one entry for narrow and wide
+ * games), S >= 0, 1 <= G <= 65535; snap_counts ascending.  There is no sv_rows output: no (S,R) float64 row table exists, for
+ * any game.  One kernel inverts the permutations once for all games into a 16-bit (S,R) position table - that is the whole
+ * scratch, iq_shapley_games_scratch_bytes(R, S, G) (0 for refused arguments), which therefore does not grow with G - and a grid
+ * of (ceil(R/64), G) workgroups runs the staged sum of iq_shapley_accum, reading v[g][o*(R+1)+p+1] - v[g][o*(R+1)+p] through
+ * the table.  A region that a row does not name contributes 0.0; an order entry outside [0, R) is skipped and nothing is read
+ * out of bounds.  No atomics, nothing allocated, no host synchronisation. */
+size_t iq_shapley_games_scratch_bytes(int R, int S, int G);
+int iq_shapley_accum_games(const float* v /*G rows of ldv*/, size_t ldv, const int32_t* orders /*S,R*/, double* phi_sum /*G,R*/,
+                           const int32_t* snap_counts, int n_snap, double* snaps /*G,n_snap,R*/, int R, int S, int G,
+                           void* scratch, size_t scratch_bytes, iq_stream_t stream);
 
 /* final_cal_interactions.py:28-36: I[k] = ((v[4k] + v[4k+3]) - v[4k+1]) - v[4k+2] in float32. */
 int iq_interaction_reduce(const float* v /*4n*/, float* out /*n*/, int n, iq_stream_t stream);

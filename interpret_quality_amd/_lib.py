@@ -91,6 +91,9 @@ SIGNATURES = {
     "iq_context_keep_masks": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "iq_reward": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "iq_shapley_accum": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
+    "iq_reward_classes": (_I, [_P, _P, _I, _I, _P, _SZ, _I, _I, _P]),
+    "iq_shapley_games_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "iq_shapley_accum_games": (_I, [_P, _SZ, _P, _P, _P, _I, _P, _I, _I, _I, _P, _SZ, _P]),
     "iq_interaction_reduce": (_I, [_P, _P, _I, _P]),
     "iq_region_assign": (_I, [_P, _P, _P, _I, _I, _P]),
     "iq_fps": (_I, [_P, _P, _I, _I, _I, _P]),
@@ -177,7 +180,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 117  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 118  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

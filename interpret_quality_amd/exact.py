@@ -30,12 +30,14 @@ def _players(args, players):
     return pl, int(pl.size)
 
 
-def value_table(model, data, lbl, region_id, args, players=None, base=0, chunk=1 << 16):
+def value_table(model, data, lbl, region_id, args, players=None, base=0, chunk=1 << 16, classes=None):
     """Rewards of ALL coalitions of one cloud ``data`` (1,N,3): (2^n,) float32 on the device, v[c] = iq_reward of the logits of
     the cloud that keeps ``base`` and the regions players[k] of the set bits k of c (every other point collapses onto the centre,
     the mean of the cloud: tools/final_common.py:80).  ``chunk`` coalitions at a time go through the model's own
     ``coalition_logits`` (which splits launches by the memory that is free), so the logits of 2^24 coalitions are never resident
-    at once; a coalition's logits do not depend on what else is in its launch, so the table does not depend on ``chunk``."""
+    at once; a coalition's logits do not depend on what else is in its launch, so the table does not depend on ``chunk``.
+    ``classes`` (a sequence of labels, or "all"; ``lbl`` is then not read): the tables of every label from the same logits,
+    (G, 2^n), row g the bits of the call with lbl = classes[g]."""
     if not hasattr(model, "coalition_logits"):
         raise IqError("%s has no coalition entry point" % type(model).__name__)
     dev = data.device
@@ -47,14 +49,18 @@ def value_table(model, data, lbl, region_id, args, players=None, base=0, chunk=1
     rid = hip_ops.region_ids(region_id, dev, r).reshape(1, -1)
     clouds = data.contiguous()
     centers = torch.mean(data, dim=1).reshape(1, 3).contiguous()
-    v = torch.empty((1 << n,), dtype=torch.float32, device=dev)
+    v = None if classes is not None else torch.empty((1 << n,), dtype=torch.float32, device=dev)
     with torch.no_grad():
         for first in range(0, 1 << n, chunk):
             count = min(chunk, (1 << n) - first)
             keep = hip_ops.enum_keep_masks(first, count, n, dev, pl, base)
             work.add(count)
             logits = model.coalition_logits(clouds, centers, rid, keep, None, num_regions=r, validate=False)
-            v[first:first + count] = final_common.get_reward(logits, lbl, args)
+            if classes is None:
+                v[first:first + count] = final_common.get_reward(logits, lbl, args)
+            else:
+                v = final_common.reward_table(classes, logits.shape[1], 1 << n, dev) if v is None else v
+                final_common.get_reward_classes(logits, classes, args, v, first)
     return v
 
 

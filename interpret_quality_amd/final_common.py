@@ -24,6 +24,34 @@ def get_reward(logits, lbl, args):
     return hip_ops.reward(logits.contiguous(), int(lbl[0]), modified)
 
 
+ALL_CLASSES = "all"     # the ``classes`` argument that names every class of the model
+
+
+def class_labels(classes, num_classes):
+    """``classes`` - ALL_CLASSES or a sequence of labels (any order, repeats allowed) - as a list of ints in [0, num_classes)."""
+    c = int(num_classes)
+    if isinstance(classes, str):
+        if classes != ALL_CLASSES:
+            raise IqError("classes must be %r or a sequence of labels, got %r" % (ALL_CLASSES, classes))
+        return list(range(c))
+    labels = [int(x) for x in np.asarray(classes).reshape(-1)]
+    if not labels or any(not 0 <= x < c for x in labels):
+        raise IqError("classes must name at least one label in [0, %d), got %r" % (c, labels))
+    return labels
+
+
+def get_reward_classes(logits, classes, args, out=None, first=0):
+    """``get_reward`` for the labels ``classes`` (``class_labels``) of the same logits (B',C) -> (G,B'), row g the bits of
+    get_reward with lbl = classes[g]; with ``out`` (G,M) written into out[:, first:first+B'] (hip_ops.reward_classes)."""
+    modified = getattr(args, "softmax_type", "modified") != "normal"
+    return hip_ops.reward_classes(logits.contiguous(), class_labels(classes, logits.shape[1]), modified, out, first)
+
+
+def reward_table(classes, num_classes, columns, device):
+    """The empty (G,columns) float32 table that get_reward_classes fills chunk by chunk."""
+    return torch.empty((len(class_labels(classes, num_classes)), int(columns)), dtype=torch.float32, device=device)
+
+
 def cal_reward(model, data, lbl, args):
     """tools/final_common.py:26-43.  data (B',N,3) -> (v (B',), logits (B',C))."""
     x = data.permute(0, 2, 1).contiguous()

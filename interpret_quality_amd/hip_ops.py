@@ -197,6 +197,28 @@ def reward(logits, label, modified=True):
     return v
 
 
+def reward_classes(logits, labels=None, modified=True, out=None, first=0):
+    """iq_reward_classes: logits (B,C) f32, ``labels`` a sequence of labels in [0, C) (any order, repeats allowed; None = every
+    class) -> (G,B) f32 whose row g carries ``reward(logits, labels[g], modified)``'s bits.  With ``out`` ((G,M) f32, contiguous)
+    the rewards go to out[:, first:first+B] and nothing else of ``out`` is touched: a table filled one chunk of coalitions at a
+    time."""
+    lib = _lib.load()
+    b, c = _shape(logits, "logits", None, None)
+    lab = None if labels is None else [int(x) for x in labels]
+    g = c if lab is None else len(lab)
+    if out is None:
+        out, first = torch.empty((g, b), dtype=torch.float32, device=logits.device), 0
+    first = int(first)
+    _, m = _shape(out, "out", g, None)
+    if first < 0 or first + b > m:
+        raise _lib.IqError("out has %d columns: rows %d .. %d do not fit" % (m, first, first + b))
+    host = None if lab is None else (ctypes.c_int32 * max(g, 1))(*lab)
+    base = _dev(out, torch.float32, "out").value or 0
+    _lib.check(lib.iq_reward_classes(_dev(logits, torch.float32, "logits"), host, g, int(bool(modified)),
+                                     ctypes.c_void_p(base + 4 * first), m, b, c, _stream()), "iq_reward_classes")
+    return out
+
+
 def _shapley_accum(entry, v, orders, snap_counts, exact=True):
     """The body of shapley_accum and shapley_accum_wide: ``entry`` names the library call.  The kernel reads the first S*(R+1)
     rewards: a shorter ``v`` is always refused, a longer one unless ``exact`` is False."""
@@ -587,6 +609,48 @@ def shapley_accum_wide(v, orders, snap_counts=None):
     snaps or None)."""
     wide_words(orders.shape[1])
     return _shapley_accum("iq_shapley_accum_wide", v, orders, snap_counts)
+
+
+def shapley_games_scratch_bytes(num_regions, num_samples, num_games):
+    """iq_shapley_games_scratch_bytes: the 16-bit (S,R) position table of shapley_accum_games; it does not depend on the game count."""
+    return int(_lib.load().iq_shapley_games_scratch_bytes(int(num_regions), int(num_samples), int(num_games)))
+
+
+def shapley_accum_games(v, orders, snap_counts=None, validate=True):
+    """iq_shapley_accum_games: v (G,M) f32 with M >= S*(R+1) - row g the rewards of game g on the prefix coalitions of ``orders``,
+    the table reward_classes fills - and orders (S,R), 1 <= R <= MAX_WIDE_REGIONS -> (phi_sum (G,R) f64, snaps (G,n_snap,R) f64 or
+    None): per game the bits of shapley_accum_wide (for R <= 64 also shapley_accum's), without any per-game (S,R) row table.
+    ``orders``: an ndarray (validated on the host, free) or an int32 device tensor (validated by check_index_range, one 4-byte
+    read back, unless ``validate`` is False: the caller has checked them)."""
+    lib = _lib.load()
+    g, m = _shape(v, "v", None, None)
+    dev = v.device
+    if isinstance(orders, np.ndarray):
+        if orders.ndim != 2:
+            raise _lib.IqError("orders must be (S, R), got %s" % (orders.shape,))
+        check_host_indices(orders, 0, orders.shape[1], "orders")
+        orders = as_i32(orders, dev)
+    else:
+        _shape(orders, "orders", None, None)
+        if validate:
+            check_index_range(orders, 0, orders.shape[1], "orders")
+    s, r = orders.shape
+    wide_words(r)
+    if g < 1 or m < s * (r + 1):
+        raise _lib.IqError("v is (%d, %d): at least one game of %d rewards is needed for %d permutations of %d regions"
+                           % (g, m, s * (r + 1), s, r))
+    nbytes = lib.iq_shapley_games_scratch_bytes(r, s, g)
+    scratch = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    phi = torch.empty((g, r), dtype=torch.float64, device=dev)
+    snaps = counts = None
+    n_snap = 0
+    if snap_counts is not None and len(snap_counts) > 0:
+        counts = torch.tensor(list(snap_counts), dtype=torch.int32, device=dev)
+        n_snap = counts.numel()
+        snaps = torch.zeros((g, n_snap, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_shapley_accum_games(_dev(v, torch.float32, "v"), m, _p(orders), _p(phi), _p(counts), n_snap, _p(snaps), r, s, g,
+                                          _p(scratch), nbytes, _stream()), "iq_shapley_accum_games")
+    return phi, snaps
 
 
 def kshap_regions_wide(r):

@@ -143,9 +143,17 @@ def running_counts(n, rows, paired=True, counts=None):
     return [c for c in counts if 1 <= c <= rows]
 
 
-def rewards(model, data, lbl, region_id, args, keep, chunk=1 << 16):
+def _class_ends(v):
+    """The (G,M+2) reward table of ``rewards`` with ``classes`` -> (v (G,M), v_full (G,), v_empty (G,) float64 ndarrays)."""
+    ends = v[:, -2:].cpu().numpy().astype(np.float64)
+    return v[:, :-2].contiguous(), ends[:, 0].copy(), ends[:, 1].copy()
+
+
+def rewards(model, data, lbl, region_id, args, keep, chunk=1 << 16, classes=None):
     """Rewards of the coalitions ``keep`` of one cloud ``data`` (1,N,3), obtained as exact.value_table obtains them, with the
-    full and the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty)."""
+    full and the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty).
+    ``classes`` (a sequence of labels, or "all"; ``lbl`` is then not read): the rewards of every label from the same logits ->
+    (v (G,M), v_full (G,), v_empty (G,)), row g the bits of the call with lbl = classes[g]."""
     if not hasattr(model, "coalition_logits"):
         raise IqError("%s has no coalition entry point" % type(model).__name__)
     dev = data.device
@@ -154,13 +162,19 @@ def rewards(model, data, lbl, region_id, args, keep, chunk=1 << 16):
     clouds = data.contiguous()
     centers = torch.mean(data, dim=1).reshape(1, 3).contiguous()
     rows = torch.cat([keep, hip_ops.masks_to_tensor([(1 << r) - 1, 0], dev)])
-    v = torch.empty((rows.numel(),), dtype=torch.float32, device=dev)
+    v = None if classes is not None else torch.empty((rows.numel(),), dtype=torch.float32, device=dev)
     with torch.no_grad():
         for first in range(0, rows.numel(), max(1, int(chunk))):
             part = rows[first:first + chunk].contiguous()
             work.add(part.numel())
             logits = model.coalition_logits(clouds, centers, rid, part, None, num_regions=r, validate=False)
-            v[first:first + part.numel()] = final_common.get_reward(logits, lbl, args)
+            if classes is None:
+                v[first:first + part.numel()] = final_common.get_reward(logits, lbl, args)
+            else:
+                v = final_common.reward_table(classes, logits.shape[1], rows.numel(), dev) if v is None else v
+                final_common.get_reward_classes(logits, classes, args, v, first)
+    if classes is not None:
+        return _class_ends(v)
     ends = v[-2:].cpu().numpy()
     return v[:-2].contiguous(), float(ends[0]), float(ends[1])
 

@@ -142,16 +142,21 @@ def _steps(orders_dev, r, perms_per_step=None):
     return [(lo, min(lo + step, s), orders_dev[lo:lo + step].contiguous()) for lo in range(0, s, step)]
 
 
-def _rewards(model, data, lbl, rid, steps, keep, v, r, mode, args):
+def _rewards(model, data, lbl, rid, steps, keep, v, r, mode, args, reward=None):
     """The rewards of the prefix coalitions of one cloud ``data`` (1,N,3) into ``v`` (S*(R+1),), one step of ``_steps`` at a
     time.  ``keep``: None on the prefix route - a step is evaluated straight from its permutations - else step index -> the
-    step's keep rows, evaluated as arbitrary coalitions."""
+    step's keep rows, evaluated as arbitrary coalitions.  ``reward``: None - the reward of label ``lbl`` into ``v`` - or
+    ``reward(logits, first)``, which stores what it makes of a step's logits itself (coalitions first .. first + rows - 1:
+    classwise.shapley fills one table row per label); ``lbl`` and ``v`` are then not read."""
     for j, (lo, hi, step_orders) in enumerate(steps):
         if keep is None:
             logits = _prefix_logits(model, data, rid, step_orders, r, mode)
         else:
             logits = _logits(model, data, rid, keep(j), r, mode)
-        v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
+        if reward is None:
+            v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
+        else:
+            reward(logits, lo * (r + 1))
 
 
 def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None, route=None, coalitions=None):

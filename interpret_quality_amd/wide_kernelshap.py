@@ -130,10 +130,11 @@ def estimate(keep, v, v_empty, v_full, r, weights=None, gram="analytic"):
     return phi[0] if v.dim() == 1 else phi
 
 
-def rewards(model, data, lbl, region_id, args, keep, coalitions=None, chunk=1 << 16):
+def rewards(model, data, lbl, region_id, args, keep, coalitions=None, chunk=1 << 16, classes=None):
     """Rewards of the wide coalitions ``keep`` (M,W) of one cloud ``data`` (1,N,3), evaluated as ``wide.coalition_logits``
     evaluates them (``coalitions``: "dense" or "compact" for a family other than PointNet), ``chunk`` rows per call, the full and
-    the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty)."""
+    the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty).  ``classes``
+    as in kernelshap.rewards: -> (v (G,M), v_full (G,), v_empty (G,)), row g the bits of the call with lbl = classes[g]."""
     mode = wide._pick_coalitions(coalitions, data)
     dev = data.device
     r = _regions(args.num_regions)
@@ -141,12 +142,19 @@ def rewards(model, data, lbl, region_id, args, keep, coalitions=None, chunk=1 <<
     rid = hip_ops.region_ids(region_id, dev, r)
     ends = np.stack([hip_ops.region_words(np.arange(r), r), np.zeros(hip_ops.wide_words(r), dtype=np.uint64)])
     rows = torch.cat([keep, hip_ops.wide_masks_to_tensor(ends, dev)])
-    v = torch.empty((rows.shape[0],), dtype=torch.float32, device=dev)
+    v = None if classes is not None else torch.empty((rows.shape[0],), dtype=torch.float32, device=dev)
     chunk = max(1, int(chunk))
     with torch.no_grad():
         for first in range(0, rows.shape[0], chunk):
             part = rows[first:first + chunk].contiguous()
-            v[first:first + part.shape[0]] = final_common.get_reward(wide._logits(model, data, rid, part, r, mode), lbl, args)
+            logits = wide._logits(model, data, rid, part, r, mode)
+            if classes is None:
+                v[first:first + part.shape[0]] = final_common.get_reward(logits, lbl, args)
+            else:
+                v = final_common.reward_table(classes, logits.shape[1], rows.shape[0], dev) if v is None else v
+                final_common.get_reward_classes(logits, classes, args, v, first)
+    if classes is not None:
+        return kernelshap._class_ends(v)
     tail = v[-2:].cpu().numpy()
     return v[:-2].contiguous(), float(tail[0]), float(tail[1])
 
