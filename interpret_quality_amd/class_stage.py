@@ -21,7 +21,7 @@ import json
 import numpy as np
 import torch
 
-from . import classwise
+from . import classwise, kernel_stage
 from . import dist as iqdist
 from . import shapley_stage as stage1
 from . import wide, wide_kernelshap, wide_stage
@@ -127,8 +127,7 @@ def make_args(argv=None):
         parser.error("--route, --coalitions and --draw belong to games of more than %d regions" % classwise.NARROW_REGIONS)
     if args.num_samples < 1:
         parser.error("--num_samples %d: at least one permutation" % args.num_samples)
-    if args.samples is not None and args.samples < 2:
-        parser.error("--samples %d: a count of at least 2" % args.samples)
+    kernel_stage.check_samples(parser, args)
     return args
 
 

@@ -108,16 +108,10 @@ def shapley(model, data, region_id, orders, args, classes=None, snap_counts=None
     rid = hip_ops.region_ids(region_id, dev, r)
     steps = wide._steps(orders_dev, r)
     keep = None if route == "prefix" else lambda j: hip_ops.prefix_keep_masks_wide(steps[j][2])
-    table = []
-
-    def fill(logits, first):
-        if not table:
-            table.append(final_common.reward_table(cls, logits.shape[1], orders.shape[0] * (r + 1), dev))
-        final_common.get_reward_classes(logits, cls, args, table[0], first)
-
+    sink = final_common.RewardSink(None, cls, args, orders.shape[0] * (r + 1), dev)
     with torch.no_grad():
-        wide._rewards(model, data, None, rid, steps, keep, None, r, mode, args, reward=fill)
-    return _reduce(table[0], orders, snap_counts)
+        wide._rewards(model, data, rid, steps, keep, sink, r, mode)
+    return _reduce(sink.v, orders, snap_counts)
 
 
 def ends(model, data, region_id, args, classes=None, coalitions=None):
@@ -130,11 +124,9 @@ def ends(model, data, region_id, args, classes=None, coalitions=None):
     rid = hip_ops.region_ids(region_id, dev, r)
     with torch.no_grad():
         if r <= NARROW_REGIONS:
-            keep = hip_ops.masks_to_tensor([(1 << r) - 1, 0], dev)
-            logits = final_common.masked_logits(model, data, torch.mean(data, dim=1), rid, keep, args, 2)
+            logits = final_common.masked_logits(model, data, torch.mean(data, dim=1), rid, kernelshap.end_rows(r, dev), args, 2)
         else:
-            rows = np.stack([hip_ops.region_words(np.arange(r), r), np.zeros(hip_ops.wide_words(r), dtype=np.uint64)])
-            logits = wide._logits(model, data, rid, hip_ops.wide_masks_to_tensor(rows, dev), r, wide._pick_coalitions(coalitions, data))
+            logits = wide._logits(model, data, rid, wide_kernelshap.end_rows(r, dev), r, wide._pick_coalitions(coalitions, data))
         v = final_common.get_reward_classes(logits, cls, args).cpu().numpy().astype(np.float64)
     return v[:, 0].copy(), v[:, 1].copy(), logits[0].cpu().numpy()
 
@@ -147,38 +139,16 @@ def kernel_shapley(model, data, region_id, args, classes=None, samples=None, pai
     takes it whole: row g is ``kernelshap.shapley`` / ``wide_kernelshap.shapley`` with lbl = classes[g], bit for bit.  ``gram``:
     None = "sampled" up to 64 regions, "analytic" above.  ``samples``: a count, None (default_samples) or "all"."""
     cls = _classes(classes)
-    r = int(args.num_regions)
-    dev = data.device
-    narrow = r <= NARROW_REGIONS
+    narrow = int(args.num_regions) <= NARROW_REGIONS
     ks = kernelshap if narrow else wide_kernelshap
-    n = ks._regions(r)
+    ks.regions(args.num_regions)
     gram = gram or ("sampled" if narrow else "analytic")
-    if narrow:
-        if gram not in kernelshap.GRAMS:
-            raise IqError("gram must be one of %s, got %r" % (kernelshap.GRAMS, gram))
-        if draw != "stream" or coalitions is not None:
-            raise IqError("draw=%r / coalitions=%r belong to games of more than %d regions" % (draw, coalitions, NARROW_REGIONS))
-    else:
-        wide_kernelshap._gram(gram)
-        wide_kernelshap._draw_kind(draw)
-    weights = None
-    if isinstance(samples, str):
-        if samples != "all":
-            raise IqError("samples must be a count, None or 'all', got %r" % (samples,))
-        keep, weights = ks.enumerated(n, dev)
-    else:
-        samples = ks.default_samples(n) if samples is None else samples
-        if narrow:
-            keep, _ = kernelshap.draw(n, samples, paired, dev)
-        elif draw == "counter":
-            keep, _ = wide_kernelshap.draw_counter(n, samples, seed, stream, paired, dev)
-        else:
-            keep, _ = wide_kernelshap.draw(n, samples, paired, dev)
-    if narrow:
-        v, v_full, v_empty = kernelshap.rewards(model, data, None, region_id, args, keep, classes=cls)
-    else:
-        v, v_full, v_empty = wide_kernelshap.rewards(model, data, None, region_id, args, keep, coalitions, classes=cls)
-    return ks.estimate(keep, v, v_empty, v_full, n, weights, gram), v_full, v_empty
+    ks.check_gram(gram)
+    if narrow and (draw != "stream" or coalitions is not None):
+        raise IqError("draw=%r / coalitions=%r belong to games of more than %d regions" % (draw, coalitions, NARROW_REGIONS))
+    how = {} if narrow else {"draw": wide_kernelshap.drawer(draw, seed, stream), "coalitions": coalitions}
+    g = kernelshap.play(ks, model, data, None, region_id, args, samples, paired, gram, (), classes=cls, **how)
+    return g["phi"], g["v_full"], g["v_empty"]
 
 
 def exact(model, data, region_id, args, classes=None, players=None, base=0):

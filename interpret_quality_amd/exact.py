@@ -49,19 +49,14 @@ def value_table(model, data, lbl, region_id, args, players=None, base=0, chunk=1
     rid = hip_ops.region_ids(region_id, dev, r).reshape(1, -1)
     clouds = data.contiguous()
     centers = torch.mean(data, dim=1).reshape(1, 3).contiguous()
-    v = None if classes is not None else torch.empty((1 << n,), dtype=torch.float32, device=dev)
+    sink = final_common.RewardSink(lbl, classes, args, 1 << n, dev)
     with torch.no_grad():
         for first in range(0, 1 << n, chunk):
             count = min(chunk, (1 << n) - first)
             keep = hip_ops.enum_keep_masks(first, count, n, dev, pl, base)
             work.add(count)
-            logits = model.coalition_logits(clouds, centers, rid, keep, None, num_regions=r, validate=False)
-            if classes is None:
-                v[first:first + count] = final_common.get_reward(logits, lbl, args)
-            else:
-                v = final_common.reward_table(classes, logits.shape[1], 1 << n, dev) if v is None else v
-                final_common.get_reward_classes(logits, classes, args, v, first)
-    return v
+            sink.put(model.coalition_logits(clouds, centers, rid, keep, None, num_regions=r, validate=False), first)
+    return sink.v
 
 
 def _table(model, data, lbl, region_id, args, players, base, chunk, v):

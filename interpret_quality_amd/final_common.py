@@ -47,9 +47,45 @@ def get_reward_classes(logits, classes, args, out=None, first=0):
     return hip_ops.reward_classes(logits.contiguous(), class_labels(classes, logits.shape[1]), modified, out, first)
 
 
-def reward_table(classes, num_classes, columns, device):
-    """The empty (G,columns) float32 table that get_reward_classes fills chunk by chunk."""
-    return torch.empty((len(class_labels(classes, num_classes)), int(columns)), dtype=torch.float32, device=device)
+class RewardSink:
+    """Where the rewards of a game's ``columns`` coalitions go, one chunk of logits at a time.  One label ``lbl`` (``classes``
+    None): ``v`` is a (columns,) float32 vector, allocated here or the caller's ``out`` view, filled by ``get_reward``.  The
+    labels ``classes`` (``class_labels``; ``lbl`` is then not read): ``v`` is the (G,columns) table that ``get_reward_classes``
+    fills through its out/first form, row g the bits of the single-label sink with lbl = classes[g]; it exists
+    from the first chunk on, since under ALL_CLASSES only the logits say what G is."""
+
+    def __init__(self, lbl, classes, args, columns, device, out=None):
+        self.game, self.columns, self.device = (lbl, classes, args), int(columns), device
+        self.v = out if out is not None or classes is not None else torch.empty((self.columns,), dtype=torch.float32, device=device)
+
+    def put(self, logits, first):
+        """Score ``logits`` (B,C), the logits of coalitions first .. first + B - 1."""
+        lbl, classes, args = self.game
+        if classes is None:
+            self.v[first:first + logits.shape[0]] = get_reward(logits, lbl, args)
+            return
+        if self.v is None:
+            self.v = torch.empty((len(class_labels(classes, logits.shape[1])), self.columns), dtype=torch.float32, device=self.device)
+        get_reward_classes(logits, classes, args, self.v, first)
+
+
+def rewards_with_ends(logits_of, rows, ends, lbl, classes, args, chunk=1 << 16):
+    """Rewards of the coalition rows ``rows`` ((M,) narrow or (M,W) wide) with the two rows ``ends`` - the full and the empty
+    coalition - appended, so that all come from the same calls: ``logits_of(part)`` gives the logits of at most ``chunk`` rows
+    (and counts its work), a RewardSink scores them -> (v (M,) float32 device tensor, v_full, v_empty floats), or with
+    ``classes`` (v (G,M), v_full (G,), v_empty (G,) float64 ndarrays).  Nothing depends on ``chunk``."""
+    rows = torch.cat([rows, ends])
+    chunk = max(1, int(chunk))
+    sink = RewardSink(lbl, classes, args, rows.shape[0], rows.device)
+    with torch.no_grad():
+        for first in range(0, rows.shape[0], chunk):
+            sink.put(logits_of(rows[first:first + chunk].contiguous()), first)
+    v = sink.v
+    if v.dim() == 2:
+        tail = v[:, -2:].cpu().numpy().astype(np.float64)
+        return v[:, :-2].contiguous(), tail[:, 0].copy(), tail[:, 1].copy()
+    tail = v[-2:].cpu().numpy()
+    return v[:-2].contiguous(), float(tail[0]), float(tail[1])
 
 
 def cal_reward(model, data, lbl, args):

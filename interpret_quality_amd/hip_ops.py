@@ -364,24 +364,30 @@ def kshap_regions(n):
     return n
 
 
+def _kshap_keep_masks(entry, regions, words, orders, sizes, paired):
+    """The body of kshap_keep_masks and kshap_keep_masks_wide: ``entry`` names the library call, ``regions`` checks the region
+    count, ``words(n)`` is the shape of one keep row."""
+    lib = _lib.load()
+    _dev(orders, torch.int32, "orders")
+    s, n = _shape(orders, "orders", None, None)
+    n = regions(n)
+    _shape(sizes, "sizes", s)
+    keep = torch.empty((2 * s if paired else s,) + words(n), dtype=torch.int64, device=orders.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=orders.device)
+    _lib.check(getattr(lib, entry)(_p(orders), _dev(sizes, torch.int32, "sizes"), _p(keep), s, n, int(bool(paired)), _p(status),
+                                   _stream()), entry)
+    verdict = int(status.item()) if s else 0
+    if verdict:
+        raise _lib.IqError(entry[3:] + ": " + ("a size lies outside 1 .. %d" % (n - 1) if verdict == 1
+                                               else "an order entry lies outside [0, %d)" % n))
+    return keep
+
+
 def kshap_keep_masks(orders, sizes, paired=True):
     """orders (S,n) i32 permutations, sizes (S,) i32 in 1 .. n-1 -> int64-typed keep masks (iq_kshap_keep_masks): the first
     sizes[m] entries of permutation m; ``paired``: (2S,) with every set followed by its complement within the n bits, else (S,).
     A size outside 1 .. n-1 or an order entry outside [0, n) raises IqError (one 4-byte read back)."""
-    lib = _lib.load()
-    _dev(orders, torch.int32, "orders")
-    s, n = _shape(orders, "orders", None, None)
-    n = kshap_regions(n)
-    _shape(sizes, "sizes", s)
-    keep = torch.empty((2 * s if paired else s,), dtype=torch.int64, device=orders.device)
-    status = torch.zeros((1,), dtype=torch.int32, device=orders.device)
-    _lib.check(lib.iq_kshap_keep_masks(_p(orders), _dev(sizes, torch.int32, "sizes"), _p(keep), s, n, int(bool(paired)), _p(status),
-                                       _stream()), "iq_kshap_keep_masks")
-    verdict = int(status.item()) if s else 0
-    if verdict:
-        raise _lib.IqError("kshap_keep_masks: " + ("a size lies outside 1 .. %d" % (n - 1) if verdict == 1
-                                                   else "an order entry lies outside [0, %d)" % n))
-    return keep
+    return _kshap_keep_masks("iq_kshap_keep_masks", kshap_regions, lambda n: (), orders, sizes, paired)
 
 
 def kshap_accum(keep, v, v0, n, weights=None):
@@ -665,20 +671,7 @@ def kshap_keep_masks_wide(orders, sizes, paired=True):
     """``kshap_keep_masks`` for wide rows: orders (S,R) i32 permutations, sizes (S,) i32 in 1 .. R-1 -> (2S or S, W) int64-typed
     keep rows (iq_kshap_keep_masks_wide), every set followed by its complement within the R bits when ``paired``.  A size outside
     1 .. R-1 or an order entry outside [0, R) raises IqError (one 4-byte read back)."""
-    lib = _lib.load()
-    _dev(orders, torch.int32, "orders")
-    s, r = _shape(orders, "orders", None, None)
-    r = kshap_regions_wide(r)
-    _shape(sizes, "sizes", s)
-    keep = torch.empty((2 * s if paired else s, wide_words(r)), dtype=torch.int64, device=orders.device)
-    status = torch.zeros((1,), dtype=torch.int32, device=orders.device)
-    _lib.check(lib.iq_kshap_keep_masks_wide(_p(orders), _dev(sizes, torch.int32, "sizes"), _p(keep), s, r, int(bool(paired)),
-                                            _p(status), _stream()), "iq_kshap_keep_masks_wide")
-    verdict = int(status.item()) if s else 0
-    if verdict:
-        raise _lib.IqError("kshap_keep_masks_wide: " + ("a size lies outside 1 .. %d" % (r - 1) if verdict == 1
-                                                        else "an order entry lies outside [0, %d)" % r))
-    return keep
+    return _kshap_keep_masks("iq_kshap_keep_masks_wide", kshap_regions_wide, lambda r: (wide_words(r),), orders, sizes, paired)
 
 
 def kshap_moment_wide(keep, v, v0, num_regions, weights=None):

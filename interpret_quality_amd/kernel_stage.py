@@ -29,6 +29,40 @@ from . import shapley_stage as stage1
 from .final_util import NUM_REGIONS, get_folder_name_list, load_model, mkdir
 
 
+FILES = ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value")
+
+
+def artefacts(g):
+    """A game of kernelshap.game or wide_kernelshap.game -> dict of one cloud's artefacts: the FILES as ndarrays, v_full, v_empty."""
+    running = g["running"]
+    return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
+            "running_counts": np.array(sorted(running), dtype=np.int64),
+            "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), len(g["phi"])),
+            "v_full": g["v_full"], "v_empty": g["v_empty"]}
+
+
+def save(folder, out):
+    for key in FILES:
+        np.save(folder + "%s.npy" % key, out[key])
+
+
+def add_sample_flags(parser, enumerated=False):
+    """--samples and --unpaired; ``enumerated``: the stage also takes ``--samples all``."""
+    parser.add_argument("--samples", type=str if enumerated else int, default=None,
+                        help="coalition rows (model evaluations) per cloud; default 1000 (num_regions + 1)"
+                             + ("; 'all': every proper coalition" if enumerated else ""))
+    parser.add_argument("--unpaired", action="store_true", help="do not follow every sampled coalition with its complement")
+
+
+def check_samples(parser, args, enumerated=False):
+    """--samples as a count of at least 2 (an int afterwards), None, or - ``enumerated`` - 'all'; a parser error otherwise."""
+    if args.samples is None or (enumerated and args.samples == "all"):
+        return
+    if not str(args.samples).isdigit() or int(args.samples) < 2:
+        parser.error("--samples %s: a count of at least 2%s" % (args.samples, ", or 'all'" if enumerated else ""))
+    args.samples = int(args.samples)
+
+
 def _errors(est, phi):
     err = np.asarray(est) - phi
     return {"max_abs_error": float(np.abs(err).max()), "rms_error": float(np.sqrt((err ** 2).mean()))}
@@ -63,15 +97,10 @@ def compare_exact(model, data, lbl, region_id, keep, args):
 
 def kernel_one_cloud(model, data, lbl, region_id, args):
     """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact)."""
-    n = args.num_regions
     g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram)
-    keep, running = g["keep"], g["running"]
-    out = {"coalitions": keep.cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
-           "running_counts": np.array(sorted(running), dtype=np.int64),
-           "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), n),
-           "v_full": g["v_full"], "v_empty": g["v_empty"]}
+    out = artefacts(g)
     if args.compare_exact:
-        out["exact"], out["sampling_error"] = compare_exact(model, data, lbl, region_id, keep, args)
+        out["exact"], out["sampling_error"] = compare_exact(model, data, lbl, region_id, g["keep"], args)
     return out
 
 
@@ -88,8 +117,7 @@ def run(args):
             mkdir(result_path + "kernelshap/")
             region_id = stage1.cal_region_id(data, fps_index, result_path, save=False)
             out = kernel_one_cloud(model, data, lbl, region_id, args)
-            for key in ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value"):
-                np.save(result_path + "kernelshap/%s.npy" % key, out[key])
+            save(result_path + "kernelshap/", out)
             line = "pointcloud:%s, index:%d, rows:%d, sum(phi)=%.6f, v_full - v_empty=%.6f" % (
                 name, i, out["coalitions"].size, out["region_shapley_value"].sum(), out["v_full"] - out["v_empty"])
             if args.compare_exact:
@@ -106,18 +134,13 @@ def run(args):
 
 def make_args(argv=None):
     parser = stage1.build_parser()
-    parser.add_argument("--samples", type=str, default=None,
-                        help="coalition rows (model evaluations) per cloud; default 1000 (num_regions + 1); 'all': every proper coalition")
-    parser.add_argument("--unpaired", action="store_true", help="do not follow every sampled coalition with its complement")
+    add_sample_flags(parser, enumerated=True)
     parser.add_argument("--gram", type=str, default="sampled", choices=list(kernelshap.GRAMS))
     parser.add_argument("--compare_exact", action="store_true",
                         help="also enumerate the game (at most %d regions) and write sampling_error.json" % exact.MAX_PLAYERS)
     args = stage1.parse_game_args(parser, argv, NUM_REGIONS, 2, kernelshap.MAX_REGIONS,
                                   "the regression estimator takes 2 to 64 regions (final_wide_kernel_shapley.py: 65 to 1024)")
-    if args.samples is not None and args.samples != "all":
-        if not args.samples.isdigit() or int(args.samples) < 2:
-            parser.error("--samples %s: a count of at least 2, or 'all'" % args.samples)
-        args.samples = int(args.samples)
+    check_samples(parser, args, enumerated=True)
     if (args.compare_exact or args.samples == "all") and args.num_regions > exact.MAX_PLAYERS:
         parser.error("--num_regions %d: --compare_exact and --samples all enumerate 2^num_regions coalitions; at most %d regions"
                      % (args.num_regions, exact.MAX_PLAYERS))

@@ -17,6 +17,7 @@ The moments and the solve run in libiq_hip.so (csrc/iq_kshap.hip): float64, fixe
 Games of 65 .. 1024 regions: wide_kernelshap.py (the analytic variant in closed form, on wide keep rows).
 """
 import math
+import sys
 
 import numpy as np
 import torch
@@ -28,7 +29,26 @@ MAX_REGIONS = hip_ops.MAX_KSHAP_REGIONS
 GRAMS = ("sampled", "analytic")
 
 
-_regions = hip_ops.kshap_regions
+regions = hip_ops.kshap_regions
+_NARROW = sys.modules[__name__]      # what ``ks`` means in ``running_estimates`` and ``play`` unless wide_kernelshap.py is named
+
+
+def check_gram(gram):
+    if gram not in GRAMS:
+        raise IqError("gram must be one of %s, got %r" % (GRAMS, gram))
+
+
+def draws(samples, paired=True):
+    """The coalitions to draw for ``samples`` rows: half of them, rounded down, when every one is followed by its complement."""
+    s = int(samples) // 2 if paired else int(samples)
+    if s < 1:
+        raise IqError("samples=%d leaves no coalition to draw" % int(samples))
+    return s
+
+
+def end_rows(n, device):
+    """The full and the empty coalition of n regions: the two rows ``rewards`` appends -> (2,) int64-typed."""
+    return hip_ops.masks_to_tensor([(1 << n) - 1, 0], device)
 
 
 def _size_cdf(n):
@@ -48,12 +68,12 @@ def _draw_sizes(n, count):
 
 def size_cdf(n):
     """(n-1,) float64: entry s-1 = P(size <= s) under p(s) = (1 / (s (n - s))) / Z; the last entry is exactly 1.0."""
-    return _size_cdf(_regions(n))
+    return _size_cdf(regions(n))
 
 
 def analytic_gram(n):
     """(n,n) float64: E[z z^T] under the size law - 1/2 on the diagonal, 1/2 - 1 / (2 H_{n-1}) off it."""
-    n = _regions(n)
+    n = regions(n)
     h = math.fsum(1.0 / k for k in range(1, n))
     a = np.full((n, n), 0.5 - 1.0 / (2.0 * h))
     np.fill_diagonal(a, 0.5)
@@ -62,17 +82,15 @@ def analytic_gram(n):
 
 def draw_sizes(n, count):
     """``count`` coalition sizes by the contract: one random_sample call on NumPy's global generator -> (count,) int32."""
-    return _draw_sizes(_regions(n), count)
+    return _draw_sizes(regions(n), count)
 
 
 def draw(n, samples, paired=True, device="cuda"):
     """One cloud's draw of ``samples`` rows (paired: rounded down to even, half of them drawn) -> (keep (M,) int64-typed device
     tensor, sizes (S,) int32 ndarray).  S doubles on the host, then S permutations on the device; NumPy's global generator is
     left where the reference's stream stands after both."""
-    n = _regions(n)
-    s = int(samples) // 2 if paired else int(samples)
-    if s < 1:
-        raise IqError("samples=%d leaves no coalition to draw" % int(samples))
+    n = regions(n)
+    s = draws(samples, paired)
     sizes = draw_sizes(n, s)
     state = hip_ops.mt_state_to_device(device)
     orders = hip_ops.sample_permutations(state, s, n)
@@ -91,7 +109,7 @@ def enumeration_weights(n):
 def enumerated(n, device):
     """-> (keep (2^n - 2,) int64-typed, weights (2^n - 2,) float64), both on the device: every proper coalition of regions 0 .. n-1
     with the weight under which the regression returns the exact Shapley vector."""
-    n = _regions(n)
+    n = regions(n)
     if n > hip_ops.MAX_EXACT_PLAYERS:
         raise IqError("an enumerated game has 2^n rows: n=%d is above the limit of %d" % (n, hip_ops.MAX_EXACT_PLAYERS))
     count = (1 << n) - 2
@@ -103,27 +121,30 @@ def enumerated(n, device):
     return keep, torch.from_numpy(enumeration_weights(n)[size]).to(keep.device)
 
 
-def _f64(x, g, dev, what):
-    t = torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64).reshape(-1))
-    if t.numel() != g:
-        raise IqError("%s holds %d values for %d games" % (what, t.numel(), g))
-    return t.to(dev)
+def games(keep, v, v_empty, v_full):
+    """What both ``estimate``s make of their rewards -> (v as a contiguous (G,M) tensor, v_empty (G,), v_full (G,) float64 on the
+    device of ``keep``)."""
+    if not isinstance(v, torch.Tensor) or v.dim() not in (1, 2):
+        raise IqError("v must be a (M,) or (G,M) tensor")
+    v2 = v.reshape(1, -1) if v.dim() == 1 else v
+    ends = []
+    for x, what in ((v_empty, "v_empty"), (v_full, "v_full")):
+        t = torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64).reshape(-1))
+        if t.numel() != v2.shape[0]:
+            raise IqError("%s holds %d values for %d games" % (what, t.numel(), v2.shape[0]))
+        ends.append(t.to(keep.device))
+    return v2.contiguous(), ends[0], ends[1]
 
 
 def estimate(keep, v, v_empty, v_full, n, weights=None, gram="sampled"):
     """phi of the rows ``keep`` (M,) with rewards ``v`` ((M,) float32 device tensor, or (G,M) for G games on the same rows;
     v_empty, v_full: scalars or (G,)) -> float64 ndarray (n,) or (G,n).  IqError (hip_ops.KshapSingular) if the rows leave the
     sampled A singular."""
-    n = _regions(n)
-    if gram not in GRAMS:
-        raise IqError("gram must be one of %s, got %r" % (GRAMS, gram))
-    if not isinstance(v, torch.Tensor) or v.dim() not in (1, 2):
-        raise IqError("v must be a (M,) or (G,M) tensor")
-    v2 = v.reshape(1, -1) if v.dim() == 1 else v
-    g, dev = v2.shape[0], keep.device
-    v0, v1 = _f64(v_empty, g, dev, "v_empty"), _f64(v_full, g, dev, "v_full")
-    a, b, wsum = hip_ops.kshap_accum(keep, v2.contiguous(), v0, n, weights)
-    a = a / wsum if gram == "sampled" else torch.from_numpy(analytic_gram(n)).to(dev)
+    n = regions(n)
+    check_gram(gram)
+    v2, v0, v1 = games(keep, v, v_empty, v_full)
+    a, b, wsum = hip_ops.kshap_accum(keep, v2, v0, n, weights)
+    a = a / wsum if gram == "sampled" else torch.from_numpy(analytic_gram(n)).to(keep.device)
     phi = hip_ops.kshap_solve(a.contiguous(), (b / wsum).contiguous(), v1 - v0).cpu().numpy()
     return phi[0] if v.dim() == 1 else phi
 
@@ -143,70 +164,66 @@ def running_counts(n, rows, paired=True, counts=None):
     return [c for c in counts if 1 <= c <= rows]
 
 
-def _class_ends(v):
-    """The (G,M+2) reward table of ``rewards`` with ``classes`` -> (v (G,M), v_full (G,), v_empty (G,) float64 ndarrays)."""
-    ends = v[:, -2:].cpu().numpy().astype(np.float64)
-    return v[:, :-2].contiguous(), ends[:, 0].copy(), ends[:, 1].copy()
-
-
 def rewards(model, data, lbl, region_id, args, keep, chunk=1 << 16, classes=None):
     """Rewards of the coalitions ``keep`` of one cloud ``data`` (1,N,3), obtained as exact.value_table obtains them, with the
-    full and the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty).
-    ``classes`` (a sequence of labels, or "all"; ``lbl`` is then not read): the rewards of every label from the same logits ->
-    (v (G,M), v_full (G,), v_empty (G,)), row g the bits of the call with lbl = classes[g]."""
+    full and the empty coalition as two extra rows of the same calls (final_common.rewards_with_ends) -> (v (M,) float32 device
+    tensor, v_full, v_empty).  ``classes`` (a sequence of labels, or "all"; ``lbl`` is then not read): the rewards of every
+    label from the same logits -> (v (G,M), v_full (G,), v_empty (G,)), row g the bits of the call with lbl = classes[g]."""
     if not hasattr(model, "coalition_logits"):
         raise IqError("%s has no coalition entry point" % type(model).__name__)
-    dev = data.device
-    r = _regions(args.num_regions)
-    rid = hip_ops.region_ids(region_id, dev, r).reshape(1, -1)
+    r = regions(args.num_regions)
+    rid = hip_ops.region_ids(region_id, data.device, r).reshape(1, -1)
     clouds = data.contiguous()
     centers = torch.mean(data, dim=1).reshape(1, 3).contiguous()
-    rows = torch.cat([keep, hip_ops.masks_to_tensor([(1 << r) - 1, 0], dev)])
-    v = None if classes is not None else torch.empty((rows.numel(),), dtype=torch.float32, device=dev)
-    with torch.no_grad():
-        for first in range(0, rows.numel(), max(1, int(chunk))):
-            part = rows[first:first + chunk].contiguous()
-            work.add(part.numel())
-            logits = model.coalition_logits(clouds, centers, rid, part, None, num_regions=r, validate=False)
-            if classes is None:
-                v[first:first + part.numel()] = final_common.get_reward(logits, lbl, args)
-            else:
-                v = final_common.reward_table(classes, logits.shape[1], rows.numel(), dev) if v is None else v
-                final_common.get_reward_classes(logits, classes, args, v, first)
-    if classes is not None:
-        return _class_ends(v)
-    ends = v[-2:].cpu().numpy()
-    return v[:-2].contiguous(), float(ends[0]), float(ends[1])
+
+    def logits_of(part):
+        work.add(part.numel())
+        return model.coalition_logits(clouds, centers, rid, part, None, num_regions=r, validate=False)
+    return final_common.rewards_with_ends(logits_of, keep, end_rows(r, data.device), lbl, classes, args, chunk)
 
 
-def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled"):
-    """{count: phi of the first ``count`` rows}; a count whose rows leave A singular is left out."""
+def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled", ks=_NARROW):
+    """{count: ``ks.estimate`` of the first ``count`` rows}; a count whose rows leave the sampled A singular is left out (the
+    wide estimator has no such case: every count is there)."""
     out = {}
     for c in counts:
         try:
-            out[c] = estimate(keep[:c].contiguous(), v[:c].contiguous(), v_empty, v_full, n, None, gram)
+            out[c] = ks.estimate(keep[:c].contiguous(), v[:c].contiguous(), v_empty, v_full, n, None, gram)
         except hip_ops.KshapSingular:
             pass
     return out
 
 
-def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):
-    """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
-    sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows}."""
-    n = _regions(args.num_regions)
+def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, draw=None, classes=None,
+         **how):
+    """The body of ``game``, wide_kernelshap.game and classwise.kernel_shapley, which check their own arguments first.  ``ks``:
+    the estimator's module, this one or wide_kernelshap.  Refused before anything is drawn or run: the region count and
+    ``gram``.  Then the rows - ``samples`` a count, None (``ks.default_samples``) or "all" (``ks.enumerated``); ``draw``:
+    (n, samples, paired, device) -> (keep, sizes), default ``ks.draw`` - their rewards (``ks.rewards`` with ``classes`` and
+    ``how``), ``ks.estimate`` and the running estimates at ``ks.running_counts`` (``counts=()``: none) -> the dict ``game``
+    describes."""
+    n = ks.regions(args.num_regions)
+    ks.check_gram(gram)
     weights = None
     if isinstance(samples, str):
         if samples != "all":
             raise IqError("samples must be a count, None or 'all', got %r" % (samples,))
-        keep, weights = enumerated(n, data.device)
+        keep, weights = ks.enumerated(n, data.device)
     else:
-        keep, _ = draw(n, default_samples(n) if samples is None else samples, paired, data.device)
-    v, v_full, v_empty = rewards(model, data, lbl, region_id, args, keep)
-    phi = estimate(keep, v, v_empty, v_full, n, weights, gram)
+        keep, _ = (draw or ks.draw)(n, ks.default_samples(n) if samples is None else samples, paired, data.device)
+    v, v_full, v_empty = ks.rewards(model, data, lbl, region_id, args, keep, classes=classes, **how)
+    phi = ks.estimate(keep, v, v_empty, v_full, n, weights, gram)
     running = {}
     if weights is None:
-        running = running_estimates(keep, v, v_empty, v_full, n, running_counts(n, keep.numel(), paired, counts), gram)
+        running = running_estimates(keep, v, v_empty, v_full, n, ks.running_counts(n, keep.shape[0], paired, counts), gram, ks)
     return {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
+
+
+def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):
+    """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
+    sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows}.  A
+    ``gram`` outside GRAMS is refused before anything is drawn or run."""
+    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):

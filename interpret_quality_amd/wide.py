@@ -142,21 +142,16 @@ def _steps(orders_dev, r, perms_per_step=None):
     return [(lo, min(lo + step, s), orders_dev[lo:lo + step].contiguous()) for lo in range(0, s, step)]
 
 
-def _rewards(model, data, lbl, rid, steps, keep, v, r, mode, args, reward=None):
-    """The rewards of the prefix coalitions of one cloud ``data`` (1,N,3) into ``v`` (S*(R+1),), one step of ``_steps`` at a
-    time.  ``keep``: None on the prefix route - a step is evaluated straight from its permutations - else step index -> the
-    step's keep rows, evaluated as arbitrary coalitions.  ``reward``: None - the reward of label ``lbl`` into ``v`` - or
-    ``reward(logits, first)``, which stores what it makes of a step's logits itself (coalitions first .. first + rows - 1:
-    classwise.shapley fills one table row per label); ``lbl`` and ``v`` are then not read."""
-    for j, (lo, hi, step_orders) in enumerate(steps):
+def _rewards(model, data, rid, steps, keep, sink, r, mode):
+    """The rewards of the S*(R+1) prefix coalitions of one cloud ``data`` (1,N,3) into ``sink`` (a final_common.RewardSink), one
+    step of ``_steps`` at a time.  ``keep``: None on the prefix route - a step is evaluated straight from its permutations - else
+    step index -> the step's keep rows, evaluated as arbitrary coalitions."""
+    for j, (lo, _, step_orders) in enumerate(steps):
         if keep is None:
             logits = _prefix_logits(model, data, rid, step_orders, r, mode)
         else:
             logits = _logits(model, data, rid, keep(j), r, mode)
-        if reward is None:
-            v[lo * (r + 1):hi * (r + 1)] = final_common.get_reward(logits, lbl, args)
-        else:
-            reward(logits, lo * (r + 1))
+        sink.put(logits, lo * (r + 1))
 
 
 def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_per_step=None, route=None, coalitions=None):
@@ -175,10 +170,10 @@ def shapley(model, data, lbl, region_id, orders, args, snap_counts=None, perms_p
     steps = _steps(orders_dev, r, perms_per_step)
     # the keep rows of one step at a time: at R = 1024 and 1000 permutations all of them would be about 130 MB
     keep = None if route == "prefix" else lambda j: hip_ops.prefix_keep_masks_wide(steps[j][2])
-    v = torch.empty((orders.shape[0] * (r + 1),), dtype=torch.float32, device=dev)
+    sink = final_common.RewardSink(lbl, None, args, orders.shape[0] * (r + 1), dev)
     with torch.no_grad():
-        _rewards(model, data, lbl, rid, steps, keep, v, r, mode, args)
-    return hip_ops.shapley_snapshots(v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
+        _rewards(model, data, rid, steps, keep, sink, r, mode)
+    return hip_ops.shapley_snapshots(sink.v, orders_dev, snap_counts, hip_ops.shapley_accum_wide)
 
 
 def shapley_over_poses(model, poses, lbl, region_id, orders, args, route=None, coalitions=None):
@@ -211,7 +206,8 @@ def shapley_over_poses(model, poses, lbl, region_id, orders, args, route=None, c
         keep = None if rows is None else rows.__getitem__
         v = torch.empty((p * per,), dtype=torch.float32, device=dev)
         for k in range(p):
-            _rewards(model, poses[k:k + 1], lbl, rid, steps, keep, v[k * per:(k + 1) * per], r, mode, args)
+            sink = final_common.RewardSink(lbl, None, args, per, dev, out=v[k * per:(k + 1) * per])      # a view: no copy
+            _rewards(model, poses[k:k + 1], rid, steps, keep, sink, r, mode)
         for k in range(p):
             total, _, _ = hip_ops.shapley_accum_wide(v[k * per:(k + 1) * per], orders_dev)
             # a true float64 division, as ``total / S`` on the host: a tensor divided by a Python number is multiplied by its

@@ -31,23 +31,17 @@ import torch
 
 from . import dist as iqdist
 from . import shapley_stage as stage1
-from . import wide_kernelshap, wide_stage
+from . import kernel_stage, wide_kernelshap, wide_stage
 from .final_util import get_folder_name_list, load_model, mkdir
 
-FILES = ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value")
+FILES = kernel_stage.FILES
 
 
 def kernel_one_cloud(model, data, lbl, region_id, args, cloud=0):
-    """-> dict of one cloud's artefacts (ndarrays) plus v_full and v_empty.  ``cloud``: its index, the key's second word under
+    """-> dict of one cloud's artefacts (kernel_stage.artefacts).  ``cloud``: its index, the key's second word under
     ``--draw counter``."""
-    r = args.num_regions
-    g = wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, coalitions=args.coalitions,
-                             draw=args.draw, seed=args.seed, stream=cloud)
-    running = g["running"]
-    return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
-            "running_counts": np.array(sorted(running), dtype=np.int64),
-            "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), r),
-            "v_full": g["v_full"], "v_empty": g["v_empty"]}
+    return kernel_stage.artefacts(wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired,
+                                                       coalitions=args.coalitions, draw=args.draw, seed=args.seed, stream=cloud))
 
 
 def stage1_estimate(result_path, i):
@@ -78,8 +72,7 @@ def run(args):
             mkdir(result_path + "kernelshap/")
             region_id = wide_stage.cal_region_id(data, fps_index, result_path, save=False)
             out = kernel_one_cloud(model, data, lbl, region_id, args, i)
-            for key in FILES:
-                np.save(result_path + "kernelshap/%s.npy" % key, out[key])
+            kernel_stage.save(result_path + "kernelshap/", out)
             with open(result_path + "kernelshap/draw.json", "w") as f:
                 json.dump({"draw": args.draw, "seed": int(args.seed), "stream": i if args.draw == "counter" else None}, f)
             phi = out["region_shapley_value"]
@@ -96,15 +89,12 @@ def run(args):
 def make_args(argv=None):
     parser = stage1.build_parser()
     wide_stage.add_wide_flags(parser, route=False)
-    parser.add_argument("--samples", type=int, default=None,
-                        help="coalition rows (model evaluations) per cloud; default 1000 (num_regions + 1)")
-    parser.add_argument("--unpaired", action="store_true", help="do not follow every sampled coalition with its complement")
+    kernel_stage.add_sample_flags(parser)
     parser.add_argument("--draw", choices=wide_kernelshap.DRAWS, default="stream",
                         help="how the rows are drawn: from NumPy's MT19937 stream (default), or counter-based (Philox keyed by "
                              "--seed and the cloud's index): any cloud alone, no skip draws")
     args = wide_stage.parse_wide_args(parser, argv, "final_kernel_shapley.py", samples=False)
-    if args.samples is not None and args.samples < 2:
-        parser.error("--samples %d: a count of at least 2" % args.samples)
+    kernel_stage.check_samples(parser, args)
     return args
 
 

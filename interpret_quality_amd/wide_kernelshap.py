@@ -20,6 +20,8 @@ estimator"):
 The A of SAMPLED rows above 64 regions is not built: ``gram="sampled"`` is an IqError here (``SAMPLED_REFUSAL`` says why).
 The moment and phi run in libiq_hip.so (csrc/iq_kshap_wide.hip): float64, ``kshap_accum``'s order, bitwise repeatable.
 """
+import sys
+
 import numpy as np
 import torch
 
@@ -34,26 +36,32 @@ SAMPLED_REFUSAL = ("the wide estimator has gram='analytic' only: the sampled Gra
                    "float64 factorisation over several workgroups and more rows than regions before it is regular, and on the one "
                    "game measured it was behind the analytic variant at every budget (kernelshap.estimate has it up to 64 regions)")
 
-_regions = hip_ops.kshap_regions_wide
+regions = hip_ops.kshap_regions_wide
 default_samples = kernelshap.default_samples      # 1000 (R + 1), even: no region count enters but through the argument
 running_counts = kernelshap.running_counts        # c (R + 1) for c in stage 1's sample counts
 
 
-def _gram(gram):
+def check_gram(gram):
     if gram == "sampled":
         raise IqError(SAMPLED_REFUSAL)
     if gram not in GRAMS:
         raise IqError("gram must be one of %s, got %r" % (GRAMS, gram))
 
 
+def end_rows(r, device):
+    """The full and the empty coalition of R regions: the two rows ``rewards`` appends -> (2,W) int64-typed."""
+    rows = np.stack([hip_ops.region_words(np.arange(r), r), np.zeros(hip_ops.wide_words(r), dtype=np.uint64)])
+    return hip_ops.wide_masks_to_tensor(rows, device)
+
+
 def size_cdf(r):
     """(R-1,) float64: entry s-1 = P(size <= s) under p(s) = (1 / (s (R - s))) / Z; the last entry is exactly 1.0."""
-    return kernelshap._size_cdf(_regions(r))
+    return kernelshap._size_cdf(regions(r))
 
 
 def draw_sizes(r, count):
     """``count`` coalition sizes by the contract: one random_sample call on NumPy's global generator -> (count,) int32."""
-    return kernelshap._draw_sizes(_regions(r), count)
+    return kernelshap._draw_sizes(regions(r), count)
 
 
 def draw(r, samples, paired=True, device="cuda", chunk=DRAW_CHUNK, skip=False):
@@ -62,10 +70,8 @@ def draw(r, samples, paired=True, device="cuda", chunk=DRAW_CHUNK, skip=False):
     chunk turned into keep rows before the next is drawn; NumPy's global generator is left where a host-only draw would leave it.
     Rows and end state do not depend on ``chunk``.  ``skip``: the same draws, nothing written (keep is None): the draw of a cloud
     that is not selected."""
-    r = _regions(r)
-    s = int(samples) // 2 if paired else int(samples)
-    if s < 1:
-        raise IqError("samples=%d leaves no coalition to draw" % int(samples))
+    r = regions(r)
+    s = kernelshap.draws(samples, paired)
     chunk = max(1, int(chunk))
     sizes = draw_sizes(r, s)
     state = hip_ops.mt_state_to_device(device)
@@ -86,10 +92,14 @@ def draw(r, samples, paired=True, device="cuda", chunk=DRAW_CHUNK, skip=False):
 _draw_stream = draw      # ``game`` and ``shapley`` have an argument of that name
 
 
-def _draw_kind(kind):
+def drawer(kind, seed=1, stream=0):
+    """The ``draw`` argument of ``game`` (``kind`` in DRAWS, else IqError) -> the (r, samples, paired, device) -> (keep, sizes) that
+    draws a cloud's rows: ``draw``, or ``draw_counter`` keyed by (``seed``, ``stream``)."""
     if kind not in DRAWS:
         raise IqError("draw must be one of %s, got %r" % (DRAWS, kind))
-    return kind
+    if kind == "stream":
+        return _draw_stream
+    return lambda r, samples, paired, device: draw_counter(r, samples, seed, stream, paired, device)
 
 
 def draw_counter(r, samples, seed, stream=0, paired=True, device="cuda", first=0):
@@ -97,10 +107,8 @@ def draw_counter(r, samples, seed, stream=0, paired=True, device="cuda", first=0
     int64-typed device tensor, sizes (S,) int32 ndarray): samples ``first .. first + S - 1`` of the cloud ``stream`` under ``seed``
     (include/iq.h, "The COUNTER-BASED draw"), each a pure function of (seed, stream, index, r).  One launch, no
     chunks, no generator state: NumPy's global generator is not touched and a cloud that is not selected draws nothing."""
-    r = _regions(r)
-    s = int(samples) // 2 if paired else int(samples)
-    if s < 1:
-        raise IqError("samples=%d leaves no coalition to draw" % int(samples))
+    r = regions(r)
+    s = kernelshap.draws(samples, paired)
     keep, sizes = hip_ops.kshap_draw_counter(seed, stream, first, s, r, size_cdf(r), paired, device)
     return keep, sizes.cpu().numpy()
 
@@ -108,7 +116,7 @@ def draw_counter(r, samples, seed, stream=0, paired=True, device="cuda", first=0
 def enumerated(r, device):
     """``kernelshap.enumerated`` with the rows widened to (2^R - 2, 1): every proper coalition of at most exact.MAX_PLAYERS regions
     and the weight under which the regression returns the exact Shapley vector."""
-    r = _regions(r)
+    r = regions(r)
     if r > hip_ops.MAX_EXACT_PLAYERS:
         raise IqError("an enumerated game has 2^R rows: R=%d is above the limit of %d" % (r, hip_ops.MAX_EXACT_PLAYERS))
     keep, weights = kernelshap.enumerated(r, device)
@@ -118,14 +126,10 @@ def enumerated(r, device):
 def estimate(keep, v, v_empty, v_full, r, weights=None, gram="analytic"):
     """phi of the wide rows ``keep`` (M,W) with rewards ``v`` ((M,) float32 device tensor, or (G,M) for G games on the same rows;
     v_empty, v_full: scalars or (G,)) -> float64 ndarray (R,) or (G,R): the moment kernel, then the closed form."""
-    r = _regions(r)
-    _gram(gram)
-    if not isinstance(v, torch.Tensor) or v.dim() not in (1, 2):
-        raise IqError("v must be a (M,) or (G,M) tensor")
-    v2 = v.reshape(1, -1) if v.dim() == 1 else v
-    g, dev = v2.shape[0], keep.device
-    v0, v1 = kernelshap._f64(v_empty, g, dev, "v_empty"), kernelshap._f64(v_full, g, dev, "v_full")
-    b, wsum = hip_ops.kshap_moment_wide(keep, v2.contiguous(), v0, r, weights)
+    r = regions(r)
+    check_gram(gram)
+    v2, v0, v1 = kernelshap.games(keep, v, v_empty, v_full)
+    b, wsum = hip_ops.kshap_moment_wide(keep, v2, v0, r, weights)
     phi = hip_ops.kshap_phi_analytic(b, wsum, v1 - v0).cpu().numpy()
     return phi[0] if v.dim() == 1 else phi
 
@@ -136,61 +140,30 @@ def rewards(model, data, lbl, region_id, args, keep, coalitions=None, chunk=1 <<
     the empty coalition as two extra rows of the same calls -> (v (M,) float32 device tensor, v_full, v_empty).  ``classes``
     as in kernelshap.rewards: -> (v (G,M), v_full (G,), v_empty (G,)), row g the bits of the call with lbl = classes[g]."""
     mode = wide._pick_coalitions(coalitions, data)
-    dev = data.device
-    r = _regions(args.num_regions)
+    r = regions(args.num_regions)
     hip_ops.wide_keep(keep, r)
-    rid = hip_ops.region_ids(region_id, dev, r)
-    ends = np.stack([hip_ops.region_words(np.arange(r), r), np.zeros(hip_ops.wide_words(r), dtype=np.uint64)])
-    rows = torch.cat([keep, hip_ops.wide_masks_to_tensor(ends, dev)])
-    v = None if classes is not None else torch.empty((rows.shape[0],), dtype=torch.float32, device=dev)
-    chunk = max(1, int(chunk))
-    with torch.no_grad():
-        for first in range(0, rows.shape[0], chunk):
-            part = rows[first:first + chunk].contiguous()
-            logits = wide._logits(model, data, rid, part, r, mode)
-            if classes is None:
-                v[first:first + part.shape[0]] = final_common.get_reward(logits, lbl, args)
-            else:
-                v = final_common.reward_table(classes, logits.shape[1], rows.shape[0], dev) if v is None else v
-                final_common.get_reward_classes(logits, classes, args, v, first)
-    if classes is not None:
-        return kernelshap._class_ends(v)
-    tail = v[-2:].cpu().numpy()
-    return v[:-2].contiguous(), float(tail[0]), float(tail[1])
+    rid = hip_ops.region_ids(region_id, data.device, r)
+    return final_common.rewards_with_ends(lambda part: wide._logits(model, data, rid, part, r, mode), keep, end_rows(r, data.device),
+                                          lbl, classes, args, chunk)
 
 
 def running_estimates(keep, v, v_empty, v_full, r, counts, gram="analytic"):
     """{count: phi of the first ``count`` rows}, every count: there is no singular case."""
-    _gram(gram)
-    return {c: estimate(keep[:c].contiguous(), v[:c].contiguous(), v_empty, v_full, r, None, gram) for c in counts}
+    check_gram(gram)
+    return kernelshap.running_estimates(keep, v, v_empty, v_full, r, counts, gram, sys.modules[__name__])
 
 
 def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",
          seed=1, stream=0):
     """One cloud's sampled (or, at most exact.MAX_PLAYERS regions, enumerated) game with everything the driver stores: dict of
     keep (M,W), weights (None when sampled), v (M,) float32 rewards, v_full, v_empty, phi (R,) and running {count: phi of the
-    first ``count`` rows}.  ``draw``: "stream" - ``draw`` on NumPy's global generator - or "counter" - ``draw_counter`` keyed by
-    (``seed``, ``stream``), which the other kind ignores."""
-    r = _regions(args.num_regions)
-    _gram(gram)
-    _draw_kind(draw)
-    weights = None
-    if isinstance(samples, str):
-        if samples != "all":
-            raise IqError("samples must be a count, None or 'all', got %r" % (samples,))
-        keep, weights = enumerated(r, data.device)
-    else:
-        samples = default_samples(r) if samples is None else samples
-        if draw == "counter":
-            keep, _ = draw_counter(r, samples, seed, stream, paired, data.device)
-        else:
-            keep, _ = _draw_stream(r, samples, paired, data.device)
-    v, v_full, v_empty = rewards(model, data, lbl, region_id, args, keep, coalitions)
-    phi = estimate(keep, v, v_empty, v_full, r, weights, gram)
-    running = {}
-    if weights is None:
-        running = running_estimates(keep, v, v_empty, v_full, r, running_counts(r, keep.shape[0], paired, counts), gram)
-    return {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
+    first ``count`` rows} (kernelshap.play on this module).  ``draw``: "stream" - ``draw`` on NumPy's global generator - or
+    "counter" - ``draw_counter`` keyed by (``seed``, ``stream``), which the other kind ignores.  The region count, ``gram`` and
+    ``draw`` are refused, in that order, before anything else is looked at."""
+    regions(args.num_regions)
+    check_gram(gram)
+    return kernelshap.play(sys.modules[__name__], model, data, lbl, region_id, args, samples, paired, gram, counts,
+                           drawer(draw, seed, stream), coalitions=coalitions)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",

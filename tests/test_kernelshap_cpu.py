@@ -138,3 +138,21 @@ def test_driver_parser_refuses_1_and_65_regions(capsys):
     with pytest.raises(SystemExit):
         kernel_stage.make_args(["--model", "pointnet", "--num_regions", "25", "--compare_exact"])
     assert "24" in capsys.readouterr().err
+
+
+def test_game_refuses_a_bad_gram_before_it_draws_or_loads_the_library(monkeypatch):
+    """The mirror of test_kshap_counter_cpu.py::test_python_level_refusals_need_no_library_call for the narrow game: a ``gram``
+    outside GRAMS is refused before a row is drawn (NumPy's global generator stands where it stood) and before any forward."""
+    import argparse
+
+    from interpret_quality_amd import kernelshap
+
+    def no_library():
+        raise AssertionError("the library was loaded")
+    monkeypatch.setattr(_lib, "load", no_library)
+    state = np.random.get_state()
+    for call in (kernelshap.game, kernelshap.shapley):
+        with pytest.raises(_lib.IqError, match="gram must be one of"):
+            call(None, None, None, None, argparse.Namespace(num_regions=8), samples=64, gram="bogus")
+    after = np.random.get_state()
+    assert state[0] == after[0] and np.array_equal(state[1], after[1]) and state[2:] == after[2:]
