@@ -72,8 +72,10 @@ enum {
  * 116: new entry point, no layout change (the counter-based draw of a wide game's rows: iq_kshap_draw_counter).
  * 117: new entry point, no layout change (the fused PointConv path's inverse density on its own: iq_pointconv_inverse_density).
  * 118: new entry points, no layout change (all-class games on shared coalitions: iq_reward_classes, iq_shapley_games_scratch_bytes,
- * iq_shapley_accum_games). */
-#define IQ_ABI_VERSION 118
+ * iq_shapley_accum_games).
+ * 119: one new diagnostic entry point, no layout change (iq_debug.h: iq_debug_pointnet_slots); the narrow PointNet workspace grew by
+ * 12 bytes per coalition (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes: the slots of the distinct coalitions). */
+#define IQ_ABI_VERSION 119
 int iq_version(void);
 const char* iq_last_error(void);
 

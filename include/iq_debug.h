@@ -45,7 +45,7 @@ int iq_profile_read_work(int slot, double* total_ms, int* launches, double* tota
  *   5    57          dense layers on the fp32 MFMA
  *   5    59          bf16x3 dense layers with 128-row tiles only (the launch before the short tiles; bit-identical results)
  *   5    60          PointNet coalition chains run every repeated coalition of a batch instead of copying the first one's rows
- *                    (no representatives are sought, pn_dup_copy_kernel does not run; bit-identical results) */
+ *                    (no representatives are sought, every item is its own slot and nothing is expanded; bit-identical results) */
 int iq_set_tuning(int key, int value);
 int iq_profile_read(int slot, double* total_ms, int* launches);
 
@@ -66,11 +66,19 @@ int iq_debug_mfma_sustained_shape(int shape, double seconds, float* scratch /*de
 /* Diagnostic: the representatives iq_pointnet_coalitions finds in a batch of keep masks before its chains run - the same launches
  * from the same launcher, with the caller's scratch in place of the workspace.  rep_out[i] = the lowest j <= i with
  * cloud_of[j] == cloud_of[i] (NULL: one cloud, nclouds must be 1) and (keep[j] ^ keep[i]) clear in its low R bits; items with
- * rep_out[i] != i are the ones whose chain output the forward copies from row rep_out[i].  keep (B) uint64, cloud_of (B) int32 or
+ * rep_out[i] != i are the ones the forward does not evaluate: they take the results of item rep_out[i].  keep (B) uint64, cloud_of (B) int32 or
  * NULL, rep_out (B) int32: device.  scratch: device, 4 bytes times the smallest power of two >= max(4, 2 B) - 16 * max(B, 1) bytes
  * always suffice; less is IQ_EWORKSPACE.  No synchronisation. */
 int iq_debug_pointnet_reps(const uint64_t* keep /*device*/, const int32_t* cloud_of /*device or NULL*/, int B, int nclouds, int R,
                            int32_t* rep_out /*device*/, void* scratch /*device*/, size_t scratch_bytes, iq_stream_t stream);
+
+/* Diagnostic: the slots iq_pointnet_coalitions then gives the distinct coalitions - the forward's launches again, the caller's scratch
+ * in place of the workspace.  slots_out (3 B + 1) int32, device: slot_of[B], slot_of[i] = the number of representatives j == rep[j]
+ * below rep[i]; item_u[B], its first U entries the representatives in ascending order; cloud_u[B], its first U entries their clouds
+ * (not written when cloud_of is NULL); n_distinct = U.  Entries at U and beyond are not written.  scratch: device,
+ * 24 * max(B, 1) + 8 bytes always suffice; less than needed is IQ_EWORKSPACE.  No synchronisation. */
+int iq_debug_pointnet_slots(const uint64_t* keep /*device*/, const int32_t* cloud_of /*device or NULL*/, int B, int nclouds, int R,
+                            int32_t* slots_out /*device*/, void* scratch /*device*/, size_t scratch_bytes, iq_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -177,10 +177,11 @@ SIGNATURES = {
     "iq_debug_mfma_sustained_shape": (_I, [_I, ctypes.c_double, _P, _SZ, ctypes.POINTER(ctypes.c_double),
                                            ctypes.POINTER(ctypes.c_double), _P]),
     "iq_debug_pointnet_reps": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "iq_debug_pointnet_slots": (_I, [_P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
 }
 
 _lib = None
-ABI_VERSION = 118  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 119  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

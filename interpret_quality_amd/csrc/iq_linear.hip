@@ -338,7 +338,7 @@ __device__ __forceinline__ void gemm_bf3_tile(const float* __restrict__ A, int l
                                               const float* __restrict__ bias, float* __restrict__ out, int ldo, int M, int K, int Nout,
                                               int relu, const int32_t* __restrict__ m_dev, const float* __restrict__ row_w,
                                               int col_blocks, const int32_t* __restrict__ tile_nu, int rows_per_cloud, int Kreal,
-                                              int chunks_per_split) {
+                                              int chunks_per_split, int m_base) {
     // SPLITK (few rows, very long K: launch_linear_splitk): workgroup row blockIdx.y takes chunks_per_split 32-k chunks and writes
     // its RAW partial sums to out + blockIdx.y * M * ldo; bias and activation belong to splitk_reduce_kernel.
     // K = the layer's inputs rounded up to a multiple of 32 (the weight image is zero there, iq_pack_weight_bf3), Kreal = the
@@ -356,7 +356,7 @@ __device__ __forceinline__ void gemm_bf3_tile(const float* __restrict__ A, int l
     const int per = 8 * col_blocks, grp = blockIdx.x / per, rr = blockIdx.x - grp * per;
     const int bx = grp * 8 + (rr & 7), by = rr >> 3;                   // column blocks of a row tile side by side on one XCD
     if (bx >= row_tiles) return;
-    if (m_dev) M = min(M, *m_dev);
+    if (m_dev) M = min(M, *m_dev - m_base);   // m_base: the rows of *m_dev in front of this grid's row 0 (launch_bf3's second grid)
     int m0 = bx * ROWS;
     if (!POOL && MT == 4 && tile_nu) {   // as pn_gemm_lds_kernel: cloud-fastest walk, tiles beyond a cloud's live rows skipped
         const int ntc = rows_per_cloud / 128, nc = row_tiles / ntc;
@@ -555,8 +555,9 @@ __device__ __forceinline__ void gemm_bf3_tile(const float* __restrict__ A, int l
     const float *__restrict__ A, int lda, const unsigned short *__restrict__ w3, const float *__restrict__ bias,                     \
         float *__restrict__ out, int ldo, int M, int K, int Nout, int relu, const int32_t *__restrict__ m_dev,                       \
         const float *__restrict__ row_w, int col_blocks, const int32_t *__restrict__ tile_nu, int rows_per_cloud, int Kreal,         \
-        int chunks_per_split
-#define IQ_GEMM_BF3_ARGS A, lda, w3, bias, out, ldo, M, K, Nout, relu, m_dev, row_w, col_blocks, tile_nu, rows_per_cloud, Kreal, chunks_per_split
+        int chunks_per_split, int m_base
+#define IQ_GEMM_BF3_ARGS                                                                                                            \
+    A, lda, w3, bias, out, ldo, M, K, Nout, relu, m_dev, row_w, col_blocks, tile_nu, rows_per_cloud, Kreal, chunks_per_split, m_base
 
 // the 128-row tile: two workgroups per CU
 template <bool POOL, int NW = 4, bool RAGGED = false, bool SPLITK = false>
@@ -590,9 +591,10 @@ int cu_count() {
 }
 
 // one grid of pn_gemm_bf3_kernel<false> (MT = 4) or pn_gemm_bf3_short_kernel with MT m-tiles per workgroup over rows [0, M) and the first gy column blocks of 256
+// m_base: where A and out start inside the matrix that m_dev counts the live rows of
 template <int MT>
 void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
-                     const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy) {
+                     const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, int m_base = 0) {
     const int Kp = (L.cin + 31) & ~31;     // the bf16x3 image's k range (iq_pack_weight_bf3 pads with zero columns)
     const int gx = (M + 32 * MT - 1) / (32 * MT);
     const dim3 grid((unsigned)((gx + 7) / 8 * 8 * gy));
@@ -600,7 +602,7 @@ void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* ou
     const bool ragged = Kp != L.cin;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, A, lda, w3, L.b, out, ldo, M, Kp, L.cout, relu, m_dev,
-                           static_cast<const float*>(nullptr), gy, tile_nu, rows_per_cloud, L.cin, 0);
+                           static_cast<const float*>(nullptr), gy, tile_nu, rows_per_cloud, L.cin, 0, m_base);
     };
     if constexpr (MT == 4) {
         if (ragged) launch(pn_gemm_bf3_kernel<false, 4, true>);
@@ -621,12 +623,14 @@ void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* ou
 //   * from two rounds on: 128-row tiles, and where the last round is at most a quarter / a half full its rows go to a second grid
 //     of 32- / 64-row tiles behind the whole rounds                       (256 -> 4096: 8.06 rounds, 447 -> 445 us, nothing; 64-row
 //     tiles throughout 433, 32-row ones 509 - the short tiles' weight stream is 2 x / 4 x per row)
-//   * without fit_tiles (the other families' launches, not re-measured), with rows that only the device knows (m_dev), with
-//     tile_nu and under twin kTwinDenseTile128: 128-row tiles only, the former launch.
+//   * without fit_tiles (the other families' launches, not re-measured), with tile_nu and under twin kTwinDenseTile128: 128-row
+//     tiles only, the former launch.
 // Which tile a row falls in changes nothing in its result (gemm_bf3_tile: MT), so the result stays independent of M.
+// With a live row count that only the device knows (m_dev <= M) the scheme is chosen from M, the host's bound, and every grid
+// clamps its rows to *m_dev: workgroups past it leave, the heights stay those measured for M rows.
 int launch_bf3(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
                const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, bool fit_tiles) {
-    if (!fit_tiles || m_dev || tile_nu || iq::twin() == iq::kTwinDenseTile128) {
+    if (!fit_tiles || tile_nu || iq::twin() == iq::kTwinDenseTile128) {
         launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy);
         return iq::check_launch("pn_gemm_bf3_kernel");
     }
@@ -635,17 +639,17 @@ int launch_bf3(const float* A, int lda, const iq_dense_layer& L, float* out, int
     const long long round = 2LL * cus, tiles = (M + 127) / 128, wgs = tiles * gy;
     const int m_full = (int)(wgs / round * round / gy) * 128;     // rows of the whole rounds
     if (wgs < round) {
-        launch_bf3_rows<1>(A, lda, L, out, ldo, M, relu, st, nullptr, nullptr, 0, gy);
+        launch_bf3_rows<1>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy);
     } else if (wgs < 2 * round) {
-        launch_bf3_rows<2>(A, lda, L, out, ldo, M, relu, st, nullptr, nullptr, 0, gy);
+        launch_bf3_rows<2>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy);
     } else if (wgs % round == 0 || wgs % round > round / 2 || m_full <= 0 || m_full >= M) {
-        launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, nullptr, nullptr, 0, gy);
+        launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy);
     } else {
-        launch_bf3_rows<4>(A, lda, L, out, ldo, m_full, relu, st, nullptr, nullptr, 0, gy);
+        launch_bf3_rows<4>(A, lda, L, out, ldo, m_full, relu, st, m_dev, nullptr, 0, gy);
         const float* At = A + (size_t)m_full * lda;
         float* ot = out + (size_t)m_full * ldo;
-        if (wgs % round <= round / 4) launch_bf3_rows<1>(At, lda, L, ot, ldo, M - m_full, relu, st, nullptr, nullptr, 0, gy);
-        else launch_bf3_rows<2>(At, lda, L, ot, ldo, M - m_full, relu, st, nullptr, nullptr, 0, gy);
+        if (wgs % round <= round / 4) launch_bf3_rows<1>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full);
+        else launch_bf3_rows<2>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full);
     }
     return iq::check_launch("pn_gemm_bf3_kernel");
 }
@@ -753,7 +757,7 @@ int iq::launch_linear_splitk(const float* A, int lda, const iq_dense_layer& L, f
         const int gx = (M + 127) / 128, gy = L.cout / 256;
         hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, false, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy), (unsigned)splits), dim3(kThreads), 0,
                            st, A, lda, reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, scratch, L.cout, M, L.cin, L.cout, 0, nullptr, nullptr,
-                           gy, nullptr, 0, L.cin, kbs * 8 / 32);
+                           gy, nullptr, 0, L.cin, kbs * 8 / 32, 0);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
                            out, ldo, M, L.cout, splits, relu);
         return iq::check_launch("pn_gemm_bf3_kernel<split-K>");
@@ -779,7 +783,7 @@ int iq::launch_linear_pool(const float* A, int lda, const iq_dense_layer& L, flo
     if (w_bf3 && L.cout % 256 == 0) {
         hipLaunchKernelGGL(pn_gemm_bf3_kernel<true>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
                            reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy,
-                           nullptr, 0, L.cin, 0);
+                           nullptr, 0, L.cin, 0, 0);
         return iq::check_launch("pn_gemm_bf3_kernel<pool>");
     }
     hipLaunchKernelGGL((pn_gemm_lds_kernel<4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda, L.w, L.b,

@@ -117,7 +117,7 @@ namespace iq {
 // tile_nu[cloud] are wanted - 128-row tiles that lie entirely beyond are skipped (their outputs are left untouched).
 // fit_tiles: a bf16x3 layer may take 64- / 32-row workgroup tiles where 128-row ones would leave the chip part empty (launch_bf3 in
 // iq_linear.hip; bit-identical results).  Asked for by PointNet's heads and by iq_linear, where it is measured; the other families'
-// launches keep the 128-row tiling their steps were measured with.
+// launches keep the 128-row tiling their steps were measured with.  With m_dev the heights are chosen from M, the host's bound.
 int launch_linear(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu,
                   hipStream_t st, const int32_t* m_dev = nullptr, const int32_t* tile_nu = nullptr, int rows_per_cloud = 0,
                   bool fit_tiles = false);

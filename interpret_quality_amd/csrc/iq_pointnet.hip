@@ -100,6 +100,8 @@ __global__ __launch_bounds__(kThreads) void pn_prepare_kernel(const int32_t* __r
 // centre), r == R is the centre alone.  The list is padded with replicas of a valid row (duplicates
 // never change a max) to a multiple of the chunk size of either chain kernel, whichever ends later:
 // the 96-row kernel's fetch lanes read whole chunks (at most 43 x 96 = 4128 <= kRowCap entries).
+// Distinct coalitions only (pn_compact kernels): item = a slot, cloud_of = a cloud per slot, src = the batch item whose mask the slot
+// takes, n_dev = the slots in use; a workgroup past them leaves.
 __device__ __forceinline__ int padded_rows(int nrows) {
     static_assert((kMaxN + kMC96 - 1) / kMC96 * kMC96 <= kRowCap, "a padded row list fits its stride");
     return max((nrows + kMC - 1) / kMC * kMC, (nrows + kMC96 - 1) / kMC96 * kMC96);
@@ -109,8 +111,10 @@ __global__ __launch_bounds__(64) void pn_rows_kernel(const uint16_t* __restrict_
                                                      const uint64_t* __restrict__ keep_all,
                                                      const int32_t* __restrict__ cloud_of, uint16_t* __restrict__ rows_all,
                                                      int32_t* __restrict__ nrows_all, int N, int R, int nclouds,
-                                                     int with_centre, int prepool) {
+                                                     int with_centre, int prepool, const int32_t* __restrict__ src,
+                                                     const int32_t* __restrict__ n_dev) {
     const int item = blockIdx.x, lane = threadIdx.x;
+    if (n_dev && item >= *n_dev) return;
     int cloud;
     uint64_t keep;
     bool add_centre;
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(64) void pn_rows_kernel(const uint16_t* __restrict_
     } else {
         cloud = cloud_of ? cloud_of[item] : (nclouds == 1 ? 0 : item);
         const uint64_t full = R >= 64 ? ~0ull : ((1ull << R) - 1);
-        keep = (keep_all ? keep_all[item] : ~0ull) & full;
+        keep = (keep_all ? keep_all[src ? src[item] : item] : ~0ull) & full;
         add_centre = false;
     }
     const int32_t* roff = roff_all + (size_t)cloud * (R + 1);
@@ -353,8 +357,9 @@ constexpr int kBins = kMaxN / kMC + 2;
 
 __global__ __launch_bounds__(kThreads) void pn_order_count_kernel(const int32_t* __restrict__ nrows_all,
                                                                   int32_t* __restrict__ bin_of, int32_t* __restrict__ hist,
-                                                                  int B) {
+                                                                  int B, const int32_t* __restrict__ n_dev) {
     __shared__ int lh[kBins];   // per-workgroup histogram: one global atomic per bin and workgroup instead of one per item
+    if (n_dev) B = min(B, *n_dev);   // the live items where only the device knows them: the others do not enter the order
     if (threadIdx.x < kBins) lh[threadIdx.x] = 0;
     __syncthreads();
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
@@ -379,8 +384,10 @@ __global__ void pn_order_scan_kernel(int32_t* __restrict__ hist) {
 // (the order inside a bin is irrelevant: equal chunk counts)
 __global__ __launch_bounds__(kThreads) void pn_order_scatter_kernel(const int32_t* __restrict__ bin_of,
                                                                     int32_t* __restrict__ cursor,
-                                                                    int32_t* __restrict__ order, int B) {
+                                                                    int32_t* __restrict__ order, int B,
+                                                                    const int32_t* __restrict__ n_dev) {
     __shared__ int lh[kBins], base[kBins];
+    if (n_dev) B = min(B, *n_dev);
     if (threadIdx.x < kBins) lh[threadIdx.x] = 0;
     __syncthreads();
     const int item = blockIdx.x * blockDim.x + threadIdx.x;
@@ -402,9 +409,11 @@ __global__ __launch_bounds__(kThreads) void pn_order_scatter_kernel(const int32_
 constexpr int kOrderThreads = 1024, kOrderPer = 4, kOrderFusedMax = kOrderThreads * kOrderPer;
 
 __global__ __launch_bounds__(kOrderThreads) void pn_order_fused_kernel(const int32_t* __restrict__ nrows_all,
-                                                                       int32_t* __restrict__ order, int B) {
+                                                                       int32_t* __restrict__ order, int B,
+                                                                       const int32_t* __restrict__ n_dev) {
     __shared__ int lh[kBins];
     const int tid = threadIdx.x, lane = tid & 63;
+    if (n_dev) B = min(B, *n_dev);
     if (tid < kBins) lh[tid] = 0;
     __syncthreads();
     int bin[kOrderPer], pos[kOrderPer];
@@ -440,7 +449,7 @@ __global__ __launch_bounds__(kOrderThreads) void pn_order_fused_kernel(const int
     }
 }
 
-// ---- repeated coalitions of a batch: the first item of every (cloud, keep mask) is computed, the others copy its chain output ----
+// ---- repeated coalitions of a batch: only the first item of every (cloud, keep mask) is evaluated, the others take its results ----
 // rep[i] = the lowest item j <= i on i's cloud with the same kept regions (the mask's low R bits, as pn_stn_gather_kernel forms them):
 // the same row list in table order under the same transforms, so whichever member computes, the row is the same; the lowest makes rep
 // independent of timing and rep[rep[i]] == rep[i].  An open-addressing table of item indices, cleared to -1, at most half full:
@@ -502,34 +511,175 @@ __global__ __launch_bounds__(kThreads) void pn_rep_insert_kernel(const uint64_t*
     if (live) rep[item] = slot;
 }
 
-__global__ __launch_bounds__(kThreads) void pn_rep_write_kernel(const int32_t* __restrict__ table, int32_t* __restrict__ rep, int B) {
+// block_cnt (optional): the representatives among this workgroup's kThreads items, for pn_compact_scan_kernel
+__global__ __launch_bounds__(kThreads) void pn_rep_write_kernel(const int32_t* __restrict__ table, int32_t* __restrict__ rep, int B,
+                                                                int32_t* __restrict__ block_cnt) {
     const int item = blockIdx.x * kThreads + threadIdx.x;
-    if (item < B) rep[item] = table[rep[item]];
+    int r = -1;
+    if (item < B) rep[item] = r = table[rep[item]];
+    if (block_cnt) {
+        const int n = __syncthreads_count(r == item);
+        if (threadIdx.x == 0) block_cnt[blockIdx.x] = n;
+    }
 }
 
 // rep (B) from keep (B) and cloud_of (B, or null: one cloud); table: rep_slots(B) int32 of scratch.  The same three launches for
 // every B: one workgroup with the table in LDS took 40 us on a pose-sized batch against 26 us for these (profiles/chain_repeats_ab.txt)
-int launch_reps(const uint64_t* keep, const int32_t* cloud_of, int B, int R, int32_t* rep, int32_t* table, hipStream_t st) {
+int launch_reps(const uint64_t* keep, const int32_t* cloud_of, int B, int R, int32_t* rep, int32_t* table, hipStream_t st,
+                int32_t* block_cnt = nullptr) {
     const size_t slots = rep_slots(B);
     if (hipMemsetAsync(table, 0xff, slots * sizeof(int32_t), st) != hipSuccess)
         return iq::fail(IQ_ELAUNCH, "pn_rep kernels: memset failed");
     const dim3 grid((B + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(pn_rep_insert_kernel, grid, dim3(kThreads), 0, st, keep, cloud_of, table, rep, B, R, (uint32_t)(slots - 1));
-    hipLaunchKernelGGL(pn_rep_write_kernel, grid, dim3(kThreads), 0, st, table, rep, B);
+    hipLaunchKernelGGL(pn_rep_write_kernel, grid, dim3(kThreads), 0, st, table, rep, B, block_cnt);
     return iq::check_launch("pn_rep kernels");
 }
 
-// after a chain launch: row `item` of out (and of argrow, if any) = the row of its representative
-__global__ __launch_bounds__(kThreads) void pn_dup_copy_kernel(const int32_t* __restrict__ rep, float* __restrict__ out,
-                                                               int32_t* __restrict__ argrow) {
-    const int item = blockIdx.x;
-    const int src = rep[item];
-    if (src == item) return;
-    static_assert(kFeat == 4 * kThreads, "one float4 per thread");
-    reinterpret_cast<f32x4*>(out + (size_t)item * kFeat)[threadIdx.x] = reinterpret_cast<const f32x4*>(out + (size_t)src * kFeat)[threadIdx.x];
-    if (argrow) {
-        const int4 v = reinterpret_cast<const int4*>(argrow + (size_t)src * kFeat)[threadIdx.x];
-        reinterpret_cast<int4*>(argrow + (size_t)item * kFeat)[threadIdx.x] = v;
+// The distinct coalitions of a batch in slots 0 .. U-1, in the order of their first items: slot_of[i] = the number of representatives
+// below rep[i] (a rank, so the map does not depend on timing), item_u[s] = the representative in slot s, cloud_u[s] = its cloud (only
+// with cloud_of), *n_distinct = U.  Everything after this runs on U slots, a count that stays on the device; pn_expand kernels give
+// every item its slot's results at the end.  Up to kOrderFusedMax items one workgroup does it, a thread kOrderPer CONSECUTIVE
+// items; above, the count (pn_rep_write_kernel) / scan / scatter / fill launches below, as the launch order does.
+__device__ __forceinline__ int block_exclusive_scan(int v, int* wsum, int& total) {   // blockDim.x / 64 <= 16 waves; wsum: one int each
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off);
+        if (lane >= off) inc += t;
+    }
+    __syncthreads();   // wsum may still be read from an earlier call
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int run = inc - v;
+    total = 0;
+    for (int w = 0; w < nw; ++w) {
+        const int c = wsum[w];
+        if (w < wave) run += c;
+        total += c;
+    }
+    return run;
+}
+
+__global__ __launch_bounds__(kOrderThreads) void pn_compact_fused_kernel(const int32_t* __restrict__ rep, const int32_t* __restrict__ cloud_of,
+                                                                         int32_t* __restrict__ slot_of, int32_t* __restrict__ item_u,
+                                                                         int32_t* __restrict__ cloud_u, int32_t* __restrict__ n_distinct,
+                                                                         int B) {
+    __shared__ int slot_s[kOrderFusedMax];   // a representative's slot
+    __shared__ int wsum[kOrderThreads / 64];
+    const int tid = threadIdx.x;
+    int r[kOrderPer], cnt = 0;
+#pragma unroll
+    for (int j = 0; j < kOrderPer; ++j) {
+        const int item = tid * kOrderPer + j;
+        r[j] = item < B ? rep[item] : -1;
+        cnt += r[j] == item;
+    }
+    int total;
+    int slot = block_exclusive_scan(cnt, wsum, total);
+#pragma unroll
+    for (int j = 0; j < kOrderPer; ++j) {
+        const int item = tid * kOrderPer + j;
+        if (r[j] == item) {
+            slot_s[item] = slot;
+            item_u[slot] = item;
+            if (cloud_of) cloud_u[slot] = cloud_of[item];
+            ++slot;
+        }
+    }
+    if (tid == 0) *n_distinct = total;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kOrderPer; ++j) {
+        const int item = tid * kOrderPer + j;
+        if (item < B) slot_of[item] = slot_s[r[j]];
+    }
+}
+
+// block_cnt (nb counts of representatives, pn_rep_write_kernel) -> the first slot of every workgroup, in place; *n_distinct
+__global__ __launch_bounds__(kThreads) void pn_compact_scan_kernel(int32_t* __restrict__ block_cnt, int32_t* __restrict__ n_distinct, int nb) {
+    __shared__ int wsum[kThreads / 64];
+    int carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += kThreads) {
+        const int b = b0 + threadIdx.x, c = b < nb ? block_cnt[b] : 0;
+        int total;
+        const int ex = block_exclusive_scan(c, wsum, total);
+        if (b < nb) block_cnt[b] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *n_distinct = carry;
+}
+
+// the representatives: their slot (slot_of), and the slot's item and cloud
+__global__ __launch_bounds__(kThreads) void pn_compact_scatter_kernel(const int32_t* __restrict__ rep, const int32_t* __restrict__ cloud_of,
+                                                                      const int32_t* __restrict__ block_first,
+                                                                      int32_t* __restrict__ slot_of, int32_t* __restrict__ item_u,
+                                                                      int32_t* __restrict__ cloud_u, int B) {
+    __shared__ int wsum[kThreads / 64];
+    const int item = blockIdx.x * kThreads + threadIdx.x;
+    const bool is_rep = item < B && rep[item] == item;
+    int total;
+    const int slot = block_first[blockIdx.x] + block_exclusive_scan(is_rep ? 1 : 0, wsum, total);
+    if (is_rep) {
+        slot_of[item] = slot;
+        item_u[slot] = item;
+        if (cloud_of) cloud_u[slot] = cloud_of[item];
+    }
+}
+
+// the other items: their representative's slot (written by the launch before)
+__global__ __launch_bounds__(kThreads) void pn_compact_fill_kernel(const int32_t* __restrict__ rep, int32_t* slot_of, int B) {
+    const int item = blockIdx.x * kThreads + threadIdx.x;
+    if (item >= B) return;
+    const int r = rep[item];
+    if (r != item) slot_of[item] = slot_of[r];
+}
+
+// rep (B; launch_reps with block_cnt above kOrderFusedMax items) -> slot_of (B), item_u, cloud_u (null without cloud_of), n_distinct
+int launch_compact(const int32_t* rep, const int32_t* cloud_of, int B, int32_t* block_cnt, int32_t* slot_of, int32_t* item_u,
+                   int32_t* cloud_u, int32_t* n_distinct, hipStream_t st) {
+    if (B <= kOrderFusedMax) {
+        hipLaunchKernelGGL(pn_compact_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, rep, cloud_of, slot_of, item_u, cloud_u,
+                           n_distinct, B);
+    } else {
+        const int nb = (B + kThreads - 1) / kThreads;
+        hipLaunchKernelGGL(pn_compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, n_distinct, nb);
+        hipLaunchKernelGGL(pn_compact_scatter_kernel, dim3(nb), dim3(kThreads), 0, st, rep, cloud_of, block_cnt, slot_of, item_u,
+                           cloud_u, B);
+        hipLaunchKernelGGL(pn_compact_fill_kernel, dim3(nb), dim3(kThreads), 0, st, rep, slot_of, B);
+    }
+    return iq::check_launch("pn_compact kernels");
+}
+
+// at the end: every item takes its slot's logits ...
+__global__ __launch_bounds__(kThreads) void pn_expand_logits_kernel(const float* __restrict__ logits_u, const int32_t* __restrict__ slot_of,
+                                                                    float* __restrict__ logits, int B, int ncls) {
+    const size_t t = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (t >= (size_t)B * ncls) return;
+    const int item = (int)(t / ncls), c = (int)(t - (size_t)item * ncls);
+    logits[t] = logits_u[(size_t)slot_of[item] * ncls + c];
+}
+
+// ... and, where the caller asked for them, its slot's packed feature transform (tfp_u, by slot, -> tfp, by item) and its
+// representative's row of crt_points, which the trunk chain wrote in place (ChainArgs::arg_row): representatives' rows are only read
+__global__ __launch_bounds__(kThreads) void pn_expand_rows_kernel(const int32_t* __restrict__ slot_of, const int32_t* __restrict__ item_u,
+                                                                  const float* __restrict__ tfp_u, float* __restrict__ tfp,
+                                                                  int32_t* crt_points) {
+    const int item = blockIdx.x, slot = slot_of[item];
+    static_assert(kFeat == 4 * kThreads, "one int4 per thread");
+    if (tfp) {
+        const f32x4* s4 = reinterpret_cast<const f32x4*>(tfp_u + (size_t)slot * 4096);
+        f32x4* d4 = reinterpret_cast<f32x4*>(tfp + (size_t)item * 4096);
+#pragma unroll
+        for (int q = 0; q < 4096 / 4 / kThreads; ++q) d4[threadIdx.x + q * kThreads] = s4[threadIdx.x + q * kThreads];
+    }
+    if (crt_points) {
+        const int src = item_u[slot];
+        if (src != item) {
+            const int4 v = reinterpret_cast<const int4*>(crt_points + (size_t)src * kFeat)[threadIdx.x];
+            reinterpret_cast<int4*>(crt_points + (size_t)item * kFeat)[threadIdx.x] = v;
+        }
     }
 }
 
@@ -539,11 +689,13 @@ __global__ __launch_bounds__(kThreads) void pn_stn_gather_kernel(const float* __
                                                                  const uint64_t* __restrict__ keep,
                                                                  const int32_t* __restrict__ cloud_of,
                                                                  float* __restrict__ out, int R, int nclouds,
-                                                                 int with_centre) {
-    const int item = blockIdx.x;
+                                                                 int with_centre, const int32_t* __restrict__ src,
+                                                                 const int32_t* __restrict__ n_dev) {
+    const int item = blockIdx.x;   // src, n_dev: as in pn_rows_kernel
+    if (n_dev && item >= *n_dev) return;
     const int cloud = cloud_of ? cloud_of[item] : (nclouds == 1 ? 0 : item);
     const uint64_t full = R >= 64 ? ~0ull : ((1ull << R) - 1);
-    const uint64_t k = (keep ? keep[item] : ~0ull) & full;
+    const uint64_t k = (keep ? keep[src ? src[item] : item] : ~0ull) & full;
     const int per = R + with_centre;
     const f32x4* g4 = reinterpret_cast<const f32x4*>(G) + (size_t)cloud * per * (kFeat / 4) + threadIdx.x;
     f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -676,13 +828,18 @@ struct Workspace {
     uint16_t* rows;      // (B, kRowCap)
     int32_t* nrows;      // (B)
     int32_t* order;    // (B) launch order
-    int32_t* bin_of;   // (B) launch-order bins until the order is scattered (above kOrderFusedMax items only); afterwards, on the narrow
-                       // keep-mask route, every item's representative (launch_reps) - on the prefix route a cloud per item instead
+    int32_t* bin_of;   // (B) on the narrow keep-mask route every item's representative (launch_reps) until the slots are assigned; then
+                       // launch-order bins until the order is scattered (above kOrderFusedMax items only); afterwards, on the prefix
+                       // route, a cloud per item
     int32_t* hist;     // (kBins)
+    int32_t* slot_of;  // (B) the slot of every item, (B) the item and (B) the cloud of every slot, and the number of slots in use
+    int32_t* item_u;   // (pn_compact kernels): one block of 3 B + 1 int32
+    int32_t* cloud_u;
+    int32_t* n_distinct;
     float* G;
     float* gbuf;
-    float* h1;         // (B,512) the heads' first hidden layer; before the input-STN head writes it, the table of launch_reps
-                       // (rep_slots(B) int32 < 4 B of them)
+    float* h1;         // (B,512) the heads' first hidden layer, and at the end the logits by slot; before the input-STN head writes
+                       // it, the table of launch_reps (rep_slots(B) int32 < 4 B of them) and behind it the compaction's counts
     float* h2;
     float* trans;
     float* tfp;
@@ -704,6 +861,10 @@ Workspace carve(void* base, int B, int nclouds, int N, int R, int roff_entries =
     w.order = c.take<int32_t>(b);
     w.bin_of = c.take<int32_t>(b);
     w.hist = c.take<int32_t>((size_t)kBins);
+    w.slot_of = c.take<int32_t>(3 * b + 1);
+    w.item_u = w.slot_of + b;
+    w.cloud_u = w.item_u + b;
+    w.n_distinct = w.cloud_u + b;
     w.G = c.take<float>(nc * (R + 1) * kFeat);
     w.gbuf = c.take<float>(b * kFeat);
     w.h1 = c.take<float>(b * 512);
@@ -770,10 +931,28 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
 
+    // Repeated coalitions: narrow keep masks in table order only (a prefix route's row lists follow its permutations), and a cloud
+    // per item that is known - without cloud_of and with several clouds every item has its own.  The distinct ones move to slots
+    // 0 .. U-1 (pn_compact kernels) and every launch below works on slots: grids for B, the bound the host knows, and n_dev = U on
+    // the device for the workgroups past it to leave.  rows, nrows, gbuf, trans, tfp, h1 and h2 are then indexed by slot.  Every
+    // other call is the same launches with the identity map: n_dev null, an item its own slot.  rep borrows the launch order's
+    // bins, the table and the counts h1: both idle up to here (Workspace).
+    const int32_t *n_dev = nullptr, *slot_item = nullptr, *slot_cloud = cloud_of;
+    if (!wide_words && !orders && keep && B > 1 && (cloud_of || nclouds == 1) && iq::twin() != iq::kTwinChainNoDedup) {
+        static_assert(sizeof(int32_t) * 5 <= sizeof(float) * 512, "rep_slots(B) < 4 B int32 and B / kThreads + 1 counts inside h1's (B,512) floats");
+        int32_t* table = reinterpret_cast<int32_t*>(ws.h1);
+        int32_t* block_cnt = B > kOrderFusedMax ? table + rep_slots(B) : nullptr;
+        if ((rc = launch_reps(keep, cloud_of, B, R, ws.bin_of, table, st, block_cnt))) return rc;
+        if ((rc = launch_compact(ws.bin_of, cloud_of, B, block_cnt, ws.slot_of, ws.item_u, ws.cloud_u, ws.n_distinct, st))) return rc;
+        n_dev = ws.n_distinct;
+        slot_item = ws.item_u;
+        if (cloud_of) slot_cloud = ws.cloud_u;
+    }
+
     const int pre_items = nclouds * (R + with_centre);
     // the chain kernels take a cloud per item: the prefix route writes one (pn_stn_prefix_kernel) where the launch order kept its
     // bins, which nothing reads once the order is scattered
-    const int32_t* item_cloud = orders ? (nclouds > 1 ? ws.bin_of : nullptr) : cloud_of;
+    const int32_t* item_cloud = orders ? (nclouds > 1 ? ws.bin_of : nullptr) : slot_cloud;
     if (wide_words) {
         hipLaunchKernelGGL(pn_prepare_wide_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
         if ((rc = iq::check_launch("pn_prepare_wide_kernel"))) return rc;
@@ -793,34 +972,24 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         hipLaunchKernelGGL(pn_prepare_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
         if ((rc = iq::check_launch("pn_prepare_kernel"))) return rc;
         hipLaunchKernelGGL(pn_rows_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
-                           ws.rows_pre, ws.nrows_pre, N, R, nclouds, with_centre, 1);
-        hipLaunchKernelGGL(pn_rows_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
-                           ws.nrows, N, R, nclouds, with_centre, 0);
+                           ws.rows_pre, ws.nrows_pre, N, R, nclouds, with_centre, 1, nullptr, nullptr);
+        hipLaunchKernelGGL(pn_rows_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, slot_cloud, ws.rows,
+                           ws.nrows, N, R, nclouds, with_centre, 0, slot_item, n_dev);
         if ((rc = iq::check_launch("pn_rows_kernel"))) return rc;
     }
     // launch order of the coalition chains: most rows first, so the grid drains evenly
     if (B <= kOrderFusedMax) {
-        hipLaunchKernelGGL(pn_order_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.order, B);
+        hipLaunchKernelGGL(pn_order_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.order, B, n_dev);
     } else {
         if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
             return iq::fail(IQ_ELAUNCH, "%s: memset failed", who);
         hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
-                           ws.bin_of, ws.hist, B);
+                           ws.bin_of, ws.hist, B, n_dev);
         hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
         hipLaunchKernelGGL(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                           ws.bin_of, ws.hist, ws.order, B);
+                           ws.bin_of, ws.hist, ws.order, B, n_dev);
     }
     if ((rc = iq::check_launch("pn_order kernels"))) return rc;
-    // repeated coalitions: narrow keep masks in table order only (a prefix route's row lists follow its permutations), and a cloud
-    // per item that is known - without cloud_of and with several clouds every item has its own.  rep takes the place of the launch
-    // order's bins and the table that of h1, both idle from here to the heads (Workspace).
-    const int32_t* dup_rep = nullptr;
-    if (!wide_words && !orders && keep && B > 1 && (cloud_of || nclouds == 1) && iq::twin() != iq::kTwinChainNoDedup) {
-        static_assert(sizeof(int32_t) * 4 <= sizeof(float) * 512, "rep_slots(B) < 4 B int32 inside h1's (B,512) floats");
-        if ((rc = launch_reps(keep, cloud_of, B, R, ws.bin_of, reinterpret_cast<int32_t*>(ws.h1), st))) return rc;
-        dup_rep = ws.bin_of;
-    }
-
     ChainArgs a{};
     a.clouds = clouds;
     if (channel_first) { a.ps = 1; a.cs = N; } else { a.ps = 3; a.cs = 1; }
@@ -855,23 +1024,24 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         hipLaunchKernelGGL(pn_stn_gather_wide_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
                            R, wide_words, nclouds, with_centre);
     else
-        hipLaunchKernelGGL(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
-                           R, nclouds, with_centre);
+        hipLaunchKernelGGL(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, slot_cloud, ws.gbuf,
+                           R, nclouds, with_centre, slot_item, n_dev);
     if ((rc = iq::check_launch(orders ? "pn_stn_prefix_kernel" : wide_words ? "pn_stn_gather_wide_kernel" : "pn_stn_gather_kernel")))
         return rc;
-    if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st, nullptr, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st, n_dev, nullptr, 0, true))) return rc;
 
     // 2. feature-STN chain over each coalition's distinct points
     a.cloud_of = item_cloud; a.trans = ws.trans;
     a.rows = ws.rows; a.nrows = ws.nrows;
     a.item_order = ws.order;
-    a.dup_rep = dup_rep;
+    a.n_dev = n_dev;
     a.w_in = w->feat_in;
     a.items = B;
     a.out = ws.gbuf;
-    float* tfp = trans_feat_packed ? trans_feat_packed : ws.tfp;
+    // by slot: the workspace's image; the caller's, if any, is expanded from it at the end
+    float* tfp = trans_feat_packed && !n_dev ? trans_feat_packed : ws.tfp;
     if (w->fstn_c1.w) {
         a.w1 = w->fstn_c1.w; a.b1 = w->fstn_c1.b;
         a.w2 = w->fstn_c2.w; a.b2 = w->fstn_c2.b;
@@ -881,10 +1051,9 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
             iq::ProfileSpan span(iq::kSlotFstn, st);
             launch_chain<kFstn>(a, st);
         }
-        if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, dup_rep, ws.gbuf, nullptr);
         if ((rc = iq::check_launch("pn_chain_kernel<fstn>"))) return rc;
-        if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
-        if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
+        if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+        if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true))) return rc;
         // fstn.fc3 (256 -> 4096, 70 % of the heads' FLOP) on the bf16 matrix pipe like the other wide layers.  The descriptor brings
         // no bf16x3 image of it (its rows are permuted by iq_pack_fstn_fc3; the packed weight set is what it has always been), so the
         // image is split off the float32 one here, per call: 1 M weights, a few microseconds, and nothing to go stale when a
@@ -895,7 +1064,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
             if ((rc = iq::launch_split_bf3(fc3.w, ws.fc3_bf3, 4096, 256, st))) return rc;
             fc3.w_bf3 = ws.fc3_bf3;
         }
-        if ((rc = launch_linear(ws.h2, 256, fc3, tfp, 4096, B, 0, st, nullptr, nullptr, 0, true))) return rc;
+        if ((rc = launch_linear(ws.h2, 256, fc3, tfp, 4096, B, 0, st, n_dev, nullptr, 0, true))) return rc;
     } else {
         // feature_transform = False (models/pointnet.py:62-63,72-78): no feature STN.  The trunk multiplies by the packed
         // IDENTITY instead (fstn_fc3.b = iq_pack_fstn_fc3 of a zero layer): sum_k f[k] I[k][n] = f[n] + zeros, exact.
@@ -907,6 +1076,7 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
 
     // 3. trunk chain
     a.argrow = crt_points;
+    a.arg_row = slot_item;   // a representative writes its own row of crt_points: the others copy it (pn_expand_rows_kernel)
     a.w1 = tfp; a.b1 = nullptr;
     a.w2 = w->feat_c2.w; a.b2 = w->feat_c2.b;
     a.w3 = w->feat_c3.w; a.b3 = w->feat_c3.b; a.w3_bf3 = reinterpret_cast<const unsigned short*>(w->feat_c3_bf3);
@@ -915,12 +1085,20 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         iq::ProfileSpan span(iq::kSlotTrunk, st);
         launch_chain<kTrunk>(a, st);
     }
-    if (dup_rep) hipLaunchKernelGGL(pn_dup_copy_kernel, dim3(B), dim3(kThreads), 0, st, dup_rep, ws.gbuf, crt_points);
     if ((rc = iq::check_launch("pn_chain_kernel<trunk>"))) return rc;
-    if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, nullptr, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, nullptr, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h2, 256, w->cls_fc3, logits, w->cls_fc3.cout, B, 0, st, nullptr, nullptr, 0, true))) return rc;
-    return IQ_OK;
+    if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+    if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+    if (!n_dev) return launch_linear(ws.h2, 256, w->cls_fc3, logits, w->cls_fc3.cout, B, 0, st, nullptr, nullptr, 0, true);
+    // the logits by slot where h1 was (cls_fc2 has read it), then every item its slot's results
+    const int ncls = w->cls_fc3.cout;
+    IQ_REQUIRE(ncls <= 512, "%s: %d classes", who, ncls);
+    if ((rc = launch_linear(ws.h2, 256, w->cls_fc3, ws.h1, ncls, B, 0, st, n_dev, nullptr, 0, true))) return rc;
+    hipLaunchKernelGGL(pn_expand_logits_kernel, dim3((unsigned)(((size_t)B * ncls + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       ws.h1, ws.slot_of, logits, B, ncls);
+    if (trans_feat_packed || crt_points)
+        hipLaunchKernelGGL(pn_expand_rows_kernel, dim3(B), dim3(kThreads), 0, st, ws.slot_of, ws.item_u, ws.tfp, trans_feat_packed,
+                           crt_points);
+    return iq::check_launch("pn_expand kernels");
 }
 
 }  // namespace
@@ -946,6 +1124,24 @@ extern "C" int iq_debug_pointnet_reps(const uint64_t* keep, const int32_t* cloud
     if (!scratch || scratch_bytes < need)
         return iq::fail(IQ_EWORKSPACE, "iq_debug_pointnet_reps: scratch %zu < %zu bytes", scratch_bytes, need);
     return launch_reps(keep, cloud_of, B, R, rep_out, reinterpret_cast<int32_t*>(scratch), iq::as_stream(stream));
+}
+
+// include/iq_debug.h: the slot map alone, from the two launchers the forward uses, with the caller's scratch for rep, table and counts
+extern "C" int iq_debug_pointnet_slots(const uint64_t* keep, const int32_t* cloud_of, int B, int nclouds, int R, int32_t* slots_out,
+                                       void* scratch, size_t scratch_bytes, iq_stream_t stream) {
+    IQ_REQUIRE(B >= 0 && nclouds >= 1, "iq_debug_pointnet_slots: B=%d nclouds=%d", B, nclouds);
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_REGIONS, "iq_debug_pointnet_slots: R=%d not in [1,%d]", R, IQ_MAX_REGIONS);
+    IQ_REQUIRE(cloud_of || nclouds == 1, "iq_debug_pointnet_slots: cloud_of required when nclouds > 1");
+    if (B == 0) return IQ_OK;
+    IQ_REQUIRE(keep && slots_out, "iq_debug_pointnet_slots: null pointer");
+    const size_t b = (size_t)B, nb = (b + kThreads - 1) / kThreads, need = (b + rep_slots(B) + nb) * sizeof(int32_t);
+    if (!scratch || scratch_bytes < need)
+        return iq::fail(IQ_EWORKSPACE, "iq_debug_pointnet_slots: scratch %zu < %zu bytes", scratch_bytes, need);
+    hipStream_t st = iq::as_stream(stream);
+    int32_t *rep = reinterpret_cast<int32_t*>(scratch), *table = rep + b;
+    int32_t* block_cnt = B > kOrderFusedMax ? table + rep_slots(B) : nullptr;
+    if (int rc = launch_reps(keep, cloud_of, B, R, rep, table, st, block_cnt)) return rc;
+    return launch_compact(rep, cloud_of, B, block_cnt, slots_out, slots_out + b, slots_out + 2 * b, slots_out + 3 * b, st);
 }
 
 extern "C" size_t iq_pointnet_wide_workspace_bytes(int B, int nclouds, int N, int R) {

@@ -72,8 +72,9 @@ struct ChainArgs {
     const unsigned short* w2_bf3;   // layer 2's, likewise (L3V = 3 needs both)
     float* out;                // (items,1024)
     int32_t* argrow;           // (items,1024) point index of the row that attains each column maximum, or null [ARGMAX trunk only]
-    const int32_t* dup_rep;    // (items) the first item of the batch with this item's cloud and kept regions, or null: every other
-                               // item is a copy of that one and leaves at once (launch_reps, pn_dup_copy_kernel)   [kFstn/kTrunk]
+    const int32_t* arg_row;    // (items) the row of argrow that an item writes, or null: its own                [ARGMAX trunk only]
+    const int32_t* n_dev;      // the live item count where only the device knows it (the distinct coalitions of a batch,
+                               // pn_compact kernels), or null: `items`.  A workgroup past it leaves at once       [kFstn/kTrunk]
     int N, R, items, nclouds, with_centre;
     int tail16;                  // last m-tile of an item on 16x16x4 MFMAs when it holds at most 16 rows (l3_tail16)
     int l3_single;               // twin kTwinChainL3Single: the 64-row bf16x3 kernel, one n-tile per pass (launch_chain; the 96-row kernel's reference)
@@ -514,7 +515,7 @@ __device__ __forceinline__ void chain_epilogue_fp32(const ChainArgs& a, int item
             const float v2 = __shfl_xor(v, 32);
             const int r2 = __shfl_xor(runarg[q], 32);
             const int r = (v2 > v || (v2 == v && r2 < runarg[q])) ? r2 : runarg[q];
-            if (lane < 32 && a.argrow) a.argrow[(size_t)item * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
+            if (lane < 32 && a.argrow) a.argrow[(size_t)(a.arg_row ? a.arg_row[item] : item) * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
         }
         v = fmaxf(v, __shfl_xor(v, 32));
         v += a.b3[n];
@@ -543,7 +544,7 @@ __device__ __forceinline__ void chain_epilogue_bf3(const ChainArgs& a, int item,
                 r = other ? r2 : r;
                 v = other ? v2 : v;
             }
-            if (lane < 16 && a.argrow) a.argrow[(size_t)item * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
+            if (lane < 16 && a.argrow) a.argrow[(size_t)(a.arg_row ? a.arg_row[item] : item) * kFeat + n] = (int)a.rows[(size_t)item * kRowCap + r];   // row -> point
         } else {
             v = fmaxf(v, __shfl_xor(v, 16));
             v = fmaxf(v, __shfl_xor(v, 32));
@@ -872,13 +873,13 @@ template <int CM, int L3V, bool ARGMAX = false>
 __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(ChainArgs a) {
     constexpr int MODE = CM >= kFstn64 ? CM - kFstn64 + kFstn : CM;
     static_assert(CM < kFstn64 || (L3V == 3 && !ARGMAX), "kFstn64 / kTrunk64: the 64-row twins of the product instantiations only");
+    if (MODE != kPrepool && a.n_dev && (int)blockIdx.x >= *a.n_dev) return;   // past the distinct coalitions: no entry in item_order
     const int item = a.item_order ? a.item_order[blockIdx.x] : blockIdx.x;
     int cloud;
     if (MODE == kPrepool) cloud = item / (a.R + a.with_centre);
     else cloud = a.cloud_of ? a.cloud_of[item] : (a.nclouds == 1 ? 0 : item);
 
     const int nrows = a.nrows[item] & 0xffff;
-    if (MODE != kPrepool && a.dup_rep && a.dup_rep[item] != item) return;   // a repeated coalition: pn_dup_copy_kernel fills its row
     if (nrows == 0) {  // empty region in the pre-pool: identity of max
         float* outp = a.out + (size_t)item * kFeat;
         for (int c = threadIdx.x; c < kFeat; c += kThreads) outp[c] = -INFINITY;

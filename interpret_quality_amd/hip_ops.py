@@ -969,3 +969,20 @@ def pointnet_reps(keep, cloud_of=None, num_regions=64, nclouds=1, scratch_bytes=
                                           else ctypes.c_void_p(0), b, int(nclouds), int(num_regions), _p(rep), _p(scratch), nbytes,
                                           _stream()), "iq_debug_pointnet_reps")
     return rep
+
+
+def pointnet_slots(keep, cloud_of=None, num_regions=64, nclouds=1):
+    """Diagnostic (iq_debug_pointnet_slots; no product path calls it): the slots the PointNet forward gives the distinct coalitions
+    of a batch.  keep (B,) int64-typed masks, cloud_of (B,) int32 or None -> (slot_of (B,), item_u (U,), cloud_u (U,) or None, U):
+    slot_of[i] = the rank of item i's representative among the representatives, item_u / cloud_u = the item and the cloud in
+    every slot."""
+    lib = _lib.load()
+    b = keep.shape[0]
+    out = torch.full((3 * b + 1,), -1, dtype=torch.int32, device=keep.device)
+    nbytes = 24 * max(b, 1) + 8
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=keep.device)
+    _lib.check(lib.iq_debug_pointnet_slots(_dev(keep, torch.int64, "keep"), _dev(cloud_of, torch.int32, "cloud_of") if cloud_of is not None
+                                           else ctypes.c_void_p(0), b, int(nclouds), int(num_regions), _p(out), _p(scratch), nbytes,
+                                           _stream()), "iq_debug_pointnet_slots")
+    u = int(out[3 * b].item()) if b else 0
+    return out[:b], out[b:b + u], (out[2 * b:2 * b + u] if cloud_of is not None else None), u
