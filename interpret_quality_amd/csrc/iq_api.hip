@@ -205,10 +205,10 @@ extern "C" int iq_debug_mfma_sustained_shape(int shape, double seconds, float* s
     int rc = IQ_OK;
     for (int pass = 0; pass < 2 && rc == IQ_OK; ++pass) {        // pass 0 calibrates the iteration count for ~`seconds`
         (void)hipEventRecord(e0, st);
-        if (shape == 16) hipLaunchKernelGGL(mfma_sustained16_kernel, dim3(grid), dim3(256), 0, st, scratch, iters, 12345 + pass);
-        else hipLaunchKernelGGL(mfma_sustained_kernel, dim3(grid), dim3(256), 0, st, scratch, iters, 12345 + pass);
+        if (shape == 16) rc = iq::launch("mfma_sustained16_kernel", mfma_sustained16_kernel, dim3(grid), dim3(256), 0, st, scratch, iters, 12345 + pass);
+        else rc = iq::launch("mfma_sustained_kernel", mfma_sustained_kernel, dim3(grid), dim3(256), 0, st, scratch, iters, 12345 + pass);
         (void)hipEventRecord(e1, st);
-        if ((rc = iq::check_launch("mfma_sustained_kernel"))) break;
+        if (rc) break;
         if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = iq::fail(IQ_ELAUNCH, "event timing failed");
         if (pass == 0) iters = (int)std::min(2.0e9, std::max(1000.0, iters * seconds * 1e3 / std::max(ms, 1e-3f)));
     }

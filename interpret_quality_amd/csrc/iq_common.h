@@ -1,4 +1,12 @@
 // Shared host-side helpers for libiq_hip.so (gfx950 only).
+//
+// Launch convention: every kernel goes out through iq::launch, which checks it under the kernel's own name, so after a launch
+// that failed nothing more is started.  Host code writes IQ_LAUNCH(kernel, grid, block, lds, stream, args...) - an instantiation
+// with a comma in parentheses, (k<1, 2>) - and IQ_TRY(f(...)) for any call that returns a status; both return the status from
+// the enclosing function, as IQ_REQUIRE does.  Where no early return is possible (a generic lambda, a loop that must finish
+// its bookkeeping) iq::launch("name", ...) is called directly and its status passed on.  The arguments are converted to the
+// kernel's parameter types, so a bare nullptr or 0 is fine.  HIP runtime calls (memset, copy, synchronise) go through
+// IQ_TRY(iq::hip_ok(call, "what")).  tests/test_cabi_cpu.py keeps the spelling from eroding.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +32,19 @@ inline int fail(int code, const char* fmt, ...) {
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(IQ_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return IQ_OK;
+}
+
+// One kernel launch and its check: a launch error comes back under the kernel's own name, and nothing is launched after it.
+template <class... P, class... A>
+inline int launch(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A&&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+    return check_launch(name);
+}
+
+// A HIP runtime call (memset, copy, synchronise) and its check, with HIP's own error string.
+inline int hip_ok(hipError_t e, const char* what) {
     if (e != hipSuccess) return fail(IQ_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
     return IQ_OK;
 }
@@ -128,3 +149,5 @@ __device__ inline int xcd_cloud(int block, int wgs_per_cloud, int B) {
     do {                      \
         if (!(cond)) return iq::fail(IQ_EINVAL, __VA_ARGS__); \
     } while (0)
+#define IQ_TRY(expr)  do { if (int rc_ = (expr)) return rc_; } while (0)
+#define IQ_LAUNCH(kernel, ...) IQ_TRY(iq::launch(#kernel, kernel, __VA_ARGS__))

@@ -313,13 +313,12 @@ extern "C" int iq_knn(const float* x, int32_t* idx, void* tmp, size_t tmp_bytes,
     int32_t* roff = c.take<int32_t>((size_t)B + 1);
     int32_t* nkept = c.take<int32_t>((size_t)B);
     int32_t* ncopy = c.take<int32_t>((size_t)B);
-    hipLaunchKernelGGL(dg_dense_layout_kernel, dim3((r + 256) / 256), dim3(256), 0, st, roff, nkept, ncopy, row_cloud,
-                       (float*)nullptr, B, N, N);
+    IQ_LAUNCH(dg_dense_layout_kernel, dim3((r + 256) / 256), dim3(256), 0, st, roff, nkept, ncopy, row_cloud, nullptr, B, N, N);
     const Ragged rg{roff, nkept, ncopy, row_cloud, nullptr};
     const float* src = x;
     int ld = C, cpad = C;
     if (C == 3) {
-        hipLaunchKernelGGL(pad_xyz_kernel, dim3((r + 255) / 256), dim3(256), 0, st, x, x0, B, N, N);
+        IQ_LAUNCH(pad_xyz_kernel, dim3((r + 255) / 256), dim3(256), 0, st, x, x0, B, N, N);
         src = x0; ld = 8; cpad = 8;
     }
     // room for the bf16x3 operand image behind the other scratch: the distances of the feature-space graphs run on the bf16 matrix
@@ -327,11 +326,10 @@ extern "C" int iq_knn(const float* x, int32_t* idx, void* tmp, size_t tmp_bytes,
     const bool fp32 = iq::twin() == iq::kTwinKnnFp32Mfma || iq::twin() == iq::kTwinKnnFp32Rank;
     unsigned char* planes = nullptr;
     if ((C == 64 || C == 128) && !fp32 && tmp_bytes >= c.bytes() + r * C * 6) planes = c.take<unsigned char>(r * C * 6);
-    hipLaunchKernelGGL(rownorm_kernel, dim3((r + 63) / 64), dim3(kThreads), 0, st, src, ld, C, xx, rg, B, planes, (int)(r / 32));
-    int rc = launch_knn(src, ld, cpad, xx, i16, near_tie, B, N, (int)r, rg, st, false, planes, (int)(r / 32));
-    if (rc) return rc;
-    hipLaunchKernelGGL(widen_idx_kernel, dim3((r * kK + 255) / 256), dim3(256), 0, st, i16, idx, r * kK);
-    return iq::check_launch("iq_knn");
+    IQ_LAUNCH(rownorm_kernel, dim3((r + 63) / 64), dim3(kThreads), 0, st, src, ld, C, xx, rg, B, planes, (int)(r / 32));
+    IQ_TRY(launch_knn(src, ld, cpad, xx, i16, near_tie, B, N, (int)r, rg, st, false, planes, (int)(r / 32)));
+    IQ_LAUNCH(widen_idx_kernel, dim3((r * kK + 255) / 256), dim3(256), 0, st, i16, idx, r * kK);
+    return IQ_OK;
 }
 
 namespace {
@@ -353,7 +351,6 @@ int run_network(const iq_dgcnn_weights* w, const WsD& s, float* logits, int B, i
                 hipStream_t st, const WalkCtx* walk = nullptr) {
     const Ragged rg{s.roff, s.nkept, s.ncopy, s.row_cloud, s.row_w};
     const int32_t* live = s.roff + B;
-    int rc;
     const float* src = s.x0;
     int ld = 8, cin = 8, creal = 3, col = 0;
     const int Np = (N + 31) / 32 * 32;
@@ -365,10 +362,9 @@ int run_network(const iq_dgcnn_weights* w, const WsD& s, float* logits, int B, i
         IQ_REQUIRE(w->pq[l].cin == cin, "iq_dgcnn: layer %d expects %d inputs, got %d", l, cin, w->pq[l].cin);
         if (l == 0 && walk) {
             iq::ProfileSpan span(iq::kSlotPrepool, st);
-            hipLaunchKernelGGL((walk->W ? dg_walk_kernel<true> : dg_walk_kernel<false>), dim3((Np + 63) / 64, B), dim3(64), 0, st,
-                               walk->sorted, walk->src, walk->region_id, walk->keep, walk->cloud_of, s.idx, rg, N, Np, walk->Nsl,
-                               walk->nclouds, fused ? 1 : 0, walk->R, walk->W);
-            if ((rc = iq::check_launch("dg_walk_kernel"))) return rc;
+            IQ_LAUNCH((walk->W ? dg_walk_kernel<true> : dg_walk_kernel<false>), dim3((Np + 63) / 64, B), dim3(64), 0, st,
+                      walk->sorted, walk->src, walk->region_id, walk->keep, walk->cloud_of, s.idx, rg, N, Np, walk->Nsl,
+                      walk->nclouds, fused ? 1 : 0, walk->R, walk->W);
         } else if (l == 0 || !fixed_graph) {
             iq::ProfileSpan span(iq::kSlotPrepool, st);
             // feature-space graphs of the fused path: distances on the bf16 matrix pipe, the operand image in the upper half of the
@@ -376,12 +372,12 @@ int run_network(const iq_dgcnn_weights* w, const WsD& s, float* logits, int B, i
             // kTwinKnnFp32Rank: the fp32 MFMA (A/B, tests)
             const bool bf3 = fused && (cin == 64 || cin == 128) && iq::twin() != iq::kTwinKnnFp32Mfma && iq::twin() != iq::kTwinKnnFp32Rank;
             unsigned char* planes = bf3 ? reinterpret_cast<unsigned char*>(s.pq) + (size_t)rows * 1024 : nullptr;
-            hipLaunchKernelGGL(rownorm_kernel, dim3((rows + 63) / 64), dim3(kThreads), 0, st, src, ld, creal, s.xx, rg, B, planes, rows / 32);
-            if ((rc = launch_knn(src, ld, cin, s.xx, s.idx, s.near_tie, B, N, rows, rg, st, fused, planes, rows / 32))) return rc;
+            IQ_LAUNCH(rownorm_kernel, dim3((rows + 63) / 64), dim3(kThreads), 0, st, src, ld, creal, s.xx, rg, B, planes, rows / 32);
+            IQ_TRY(launch_knn(src, ld, cin, s.xx, s.idx, s.near_tie, B, N, rows, rg, st, fused, planes, rows / 32));
         }
         {
             iq::ProfileSpan span(iq::kSlotFstn, st);
-            if ((rc = launch_edgeconv(fused, src, ld, w->pq[l], s.idx, s.pq, s.xc + col, 512, rg, B, Np, rows, live, st))) return rc;
+            IQ_TRY(launch_edgeconv(fused, src, ld, w->pq[l], s.idx, s.pq, s.xc + col, 512, rg, B, Np, rows, live, st));
         }
         src = s.xc + col; ld = 512; cin = co; creal = co; col += co;
     }
@@ -397,13 +393,12 @@ int run_network(const iq_dgcnn_weights* w, const WsD& s, float* logits, int B, i
                 work = 2.0 * 512.0 * 1024.0 * (double)((n + 127) / 128 * 128);
         }
         iq::ProfileSpan dom(iq::kSlotDominant, st, work);
-        if ((rc = iq::launch_linear_pool(s.xc, 512, w->conv5, s.h, rows, 2, s.row_w, st, live, w->conv5_bf3))) return rc;
-        hipLaunchKernelGGL(pool_reduce_kernel, dim3(1024 / kThreads, B), dim3(kThreads), 0, st, s.h, s.g, rg, N, 1024);
-        if ((rc = iq::check_launch("pool_reduce_kernel"))) return rc;
+        IQ_TRY(iq::launch_linear_pool(s.xc, 512, w->conv5, s.h, rows, 2, s.row_w, st, live, w->conv5_bf3));
+        IQ_LAUNCH(pool_reduce_kernel, dim3(1024 / kThreads, B), dim3(kThreads), 0, st, s.h, s.g, rg, N, 1024);
     }
-    if ((rc = iq::launch_linear(s.g, 2048, w->fc1, s.f1, 512, B, 2, st))) return rc;
-    if ((rc = iq::launch_linear(s.f1, 512, w->fc2, s.f2, 256, B, 2, st))) return rc;
-    if ((rc = iq::launch_linear(s.f2, 256, w->fc3, logits, w->fc3.cout, B, 0, st))) return rc;
+    IQ_TRY(iq::launch_linear(s.g, 2048, w->fc1, s.f1, 512, B, 2, st));
+    IQ_TRY(iq::launch_linear(s.f1, 512, w->fc2, s.f2, 256, B, 2, st));
+    IQ_TRY(iq::launch_linear(s.f2, 256, w->fc3, logits, w->fc3.cout, B, 0, st));
     return IQ_OK;
 }
 
@@ -422,12 +417,10 @@ extern "C" int iq_dgcnn_forward(const iq_dgcnn_weights* w, const float* xyz, flo
     hipStream_t st = iq::as_stream(stream);
     const int Np = (N + 31) / 32 * 32;  // rows N..Np-1 of every cloud are dead padding
     const int rows = B * Np;
-    int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
-    hipLaunchKernelGGL(dg_dense_layout_kernel, dim3((rows + 256) / 256), dim3(256), 0, st, s.roff, s.nkept, s.ncopy,
-                       s.row_cloud, s.row_w, B, N, Np);
-    hipLaunchKernelGGL(pad_xyz_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, xyz, s.x0, B, N, Np);
-    if ((rc = iq::check_launch("pad_xyz_kernel"))) return rc;
+    IQ_LAUNCH(dg_dense_layout_kernel, dim3((rows + 256) / 256), dim3(256), 0, st, s.roff, s.nkept, s.ncopy,
+              s.row_cloud, s.row_w, B, N, Np);
+    IQ_LAUNCH(pad_xyz_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, xyz, s.x0, B, N, Np);
     return run_network(w, s, logits, B, N, rows, fixed_graph, st);
 }
 
@@ -449,7 +442,6 @@ int dgcnn_coalitions(const char* name, const iq_dgcnn_weights* w, const float* c
         return iq::fail(IQ_EWORKSPACE, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
     WsD s = carve_d(workspace, B, N);
     hipStream_t st = iq::as_stream(stream);
-    int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
     // Layer-1 graph from the source clouds' sorted neighbour lists when a few source clouds serve many coalitions.  The
     // tables are carved from the P/Q buffer, which the fused EdgeConv path does not touch (twin kTwinKnnCompact: knn_kernel<8>).
@@ -466,20 +458,18 @@ int dgcnn_coalitions(const char* name, const iq_dgcnn_weights* w, const float* c
         use_walk = N <= kWalkMaxN && (long long)nclouds * 8 <= B && fused_path(w, N) && iq::twin() != iq::kTwinKnnCompact &&
                    c.bytes() <= (size_t)B * Np * 256 * 4;     // the lower half: the upper one holds the kNN operand image (run_network)
         if (use_walk) {
-            hipLaunchKernelGGL(sl_rows_kernel, dim3((Nsp + 255) / 256, nclouds), dim3(256), 0, st, clouds, centers, xs, xxs, N, Nsp);
-            hipLaunchKernelGGL(sl_dist_kernel<0>, dim3(Nsp / 32, nclouds), dim3(64), 0, st, xs, xxs, dmat, Nsp);
-            hipLaunchKernelGGL(sl_sort_kernel, dim3(N + 1, nclouds), dim3(256), 0, st, dmat, sorted, N, Nsp, Nsl);
-            if ((rc = iq::check_launch("sl_sort_kernel"))) return rc;
+            IQ_LAUNCH(sl_rows_kernel, dim3((Nsp + 255) / 256, nclouds), dim3(256), 0, st, clouds, centers, xs, xxs, N, Nsp);
+            IQ_LAUNCH(sl_dist_kernel<0>, dim3(Nsp / 32, nclouds), dim3(64), 0, st, xs, xxs, dmat, Nsp);
+            IQ_LAUNCH(sl_sort_kernel, dim3(N + 1, nclouds), dim3(256), 0, st, dmat, sorted, N, Nsp, Nsl);
             walk = WalkCtx{sorted, srcrow, region_id, keep, cloud_of, nclouds, Nsl, R, W};
         }
     }
-    hipLaunchKernelGGL((W ? dg_count_kernel<true> : dg_count_kernel<false>), dim3(B), dim3(64), 0, st, region_id, keep, cloud_of,
-                       s.nkept, s.ncopy, s.dpad, N, nclouds, R, W);
-    hipLaunchKernelGGL(dg_scan_kernel, dim3(1), dim3(1024), 0, st, s.dpad, s.roff, B);
-    hipLaunchKernelGGL((W ? dg_compact_kernel<true> : dg_compact_kernel<false>), dim3(B), dim3(64), 0, st, clouds, centers, region_id,
-                       keep, cloud_of, s.roff, s.nkept, s.ncopy, s.x0, s.row_cloud, s.row_w, N, nclouds,
-                       use_walk ? const_cast<int16_t*>(walk.src) : (int16_t*)nullptr, Np, R, W);
-    if ((rc = iq::check_launch("dg_compact_kernel"))) return rc;
+    IQ_LAUNCH((W ? dg_count_kernel<true> : dg_count_kernel<false>), dim3(B), dim3(64), 0, st, region_id, keep, cloud_of,
+              s.nkept, s.ncopy, s.dpad, N, nclouds, R, W);
+    IQ_LAUNCH(dg_scan_kernel, dim3(1), dim3(1024), 0, st, s.dpad, s.roff, B);
+    IQ_LAUNCH((W ? dg_compact_kernel<true> : dg_compact_kernel<false>), dim3(B), dim3(64), 0, st, clouds, centers, region_id,
+              keep, cloud_of, s.roff, s.nkept, s.ncopy, s.x0, s.row_cloud, s.row_w, N, nclouds,
+              use_walk ? const_cast<int16_t*>(walk.src) : nullptr, Np, R, W);
     return run_network(w, s, logits, B, N, B * Np, fixed_graph, st, use_walk ? &walk : nullptr);
 }
 

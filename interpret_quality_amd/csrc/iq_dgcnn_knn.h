@@ -548,10 +548,10 @@ int launch_knn(const float* x, int ldx, int C, const float* xx, int16_t* idx, in
     else if (C == 64) { knn = knn_feature_kernel<64>(refine, planes != nullptr); rerank = knn_refine_kernel<64>; }
     else if (C == 128) { knn = knn_feature_kernel<128>(refine, planes != nullptr); rerank = knn_refine_kernel<128>; }
     else return iq::fail(IQ_EUNSUPPORTED, "knn: C=%d has no kernel instantiation (8, 64, 128)", C);
-    hipLaunchKernelGGL(knn, dim3((unsigned)((B + 7) / 8 * 8 * tiles)), dim3(64), 0, st, x, ldx, xx, idx, near_tie, rg, B, tiles, as_addr,
-                       planes, term_tiles);
-    if (refine) hipLaunchKernelGGL(rerank, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, x, ldx, near_tie, idx, rg, B, as_addr);
-    return iq::check_launch("knn_kernel");
+    IQ_TRY(iq::launch("knn_kernel", knn, dim3((unsigned)((B + 7) / 8 * 8 * tiles)), dim3(64), 0, st, x, ldx, xx, idx, near_tie, rg, B, tiles,
+                      as_addr, planes, term_tiles));
+    if (refine) IQ_TRY(iq::launch("knn_refine_kernel", rerank, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, x, ldx, near_tie, idx, rg, B, as_addr));
+    return IQ_OK;
 }
 
 }  // namespace

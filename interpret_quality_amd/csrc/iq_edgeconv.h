@@ -332,21 +332,21 @@ int launch_edgeconv(bool fused, const float* x, int ldx, const iq_dense_layer& L
     if (fused) {
         // the whole layer in one kernel: co / 16 workgroups per cloud
         const auto kernel = L.cin == 8 ? edge_fused_kernel<1> : L.cin == 64 ? edge_fused_kernel<8> : edge_fused_kernel<16>;
-        hipLaunchKernelGGL(kernel, grid(co / 16), dim3(kGlThreads), 0, st, x, ldx, L.w, L.b, co, idx, out, ldo, rg, B, co / 16);
-        return iq::check_launch("edge_fused_kernel");
+        IQ_TRY(iq::launch("edge_fused_kernel", kernel, grid(co / 16), dim3(kGlThreads), 0, st, x, ldx, L.w, L.b, co, idx, out, ldo, rg, B, co / 16));
+        return IQ_OK;
     }
-    if (int rc = iq::launch_linear(x, ldx, L, pq, 2 * co, rows, 0, st, live)) return rc;
+    IQ_TRY(iq::launch_linear(x, ldx, L, pq, 2 * co, rows, 0, st, live));
     if (Np <= kGlMaxRows && co % 16 == 0 && iq::twin() != iq::kTwinEdgeGemmL2) {
         // P slices through LDS: co / 16 workgroups per cloud (the surplus ones of small clouds exit at once)
-        hipLaunchKernelGGL(gather_lds_kernel, grid(co / 16), dim3(kGlThreads), 0, st, pq, co, idx, out, ldo, rg, B, co / 16);
+        IQ_LAUNCH(gather_lds_kernel, grid(co / 16), dim3(kGlThreads), 0, st, pq, co, idx, out, ldo, rg, B, co / 16);
     } else {
         // clouds of more than 1024 rows (or twin kTwinEdgeGemmL2): straight from L2.  Grid sized for the largest cloud (Np rows);
         // workgroups past a cloud's live row count exit at once
         const int pts_per_wg = kThreads / (co / 4);
         const int wgs_per_cloud = (Np + pts_per_wg - 1) / pts_per_wg;
-        hipLaunchKernelGGL(gather_max_kernel, grid(wgs_per_cloud), dim3(kThreads), 0, st, pq, co, idx, out, ldo, rg, B, wgs_per_cloud);
+        IQ_LAUNCH(gather_max_kernel, grid(wgs_per_cloud), dim3(kThreads), 0, st, pq, co, idx, out, ldo, rg, B, wgs_per_cloud);
     }
-    return iq::check_launch("gather_max_kernel");
+    return IQ_OK;
 }
 
 }  // namespace

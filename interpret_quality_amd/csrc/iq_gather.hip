@@ -149,14 +149,13 @@ extern "C" int iq_index_points(const float* points, const int32_t* idx, float* o
     hipStream_t st = iq::as_stream(stream);
     if (C % 4 == 0 && aligned16(points)) {
         const unsigned t4 = (unsigned)(total / 4);
-        hipLaunchKernelGGL(gather_rows4_kernel, dim3((t4 + kThreads - 1) / kThreads), dim3(kThreads), 0, st, points, idx, out,
-                           N, M, C, t4);
-        return iq::check_launch("gather_rows4_kernel");
+        IQ_LAUNCH(gather_rows4_kernel, dim3((t4 + kThreads - 1) / kThreads), dim3(kThreads), 0, st, points, idx, out, N, M, C, t4);
+        return IQ_OK;
     }
     const RowGather g{nullptr, nullptr, points, idx, out, 0, C, 0, N, 1, M, B};
     const unsigned quads = (unsigned)((total + 3) / 4);
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((quads + kThreads - 1) / kThreads), dim3(kThreads), 0, st, g, (unsigned)total);
-    return iq::check_launch("gather_rows_kernel");
+    IQ_LAUNCH(gather_rows_kernel, dim3((quads + kThreads - 1) / kThreads), dim3(kThreads), 0, st, g, (unsigned)total);
+    return IQ_OK;
 }
 
 extern "C" int iq_group_points(const float* xyz, const float* points, const float* new_xyz, const int32_t* idx, float* out,
@@ -171,9 +170,9 @@ extern "C" int iq_group_points(const float* xyz, const float* points, const floa
     const size_t total = (size_t)B * S * K * (3 + D);
     IQ_REQUIRE(total <= kMaxElems, "iq_group_points: output of %zu floats exceeds 2^31", total);
     const unsigned quads = (unsigned)((total + 3) / 4);
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((quads + kThreads - 1) / kThreads), dim3(kThreads), 0, iq::as_stream(stream), g,
-                       (unsigned)total);
-    return iq::check_launch("gather_rows_kernel");
+    IQ_LAUNCH(gather_rows_kernel, dim3((quads + kThreads - 1) / kThreads), dim3(kThreads), 0, iq::as_stream(stream), g,
+              (unsigned)total);
+    return IQ_OK;
 }
 
 extern "C" int iq_edgeconv_gather(const float* x, const int32_t* idx, float* out, int channel_first, int B, int N, int C, int k,
@@ -185,7 +184,7 @@ extern "C" int iq_edgeconv_gather(const float* x, const int32_t* idx, float* out
     IQ_REQUIRE(aligned16(out), "iq_edgeconv_gather: out must be 16-byte aligned");
     IQ_REQUIRE(total <= kMaxElems, "iq_edgeconv_gather: output of %zu floats exceeds 2^31", total);
     const unsigned quads = (unsigned)((total + 3) / 4);
-    hipLaunchKernelGGL(edgeconv_gather_kernel, dim3((quads + kThreads - 1) / kThreads), dim3(kThreads), 0, iq::as_stream(stream),
-                       x, idx, out, channel_first ? 1 : 0, B, N, C, k, (unsigned)total);
-    return iq::check_launch("edgeconv_gather_kernel");
+    IQ_LAUNCH(edgeconv_gather_kernel, dim3((quads + kThreads - 1) / kThreads), dim3(kThreads), 0, iq::as_stream(stream),
+              x, idx, out, channel_first ? 1 : 0, B, N, C, k, (unsigned)total);
+    return IQ_OK;
 }

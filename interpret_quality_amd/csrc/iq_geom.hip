@@ -306,9 +306,8 @@ extern "C" int iq_region_assign(const float* cloud, const int32_t* fps_idx, int3
                                 int N, int R, iq_stream_t stream) {
     IQ_REQUIRE(cloud && fps_idx && region_id, "iq_region_assign: null pointer");
     IQ_REQUIRE(N > 0 && R >= 1 && R <= IQ_MAX_REGIONS, "iq_region_assign: N=%d R=%d", N, R);
-    hipLaunchKernelGGL(region_assign_kernel, dim3((N + 255) / 256), dim3(256), 0, iq::as_stream(stream),
-                       cloud, fps_idx, region_id, N, R);
-    return iq::check_launch("region_assign_kernel");
+    IQ_LAUNCH(region_assign_kernel, dim3((N + 255) / 256), dim3(256), 0, iq::as_stream(stream), cloud, fps_idx, region_id, N, R);
+    return IQ_OK;
 }
 
 int iq::launch_fps(const float* xyz, int32_t* idx, int32_t* n_unique, int B, int N, int S, hipStream_t st) {
@@ -317,18 +316,18 @@ int iq::launch_fps(const float* xyz, int32_t* idx, int32_t* n_unique, int B, int
     IQ_REQUIRE(xyz && idx, "iq_fps: null pointer");
     // many clouds of at most 1024 points: one wave per cloud (points in registers); few or larger clouds: one workgroup per cloud
     if (B >= 64 && N <= 1024) {
-        if (N <= 128) hipLaunchKernelGGL(fps_wave_kernel<2>, dim3(B), dim3(64), 0, st, xyz, idx, n_unique, N, S);
-        else if (N <= 512) hipLaunchKernelGGL(fps_wave_kernel<8>, dim3(B), dim3(64), 0, st, xyz, idx, n_unique, N, S);
-        else hipLaunchKernelGGL(fps_wave_kernel<16>, dim3(B), dim3(64), 0, st, xyz, idx, n_unique, N, S);
-        return iq::check_launch("fps_wave_kernel");
+        if (N <= 128) IQ_LAUNCH(fps_wave_kernel<2>, dim3(B), dim3(64), 0, st, xyz, idx, n_unique, N, S);
+        else if (N <= 512) IQ_LAUNCH(fps_wave_kernel<8>, dim3(B), dim3(64), 0, st, xyz, idx, n_unique, N, S);
+        else IQ_LAUNCH(fps_wave_kernel<16>, dim3(B), dim3(64), 0, st, xyz, idx, n_unique, N, S);
+        return IQ_OK;
     }
     const size_t lds = (size_t)N * 4 * sizeof(float);
     if (lds > 48 * 1024) {  // above the default dynamic-LDS limit (N > 3072): opt in, up to 128 KB at N = 8192
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(fps_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return iq::fail(IQ_ELAUNCH, "iq_fps: cannot reserve %zu bytes of LDS for N=%d", lds, N);
     }
-    hipLaunchKernelGGL(fps_kernel, dim3(B), dim3(kFpsThreads), lds, st, xyz, idx, n_unique, N, S);
-    return iq::check_launch("fps_kernel");
+    IQ_LAUNCH(fps_kernel, dim3(B), dim3(kFpsThreads), lds, st, xyz, idx, n_unique, N, S);
+    return IQ_OK;
 }
 
 extern "C" int iq_fps(const float* xyz, int32_t* idx, int B, int N, int S, iq_stream_t stream) {
@@ -346,9 +345,9 @@ extern "C" int iq_knn_point(const float* xyz, const float* new_xyz, int K, int32
     IQ_REQUIRE((size_t)B * S <= 0x7fffffffu, "iq_knn_point: B*S=%zu queries", (size_t)B * S);
     int P = 2;
     while (P < N) P <<= 1;
-    hipLaunchKernelGGL(knn_point_kernel, dim3((unsigned)(B * S)), dim3(64), (size_t)P * 8, iq::as_stream(stream), xyz, new_xyz, idx,
-                       N, S, K, P);
-    return iq::check_launch("knn_point_kernel");
+    IQ_LAUNCH(knn_point_kernel, dim3((unsigned)(B * S)), dim3(64), (size_t)P * 8, iq::as_stream(stream), xyz, new_xyz, idx,
+              N, S, K, P);
+    return IQ_OK;
 }
 
 extern "C" int iq_sort_neighbours(const float* q, const float* keys, int32_t* idx, int B, int N, int S, int C, int k,
@@ -359,9 +358,9 @@ extern "C" int iq_sort_neighbours(const float* q, const float* keys, int32_t* id
     if (rows == 0) return IQ_OK;
     IQ_REQUIRE(q && keys && idx, "iq_sort_neighbours: null pointer");
     IQ_REQUIRE(rows <= 0x7ffffff0u, "iq_sort_neighbours: B*S=%zu rows", rows);
-    hipLaunchKernelGGL(sort_neighbours_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, iq::as_stream(stream), q, keys, idx,
-                       (int)rows, N, S, C, k);
-    return iq::check_launch("sort_neighbours_kernel");
+    IQ_LAUNCH(sort_neighbours_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, iq::as_stream(stream), q, keys, idx,
+              (int)rows, N, S, C, k);
+    return IQ_OK;
 }
 
 extern "C" int iq_density(const float* xyz, double bandwidth, float* out, int B, int N, iq_stream_t stream) {
@@ -370,6 +369,6 @@ extern "C" int iq_density(const float* xyz, double bandwidth, float* out, int B,
     if (B == 0) return IQ_OK;
     IQ_REQUIRE(xyz && out, "iq_density: null pointer");
     const float c0 = (float)(2.0 * bandwidth * bandwidth), c1 = (float)(2.5 * bandwidth);
-    hipLaunchKernelGGL(density_kernel, dim3((N + 255) / 256, B), dim3(256), 0, iq::as_stream(stream), xyz, c0, c1, out, N);
-    return iq::check_launch("density_kernel");
+    IQ_LAUNCH(density_kernel, dim3((N + 255) / 256, B), dim3(256), 0, iq::as_stream(stream), xyz, c0, c1, out, N);
+    return IQ_OK;
 }

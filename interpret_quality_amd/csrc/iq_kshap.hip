@@ -236,9 +236,9 @@ extern "C" int iq_kshap_keep_masks(const int32_t* orders, const int32_t* sizes, 
     IQ_REQUIRE(S >= 0 && S <= (1 << 29), "iq_kshap_keep_masks: S=%d", S);
     if (S == 0) return IQ_OK;
     IQ_REQUIRE(orders && sizes && keep && status, "iq_kshap_keep_masks: null pointer");
-    hipLaunchKernelGGL(kshap_keep_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, iq::as_stream(stream), orders, sizes,
-                       reinterpret_cast<unsigned long long*>(keep), S, n, paired ? 1 : 0, status);
-    return iq::check_launch("kshap_keep_kernel");
+    IQ_LAUNCH(kshap_keep_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, iq::as_stream(stream), orders, sizes,
+              reinterpret_cast<unsigned long long*>(keep), S, n, paired ? 1 : 0, status);
+    return IQ_OK;
 }
 
 extern "C" int iq_kshap_accum(const uint64_t* keep, const float* v, const double* v0, const double* weights, int M, int n, int G,
@@ -252,26 +252,22 @@ extern "C" int iq_kshap_accum(const uint64_t* keep, const float* v, const double
     hipStream_t st = iq::as_stream(stream);
     const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
     if (weights)
-        hipLaunchKernelGGL(kshap_gram_kernel<double>, dim3(ch.count), dim3(kThreads), 0, st, k, weights, M, n, ch.tiles_per,
-                           static_cast<double*>(s.partA), s.partW);
+        IQ_LAUNCH(kshap_gram_kernel<double>, dim3(ch.count), dim3(kThreads), 0, st, k, weights, M, n, ch.tiles_per,
+                  static_cast<double*>(s.partA), s.partW);
     else
-        hipLaunchKernelGGL(kshap_gram_kernel<unsigned long long>, dim3(ch.count), dim3(kThreads), 0, st, k, (const double*)nullptr, M, n,
-                           ch.tiles_per, static_cast<unsigned long long*>(s.partA), (double*)nullptr);
-    int rc = iq::check_launch("kshap_gram_kernel");
-    if (rc) return rc;
-    hipLaunchKernelGGL(kshap_moment_kernel, dim3(ch.count, G), dim3(kThreads), 0, st, k, v, v0, weights, M, n, ch.tiles_per, s.partB);
-    rc = iq::check_launch("kshap_moment_kernel");
-    if (rc) return rc;
+        IQ_LAUNCH(kshap_gram_kernel<unsigned long long>, dim3(ch.count), dim3(kThreads), 0, st, k, nullptr, M, n,
+                  ch.tiles_per, static_cast<unsigned long long*>(s.partA), nullptr);
+    IQ_LAUNCH(kshap_moment_kernel, dim3(ch.count, G), dim3(kThreads), 0, st, k, v, v0, weights, M, n, ch.tiles_per, s.partB);
     const int outputs = n * n + G * n + 1;
-    hipLaunchKernelGGL(kshap_fold_kernel, dim3((outputs + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (const void*)s.partA,
-                       (const double*)s.partB, (const double*)s.partW, weights ? 1 : 0, M, n, G, ch.count, A, b, wsum);
-    return iq::check_launch("kshap_fold_kernel");
+    IQ_LAUNCH(kshap_fold_kernel, dim3((outputs + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (const void*)s.partA,
+              (const double*)s.partB, (const double*)s.partW, weights ? 1 : 0, M, n, G, ch.count, A, b, wsum);
+    return IQ_OK;
 }
 
 extern "C" int iq_kshap_solve(const double* A, const double* b, const double* delta, double* phi, int32_t* status, int n, int G,
                               iq_stream_t stream) {
     IQ_REQUIRE(n >= 2 && n <= kMaxN && G >= 1 && G <= 65535, "iq_kshap_solve: n=%d, G=%d (2 <= n <= %d, 1 <= G <= 65535)", n, G, kMaxN);
     IQ_REQUIRE(A && b && delta && phi && status, "iq_kshap_solve: null pointer");
-    hipLaunchKernelGGL(kshap_solve_kernel, dim3(1), dim3(kThreads), 0, iq::as_stream(stream), A, b, delta, phi, status, n, G);
-    return iq::check_launch("kshap_solve_kernel");
+    IQ_LAUNCH(kshap_solve_kernel, dim3(1), dim3(kThreads), 0, iq::as_stream(stream), A, b, delta, phi, status, n, G);
+    return IQ_OK;
 }

@@ -97,10 +97,11 @@ __global__ __launch_bounds__(64 * kSamplesPerWg) void kshap_draw_counter_kernel(
 }
 
 template <int K>
-void launch(unsigned k0, unsigned k1, long long first, int S, int R, const double* cdf, int paired, uint64_t* keep, int32_t* sizes,
+int launch(unsigned k0, unsigned k1, long long first, int S, int R, const double* cdf, int paired, uint64_t* keep, int32_t* sizes,
             hipStream_t st) {
-    hipLaunchKernelGGL(kshap_draw_counter_kernel<K>, dim3((unsigned)((S + kSamplesPerWg - 1) / kSamplesPerWg)), dim3(64 * kSamplesPerWg), 0,
-                       st, k0, k1, first, S, R, iq::keep_words(R), cdf, paired ? 1 : 0, reinterpret_cast<unsigned long long*>(keep), sizes);
+    IQ_LAUNCH(kshap_draw_counter_kernel<K>, dim3((unsigned)((S + kSamplesPerWg - 1) / kSamplesPerWg)), dim3(64 * kSamplesPerWg), 0,
+              st, k0, k1, first, S, R, iq::keep_words(R), cdf, paired ? 1 : 0, reinterpret_cast<unsigned long long*>(keep), sizes);
+    return IQ_OK;
 }
 
 }  // namespace
@@ -116,10 +117,9 @@ extern "C" int iq_kshap_draw_counter(uint64_t seed, uint64_t stream, int64_t fir
     const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(stream & 0xffffffffull);
     hipStream_t st = iq::as_stream(queue);
     const int W = iq::keep_words(R);
-    if (W <= 1) launch<1>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
-    else if (W <= 2) launch<2>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
-    else if (W <= 4) launch<4>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
-    else if (W <= 8) launch<8>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
-    else launch<16>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
-    return iq::check_launch("kshap_draw_counter_kernel");
+    if (W <= 1) return launch<1>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
+    else if (W <= 2) return launch<2>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
+    else if (W <= 4) return launch<4>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
+    else if (W <= 8) return launch<8>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
+    else return launch<16>(k0, k1, first, S, R, cdf, paired, keep, sizes, st);
 }

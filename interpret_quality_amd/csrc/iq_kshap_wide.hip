@@ -139,10 +139,10 @@ extern "C" int iq_kshap_keep_masks_wide(const int32_t* orders, const int32_t* si
     IQ_REQUIRE(S >= 0 && S <= (1 << 29), "iq_kshap_keep_masks_wide: S=%d", S);
     if (S == 0) return IQ_OK;
     IQ_REQUIRE(orders && sizes && keep && status, "iq_kshap_keep_masks_wide: null pointer");
-    hipLaunchKernelGGL(kshap_keep_wide_kernel, dim3((unsigned)((S + kSamplesPerWg - 1) / kSamplesPerWg)), dim3(64 * kSamplesPerWg), 0,
-                       iq::as_stream(stream), orders, sizes, reinterpret_cast<unsigned long long*>(keep), S, R, iq::keep_words(R),
-                       paired ? 1 : 0, status);
-    return iq::check_launch("kshap_keep_wide_kernel");
+    IQ_LAUNCH(kshap_keep_wide_kernel, dim3((unsigned)((S + kSamplesPerWg - 1) / kSamplesPerWg)), dim3(64 * kSamplesPerWg), 0,
+              iq::as_stream(stream), orders, sizes, reinterpret_cast<unsigned long long*>(keep), S, R, iq::keep_words(R),
+              paired ? 1 : 0, status);
+    return IQ_OK;
 }
 
 extern "C" size_t iq_kshap_scratch_bytes_wide(int M, int R, int G) {
@@ -159,14 +159,12 @@ extern "C" int iq_kshap_moment_wide(const uint64_t* keep, const float* v, const 
     const Chunks ch = chunks_of(M);
     const int W = iq::keep_words(R);
     hipStream_t st = iq::as_stream(stream);
-    hipLaunchKernelGGL(kshap_moment_wide_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st,
-                       reinterpret_cast<const unsigned long long*>(keep), v, v0, weights, (long long)M, R, W, ch.tiles_per, s.partB, s.partW);
-    int rc = iq::check_launch("kshap_moment_wide_kernel");
-    if (rc) return rc;
+    IQ_LAUNCH(kshap_moment_wide_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st,
+              reinterpret_cast<const unsigned long long*>(keep), v, v0, weights, (long long)M, R, W, ch.tiles_per, s.partB, s.partW);
     const long long outputs = (long long)G * R + 1;
-    hipLaunchKernelGGL(kshap_fold_wide_kernel, dim3((unsigned)((outputs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                       (const double*)s.partB, (const double*)s.partW, weights ? 1 : 0, (long long)M, R, G, ch.count, b, wsum);
-    return iq::check_launch("kshap_fold_wide_kernel");
+    IQ_LAUNCH(kshap_fold_wide_kernel, dim3((unsigned)((outputs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+              (const double*)s.partB, (const double*)s.partW, weights ? 1 : 0, (long long)M, R, G, ch.count, b, wsum);
+    return IQ_OK;
 }
 
 extern "C" int iq_kshap_phi_analytic(const double* b, const double* wsum, const double* delta, double* phi, int R, int G,
@@ -175,6 +173,6 @@ extern "C" int iq_kshap_phi_analytic(const double* b, const double* wsum, const 
     IQ_REQUIRE(b && wsum && delta && phi, "iq_kshap_phi_analytic: null pointer");
     double h = 0.0;                                   // H_{R-1}, float64, ascending k: summed here on the host, passed by value
     for (int k = 1; k < R; ++k) h += 1.0 / (double)k;
-    hipLaunchKernelGGL(kshap_phi_analytic_kernel, dim3(G), dim3(kThreads), 0, iq::as_stream(stream), b, wsum, delta, phi, R, 2.0 * h);
-    return iq::check_launch("kshap_phi_analytic_kernel");
+    IQ_LAUNCH(kshap_phi_analytic_kernel, dim3(G), dim3(kThreads), 0, iq::as_stream(stream), b, wsum, delta, phi, R, 2.0 * h);
+    return IQ_OK;
 }

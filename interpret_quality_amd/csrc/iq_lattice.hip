@@ -214,9 +214,9 @@ extern "C" int iq_enum_keep_masks(uint64_t* keep, uint64_t first, size_t count, 
     }
     if (count == 0) return IQ_OK;
     IQ_REQUIRE(keep, "iq_enum_keep_masks: null pointer");
-    hipLaunchKernelGGL(enum_keep_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, iq::as_stream(stream),
-                       reinterpret_cast<unsigned long long*>(keep), (unsigned long long)first, count, pl, n, (unsigned long long)base);
-    return iq::check_launch("enum_keep_kernel");
+    IQ_LAUNCH(enum_keep_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, iq::as_stream(stream),
+              reinterpret_cast<unsigned long long*>(keep), (unsigned long long)first, count, pl, n, (unsigned long long)base);
+    return IQ_OK;
 }
 
 extern "C" int iq_exact_shapley(const float* v, int n, double* phi, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
@@ -231,11 +231,9 @@ extern "C" int iq_exact_shapley(const float* v, int n, double* phi, void* scratc
     Denominators den;
     for (int s = 0; s < n; ++s) den.d[s] = n * binomial(n - 1, s);   // 1 / w(s), an integer
     hipStream_t st = iq::as_stream(stream);
-    hipLaunchKernelGGL(strata_kernel<1>, dim3(nchunk, n), dim3(kThreads), 0, st, v, (const int32_t*)nullptr, n, nchunk, part);
-    const int rc = iq::check_launch("strata_kernel<1>");
-    if (rc) return rc;
-    hipLaunchKernelGGL(strata_gather_kernel, dim3(n), dim3(32), 0, st, part, nchunk, n, den, 1, phi);
-    return iq::check_launch("strata_gather_kernel");
+    IQ_LAUNCH(strata_kernel<1>, dim3(nchunk, n), dim3(kThreads), 0, st, v, nullptr, n, nchunk, part);
+    IQ_LAUNCH(strata_gather_kernel, dim3(n), dim3(32), 0, st, part, nchunk, n, den, 1, phi);
+    return IQ_OK;
 }
 
 extern "C" int iq_exact_interactions(const float* v, int n, const int32_t* pairs, int P, double* out, void* scratch,
@@ -254,11 +252,9 @@ extern "C" int iq_exact_interactions(const float* v, int n, const int32_t* pairs
     Denominators den;
     for (int m = 0; m < n - 1; ++m) den.d[m] = binomial(n - 2, m);   // the number of contexts of order m
     hipStream_t st = iq::as_stream(stream);
-    hipLaunchKernelGGL(strata_kernel<2>, dim3(nchunk, P), dim3(kThreads), 0, st, v, pairs, n, nchunk, part);
-    int rc = iq::check_launch("strata_kernel<2>");
-    if (rc) return rc;
-    hipLaunchKernelGGL(strata_gather_kernel, dim3(P), dim3(32), 0, st, part, nchunk, n - 1, den, 0, out);
-    return iq::check_launch("strata_gather_kernel");
+    IQ_LAUNCH(strata_kernel<2>, dim3(nchunk, P), dim3(kThreads), 0, st, v, pairs, n, nchunk, part);
+    IQ_LAUNCH(strata_gather_kernel, dim3(P), dim3(32), 0, st, part, nchunk, n - 1, den, 0, out);
+    return IQ_OK;
 }
 
 extern "C" int iq_moebius(const float* v, int n, double* a, iq_stream_t stream) {
@@ -266,16 +262,14 @@ extern "C" int iq_moebius(const float* v, int n, double* a, iq_stream_t stream) 
     IQ_REQUIRE(v && a, "iq_moebius: null pointer");
     hipStream_t st = iq::as_stream(stream);
     const int L = n < kMoebiusLow ? n : kMoebiusLow;
-    hipLaunchKernelGGL(moebius_low_kernel, dim3(1u << (n - L)), dim3(kThreads), 0, st, v, a, L);
-    int rc = iq::check_launch("moebius_low_kernel");
-    for (int b = L; b < n && !rc;) {
+    IQ_LAUNCH(moebius_low_kernel, dim3(1u << (n - L)), dim3(kThreads), 0, st, v, a, L);
+    for (int b = L; b < n;) {
         const int nb = n - b >= 3 ? 3 : n - b;
         const unsigned blocks = (unsigned)((((size_t)1 << (n - nb)) + kThreads - 1) / kThreads);
-        if (nb == 3) hipLaunchKernelGGL(moebius_high_kernel<3>, dim3(blocks), dim3(kThreads), 0, st, a, n, b);
-        else if (nb == 2) hipLaunchKernelGGL(moebius_high_kernel<2>, dim3(blocks), dim3(kThreads), 0, st, a, n, b);
-        else hipLaunchKernelGGL(moebius_high_kernel<1>, dim3(blocks), dim3(kThreads), 0, st, a, n, b);
-        rc = iq::check_launch("moebius_high_kernel");
+        if (nb == 3) IQ_LAUNCH(moebius_high_kernel<3>, dim3(blocks), dim3(kThreads), 0, st, a, n, b);
+        else if (nb == 2) IQ_LAUNCH(moebius_high_kernel<2>, dim3(blocks), dim3(kThreads), 0, st, a, n, b);
+        else IQ_LAUNCH(moebius_high_kernel<1>, dim3(blocks), dim3(kThreads), 0, st, a, n, b);
         b += nb;
     }
-    return rc;
+    return IQ_OK;
 }

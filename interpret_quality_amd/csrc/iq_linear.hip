@@ -593,7 +593,7 @@ int cu_count() {
 // one grid of pn_gemm_bf3_kernel<false> (MT = 4) or pn_gemm_bf3_short_kernel with MT m-tiles per workgroup over rows [0, M) and the first gy column blocks of 256
 // m_base: where A and out start inside the matrix that m_dev counts the live rows of
 template <int MT>
-void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
+int launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
                      const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, int m_base = 0) {
     const int Kp = (L.cin + 31) & ~31;     // the bf16x3 image's k range (iq_pack_weight_bf3 pads with zero columns)
     const int gx = (M + 32 * MT - 1) / (32 * MT);
@@ -601,15 +601,15 @@ void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* ou
     const unsigned short* w3 = reinterpret_cast<const unsigned short*>(L.w_bf3);
     const bool ragged = Kp != L.cin;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, st, A, lda, w3, L.b, out, ldo, M, Kp, L.cout, relu, m_dev,
-                           static_cast<const float*>(nullptr), gy, tile_nu, rows_per_cloud, L.cin, 0, m_base);
+        return iq::launch(MT == 4 ? "pn_gemm_bf3_kernel" : "pn_gemm_bf3_short_kernel", kernel, grid, dim3(kThreads), 0, st, A, lda, w3,
+                          L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy, tile_nu, rows_per_cloud, L.cin, 0, m_base);
     };
     if constexpr (MT == 4) {
-        if (ragged) launch(pn_gemm_bf3_kernel<false, 4, true>);
-        else launch(pn_gemm_bf3_kernel<false>);
+        if (ragged) return launch(pn_gemm_bf3_kernel<false, 4, true>);
+        else return launch(pn_gemm_bf3_kernel<false>);
     } else {
-        if (ragged) launch(pn_gemm_bf3_short_kernel<MT, true>);
-        else launch(pn_gemm_bf3_short_kernel<MT, false>);
+        if (ragged) return launch(pn_gemm_bf3_short_kernel<MT, true>);
+        else return launch(pn_gemm_bf3_short_kernel<MT, false>);
     }
 }
 
@@ -631,27 +631,26 @@ void launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* ou
 int launch_bf3(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
                const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, bool fit_tiles) {
     if (!fit_tiles || tile_nu || iq::twin() == iq::kTwinDenseTile128) {
-        launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy);
-        return iq::check_launch("pn_gemm_bf3_kernel");
+        return launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy);
     }
     const int cus = cu_count();
     if (cus <= 0) return iq::fail(IQ_ELAUNCH, "dense layer: cannot read the device's multiprocessor count");
     const long long round = 2LL * cus, tiles = (M + 127) / 128, wgs = tiles * gy;
     const int m_full = (int)(wgs / round * round / gy) * 128;     // rows of the whole rounds
     if (wgs < round) {
-        launch_bf3_rows<1>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy);
+        IQ_TRY(launch_bf3_rows<1>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy));
     } else if (wgs < 2 * round) {
-        launch_bf3_rows<2>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy);
+        IQ_TRY(launch_bf3_rows<2>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy));
     } else if (wgs % round == 0 || wgs % round > round / 2 || m_full <= 0 || m_full >= M) {
-        launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy);
+        IQ_TRY(launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy));
     } else {
-        launch_bf3_rows<4>(A, lda, L, out, ldo, m_full, relu, st, m_dev, nullptr, 0, gy);
+        IQ_TRY(launch_bf3_rows<4>(A, lda, L, out, ldo, m_full, relu, st, m_dev, nullptr, 0, gy));
         const float* At = A + (size_t)m_full * lda;
         float* ot = out + (size_t)m_full * ldo;
-        if (wgs % round <= round / 4) launch_bf3_rows<1>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full);
-        else launch_bf3_rows<2>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full);
+        if (wgs % round <= round / 4) IQ_TRY(launch_bf3_rows<1>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full));
+        else IQ_TRY(launch_bf3_rows<2>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full));
     }
-    return iq::check_launch("pn_gemm_bf3_kernel");
+    return IQ_OK;
 }
 
 }  // namespace
@@ -670,8 +669,7 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
     const bool fp32 = iq::twin() == iq::kTwinDenseFp32;
     if (L.w_bf3 && L.cout > 256 && L.cout % 256 == 64 && L.cin >= 32 && !fp32) {
         const int gy = L.cout / 256;
-        int rc = launch_bf3(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy, fit_tiles);
-        if (rc) return rc;
+        IQ_TRY(launch_bf3(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy, fit_tiles));
         iq_dense_layer rest = L;                       // n-tiles 8 gy, 8 gy + 1 of the fp32 image (n-tile-major, cin / 8 fragments each)
         rest.w = L.w + (size_t)(8 * gy) * (L.cin / 8) * (kFragBytes / 4);
         rest.b = L.b + 256 * gy;
@@ -685,40 +683,40 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
         if (ntiles % 10 == 0 && (long long)((M + 127) / 128) * (ntiles / 10) >= 2048) {
             // 320 / 640 ... outputs: column blocks of exactly 10 tiles (NT = 5), nothing padded
             dim3 grid((M + 127) / 128, ntiles / 10);
-            hipLaunchKernelGGL((pn_gemm_lds_kernel<5, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                               L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, 0);
+            IQ_LAUNCH((pn_gemm_lds_kernel<5, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
+                      L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, 0);
         } else if (ntiles == 2 && (M + 255) / 256 >= 2048) {
             // 64 outputs (the fp32 rest of a 320-output layer): 256-row tiles, every wave both column tiles
             dim3 grid((M + 255) / 256, 1);
-            hipLaunchKernelGGL((pn_gemm_lds_kernel<2, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                               L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
+            IQ_LAUNCH((pn_gemm_lds_kernel<2, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
+                      L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
         } else if (ntiles == 4 && (M + 255) / 256 >= 2048) {
             // 128 outputs: 256-row workgroup tiles, every wave all four column tiles
             dim3 grid((M + 255) / 256, 1);
-            hipLaunchKernelGGL((pn_gemm_lds_kernel<4, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                               L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
+            IQ_LAUNCH((pn_gemm_lds_kernel<4, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
+                      L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
         } else if (ntiles >= 8 && (long long)((M + 127) / 128) * ((ntiles + 7) / 8) >= 2048) {
             const int gx = (M + 127) / 128, gy = (ntiles + 7) / 8;
             const bool flat = gy > 1;       // column blocks of a row tile side by side on one XCD (see the kernel)
-            hipLaunchKernelGGL((pn_gemm_lds_kernel<4, false>), flat ? dim3((unsigned)((gx + 7) / 8 * 8 * gy)) : dim3(gx, gy), dim3(kThreads), 0,
-                               st, A, lda, L.w, L.b, out, ldo, M, L.cin, L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, flat ? gy : 0);
+            IQ_LAUNCH((pn_gemm_lds_kernel<4, false>), flat ? dim3((unsigned)((gx + 7) / 8 * 8 * gy)) : dim3(gx, gy), dim3(kThreads), 0,
+                      st, A, lda, L.w, L.b, out, ldo, M, L.cin, L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, flat ? gy : 0);
         } else {
             dim3 grid((M + 127) / 128, (ntiles + 3) / 4);
-            hipLaunchKernelGGL((pn_gemm_lds_kernel<2, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                               L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, 0);
+            IQ_LAUNCH((pn_gemm_lds_kernel<2, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
+                      L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, 0);
         }
-        return iq::check_launch("pn_gemm_lds_kernel");
+        return IQ_OK;
     }
     if (ntiles >= 4) {
         dim3 grid((M + 127) / 128, (ntiles + 3) / 4);
-        hipLaunchKernelGGL((pn_linear_kernel<2, 2, 2, 2>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M,
-                           L.cin, L.cout, relu, m_dev, 0);
+        IQ_LAUNCH((pn_linear_kernel<2, 2, 2, 2>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M,
+                  L.cin, L.cout, relu, m_dev, 0);
     } else {
         dim3 grid((M + 255) / 256, ntiles);
-        hipLaunchKernelGGL((pn_linear_kernel<2, 1, 4, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M,
-                           L.cin, L.cout, relu, m_dev, 0);
+        IQ_LAUNCH((pn_linear_kernel<2, 1, 4, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M,
+                  L.cin, L.cout, relu, m_dev, 0);
     }
-    return iq::check_launch("pn_linear_kernel");
+    return IQ_OK;
 }
 
 namespace {
@@ -755,21 +753,21 @@ int iq::launch_linear_splitk(const float* A, int lda, const iq_dense_layer& L, f
         IQ_REQUIRE(scratch && (size_t)splits * M * L.cout <= scratch_floats, "split-K dense layer: scratch %zu floats < %zu",
                    scratch_floats, (size_t)splits * M * L.cout);
         const int gx = (M + 127) / 128, gy = L.cout / 256;
-        hipLaunchKernelGGL((pn_gemm_bf3_kernel<false, 4, false, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy), (unsigned)splits), dim3(kThreads), 0,
-                           st, A, lda, reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, scratch, L.cout, M, L.cin, L.cout, 0, nullptr, nullptr,
-                           gy, nullptr, 0, L.cin, kbs * 8 / 32, 0);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
-                           out, ldo, M, L.cout, splits, relu);
-        return iq::check_launch("pn_gemm_bf3_kernel<split-K>");
+        IQ_LAUNCH((pn_gemm_bf3_kernel<false, 4, false, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy), (unsigned)splits), dim3(kThreads), 0,
+                  st, A, lda, reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, scratch, L.cout, M, L.cin, L.cout, 0, nullptr, nullptr,
+                  gy, nullptr, 0, L.cin, kbs * 8 / 32, 0);
+        IQ_LAUNCH(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
+                  out, ldo, M, L.cout, splits, relu);
+        return IQ_OK;
     }
     IQ_REQUIRE(scratch && (size_t)splits * M * L.cout <= scratch_floats, "split-K dense layer: scratch %zu floats < %zu",
                scratch_floats, (size_t)splits * M * L.cout);
     dim3 grid((M + 127) / 128, (ntiles + 3) / 4, splits);
-    hipLaunchKernelGGL((pn_linear_kernel<2, 2, 2, 2>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, scratch, L.cout, M, L.cin,
-                       L.cout, 0, nullptr, kbs);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
-                       out, ldo, M, L.cout, splits, relu);
-    return iq::check_launch("pn_linear_kernel<split-K>");
+    IQ_LAUNCH((pn_linear_kernel<2, 2, 2, 2>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, scratch, L.cout, M, L.cin,
+              L.cout, 0, nullptr, kbs);
+    IQ_LAUNCH(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
+              out, ldo, M, L.cout, splits, relu);
+    return IQ_OK;
 }
 
 int iq::launch_linear_pool(const float* A, int lda, const iq_dense_layer& L, float* partial, int M, int relu,
@@ -781,14 +779,14 @@ int iq::launch_linear_pool(const float* A, int lda, const iq_dense_layer& L, flo
         return iq::fail(IQ_EUNSUPPORTED, "dense layer + pool: cin=%d cout=%d", L.cin, L.cout);
     const int gy = (ntiles + 7) / 8, gx = (M + 127) / 128;
     if (w_bf3 && L.cout % 256 == 0) {
-        hipLaunchKernelGGL(pn_gemm_bf3_kernel<true>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                           reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy,
-                           nullptr, 0, L.cin, 0, 0);
-        return iq::check_launch("pn_gemm_bf3_kernel<pool>");
+        IQ_LAUNCH(pn_gemm_bf3_kernel<true>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
+                  reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy,
+                  nullptr, 0, L.cin, 0, 0);
+        return IQ_OK;
     }
-    hipLaunchKernelGGL((pn_gemm_lds_kernel<4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda, L.w, L.b,
-                       partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, nullptr, 0, gy);
-    return iq::check_launch("pn_gemm_lds_kernel<pool>");
+    IQ_LAUNCH((pn_gemm_lds_kernel<4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda, L.w, L.b,
+              partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, nullptr, 0, gy);
+    return IQ_OK;
 }
 
 extern "C" int iq_linear(const float* A, int lda, const iq_dense_layer* L, float* out, int ldo, int M, int act,
@@ -881,8 +879,8 @@ int iq::launch_split_bf3(const float* packed_w, unsigned short* out_bf3, int cou
     IQ_REQUIRE(packed_w && out_bf3 && cout >= 1 && cin >= 8 && cin % 8 == 0, "iq_split_packed_weight_bf3: cout=%d cin=%d", cout, cin);
     const int KS = ((cin + 31) & ~31) / 16, ntiles = iq_padded_cout(cout) / 32;
     const size_t threads = (size_t)ntiles * KS * 64;
-    hipLaunchKernelGGL(split_packed_bf3_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, packed_w, out_bf3, ntiles, KS, cin);
-    return iq::check_launch("split_packed_bf3_kernel");
+    IQ_LAUNCH(split_packed_bf3_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, packed_w, out_bf3, ntiles, KS, cin);
+    return IQ_OK;
 }
 
 extern "C" int iq_split_packed_weight_bf3(const float* packed_w, unsigned short* out_bf3, int cout, int cin, iq_stream_t stream) {

@@ -113,8 +113,8 @@ int launch(MaskArgs a, iq_stream_t stream) {
     IQ_REQUIRE(a.N > 0 && a.N <= IQ_MAX_POINTS, "mask: N=%d not in (0,%d]", a.N, IQ_MAX_POINTS);
     IQ_REQUIRE(a.R >= 0 && a.R <= IQ_MAX_REGIONS, "mask: R=%d out of range", a.R);
     const int grid = (a.rows + kRowsPerWg - 1) / kRowsPerWg;
-    hipLaunchKernelGGL(mask_rows_kernel, dim3(grid), dim3(kThreads), 0, iq::as_stream(stream), a);
-    return iq::check_launch("mask_rows_kernel");
+    IQ_LAUNCH(mask_rows_kernel, dim3(grid), dim3(kThreads), 0, iq::as_stream(stream), a);
+    return IQ_OK;
 }
 
 }  // namespace
@@ -154,14 +154,11 @@ extern "C" int iq_check_index_range(const int32_t* idx, size_t count, int lo, in
     if (count == 0) return IQ_OK;
     hipStream_t st = iq::as_stream(stream);
     uint32_t bad = 0xffffffffu;
-    if (hipMemcpyAsync(scratch, &bad, sizeof(bad), hipMemcpyHostToDevice, st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "iq_check_index_range: copy failed");
+    IQ_TRY(iq::hip_ok(hipMemcpyAsync(scratch, &bad, sizeof(bad), hipMemcpyHostToDevice, st), "iq_check_index_range: copy"));
     const int grid = (int)std::min<size_t>((count + 255) / 256, 1024);
-    hipLaunchKernelGGL(index_range_kernel, dim3(grid), dim3(256), 0, st, idx, count, lo, hi, scratch);
-    int rc = iq::check_launch("index_range_kernel");
-    if (rc) return rc;
-    if (hipMemcpyAsync(&bad, scratch, sizeof(bad), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "iq_check_index_range: read-back failed");
+    IQ_LAUNCH(index_range_kernel, dim3(grid), dim3(256), 0, st, idx, count, lo, hi, scratch);
+    IQ_TRY(iq::hip_ok(hipMemcpyAsync(&bad, scratch, sizeof(bad), hipMemcpyDeviceToHost, st), "iq_check_index_range: read-back"));
+    IQ_TRY(iq::hip_ok(hipStreamSynchronize(st), "iq_check_index_range: read-back"));
     if (bad != 0xffffffffu) return iq::fail(IQ_EINVAL, "index at position %u is outside [%d, %d)", bad, lo, hi);
     return IQ_OK;
 }

@@ -932,12 +932,12 @@ template <int K>
 int launch_pc_knn(const float* keys, int nkeys, const float* queries, int S, WsC& s, int16_t* idx, int B, hipStream_t st,
                   const int32_t* n_unique = nullptr) {
     const int nkp = (nkeys + 31) / 32 * 32;
-    hipLaunchKernelGGL(pc_pad8_kernel, dim3((B * nkp + 255) / 256), dim3(256), 0, st, keys, s.k8, B, nkeys, nkp);
-    hipLaunchKernelGGL(pc_pad8_kernel, dim3((B * S + 255) / 256), dim3(256), 0, st, queries, s.q8, B, S, S);
+    IQ_LAUNCH(pc_pad8_kernel, dim3((B * nkp + 255) / 256), dim3(256), 0, st, keys, s.k8, B, nkeys, nkp);
+    IQ_LAUNCH(pc_pad8_kernel, dim3((B * S + 255) / 256), dim3(256), 0, st, queries, s.q8, B, S, S);
     const int wpc = (S + 127) / 128;
-    hipLaunchKernelGGL(pc_knn_kernel<K>, dim3((unsigned)((B + 7) / 8 * 8 * wpc)), dim3(kThreads), 0, st, s.k8, s.q8, idx, nkp, S, B,
-                       wpc, n_unique);
-    return iq::check_launch("pc_knn_kernel");
+    IQ_LAUNCH(pc_knn_kernel<K>, dim3((unsigned)((B + 7) / 8 * 8 * wpc)), dim3(kThreads), 0, st, s.k8, s.q8, idx, nkp, S, B,
+              wpc, n_unique);
+    return IQ_OK;
 }
 
 // members -> (rel, sw) records, then the grouped kernel.  xyz (B,N,3) member coordinates, new_xyz (B,S,3) centroids,
@@ -949,10 +949,8 @@ int launch_pc_group(const iq_pointconv_sa& sa, const float* xyz, const float* ne
     const size_t total = (size_t)B * S * K;
     const TinyNets nets{sa.densitynet, sa.weightnet};
     const unsigned mgrid = (unsigned)((total + kThreads - 1) / kThreads);
-    if (K == 32) hipLaunchKernelGGL(pc_member_kernel<32>, dim3(mgrid), dim3(kThreads), 0, st, xyz, new_xyz, idx, inv_density, nets, s.mrel, s.msw, N, S, total, n_unique);
-    else         hipLaunchKernelGGL(pc_member_kernel<64>, dim3(mgrid), dim3(kThreads), 0, st, xyz, new_xyz, idx, inv_density, nets, s.mrel, s.msw, N, S, total, n_unique);
-    int rc = iq::check_launch("pc_member_kernel");
-    if (rc) return rc;
+    if (K == 32) IQ_LAUNCH(pc_member_kernel<32>, dim3(mgrid), dim3(kThreads), 0, st, xyz, new_xyz, idx, inv_density, nets, s.mrel, s.msw, N, S, total, n_unique);
+    else         IQ_LAUNCH(pc_member_kernel<64>, dim3(mgrid), dim3(kThreads), 0, st, xyz, new_xyz, idx, inv_density, nets, s.mrel, s.msw, N, S, total, n_unique);
     PcGroupArgs a{};
     a.mrel = s.mrel; a.msw = s.msw; a.U = U; a.ldu = ldu;
     a.w1x = sa.w1x;
@@ -964,18 +962,18 @@ int launch_pc_group(const iq_pointconv_sa& sa, const float* xyz, const float* ne
     a.wgs_per_cloud = (chunks + a.chunks_per_wg - 1) / a.chunks_per_wg;
     dim3 grid((unsigned)((B + 7) / 8 * 8 * a.wgs_per_cloud));
     const int c1 = sa.l2.cin, c2 = sa.l2.cout, c3 = sa.l3.cout;
-    if (c1 == 64 && c2 == 64 && c3 == 128) hipLaunchKernelGGL((pc_group_kernel<64, 64, 128>), grid, dim3(kThreads), 0, st, a);
+    if (c1 == 64 && c2 == 64 && c3 == 128) IQ_LAUNCH((pc_group_kernel<64, 64, 128>), grid, dim3(kThreads), 0, st, a);
     else if (c1 == 128 && c2 == 128 && c3 == 256) {
         // every group runs all its K members (sums, not maxima: nothing is skipped); MFMA work = the two dense layers + the
         // contraction's 16x16x4 tiles
         iq::ProfileSpan dom(iq::kSlotDominant, st, 2.0 * (double)B * S * K * ((double)c1 * c2 + (double)c2 * c3 + 16.0 * c3));
         if (a.w2_bf3 && a.w3_bf3 && iq::twin() != iq::kTwinGroupFp32)   // the twin: the fp32-MFMA kernel (A/B and tests)
-            hipLaunchKernelGGL(pc_group_bf3_kernel, grid, dim3(kThreads), 0, st, a);
+            IQ_LAUNCH(pc_group_bf3_kernel, grid, dim3(kThreads), 0, st, a);
         else
-            hipLaunchKernelGGL((pc_group_kernel<128, 128, 256>), grid, dim3(kThreads), 0, st, a);
+            IQ_LAUNCH((pc_group_kernel<128, 128, 256>), grid, dim3(kThreads), 0, st, a);
     }
     else return iq::fail(IQ_EUNSUPPORTED, "pointconv stage %d-%d-%d has no kernel instantiation", c1, c2, c3);
-    return iq::check_launch("pc_group_kernel");
+    return IQ_OK;
 }
 
 }  // namespace
@@ -1003,90 +1001,81 @@ struct PcWalk {
 // the network on B materialised clouds xyz (B,N,3)
 int run_pointconv(const iq_pointconv_weights* w, const float* xyz, float* logits, WsC& s, int B, int N, hipStream_t st,
                   const PcWalk* walk) {
-    int rc;
     constexpr int S1 = 512, S2 = 128;
     bool fused_sa1 = false;
 
     // ---- sa1: 1024 -> 512 points, K = 32, 3 -> 64 -> 64 -> 128 ---------------------------------------------------
     {
         iq::ProfileSpan span(iq::kSlotPrepool, st);
-        hipLaunchKernelGGL(pc_density_kernel, dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)N * 16, st, xyz,
-                           w->sa[0].bandwidth, s.inv1, N);
-        if ((rc = iq::launch_fps(xyz, s.fps1, s.nu1, B, N, S1, st))) return rc;
-        hipLaunchKernelGGL(pc_gather_xyz_kernel, dim3((B * S1 + 255) / 256), dim3(256), 0, st, xyz, 3, s.fps1, s.nx1, N, S1, B * S1);
+        IQ_LAUNCH(pc_density_kernel, dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)N * 16, st, xyz,
+                  w->sa[0].bandwidth, s.inv1, N);
+        IQ_TRY(iq::launch_fps(xyz, s.fps1, s.nu1, B, N, S1, st));
+        IQ_LAUNCH(pc_gather_xyz_kernel, dim3((B * S1 + 255) / 256), dim3(256), 0, st, xyz, 3, s.fps1, s.nx1, N, S1, B * S1);
         // a masked cloud has at most kept + 1 distinct locations: once FPS has used them up it returns index 0, so centroids
         // s >= nu1 are copies of centroid 0 and their groups (kNN, members, MLP, contraction, linear layer) are not computed
         if (walk) {
-            hipLaunchKernelGGL(pc_walk1_kernel<32>, dim3(S1 / 64, B), dim3(64), 0, st, walk->sorted, walk->kept, walk->mfirst,
-                               walk->mcount, s.fps1, s.nu1, walk->cloud_of, s.idx1, N, S1, walk->Nsl, walk->nclouds);
-            if ((rc = iq::check_launch("pc_walk1_kernel"))) return rc;
-        } else if ((rc = launch_pc_knn<32>(xyz, N, s.nx1, S1, s, s.idx1, B, st, s.nu1))) {
-            return rc;
+            IQ_LAUNCH(pc_walk1_kernel<32>, dim3(S1 / 64, B), dim3(64), 0, st, walk->sorted, walk->kept, walk->mfirst,
+                      walk->mcount, s.fps1, s.nu1, walk->cloud_of, s.idx1, N, S1, walk->Nsl, walk->nclouds);
+        } else {
+            IQ_TRY(launch_pc_knn<32>(xyz, N, s.nx1, S1, s, s.idx1, B, st, s.nu1));
         }
         if (walk && walk->feat_tab) {   // members' weights as usual, the MLP rows from the pair table
             const size_t total = (size_t)B * S1 * 32;
             const TinyNets nets{w->sa[0].densitynet, w->sa[0].weightnet};
-            hipLaunchKernelGGL(pc_member_kernel<32>, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, xyz, s.nx1,
-                               s.idx1, s.inv1, nets, s.mrel, s.msw, N, S1, total, s.nu1);
+            IQ_LAUNCH(pc_member_kernel<32>, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, xyz, s.nx1,
+                      s.idx1, s.inv1, nets, s.mrel, s.msw, N, S1, total, s.nu1);
             const iq_dense_layer& lin = w->sa[0].linear;
             if (lin.cin == 2048 && lin.cout == 128 && iq::twin() != iq::kTwinPcTwoKernel) {
                 // contraction + the 2048 -> 128 layer in one kernel (twin kTwinPcTwoKernel: the two-kernel form, A/B runs and tests)
                 PcFusedArgs fa{walk->feat_tab, s.msw, s.idx1, s.fps1, walk->kept, s.nu1, walk->cloud_of, lin.w, lin.b, s.l1, N, S1, B,
                                walk->nclouds};
-                hipLaunchKernelGGL(pc_tab_fused_kernel, dim3((unsigned)(8 * ((B + 7) / 8) * (S1 / 32))), dim3(kThreads), 0, st, fa);
-                if ((rc = iq::check_launch("pc_tab_fused_kernel"))) return rc;
+                IQ_LAUNCH(pc_tab_fused_kernel, dim3((unsigned)(8 * ((B + 7) / 8) * (S1 / 32))), dim3(kThreads), 0, st, fa);
                 fused_sa1 = true;
             } else {
-                hipLaunchKernelGGL(pc_tab_group_kernel, dim3((unsigned)(((size_t)B * S1 + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads),
-                                   0, st, walk->feat_tab, s.msw, s.idx1, s.fps1, walk->kept, s.nu1, walk->cloud_of, s.g1, N, S1, B,
-                                   walk->nclouds);
-                if ((rc = iq::check_launch("pc_tab_group_kernel"))) return rc;
+                IQ_LAUNCH(pc_tab_group_kernel, dim3((unsigned)(((size_t)B * S1 + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads),
+                          0, st, walk->feat_tab, s.msw, s.idx1, s.fps1, walk->kept, s.nu1, walk->cloud_of, s.g1, N, S1, B,
+                          walk->nclouds);
             }
-        } else if ((rc = launch_pc_group(w->sa[0], xyz, s.nx1, s.idx1, s.inv1, nullptr, 0, s.g1, s, N, S1, 32, B, st, s.nu1))) {
-            return rc;
+        } else {
+            IQ_TRY(launch_pc_group(w->sa[0], xyz, s.nx1, s.idx1, s.inv1, nullptr, 0, s.g1, s, N, S1, 32, B, st, s.nu1));
         }
-        if (!fused_sa1 && (rc = iq::launch_linear(s.g1, 2048, w->sa[0].linear, s.l1, 128, B * S1, 1, st, nullptr, s.nu1, S1))) return rc;
-        hipLaunchKernelGGL(pc_fill_dup_rows_kernel, dim3(S1, B), dim3(64), 0, st, s.l1, S1, 128, s.nu1);
-        if ((rc = iq::check_launch("pc_fill_dup_rows_kernel"))) return rc;
+        if (!fused_sa1) IQ_TRY(iq::launch_linear(s.g1, 2048, w->sa[0].linear, s.l1, 128, B * S1, 1, st, nullptr, s.nu1, S1));
+        IQ_LAUNCH(pc_fill_dup_rows_kernel, dim3(S1, B), dim3(64), 0, st, s.l1, S1, 128, s.nu1);
     }
     // ---- sa2: 512 -> 128 points, K = 64, 131 -> 128 -> 128 -> 256 --------------------------------------------------
     {
         iq::ProfileSpan span(iq::kSlotFstn, st);
-        hipLaunchKernelGGL(pc_density_kernel, dim3((S1 + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)S1 * 16, st, s.nx1,
-                           w->sa[1].bandwidth, s.inv2, S1);
-        if ((rc = iq::launch_fps(s.nx1, s.fps2, nullptr, B, S1, S2, st))) return rc;
-        hipLaunchKernelGGL(pc_gather_xyz_kernel, dim3((B * S2 + 255) / 256), dim3(256), 0, st, s.nx1, 3, s.fps2, s.nx2, S1, S2, B * S2);
+        IQ_LAUNCH(pc_density_kernel, dim3((S1 + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)S1 * 16, st, s.nx1,
+                  w->sa[1].bandwidth, s.inv2, S1);
+        IQ_TRY(iq::launch_fps(s.nx1, s.fps2, nullptr, B, S1, S2, st));
+        IQ_LAUNCH(pc_gather_xyz_kernel, dim3((B * S2 + 255) / 256), dim3(256), 0, st, s.nx1, 3, s.fps2, s.nx2, S1, S2, B * S2);
         if (walk) {
-            hipLaunchKernelGGL(pc_pos_kernel, dim3(B), dim3(64), 0, st, walk->kept, s.fps1, s.nu1, walk->src1, walk->pos, N, S1, walk->Npos);
-            hipLaunchKernelGGL(pc_walk2_kernel<64>, dim3(S2 / 64, B), dim3(64), 0, st, walk->sorted, walk->src1, walk->pos, s.fps2, s.nu1,
-                               walk->cloud_of, s.idx2, N, S1, S2, walk->Nsl, walk->Npos, walk->nclouds);
-            if ((rc = iq::check_launch("pc_walk2_kernel"))) return rc;
-        } else if ((rc = launch_pc_knn<64>(s.nx1, S1, s.nx2, S2, s, s.idx2, B, st))) {
-            return rc;
+            IQ_LAUNCH(pc_pos_kernel, dim3(B), dim3(64), 0, st, walk->kept, s.fps1, s.nu1, walk->src1, walk->pos, N, S1, walk->Npos);
+            IQ_LAUNCH(pc_walk2_kernel<64>, dim3(S2 / 64, B), dim3(64), 0, st, walk->sorted, walk->src1, walk->pos, s.fps2, s.nu1,
+                      walk->cloud_of, s.idx2, N, S1, S2, walk->Nsl, walk->Npos, walk->nclouds);
+        } else {
+            IQ_TRY(launch_pc_knn<64>(s.nx1, S1, s.nx2, S2, s, s.idx2, B, st));
         }
-        if ((rc = iq::launch_linear(s.l1, 128, w->sa[1].u, s.u2, 128, B * S1, 0, st))) return rc;
-        if ((rc = launch_pc_group(w->sa[1], s.nx1, s.nx2, s.idx2, s.inv2, s.u2, 128, s.g2, s, S1, S2, 64, B, st, nullptr, w->sa2_l2_bf3, w->sa2_l3_bf3))) return rc;
-        if ((rc = iq::launch_linear(s.g2, 4096, w->sa[1].linear, s.l2, 256, B * S2, 1, st))) return rc;
+        IQ_TRY(iq::launch_linear(s.l1, 128, w->sa[1].u, s.u2, 128, B * S1, 0, st));
+        IQ_TRY(launch_pc_group(w->sa[1], s.nx1, s.nx2, s.idx2, s.inv2, s.u2, 128, s.g2, s, S1, S2, 64, B, st, nullptr, w->sa2_l2_bf3, w->sa2_l3_bf3));
+        IQ_TRY(iq::launch_linear(s.g2, 4096, w->sa[1].linear, s.l2, 256, B * S2, 1, st));
     }
     // ---- sa3: group all 128 points, 259 -> 256 -> 512 -> 1024 ------------------------------------------------------
     {
         iq::ProfileSpan span(iq::kSlotTrunk, st);
-        hipLaunchKernelGGL(pc_density_kernel, dim3(1, B), dim3(kThreads), (size_t)S2 * 16, st, s.nx2, w->sa[2].bandwidth, s.inv3, S2);
-        if ((rc = iq::launch_linear(s.l2, 256, w->sa[2].u, s.u3, 256, B * S2, 0, st))) return rc;
+        IQ_LAUNCH(pc_density_kernel, dim3(1, B), dim3(kThreads), (size_t)S2 * 16, st, s.nx2, w->sa[2].bandwidth, s.inv3, S2);
+        IQ_TRY(iq::launch_linear(s.l2, 256, w->sa[2].u, s.u3, 256, B * S2, 0, st));
         TinyNets nets{w->sa[2].densitynet, w->sa[2].weightnet};
-        hipLaunchKernelGGL(pc_all_prepare_kernel, dim3(B), dim3(128), 0, st, s.nx2, s.inv3, nets, w->sa[2].w1x, s.u3, 256, s.h1,
-                           s.sw3, S2);
-        if ((rc = iq::check_launch("pc_all_prepare_kernel"))) return rc;
-        if ((rc = iq::launch_linear(s.h1, 256, w->sa[2].l2, s.h2, 512, B * S2, 1, st))) return rc;
-        if ((rc = iq::launch_linear(s.h2, 512, w->sa[2].l3, s.h3, 1024, B * S2, 1, st))) return rc;
-        hipLaunchKernelGGL(pc_all_contract_kernel, dim3(1024 / kThreads, B), dim3(kThreads), 0, st, s.h3, s.sw3, s.g3, S2, 1024);
-        if ((rc = iq::check_launch("pc_all_contract_kernel"))) return rc;
+        IQ_LAUNCH(pc_all_prepare_kernel, dim3(B), dim3(128), 0, st, s.nx2, s.inv3, nets, w->sa[2].w1x, s.u3, 256, s.h1, s.sw3, S2);
+        IQ_TRY(iq::launch_linear(s.h1, 256, w->sa[2].l2, s.h2, 512, B * S2, 1, st));
+        IQ_TRY(iq::launch_linear(s.h2, 512, w->sa[2].l3, s.h3, 1024, B * S2, 1, st));
+        IQ_LAUNCH(pc_all_contract_kernel, dim3(1024 / kThreads, B), dim3(kThreads), 0, st, s.h3, s.sw3, s.g3, S2, 1024);
         // 16384 -> 1024 on only B rows: split K over workgroups (scratch: the h3 buffer, free by now, B*128*1024 floats)
-        if ((rc = iq::launch_linear_splitk(s.g3, 16384, w->sa[2].linear, s.l3, 1024, B, 1, s.h3, (size_t)B * 128 * 1024, st))) return rc;
+        IQ_TRY(iq::launch_linear_splitk(s.g3, 16384, w->sa[2].linear, s.l3, 1024, B, 1, s.h3, (size_t)B * 128 * 1024, st));
     }
-    if ((rc = iq::launch_linear(s.l3, 1024, w->fc1, s.f1, 512, B, 1, st))) return rc;
-    if ((rc = iq::launch_linear(s.f1, 512, w->fc2, s.f2, 256, B, 1, st))) return rc;
-    if ((rc = iq::launch_linear(s.f2, 256, w->fc3, logits, w->fc3.cout, B, 0, st))) return rc;
+    IQ_TRY(iq::launch_linear(s.l3, 1024, w->fc1, s.f1, 512, B, 1, st));
+    IQ_TRY(iq::launch_linear(s.f1, 512, w->fc2, s.f2, 256, B, 1, st));
+    IQ_TRY(iq::launch_linear(s.f2, 256, w->fc3, logits, w->fc3.cout, B, 0, st));
     return IQ_OK;
 }
 
@@ -1222,14 +1211,12 @@ static int pointconv_coalitions(const iq_pointconv_weights* w, const float* clou
     int have = tables_state ? (*tables_state & 3) : 0;    // bit 0: sorted lists, bit 1: pair tables (see above)
     const int force = tables_state ? ((*tables_state >> 2) & 3) : 0;
     hipStream_t st = iq::as_stream(stream);
-    int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
     const int Nsp = (N + 1 + 31) / 32 * 32, Nsl = (N + 1 + 7) / 8 * 8;
-    hipLaunchKernelGGL((W ? pc_coal_prep_kernel<true> : pc_coal_prep_kernel<false>), dim3(B), dim3(64), 0, st, region_id, keep, cloud_of,
-                       t.kept, t.mfirst, t.mcount, N, nclouds, R, W);
-    hipLaunchKernelGGL(pc_mask_kernel, dim3((unsigned)(((size_t)B * N + 255) / 256)), dim3(256), 0, st, clouds, centers, t.kept, cloud_of,
-                       t.X, N, B, nclouds);
-    if ((rc = iq::check_launch("pc_mask_kernel"))) return rc;
+    IQ_LAUNCH((W ? pc_coal_prep_kernel<true> : pc_coal_prep_kernel<false>), dim3(B), dim3(64), 0, st, region_id, keep, cloud_of,
+              t.kept, t.mfirst, t.mcount, N, nclouds, R, W);
+    IQ_LAUNCH(pc_mask_kernel, dim3((unsigned)(((size_t)B * N + 255) / 256)), dim3(256), 0, st, clouds, centers, t.kept, cloud_of,
+              t.X, N, B, nclouds);
     // the lists for up to 8 source clouds whatever B is: the two ways of forming a group differ in the order of the sum over its
     // members, and a coalition's logits must not depend on how many others share its launch (twin kTwinPcKnn: pc_knn_kernel)
     // tables_state bits 2-3 (in): 1 = always the list walk, 2 = never - a caller that splits one batch over several launches names
@@ -1238,10 +1225,9 @@ static int pointconv_coalitions(const iq_pointconv_weights* w, const float* clou
     PcWalk walk{};
     if (use_walk) {
         if (!(have & 1)) {
-            hipLaunchKernelGGL(sl_rows_kernel, dim3((Nsp + 255) / 256, nclouds), dim3(256), 0, st, clouds, centers, t.xs, t.xxs, N, Nsp);
-            hipLaunchKernelGGL(sl_dist_kernel<1>, dim3(Nsp / 32, nclouds), dim3(64), 0, st, t.xs, t.xxs, t.dmat, Nsp);
-            hipLaunchKernelGGL(sl_sort_kernel, dim3(N + 1, nclouds), dim3(256), 0, st, t.dmat, t.sorted, N, Nsp, Nsl);
-            if ((rc = iq::check_launch("sl_sort_kernel"))) return rc;
+            IQ_LAUNCH(sl_rows_kernel, dim3((Nsp + 255) / 256, nclouds), dim3(256), 0, st, clouds, centers, t.xs, t.xxs, N, Nsp);
+            IQ_LAUNCH(sl_dist_kernel<1>, dim3(Nsp / 32, nclouds), dim3(64), 0, st, t.xs, t.xxs, t.dmat, Nsp);
+            IQ_LAUNCH(sl_sort_kernel, dim3(N + 1, nclouds), dim3(256), 0, st, t.dmat, t.sorted, N, Nsp, Nsl);
             have |= 1;
         }
         walk = PcWalk{t.sorted, t.kept, t.mfirst, t.mcount, t.src1, t.pos, cloud_of, nclouds, Nsl, Nsl, nullptr};
@@ -1252,11 +1238,10 @@ static int pointconv_coalitions(const iq_pointconv_weights* w, const float* clou
             const int n1 = N + 1;
             const size_t rows = (size_t)n1 * n1;
             for (int c = 0; c < nclouds && !(have & 2); ++c) {
-                hipLaunchKernelGGL(pc_tab_l1_kernel, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, st, t.xs + (size_t)c * Nsp * 8,
-                                   sa.w1x, t.th1, n1);
-                if ((rc = iq::check_launch("pc_tab_l1_kernel"))) return rc;
-                if ((rc = iq::launch_linear(t.th1, 64, sa.l2, t.th2, 64, (int)rows, 1, st))) return rc;
-                if ((rc = iq::launch_linear(t.th2, 64, sa.l3, t.feat + (size_t)c * rows * 128, 128, (int)rows, 1, st))) return rc;
+                IQ_LAUNCH(pc_tab_l1_kernel, dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, st, t.xs + (size_t)c * Nsp * 8,
+                          sa.w1x, t.th1, n1);
+                IQ_TRY(iq::launch_linear(t.th1, 64, sa.l2, t.th2, 64, (int)rows, 1, st));
+                IQ_TRY(iq::launch_linear(t.th2, 64, sa.l3, t.feat + (size_t)c * rows * 128, 128, (int)rows, 1, st));
             }
             have |= 2;
             walk.feat_tab = t.feat;
@@ -1300,7 +1285,7 @@ extern "C" int iq_pointconv_inverse_density(const float* xyz, double bandwidth, 
     IQ_REQUIRE(bandwidth > 0.0, "iq_pointconv_inverse_density: bandwidth %g must be positive", bandwidth);
     if (B == 0) return IQ_OK;
     IQ_REQUIRE(xyz && out, "iq_pointconv_inverse_density: null pointer");
-    hipLaunchKernelGGL(pc_density_kernel, dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)N * 16, iq::as_stream(stream),
-                       xyz, (float)bandwidth, out, N);
-    return iq::check_launch("pc_density_kernel");
+    IQ_LAUNCH(pc_density_kernel, dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), (size_t)N * 16, iq::as_stream(stream),
+              xyz, (float)bandwidth, out, N);
+    return IQ_OK;
 }

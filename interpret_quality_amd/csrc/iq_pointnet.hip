@@ -528,12 +528,11 @@ __global__ __launch_bounds__(kThreads) void pn_rep_write_kernel(const int32_t* _
 int launch_reps(const uint64_t* keep, const int32_t* cloud_of, int B, int R, int32_t* rep, int32_t* table, hipStream_t st,
                 int32_t* block_cnt = nullptr) {
     const size_t slots = rep_slots(B);
-    if (hipMemsetAsync(table, 0xff, slots * sizeof(int32_t), st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "pn_rep kernels: memset failed");
+    IQ_TRY(iq::hip_ok(hipMemsetAsync(table, 0xff, slots * sizeof(int32_t), st), "pn_rep table memset"));
     const dim3 grid((B + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(pn_rep_insert_kernel, grid, dim3(kThreads), 0, st, keep, cloud_of, table, rep, B, R, (uint32_t)(slots - 1));
-    hipLaunchKernelGGL(pn_rep_write_kernel, grid, dim3(kThreads), 0, st, table, rep, B, block_cnt);
-    return iq::check_launch("pn_rep kernels");
+    IQ_LAUNCH(pn_rep_insert_kernel, grid, dim3(kThreads), 0, st, keep, cloud_of, table, rep, B, R, (uint32_t)(slots - 1));
+    IQ_LAUNCH(pn_rep_write_kernel, grid, dim3(kThreads), 0, st, table, rep, B, block_cnt);
+    return IQ_OK;
 }
 
 // The distinct coalitions of a batch in slots 0 .. U-1, in the order of their first items: slot_of[i] = the number of representatives
@@ -640,16 +639,16 @@ __global__ __launch_bounds__(kThreads) void pn_compact_fill_kernel(const int32_t
 int launch_compact(const int32_t* rep, const int32_t* cloud_of, int B, int32_t* block_cnt, int32_t* slot_of, int32_t* item_u,
                    int32_t* cloud_u, int32_t* n_distinct, hipStream_t st) {
     if (B <= kOrderFusedMax) {
-        hipLaunchKernelGGL(pn_compact_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, rep, cloud_of, slot_of, item_u, cloud_u,
-                           n_distinct, B);
+        IQ_LAUNCH(pn_compact_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, rep, cloud_of, slot_of, item_u, cloud_u,
+                  n_distinct, B);
     } else {
         const int nb = (B + kThreads - 1) / kThreads;
-        hipLaunchKernelGGL(pn_compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, n_distinct, nb);
-        hipLaunchKernelGGL(pn_compact_scatter_kernel, dim3(nb), dim3(kThreads), 0, st, rep, cloud_of, block_cnt, slot_of, item_u,
-                           cloud_u, B);
-        hipLaunchKernelGGL(pn_compact_fill_kernel, dim3(nb), dim3(kThreads), 0, st, rep, slot_of, B);
+        IQ_LAUNCH(pn_compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, block_cnt, n_distinct, nb);
+        IQ_LAUNCH(pn_compact_scatter_kernel, dim3(nb), dim3(kThreads), 0, st, rep, cloud_of, block_cnt, slot_of, item_u,
+                  cloud_u, B);
+        IQ_LAUNCH(pn_compact_fill_kernel, dim3(nb), dim3(kThreads), 0, st, rep, slot_of, B);
     }
-    return iq::check_launch("pn_compact kernels");
+    return IQ_OK;
 }
 
 // at the end: every item takes its slot's logits ...
@@ -928,7 +927,6 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         return iq::fail(IQ_EWORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     Workspace ws = wide_words ? carve(workspace, B, nclouds, N, R, R + 1) : carve(workspace, B, nclouds, N, R);
     hipStream_t st = iq::as_stream(stream);
-    int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
 
     // Repeated coalitions: narrow keep masks in table order only (a prefix route's row lists follow its permutations), and a cloud
@@ -942,8 +940,8 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         static_assert(sizeof(int32_t) * 5 <= sizeof(float) * 512, "rep_slots(B) < 4 B int32 and B / kThreads + 1 counts inside h1's (B,512) floats");
         int32_t* table = reinterpret_cast<int32_t*>(ws.h1);
         int32_t* block_cnt = B > kOrderFusedMax ? table + rep_slots(B) : nullptr;
-        if ((rc = launch_reps(keep, cloud_of, B, R, ws.bin_of, table, st, block_cnt))) return rc;
-        if ((rc = launch_compact(ws.bin_of, cloud_of, B, block_cnt, ws.slot_of, ws.item_u, ws.cloud_u, ws.n_distinct, st))) return rc;
+        IQ_TRY(launch_reps(keep, cloud_of, B, R, ws.bin_of, table, st, block_cnt));
+        IQ_TRY(launch_compact(ws.bin_of, cloud_of, B, block_cnt, ws.slot_of, ws.item_u, ws.cloud_u, ws.n_distinct, st));
         n_dev = ws.n_distinct;
         slot_item = ws.item_u;
         if (cloud_of) slot_cloud = ws.cloud_u;
@@ -954,42 +952,34 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     // bins, which nothing reads once the order is scattered
     const int32_t* item_cloud = orders ? (nclouds > 1 ? ws.bin_of : nullptr) : slot_cloud;
     if (wide_words) {
-        hipLaunchKernelGGL(pn_prepare_wide_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
-        if ((rc = iq::check_launch("pn_prepare_wide_kernel"))) return rc;
-        hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
-                           ws.rows_pre, ws.nrows_pre, N, R, wide_words, nclouds, with_centre, 1);
-        if ((rc = iq::check_launch("pn_rows_wide_kernel"))) return rc;
+        IQ_LAUNCH(pn_prepare_wide_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
+        IQ_LAUNCH(pn_rows_wide_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
+                  ws.rows_pre, ws.nrows_pre, N, R, wide_words, nclouds, with_centre, 1);
         if (orders) {
-            hipLaunchKernelGGL(pn_rows_prefix_kernel, dim3(groups), dim3(kThreads), 0, st, ws.sorted_pts, ws.roff, orders, cloud_of,
-                               ws.rows, ws.nrows, N, R, nclouds, with_centre);
-            if ((rc = iq::check_launch("pn_rows_prefix_kernel"))) return rc;
+            IQ_LAUNCH(pn_rows_prefix_kernel, dim3(groups), dim3(kThreads), 0, st, ws.sorted_pts, ws.roff, orders, cloud_of,
+                      ws.rows, ws.nrows, N, R, nclouds, with_centre);
         } else {
-            hipLaunchKernelGGL(pn_rows_wide_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
-                               ws.nrows, N, R, wide_words, nclouds, with_centre, 0);
-            if ((rc = iq::check_launch("pn_rows_wide_kernel"))) return rc;
+            IQ_LAUNCH(pn_rows_wide_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, cloud_of, ws.rows,
+                      ws.nrows, N, R, wide_words, nclouds, with_centre, 0);
         }
     } else {
-        hipLaunchKernelGGL(pn_prepare_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
-        if ((rc = iq::check_launch("pn_prepare_kernel"))) return rc;
-        hipLaunchKernelGGL(pn_rows_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
-                           ws.rows_pre, ws.nrows_pre, N, R, nclouds, with_centre, 1, nullptr, nullptr);
-        hipLaunchKernelGGL(pn_rows_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, slot_cloud, ws.rows,
-                           ws.nrows, N, R, nclouds, with_centre, 0, slot_item, n_dev);
-        if ((rc = iq::check_launch("pn_rows_kernel"))) return rc;
+        IQ_LAUNCH(pn_prepare_kernel, dim3(nclouds), dim3(kThreads), 0, st, region_id, ws.sorted_pts, ws.roff, N, R);
+        IQ_LAUNCH(pn_rows_kernel, dim3(pre_items), dim3(64), 0, st, ws.sorted_pts, ws.roff, nullptr, nullptr,
+                  ws.rows_pre, ws.nrows_pre, N, R, nclouds, with_centre, 1, nullptr, nullptr);
+        IQ_LAUNCH(pn_rows_kernel, dim3(B), dim3(64), 0, st, ws.sorted_pts, ws.roff, keep, slot_cloud, ws.rows,
+                  ws.nrows, N, R, nclouds, with_centre, 0, slot_item, n_dev);
     }
     // launch order of the coalition chains: most rows first, so the grid drains evenly
     if (B <= kOrderFusedMax) {
-        hipLaunchKernelGGL(pn_order_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.order, B, n_dev);
+        IQ_LAUNCH(pn_order_fused_kernel, dim3(1), dim3(kOrderThreads), 0, st, ws.nrows, ws.order, B, n_dev);
     } else {
-        if (hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st) != hipSuccess)
-            return iq::fail(IQ_ELAUNCH, "%s: memset failed", who);
-        hipLaunchKernelGGL(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
-                           ws.bin_of, ws.hist, B, n_dev);
-        hipLaunchKernelGGL(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
-        hipLaunchKernelGGL(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
-                           ws.bin_of, ws.hist, ws.order, B, n_dev);
+        IQ_TRY(iq::hip_ok(hipMemsetAsync(ws.hist, 0, kBins * sizeof(int32_t), st), "pn_order histogram memset"));
+        IQ_LAUNCH(pn_order_count_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st, ws.nrows,
+                  ws.bin_of, ws.hist, B, n_dev);
+        IQ_LAUNCH(pn_order_scan_kernel, dim3(1), dim3(64), 0, st, ws.hist);
+        IQ_LAUNCH(pn_order_scatter_kernel, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, st,
+                  ws.bin_of, ws.hist, ws.order, B, n_dev);
     }
-    if ((rc = iq::check_launch("pn_order kernels"))) return rc;
     ChainArgs a{};
     a.clouds = clouds;
     if (channel_first) { a.ps = 1; a.cs = N; } else { a.ps = 3; a.cs = 1; }
@@ -1013,24 +1003,21 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     a.items = pre_items;
     {
         iq::ProfileSpan span(iq::kSlotPrepool, st);
-        launch_chain<kPrepool>(a, st);
+        IQ_TRY(launch_chain<kPrepool>(a, st));
     }
-    if ((rc = iq::check_launch("pn_chain_kernel<prepool>"))) return rc;
 
     if (orders)
-        hipLaunchKernelGGL(pn_stn_prefix_kernel, dim3(groups, kFeat / 256), dim3(64), 0, st, ws.G, ws.nrows, orders, cloud_of, ws.gbuf,
-                           item_cloud ? ws.bin_of : nullptr, R, nclouds, with_centre);
+        IQ_LAUNCH(pn_stn_prefix_kernel, dim3(groups, kFeat / 256), dim3(64), 0, st, ws.G, ws.nrows, orders, cloud_of, ws.gbuf,
+                  item_cloud ? ws.bin_of : nullptr, R, nclouds, with_centre);
     else if (wide_words)
-        hipLaunchKernelGGL(pn_stn_gather_wide_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
-                           R, wide_words, nclouds, with_centre);
+        IQ_LAUNCH(pn_stn_gather_wide_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, cloud_of, ws.gbuf,
+                  R, wide_words, nclouds, with_centre);
     else
-        hipLaunchKernelGGL(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, slot_cloud, ws.gbuf,
-                           R, nclouds, with_centre, slot_item, n_dev);
-    if ((rc = iq::check_launch(orders ? "pn_stn_prefix_kernel" : wide_words ? "pn_stn_gather_wide_kernel" : "pn_stn_gather_kernel")))
-        return rc;
-    if ((rc = launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st, n_dev, nullptr, 0, true))) return rc;
+        IQ_LAUNCH(pn_stn_gather_kernel, dim3(B), dim3(kThreads), 0, st, ws.G, ws.nrows, keep, slot_cloud, ws.gbuf,
+                  R, nclouds, with_centre, slot_item, n_dev);
+    IQ_TRY(launch_linear(ws.gbuf, kFeat, w->stn_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true));
+    IQ_TRY(launch_linear(ws.h1, 512, w->stn_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true));
+    IQ_TRY(launch_linear(ws.h2, 256, w->stn_fc3, ws.trans, 9, B, 0, st, n_dev, nullptr, 0, true));
 
     // 2. feature-STN chain over each coalition's distinct points
     a.cloud_of = item_cloud; a.trans = ws.trans;
@@ -1049,11 +1036,10 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         a.w2_bf3 = reinterpret_cast<const unsigned short*>(w->fstn_c2_bf3);
         {
             iq::ProfileSpan span(iq::kSlotFstn, st);
-            launch_chain<kFstn>(a, st);
+            IQ_TRY(launch_chain<kFstn>(a, st));
         }
-        if ((rc = iq::check_launch("pn_chain_kernel<fstn>"))) return rc;
-        if ((rc = launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true))) return rc;
-        if ((rc = launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+        IQ_TRY(launch_linear(ws.gbuf, kFeat, w->fstn_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true));
+        IQ_TRY(launch_linear(ws.h1, 512, w->fstn_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true));
         // fstn.fc3 (256 -> 4096, 70 % of the heads' FLOP) on the bf16 matrix pipe like the other wide layers.  The descriptor brings
         // no bf16x3 image of it (its rows are permuted by iq_pack_fstn_fc3; the packed weight set is what it has always been), so the
         // image is split off the float32 one here, per call: 1 M weights, a few microseconds, and nothing to go stale when a
@@ -1061,17 +1047,16 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
         iq_dense_layer fc3 = w->fstn_fc3;
         IQ_REQUIRE(fc3.cin == 256 && fc3.cout == 4096, "%s: fstn_fc3 is %d -> %d, not 256 -> 4096", who, fc3.cin, fc3.cout);
         if (!fc3.w_bf3 && iq::twin() != iq::kTwinDenseFp32) {
-            if ((rc = iq::launch_split_bf3(fc3.w, ws.fc3_bf3, 4096, 256, st))) return rc;
+            IQ_TRY(iq::launch_split_bf3(fc3.w, ws.fc3_bf3, 4096, 256, st));
             fc3.w_bf3 = ws.fc3_bf3;
         }
-        if ((rc = launch_linear(ws.h2, 256, fc3, tfp, 4096, B, 0, st, n_dev, nullptr, 0, true))) return rc;
+        IQ_TRY(launch_linear(ws.h2, 256, fc3, tfp, 4096, B, 0, st, n_dev, nullptr, 0, true));
     } else {
         // feature_transform = False (models/pointnet.py:62-63,72-78): no feature STN.  The trunk multiplies by the packed
         // IDENTITY instead (fstn_fc3.b = iq_pack_fstn_fc3 of a zero layer): sum_k f[k] I[k][n] = f[n] + zeros, exact.
         IQ_REQUIRE(w->fstn_fc3.b, "%s: without a feature STN, fstn_fc3.b must hold the packed identity", who);
-        hipLaunchKernelGGL(pn_fill_rows_kernel, dim3((unsigned)(((size_t)B * 1024 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                           tfp, w->fstn_fc3.b, B);
-        if ((rc = iq::check_launch("pn_fill_rows_kernel"))) return rc;
+        IQ_LAUNCH(pn_fill_rows_kernel, dim3((unsigned)(((size_t)B * 1024 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                  tfp, w->fstn_fc3.b, B);
     }
 
     // 3. trunk chain
@@ -1083,22 +1068,21 @@ int pointnet_coalitions(const iq_pointnet_weights* w, const float* clouds, const
     a.w2_bf3 = reinterpret_cast<const unsigned short*>(w->feat_c2_bf3);
     {
         iq::ProfileSpan span(iq::kSlotTrunk, st);
-        launch_chain<kTrunk>(a, st);
+        IQ_TRY(launch_chain<kTrunk>(a, st));
     }
-    if ((rc = iq::check_launch("pn_chain_kernel<trunk>"))) return rc;
-    if ((rc = launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true))) return rc;
-    if ((rc = launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true))) return rc;
+    IQ_TRY(launch_linear(ws.gbuf, kFeat, w->cls_fc1, ws.h1, 512, B, 1, st, n_dev, nullptr, 0, true));
+    IQ_TRY(launch_linear(ws.h1, 512, w->cls_fc2, ws.h2, 256, B, 1, st, n_dev, nullptr, 0, true));
     if (!n_dev) return launch_linear(ws.h2, 256, w->cls_fc3, logits, w->cls_fc3.cout, B, 0, st, nullptr, nullptr, 0, true);
     // the logits by slot where h1 was (cls_fc2 has read it), then every item its slot's results
     const int ncls = w->cls_fc3.cout;
     IQ_REQUIRE(ncls <= 512, "%s: %d classes", who, ncls);
-    if ((rc = launch_linear(ws.h2, 256, w->cls_fc3, ws.h1, ncls, B, 0, st, n_dev, nullptr, 0, true))) return rc;
-    hipLaunchKernelGGL(pn_expand_logits_kernel, dim3((unsigned)(((size_t)B * ncls + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                       ws.h1, ws.slot_of, logits, B, ncls);
+    IQ_TRY(launch_linear(ws.h2, 256, w->cls_fc3, ws.h1, ncls, B, 0, st, n_dev, nullptr, 0, true));
+    IQ_LAUNCH(pn_expand_logits_kernel, dim3((unsigned)(((size_t)B * ncls + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+              ws.h1, ws.slot_of, logits, B, ncls);
     if (trans_feat_packed || crt_points)
-        hipLaunchKernelGGL(pn_expand_rows_kernel, dim3(B), dim3(kThreads), 0, st, ws.slot_of, ws.item_u, ws.tfp, trans_feat_packed,
-                           crt_points);
-    return iq::check_launch("pn_expand kernels");
+        IQ_LAUNCH(pn_expand_rows_kernel, dim3(B), dim3(kThreads), 0, st, ws.slot_of, ws.item_u, ws.tfp, trans_feat_packed,
+                  crt_points);
+    return IQ_OK;
 }
 
 }  // namespace
@@ -1140,7 +1124,7 @@ extern "C" int iq_debug_pointnet_slots(const uint64_t* keep, const int32_t* clou
     hipStream_t st = iq::as_stream(stream);
     int32_t *rep = reinterpret_cast<int32_t*>(scratch), *table = rep + b;
     int32_t* block_cnt = B > kOrderFusedMax ? table + rep_slots(B) : nullptr;
-    if (int rc = launch_reps(keep, cloud_of, B, R, rep, table, st, block_cnt)) return rc;
+    IQ_TRY(launch_reps(keep, cloud_of, B, R, rep, table, st, block_cnt));
     return launch_compact(rep, cloud_of, B, block_cnt, slots_out, slots_out + b, slots_out + 2 * b, slots_out + 3 * b, st);
 }
 

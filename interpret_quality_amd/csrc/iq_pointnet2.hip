@@ -511,12 +511,12 @@ int launch_group_t(GroupArgs a, int B, hipStream_t st) {
     // twins kTwinGroupFp32 / kTwinGroupFp32Chunk64: the fp32-MFMA kernel with 32- / 64-row chunks (A/B and tests)
     const bool fp32 = iq::twin() == iq::kTwinGroupFp32 || iq::twin() == iq::kTwinGroupFp32Chunk64;
     if (C1 == 128 && C2 == 128 && C3 == 256 && a.w2_bf3 && a.w3_bf3 && !fp32)
-        hipLaunchKernelGGL(pn2_group_bf3_kernel, grid, dim3(kThreads), 0, st, a);
+        IQ_LAUNCH(pn2_group_bf3_kernel, grid, dim3(kThreads), 0, st, a);
     else if (C3 >= 256 && iq::twin() != iq::kTwinGroupFp32Chunk64)
-        hipLaunchKernelGGL((pn2_group_kernel<C1, C2, C3, 32>), grid, dim3(kThreads), 0, st, a);
+        IQ_LAUNCH((pn2_group_kernel<C1, C2, C3, 32>), grid, dim3(kThreads), 0, st, a);
     else
-        hipLaunchKernelGGL((pn2_group_kernel<C1, C2, C3, 64>), grid, dim3(kThreads), 0, st, a);
-    return iq::check_launch("pn2_group_kernel");
+        IQ_LAUNCH((pn2_group_kernel<C1, C2, C3, 64>), grid, dim3(kThreads), 0, st, a);
+    return IQ_OK;
 }
 
 // FLOP the MFMA tiles of pn2_group_kernel execute for the block table just built (profiling only: reads the per-cloud block
@@ -553,10 +553,8 @@ int launch_group(const iq_pn2_scale& sc, GroupArgs a, const int32_t* n_unique, i
     IQ_REQUIRE(sc.l3.cin == c2, "pointnet2 scale: layer sizes do not chain");
     IQ_REQUIRE(a.S <= 4 * kThreads, "pointnet2: S=%d too large for the block scan", a.S);
     IQ_REQUIRE(a.maxblocks <= 8192, "pointnet2: %d groups x %d samples exceed the block table", a.S, a.K);
-    hipLaunchKernelGGL(pn2_blocks_kernel, dim3(B), dim3(kThreads), 0, st, a.cnt, n_unique, const_cast<int32_t*>(a.block_start),
-                       const_cast<uint16_t*>(a.blockmap), a.S, a.maxblocks);
-    int rc = iq::check_launch("pn2_blocks_kernel");
-    if (rc) return rc;
+    IQ_LAUNCH(pn2_blocks_kernel, dim3(B), dim3(kThreads), 0, st, a.cnt, n_unique, const_cast<int32_t*>(a.block_start),
+              const_cast<uint16_t*>(a.blockmap), a.S, a.maxblocks);
     if (c1 == 32 && c2 == 32 && c3 == 64) return launch_group_t<32, 32, 64>(a, B, st);
     if (c1 == 64 && c2 == 64 && c3 == 128) return launch_group_t<64, 64, 128>(a, B, st);
     if (c1 == 64 && c2 == 96 && c3 == 128) return launch_group_t<64, 96, 128>(a, B, st);
@@ -578,9 +576,9 @@ int launch_ball(const float* xyz, const float* new_xyz, int ldc, const iq_pn2_sc
         a.idx[q] = idx[q];
         a.cnt[q] = cnt[q];
     }
-    hipLaunchKernelGGL(ball_query_kernel<int16_t>, dim3((S + kThreads - 1) / kThreads, B), dim3(kThreads),
-                       (size_t)N * 4 * sizeof(float), st, a);
-    return iq::check_launch("ball_query_kernel");
+    IQ_LAUNCH(ball_query_kernel<int16_t>, dim3((S + kThreads - 1) / kThreads, B), dim3(kThreads),
+              (size_t)N * 4 * sizeof(float), st, a);
+    return IQ_OK;
 }
 
 // ==== sa1 from pair tables (iq_pointnet2_coalitions) ==================================================================
@@ -1064,9 +1062,9 @@ extern "C" int iq_ball_query(const float* xyz, const float* new_xyz, float radiu
     a.r2[0] = (float)((double)radius * (double)radius);
     a.K[0] = K;
     a.idx[0] = idx;
-    hipLaunchKernelGGL(ball_query_kernel<int32_t>, dim3((S + kThreads - 1) / kThreads, B), dim3(kThreads),
-                       (size_t)N * 4 * sizeof(float), iq::as_stream(stream), a);
-    return iq::check_launch("ball_query_kernel");
+    IQ_LAUNCH(ball_query_kernel<int32_t>, dim3((S + kThreads - 1) / kThreads, B), dim3(kThreads),
+              (size_t)N * 4 * sizeof(float), iq::as_stream(stream), a);
+    return IQ_OK;
 }
 
 namespace {
@@ -1074,28 +1072,24 @@ namespace {
 // The network on B materialised clouds xyz (B,N,3).  tab != null: sa1 scales with tab->use[q] come from pair tables.
 int run_pn2(const iq_pointnet2_weights* w, const float* xyz, float* logits, const Ws2& s, int B, int N, hipStream_t st,
             const PairTabs* tab, const GatherArgs* gat) {
-    int rc;
     constexpr int S1 = 512, S2 = 128, F1 = 320, LD3 = 648;
 
     // ---- sa1 ---------------------------------------------------------------------------------------
-    if ((rc = iq::launch_fps(xyz, s.fps1, s.nu1, B, N, S1, st))) return rc;
-    hipLaunchKernelGGL(gather_xyz_kernel, dim3((B * S1 + 255) / 256), dim3(256), 0, st, xyz, s.fps1, s.nx1, 3, N, S1, B * S1);
-    if ((rc = iq::check_launch("gather_xyz_kernel"))) return rc;
+    IQ_TRY(iq::launch_fps(xyz, s.fps1, s.nu1, B, N, S1, st));
+    IQ_LAUNCH(gather_xyz_kernel, dim3((B * S1 + 255) / 256), dim3(256), 0, st, xyz, s.fps1, s.nx1, 3, N, S1, B * S1);
     if (tab && tab->ball_bits[0]) {
         BitBallArgs ba{};
         for (int q = 0; q < 3; ++q) { ba.bits[q] = tab->ball_bits[q]; ba.idx[q] = s.idx1[q]; ba.cnt[q] = s.cnt1[q]; ba.K[q] = w->sa1[q].nsample; }
         ba.kept = tab->kept_bits; ba.fps = s.fps1; ba.n_unique = s.nu1; ba.cloud_of = gat->cloud_of;
         ba.N = N; ba.S = S1; ba.B = B; ba.nclouds = gat->nclouds;
         for (int q = 0; q < 3; ++q) ba.touch[q] = tab->use[q] ? tab->touch[q] : nullptr;
-        hipLaunchKernelGGL(pn2_bitball_kernel, dim3((S1 + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, ba);
-        if ((rc = iq::check_launch("pn2_bitball_kernel"))) return rc;
-    } else if ((rc = launch_ball(xyz, s.nx1, 3, w->sa1, 3, s.idx1, s.cnt1, nullptr, B, N, S1, st))) {
-        return rc;
+        IQ_LAUNCH(pn2_bitball_kernel, dim3((S1 + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, ba);
+    } else {
+        IQ_TRY(launch_ball(xyz, s.nx1, 3, w->sa1, 3, s.idx1, s.cnt1, nullptr, B, N, S1, st));
     }
     // the grouped kernel merges straddling groups with an atomic max (zero-initialised output); the table gather stores
     const bool all_tables = tab && tab->use[0] && tab->use[1] && tab->use[2];
-    if (!all_tables && hipMemsetAsync(s.l1, 0, (size_t)B * S1 * F1 * sizeof(float), st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "iq_pointnet2_forward: memset failed");
+    if (!all_tables) IQ_TRY(iq::hip_ok(hipMemsetAsync(s.l1, 0, (size_t)B * S1 * F1 * sizeof(float), st), "iq_pointnet2_forward: sa1 memset"));
     int col = 0;
     for (int q = 0; q < 3; ++q) {
         IQ_REQUIRE(w->sa1[q].nsample <= 128 && w->sa2[q].nsample <= 128, "pointnet2: nsample > 128");
@@ -1107,9 +1101,8 @@ int run_pn2(const iq_pointnet2_weights* w, const float* xyz, float* logits, cons
             g.out = s.l1 + col; g.ldo = F1; g.N = N; g.S = S1; g.K = w->sa1[q].nsample; g.B = B;
             const int gpb = kThreads / (g.C3 / 4);
             iq::ProfileSpan span(iq::kSlotPrepool, st);
-            hipLaunchKernelGGL((g.kept_bits ? pt_gather_kernel<true> : pt_gather_kernel<false>),
-                               dim3((unsigned)((B + 7) / 8 * 8 * ((S1 + gpb - 1) / gpb))), dim3(kThreads), 0, st, g);
-            if ((rc = iq::check_launch("pt_gather_kernel"))) return rc;
+            IQ_LAUNCH((g.kept_bits ? pt_gather_kernel<true> : pt_gather_kernel<false>),
+                      dim3((unsigned)((B + 7) / 8 * 8 * ((S1 + gpb - 1) / gpb))), dim3(kThreads), 0, st, g);
             col += w->sa1[q].l3.cout;
             continue;
         }
@@ -1119,21 +1112,18 @@ int run_pn2(const iq_pointnet2_weights* w, const float* xyz, float* logits, cons
         a.U = nullptr; a.ldu = 0;
         a.out = s.l1 + col; a.ldo = F1; a.N = N; a.S = S1;
         iq::ProfileSpan span(iq::kSlotPrepool, st);
-        if ((rc = launch_group(w->sa1[q], a, s.nu1, B, st))) return rc;
+        IQ_TRY(launch_group(w->sa1[q], a, s.nu1, B, st));
         col += w->sa1[q].l3.cout;
     }
     IQ_REQUIRE(col == F1, "pointnet2: sa1 output channels %d != 320", col);
-    hipLaunchKernelGGL(fill_dup_rows_kernel, dim3(S1, B), dim3(64), 0, st, s.l1, F1, S1, 0, F1, s.nu1);
-    if ((rc = iq::check_launch("fill_dup_rows_kernel"))) return rc;
+    IQ_LAUNCH(fill_dup_rows_kernel, dim3(S1, B), dim3(64), 0, st, s.l1, F1, S1, 0, F1, s.nu1);
 
     // ---- sa2 ---------------------------------------------------------------------------------------
-    if ((rc = iq::launch_fps(s.nx1, s.fps2, s.nu2, B, S1, S2, st))) return rc;
-    if (hipMemsetAsync(s.a3, 0, (size_t)B * S2 * LD3 * sizeof(float), st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "iq_pointnet2_forward: memset failed");
-    hipLaunchKernelGGL(gather_xyz_kernel, dim3((B * S2 + 255) / 256), dim3(256), 0, st, s.nx1, s.fps2, s.a3, LD3, S1, S2, B * S2);
-    if ((rc = iq::check_launch("gather_xyz_kernel"))) return rc;
-    if ((rc = launch_ball(s.nx1, s.a3, LD3, w->sa2, 3, s.idx2, s.cnt2, s.nu1, B, S1, S2, st))) return rc;
-    if ((rc = iq::launch_linear(s.l1, F1, w->sa2_u, s.U, F1, B * S1, 0, st))) return rc;  // U = W_f f_p + b (all scales)
+    IQ_TRY(iq::launch_fps(s.nx1, s.fps2, s.nu2, B, S1, S2, st));
+    IQ_TRY(iq::hip_ok(hipMemsetAsync(s.a3, 0, (size_t)B * S2 * LD3 * sizeof(float), st), "iq_pointnet2_forward: sa2 memset"));
+    IQ_LAUNCH(gather_xyz_kernel, dim3((B * S2 + 255) / 256), dim3(256), 0, st, s.nx1, s.fps2, s.a3, LD3, S1, S2, B * S2);
+    IQ_TRY(launch_ball(s.nx1, s.a3, LD3, w->sa2, 3, s.idx2, s.cnt2, s.nu1, B, S1, S2, st));
+    IQ_TRY(iq::launch_linear(s.l1, F1, w->sa2_u, s.U, F1, B * S1, 0, st));  // U = W_f f_p + b (all scales)
     col = 0;
     int ucol = 0;
     for (int q = 0; q < 3; ++q) {
@@ -1143,26 +1133,24 @@ int run_pn2(const iq_pointnet2_weights* w, const float* xyz, float* logits, cons
         a.U = s.U + ucol; a.ldu = F1;
         a.out = s.a3 + 3 + col; a.ldo = LD3; a.N = S1; a.S = S2;
         iq::ProfileSpan span(iq::kSlotFstn, st);
-        if ((rc = launch_group(w->sa2[q], a, s.nu2, B, st, true, w->sa2_l2_bf3[q], w->sa2_l3_bf3[q]))) return rc;
+        IQ_TRY(launch_group(w->sa2[q], a, s.nu2, B, st, true, w->sa2_l2_bf3[q], w->sa2_l3_bf3[q]));
         col += w->sa2[q].l3.cout;
         ucol += w->sa2[q].l2.cin;
     }
     IQ_REQUIRE(col == 640 && ucol == F1, "pointnet2: sa2 channels %d / %d", col, ucol);
-    hipLaunchKernelGGL(fill_dup_rows_kernel, dim3(S2, B), dim3(64), 0, st, s.a3, LD3, S2, 3, 640, s.nu2);
-    if ((rc = iq::check_launch("fill_dup_rows_kernel"))) return rc;
+    IQ_LAUNCH(fill_dup_rows_kernel, dim3(S2, B), dim3(64), 0, st, s.a3, LD3, S2, 3, 640, s.nu2);
 
     // ---- sa3 (group all) + head --------------------------------------------------------------------
     {
         iq::ProfileSpan span(iq::kSlotTrunk, st);
-        if ((rc = iq::launch_linear(s.a3, LD3, w->sa3_l1, s.h1, 256, B * S2, 1, st))) return rc;
-        if ((rc = iq::launch_linear(s.h1, 256, w->sa3_l2, s.h2, 512, B * S2, 1, st))) return rc;
-        if ((rc = iq::launch_linear(s.h2, 512, w->sa3_l3, s.h3, 1024, B * S2, 1, st))) return rc;
+        IQ_TRY(iq::launch_linear(s.a3, LD3, w->sa3_l1, s.h1, 256, B * S2, 1, st));
+        IQ_TRY(iq::launch_linear(s.h1, 256, w->sa3_l2, s.h2, 512, B * S2, 1, st));
+        IQ_TRY(iq::launch_linear(s.h2, 512, w->sa3_l3, s.h3, 1024, B * S2, 1, st));
     }
-    hipLaunchKernelGGL(colmax_kernel, dim3(1024 / 256, B), dim3(256), 0, st, s.h3, s.g, S2, 1024);
-    if ((rc = iq::check_launch("colmax_kernel"))) return rc;
-    if ((rc = iq::launch_linear(s.g, 1024, w->fc1, s.f1, 512, B, 1, st))) return rc;
-    if ((rc = iq::launch_linear(s.f1, 512, w->fc2, s.f2, 256, B, 1, st))) return rc;
-    if ((rc = iq::launch_linear(s.f2, 256, w->fc3, logits, w->fc3.cout, B, 0, st))) return rc;
+    IQ_LAUNCH(colmax_kernel, dim3(1024 / 256, B), dim3(256), 0, st, s.h3, s.g, S2, 1024);
+    IQ_TRY(iq::launch_linear(s.g, 1024, w->fc1, s.f1, 512, B, 1, st));
+    IQ_TRY(iq::launch_linear(s.f1, 512, w->fc2, s.f2, 256, B, 1, st));
+    IQ_TRY(iq::launch_linear(s.f2, 256, w->fc3, logits, w->fc3.cout, B, 0, st));
     return IQ_OK;
 }
 
@@ -1249,28 +1237,26 @@ static int pointnet2_coalitions(const iq_pointnet2_weights* w, const float* clou
     Ws2 s = carve2(workspace, B, w);
     WsC t = carve_c(reinterpret_cast<char*>(workspace) + base_bytes, B, nclouds, N);
     hipStream_t st = iq::as_stream(stream);
-    int rc;
     iq::ProfileSpan call_span(iq::kSlotCall, st);
     const int n1 = N + 1;
 
     if (W)
-        hipLaunchKernelGGL(pn2_mask_wide_kernel, dim3((B + kMaskWideWaves - 1) / kMaskWideWaves), dim3(64 * kMaskWideWaves), 0, st,
-                           clouds, centers, region_id, keep, cloud_of, t.X, N, B, nclouds, R, W);
+        IQ_LAUNCH(pn2_mask_wide_kernel, dim3((B + kMaskWideWaves - 1) / kMaskWideWaves), dim3(64 * kMaskWideWaves), 0, st,
+                  clouds, centers, region_id, keep, cloud_of, t.X, N, B, nclouds, R, W);
     else
-        hipLaunchKernelGGL(pn2_mask_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, clouds, centers, region_id, keep, cloud_of,
-                           t.X, N, B, nclouds);
-    hipLaunchKernelGGL(pt_points_kernel, dim3((nclouds * n1 + 255) / 256), dim3(256), 0, st, clouds, centers, t.P, N, nclouds);
+        IQ_LAUNCH(pn2_mask_kernel, dim3((B * N + 255) / 256), dim3(256), 0, st, clouds, centers, region_id, keep, cloud_of,
+                  t.X, N, B, nclouds);
+    IQ_LAUNCH(pt_points_kernel, dim3((nclouds * n1 + 255) / 256), dim3(256), 0, st, clouds, centers, t.P, N, nclouds);
     float r2[3];
     for (int q = 0; q < 3; ++q) r2[q] = (float)((double)w->sa1[q].radius * (double)w->sa1[q].radius);
     IQ_REQUIRE(r2[0] <= r2[1] && r2[1] <= r2[2], "iq_pointnet2_coalitions: sa1 radii must ascend");
-    hipLaunchKernelGGL(pt_count_kernel, dim3(n1, nclouds), dim3(kThreads), 0, st, t.P, N, r2[0], r2[1], r2[2], t.cntp);
-    hipLaunchKernelGGL(pt_scan_kernel, dim3(nclouds * 3), dim3(1024), 0, st, t.cntp, t.off, t.total, N);
-    if ((rc = iq::check_launch("pt_scan_kernel"))) return rc;
+    IQ_LAUNCH(pt_count_kernel, dim3(n1, nclouds), dim3(kThreads), 0, st, t.P, N, r2[0], r2[1], r2[2], t.cntp);
+    IQ_LAUNCH(pt_scan_kernel, dim3(nclouds * 3), dim3(1024), 0, st, t.cntp, t.off, t.total, N);
     // the one host round trip of the call: pair counts decide, per scale, between the table and the grouped MLP
     int32_t totals[64 * 3];
-    if (hipMemcpyAsync(totals, t.total, (size_t)nclouds * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return iq::fail(IQ_ELAUNCH, "iq_pointnet2_coalitions: reading the pair counts failed");
+    const char* what = "iq_pointnet2_coalitions: reading the pair counts";
+    IQ_TRY(iq::hip_ok(hipMemcpyAsync(totals, t.total, (size_t)nclouds * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st), what));
+    IQ_TRY(iq::hip_ok(hipStreamSynchronize(st), what));
     const size_t cap = (size_t)nclouds * kPairFan * n1;
     PairTabs tab{};
     for (int q = 0; q < 3; ++q) {
@@ -1283,51 +1269,47 @@ static int pointnet2_coalitions(const iq_pointnet2_weights* w, const float* clou
         if (!tab.use[q]) continue;
         int row0 = 0;
         for (int c = 0; c < nclouds; ++c) {  // rows of cloud c: [row0, row0 + totals)
-            hipLaunchKernelGGL(pt_fill_kernel, dim3(n1, 1), dim3(64), 0, st, t.P + (size_t)c * n1 * 4, N, r2[q],
-                               t.off + ((size_t)c * 3 + q) * n1, row0, t.map[q] + (size_t)c * n1 * n1, t.pairs);
+            IQ_LAUNCH(pt_fill_kernel, dim3(n1, 1), dim3(64), 0, st, t.P + (size_t)c * n1 * 4, N, r2[q],
+                      t.off + ((size_t)c * 3 + q) * n1, row0, t.map[q] + (size_t)c * n1 * n1, t.pairs);
             const int nr = totals[c * 3 + q];
             if (nr > 0) {
-                hipLaunchKernelGGL(pt_l1_kernel, dim3((unsigned)(((size_t)nr * sc.l2.cin + 255) / 256)), dim3(256), 0, st,
-                                   t.P + (size_t)c * n1 * 4, t.pairs + row0, sc.w1x, t.h1 + (size_t)row0 * sc.l2.cin, sc.l2.cin, nr);
+                IQ_LAUNCH(pt_l1_kernel, dim3((unsigned)(((size_t)nr * sc.l2.cin + 255) / 256)), dim3(256), 0, st,
+                          t.P + (size_t)c * n1 * 4, t.pairs + row0, sc.w1x, t.h1 + (size_t)row0 * sc.l2.cin, sc.l2.cin, nr);
             }
             row0 += nr;
         }
-        if ((rc = iq::check_launch("pt_fill_kernel"))) return rc;
         if (row0 > 0) {
-            if ((rc = iq::launch_linear(t.h1, sc.l2.cin, sc.l2, t.h2, sc.l2.cout, row0, 1, st))) return rc;
-            if ((rc = iq::launch_linear(t.h2, sc.l2.cout, sc.l3, t.feat[q], sc.l3.cout, row0, 1, st))) return rc;
+            IQ_TRY(iq::launch_linear(t.h1, sc.l2.cin, sc.l2, t.h2, sc.l2.cout, row0, 1, st));
+            IQ_TRY(iq::launch_linear(t.h2, sc.l2.cout, sc.l3, t.feat[q], sc.l3.cout, row0, 1, st));
         }
         // region-reduced rows of this scale (the twin: member walk only, A/B and tests; a wide game: the tables hold 64 regions)
         if (iq::twin() != iq::kTwinPn2MemberWalk && !W) {
             int r0c = 0;
             for (int c = 0; c < nclouds; ++c) {
-                hipLaunchKernelGGL(pt_regtab_kernel, dim3(n1), dim3(kThreads), (size_t)kRegSlots * sc.l3.cout * 4, st, t.feat[q], t.pairs,
-                                   t.off + ((size_t)c * 3 + q) * n1, t.cntp + ((size_t)c * 3 + q) * n1, r0c, region_id + (size_t)c * N, N,
-                                   sc.nsample, sc.l3.cout, t.regtab[q] + (size_t)c * n1 * kRegSlots * sc.l3.cout, t.touch[q] + (size_t)c * n1);
+                IQ_LAUNCH(pt_regtab_kernel, dim3(n1), dim3(kThreads), (size_t)kRegSlots * sc.l3.cout * 4, st, t.feat[q], t.pairs,
+                          t.off + ((size_t)c * 3 + q) * n1, t.cntp + ((size_t)c * 3 + q) * n1, r0c, region_id + (size_t)c * N, N,
+                          sc.nsample, sc.l3.cout, t.regtab[q] + (size_t)c * n1 * kRegSlots * sc.l3.cout, t.touch[q] + (size_t)c * n1);
                 r0c += totals[c * 3 + q];
             }
-            if ((rc = iq::check_launch("pt_regtab_kernel"))) return rc;
             tab.touch[q] = t.touch[q]; tab.regtab[q] = t.regtab[q];
         }
     }
     if (tab.use[0] && tab.use[1] && tab.use[2] && N <= 1024) {
         // sa1's ball query by bit operations on the row maps just built
         for (int q = 0; q < 3; ++q) {
-            hipLaunchKernelGGL(pt_bits_kernel, dim3(n1, nclouds), dim3(64), 0, st, t.map[q], t.ball_bits[q], n1);
+            IQ_LAUNCH(pt_bits_kernel, dim3(n1, nclouds), dim3(64), 0, st, t.map[q], t.ball_bits[q], n1);
             tab.ball_bits[q] = t.ball_bits[q];
         }
         if (!W) {
-            hipLaunchKernelGGL(pn2_kept_bits_kernel<false>, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N,
-                               nclouds, 64, 0);
-            if ((rc = iq::check_launch("pn2_kept_bits_kernel"))) return rc;
+            IQ_LAUNCH(pn2_kept_bits_kernel<false>, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N,
+                      nclouds, 64, 0);
         }
         tab.kept_bits = t.kept_bits;
     }
     GatherArgs g{};
     g.region_id = region_id; g.keep = keep; g.cloud_of = cloud_of; g.nclouds = nclouds;
     if (W) {   // the bitmap whatever the scales run on: the gather kernel of a wide game takes "kept" from it
-        hipLaunchKernelGGL(pn2_kept_bits_kernel<true>, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N, nclouds, R, W);
-        if ((rc = iq::check_launch("pn2_kept_bits_kernel"))) return rc;
+        IQ_LAUNCH(pn2_kept_bits_kernel<true>, dim3(B), dim3(64), 0, st, region_id, keep, cloud_of, t.kept_bits, N, nclouds, R, W);
         g.keep = nullptr; g.kept_bits = t.kept_bits;
     }
     return run_pn2(w, t.X, logits, s, B, N, st, &tab, &g);

@@ -891,25 +891,25 @@ __global__ __launch_bounds__(kThreads, L3V == 3 ? 2 : 3) void pn_chain_kernel(Ch
 }
 
 template <int MODE>
-void launch_chain(const ChainArgs& a, hipStream_t st) {
+int launch_chain(const ChainArgs& a, hipStream_t st) {
     // twins kTwinChainL3Fp32 / kTwinChainL3Fp32NoTail16: layer 3 on the fp32 MFMA (round 3's kernel; A/B and tests)
-    const bool fp32_l3 = iq::twin() == iq::kTwinChainL3Fp32 || iq::twin() == iq::kTwinChainL3Fp32NoTail16;
-    const bool bf3 = a.w3_bf3 && a.w2_bf3 && !fp32_l3;
+    const bool bf3 = a.w3_bf3 && a.w2_bf3 && iq::twin() != iq::kTwinChainL3Fp32 && iq::twin() != iq::kTwinChainL3Fp32NoTail16;
     if constexpr (MODE == kTrunk) {
         if (a.argrow) {
-            if (bf3) hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 3, true>), dim3(a.items), dim3(kThreads), 0, st, a);
-            else     hipLaunchKernelGGL((pn_chain_kernel<kTrunk, 2, true>), dim3(a.items), dim3(kThreads), 0, st, a);
-            return;
+            if (bf3) IQ_LAUNCH((pn_chain_kernel<kTrunk, 3, true>), dim3(a.items), dim3(kThreads), 0, st, a);
+            else     IQ_LAUNCH((pn_chain_kernel<kTrunk, 2, true>), dim3(a.items), dim3(kThreads), 0, st, a);
+            return IQ_OK;
         }
     }
     if constexpr (MODE != kPrepool) {
         if (bf3) {   // the product path: 96-row chunks; twin kTwinChainL3Single: 64-row chunks, one n-tile per pass (its bitwise reference)
-            if (a.l3_single) hipLaunchKernelGGL((pn_chain_kernel<MODE - kFstn + kFstn64, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
-            else             hipLaunchKernelGGL((pn_chain_kernel<MODE, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
-            return;
+            if (a.l3_single) IQ_LAUNCH((pn_chain_kernel<MODE - kFstn + kFstn64, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
+            else             IQ_LAUNCH((pn_chain_kernel<MODE, 3>), dim3(a.items), dim3(kThreads), 0, st, a);
+            return IQ_OK;
         }
     }
-    hipLaunchKernelGGL((pn_chain_kernel<MODE, 2>), dim3(a.items), dim3(kThreads), 0, st, a);
+    IQ_LAUNCH((pn_chain_kernel<MODE, 2>), dim3(a.items), dim3(kThreads), 0, st, a);
+    return IQ_OK;
 }
 
 }  // namespace

@@ -150,9 +150,8 @@ extern "C" int iq_reward(const float* logits, int label, int modified, float* v,
     IQ_REQUIRE(label >= 0 && label < C, "iq_reward: label %d not in [0,%d)", label, C);
     if (B == 0) return IQ_OK;
     IQ_REQUIRE(logits && v, "iq_reward: null pointer");
-    hipLaunchKernelGGL(reward_kernel, dim3((B + 255) / 256), dim3(256), 0, iq::as_stream(stream),
-                       logits, label, modified, v, B, C);
-    return iq::check_launch("reward_kernel");
+    IQ_LAUNCH(reward_kernel, dim3((B + 255) / 256), dim3(256), 0, iq::as_stream(stream), logits, label, modified, v, B, C);
+    return IQ_OK;
 }
 
 extern "C" int iq_shapley_accum(const float* v, const int32_t* orders, double* sv_rows, double* phi_sum,
@@ -164,14 +163,10 @@ extern "C" int iq_shapley_accum(const float* v, const int32_t* orders, double* s
     IQ_REQUIRE(S == 0 || (v && orders), "iq_shapley_accum: null input");
     hipStream_t st = iq::as_stream(stream);
     if (S > 0) {
-        hipLaunchKernelGGL(shapley_scatter_kernel, dim3((S * R + 255) / 256), dim3(256), 0, st,
-                           v, orders, sv_rows, R, S);
-        int rc = iq::check_launch("shapley_scatter_kernel");
-        if (rc) return rc;
+        IQ_LAUNCH(shapley_scatter_kernel, dim3((S * R + 255) / 256), dim3(256), 0, st, v, orders, sv_rows, R, S);
     }
-    hipLaunchKernelGGL(shapley_sum_kernel, dim3(1), dim3(iq::kSumThreads), 0, st, sv_rows, phi_sum, snap_counts,
-                       n_snap, snaps, R, S);
-    return iq::check_launch("shapley_sum_kernel");
+    IQ_LAUNCH(shapley_sum_kernel, dim3(1), dim3(iq::kSumThreads), 0, st, sv_rows, phi_sum, snap_counts, n_snap, snaps, R, S);
+    return IQ_OK;
 }
 
 extern "C" int iq_reward_classes(const float* logits, const int32_t* labels, int G, int modified, float* v, size_t ldv, int B, int C,
@@ -188,9 +183,9 @@ extern "C" int iq_reward_classes(const float* logits, const int32_t* labels, int
     }
     if (B == 0) return IQ_OK;
     IQ_REQUIRE(logits && v, "iq_reward_classes: null pointer");
-    hipLaunchKernelGGL(reward_classes_kernel, dim3((unsigned)(((long long)B + kClsRows - 1) / kClsRows)), dim3(kClsRows), 0,
-                       iq::as_stream(stream), logits, lab, G, modified, v, ldv, B, C);
-    return iq::check_launch("reward_classes_kernel");
+    IQ_LAUNCH(reward_classes_kernel, dim3((unsigned)(((long long)B + kClsRows - 1) / kClsRows)), dim3(kClsRows), 0,
+              iq::as_stream(stream), logits, lab, G, modified, v, ldv, B, C);
+    return IQ_OK;
 }
 
 extern "C" size_t iq_shapley_games_scratch_bytes(int R, int S, int G) {
@@ -214,20 +209,17 @@ extern "C" int iq_shapley_accum_games(const float* v, size_t ldv, const int32_t*
     uint16_t* pos = static_cast<uint16_t*>(scratch);
     if (S > 0) {
         const int per = kInvEntries / R;
-        hipLaunchKernelGGL(invert_orders_kernel, dim3((S + per - 1) / per), dim3(kInvThreads), 0, st, orders, pos, R, S);
-        int rc = iq::check_launch("invert_orders_kernel");
-        if (rc) return rc;
+        IQ_LAUNCH(invert_orders_kernel, dim3((S + per - 1) / per), dim3(kInvThreads), 0, st, orders, pos, R, S);
     }
-    hipLaunchKernelGGL(shapley_sum_games_kernel, dim3((R + 63) / 64, G), dim3(iq::kSumThreads), 0, st, v, ldv, pos, phi_sum, snap_counts,
-                       n_snap, snaps, R, S);
-    return iq::check_launch("shapley_sum_games_kernel");
+    IQ_LAUNCH(shapley_sum_games_kernel, dim3((R + 63) / 64, G), dim3(iq::kSumThreads), 0, st, v, ldv, pos, phi_sum, snap_counts,
+              n_snap, snaps, R, S);
+    return IQ_OK;
 }
 
 extern "C" int iq_interaction_reduce(const float* v, float* out, int n, iq_stream_t stream) {
     IQ_REQUIRE(n >= 0, "iq_interaction_reduce: n=%d", n);
     if (n == 0) return IQ_OK;
     IQ_REQUIRE(v && out, "iq_interaction_reduce: null pointer");
-    hipLaunchKernelGGL(interaction_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0,
-                       iq::as_stream(stream), v, out, n);
-    return iq::check_launch("interaction_reduce_kernel");
+    IQ_LAUNCH(interaction_reduce_kernel, dim3((n + 255) / 256), dim3(256), 0, iq::as_stream(stream), v, out, n);
+    return IQ_OK;
 }

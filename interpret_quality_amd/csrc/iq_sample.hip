@@ -461,11 +461,11 @@ int mt_sample_one(const char* what, uint32_t* mt_state, int32_t* orders, int S, 
     IQ_REQUIRE(mt_state && (orders || head == 0), "%s: null pointer", what);
     if (R == 1) {                                  // nothing is drawn; a row is the one region
         if (head == 0) return IQ_OK;
-        hipLaunchKernelGGL(zero_orders_kernel, dim3((S + 255) / 256), dim3(256), 0, st, orders, S);
-        return iq::check_launch("zero_orders_kernel");
+        IQ_LAUNCH(zero_orders_kernel, dim3((S + 255) / 256), dim3(256), 0, st, orders, S);
+        return IQ_OK;
     }
-    hipLaunchKernelGGL(mt_permutations_kernel<Cfg>, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, head, nullptr, nullptr, 0);
-    return iq::check_launch("mt_permutations_kernel");
+    IQ_LAUNCH(mt_permutations_kernel<Cfg>, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, head, nullptr, nullptr, 0);
+    return IQ_OK;
 }
 
 // The spread kernels over as many blocks as the workspace holds, then the one-workgroup kernel for what is left
@@ -487,14 +487,12 @@ int mt_sample_ws(const char* what, uint32_t* mt_state, int32_t* orders, int S, i
     uint32_t* keys = static_cast<uint32_t*>(workspace) + kMtCtl;
     uint32_t* next = keys + W;
     uint2* hop = reinterpret_cast<uint2*>(next + W + 2);
-    hipLaunchKernelGGL(mt_words_kernel, dim3(1), dim3(256), 0, st, mt_state, keys, ctl, nblk);
-    hipLaunchKernelGGL(mt_next_kernel<Cfg>, dim3(W / 256 + 1), dim3(256), 0, st, keys, ctl, next, W, R, Cfg::next_tail(R));
-    hipLaunchKernelGGL(mt_jump_kernel, dim3(nseg), dim3(kMtSegThreads), 0, st, next, ctl, hop, W, nseg);
-    hipLaunchKernelGGL(mt_replay_kernel<Cfg>, dim3(nseg), dim3(kMtSegThreads), 0, st, keys, next, hop, ctl, orders, S, R, head, W, nseg);
-    int rc = iq::check_launch("mt_words / mt_next / mt_jump / mt_replay kernels");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mt_permutations_kernel<Cfg>, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, head, keys, ctl, nblk);
-    return iq::check_launch("mt_permutations_kernel");
+    IQ_LAUNCH(mt_words_kernel, dim3(1), dim3(256), 0, st, mt_state, keys, ctl, nblk);
+    IQ_LAUNCH(mt_next_kernel<Cfg>, dim3(W / 256 + 1), dim3(256), 0, st, keys, ctl, next, W, R, Cfg::next_tail(R));
+    IQ_LAUNCH(mt_jump_kernel, dim3(nseg), dim3(kMtSegThreads), 0, st, next, ctl, hop, W, nseg);
+    IQ_LAUNCH(mt_replay_kernel<Cfg>, dim3(nseg), dim3(kMtSegThreads), 0, st, keys, next, hop, ctl, orders, S, R, head, W, nseg);
+    IQ_LAUNCH(mt_permutations_kernel<Cfg>, dim3(1), dim3(kMtThreads), 0, st, mt_state, orders, S, R, head, keys, ctl, nblk);
+    return IQ_OK;
 }
 
 // heads (P,C,m) of permutations of R - 2 -> region ids: entry k of the ascending list of the regions outside the pair
@@ -546,17 +544,17 @@ extern "C" int iq_context_regions_wide(const int32_t* pairs, int32_t* heads, int
     const size_t total = (size_t)P * C * m;
     if (total == 0) return IQ_OK;
     IQ_REQUIRE(pairs && heads, "iq_context_regions_wide: null pointer");
-    hipLaunchKernelGGL(context_regions_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, iq::as_stream(stream), pairs, heads, total,
-                       C * m);
-    return iq::check_launch("context_regions_kernel");
+    IQ_LAUNCH(context_regions_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, iq::as_stream(stream), pairs, heads, total,
+              C * m);
+    return IQ_OK;
 }
 
 extern "C" int iq_prefix_keep_masks(const int32_t* orders, uint64_t* keep, int S, int R, iq_stream_t stream) {
     IQ_REQUIRE(S >= 0 && R >= 1 && R <= IQ_MAX_REGIONS, "iq_prefix_keep_masks: S=%d R=%d", S, R);
     if (S == 0) return IQ_OK;
     IQ_REQUIRE(orders && keep, "iq_prefix_keep_masks: null pointer");
-    hipLaunchKernelGGL(prefix_keep_kernel, dim3((S + 255) / 256), dim3(256), 0, iq::as_stream(stream), orders, keep, S, R);
-    return iq::check_launch("prefix_keep_kernel");
+    IQ_LAUNCH(prefix_keep_kernel, dim3((S + 255) / 256), dim3(256), 0, iq::as_stream(stream), orders, keep, S, R);
+    return IQ_OK;
 }
 
 extern "C" int iq_context_keep_masks(const int32_t* pairs, const int32_t* contexts, uint64_t* keep, int P, int C, int m,
@@ -565,7 +563,7 @@ extern "C" int iq_context_keep_masks(const int32_t* pairs, const int32_t* contex
     if ((size_t)P * C == 0) return IQ_OK;
     IQ_REQUIRE(pairs && keep && (contexts || m == 0), "iq_context_keep_masks: null pointer");
     const size_t n = (size_t)P * C;
-    hipLaunchKernelGGL(context_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, iq::as_stream(stream), pairs, contexts, keep,
-                       P, C, m);
-    return iq::check_launch("context_keep_kernel");
+    IQ_LAUNCH(context_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, iq::as_stream(stream), pairs, contexts, keep,
+              P, C, m);
+    return IQ_OK;
 }

@@ -340,11 +340,11 @@ static int launch_smooth_enum(const char* name, int max_regions, const float* cl
     IQ_REQUIRE(objective == 1 || objective == -1, "%s: objective %d (+1 inc, -1 dec)", name, objective);
     IQ_REQUIRE(prm->epochs >= 1 && prm->epochs <= 4096 && prm->max_iteration >= 0, "%s: epochs=%d max_iteration=%d", name,
                prm->epochs, prm->max_iteration);
-    hipLaunchKernelGGL(smooth_passthrough_kernel, dim3((N + kWave - 1) / kWave), dim3(kWave), 0, iq::as_stream(stream), cloud, region_id,
-                       N, R, prm->epochs, data_out);
-    hipLaunchKernelGGL(smooth_enum_kernel, dim3(R), dim3(kWave), 0, iq::as_stream(stream), cloud,
-                       origin ? origin : cloud, region_id, N, R, mode, objective, *prm, data_out, smooth_out, var_out, orig_out, stop_epoch);
-    return iq::check_launch("smooth_enum_kernel");
+    IQ_LAUNCH(smooth_passthrough_kernel, dim3((N + kWave - 1) / kWave), dim3(kWave), 0, iq::as_stream(stream), cloud, region_id,
+              N, R, prm->epochs, data_out);
+    IQ_LAUNCH(smooth_enum_kernel, dim3(R), dim3(kWave), 0, iq::as_stream(stream), cloud,
+              origin ? origin : cloud, region_id, N, R, mode, objective, *prm, data_out, smooth_out, var_out, orig_out, stop_epoch);
+    return IQ_OK;
 }
 
 extern "C" int iq_smoothness_enum(const float* cloud, const float* origin, const int32_t* region_id, int N, int R, int mode, int objective,

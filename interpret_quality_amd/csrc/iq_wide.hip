@@ -182,9 +182,9 @@ extern "C" int iq_prefix_keep_masks_wide(const int32_t* orders, uint64_t* keep, 
     const int W = words_of(R);
     const size_t n = (size_t)S * W;
     IQ_REQUIRE((n + 255) / 256 <= 0x7fffffffu, "iq_prefix_keep_masks_wide: S=%d is too large", S);
-    hipLaunchKernelGGL(prefix_keep_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, iq::as_stream(stream), orders, keep,
-                       S, R, W);
-    return iq::check_launch("prefix_keep_wide_kernel");
+    IQ_LAUNCH(prefix_keep_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, iq::as_stream(stream), orders, keep,
+              S, R, W);
+    return IQ_OK;
 }
 
 extern "C" int iq_context_keep_masks_wide(const int32_t* pairs, const int32_t* contexts, uint64_t* keep, int P, int C, int m, int R,
@@ -196,9 +196,9 @@ extern "C" int iq_context_keep_masks_wide(const int32_t* pairs, const int32_t* c
     IQ_REQUIRE(pairs && keep && (contexts || m == 0), "iq_context_keep_masks_wide: null pointer");
     const size_t grid = (n + kCtxPerWg - 1) / kCtxPerWg;
     IQ_REQUIRE(grid <= 0x7fffffffu, "iq_context_keep_masks_wide: P=%d C=%d is too large", P, C);
-    hipLaunchKernelGGL(context_keep_wide_kernel, dim3((unsigned)grid), dim3(64 * kCtxPerWg), 0, iq::as_stream(stream), pairs, contexts,
-                       keep, n, C, m, R, words_of(R));
-    return iq::check_launch("context_keep_wide_kernel");
+    IQ_LAUNCH(context_keep_wide_kernel, dim3((unsigned)grid), dim3(64 * kCtxPerWg), 0, iq::as_stream(stream), pairs, contexts,
+              keep, n, C, m, R, words_of(R));
+    return IQ_OK;
 }
 
 extern "C" int iq_mask_coalitions_wide(const float* cloud, const int32_t* region_id, const uint64_t* keep, const float* center,
@@ -209,18 +209,18 @@ extern "C" int iq_mask_coalitions_wide(const float* cloud, const int32_t* region
     if (B == 0) return IQ_OK;
     IQ_REQUIRE(cloud && region_id && keep && center && out, "iq_mask_coalitions_wide: null pointer");
     const int grid = (B + kRowsPerWg - 1) / kRowsPerWg;
-    hipLaunchKernelGGL(mask_rows_wide_kernel, dim3(grid), dim3(kThreads), 0, iq::as_stream(stream), cloud, region_id, keep, center,
-                       out, N, R, words_of(R), B, channel_first);
-    return iq::check_launch("mask_rows_wide_kernel");
+    IQ_LAUNCH(mask_rows_wide_kernel, dim3(grid), dim3(kThreads), 0, iq::as_stream(stream), cloud, region_id, keep, center,
+              out, N, R, words_of(R), B, channel_first);
+    return IQ_OK;
 }
 
 extern "C" int iq_region_assign_wide(const float* cloud, const int32_t* fps_idx, int32_t* region_id, int N, int R,
                                      iq_stream_t stream) {
     IQ_REQUIRE(cloud && fps_idx && region_id, "iq_region_assign_wide: null pointer");
     IQ_REQUIRE(N > 0 && R >= 1 && R <= IQ_MAX_WIDE_REGIONS, "iq_region_assign_wide: N=%d R=%d", N, R);
-    hipLaunchKernelGGL(region_assign_wide_kernel, dim3((N + 255) / 256), dim3(256), 0, iq::as_stream(stream), cloud, fps_idx,
-                       region_id, N, R);
-    return iq::check_launch("region_assign_wide_kernel");
+    IQ_LAUNCH(region_assign_wide_kernel, dim3((N + 255) / 256), dim3(256), 0, iq::as_stream(stream), cloud, fps_idx,
+              region_id, N, R);
+    return IQ_OK;
 }
 
 extern "C" int iq_shapley_accum_wide(const float* v, const int32_t* orders, double* sv_rows, double* phi_sum,
@@ -233,11 +233,9 @@ extern "C" int iq_shapley_accum_wide(const float* v, const int32_t* orders, doub
     if (S > 0) {
         const size_t n = (size_t)S * R;
         IQ_REQUIRE((n + 255) / 256 <= 0x7fffffffu, "iq_shapley_accum_wide: S=%d is too large", S);
-        hipLaunchKernelGGL(shapley_scatter_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, v, orders, sv_rows, R, S);
-        int rc = iq::check_launch("shapley_scatter_wide_kernel");
-        if (rc) return rc;
+        IQ_LAUNCH(shapley_scatter_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, v, orders, sv_rows, R, S);
     }
-    hipLaunchKernelGGL(shapley_sum_wide_kernel, dim3((R + 63) / 64), dim3(iq::kSumThreads), 0, st, sv_rows, phi_sum, snap_counts, n_snap, snaps,
-                       R, S);
-    return iq::check_launch("shapley_sum_wide_kernel");
+    IQ_LAUNCH(shapley_sum_wide_kernel, dim3((R + 63) / 64), dim3(iq::kSumThreads), 0, st, sv_rows, phi_sum, snap_counts, n_snap, snaps,
+              R, S);
+    return IQ_OK;
 }

@@ -163,3 +163,18 @@ def test_ctypes_structures_have_the_layout_of_the_header(tmp_path):
         assert int(val) == want, (cname, what, val, want)
         seen += 1
     assert seen == sum(1 + len(c._fields_) for c in pairs.values())
+
+
+def test_every_kernel_launch_goes_through_the_one_checked_helper():
+    """csrc's launch convention (iq_common.h): the only raw launch is the one inside iq::launch, which checks it under the
+    kernel's own name; no file checks a launch by hand, and a status travels through IQ_TRY, not a local `rc`."""
+    csrc = os.path.join(REPO, "interpret_quality_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))}
+    assert len(text) >= 20 and "iq_common.h" in text
+    raw = {f: t.count("hipLaunchKernelGGL") for f, t in text.items() if "hipLaunchKernelGGL" in t}
+    assert raw == {"iq_common.h": 1}, raw
+    helper = text["iq_common.h"]
+    at = helper.index("hipLaunchKernelGGL")
+    assert helper.rindex("inline int launch(", 0, at) > helper.rindex("}", 0, at)      # inside iq::launch's body
+    assert [f for f, t in text.items() if "check_launch(" in t] == ["iq_common.h"]
+    assert [f for f, t in text.items() if "if ((rc =" in t] == []
