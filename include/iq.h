@@ -74,8 +74,10 @@ enum {
  * 118: new entry points, no layout change (all-class games on shared coalitions: iq_reward_classes, iq_shapley_games_scratch_bytes,
  * iq_shapley_accum_games).
  * 119: one new diagnostic entry point, no layout change (iq_debug.h: iq_debug_pointnet_slots); the narrow PointNet workspace grew by
- * 12 bytes per coalition (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes: the slots of the distinct coalitions). */
-#define IQ_ABI_VERSION 119
+ * 12 bytes per coalition (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes: the slots of the distinct coalitions).
+ * 120: new entry points, no layout change (all-pairs interactions from the regression rows: iq_kshap_pairs_scratch_bytes,
+ * iq_kshap_pairs). */
+#define IQ_ABI_VERSION 120
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -732,6 +734,49 @@ int iq_kshap_phi_analytic(const double* b /*G,R raw*/, const double* wsum /*1, d
  * otherwise cdf and keep must not be NULL.  One wave per sample, no atomics, nothing read back. */
 int iq_kshap_draw_counter(uint64_t seed, uint64_t stream, int64_t first, int S, int R, const double* cdf /*R-1, device*/, int paired,
                           uint64_t* keep /*rows,W*/, int32_t* sizes /*S or NULL*/, iq_stream_t queue);
+
+/* ---------------------------------------------------------------------------------------------
+ * All-pairs interactions from the regression rows (SHAP-IQ; csrc/iq_kshap_pairs.hip)
+ *
+ * The rows of the regression estimator are drawn from the Shapley kernel with known probabilities: P(S) = p(s) / C(R,s),
+ * p(s) = 1 / (s (R - s) Z), Z = 2 H / R, H = H_{R-1} = sum_{k<R} 1/k (float64, ascending k, on the host).  The pairwise Shapley
+ * interaction index SII_ij = sum_S v(S) gamma(|S|, |S & {i,j}|), gamma(s,k) = (-1)^k (s-k)! (R-s-2+k)! / (R-1)!, is therefore
+ * estimated without bias, for all R (R-1) / 2 pairs at once and with no further model evaluation, by (Fumagalli et al., 2023)
+ *     I_ij = delta / (R - 1) + (1 / W_sum) sum_m d_m mu(s_m, z_mi + z_mj),      i != j,
+ *     mu(s,2) = 2 H (R - s) / (s - 1)  (s >= 2),   mu(s,1) = -2 H,   mu(s,0) = 2 H s / (R - s - 1)  (s <= R - 2),
+ * with mu = gamma C(R,s) / p(s), s_m = popcount(z_m), d_m = w_m ((double)v_m - v0) as the moment b forms it, W_sum = sum w_m,
+ * v0 = v(empty), delta = v(all) - v(empty).  Subtracting v0 is free (a constant game has no interaction) and leaves
+ * delta / (R - 1) from the full coalition.  A row with s = 0 (a row the keep kernels wrote as 0 after a refusal) or s = R
+ * contributes 0 whatever its reward, but counts in W_sum, as in iq_kshap_accum.  With all 2^R - 2 proper coalitions and the
+ * weights w(S) = (R-1) / (C(R,s) s (R-s)) the sum is the exact SII: the mean over the orders m = 0 .. R-2 of the
+ * context-averaged I_ij^(m) of iq_exact_interactions.
+ *
+ * Computed in the form of one product, mu(s,k) = alpha_s + beta_s k + gamma_s [k = 2] with alpha_s = mu(s,0) (0 at s = R-1),
+ * beta_s = -2H - alpha_s, gamma_s = mu(s,2) + 4H + alpha_s (0 at s = 1), rows 0 and R zero - the (R+1, 3) float64 table `coef`
+ * the host builds (kernelshap.pair_coefficients):
+ *     I_ij = delta / (R-1) + (((A + L_i) + L_j) + Q_ij) / W_sum,
+ *     A = sum d_m alpha_s,   L_i = sum (d_m beta_s) z_mi,   Q_ij = sum (d_m gamma_s) z_mi z_mj.
+ * The terms cancel near s = R-2 (alpha and gamma of size 2 H R, mu(s,2) small): in float64 the error stays within
+ * (M + 16) 2^-53 sum_m |d_m| (|alpha_s| + 2 |beta_s| + |gamma_s|) / W_sum for any summation order.
+ *
+ * Order.  Q on v_mfma_f64_16x16x4_f64: rows cut into chunks of whole 256-row tiles, chunks_of(M) with the count capped so that
+ * count * R * R * 8 bytes stay within 64 MB (8 chunks at R = 1024) - a function of (M, R) alone; within a chunk wave q of four
+ * adds rows 64 q .. 64 q + 63 of every tile, four rows per instruction in row order, the waves added as ((0 + 1) + 2) + 3, the
+ * chunks in chunk order.  L, A and W_sum: the order of iq_kshap_moment_wide on chunks_of(M) (A: a chunk's sum as its sum of
+ * weights is taken).  No floating-point atomics, no grid chosen at run time: two calls give the same bits, a game's bits do not
+ * depend on G or on its place among the games, and a game never meets another game's rewards.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Scratch (bytes) of iq_kshap_pairs; 0 for arguments out of range (M outside 1 .. 2^30, R outside 2 .. IQ_MAX_WIDE_REGIONS,
+ * G outside 1 .. 65535). */
+size_t iq_kshap_pairs_scratch_bytes(int M, int R, int G);
+
+/* out[g][i][j] = I_ij of game g from M rows of W = ceil(R / 64) words (W = 1: the narrow format; bits at or above R are ignored)
+ * shared by G games; out[g][i][i] = 0, and out[g][i][j] and out[g][j][i] are the same bits (the upper triangle is built and
+ * mirrored).  coef: the (R+1, 3) table above, on the device.  weights == NULL: w_m = 1 and W_sum = M. */
+int iq_kshap_pairs(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, const double* delta /*G*/,
+                   const double* weights /*M or NULL*/, const double* coef /*R+1,3 device*/, int M, int R, int G,
+                   double* out /*G,R,R*/, void* scratch, size_t scratch_bytes, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

@@ -20,6 +20,20 @@ __host__ __device__ inline Chunks chunks_of(long long M) {
     return {(int)((tiles + per - 1) / per), (int)per};
 }
 
+// The cut of the pairwise product Q (iq_kshap_pairs.hip), whose partials are R x R per chunk: chunks_of(M) with the count capped so
+// that one game's partials, counted as count * R * R float64, stay within kPairPartialBytes (8 chunks at R = 1024) - a function
+// of (M, R) alone.  Where the cap does not bind it is chunks_of(M).
+constexpr long long kPairPartialBytes = 64ll << 20;
+
+__host__ __device__ inline Chunks pair_chunks_of(long long M, int R) {
+    const Chunks ch = chunks_of(M);
+    const long long cap = kPairPartialBytes / (8ll * R * R);      // >= 8 for R <= 1024
+    if (ch.count <= cap) return ch;
+    const long long tiles = (M + kTile - 1) / kTile;
+    const long long per = (tiles + cap - 1) / cap;
+    return {(int)((tiles + per - 1) / per), (int)per};
+}
+
 // The workgroup's values x, one per thread, added in thread order through the kThreads words of `sh` (free to be overwritten:
 // every thread is past its last read of them); the sum is thread 0's return value.
 template <typename T>
@@ -32,14 +46,15 @@ __device__ __forceinline__ T sum_threads_in_order(T* sh, T x) {
     return s;
 }
 
-// One chunk's sum of w_m z_mi ((double)vg[m] - base) for the 64 regions of word `word` of rows of W words (narrow: W = 1, word 0),
-// on a workgroup of kThreads: lane i of wave q adds rows 64 q .. 64 q + 63 of every tile in row order, then the four waves are
-// added as ((0 + 1) + 2) + 3.  Every LDS read of the inner loop is a broadcast.  Threads t < 64 write out[t] when t < live_bits
-// (the regions of this word that exist).  With wpart the workgroup also leaves the chunk's sum of weights there: per thread over
-// its rows t, t + 256, ... of the chunk, then the 256 threads in index order.
-__device__ __forceinline__ void moment_chunk(const unsigned long long* __restrict__ keep, int W, int word, const float* __restrict__ vg,
-                                             double base, const double* __restrict__ weights, long long M, int tiles_per, int chunk,
-                                             double* __restrict__ out, int live_bits, double* __restrict__ wpart) {
+// One chunk's sum of d_m z_mi for the 64 regions of word `word` of rows of W words (narrow: W = 1, word 0), d_m = value(m, w_m) of a
+// live row, on a workgroup of kThreads: lane i of wave q adds rows 64 q .. 64 q + 63 of every tile in row order, then the four
+// waves are added as ((0 + 1) + 2) + 3.  Every LDS read of the inner loop is a broadcast.  Threads t < 64 write out[t] when
+// t < live_bits (the regions of this word that exist).  With wpart the workgroup also leaves the chunk's sum of weights there: per
+// thread over its rows t, t + 256, ... of the chunk, then the 256 threads in index order.
+template <typename RowValue>
+__device__ __forceinline__ void moment_chunk_of(const unsigned long long* __restrict__ keep, int W, int word, RowValue value,
+                                                const double* __restrict__ weights, long long M, int tiles_per, int chunk,
+                                                double* __restrict__ out, int live_bits, double* __restrict__ wpart) {
     __shared__ unsigned long long sh_keep[kTile];
     __shared__ double sh_d[kTile];
     __shared__ double sh_fold[4][64];
@@ -51,7 +66,7 @@ __device__ __forceinline__ void moment_chunk(const unsigned long long* __restric
         const bool live = m < M;
         const double w = live ? (weights ? weights[m] : 1.0) : 0.0;
         sh_keep[t] = live ? keep[(size_t)m * W + word] : 0ull;
-        sh_d[t] = live ? w * ((double)vg[m] - base) : 0.0;
+        sh_d[t] = live ? value(m, w) : 0.0;
         wacc += w;
         __syncthreads();
 #pragma unroll 8
@@ -65,6 +80,14 @@ __device__ __forceinline__ void moment_chunk(const unsigned long long* __restric
         const double s = sum_threads_in_order(sh_d, wacc);      // sh_d: the barrier above is past its last read
         if (t == 0) *wpart = s;
     }
+}
+
+// moment_chunk_of with d_m = w_m ((double)vg[m] - base): the moment b of the regression estimator.
+__device__ __forceinline__ void moment_chunk(const unsigned long long* __restrict__ keep, int W, int word, const float* __restrict__ vg,
+                                             double base, const double* __restrict__ weights, long long M, int tiles_per, int chunk,
+                                             double* __restrict__ out, int live_bits, double* __restrict__ wpart) {
+    moment_chunk_of(keep, W, word, [vg, base](long long m, double w) { return w * ((double)vg[m] - base); }, weights, M, tiles_per,
+                    chunk, out, live_bits, wpart);
 }
 
 // The chunks' partials p[0], p[stride], ... added in chunk order.

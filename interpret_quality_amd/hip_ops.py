@@ -714,6 +714,39 @@ def kshap_phi_analytic(b, wsum, delta):
     return phi
 
 
+def kshap_pairs(keep, v, v0, delta, r, weights=None):
+    """keep (M,) int64-typed narrow rows (r <= 64) or (M,W) wide rows, v (G,M) f32 rewards of G games on those rows, v0 and delta
+    (G,) f64, weights (M,) f64 or None (all 1) -> (G,r,r) f64: the SHAP-IQ estimate of the pairwise Shapley interaction index of
+    every pair of regions (iq_kshap_pairs: float64, the product on the f64 matrix pipe, a fixed order, bitwise repeatable; the
+    diagonal is 0, the matrix symmetric bit for bit).  One entry for both row formats: a narrow row is a wide row of one word."""
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    if isinstance(keep, torch.Tensor) and keep.dim() == 1:
+        if r > 64:
+            raise _lib.IqError("keep must be (M, %d) for %d regions, got %s" % (wide_words(r), r, tuple(keep.shape)))
+        kp = _dev(keep, torch.int64, "keep")
+    else:
+        kp = wide_keep(keep, r)
+    m = keep.shape[0]
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    _shape(delta, "delta", g)
+    if weights is not None:
+        _shape(weights, "weights", m)
+    dev = keep.device
+    nbytes = lib.iq_kshap_pairs_scratch_bytes(m, r, g)
+    if nbytes == 0:
+        raise _lib.IqError("kshap_pairs: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
+    from . import kernelshap
+    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
+    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = torch.empty((g, r, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_pairs(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"), _dev(delta, torch.float64, "delta"),
+                                  _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0),
+                                  _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()), "iq_kshap_pairs")
+    return out
+
+
 def kshap_draw_counter(seed, stream, first, count, r, cdf=None, paired=True, device="cuda"):
     """The counter-based draw of samples ``first .. first + count - 1`` of one cloud (iq_kshap_draw_counter: Philox4x32-10 keyed by
     (seed, stream), each sample a pure function of (seed, stream, index, r)) -> (keep (2 count or count, W) int64-typed wide rows,

@@ -12,12 +12,20 @@ Per selected cloud, under the experiment folder that ``exp_folder`` derives from
                                                   reward units, of this estimator and of stage 1's permutation estimate at the same
                                                   number of model evaluations, against exact.shapley of the same cloud; the last row
                                                   is the largest budget both have
+    kernelshap/region_interaction.npy             (n, n) float64 with --pairs: the SHAP-IQ estimate of the pairwise Shapley
+                                                  interaction index of every pair of regions from the same M rows (kernelshap.pairs;
+                                                  symmetric, zero diagonal); with --compare_exact also a "pairs" object in
+                                                  sampling_error.json, its max and RMS error over the pairs against the exact index
+                                                  (the mean over the orders of exact.interactions, from the same value table)
+
+Without --pairs every artefact is what it was before the flag existed, byte for byte.
 
 ``--samples`` is the number of rows M (model evaluations; default 1000 (n + 1), stage 1's budget; ``all``: the enumerated game).
 With --compare_exact both estimates are read off ONE exact value table, not run through the network again; the permutations are
 the ones stage 1 would draw at this point of the stream, and the generator is put back afterwards, so the flag does not change
 what any cloud draws.  Single process: under several ranks rank 0 does the work and the others wait at the end.
 """
+import argparse
 import json
 
 import numpy as np
@@ -38,12 +46,23 @@ def artefacts(g):
     return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
             "running_counts": np.array(sorted(running), dtype=np.int64),
             "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), len(g["phi"])),
-            "v_full": g["v_full"], "v_empty": g["v_empty"]}
+            "v_full": g["v_full"], "v_empty": g["v_empty"], **({"region_interaction": g["interaction"]} if "interaction" in g else {})}
 
 
 def save(folder, out):
-    for key in FILES:
+    for key in FILES + (("region_interaction",) if "region_interaction" in out else ()):
         np.save(folder + "%s.npy" % key, out[key])
+
+
+def add_pairs_flag(parser):
+    """--pairs; a namespace parsed without it holds no trace of the flag (``wants_pairs`` reads it)."""
+    parser.add_argument("--pairs", action="store_true", default=argparse.SUPPRESS,
+                        help="also write kernelshap/region_interaction.npy: the pairwise Shapley interaction index of every pair "
+                             "of regions, estimated from the same rows (SHAP-IQ), no further model evaluation")
+
+
+def wants_pairs(args):
+    return bool(getattr(args, "pairs", False))
 
 
 def add_sample_flags(parser, enumerated=False):
@@ -68,12 +87,23 @@ def _errors(est, phi):
     return {"max_abs_error": float(np.abs(err).max()), "rms_error": float(np.sqrt((err ** 2).mean()))}
 
 
-def compare_exact(model, data, lbl, region_id, keep, args):
+def exact_pairs(v):
+    """The exact pairwise Shapley interaction index off a value table -> (n,n) float64, symmetric, zero diagonal: the mean over
+    the orders m = 0 .. n-2 of exact.interactions' context-averaged I_ij^(m)."""
+    n = int(v.numel()).bit_length() - 1
+    out = np.zeros((n, n))
+    pr = hip_ops.all_pairs(n)
+    out[pr[:, 0], pr[:, 1]] = out[pr[:, 1], pr[:, 0]] = hip_ops.exact_interactions(v).cpu().numpy().mean(axis=1)
+    return out
+
+
+def compare_exact(model, data, lbl, region_id, keep, args, v=None):
     """-> (exact phi, rows of sampling_error.json): for every sample count c of stage 1 whose c (n + 1) evaluations both
     estimators have, and for the largest number of permutations both have, the errors of the permutation estimate of c
-    permutations and of this estimator's first c (n + 1) rows."""
+    permutations and of this estimator's first c (n + 1) rows.  ``v``: the cloud's exact value table where the caller has it."""
     n = args.num_regions
-    v = exact.value_table(model, data, lbl, region_id, args)
+    if v is None:
+        v = exact.value_table(model, data, lbl, region_id, args)
     phi, _, _ = exact.shapley(model, data, lbl, region_id, args, v=v)
     if args.samples == "all":       # the enumerated rows are no sample: only the final estimate is compared
         return phi, []
@@ -96,11 +126,16 @@ def compare_exact(model, data, lbl, region_id, keep, args):
 
 
 def kernel_one_cloud(model, data, lbl, region_id, args):
-    """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact)."""
-    g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram)
+    """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact, 'region_interaction' only with
+    --pairs, 'pairs_error' only with both)."""
+    g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram, pairs=wants_pairs(args))
     out = artefacts(g)
     if args.compare_exact:
-        out["exact"], out["sampling_error"] = compare_exact(model, data, lbl, region_id, g["keep"], args)
+        v = exact.value_table(model, data, lbl, region_id, args)
+        out["exact"], out["sampling_error"] = compare_exact(model, data, lbl, region_id, g["keep"], args, v)
+        if wants_pairs(args):
+            upper = np.triu_indices(args.num_regions, 1)
+            out["pairs_error"] = _errors(g["interaction"][upper], exact_pairs(v)[upper])
     return out
 
 
@@ -123,7 +158,8 @@ def run(args):
             if args.compare_exact:
                 with open(result_path + "kernelshap/sampling_error.json", "w") as f:
                     json.dump({"num_regions": args.num_regions, "gram": args.gram, "paired": not args.unpaired, "v_full": out["v_full"], "v_empty": out["v_empty"],
-                               "final": _errors(out["region_shapley_value"], out["exact"]), "sample_counts": out["sampling_error"]},
+                               "final": _errors(out["region_shapley_value"], out["exact"]), "sample_counts": out["sampling_error"],
+                               **({"pairs": out["pairs_error"]} if "pairs_error" in out else {})},
                               f, indent=1)
                 if out["sampling_error"]:
                     last = out["sampling_error"][-1]
@@ -138,6 +174,7 @@ def make_args(argv=None):
     parser.add_argument("--gram", type=str, default="sampled", choices=list(kernelshap.GRAMS))
     parser.add_argument("--compare_exact", action="store_true",
                         help="also enumerate the game (at most %d regions) and write sampling_error.json" % exact.MAX_PLAYERS)
+    add_pairs_flag(parser)
     args = stage1.parse_game_args(parser, argv, NUM_REGIONS, 2, kernelshap.MAX_REGIONS,
                                   "the regression estimator takes 2 to 64 regions (final_wide_kernel_shapley.py: 65 to 1024)")
     check_samples(parser, args, enumerated=True)

@@ -149,6 +149,62 @@ def estimate(keep, v, v_empty, v_full, n, weights=None, gram="sampled"):
     return phi[0] if v.dim() == 1 else phi
 
 
+def pair_coefficients(n):
+    """(n+1, 3) float64: row s = (alpha_s, beta_s, gamma_s) with mu(s, k) = alpha_s + beta_s k + gamma_s [k = 2] the SHAP-IQ
+    weight of a row of s regions that holds k of a pair's two (include/iq.h, "All-pairs interactions from the regression rows"):
+    alpha_s = 2 H s / (n - s - 1) (0 at s = n-1), beta_s = -2 H - alpha_s, gamma_s = 2 H (n - s) / (s - 1) + 4 H + alpha_s (0 at
+    s = 1), rows 0 and n zero.  H = H_{n-1} is the float64 sum in ascending k of the contract; from it every entry is formed in
+    rationals and rounded once.  Any n >= 2 (``hip_ops.kshap_pairs`` checks the range of a game)."""
+    from fractions import Fraction
+    n = int(n)
+    if n < 2:
+        raise IqError("a pair needs at least 2 regions, got %d" % n)
+    h = 0.0
+    for k in range(1, n):
+        h += 1.0 / k
+    two_h = 2 * Fraction(h)
+    out = np.zeros((n + 1, 3))
+    for s in range(1, n):
+        alpha = two_h * s / (n - s - 1) if s <= n - 2 else Fraction(0)
+        gamma = two_h * (n - s) / (s - 1) + 2 * two_h + alpha if s >= 2 else Fraction(0)
+        out[s] = float(alpha), float(-two_h - alpha), float(gamma)
+    return out
+
+
+PAIR_PARTIAL_BYTES = 64 << 20     # kPairPartialBytes of csrc/iq_kshap_order.h
+
+
+def chunks(m):
+    """(count, tiles_per): the cut of m rows into chunks of whole 256-row tiles, at most 256 chunks - chunks_of of
+    csrc/iq_kshap_order.h restated (the order of every moment; tests hold the two together through the scratch sizes)."""
+    tiles = (int(m) + 255) // 256
+    per = (tiles + 255) // 256
+    return (tiles + per - 1) // per, per
+
+
+def pair_chunks(m, n):
+    """(count, tiles_per): the cut of the pairwise product's rows, ``chunks(m)`` with the count capped so that count * n * n
+    float64 partials stay within PAIR_PARTIAL_BYTES (8 chunks at n = 1024) - pair_chunks_of of csrc/iq_kshap_order.h restated: a
+    function of (m, n) alone."""
+    count, per = chunks(m)
+    cap = PAIR_PARTIAL_BYTES // (8 * int(n) * int(n))
+    if count <= cap:
+        return count, per
+    tiles = (int(m) + 255) // 256
+    per = (tiles + cap - 1) // cap
+    return (tiles + per - 1) // per, per
+
+
+def pairs(keep, v, v_empty, v_full, n, weights=None):
+    """The SHAP-IQ estimate of the pairwise Shapley interaction index of ALL pairs of regions from the rows ``keep`` ((M,) narrow or
+    (M,W) wide) with rewards ``v`` ((M,) float32 device tensor, or (G,M) for G games on the same rows; v_empty, v_full: scalars or
+    (G,)) -> float64 ndarray (n,n) or (G,n,n), symmetric with a zero diagonal.  No further model evaluation: the rows are those
+    ``estimate`` takes; with the enumerated rows and weights the result is the exact index."""
+    v2, v0, v1 = games(keep, v, v_empty, v_full)
+    out = hip_ops.kshap_pairs(keep, v2, v0, v1 - v0, n, weights).cpu().numpy()
+    return out[0] if v.dim() == 1 else out
+
+
 def default_samples(n):
     """Stage 1's budget of model evaluations: 1000 permutations of n + 1 prefix coalitions, rounded down to even."""
     return 1000 * (n + 1) // 2 * 2
@@ -195,13 +251,14 @@ def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled", ks=_N
 
 
 def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, draw=None, classes=None,
-         **how):
+         pairs=False, **how):
     """The body of ``game``, wide_kernelshap.game and classwise.kernel_shapley, which check their own arguments first.  ``ks``:
     the estimator's module, this one or wide_kernelshap.  Refused before anything is drawn or run: the region count and
     ``gram``.  Then the rows - ``samples`` a count, None (``ks.default_samples``) or "all" (``ks.enumerated``); ``draw``:
     (n, samples, paired, device) -> (keep, sizes), default ``ks.draw`` - their rewards (``ks.rewards`` with ``classes`` and
     ``how``), ``ks.estimate`` and the running estimates at ``ks.running_counts`` (``counts=()``: none) -> the dict ``game``
-    describes."""
+    describes; ``pairs``: also "interaction", ``ks.pairs`` of the same rows and rewards ((n,n), or (G,n,n) with ``classes``; no
+    running estimates of it)."""
     n = ks.regions(args.num_regions)
     ks.check_gram(gram)
     weights = None
@@ -216,14 +273,18 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
     running = {}
     if weights is None:
         running = running_estimates(keep, v, v_empty, v_full, n, ks.running_counts(n, keep.shape[0], paired, counts), gram, ks)
-    return {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
+    out = {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
+    if pairs:
+        out["interaction"] = ks.pairs(keep, v, v_empty, v_full, n, weights)
+    return out
 
 
-def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):
+def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, pairs=False):
     """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
-    sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows}.  A
-    ``gram`` outside GRAMS is refused before anything is drawn or run."""
-    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts)
+    sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows};
+    ``pairs``: also interaction (n,n), ``pairs`` of the same rows.  A ``gram`` outside GRAMS is refused before anything is
+    drawn or run."""
+    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):
@@ -242,3 +303,12 @@ def from_table(v_table, keep, weights=None, gram="sampled"):
         raise IqError("v_table must be a (2^n,) table, got shape %s" % (tuple(v_table.shape),))
     ends = v_table[[0, v_table.numel() - 1]].cpu().numpy()
     return estimate(keep, v_table.index_select(0, keep).contiguous(), float(ends[0]), float(ends[1]), n, weights, gram)
+
+
+def pairs_from_table(v_table, keep, weights=None):
+    """``pairs`` of the rows ``keep`` with rewards read off an exact value table, as ``from_table`` reads them -> (n,n) float64."""
+    n = int(v_table.numel()).bit_length() - 1
+    if v_table.dim() != 1 or v_table.numel() != 1 << n:
+        raise IqError("v_table must be a (2^n,) table, got shape %s" % (tuple(v_table.shape),))
+    ends = v_table[[0, v_table.numel() - 1]].cpu().numpy()
+    return pairs(keep, v_table.index_select(0, keep).contiguous(), float(ends[0]), float(ends[1]), n, weights)

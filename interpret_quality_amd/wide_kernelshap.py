@@ -39,6 +39,7 @@ SAMPLED_REFUSAL = ("the wide estimator has gram='analytic' only: the sampled Gra
 regions = hip_ops.kshap_regions_wide
 default_samples = kernelshap.default_samples      # 1000 (R + 1), even: no region count enters but through the argument
 running_counts = kernelshap.running_counts        # c (R + 1) for c in stage 1's sample counts
+pairs = kernelshap.pairs                          # all-pairs interactions: one entry for both row formats, here on (M,W) rows
 
 
 def check_gram(gram):
@@ -154,16 +155,17 @@ def running_estimates(keep, v, v_empty, v_full, r, counts, gram="analytic"):
 
 
 def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",
-         seed=1, stream=0):
+         seed=1, stream=0, pairs=False):
     """One cloud's sampled (or, at most exact.MAX_PLAYERS regions, enumerated) game with everything the driver stores: dict of
     keep (M,W), weights (None when sampled), v (M,) float32 rewards, v_full, v_empty, phi (R,) and running {count: phi of the
     first ``count`` rows} (kernelshap.play on this module).  ``draw``: "stream" - ``draw`` on NumPy's global generator - or
-    "counter" - ``draw_counter`` keyed by (``seed``, ``stream``), which the other kind ignores.  The region count, ``gram`` and
-    ``draw`` are refused, in that order, before anything else is looked at."""
+    "counter" - ``draw_counter`` keyed by (``seed``, ``stream``), which the other kind ignores.  ``pairs``: also interaction
+    (R,R), ``pairs`` of the same rows.  The region count, ``gram`` and ``draw`` are refused, in that order, before anything else
+    is looked at."""
     regions(args.num_regions)
     check_gram(gram)
     return kernelshap.play(sys.modules[__name__], model, data, lbl, region_id, args, samples, paired, gram, counts,
-                           drawer(draw, seed, stream), coalitions=coalitions)
+                           drawer(draw, seed, stream), pairs=pairs, coalitions=coalitions)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Times the all-pairs interaction estimator (``hip_ops.kshap_pairs``: SHAP-IQ on the regression rows) and measures
+how many rows a usable interaction map needs (not the flagship workload: that is bench.py).
+
+    python tools/bench_kshap_pairs.py [--out profiles/kshap_pairs.json] [--seeds 20] [--runs 5]
+
+Part 1 - time.  PointNet, synthetic cloud 0, (R, M) = (32, 33 000), (128, 129 000) and (1024, 1 025 000), G = 1 game (the cloud's
+label) and G = 10 (labels 0 .. 9 from the same forwards).  ``--runs`` runs each after a warm-up, wall clock around a synchronised
+call, median and the smallest and largest run:
+  * the PointNet forwards of the rows (``rewards``);
+  * ``hip_ops.kshap_pairs`` - the whole entry: row sizes, Q on the f64 matrix pipe, L, A, the folds and the assembly, with the
+    wrapper's allocations and the coefficient table;
+  * the eager PyTorch float64 form of Q ALONE, ``(Z * e[:, None]).T @ Z`` per game, in blocks of ``--block`` rows, Z unpacked from
+    the same keep words on the device inside the timed region (the kernel starts from the words too) - and, as
+    ``eager_product_only``, the same with the unpacked blocks prepared outside the timed region.
+The kernel and the eager form are ALTERNATED in one process.  Reported: the kernel's share of forwards + kernel, the ratio eager /
+kernel of the medians, whether the difference exceeds the larger spread, and the float64 rate 2 R^2 M G / time of both (the
+kernel builds the blocks on and above the diagonal only: its rate is quoted on the full square for comparison, and on the
+multiply-adds it performs).
+
+Part 2 - error.  PointNet, synthetic cloud 0, n = 16 regions, ``--seeds`` seeds: RMS over pairs and seeds of
+``kernelshap.pairs_from_table`` against the exact index (the mean over the orders of ``hip_ops.exact_interactions`` of the
+cloud's value table) at 100 / 300 / 1000 permutations' worth of rows (c (n + 1), paired), beside the RMS of the exact index
+itself.  There is no rival estimator at equal evaluations: the number says how many rows a usable map needs."""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from interpret_quality_amd import exact, hip_ops, kernelshap, synth, wide_kernelshap  # noqa: E402
+from interpret_quality_amd.pointnet import PointNetCls  # noqa: E402
+
+SHAPES = ((32, 33000), (128, 129000), (1024, 1025000))
+BUDGETS = (100, 300, 1000)      # permutations' worth of evaluations
+
+
+def _setup(r, dev):
+    model = PointNetCls(None)
+    model.load_state_dict(synth.to_torch(synth.pointnet_state_dict(0)))
+    model = model.to(dev).eval()
+    pts, label = synth.make_cloud(0)
+    data, lbl = torch.from_numpy(pts).unsqueeze(0).to(dev), torch.tensor([label], device=dev)
+    rid = hip_ops.region_assign_wide(data[0].contiguous(), hip_ops.fps(data, r)[0].contiguous()).cpu().numpy().astype(np.int64)
+    args = SimpleNamespace(model="pointnet", softmax_type="modified", num_points=1024, num_regions=r, verbose=False)
+    return model, data, lbl, rid, args
+
+
+def _wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, res
+
+
+def _spread(times):
+    return {"median_seconds": float(np.median(times)), "min_seconds": float(min(times)), "max_seconds": float(max(times)),
+            "runs": [float(t) for t in times]}
+
+
+def _unpack(words, r):
+    """(B,W) int64-typed keep words -> (B,R) float64 rows z."""
+    shifts = torch.arange(64, device=words.device, dtype=torch.int64)
+    return ((words[:, :, None] >> shifts) & 1).reshape(words.shape[0], -1)[:, :r].to(torch.float64)
+
+
+def _eager_q(words, e, r, block, unpacked=None):
+    """sum over row blocks of (Z * e_g[:, None]).T @ Z for every game g -> (G,R,R) float64."""
+    out = torch.zeros((e.shape[0], r, r), dtype=torch.float64, device=words.device)
+    for k, lo in enumerate(range(0, words.shape[0], block)):
+        z = unpacked[k] if unpacked is not None else _unpack(words[lo:lo + block], r)
+        for g in range(e.shape[0]):
+            out[g] += (z * e[g, lo:lo + block, None]).T @ z
+    return out
+
+
+def time_shape(r, m, games, runs, block, dev):
+    model, data, lbl, rid, args = _setup(r, dev)
+    ks = kernelshap if r <= kernelshap.MAX_REGIONS else wide_kernelshap
+    np.random.seed(1)
+    keep = kernelshap.draw(r, m, True, dev)[0] if ks is kernelshap else wide_kernelshap.draw_counter(r, m, 1, 0, True, dev)[0]
+    classes = None if games == 1 else list(range(games))
+    forwards = lambda: ks.rewards(model, data, None if classes else lbl, rid, args, keep, classes=classes)      # noqa: E731
+    ks.rewards(model, data, lbl, rid, args, keep[:4096].contiguous())          # warm-up: engine, workspace, code objects
+    fwd = []
+    for _ in range(runs):
+        t, (v, v_full, v_empty) = _wall(forwards)
+        fwd.append(t)
+    v2, v0, v1 = kernelshap.games(keep, v, v_empty, v_full)
+    delta = v1 - v0
+    words = keep.reshape(len(keep), -1)
+    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
+    sizes = _unpack(words, r).sum(dim=1).to(torch.int64) if r <= 128 else torch.cat(
+        [_unpack(words[lo:lo + block], r).sum(dim=1).to(torch.int64) for lo in range(0, len(words), block)])
+    e = (v2.to(torch.float64) - v0[:, None]) * coef[sizes, 2][None]
+    unpacked = None
+    if 8 * r * len(words) <= 16 << 30:
+        unpacked = [_unpack(words[lo:lo + block], r) for lo in range(0, len(words), block)]
+    kernel_call = lambda: hip_ops.kshap_pairs(keep, v2, v0, delta, r)           # noqa: E731
+    kernel_call()
+    _eager_q(words, e, r, block)
+    kern, eager, product = [], [], []
+    for _ in range(runs):                                                       # alternated in one process
+        kern.append(_wall(kernel_call)[0])
+        eager.append(_wall(lambda: _eager_q(words, e, r, block))[0])
+        if unpacked is not None:
+            product.append(_wall(lambda: _eager_q(words, e, r, block, unpacked))[0])
+    f, k, q = (float(np.median(x)) for x in (fwd, kern, eager))
+    larger = max(max(kern) - min(kern), max(eager) - min(eager))
+    nb = (r + 63) // 64
+    square = 2.0 * r * r * len(words) * games
+    built = 2.0 * (nb * (nb + 1) // 2) * 4096 * len(words) * games
+    out = {"num_regions": r, "rows": int(len(words)), "games": games, "pointnet_forwards": _spread(fwd),
+           "coalitions_per_s": (len(words) + 2) / f, "kshap_pairs": _spread(kern), "eager_q": _spread(eager),
+           "kshap_pairs_share_of_forwards_plus_reduction": k / (f + k), "eager_over_kernel": q / k,
+           "larger_spread_seconds": larger, "difference_exceeds_the_larger_spread": bool(abs(q - k) > larger),
+           "kernel_ahead_of_eager": bool(k < q),
+           "kernel_tflops_on_the_full_square": square / k / 1e12, "kernel_tflops_on_the_blocks_it_builds": built / k / 1e12,
+           "eager_tflops": square / q / 1e12, "eager_block_rows": block}
+    if product:
+        p = float(np.median(product))
+        out.update({"eager_product_only": _spread(product), "eager_product_only_over_kernel": p / k,
+                    "eager_product_only_tflops": square / p / 1e12})
+    return out
+
+
+def error_table(n, seeds, dev):
+    model, data, lbl, rid, args = _setup(n, dev)
+    table = exact.value_table(model, data, lbl, rid, args)
+    pr = hip_ops.all_pairs(n)
+    want = hip_ops.exact_interactions(table).cpu().numpy().mean(axis=1)
+    most = max(BUDGETS) * (n + 1)
+    sq = {b: [] for b in BUDGETS}
+    for seed in range(seeds):
+        np.random.seed(1000 + seed)
+        keep, _ = kernelshap.draw(n, most, True, dev)
+        for b in BUDGETS:
+            count = b * (n + 1) // 2 * 2
+            got = kernelshap.pairs_from_table(table, keep[:count].contiguous())[pr[:, 0], pr[:, 1]]
+            sq[b].append(float(((got - want) ** 2).mean()))
+    return {"model": "pointnet", "cloud": "synthetic_00", "num_regions": n, "pairs": int(len(pr)), "seeds": seeds,
+            "exact_index_rms": float(np.sqrt((want ** 2).mean())), "exact_index_max_abs": float(np.abs(want).max()),
+            "budgets": [{"permutations": b, "rows": b * (n + 1) // 2 * 2, "rms_error": float(np.sqrt(np.mean(sq[b]))),
+                         "rms_error_over_exact_index_rms": float(np.sqrt(np.mean(sq[b])) / np.sqrt((want ** 2).mean())),
+                         "per_seed_rms": {"mean": float(np.sqrt(sq[b]).mean()),
+                                          "std": float(np.sqrt(sq[b]).std(ddof=1)) if seeds > 1 else None}} for b in BUDGETS]}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "kshap_pairs.json"))
+    ap.add_argument("--seeds", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--block", type=int, default=1 << 16, help="rows per block of the eager form")
+    ap.add_argument("--error_regions", type=int, default=16)
+    ap.add_argument("--games", type=int, nargs="+", default=[1, 10])
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_kshap_pairs.py needs a GPU: a time taken elsewhere says nothing about the MI355X")
+    dev = torch.device("cuda:0")
+    with torch.no_grad():
+        res = {"device": torch.cuda.get_device_name(0),
+               "time": [time_shape(r, m, g, args.runs, args.block, dev) for r, m in SHAPES for g in args.games],
+               "error": error_table(args.error_regions, args.seeds, dev)}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
