@@ -7,7 +7,7 @@
  * the profiler or flips a knob affects only the launches it issues itself; other threads and other processes are untouched.
  * WITHIN that thread a knob applies to every engine: iq_set_tuning(5, v) in particular switches the arithmetic path (bf16x3 <->
  * float32 MFMA twins, fused <-> two-kernel forms) of all later launches of the thread until it is set back - tests and tools
- * restore it in try/finally.
+ * select a knob through the context managers of interpret_quality_amd/tuning.py, which check both calls and restore it.
  */
 #ifndef IQ_DEBUG_H_
 #define IQ_DEBUG_H_
@@ -33,19 +33,31 @@ int iq_profile_read_work(int slot, double* total_ms, int* launches, double* tota
  * compared or timed interleaved in ONE process.  Value 0 on either key restores the product paths.  Any other (key, value)
  * returns IQ_EINVAL and iq_last_error names it.
  *
- *   key  value       selects
- *   3    1           dense layers without the LDS-staged GEMM (pn_gemm_lds_kernel)
- *   5    7, 8        DGCNN EdgeConv as GEMM + L2 gather / GEMM + LDS gather
- *   5    12          DGCNN compact-row knn_kernel<8> instead of the region walk
- *   5    14, 15, 31  PointConv kNN path / grouped MLP / sa1 contraction and 2048 -> 128 layer as two kernels
- *   5    20, 22      DGCNN kNN ranking in float32 only / feature-space distances on the fp32 MFMA
- *   5    21          PointNet++ member walk
- *   5    54, 55, 58  PointNet chain layer 3 on the fp32 MFMA (55: without the 16-row tail tiles) / one n-tile per pass
- *   5    56, 64      fp32-MFMA grouped kernels (32- / 64-row chunks; PointConv: 56)
- *   5    57          dense layers on the fp32 MFMA
- *   5    59          bf16x3 dense layers with 128-row tiles only (the launch before the short tiles; bit-identical results)
- *   5    60          PointNet coalition chains run every repeated coalition of a batch instead of copying the first one's rows
- *                    (no representatives are sought, every item is its own slot and nothing is expanded; bit-identical results) */
+ * The key-5 values are the twins listed once in interpret_quality_amd/csrc/iq_twin.h (IQ_TWINS); the names below are the ones
+ * interpret_quality_amd/tuning.py selects them by (the enumerator kTwin<Name> in snake case).
+ *
+ *   key  value  name                     selects
+ *   3    1                               dense layers without the LDS-staged GEMM (pn_gemm_lds_kernel)
+ *   5    7      edge_gemm_l2             DGCNN EdgeConv as GEMM + L2 gather
+ *   5    8      edge_gemm_lds            DGCNN EdgeConv as GEMM + LDS gather
+ *   5    12     knn_compact              DGCNN compact-row knn_kernel<8> instead of the region walk
+ *   5    14     pc_knn                   PointConv kNN path instead of the walk
+ *   5    15     pc_grouped_mlp           PointConv grouped MLP
+ *   5    20     knn_fp32_rank            DGCNN kNN ranking in float32 only
+ *   5    21     pn2_member_walk          PointNet++ member walk
+ *   5    22     knn_fp32_mfma            DGCNN feature-space kNN distances on the fp32 MFMA
+ *   5    31     pc_two_kernel            PointConv sa1 contraction and 2048 -> 128 layer as two kernels
+ *   5    54     chain_l3_fp32            PointNet chain layer 3 on the fp32 MFMA
+ *   5    55     chain_l3_fp32_no_tail16  the same without the 16-row tail tiles
+ *   5    56     group_fp32               fp32-MFMA grouped kernels (PointNet++ 32-row chunks, PointConv)
+ *   5    57     dense_fp32               dense layers on the fp32 MFMA
+ *   5    58     chain_l3_single          bf16x3 chain layer 3 with one n-tile per pass
+ *   5    59     dense_tile128            bf16x3 dense layers with 128-row tiles only (the launch before the short tiles;
+ *                                        bit-identical results)
+ *   5    60     chain_no_dedup           PointNet coalition chains run every repeated coalition of a batch instead of copying the
+ *                                        first one's rows (no representatives are sought, every item is its own slot and nothing
+ *                                        is expanded; bit-identical results)
+ *   5    64     group_fp32_chunk64       PointNet++ fp32-MFMA grouped kernel with 64-row chunks */
 int iq_set_tuning(int key, int value);
 int iq_profile_read(int slot, double* total_ms, int* launches);
 

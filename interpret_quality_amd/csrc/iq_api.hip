@@ -5,6 +5,7 @@
 #include "../../include/iq_debug.h"
 #include "iq_common.h"
 #include "iq_profile.h"
+#include "iq_twin.h"
 
 extern "C" int iq_version(void) { return IQ_ABI_VERSION; }
 
@@ -51,16 +52,9 @@ extern "C" int iq_set_tuning(int key, int value) {
         iq::ts().no_lds_gemm = value != 0;
         return IQ_OK;
     }
-    if (key == iq::kTuneTwin) {
-        switch (value) {
-            case 0: case iq::kTwinEdgeGemmL2: case iq::kTwinEdgeGemmLds: case iq::kTwinKnnCompact: case iq::kTwinPcKnn:
-            case iq::kTwinPcGroupedMlp: case iq::kTwinKnnFp32Rank: case iq::kTwinPn2MemberWalk: case iq::kTwinKnnFp32Mfma:
-            case iq::kTwinPcTwoKernel: case iq::kTwinChainL3Fp32: case iq::kTwinChainL3Fp32NoTail16: case iq::kTwinGroupFp32:
-            case iq::kTwinDenseFp32: case iq::kTwinChainL3Single: case iq::kTwinDenseTile128: case iq::kTwinChainNoDedup:
-            case iq::kTwinGroupFp32Chunk64:
-                iq::ts().twin = value;
-                return IQ_OK;
-        }
+    if (key == iq::kTuneTwin && (value == 0 || iq::is_twin(value))) {
+        iq::ts().twin = value;
+        return IQ_OK;
     }
     return iq::fail(IQ_EINVAL, "iq_set_tuning: key %d value %d is not an experiment knob", key, value);
 }

@@ -25,7 +25,9 @@
 // (fused_path, launch_edgeconv).  Here: the layout kernels, the layer-1 walk, the pooling's second stage and the host driver.
 #include "iq_dgcnn_knn.h"
 #include "iq_edgeconv.h"
+#include "iq_profile.h"
 #include "iq_srclist.h"
+#include "iq_twin.h"
 
 namespace {
 

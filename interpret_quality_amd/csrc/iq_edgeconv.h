@@ -3,6 +3,7 @@
 // or gather_max_kernel.  fused_path decides per forward, launch_edgeconv per layer.  Included by iq_dgcnn.hip alone.
 #pragma once
 #include "iq_dgcnn_knn.h"
+#include "iq_twin.h"
 
 namespace {
 

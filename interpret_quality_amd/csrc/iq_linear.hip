@@ -8,7 +8,7 @@
 
 #include "iq_common.h"
 #include "iq_mfma.h"
-#include "iq_profile.h"
+#include "iq_twin.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 #include "iq_profile.h"
 #include "iq_srclist.h"
 #include "iq_topk.h"
+#include "iq_twin.h"
 
 namespace {
 

@@ -11,6 +11,8 @@
 #include <algorithm>
 
 #include "iq_pointnet_chain.h"
+#include "iq_profile.h"
+#include "iq_twin.h"
 
 namespace {
 

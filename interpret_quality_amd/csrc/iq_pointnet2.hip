@@ -26,6 +26,7 @@
 #include "iq_group_mlp.h"
 #include "iq_mfma.h"
 #include "iq_profile.h"
+#include "iq_twin.h"
 
 // Index-valued results depend on individually rounded operations: forbid the compiler from fusing
 // a*b+c into an fma anywhere in this file (explicit fmaf / MFMA calls are unaffected).

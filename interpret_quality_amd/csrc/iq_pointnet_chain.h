@@ -27,7 +27,7 @@
 #include <type_traits>
 
 #include "iq_common.h"
-#include "iq_profile.h"
+#include "iq_twin.h"
 
 #include "iq_bf3.h"
 #include "iq_mfma.h"

@@ -24,6 +24,7 @@ import numpy as np
 
 import probes
 import weight_variants as V
+from probes import rel_err  # noqa: F401  (the tests that import this module read it as F.rel_err)
 
 FAMILIES = ("pointnet2", "pointconv", "gcnn")
 VARIANTS = ("base", "seed1", "dead", "negshift", "varspread")
@@ -307,10 +308,6 @@ def choice_mismatches(run):
     a, b = run["choices"]["float32"], run["choices"]["float64"]
     assert [n for n, _ in a] == [n for n, _ in b]
     return [n for (n, x), (_, y) in zip(a, b) if x.shape != y.shape or not np.array_equal(x, y)]
-
-
-def rel_err(x, ref64):
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref64).max() / np.abs(ref64).max())
 
 
 def bar(e_ref, factor=FACTOR):

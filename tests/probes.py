@@ -406,6 +406,17 @@ def density_problems(got, want32, want64):
     return out
 
 
+def rel_err(x, ref64):
+    """max |x - ref64| over max |ref64|, in float64: the error figure of the float64-anchored tests."""
+    return float(np.abs(np.asarray(x, dtype=np.float64) - ref64).max() / np.abs(ref64).max())
+
+
+def same_tensors(a, b):
+    """Two sequences of torch tensors: as many, and each pair torch.equal."""
+    import torch
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
 def bitwise_equal(got, want):
     """Same shape and the same float32 bits everywhere."""
     got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)

@@ -3,8 +3,8 @@ pn_chain_kernel<kFstn | kTrunk, 3, false>; the 64-row twins are the modes kFstn6
 
 The cases are coalitions whose row counts sit on every edge of the 32-row m-tiles and of the 96-row chunks: 1, 31, 32, 33, 63, 64,
 65, 95, 96, 97, 127, 128, 129, 159, 160, 161, 191, 192, 193 rows and the full cloud (1024 rows: ten full chunks and a 64-row
-remainder).  Bars (tests/test_chain_shape_gpu.py's, none of them new): the 64-row kernel with one n-tile per pass (tuning 5 = 58)
-bit for bit, on logits and feature transforms; the fp32-MFMA twin (5 = 54) within 2e-6 of the largest value; a coalition alone in
+remainder).  Bars (tests/test_chain_shape_gpu.py's, none of them new): the 64-row kernel with one n-tile per pass ("chain_l3_single")
+bit for bit, on logits and feature transforms; the fp32-MFMA twin ("chain_l3_fp32") within 2e-6 of the largest value; a coalition alone in
 a launch against the same coalition inside the batch bit for bit; the dense forward on the materialised cloud (the 64-row arg-max
 kernel) bit for bit.
 
@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from interpret_quality_amd import hip_ops, synth
+from interpret_quality_amd import hip_ops, synth, tuning
 from interpret_quality_amd.pointnet import PointNetCls
 
 pytestmark = pytest.mark.gpu
@@ -62,19 +62,12 @@ def batch(model, case):
 
 
 def test_chunk_edges_against_the_64_row_kernel_and_the_fp32_twin(model, case, batch):
-    from interpret_quality_amd import _lib
     eng = model.engine()
     run = lambda: eng.coalition_logits(case["data"], case["center"], case["rid"], case["keep_t"], None, num_regions=case["nreg"],
                                        return_trans_feat=True)
     got, tf = batch
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, 54)
-        f32, tf_f32 = run()
-        lib.iq_set_tuning(5, 58)
-        one, tf_one = run()
-    finally:
-        lib.iq_set_tuning(5, 0)
+    f32, tf_f32 = tuning.tuned("chain_l3_fp32", run)
+    one, tf_one = tuning.tuned("chain_l3_single", run)
     assert torch.isfinite(got).all() and torch.isfinite(tf).all()
     err = (got - f32).abs().max().item() / f32.abs().max().item()
     err_tf = (tf - tf_f32).abs().max().item() / tf_f32.abs().max().item()
@@ -105,19 +98,14 @@ def test_dense_forward_equals_the_coalition_path(model, case, batch):
 
 def test_argmax_trunks_equal_their_plain_twins_and_name_kept_points(model, case, batch):
     """The arg-max trunks against the trunks without arg-max, logits bit for bit: pn_chain_kernel<kTrunk, 2, true> against
-    <kTrunk, 2, false> with its 16-row tails (tuning 5 = 54, documented bit-identical), and in the product path <kTrunk, 3, true>
-    (64-row chunks) against <kTrunk, 3, false> (96-row chunks).  Every arg-max index is a kept point of its coalition, or N (the
-    centre) in a coalition that has a centre row; the coalition of the centre alone names nothing else."""
-    from interpret_quality_amd import _lib
+    <kTrunk, 2, false> with its 16-row tails (twin "chain_l3_fp32", documented bit-identical), and in the product path
+    <kTrunk, 3, true> (64-row chunks) against <kTrunk, 3, false> (96-row chunks).  Every arg-max index is a kept point of its
+    coalition, or N (the centre) in a coalition that has a centre row; the coalition of the centre alone names nothing else."""
     eng = model.engine()
     run = lambda **kw: eng.coalition_logits(case["data"], case["center"], case["rid"], case["keep_t"], None, num_regions=case["nreg"], **kw)
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, 54)
+    with tuning.twin("chain_l3_fp32"):
         f32 = run()
         f32_arg, crt_f32 = run(return_crt=True)
-    finally:
-        lib.iq_set_tuning(5, 0)
     bf3_arg, crt_bf3 = run(return_crt=True)
     assert torch.equal(f32_arg, f32)
     assert torch.equal(bf3_arg, batch[0])

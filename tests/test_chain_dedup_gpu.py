@@ -1,13 +1,13 @@
 """GPU: repeated full and empty sets in one batch of PointNet coalitions.  Every permutation of a Shapley sample brings the full and
 the empty set once; with one cloud per call the chain kernels compute the first of each kind and the others take its pooled rows
 (pn_dup_rep_kernel, pn_dup_copy_kernel).  Logits, feature transforms and arg-max rows must equal, bit for bit, what the twin that
-computes every item gives (tuning key 5 = 60) and what an item gives alone - wherever the first of a kind stands."""
+computes every item gives (the twin "chain_no_dedup") and what an item gives alone - wherever the first of a kind stands."""
 import numpy as np
 import pytest
 import torch
 
 import probes
-from interpret_quality_amd import _lib, hip_ops, pointnet, synth
+from interpret_quality_amd import hip_ops, pointnet, synth, tuning
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -28,16 +28,12 @@ def _inputs(n, stray=False):
     return _INPUTS[n, stray]
 
 
-def _run(n, masks, twin=0, stray=False):
+def _run(n, masks, twin=None, stray=False):
     model, _ = probes.coalition_model("pointnet", DEV)
     clouds, centers, rid = _inputs(n, stray)
     keep = hip_ops.masks_to_tensor(np.asarray(masks, dtype=np.uint64), DEV)
-    lib = _lib.load()
-    try:
-        assert lib.iq_set_tuning(5, twin) == 0
+    with tuning.twin(twin):
         return model.engine().coalition_logits(clouds, centers, rid, keep, None, num_regions=R, return_trans_feat=True, return_crt=True)
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 def _batch(rng, b, first_full, first_empty):
@@ -56,10 +52,6 @@ def _batch(rng, b, first_full, first_empty):
     return masks
 
 
-def _same(a, b):
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("n", [200, 1024])
 @pytest.mark.parametrize("b,first_full,first_empty", [(2, 0, 2), (2, 2, 0), (37, 0, 1), (37, 36, 35), (37, 5, 37), (37, 37, 9),
                                                       (pointnet.ORDER_FUSED_MAX + 1, 4000, 17)])
@@ -69,13 +61,13 @@ def test_repeated_sets_equal_the_twin_and_the_item_alone(n, b, first_full, first
         masks[:] = FULL if first_full == 0 else 0       # nothing but copies of one item
     got = _run(n, masks)
     assert got[0].shape == (b, 10) and torch.isfinite(got[0]).all()
-    assert _same(got, _run(n, masks, twin=60))
+    assert probes.same_tensors(got, _run(n, masks, twin="chain_no_dedup"))
     for i in {b - 1, b // 2, min(first_full + 1, b - 1), min(first_empty + 1, b - 1)}:     # a copy (or any item) alone
-        assert _same([t[i:i + 1] for t in got], _run(n, masks[i:i + 1]))
+        assert probes.same_tensors([t[i:i + 1] for t in got], _run(n, masks[i:i + 1]))
 
 
 def test_a_full_mask_over_stray_points_is_no_full_set():
     """With a point outside every region the full mask keeps n - 1 points plus the centre: such items are computed, not copied -
     and still agree with the twin."""
     masks = _batch(np.random.default_rng(3), 21, 2, 4)
-    assert _same(_run(200, masks, stray=True), _run(200, masks, twin=60, stray=True))
+    assert probes.same_tensors(_run(200, masks, stray=True), _run(200, masks, twin="chain_no_dedup", stray=True))

@@ -5,10 +5,10 @@ stage0b_planes; every pn_chain_kernel<*, 3, *>).  One 200-point cloud, five regi
     magnitudes log-uniform in 2^-10 .. 2^10 and mixed signs, fstn.fc3 scaled so that the regressed 64 x 64 transform (the trunk's
     layer-1 weights) spans 1e-8 .. 1e2 with cancelling pairs in every column.  Logits and feature transforms against the float64
     CPU oracle with the project's bar e(HIP) <= min(4 e(float32 oracle) + 1e-7, 1e-4), e(x) = max |x - float64| / max |float64|,
-    and against the fp32-MFMA twin (tuning 5 = 54) within 2e-6 of the largest logit.
+    and against the fp32-MFMA twin ("chain_l3_fp32") within 2e-6 of the largest logit.
 (b) Row counts on both sides of every 16-row m-tile edge of layer 1: 1, 15, 16, 17, 32, 33, 64, 65, 80, 81, 96, 97, 192 and 193 rows
     (two labellings share them: no five region sizes give all fourteen) and the centre alone (the 1-row case); per count the
-    product kernels, the 64-row twin (5 = 58), the dense forward on the materialised cloud and the coalition alone in a launch
+    product kernels, the 64-row twin ("chain_l3_single"), the dense forward on the materialised cloud and the coalition alone in a launch
     agree bit for bit on logits, feature transforms and arg-max rows.
 (c) A row's result does not depend on its place: the same coalition through two labellings that order its rows differently gives
     the same pooled features, seen through the logits, the feature transform and the arg-max POINTS (every channel's maximum is
@@ -19,23 +19,16 @@ import torch
 
 import chain_l1_cases as C
 import weight_variants as V
-from interpret_quality_amd import _lib, hip_ops, synth
+from interpret_quality_amd import hip_ops, synth
 from interpret_quality_amd.pointnet import PointNetCls
+from interpret_quality_amd.tuning import tuned
+from probes import rel_err
 
 pytestmark = pytest.mark.gpu
 
 
 def dev():
     return torch.device("cuda:0")
-
-
-def tuned(key, fn):
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, key)
-        return fn()
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 def build_model(sd):
@@ -66,10 +59,6 @@ def dense(model, cloud, rid, keep):
 
 
 # ---- (a) wide-range layer-1 weights -----------------------------------------------------------------------------------------------
-
-def rel_err(x, ref64):
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref64).max() / np.abs(ref64).max())
-
 
 def assert_within_the_oracles_error(name, got, ref32, ref64):
     e_hip, e_ref = rel_err(got, ref64), rel_err(ref32, ref64)
@@ -103,7 +92,7 @@ def test_wide_range_layer1_weights_against_float64_and_the_fp32_twin(cloud, seed
     assert_within_the_oracles_error(tag + "dense logits", d_logits.cpu().numpy(), l32, l64)
     assert_within_the_oracles_error(tag + "dense trans_feat", d_tf.cpu().numpy(), t32, t64)
 
-    f32, tfp_f32 = tuned(54, lambda: run(model, cloud, rid, keep))
+    f32, tfp_f32 = tuned("chain_l3_fp32", lambda: run(model, cloud, rid, keep))
     err = (logits - f32).abs().max().item() / f32.abs().max().item()
     err_tf = (tfp - tfp_f32).abs().max().item() / tfp_f32.abs().max().item()
     print("%sagainst the fp32 twin: logits %.3g, feature transforms %.3g of the largest value" % (tag, err, err_tf))
@@ -126,7 +115,7 @@ def test_row_counts_across_the_tile_edges_bit_for_bit(model, cloud, sizes, seed)
     masks = C.masks_for(sizes, C.WANT_ROWS)
     keep = list(masks.values())
     got = run(model, cloud, rid, keep, return_crt=True)                     # logits, packed feature transforms, arg-max rows
-    twin = tuned(58, lambda: run(model, cloud, rid, keep, return_crt=True))
+    twin = tuned("chain_l3_single", lambda: run(model, cloud, rid, keep, return_crt=True))
     d_logits, d_tf, d_crt = dense(model, cloud, rid, keep)
     tf = got[1].index_select(1, model.engine().weights.unpack_index).reshape(-1, 64, 64)
     kept = np.stack([((k >> rid) & 1).astype(bool) for k in keep])

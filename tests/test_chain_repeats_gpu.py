@@ -2,14 +2,14 @@
 (1000 one-region prefixes are at most R distinct sets), so the library finds, on the device, the first item of every (cloud, kept
 regions) of a batch (pn_rep_insert_kernel, pn_rep_write_kernel), the chain kernels compute only those and the others take their
 pooled rows (pn_dup_copy_kernel).  Logits, feature transforms and arg-max rows must equal, bit for bit, what the twin that computes
-every item gives (tuning key 5 = 60) and what an item gives alone; the representatives themselves (iq_debug_pointnet_reps) must be
-NumPy's first occurrences, exactly."""
+every item gives (the twin "chain_no_dedup") and what an item gives alone; the representatives themselves
+(iq_debug_pointnet_reps) must be NumPy's first occurrences, exactly."""
 import numpy as np
 import pytest
 import torch
 
 import probes
-from interpret_quality_amd import _lib, hip_ops, pointnet, synth
+from interpret_quality_amd import _lib, hip_ops, pointnet, synth, tuning
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -32,21 +32,16 @@ def _inputs(n, r=R, nc=1, stray=False):
     return _INPUTS[key]
 
 
-def _run(inputs, masks, r=R, cloud_of=None, twin=0):
+def _run(inputs, masks, r=R, cloud_of=None, twin=None):
     model, _ = probes.coalition_model("pointnet", DEV)
     clouds, centers, rid = inputs
     keep = hip_ops.masks_to_tensor(np.asarray(masks, dtype=np.uint64), DEV)
     names = None if cloud_of is None else hip_ops.as_i32(np.asarray(cloud_of, dtype=np.int64), DEV)
-    lib = _lib.load()
-    try:
-        assert lib.iq_set_tuning(5, twin) == 0
+    with tuning.twin(twin):
         return model.engine().coalition_logits(clouds, centers, rid, keep, names, num_regions=r, return_trans_feat=True, return_crt=True)
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
-def _same(a, b):
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+_same = probes.same_tensors
 
 
 def _rows(out, idx):
@@ -101,7 +96,7 @@ def _high_bit_batch():
 def _check_twin_and_alone(inputs, masks, r=R, alone=()):
     got = _run(inputs, masks, r)
     assert got[0].shape == (len(masks), 10) and torch.isfinite(got[0]).all()
-    assert _same(got, _run(inputs, masks, r, twin=60))
+    assert _same(got, _run(inputs, masks, r, twin="chain_no_dedup"))
     for i in alone:
         assert _same(_rows(got, slice(i, i + 1)), _run(inputs, masks[i:i + 1], r)), i
     return got
@@ -133,7 +128,7 @@ def test_several_clouds_share_rows_only_inside_a_cloud():
     masks, cloud_of = _cloud_batch(nc=nc)
     inputs = _inputs(200, nc=nc)
     got = _run(inputs, masks, cloud_of=cloud_of)
-    assert _same(got, _run(inputs, masks, cloud_of=cloud_of, twin=60))
+    assert _same(got, _run(inputs, masks, cloud_of=cloud_of, twin="chain_no_dedup"))
     for c in range(nc):                                     # the same mask on another cloud is another coalition
         sel = np.flatnonzero(cloud_of == c)
         one = tuple(t[c:c + 1].contiguous() for t in inputs)

@@ -2,9 +2,9 @@
 
 The m-tiles are 16 rows now and a column's rows are spread over four lane groups, so the cases are coalitions whose row counts
 cover every residue mod 16 and the chunk edges: 1, 15, 16, 17, 31, 32, 33, 63, 64, 65 rows (and 2 .. 14), and the full cloud
-(1024 rows).  Bars (none of them new): the bf16x3 kernel against the fp32-MFMA twin (tuning 5 = 54) within 2e-6 of the largest
+(1024 rows).  Bars (none of them new): the bf16x3 kernel against the fp32-MFMA twin ("chain_l3_fp32") within 2e-6 of the largest
 value, on logits and feature transforms (tests/test_hip_parity.py's bar: the two differ only in the order of float32 additions);
-two n-tiles per pass (default) against one (5 = 58) bit for bit; a coalition alone in a launch against the same coalition inside a
+two n-tiles per pass (default) against one ("chain_l3_single") bit for bit; a coalition alone in a launch against the same coalition inside a
 batch bit for bit; the dense forward on the materialised cloud against the coalition path bit for bit, and its crt_points (the
 arg-max variant of the kernel) consistent with the pooled maxima: the same critical POINTS as the coalition path's arg-max, the
 lowest row among identical points (tie rule), and the same points after the rows are permuted (a row's result depends neither on
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from interpret_quality_amd import hip_ops, synth
+from interpret_quality_amd import hip_ops, synth, tuning
 from interpret_quality_amd.pointnet import PointNetCls
 
 pytestmark = pytest.mark.gpu
@@ -52,19 +52,12 @@ def case():
 
 
 def test_every_row_residue_against_the_fp32_twin_and_the_single_tile_pass(model, case):
-    from interpret_quality_amd import _lib
     eng = model.engine()
     run = lambda: eng.coalition_logits(case["data"], case["center"], case["rid"], case["keep_t"], None, num_regions=case["nreg"],
                                        return_trans_feat=True)
     got, tf = run()
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, 54)
-        f32, tf_f32 = run()
-        lib.iq_set_tuning(5, 58)
-        one, tf_one = run()
-    finally:
-        lib.iq_set_tuning(5, 0)
+    f32, tf_f32 = tuning.tuned("chain_l3_fp32", run)
+    one, tf_one = tuning.tuned("chain_l3_single", run)
     assert torch.isfinite(got).all() and torch.isfinite(tf).all()
     err = (got - f32).abs().max().item() / f32.abs().max().item()
     err_tf = (tf - tf_f32).abs().max().item() / tf_f32.abs().max().item()

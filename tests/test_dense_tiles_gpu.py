@@ -1,7 +1,7 @@
 """GPU: the bf16x3 dense layer (pn_gemm_bf3_kernel<false>, pn_gemm_bf3_short_kernel) with the tile heights launch_linear chooses for
 iq_linear and PointNet's heads - 128-row
 workgroups in whole rounds of 2 x CUs, 32- / 64-row ones throughout for a launch below one / two rounds and for the rows of a
-nearly empty last round - against the same layer on 128-row tiles only (tuning key 5 = 59, the former launch): bit for bit, for every row count
+nearly empty last round - against the same layer on 128-row tiles only (twin "dense_tile128", the former launch): bit for bit, for every row count
 around the tile edges and around the rounds of THIS device.  Each case also holds what
 test_hip_parity.py::test_dense_layer_on_the_bf16_matrix_pipe_is_float32_exact holds (its bars against a float64 product, a
 row's result independent of the launch it is in), and that the C entry writes no row beyond M.
@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from interpret_quality_amd import _lib, hip_ops
+from interpret_quality_amd.tuning import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -30,15 +31,6 @@ def dev():
 def rel_err(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
-
-
-def tuned(value, fn):
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, value)
-        return fn()
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 _LAYERS = {}
@@ -60,11 +52,11 @@ def check_case(m, cin, cout, act):
     x = np.random.default_rng(m + cin).standard_normal((m, cin)).astype(np.float32)
     xt = torch.from_numpy(x).to(d)
     got = hip_ops.linear(xt, layer, act)
-    former = tuned(59, lambda: hip_ops.linear(xt, layer, act))
+    former = tuned("dense_tile128", lambda: hip_ops.linear(xt, layer, act))
     assert torch.equal(got, former), "M=%d: %d values differ from the 128-row launch" % (m, int((got != former).sum()))
     k = min(m, 77)
     assert torch.equal(hip_ops.linear(xt[:k].contiguous(), layer, act), got[:k])          # launch-size independent
-    f32 = tuned(57, lambda: hip_ops.linear(xt, layer, act))
+    f32 = tuned("dense_fp32", lambda: hip_ops.linear(xt, layer, act))
     ref = torch.from_numpy(x).double() @ torch.from_numpy(w).double().T + torch.from_numpy(b).double()
     if act == 1:
         ref = torch.relu(ref)

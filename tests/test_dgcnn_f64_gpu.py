@@ -3,8 +3,8 @@
 
 Graphs first, so that a failure is tied to a layer before the logits are looked at: ``hip_ops.knn`` on xyz and on the float32
 oracle's x1, x2, x3 must give the float64 oracle's canonical neighbour sets for EVERY query - no mismatch allowance, these cases have
-no near ties - under the default (three-term bf16 distances, near ties re-ranked exactly), under tuning key 5 = 20 (float32 ranking
-only) and 5 = 22 (distances on the fp32 MFMA).  ``hip_ops.knn`` takes multiples of 32 rows: other sizes are padded with rows far
+no near ties - under the default (three-term bf16 distances, near ties re-ranked exactly), under the twins "knn_fp32_rank" (5 = 20,
+float32 ranking only) and "knn_fp32_mfma" (5 = 22, distances on the fp32 MFMA).  ``hip_ops.knn`` takes multiples of 32 rows: other sizes are padded with rows far
 from every point, which are nobody's neighbours and whose own lists are not looked at.
 
 Logits: with e(x) = max |x - float64| / max |float64| over the logits of a case, every route must satisfy
@@ -42,23 +42,15 @@ import dgcnn_f64_cases as D
 import f64_cases as F
 import probes
 import weight_variants as V
-from interpret_quality_amd import _lib, hip_ops, synth
+from interpret_quality_amd import hip_ops, synth
+from interpret_quality_amd.tuning import tuned
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-TWINS = (7, 8, 12, 20, 22, 57)
-KNN_KEYS = (0, 20, 22)      # the default, float32 ranking only, distances on the fp32 MFMA
+TWINS = ("edge_gemm_l2", "edge_gemm_lds", "knn_compact", "knn_fp32_rank", "knn_fp32_mfma", "dense_fp32")
+KNN_KEYS = (None, "knn_fp32_rank", "knn_fp32_mfma")      # the default, float32 ranking only, distances on the fp32 MFMA
 # per route, where it is not f64_cases.FACTOR: (factor, measured ratio, reason) - none so far
 FACTORS = {}
-
-
-def tuned(key, fn):
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, key)
-        return fn()
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 def upload(inp, wide, r):
@@ -98,8 +90,8 @@ def routes(case, model, d, twins=TWINS):
         coal = lambda: model.coalition_logits(d["clouds"], d["centers"], d["rid"], d["keep"], d["cloud_of"], num_regions=case.spec.r)
     out = [("forward_points", dense), (entry, coal)]
     for key in twins:
-        out.append(("forward_points, 5 = %d" % key, lambda key=key: tuned(key, dense)))
-        out.append(("%s, 5 = %d" % (entry, key), lambda key=key: tuned(key, coal)))
+        out.append(("forward_points, %s" % key, lambda key=key: tuned(key, dense)))
+        out.append(("%s, %s" % (entry, key), lambda key=key: tuned(key, coal)))
     return out
 
 
@@ -143,7 +135,7 @@ def test_graphs_are_the_float64_graphs(pair):
         for key in KNN_KEYS:
             got = D.canonical_sets(tuned(key, lambda: hip_graph(x, far)), rows)
             bad = int((got != want).any(axis=-1).sum())
-            print("%-44s %-8s 5 = %-2d queries with another neighbour set: %d of %d" % (D.pair_id(pair), name, key, bad, rows.size))
+            print("%-44s %-8s %-13s queries with another neighbour set: %d of %d" % (D.pair_id(pair), name, key, bad, rows.size))
             if bad:
                 wrong.append((name, key, bad))
     assert not wrong, wrong
@@ -170,7 +162,7 @@ def test_centre_multiplicity_around_k_and_the_empty_coalition():
     run = D.oracle_run(case, "base", multiplicity=True)
     assert D.decidable(run) and F.choice_mismatches(run) == []
     masked = (~D.multiplicity_inputs(case)["kept"]).sum(axis=1)
-    got = measure("multiplicity M = %d, %d" % tuple(masked), routes(case, model, device_inputs(case, True), twins=(12, 20)), run)
+    got = measure("multiplicity M = %d, %d" % tuple(masked), routes(case, model, device_inputs(case, True), twins=("knn_compact", "knn_fp32_rank")), run)
     assert not above(got), above(got)
 
 

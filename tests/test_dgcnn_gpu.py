@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import assert_close_elementwise, load_golden
-from interpret_quality_amd import hip_ops, interaction, synth
+from interpret_quality_amd import hip_ops, interaction, synth, tuning
 from interpret_quality_amd.dgcnn import DGCNN_cls, GCNN_cls
 
 pytestmark = pytest.mark.gpu
@@ -95,9 +95,8 @@ def test_knn_near_ties_are_ranked_by_exact_distances(c, arith):
     nearest, knn_refine_kernel ranks by -sum (q - k)^2 in float64 (what the reference's float64 run sees).  Rows are planted
     with near-ties at the boundary (triplets of keys whose distances to a query differ by a few 1e-5 of the distance, below the float32 noise of the expanded form); the neighbour sets must
     equal the float64 top-20 of the SAME float32 features for every query whose exact 20th / 21st gap exceeds 1e-6 of the
-    distance (a gap the float32 differences resolve), while the float32-only ranking (tuning key 5 = 20) provably gets some
+    distance (a gap the float32 differences resolve), while the float32-only ranking (twin "knn_fp32_rank") provably gets some
     of them wrong - so the test has power."""
-    from interpret_quality_amd import _lib
     rng = np.random.default_rng(c)
     b, n = 2, 512
     x = rng.standard_normal((b, n, c)).astype(np.float32) + 3.0   # large common offset: |x|^2 >> |x_i - x_j|^2, strong cancellation
@@ -119,18 +118,12 @@ def test_knn_near_ties_are_ranked_by_exact_distances(c, arith):
                     n_bad += 1
         return n_bad
 
-    lib = _lib.load()
-    lib.iq_set_tuning(5, 22 if arith == "fp32" else 0)    # the inner products: fp32 MFMA | three-term bf16 products (the default)
-    try:
+    # the inner products: fp32 MFMA | three-term bf16 products (the default)
+    with tuning.twin("knn_fp32_mfma" if arith == "fp32" else None):
         got = hip_ops.knn(xt, 20).cpu().numpy()
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert all(len(set(r.tolist())) == 20 for r in got.reshape(-1, 20))
-    lib.iq_set_tuning(5, 20)
-    try:
+    with tuning.twin("knn_fp32_rank"):
         got32 = hip_ops.knn(xt, 20).cpu().numpy()
-    finally:
-        lib.iq_set_tuning(5, 0)
     n_dec = int(decidable.sum())
     print("C=%d %s: %d of %d queries decidable; wrong neighbour sets: refined %d, float32 ranking only %d" % (c, arith, n_dec, b * n, wrong(got), wrong(got32)))
     assert n_dec > 0.9 * b * n
@@ -265,10 +258,8 @@ def test_interaction_shape_properties_at_bench_size():
 @pytest.mark.parametrize("cls", [DGCNN_cls, GCNN_cls])
 def test_fused_edgeconv_is_bitwise_the_gemm_plus_gather(cls):
     """edge_fused_kernel (P/Q GEMM transposed onto the MFMA, P slice of the cloud in LDS, neighbourhood max from LDS) against
-    the separate GEMM + gather_lds_kernel (tuning key 5 = 8) and GEMM + gather_max_kernel (5 = 7): the same products in
-    the same order and the same maxima, so bit-identical logits - dense clouds and compact coalitions of every size class."""
-    from interpret_quality_amd import _lib
-    lib = _lib.load()
+    the separate GEMM + gather_lds_kernel (twin "edge_gemm_lds") and GEMM + gather_max_kernel ("edge_gemm_l2"): the same products
+    in the same order and the same maxima, so bit-identical logits - dense clouds and compact coalitions of every size class."""
     model = make(cls)
     d = dev()
     rng = np.random.default_rng(5)
@@ -285,31 +276,19 @@ def test_fused_edgeconv_is_bitwise_the_gemm_plus_gather(cls):
         return (model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32).clone(),
                 model.forward_points(clouds).clone())
     fused = both()
-    for knob in (8, 7):
-        lib.iq_set_tuning(5, knob)
-        try:
-            split = both()
-        finally:
-            lib.iq_set_tuning(5, 0)
-        assert torch.equal(fused[0], split[0]) and torch.equal(fused[1], split[1]), knob
+    for name in ("edge_gemm_lds", "edge_gemm_l2"):
+        split = tuning.tuned(name, both)
+        assert torch.equal(fused[0], split[0]) and torch.equal(fused[1], split[1]), name
 
 
 def test_knn_on_the_bf16_pipe_gives_the_graphs_of_the_fp32_mfma():
     """DGCNN's feature-space graphs with the inner products as three-term bf16 products (knn_kernel<.., BF3>, the default) against
-    the fp32-MFMA kernels (tuning key 5 = 22).  Both score within float32 rounding of the exact inner product and both hand every
+    the fp32-MFMA kernels (twin "knn_fp32_mfma").  Both score within float32 rounding of the exact inner product and both hand every
     query whose boundary they cannot decide to the same exact re-ranking, so the neighbour SETS agree and with them the logits, bit
     for bit - on the op (random features with planted near-ties) and through the model (dense forward and compact coalitions)."""
-    from interpret_quality_amd import _lib
-    lib = _lib.load()
     d = dev()
     rng = np.random.default_rng(17)
-
-    def fp32(fn):
-        lib.iq_set_tuning(5, 22)
-        try:
-            return fn()
-        finally:
-            lib.iq_set_tuning(5, 0)
+    fp32 = lambda fn: tuning.tuned("knn_fp32_mfma", fn)
     for c in (64, 128):
         x = rng.standard_normal((3, 1024, c)).astype(np.float32) + 1.5
         x[:, 1::4] = x[:, 0::4] + (rng.standard_normal((3, 256, c)) * 1e-4).astype(np.float32)
@@ -376,10 +355,8 @@ def test_centre_multiplicity_around_k(cls):
 @pytest.mark.parametrize("cls", [DGCNN_cls, GCNN_cls])
 def test_layer1_graph_from_source_lists_is_bitwise_the_knn_kernel(cls):
     """dg_walk_kernel (layer-1 neighbours of a coalition = the first kept entries of its source point's sorted neighbour list,
-    the centre counting min(M, 20) times) against knn_kernel<8> on the compact rows (tuning key 5 = 12): the same
+    the centre counting min(M, 20) times) against knn_kernel<8> on the compact rows (twin "knn_compact"): the same
     neighbour sets, so bit-identical logits - two source clouds, coalitions from empty to full."""
-    from interpret_quality_amd import _lib
-    lib = _lib.load()
     model = make(cls)
     d = dev()
     rng = np.random.default_rng(21)
@@ -394,11 +371,8 @@ def test_layer1_graph_from_source_lists_is_bitwise_the_knn_kernel(cls):
     keep_t = hip_ops.masks_to_tensor(keep, d)
     co_t = torch.tensor(cloud_of, dtype=torch.int32, device=d)
     walk = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=34).clone()
-    lib.iq_set_tuning(5, 12)
-    try:
+    with tuning.twin("knn_compact"):
         knn = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=34).clone()
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert torch.equal(walk, knn)
 
 

@@ -2,7 +2,7 @@
 group, moves those U items to slots 0 .. U-1 (pn_compact kernels; U stays on the device), runs row lists, gather, launch order, chains
 and heads on the slots, and gives every item its slot's results at the end (pn_expand kernels).  Checked here: the slot map against
 NumPy's first occurrences and their ranks (iq_debug_pointnet_slots), and logits, feature transforms and arg-max rows bit for bit
-against the twin that evaluates every item in place (tuning key 5 = 60) and against items run alone - with U on both sides of the
+against the twin that evaluates every item in place (twin "chain_no_dedup") and against items run alone - with U on both sides of the
 heads' tile heights (32, 64, 128 rows) and of the one-workgroup bound of the order and compaction kernels, with the workspace filled
 with NaN patterns beforehand (a read of a row at or past U shows as a NaN or a changed bit), without the optional outputs, and on the
 routes that are not compacted."""
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import probes
-from interpret_quality_amd import _lib, hip_ops, pointnet, synth
+from interpret_quality_amd import _lib, hip_ops, pointnet, synth, tuning
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -34,29 +34,26 @@ def _engine():
     return probes.coalition_model("pointnet", DEV)[0].engine()
 
 
-def _run(inputs, masks, r=R, cloud_of=None, twin=0, poison=False, tf=True, crt=True):
+def _run(inputs, masks, r=R, cloud_of=None, twin=None, poison=False, tf=True, crt=True):
     """One forward.  ``poison``: in a workspace of exactly the size the library asks for, every byte 0xff (float NaNs, int -1)."""
     eng = _engine()
     clouds, centers, rid = inputs
     keep = hip_ops.masks_to_tensor(np.asarray(masks, dtype=np.uint64), DEV)
     names = None if cloud_of is None else hip_ops.as_i32(np.asarray(cloud_of, dtype=np.int64), DEV)
-    lib = _lib.load()
     if poison:
-        need = lib.iq_pointnet_workspace_bytes(len(masks), clouds.shape[0], N, r)
+        need = _lib.load().iq_pointnet_workspace_bytes(len(masks), clouds.shape[0], N, r)
         eng._ws = torch.full((int(need),), 0xFF, dtype=torch.uint8, device=DEV)
     try:
-        assert lib.iq_set_tuning(5, twin) == 0
-        out = eng.coalition_logits(clouds, centers, rid, keep, names, num_regions=r, return_trans_feat=tf, return_crt=crt)
-        torch.cuda.synchronize()
+        with tuning.twin(twin):
+            out = eng.coalition_logits(clouds, centers, rid, keep, names, num_regions=r, return_trans_feat=tf, return_crt=crt)
+            torch.cuda.synchronize()
         return out if isinstance(out, tuple) else (out,)
     finally:
-        lib.iq_set_tuning(5, 0)
         if poison:
             eng._ws = None
 
 
-def _same(a, b):
-    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+_same = probes.same_tensors
 
 
 def _reference(masks, r, cloud_of=None):
@@ -129,7 +126,7 @@ def _case(b, u, r=R):
     if key not in _RUNS:
         masks = _batch(b, u, r)
         assert _reference(masks, r)[3] == u
-        _RUNS[key] = (masks, _run(_inputs(r), masks, r), _run(_inputs(r), masks, r, twin=60))
+        _RUNS[key] = (masks, _run(_inputs(r), masks, r), _run(_inputs(r), masks, r, twin="chain_no_dedup"))
     return _RUNS[key]
 
 
@@ -170,7 +167,7 @@ def test_several_clouds_with_cloud_of():
     masks, cloud_of = _batch(140, 9, seed=4), rng.integers(0, 3, size=140)
     inputs = _inputs(nc=3)
     got = _run(inputs, masks, cloud_of=cloud_of)
-    assert _same(got, _run(inputs, masks, cloud_of=cloud_of, twin=60))
+    assert _same(got, _run(inputs, masks, cloud_of=cloud_of, twin="chain_no_dedup"))
     assert _same(got, _run(inputs, masks, cloud_of=cloud_of, poison=True))
     for c in range(3):
         sel = np.flatnonzero(cloud_of == c)
@@ -180,14 +177,10 @@ def test_several_clouds_with_cloud_of():
 
 # ---- the routes that are not compacted: the same launches with every item its own slot ------------------------------------------
 def _with_twin(fn, twin):
-    lib = _lib.load()
-    try:
-        assert lib.iq_set_tuning(5, twin) == 0
+    with tuning.twin(twin):
         out = fn()
         torch.cuda.synchronize()
         return out
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 def test_wide_entry_at_66_items():
@@ -196,8 +189,8 @@ def test_wide_entry_at_66_items():
     masks = _batch(66, 20, r, seed=6)
     keep = hip_ops.masks_to_tensor(masks, DEV).reshape(66, 1).contiguous()
     run = lambda: _engine().coalition_logits_wide(clouds, centers, rid, keep, None, num_regions=r, return_trans_feat=True)
-    got = _with_twin(run, 0)
-    assert _same(got, _with_twin(run, 60))
+    got = _with_twin(run, None)
+    assert _same(got, _with_twin(run, "chain_no_dedup"))
     narrow = _run(_inputs(r), masks, r)                     # the same coalitions through the compacted narrow entry
     assert torch.equal(got[0], narrow[0]) and torch.equal(got[1], narrow[1])
 
@@ -208,8 +201,8 @@ def test_prefix_entry_at_66_items():
     rng = np.random.default_rng(8)
     orders = hip_ops.as_i32(np.stack([rng.permutation(r) for _ in range(6)]), DEV)
     run = lambda: _engine().prefix_logits_wide(clouds, centers, rid, orders, None, num_regions=r, return_trans_feat=True)
-    got = _with_twin(run, 0)
-    assert got[0].shape == (66, 10) and _same(got, _with_twin(run, 60))
+    got = _with_twin(run, None)
+    assert got[0].shape == (66, 10) and _same(got, _with_twin(run, "chain_no_dedup"))
     keep = hip_ops.prefix_keep_masks_wide(orders)
     wide = _engine().coalition_logits_wide(clouds, centers, rid, keep, None, num_regions=r, return_trans_feat=True)
     assert _same(got, wide)
@@ -223,7 +216,7 @@ def test_a_cloud_per_item_without_cloud_of_at_66_items():
     inputs = (clouds, clouds.mean(dim=1).contiguous(), hip_ops.as_i32(rng.integers(0, R, size=(nc, N)), DEV))
     masks = _batch(nc, 5, seed=3)                           # equal masks, but every item has a cloud of its own
     got = _run(inputs, masks)
-    assert _same(got, _run(inputs, masks, twin=60))
+    assert _same(got, _run(inputs, masks, twin="chain_no_dedup"))
     assert _same(got, _run(inputs, masks, poison=True))
     for i in (0, 37, 65):
         one = tuple(t[i:i + 1].contiguous() for t in inputs)

@@ -8,7 +8,8 @@ fail it.  The last test here shows the same loss on the device.
 
 Routes, one printed row each (name, e_hip, e_ref, e_hip / e_ref, bar), per (family, case, variant):
   all       the dense forward on the uploaded host-masked clouds; the coalition entry (``coalition_logits`` with ``cloud_of``; the
-            ``wide`` case: ``coalition_logits_wide`` at R = 128); both again under every twin of the family (tuning key 5)
+            ``wide`` case: ``coalition_logits_wide`` at R = 128); both again under every twin of the family (TWINS below; the figures
+            further down name them by their tuning key 5 value: interpret_quality_amd.tuning.TWINS)
   pointnet2 twins 21 (member walk), 56 / 64 (fp32-MFMA grouped kernels), 57 (dense layers on the fp32 MFMA).  Case ``overflow``:
             256 points shrunk to a diameter of 0.3, so all 257^2 ordered pairs of (points + centre) lie within sa1's radius 0.4 and
             exceed the pair table's 192 x 257 rows: that scale runs the grouped MLP inside the coalition entry.  Known from the count
@@ -49,24 +50,16 @@ import torch
 import f64_cases as F
 import probes
 import weight_variants as V
-from interpret_quality_amd import _lib, hip_ops, synth
+from interpret_quality_amd import hip_ops, synth
+from interpret_quality_amd.tuning import tuned
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-TWINS = {"pointnet2": (21, 56, 64, 57), "pointconv": (14, 15, 31, 56, 57), "gcnn": (7, 8, 12, 57)}
+TWINS = {"pointnet2": ("pn2_member_walk", "group_fp32", "group_fp32_chunk64", "dense_fp32"),
+         "pointconv": ("pc_knn", "pc_grouped_mlp", "pc_two_kernel", "group_fp32", "dense_fp32"),
+         "gcnn": ("edge_gemm_l2", "edge_gemm_lds", "knn_compact", "dense_fp32")}
 # per route, where it is not f64_cases.FACTOR: (factor, measured ratio, reason) - none so far
 FACTORS = {}
-
-
-def tuned(key, fn):
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, key)
-        return fn()
-    finally:
-        lib.iq_set_tuning(5, 0)
-
-
 _DEVICE = {}
 
 
@@ -114,8 +107,8 @@ def routes(family, case, model):
         forced = lambda walk: model.engine().coalition_logits(*fresh(), d["rid"], d["keep"], d["cloud_of"], walk)
     out = [("forward_points", dense), (entry, coal)]
     for key in TWINS[family]:
-        out.append(("forward_points, 5 = %d" % key, lambda key=key: tuned(key, dense)))
-        out.append(("%s, 5 = %d" % (entry, key), lambda key=key: tuned(key, coal)))
+        out.append(("forward_points, %s" % key, lambda key=key: tuned(key, dense)))
+        out.append(("%s, %s" % (entry, key), lambda key=key: tuned(key, coal)))
     if family == "pointconv":
         out += [("%s, walk off" % entry, lambda: forced(False)), ("%s, walk on" % entry, lambda: forced(True))]
     return out

@@ -2,7 +2,7 @@
 three bf16 terms on the device, per call (the weight descriptor carries no bf16x3 image of it), and the layer then runs like
 the other wide heads.  64 points in 4 regions, 1, 5 and 130 coalitions (one row tile of the layer, and two with a partial one):
 (a) coalition path = dense forward on the materialised clouds = the coalition alone, bit for bit (logits, feature transforms);
-(b) under tuning key 5 = 57 (dense layers on the fp32 MFMA: no split) the feature transforms are NOT the same bits;
+(b) under the twin "dense_fp32" (dense layers on the fp32 MFMA: no split) the feature transforms are NOT the same bits;
 (c) against a float64 run of the CPU oracle the bar of tests/test_stress_weights_gpu.py,
     e(HIP) <= min(4 e(float32 oracle) + 1e-7, 1e-4), for the base weights and the variance-spread variant;
 and without a feature STN (feature_transform=False) the trunk still gets the packed identity, exactly."""
@@ -14,8 +14,10 @@ import torch
 
 import probes
 import weight_variants as V
-from interpret_quality_amd import _lib, hip_ops, synth
+from interpret_quality_amd import hip_ops, synth
 from interpret_quality_amd.pointnet import PointNetCls
+from interpret_quality_amd.tuning import tuned
+from probes import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -25,15 +27,6 @@ BATCHES = (1, 5, 130)
 
 def dev():
     return torch.device("cuda:0")
-
-
-def tuned(value, fn):
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, value)
-        return fn()
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 _CASE = {}
@@ -77,16 +70,12 @@ def test_coalition_dense_and_alone_are_the_same_bits(b):
         alone, tf_alone = run(eng, c["keep_t"][i:i + 1].contiguous())
         assert torch.equal(alone[0], logits[i]) and torch.equal(tf_alone[0], tfp[i]), "coalition %d of %d" % (i, b)
     # (b) the fp32-MFMA twin of the dense layers computes other bits: fc3 is on the bf16 pipe by default
-    _, tfp_f32 = tuned(57, lambda: run(eng, c["keep_t"][:b].contiguous()))
+    _, tfp_f32 = tuned("dense_fp32", lambda: run(eng, c["keep_t"][:b].contiguous()))
     assert not torch.equal(tfp_f32, tfp)
     assert (tfp_f32 - tfp).abs().max().item() < 1e-5 * tfp.abs().max().item()
     # and the 128-row launch of the heads the same ones
-    l128, tfp128 = tuned(59, lambda: run(eng, c["keep_t"][:b].contiguous()))
+    l128, tfp128 = tuned("dense_tile128", lambda: run(eng, c["keep_t"][:b].contiguous()))
     assert torch.equal(l128, logits) and torch.equal(tfp128, tfp)
-
-
-def rel_err(x, ref64):
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref64).max() / np.abs(ref64).max())
 
 
 @pytest.mark.parametrize("variant", ("base", "varspread"))
@@ -116,8 +105,8 @@ def test_without_a_feature_stn_the_trunk_still_gets_the_packed_identity():
     assert torch.equal(unpacked(eng, tfp), eye)                                # the packed identity, every coalition
     d_logits, d_tf, _ = m(c["masked"].permute(0, 2, 1).contiguous())
     assert d_tf is None and torch.equal(d_logits, logits)
-    for value in (57, 59):                                                     # no split and no fc3 launch either way
-        _, tfp_t = tuned(value, lambda: run(eng, c["keep_t"]))
+    for name in ("dense_fp32", "dense_tile128"):                               # no split and no fc3 launch either way
+        _, tfp_t = tuned(name, lambda: run(eng, c["keep_t"]))
         assert torch.equal(tfp_t, tfp)
-    l128, _ = tuned(59, lambda: run(eng, c["keep_t"]))
+    l128, _ = tuned("dense_tile128", lambda: run(eng, c["keep_t"]))
     assert torch.equal(l128, logits)

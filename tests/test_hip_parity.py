@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from conftest import assert_close_elementwise, load_golden
-from interpret_quality_amd import final_common, hip_ops, synth
+from interpret_quality_amd import final_common, hip_ops, synth, tuning
 from interpret_quality_amd.pointnet import PointNetCls
 
 pytestmark = pytest.mark.gpu
@@ -333,7 +333,6 @@ def test_pointnet_multi_cloud_batch(model, oracle):
                                              # exactly 10 tiles (NT = 5), 128 outputs on 256-row workgroup tiles (WN = 1)
                                              (262200, 320, 320, 1), (524400, 128, 128, 1), (525000, 64, 128, 0)])
 def test_linear_variants_agree_and_match_fp32_reference(m, cin, cout, act):
-    from interpret_quality_amd import _lib
     rng = np.random.default_rng(m + cin)
     w = (rng.standard_normal((cout, cin)) / np.sqrt(cin)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
@@ -341,13 +340,9 @@ def test_linear_variants_agree_and_match_fp32_reference(m, cin, cout, act):
     d = dev()
     layer = hip_ops.PackedLinear(w, b, d)
     xt = torch.from_numpy(x).to(d)
-    lib = _lib.load()
     got = hip_ops.linear(xt, layer, act)                       # LDS-staged GEMM where the shape allows it
-    lib.iq_set_tuning(3, 1)
-    try:
+    with tuning.no_lds_gemm():
         streaming = hip_ops.linear(xt, layer, act)             # register-streaming kernel only
-    finally:
-        lib.iq_set_tuning(3, 0)
     assert torch.equal(got, streaming)                         # same MFMA order over k: bit-identical
     ref = torch.from_numpy(x).double() @ torch.from_numpy(w).double().T + torch.from_numpy(b).double()
     if act == 1:
@@ -368,9 +363,8 @@ def test_linear_variants_agree_and_match_fp32_reference(m, cin, cout, act):
 def test_dense_layer_on_the_bf16_matrix_pipe_is_float32_exact(m, cin, cout, act):
     """A layer that carries its weights as three bf16 terms (iq_dense_layer.w_bf3, cout % 256 == 0 or 64) takes six exact bf16 products
     per float32 product, accumulated in float32 (pn_gemm_bf3_kernel<false>), for every row count: at least as close to the
-    float64 result as the fp32-MFMA kernel (tuning key 5 = 57), equal to it within float32 rounding, and a row's result does
+    float64 result as the fp32-MFMA kernel (twin "dense_fp32"), equal to it within float32 rounding, and a row's result does
     not depend on the rows around it."""
-    from interpret_quality_amd import _lib
     rng = np.random.default_rng(m + cin)
     w = (rng.standard_normal((cout, cin)) / np.sqrt(cin)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
@@ -378,13 +372,8 @@ def test_dense_layer_on_the_bf16_matrix_pipe_is_float32_exact(m, cin, cout, act)
     d = dev()
     layer = hip_ops.PackedLinear(w, b, d, bf3=True)
     xt = torch.from_numpy(x).to(d)
-    lib = _lib.load()
     got = hip_ops.linear(xt, layer, act)
-    lib.iq_set_tuning(5, 57)
-    try:
-        f32 = hip_ops.linear(xt, layer, act)
-    finally:
-        lib.iq_set_tuning(5, 0)
+    f32 = tuning.tuned("dense_fp32", lambda: hip_ops.linear(xt, layer, act))
     ref = torch.from_numpy(x).double() @ torch.from_numpy(w).double().T + torch.from_numpy(b).double()
     if act == 1:
         ref = torch.relu(ref)
@@ -449,13 +438,13 @@ def test_pointnet_without_feature_transform():
 def test_chain_tail_tiles_are_bit_identical_for_every_row_count(model):
     """Layer 3 of the chain kernel, for coalitions whose distinct-row counts cover every residue mod 32 (64 regions of 1 to 31
     points, 400 random coalitions):
-    - the fp32-MFMA kernel (tuning key 5 = 54) with its 16-row tail tiles (l3_tail16: v_mfma_f32_16x16x4_f32 fed in the k order
-      of the 32x32x2 fragments) against 32-row tiles only (5 = 55): bit-identical logits and packed feature transforms;
+    - the fp32-MFMA kernel (twin "chain_l3_fp32") with its 16-row tail tiles (l3_tail16: v_mfma_f32_16x16x4_f32 fed in the k order
+      of the 32x32x2 fragments) against 32-row tiles only ("chain_l3_fp32_no_tail16"): bit-identical logits and packed feature
+      transforms;
     - the default kernel (layers 2-3 as six bf16 products per float32 product, float32 accumulation) against the fp32-MFMA one:
       the same logits to float32 rounding (measured 3e-7 of the largest logit; the two sum k in different orders); two n-tiles
-      per pass (default) against one (5 = 58): bit-identical;
+      per pass (default) against one ("chain_l3_single"): bit-identical;
     - and the dense forward (1024 rows) on the materialised clouds of a few coalitions, bitwise against the coalition path."""
-    from interpret_quality_amd import _lib
     d = dev()
     rng = np.random.default_rng(3)
     pts, _ = synth.make_cloud(11)
@@ -477,16 +466,12 @@ def test_chain_tail_tiles_are_bit_identical_for_every_row_count(model):
     rows = kept_rows + (kept_rows < 1024)
     assert len(set((rows % 32).tolist())) == 32                      # every residue occurs
     got, tf = eng.coalition_logits(data, center, rid_t, keep_t, None, num_regions=64, return_trans_feat=True)
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, 54)
+    with tuning.twin("chain_l3_fp32"):
         f32, tf_f32 = eng.coalition_logits(data, center, rid_t, keep_t, None, num_regions=64, return_trans_feat=True)
-        lib.iq_set_tuning(5, 55)
+    with tuning.twin("chain_l3_fp32_no_tail16"):
         ref, tf_ref = eng.coalition_logits(data, center, rid_t, keep_t, None, num_regions=64, return_trans_feat=True)
-        lib.iq_set_tuning(5, 58)     # bf16x3 layer 3 one n-tile per pass instead of two: the same products in the same order
+    with tuning.twin("chain_l3_single"):     # bf16x3 layer 3 one n-tile per pass instead of two: the same products in the same order
         one, tf_one = eng.coalition_logits(data, center, rid_t, keep_t, None, num_regions=64, return_trans_feat=True)
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert torch.equal(f32, ref) and torch.equal(tf_f32, tf_ref)
     assert torch.equal(got, one) and torch.equal(tf, tf_one)
     assert not torch.equal(got, f32)                                  # two different kernels did run

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from conftest import assert_close_elementwise, load_golden
-from interpret_quality_amd import final_common, hip_ops, synth
+from interpret_quality_amd import final_common, hip_ops, synth, tuning
 from interpret_quality_amd.pointconv import PointConvDensityClsSsg
 
 pytestmark = pytest.mark.gpu
@@ -74,11 +74,9 @@ def test_coalitions_from_source_lists_equal_the_forward_on_masked_clouds(model, 
     lists, sa1's MLP rows from the per-cloud pair table) against iq_pointconv_forward on the materialised masked clouds
     (pc_knn_kernel, grouped MLP): the same groups up to ties
     and the choice among interchangeable masked points, so the logits agree to summation-order rounding - and the
-    kNN-kernel path of the same entry point (tuning key 5 = 14) does too.  Nothing / few / many / everything masked, two
+    kNN-kernel path of the same entry point (the twin "pc_knn") does too.  Nothing / few / many / everything masked, two
     source clouds (and [r4] eight - the poses of one sweep launch, each with its own pair table); 40 / 72 coalitions so that the
     lists are used (clouds * 8 <= coalitions)."""
-    from interpret_quality_amd import _lib
-    lib = _lib.load()
     d = dev()
     rng = np.random.default_rng(8)
     clouds = torch.stack([torch.from_numpy(synth.make_cloud(i)[0]) for i in range(nclouds)]).to(d)
@@ -97,26 +95,17 @@ def test_coalitions_from_source_lists_equal_the_forward_on_masked_clouds(model, 
              for k, c in zip(keep, cloud_of)]
     want = model.forward_points(torch.stack(dense))
     assert rel_err(got.cpu().numpy(), want.cpu().numpy()) < 2e-5
-    lib.iq_set_tuning(5, 15)       # lists, but sa1's rows from the grouped MLP instead of the pair table
-    try:
+    with tuning.twin("pc_grouped_mlp"):     # lists, but sa1's rows from the grouped MLP instead of the pair table
         grouped = model.coalition_logits(clouds, centers, rid.to(d), keep_t, co_t, num_regions=32)
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert rel_err(got.cpu().numpy(), grouped.cpu().numpy()) < 2e-5 and rel_err(grouped.cpu().numpy(), want.cpu().numpy()) < 2e-5
-    lib.iq_set_tuning(5, 14)
-    try:
+    with tuning.twin("pc_knn"):
         knn = model.coalition_logits(clouds, centers, rid.to(d), keep_t, co_t, num_regions=32)
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert torch.equal(knn, want)      # the same kernels on the same masked clouds
     # [r4] sa1's contraction and its 2048 -> 128 layer in one kernel (pc_tab_fused_kernel, the default) against the two-kernel
-    # form that writes the (B, 512, 2048) contractions (5 = 31): same table rows, same weights, the sum over a group's 32
+    # form that writes the (B, 512, 2048) contractions (the twin): same table rows, same weights, the sum over a group's 32
     # members in 4-member MFMA steps instead of sequentially
-    lib.iq_set_tuning(5, 31)
-    try:
+    with tuning.twin("pc_two_kernel"):
         two = model.coalition_logits(clouds, centers, rid.to(d), keep_t, co_t, num_regions=32)
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert rel_err(got.cpu().numpy(), two.cpu().numpy()) < 2e-6 and not torch.equal(two, want)
     # a coalition's logits do not depend on what else is in the launch (the fused kernel's tiles are per coalition)
     solo = model.coalition_logits(clouds, centers, rid.to(d), keep_t[5:6].contiguous(), co_t[5:6].contiguous(), num_regions=32)
@@ -170,9 +159,8 @@ def test_per_cloud_tables_are_kept_across_launches_and_never_go_stale(model):
 
 def test_sa2_on_the_bf16_matrix_pipe_equals_the_fp32_mfma_kernel_to_rounding(model):
     """sa2's grouped MLP (128 -> 128 -> 256) runs as six bf16 products per float32 product with float32 accumulation
-    (pc_group_bf3_kernel); tuning key 5 = 56 selects the fp32-MFMA kernel.  Same logits to float32 rounding, on dense clouds and
-    on coalitions."""
-    from interpret_quality_amd import _lib
+    (pc_group_bf3_kernel); the twin "group_fp32" selects the fp32-MFMA kernel.  Same logits to float32 rounding, on dense clouds
+    and on coalitions."""
     d = dev()
     rng = np.random.default_rng(23)
     clouds = torch.stack([torch.from_numpy(synth.make_cloud(i)[0]) for i in (2, 7)]).to(d)
@@ -183,13 +171,9 @@ def test_sa2_on_the_bf16_matrix_pipe_equals_the_fp32_mfma_kernel_to_rounding(mod
     co_t = torch.tensor([i % 2 for i in range(len(keep))], dtype=torch.int32, device=d)
     got = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32)
     dense = model.forward_points(clouds)
-    lib = _lib.load()
-    lib.iq_set_tuning(5, 56)
-    try:
+    with tuning.twin("group_fp32"):
         ref = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32)
         dense_ref = model.forward_points(clouds)
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert not torch.equal(got, ref)                                      # a different kernel did run
     for a, b in ((got, ref), (dense, dense_ref)):
         assert (a - b).abs().max().item() < 3e-6 * b.abs().max().item()

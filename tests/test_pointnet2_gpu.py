@@ -8,7 +8,7 @@ import torch
 
 from conftest import assert_close_elementwise, load_golden
 from probes import ball_mismatch
-from interpret_quality_amd import final_common, hip_ops, synth
+from interpret_quality_amd import final_common, hip_ops, synth, tuning
 from interpret_quality_amd.pointnet2 import PointNet2ClsMsg
 
 pytestmark = pytest.mark.gpu
@@ -131,9 +131,8 @@ def test_coalitions_with_pair_tables_equal_the_forward_on_masked_clouds(model):
 
 def test_region_reduced_tables_equal_the_member_walk(model):
     """sa1 from the region-reduced pair tables (csrc/iq_pointnet2.hip: pt_regtab_kernel - one row per kept region that reaches
-    into a ball) against the member walk over the pair rows (tuning key 5 = 21): bit-identical logits on 400 random coalitions
+    into a ball) against the member walk over the pair rows (twin "pn2_member_walk"): bit-identical logits on 400 random coalitions
     of two source clouds, among them the empty, the full and single-region ones."""
-    from interpret_quality_amd import _lib
     d = dev()
     rng = np.random.default_rng(11)
     clouds = torch.stack([torch.from_numpy(synth.make_cloud(i)[0]) for i in (2, 6)]).to(d)
@@ -143,21 +142,16 @@ def test_region_reduced_tables_equal_the_member_walk(model):
     keep_t = hip_ops.masks_to_tensor(keep, d)
     co_t = torch.tensor([i % 2 for i in range(len(keep))], dtype=torch.int32, device=d)
     got = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32)
-    lib = _lib.load()
-    lib.iq_set_tuning(5, 21)
-    try:
+    with tuning.twin("pn2_member_walk"):
         walk = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32)
-    finally:
-        lib.iq_set_tuning(5, 0)
     assert torch.equal(got, walk)
 
 
 def test_sa2_on_the_bf16_matrix_pipe_equals_the_fp32_mfma_kernel_to_rounding(model):
     """The 128-128-256 scales of sa2 run their grouped MLP as six bf16 products per float32 product, float32 accumulation
-    (pn2_group_bf3_kernel, 64-row chunks); tuning key 5 = 56 / 64 selects the fp32-MFMA kernel (32- / 64-row chunks), which
-    gives the same bits for either chunk size.  Same logits to float32 rounding (the two sum k in different orders), on dense
-    clouds and on coalitions with few and many kept points."""
-    from interpret_quality_amd import _lib
+    (pn2_group_bf3_kernel, 64-row chunks); the twins "group_fp32" / "group_fp32_chunk64" select the fp32-MFMA kernel (32- /
+    64-row chunks), which gives the same bits for either chunk size.  Same logits to float32 rounding (the two sum k in different
+    orders), on dense clouds and on coalitions with few and many kept points."""
     d = dev()
     rng = np.random.default_rng(17)
     clouds = torch.stack([torch.from_numpy(synth.make_cloud(i)[0]) for i in (1, 5)]).to(d)
@@ -168,15 +162,12 @@ def test_sa2_on_the_bf16_matrix_pipe_equals_the_fp32_mfma_kernel_to_rounding(mod
     co_t = torch.tensor([i % 2 for i in range(len(keep))], dtype=torch.int32, device=d)
     got = model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32)
     dense = model.forward_points(clouds)
-    lib = _lib.load()
     ref = {}
-    try:
-        for knob in (56, 64):
-            lib.iq_set_tuning(5, knob)
-            ref[knob] = (model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32), model.forward_points(clouds))
-    finally:
-        lib.iq_set_tuning(5, 0)
-    assert torch.equal(ref[56][0], ref[64][0]) and torch.equal(ref[56][1], ref[64][1])
-    assert not torch.equal(got, ref[56][0])                               # a different kernel did run
-    for a, b in ((got, ref[56][0]), (dense, ref[56][1])):
+    for name in ("group_fp32", "group_fp32_chunk64"):
+        with tuning.twin(name):
+            ref[name] = (model.coalition_logits(clouds, centers, rid, keep_t, co_t, num_regions=32), model.forward_points(clouds))
+    ref, ref64 = ref["group_fp32"], ref["group_fp32_chunk64"]
+    assert torch.equal(ref[0], ref64[0]) and torch.equal(ref[1], ref64[1])
+    assert not torch.equal(got, ref[0])                                   # a different kernel did run
+    for a, b in ((got, ref[0]), (dense, ref[1])):
         assert (a - b).abs().max().item() < 3e-6 * b.abs().max().item()

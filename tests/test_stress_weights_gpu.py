@@ -10,10 +10,10 @@
     bit-for-bit relations of tests/test_chain_chunk96_gpu.py are repeated under every variant.
 (b) Rescaling invariance, bit for bit, all five families: internal channels scaled by 2^k (|k| <= 12 and <= 6) and compensated in
     the next layer give the same logits (PointNet: feature transforms and arg-max rows too) as the base weights, on the product
-    kernels and on their twins (tuning key 5 = 54 / 58; 56 / 64 for PointNet++ and PointConv).  tests/test_weight_variants_cpu.py
+    kernels and on their twins (TWINS below: tuning key 5 = 54 / 58; 56 / 64 for PointNet++ and PointConv).  tests/test_weight_variants_cpu.py
     shows the same on the CPU oracle, and that a compensation left out breaks it.
 (c) PointNet++, PointConv, GCNN and DGCNN with dead channels and the negative shift: the bars of tests/test_fuzz_gpu.py against
-    the dense HIP forward and the float32 oracle; PointNet++'s member-walk twin (5 = 21) bit for bit.  These run the `>= +0`
+    the dense HIP forward and the float32 oracle; PointNet++'s member-walk twin ("pn2_member_walk") bit for bit.  These run the `>= +0`
     assumptions of the integer maxima of csrc/iq_pointnet2.hip on rows that are exactly 0 and on a bias of -0.0.
     (DGCNN's 1e-2 here stays; tests/test_dgcnn_f64_gpu.py holds the same weights to the float64 bar on clouds with decidable graphs.)
 
@@ -27,7 +27,9 @@ import torch
 import probes
 import weight_variants as V
 from conftest import assert_close_elementwise
-from interpret_quality_amd import _lib, hip_ops, synth
+from interpret_quality_amd import hip_ops, synth
+from interpret_quality_amd.tuning import tuned
+from probes import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -38,15 +40,6 @@ SIZES = [1, 7, 24, 64, 104]
 
 def dev():
     return torch.device("cuda:0")
-
-
-def tuned(key, fn):
-    lib = _lib.load()
-    try:
-        lib.iq_set_tuning(5, key)
-        return fn()
-    finally:
-        lib.iq_set_tuning(5, 0)
 
 
 # ---- the PointNet inputs: built once ------------------------------------------------------------------------------------------
@@ -145,10 +138,6 @@ def pn_run(variant, which):
     return out
 
 
-def rel_err(x, ref64):
-    return float(np.abs(np.asarray(x, dtype=np.float64) - ref64).max() / np.abs(ref64).max())
-
-
 def assert_within_the_oracles_error(name, got, ref32, ref64):
     e_hip, e_ref = rel_err(got, ref64), rel_err(ref32, ref64)
     bar = min(4 * e_ref + 1e-7, 1e-4)
@@ -229,13 +218,13 @@ def test_the_arg_max_check_sees_a_row_dropped_from_the_pool():
 
 @pytest.mark.parametrize("variant", PN_VARIANTS)
 def test_pointnet_bit_for_bit_relations(variant):
-    """tests/test_chain_chunk96_gpu.py's: the product kernels against one n-tile per pass (5 = 58), against the dense forward on the
+    """tests/test_chain_chunk96_gpu.py's: the product kernels against one n-tile per pass ("chain_l3_single"), against the dense forward on the
     materialised clouds, and a coalition alone against the same coalition in the batch."""
     model, _ = probes.coalition_model("pointnet", dev(), variant)
     eng = model.engine()
     c, r = pn_small(), pn_run(variant, "small")
     run = lambda keep_t: eng.coalition_logits(c["data"], c["center"], c["rid"], keep_t, None, num_regions=c["nreg"], return_trans_feat=True)
-    one, tf_one = tuned(58, lambda: run(c["keep_t"]))
+    one, tf_one = tuned("chain_l3_single", lambda: run(c["keep_t"]))
     assert torch.equal(one, r["logits_t"]) and torch.equal(tf_one, r["tfp_t"])
     assert torch.equal(r["dense_logits_t"], r["logits_t"])
     for i, k in enumerate(c["keep"]):
@@ -249,7 +238,8 @@ def test_pointnet_bit_for_bit_relations(variant):
 
 FAMILY_CASE = {"pointnet2": probes.CoalitionCase("pointnet2", 160, 8, 1, 12, 51), "pointconv": probes.CoalitionCase("pointconv", 100, 8, 1, 12, 52),
                "gcnn": probes.CoalitionCase("gcnn", 40, 8, 1, 12, 53), "dgcnn": probes.CoalitionCase("dgcnn", 40, 8, 1, 12, 54)}
-TWINS = {"pointnet": (0, 54, 58), "pointnet2": (0, 56, 64), "pointconv": (0, 56, 64), "gcnn": (0,), "dgcnn": (0,)}
+TWINS = {"pointnet": (None, "chain_l3_fp32", "chain_l3_single"), "pointnet2": (None, "group_fp32", "group_fp32_chunk64"),
+         "pointconv": (None, "group_fp32", "group_fp32_chunk64"), "gcnn": (None,), "dgcnn": (None,)}     # None: the product kernels
 
 
 def _pointnet_outputs(variant):
@@ -279,7 +269,7 @@ def test_rescaled_channels_give_the_same_bits(family):
             got = tuned(key, lambda: outputs(variant))
             assert len(got) == len(base)
             for i, (g, b) in enumerate(zip(got, base)):
-                assert torch.equal(g, b), "%s, tuning 5 = %d, output %d: max |diff| %.3g of %.3g" % (
+                assert torch.equal(g, b), "%s, twin %s, output %d: max |diff| %.3g of %.3g" % (
                     variant, key, i, (g.double() - b.double()).abs().max().item(), b.double().abs().max().item())
 
 
@@ -297,5 +287,5 @@ def test_grouped_families_with_dead_and_zero_channels(family, variant):
     if family != "dgcnn":
         assert_close_elementwise(got, want)
     if family == "pointnet2":                                   # the member-walk twin against the region tables
-        walk = tuned(21, lambda: probes.run_coalition_case(case, dev(), oracle_cap=0, variant=variant)[0])
+        walk = tuned("pn2_member_walk", lambda: probes.run_coalition_case(case, dev(), oracle_cap=0, variant=variant)[0])
         assert probes.bitwise_equal(walk, got)

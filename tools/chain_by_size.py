@@ -20,12 +20,12 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from interpret_quality_amd import _lib, hip_ops, synth  # noqa: E402
+from interpret_quality_amd import _lib, hip_ops, synth, tuning  # noqa: E402
 from interpret_quality_amd.pointnet import PointNetCls  # noqa: E402
 
 KS = (0, 1, 2, 3, 5, 8, 12, 16, 24, 32)
-LPT_TWIN = 60            # the patched library: plain LPT
-NO_DEDUP_TWIN = 60       # the product library: every repeated set computed
+NO_DEDUP_TWIN = "chain_no_dedup"      # 5 = 60, the product library: every repeated set computed
+LPT_TWIN = NO_DEDUP_TWIN              # the patched library gives the same value another meaning: plain LPT
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=8192)
@@ -36,7 +36,7 @@ args = ap.parse_args()
 
 lib = _lib.load()
 PATCHED = hasattr(lib, "iq_debug_chain_order")      # the host twin only the experiment patch exports
-BASE = 0 if PATCHED else NO_DEDUP_TWIN
+BASE = None if PATCHED else NO_DEDUP_TWIN
 dev = torch.device("cuda:0")
 model = PointNetCls(None)
 model.load_state_dict(synth.to_torch(synth.pointnet_state_dict(0)))
@@ -88,8 +88,7 @@ def launch_us(masks, twin=BASE):
     """us per chain launch (mean of the feature-STN and the trunk launch), one figure per repeat after one untimed call."""
     keep = hip_ops.masks_to_tensor(masks, dev)
     out = []
-    _lib.check(lib.iq_set_tuning(5, twin), "iq_set_tuning")
-    try:
+    with tuning.twin(twin):
         for rep in range(args.repeats + 1):
             lib.iq_profile_enable(1)
             model.coalition_logits(data, center, region_id, keep, None, num_regions=R, validate=False)
@@ -99,8 +98,6 @@ def launch_us(masks, twin=BASE):
             read(0), read(3)
             if rep:
                 out.append(0.5 * (f + t))
-    finally:
-        lib.iq_set_tuning(5, 0)
     return np.array(out)
 
 
@@ -135,9 +132,9 @@ if not PATCHED:      # the product library: no mixed order
     say("plain LPT (the library's order)   %s" % fmt(launch_us(masks)))
     say("# mixed order: not in this library (tools/experiments/chain_mixed_order.patch)")
     finish()
-lpt, mixed = launch_us(masks, LPT_TWIN), launch_us(masks, 0)
+lpt, mixed = launch_us(masks, LPT_TWIN), launch_us(masks, None)
 lpt2 = launch_us(masks, LPT_TWIN)
-say("plain LPT (key 5 = %d)   %s" % (LPT_TWIN, fmt(lpt)))
+say("plain LPT (key 5 = %d)   %s" % (tuning.TWINS[LPT_TWIN], fmt(lpt)))
 say("mixed order (default)   %s" % fmt(mixed))
 say("plain LPT once more     %s" % fmt(lpt2))
 d = np.median(np.concatenate([lpt, lpt2])) - np.median(mixed)

@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from interpret_quality_amd import _lib, hip_ops, synth
+from interpret_quality_amd import hip_ops, synth, tuning
 
 LOADS = ("pointnet", "pointnet_fp32_l3", "dgcnn", "linear", "matmul", "bf16mm", "copy", "idle")
 
@@ -36,9 +36,8 @@ def load(kind, seconds):
         torch.zeros(1, device=dev)
         time.sleep(seconds)
         return
+    twin = "chain_l3_fp32" if kind == "pointnet_fp32_l3" else None      # layer 3 of the chains on the fp32 MFMA
     if kind in ("pointnet", "pointnet_fp32_l3"):
-        if kind == "pointnet_fp32_l3":
-            _lib.load().iq_set_tuning(5, 54)       # layer 3 of the chains on the fp32 MFMA
         from interpret_quality_amd.pointnet import PointNetCls
         m = PointNetCls(None)
         m.load_state_dict(synth.to_torch(synth.pointnet_state_dict(0)))
@@ -72,10 +71,11 @@ def load(kind, seconds):
     else:
         raise SystemExit("unknown load %r" % kind)
     t0 = time.time()
-    while time.time() - t0 < seconds:
-        for _ in range(4):
-            step()
-        torch.cuda.synchronize()
+    with tuning.twin(twin):
+        while time.time() - t0 < seconds:
+            for _ in range(4):
+                step()
+            torch.cuda.synchronize()
 
 
 def check(seconds, show=4):
