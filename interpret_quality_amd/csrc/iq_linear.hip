@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "iq_common.h"
+#include "iq_linear_plan.h"
 #include "iq_mfma.h"
 #include "iq_twin.h"
 
@@ -590,66 +591,66 @@ int cu_count() {
     return n;
 }
 
-// one grid of pn_gemm_bf3_kernel<false> (MT = 4) or pn_gemm_bf3_short_kernel with MT m-tiles per workgroup over rows [0, M) and the first gy column blocks of 256
-// m_base: where A and out start inside the matrix that m_dev counts the live rows of
-template <int MT>
-int launch_bf3_rows(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
-                     const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, int m_base = 0) {
-    const int Kp = (L.cin + 31) & ~31;     // the bf16x3 image's k range (iq_pack_weight_bf3 pads with zero columns)
-    const int gx = (M + 32 * MT - 1) / (32 * MT);
-    const dim3 grid((unsigned)((gx + 7) / 8 * 8 * gy));
-    const unsigned short* w3 = reinterpret_cast<const unsigned short*>(L.w_bf3);
-    const bool ragged = Kp != L.cin;
-    auto launch = [&](auto kernel) {
-        return iq::launch(MT == 4 ? "pn_gemm_bf3_kernel" : "pn_gemm_bf3_short_kernel", kernel, grid, dim3(kThreads), 0, st, A, lda, w3,
-                          L.b, out, ldo, M, Kp, L.cout, relu, m_dev, nullptr, gy, tile_nu, rows_per_cloud, L.cin, 0, m_base);
-    };
-    if constexpr (MT == 4) {
-        if (ragged) return launch(pn_gemm_bf3_kernel<false, 4, true>);
-        else return launch(pn_gemm_bf3_kernel<false>);
-    } else {
-        if (ragged) return launch(pn_gemm_bf3_short_kernel<MT, true>);
-        else return launch(pn_gemm_bf3_short_kernel<MT, false>);
+// The pointers of a dense-layer launch: what the segments of a plan (iq_linear_plan.h) are executed on.
+struct LinearOperands {
+    const float* A; int lda;
+    const iq_dense_layer& L;
+    const void* w_bf3;              // the bf16x3 image (the layer's, or launch_linear_pool's argument)
+    float* out; int ldo; int relu;
+    hipStream_t st;
+    const int32_t* m_dev;
+    const int32_t* tile_nu; int rows_per_cloud;
+    const float* row_w;             // the pool kernels' row weights
+};
+
+// One segment = one launch: the only place where a dense-layer kernel is named.
+int run_segment(const iq::LinearSegment& s, const LinearOperands& o) {
+    const iq_dense_layer& L = o.L;
+    const dim3 grid(s.gx, s.gy, s.gz), block(kThreads);
+    const float* A = o.A + (size_t)s.row0 * o.lda;
+    float* out = o.out + (size_t)s.row0 * o.ldo + s.col0;
+    const int32_t* tile_nu = s.tile_nu ? o.tile_nu : nullptr;
+    // the bf16x3 kernels walk the first col_blocks column blocks of the whole layer's image (col0 = 0); s.row0 is their m_base,
+    // the rows of *m_dev in front of this grid's row 0
+    const unsigned short* w3 = reinterpret_cast<const unsigned short*>(o.w_bf3);
+#define IQ_BF3_ARGS                                                                                                                \
+    grid, block, 0, o.st, A, o.lda, w3, L.b, out, o.ldo, s.rows, s.Kp, L.cout, o.relu, o.m_dev, o.row_w, s.col_blocks, tile_nu,     \
+        o.rows_per_cloud, s.Kreal, s.chunks_per_split, s.row0
+    // the fp32 kernels take columns [col0, col0 + cols) as a layer of their own: n-tiles col0 / 32 ... of the float32 image
+    // (n-tile-major, cin / 8 fragments each)
+    const float* w = L.w + (size_t)(s.col0 / 32) * (L.cin / 8) * (kFragBytes / 4);
+    const float* b = L.b + s.col0;
+#define IQ_LDS_ARGS \
+    grid, block, 0, o.st, A, o.lda, w, b, out, o.ldo, s.rows, L.cin, s.cols, o.relu, o.m_dev, o.row_w, tile_nu, o.rows_per_cloud, s.col_blocks
+#define IQ_DIRECT_ARGS grid, block, 0, o.st, A, o.lda, w, b, out, o.ldo, s.rows, L.cin, s.cols, o.relu, o.m_dev, s.kbs
+    switch (s.kernel) {
+        case iq::kLinBf3Rows128Ragged: IQ_TRY(iq::launch("pn_gemm_bf3_kernel", pn_gemm_bf3_kernel<false, 4, true>, IQ_BF3_ARGS)); break;
+        case iq::kLinBf3Rows128: IQ_TRY(iq::launch("pn_gemm_bf3_kernel", pn_gemm_bf3_kernel<false>, IQ_BF3_ARGS)); break;
+        case iq::kLinBf3Rows32Ragged: IQ_TRY(iq::launch("pn_gemm_bf3_short_kernel", pn_gemm_bf3_short_kernel<1, true>, IQ_BF3_ARGS)); break;
+        case iq::kLinBf3Rows32: IQ_TRY(iq::launch("pn_gemm_bf3_short_kernel", pn_gemm_bf3_short_kernel<1, false>, IQ_BF3_ARGS)); break;
+        case iq::kLinBf3Rows64Ragged: IQ_TRY(iq::launch("pn_gemm_bf3_short_kernel", pn_gemm_bf3_short_kernel<2, true>, IQ_BF3_ARGS)); break;
+        case iq::kLinBf3Rows64: IQ_TRY(iq::launch("pn_gemm_bf3_short_kernel", pn_gemm_bf3_short_kernel<2, false>, IQ_BF3_ARGS)); break;
+        case iq::kLinLdsCols320: IQ_LAUNCH((pn_gemm_lds_kernel<5, false>), IQ_LDS_ARGS); break;
+        case iq::kLinLdsRows256Cols64: IQ_LAUNCH((pn_gemm_lds_kernel<2, false, 1>), IQ_LDS_ARGS); break;
+        case iq::kLinLdsRows256Cols128: IQ_LAUNCH((pn_gemm_lds_kernel<4, false, 1>), IQ_LDS_ARGS); break;
+        case iq::kLinLdsCols256: IQ_LAUNCH((pn_gemm_lds_kernel<4, false>), IQ_LDS_ARGS); break;
+        case iq::kLinLdsCols128: IQ_LAUNCH((pn_gemm_lds_kernel<2, false>), IQ_LDS_ARGS); break;
+        case iq::kLinDirectCols128: IQ_LAUNCH((pn_linear_kernel<2, 2, 2, 2>), IQ_DIRECT_ARGS); break;
+        case iq::kLinDirectRows256: IQ_LAUNCH((pn_linear_kernel<2, 1, 4, 1>), IQ_DIRECT_ARGS); break;
+        case iq::kLinSplitkBf3: IQ_LAUNCH((pn_gemm_bf3_kernel<false, 4, false, true>), IQ_BF3_ARGS); break;
+        case iq::kLinSplitkDirect: IQ_LAUNCH((pn_linear_kernel<2, 2, 2, 2>), IQ_DIRECT_ARGS); break;
+        case iq::kLinPoolBf3: IQ_LAUNCH(pn_gemm_bf3_kernel<true>, IQ_BF3_ARGS); break;
+        case iq::kLinPoolLds: IQ_LAUNCH((pn_gemm_lds_kernel<4, true>), IQ_LDS_ARGS); break;
+        case iq::kLinKernels: break;
     }
+#undef IQ_BF3_ARGS
+#undef IQ_LDS_ARGS
+#undef IQ_DIRECT_ARGS
+    return IQ_OK;
 }
 
-// The plain bf16x3 dense layer.  128-row workgroups sit two to a CU, in rounds of 2 x CUs; 64-row ones three, 32-row ones four to
-// a CU.  A grid of fewer than 2 x CUs workgroups leaves every SIMD a single wave, which does not feed the matrix pipe, and a grid a
-// few workgroups over a whole number of rounds pays nearly a round for them.  Measured at 33 000 rows on 256 CUs
-// (profiles/heads_profile.txt; 128-row tiles -> the choice below):
-//   * fewer than one round at 128 rows: 32-row tiles throughout           (512 -> 256: 258 workgroups, 80 -> 60 us; 64-row tiles 64)
-//   * fewer than two rounds: 64-row tiles throughout                      (1024 -> 512: 516 workgroups, 221 -> 188 us; 128-row
-//     tiles for the whole round and 32-row ones for the 232 rows left: 195; 32-row tiles throughout: 196)
-//   * from two rounds on: 128-row tiles, and where the last round is at most a quarter / a half full its rows go to a second grid
-//     of 32- / 64-row tiles behind the whole rounds                       (256 -> 4096: 8.06 rounds, 447 -> 445 us, nothing; 64-row
-//     tiles throughout 433, 32-row ones 509 - the short tiles' weight stream is 2 x / 4 x per row)
-//   * without fit_tiles (the other families' launches, not re-measured), with tile_nu and under twin kTwinDenseTile128: 128-row
-//     tiles only, the former launch.
-// Which tile a row falls in changes nothing in its result (gemm_bf3_tile: MT), so the result stays independent of M.
-// With a live row count that only the device knows (m_dev <= M) the scheme is chosen from M, the host's bound, and every grid
-// clamps its rows to *m_dev: workgroups past it leave, the heights stay those measured for M rows.
-int launch_bf3(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu, hipStream_t st,
-               const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, int gy, bool fit_tiles) {
-    if (!fit_tiles || tile_nu || iq::twin() == iq::kTwinDenseTile128) {
-        return launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy);
-    }
-    const int cus = cu_count();
-    if (cus <= 0) return iq::fail(IQ_ELAUNCH, "dense layer: cannot read the device's multiprocessor count");
-    const long long round = 2LL * cus, tiles = (M + 127) / 128, wgs = tiles * gy;
-    const int m_full = (int)(wgs / round * round / gy) * 128;     // rows of the whole rounds
-    if (wgs < round) {
-        IQ_TRY(launch_bf3_rows<1>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy));
-    } else if (wgs < 2 * round) {
-        IQ_TRY(launch_bf3_rows<2>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy));
-    } else if (wgs % round == 0 || wgs % round > round / 2 || m_full <= 0 || m_full >= M) {
-        IQ_TRY(launch_bf3_rows<4>(A, lda, L, out, ldo, M, relu, st, m_dev, nullptr, 0, gy));
-    } else {
-        IQ_TRY(launch_bf3_rows<4>(A, lda, L, out, ldo, m_full, relu, st, m_dev, nullptr, 0, gy));
-        const float* At = A + (size_t)m_full * lda;
-        float* ot = out + (size_t)m_full * ldo;
-        if (wgs % round <= round / 4) IQ_TRY(launch_bf3_rows<1>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full));
-        else IQ_TRY(launch_bf3_rows<2>(At, lda, L, ot, ldo, M - m_full, relu, st, m_dev, nullptr, 0, gy, m_full));
-    }
+int run_plan(const iq::LinearPlan& plan, const LinearOperands& o) {
+    for (int i = 0; i < plan.n; ++i) IQ_TRY(run_segment(plan.seg[i], o));
     return IQ_OK;
 }
 
@@ -659,64 +660,10 @@ int iq::launch_linear(const float* A, int lda, const iq_dense_layer& L, float* o
                       hipStream_t st, const int32_t* m_dev, const int32_t* tile_nu, int rows_per_cloud, bool fit_tiles) {
     if (M == 0) return IQ_OK;
     IQ_REQUIRE(L.w && L.b && L.cin % 8 == 0 && L.cout >= 1, "dense layer: bad descriptor (cin=%d cout=%d)", L.cin, L.cout);
-    const int ntiles = (L.cout + 31) / 32;
-    if (tile_nu && (rows_per_cloud <= 0 || rows_per_cloud % 128 != 0)) tile_nu = nullptr;   // tiles must not straddle clouds
-    // bf16x3 on the bf16 matrix pipe, float32-exact - for EVERY M, so that a row's result does not depend on the launch it is in
-    // (twin kTwinDenseFp32: fp32 MFMA, A/B and tests)
-    // (column blocks of 256: 320 outputs would leave the second block a quarter full, and lose to the NT = 5 fp32 tiling - so the
-    // whole blocks of such a layer go to the bf16 pipe and its last 64 columns to the fp32 MFMA as a layer of their own; which
-    // columns take which arithmetic depends on the layer only, never on M)
-    const bool fp32 = iq::twin() == iq::kTwinDenseFp32;
-    if (L.w_bf3 && L.cout > 256 && L.cout % 256 == 64 && L.cin >= 32 && !fp32) {
-        const int gy = L.cout / 256;
-        IQ_TRY(launch_bf3(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, gy, fit_tiles));
-        iq_dense_layer rest = L;                       // n-tiles 8 gy, 8 gy + 1 of the fp32 image (n-tile-major, cin / 8 fragments each)
-        rest.w = L.w + (size_t)(8 * gy) * (L.cin / 8) * (kFragBytes / 4);
-        rest.b = L.b + 256 * gy;
-        rest.cout = 64;
-        rest.w_bf3 = nullptr;
-        return launch_linear(A, lda, rest, out + 256 * gy, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, fit_tiles);
-    }
-    if (L.w_bf3 && L.cout % 256 == 0 && L.cin >= 32 && !fp32)
-        return launch_bf3(A, lda, L, out, ldo, M, relu, st, m_dev, tile_nu, rows_per_cloud, L.cout / 256, fit_tiles);
-    if (M >= 2048 && (ntiles >= 4 || (ntiles == 2 && (M + 255) / 256 >= 2048)) && L.cin % 32 == 0 && !iq::no_lds_gemm()) {
-        if (ntiles % 10 == 0 && (long long)((M + 127) / 128) * (ntiles / 10) >= 2048) {
-            // 320 / 640 ... outputs: column blocks of exactly 10 tiles (NT = 5), nothing padded
-            dim3 grid((M + 127) / 128, ntiles / 10);
-            IQ_LAUNCH((pn_gemm_lds_kernel<5, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                      L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, 0);
-        } else if (ntiles == 2 && (M + 255) / 256 >= 2048) {
-            // 64 outputs (the fp32 rest of a 320-output layer): 256-row tiles, every wave both column tiles
-            dim3 grid((M + 255) / 256, 1);
-            IQ_LAUNCH((pn_gemm_lds_kernel<2, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                      L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
-        } else if (ntiles == 4 && (M + 255) / 256 >= 2048) {
-            // 128 outputs: 256-row workgroup tiles, every wave all four column tiles
-            dim3 grid((M + 255) / 256, 1);
-            IQ_LAUNCH((pn_gemm_lds_kernel<4, false, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                      L.cout, relu, m_dev, nullptr, rows_per_cloud % 256 == 0 ? tile_nu : nullptr, rows_per_cloud, 0);
-        } else if (ntiles >= 8 && (long long)((M + 127) / 128) * ((ntiles + 7) / 8) >= 2048) {
-            const int gx = (M + 127) / 128, gy = (ntiles + 7) / 8;
-            const bool flat = gy > 1;       // column blocks of a row tile side by side on one XCD (see the kernel)
-            IQ_LAUNCH((pn_gemm_lds_kernel<4, false>), flat ? dim3((unsigned)((gx + 7) / 8 * 8 * gy)) : dim3(gx, gy), dim3(kThreads), 0,
-                      st, A, lda, L.w, L.b, out, ldo, M, L.cin, L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, flat ? gy : 0);
-        } else {
-            dim3 grid((M + 127) / 128, (ntiles + 3) / 4);
-            IQ_LAUNCH((pn_gemm_lds_kernel<2, false>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M, L.cin,
-                      L.cout, relu, m_dev, nullptr, tile_nu, rows_per_cloud, 0);
-        }
-        return IQ_OK;
-    }
-    if (ntiles >= 4) {
-        dim3 grid((M + 127) / 128, (ntiles + 3) / 4);
-        IQ_LAUNCH((pn_linear_kernel<2, 2, 2, 2>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M,
-                  L.cin, L.cout, relu, m_dev, 0);
-    } else {
-        dim3 grid((M + 255) / 256, ntiles);
-        IQ_LAUNCH((pn_linear_kernel<2, 1, 4, 1>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, out, ldo, M,
-                  L.cin, L.cout, relu, m_dev, 0);
-    }
-    return IQ_OK;
+    iq::LinearQuery q{M, L.cin, L.cout, rows_per_cloud, iq::twin(), 0, L.w_bf3 != nullptr, tile_nu != nullptr, fit_tiles, iq::no_lds_gemm()};
+    if (iq::linear_plan_reads_cus(q) && (q.cus = cu_count()) <= 0)
+        return iq::fail(IQ_ELAUNCH, "dense layer: cannot read the device's multiprocessor count");
+    return run_plan(iq::plan_linear(q), {A, lda, L, L.w_bf3, out, ldo, relu, st, m_dev, tile_nu, rows_per_cloud, nullptr});
 }
 
 namespace {
@@ -736,37 +683,20 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, const fl
 }  // namespace
 
 // Few rows, very long K (PointConv's 16384 -> 1024 layer on B rows): a plain launch has ceil(M/128) x cout/128 workgroups -
-// 48 for 660 rows - each walking all of K.  Split K over blockIdx.z until the grid fills the chip; partial sums go
+// 48 for 660 rows - each walking all of K.  Split K over the grid until it fills the chip; partial sums go
 // through `scratch` (splits x M x cout floats) and are added in a fixed order.
 int iq::launch_linear_splitk(const float* A, int lda, const iq_dense_layer& L, float* out, int ldo, int M, int relu,
                              float* scratch, size_t scratch_floats, hipStream_t st) {
     if (M == 0) return IQ_OK;
     IQ_REQUIRE(L.w && L.b && L.cin % 8 == 0 && L.cout >= 1, "dense layer: bad descriptor (cin=%d cout=%d)", L.cin, L.cout);
-    const int ntiles = (L.cout + 31) / 32, KB = L.cin / 8;
-    // 512 k per split, whatever M is: the summation order must not depend on how many rows share the launch, or a
-    // coalition's logits would change with the batch it travels in (found by the two-rank artefact comparison)
-    const int kbs = 64;
-    const int splits = (KB + kbs - 1) / kbs;
-    if (splits <= 1 || ntiles < 4) return launch_linear(A, lda, L, out, ldo, M, relu, st);
-    if (L.w_bf3 && L.cout % 256 == 0 && L.cin % 32 == 0 && iq::twin() != iq::kTwinDenseFp32) {
-        // the same 512-k splits on the bf16 matrix pipe (three-term products): 16 chunks of 32 k per workgroup row
-        IQ_REQUIRE(scratch && (size_t)splits * M * L.cout <= scratch_floats, "split-K dense layer: scratch %zu floats < %zu",
-                   scratch_floats, (size_t)splits * M * L.cout);
-        const int gx = (M + 127) / 128, gy = L.cout / 256;
-        IQ_LAUNCH((pn_gemm_bf3_kernel<false, 4, false, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy), (unsigned)splits), dim3(kThreads), 0,
-                  st, A, lda, reinterpret_cast<const unsigned short*>(L.w_bf3), L.b, scratch, L.cout, M, L.cin, L.cout, 0, nullptr, nullptr,
-                  gy, nullptr, 0, L.cin, kbs * 8 / 32, 0);
-        IQ_LAUNCH(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
-                  out, ldo, M, L.cout, splits, relu);
-        return IQ_OK;
-    }
-    IQ_REQUIRE(scratch && (size_t)splits * M * L.cout <= scratch_floats, "split-K dense layer: scratch %zu floats < %zu",
-               scratch_floats, (size_t)splits * M * L.cout);
-    dim3 grid((M + 127) / 128, (ntiles + 3) / 4, splits);
-    IQ_LAUNCH((pn_linear_kernel<2, 2, 2, 2>), grid, dim3(kThreads), 0, st, A, lda, L.w, L.b, scratch, L.cout, M, L.cin,
-              L.cout, 0, nullptr, kbs);
+    const iq::LinearPlan plan =
+        iq::plan_linear_splitk({M, L.cin, L.cout, 0, iq::twin(), 0, L.w_bf3 != nullptr, false, false, iq::no_lds_gemm()});
+    if (!plan.splits) return run_plan(plan, {A, lda, L, L.w_bf3, out, ldo, relu, st, nullptr, nullptr, 0, nullptr});
+    IQ_REQUIRE(scratch && (size_t)plan.splits * M * L.cout <= scratch_floats, "split-K dense layer: scratch %zu floats < %zu",
+               scratch_floats, (size_t)plan.splits * M * L.cout);
+    IQ_TRY(run_plan(plan, {A, lda, L, L.w_bf3, scratch, L.cout, 0, st, nullptr, nullptr, 0, nullptr}));   // raw partial sums
     IQ_LAUNCH(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * L.cout + 255) / 256)), dim3(256), 0, st, scratch, L.b,
-              out, ldo, M, L.cout, splits, relu);
+              out, ldo, M, L.cout, plan.splits, relu);
     return IQ_OK;
 }
 
@@ -774,19 +704,10 @@ int iq::launch_linear_pool(const float* A, int lda, const iq_dense_layer& L, flo
                            const float* row_w, hipStream_t st, const int32_t* m_dev, const void* w_bf3) {
     if (M == 0) return IQ_OK;
     IQ_REQUIRE(L.w && L.b && row_w && partial, "dense layer + pool: null pointer");
-    const int ntiles = (L.cout + 31) / 32;
-    if (L.cin % 32 != 0 || ntiles < 8 || L.cout % 32 != 0)
+    if (L.cin % 32 != 0 || (L.cout + 31) / 32 < 8 || L.cout % 32 != 0)
         return iq::fail(IQ_EUNSUPPORTED, "dense layer + pool: cin=%d cout=%d", L.cin, L.cout);
-    const int gy = (ntiles + 7) / 8, gx = (M + 127) / 128;
-    if (w_bf3 && L.cout % 256 == 0) {
-        IQ_LAUNCH(pn_gemm_bf3_kernel<true>, dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda,
-                  reinterpret_cast<const unsigned short*>(w_bf3), L.b, partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, gy,
-                  nullptr, 0, L.cin, 0, 0);
-        return IQ_OK;
-    }
-    IQ_LAUNCH((pn_gemm_lds_kernel<4, true>), dim3((unsigned)((gx + 7) / 8 * 8 * gy)), dim3(kThreads), 0, st, A, lda, L.w, L.b,
-              partial, 0, M, L.cin, L.cout, relu, m_dev, row_w, nullptr, 0, gy);
-    return IQ_OK;
+    const iq::LinearPlan plan = iq::plan_linear_pool({M, L.cin, L.cout, 0, 0, 0, w_bf3 != nullptr, false, false, false});
+    return run_plan(plan, {A, lda, L, w_bf3, partial, 0, relu, st, m_dev, nullptr, 0, row_w});
 }
 
 extern "C" int iq_linear(const float* A, int lda, const iq_dense_layer* L, float* out, int ldo, int M, int act,
