@@ -76,8 +76,10 @@ enum {
  * 119: one new diagnostic entry point, no layout change (iq_debug.h: iq_debug_pointnet_slots); the narrow PointNet workspace grew by
  * 12 bytes per coalition (iq_pointnet_workspace_bytes, iq_pointnet_wide_workspace_bytes: the slots of the distinct coalitions).
  * 120: new entry points, no layout change (all-pairs interactions from the regression rows: iq_kshap_pairs_scratch_bytes,
- * iq_kshap_pairs). */
-#define IQ_ABI_VERSION 120
+ * iq_kshap_pairs).
+ * 121: new entry points, no layout change (standard errors of the sampled estimates: iq_shapley_sq_accum_games,
+ * iq_kshap_pairs_se_scratch_bytes, iq_kshap_pairs_se, iq_kshap_moment_se_scratch_bytes_wide, iq_kshap_moment_se_wide). */
+#define IQ_ABI_VERSION 121
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -194,6 +196,15 @@ size_t iq_shapley_games_scratch_bytes(int R, int S, int G);
 int iq_shapley_accum_games(const float* v /*G rows of ldv*/, size_t ldv, const int32_t* orders /*S,R*/, double* phi_sum /*G,R*/,
                            const int32_t* snap_counts, int n_snap, double* snaps /*G,n_snap,R*/, int R, int S, int G,
                            void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* The second moment beside iq_shapley_accum_games, for the standard error of the permutation estimator: the same arguments,
+ * position table, scratch size and skip rules, with sq_sum[g][r] = sum over the permutations p, strictly in permutation order, of
+ * ((double)dv)^2, dv the float32 difference iq_shapley_accum_games adds for (g, p, r) - the square of a widened float32 is exact
+ * in float64 - and sq_snaps the running sums at snap_counts.  At a count n >= 2 the host forms
+ * se_r = sqrt(max(sq - sum^2 / n, 0) / (n (n - 1))) from the two sums. */
+int iq_shapley_sq_accum_games(const float* v /*G rows of ldv*/, size_t ldv, const int32_t* orders /*S,R*/, double* sq_sum /*G,R*/,
+                              const int32_t* snap_counts, int n_snap, double* sq_snaps /*G,n_snap,R*/, int R, int S, int G,
+                              void* scratch, size_t scratch_bytes, iq_stream_t stream);
 
 /* final_cal_interactions.py:28-36: I[k] = ((v[4k] + v[4k+3]) - v[4k+1]) - v[4k+2] in float32. */
 int iq_interaction_reduce(const float* v /*4n*/, float* out /*n*/, int n, iq_stream_t stream);
@@ -777,6 +788,61 @@ size_t iq_kshap_pairs_scratch_bytes(int M, int R, int G);
 int iq_kshap_pairs(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, const double* delta /*G*/,
                    const double* weights /*M or NULL*/, const double* coef /*R+1,3 device*/, int M, int R, int G,
                    double* out /*G,R,R*/, void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Standard errors of the sampled estimates (csrc/iq_kshap_pairs.hip, csrc/iq_kshap_wide.hip)
+ *
+ * For SAMPLED rows only (weights == NULL): enumerated or weighted rows have no sampling error.  A UNIT u is the iid draw:
+ * unpaired, row u (c = 1 row per unit); paired, rows 2u and 2u + 1, a set and its complement (c = 2, M even).  U units, M = c U
+ * rows, U >= 2.  For an estimate est = const + (1/M) sum_u y_u, with S1 = sum y_u and S2 = sum y_u^2,
+ *     var = (U / (U - 1)) (S2 - S1^2 / U) / M^2,      se = sqrt(max(var, 0)),
+ * is unbiased for the variance of est (the two rows of a paired unit are NOT independent: the unit, not the row, is squared).
+ * No further model evaluation: second moments of the same rows and rewards.
+ *
+ * Pairs.  mu as above, 0 where a case cannot occur (mu(s,0) at s = R-1, mu(s,2) at s = 1), evaluated in closed form from 2 H (two
+ * roundings an entry, not from the differences of `coef`).  For the pair {i,j}, k = the number of its members in the unit's first
+ * row, of size s: unpaired x_u(k) = d_u mu(s,k); paired x_u(k) = d_2u mu(s,k) + d_2u+1 mu(R-s, 2-k); d_m = (double)v_m - v0; a unit
+ * whose first row has size 0 or R has x = 0 and counts in U.  Any function of k in {0,1,2} is P + B k + G [k = 2]:
+ *     P_u = x_u(0)^2,   B_u = x_u(1)^2 - x_u(0)^2,   G_u = (x_u(2)^2 - 2 x_u(1)^2) + x_u(0)^2,
+ *     S2_ij = ((sum P + sum B z_i) + sum B z_j) + sum G z_i z_j          (z = the unit's first row),
+ * one scalar, one moment and one R x R x U product: the shape and the order of A, L and Q above on the units' first rows -
+ * pair_chunks_of(U, R) for the product on v_mfma_f64_16x16x4_f64, chunks_of(U) for the moment and the scalar.
+ * S1_ij = ((A + L_i) + L_j) + Q_ij of the estimate itself (= M (I_ij - delta / (R-1))).  Then, each operation rounded on its own,
+ * var = ((U / (U-1)) (S2 - S1 S1 / U)) / (M M) and se = sqrt(var), 0 where var < 0.  In float64 S2 stays within
+ * (U + 16) 2^-53 sum_u (|P_u| + 2 |B_u| + |G_u|) of its value for any summation order.
+ *
+ * phi under the analytic Gram matrix.  phi_i = delta / R + (1/M) sum_u y_ui, y_ui = 2 H D_u (z_ui - s_u / R), D_u = d_u
+ * (unpaired) or d_2u - d_2u+1 (paired), z and s of the unit's first row.  z^2 = z, so
+ *     S2_i = (2H 2H) (sum_u e_u z_ui + sum_u f_u),   e_u = D_u^2 (1 - 2 s_u / R),   f_u = D_u^2 (s_u^2 / R^2),
+ * a moment in iq_kshap_moment_wide's order on chunks_of(U) and a scalar (a chunk's sum as its sum of weights is taken), and
+ * S1_i = 2H (b_i - (b_0 + b_1 + ... in index order) / R) from the raw float64 b, not from phi's rounded bits.
+ * The sampled-Gram solve (iq_kshap_solve) has no standard error here.
+ *
+ * As above: no floating-point atomics, no grid chosen at run time, two calls give the same bits, a game's bits depend neither on G
+ * nor on a neighbouring game's rewards.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Scratch (bytes) of iq_kshap_pairs_se; 0 for arguments iq_kshap_pairs_scratch_bytes refuses, for fewer than 2 units and for
+ * paired != 0 with odd M. */
+size_t iq_kshap_pairs_se_scratch_bytes(int M, int R, int G, int paired);
+
+/* out: the bits of iq_kshap_pairs on the same arguments with weights == NULL (its kernels, unchanged).  se[g][i][j] = the standard
+ * error of out[g][i][j] as defined above, symmetric bit for bit, se[g][i][i] = 0.  IQ_EINVAL for fewer than 2 units, and for
+ * paired != 0 with odd M. */
+int iq_kshap_pairs_se(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, const double* delta /*G*/,
+                      const double* coef /*R+1,3 device*/, int M, int R, int G, int paired, double* out /*G,R,R*/,
+                      double* se /*G,R,R*/, void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* Scratch (bytes) of iq_kshap_moment_se_wide; 0 for arguments iq_kshap_scratch_bytes_wide refuses, for fewer than 2 units and for
+ * paired != 0 with odd M. */
+size_t iq_kshap_moment_se_scratch_bytes_wide(int M, int R, int G, int paired);
+
+/* b: the raw moment, the bits of iq_kshap_moment_wide with weights == NULL (wsum = M).  var[g][i] = the variance of phi_i of game g
+ * as defined above (it may be a rounding below 0; the caller takes sqrt(max(var, 0))).  Narrow rows are rows of W = 1 word.
+ * IQ_EINVAL for fewer than 2 units, and for paired != 0 with odd M. */
+int iq_kshap_moment_se_wide(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, int M, int R, int G,
+                            int paired, double* b /*G,R*/, double* var /*G,R*/, void* scratch, size_t scratch_bytes,
+                            iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

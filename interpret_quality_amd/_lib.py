@@ -94,6 +94,7 @@ SIGNATURES = {
     "iq_reward_classes": (_I, [_P, _P, _I, _I, _P, _SZ, _I, _I, _P]),
     "iq_shapley_games_scratch_bytes": (_SZ, [_I, _I, _I]),
     "iq_shapley_accum_games": (_I, [_P, _SZ, _P, _P, _P, _I, _P, _I, _I, _I, _P, _SZ, _P]),
+    "iq_shapley_sq_accum_games": (_I, [_P, _SZ, _P, _P, _P, _I, _P, _I, _I, _I, _P, _SZ, _P]),
     "iq_interaction_reduce": (_I, [_P, _P, _I, _P]),
     "iq_region_assign": (_I, [_P, _P, _P, _I, _I, _P]),
     "iq_fps": (_I, [_P, _P, _I, _I, _I, _P]),
@@ -152,6 +153,10 @@ SIGNATURES = {
     "iq_kshap_phi_analytic": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "iq_kshap_pairs_scratch_bytes": (_SZ, [_I, _I, _I]),
     "iq_kshap_pairs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "iq_kshap_pairs_se_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
+    "iq_kshap_pairs_se": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "iq_kshap_moment_se_scratch_bytes_wide": (_SZ, [_I, _I, _I, _I]),
+    "iq_kshap_moment_se_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "iq_kshap_draw_counter": (_I, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, _I, _I, _P, _I, _P, _P, _P]),
     "iq_prefix_keep_masks_wide": (_I, [_P, _P, _I, _I, _P]),
     "iq_context_keep_masks_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
@@ -183,7 +188,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 120  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 121  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

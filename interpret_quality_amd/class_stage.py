@@ -7,6 +7,8 @@ final_wide_shapley.py above - and reads each selected cloud's region_id.npy and,
 
     region_shapley_classes.npy   (G, R) float64   row g: the Shapley values of the game of label classes[g]
     efficiency.npy               (G,) float64     sum_r phi[g][r] - (v_full[g] - v_empty[g])
+    region_shapley_classes_se.npy (G, R) float64  with --se: the standard error of every entry of region_shapley_classes.npy, from
+                                 the second moment of the same coalitions' rewards; classes.json gains "se": true
     classes.json                 the labels, the ground-truth label, the argmax class of the full cloud, v_full and v_empty per
                                  class, the estimator and its parameters
 
@@ -14,7 +16,8 @@ final_wide_shapley.py above - and reads each selected cloud's region_id.npy and,
 region_shapley/<i>_<count>.npy at ``--num_samples`` = count, bit for bit, and nothing is drawn from NumPy's global generator.
 ``--estimator kernel`` is the regression estimator on ``--samples`` rows (``--draw stream``: NumPy's stream, which runs on from
 one selected cloud to the next; above 64 regions also ``--draw counter``, keyed by --seed and the cloud's index).  Above 64
-regions ``--route`` and ``--coalitions`` are wide.shapley's.  One rank: the stage is not sharded and refuses a larger world.
+regions ``--route`` and ``--coalitions`` are wide.shapley's.  ``--se`` with the kernel estimator follows final_kernel_shapley.py's
+rule: phi has a standard error under the analytic Gram matrix only, which this stage uses above 64 regions.  One rank: the stage is not sharded and refuses a larger world.
 """
 import json
 
@@ -59,17 +62,20 @@ def cloud_files(base, args):
 
 
 def class_one_cloud(model, data, region_id, orders, args, cloud=0):
-    """-> (phi (G,R) float64, v_full (G,), v_empty (G,), the full cloud's logits (C,)) of one cloud."""
+    """-> (phi (G,R) float64, v_full (G,), v_empty (G,), the full cloud's logits (C,)) of one cloud; with --se a fifth value,
+    the (G,R) standard error of phi."""
     wide_game = args.num_regions > classwise.NARROW_REGIONS
     route, coalitions = (args.route, args.coalitions) if wide_game else (None, None)
+    se = {"se": True} if kernel_stage.wants_se(args) else {}
     if args.estimator == "permutation":
-        _, total = classwise.shapley(model, data, region_id, orders, args, args.class_list, route=route, coalitions=coalitions)
+        _, total, *bars = classwise.shapley(model, data, region_id, orders, args, args.class_list, route=route, coalitions=coalitions, **se)
         phi = total / orders.shape[0]
     else:
-        phi, _, _ = classwise.kernel_shapley(model, data, region_id, args, args.class_list, args.samples, draw=args.draw if wide_game else "stream",
-                                             seed=args.seed, stream=cloud, coalitions=coalitions)
+        phi, _, _, *bars = classwise.kernel_shapley(model, data, region_id, args, args.class_list, args.samples,
+                                                    draw=args.draw if wide_game else "stream", seed=args.seed, stream=cloud,
+                                                    coalitions=coalitions, **se)
     v_full, v_empty, logits = classwise.ends(model, data, region_id, args, args.class_list, coalitions)
-    return phi, v_full, v_empty, logits
+    return (phi, v_full, v_empty, logits) + tuple(bars)
 
 
 def run(args):
@@ -81,12 +87,14 @@ def run(args):
                 continue
             base = args.exp_folder + "%s/" % names[i]
             region_id, orders = cloud_files(base, args)
-            phi, v_full, v_empty, logits = class_one_cloud(model, data.to(args.device), region_id, orders, args, i)
+            phi, v_full, v_empty, logits, *bars = class_one_cloud(model, data.to(args.device), region_id, orders, args, i)
             labels = list(range(logits.shape[0])) if args.class_list is None else args.class_list
             eff = phi.sum(axis=1) - (v_full - v_empty)
             mkdir(base + FOLDER)
             np.save(base + FOLDER + "region_shapley_classes.npy", phi)
             np.save(base + FOLDER + "efficiency.npy", eff)
+            if bars:
+                np.save(base + FOLDER + "region_shapley_classes_se.npy", bars[0])
             params = {"num_regions": int(args.num_regions), "softmax_type": args.softmax_type}
             if args.estimator == "permutation":
                 params.update(num_samples=int(orders.shape[0]), route=args.route, coalitions=args.coalitions)
@@ -95,7 +103,7 @@ def run(args):
             with open(base + FOLDER + "classes.json", "w") as f:
                 json.dump({"classes": [int(c) for c in labels], "label": int(lbl.reshape(-1)[0]), "predicted": int(np.argmax(logits)),
                            "v_full": [float(x) for x in v_full], "v_empty": [float(x) for x in v_empty],
-                           "estimator": args.estimator, "parameters": params}, f)
+                           "estimator": args.estimator, "parameters": params, **({"se": True} if bars else {})}, f)
             print("pointcloud:%s, index:%d, regions:%d, classes:%d, label:%d, predicted:%d, max |efficiency gap| %.3g"
                   % (names[i], i, args.num_regions, phi.shape[0], int(lbl.reshape(-1)[0]), int(np.argmax(logits)), np.abs(eff).max()))
 
@@ -111,6 +119,7 @@ def build_parser():
                         "evaluates the coalitions")
     parser.add_argument("--samples", type=int, default=None, help="kernel estimator: coalition rows per cloud; default 1000 (num_regions + 1)")
     parser.add_argument("--draw", choices=wide_kernelshap.DRAWS, default="stream", help="kernel estimator above 64 regions: how the rows are drawn")
+    kernel_stage.add_se_flag(parser)
     return parser
 
 
@@ -128,6 +137,13 @@ def make_args(argv=None):
     if args.num_samples < 1:
         parser.error("--num_samples %d: at least one permutation" % args.num_samples)
     kernel_stage.check_samples(parser, args)
+    if kernel_stage.wants_se(args):
+        if args.estimator == "permutation" and args.num_samples < 2:
+            parser.error("--se with --num_samples %d: a standard error needs at least 2 permutations" % args.num_samples)
+        if args.estimator == "kernel" and narrow:
+            parser.error("--se with --estimator kernel at %d regions: this stage solves with the sampled Gram matrix up to %d "
+                         "regions, and phi has a standard error under the analytic one only (final_kernel_shapley.py --gram "
+                         "analytic --se)" % (args.num_regions, classwise.NARROW_REGIONS))
     return args
 
 

@@ -64,33 +64,42 @@ def _orders(orders, r):
     return orders
 
 
-def _reduce(table, orders, snap_counts):
-    """One iq_shapley_accum_games over the (G, S*(R+1)) reward table -> (snaps {count: (G,R)}, total (G,R)), float64 ndarrays."""
+def _reduce(table, orders, snap_counts, se=False):
+    """One iq_shapley_accum_games over the (G, S*(R+1)) reward table -> (snaps {count: (G,R)}, total (G,R)), float64 ndarrays;
+    ``se``: also the (G,R) standard error of total / S, from one iq_shapley_sq_accum_games over the same table (S >= 2)."""
     counts = [int(c) for c in (snap_counts or []) if c <= orders.shape[0]]
+    if se and orders.shape[0] < 2:
+        raise IqError("a standard error needs at least 2 permutations, got %d" % orders.shape[0])
     total, snaps = hip_ops.shapley_accum_games(table, orders, counts)
     snaps = snaps.cpu().numpy() if snaps is not None else None
-    return {c: snaps[:, k] for k, c in enumerate(counts)}, total.cpu().numpy()
+    out = {c: snaps[:, k] for k, c in enumerate(counts)}, total.cpu().numpy()
+    if se:
+        out += (hip_ops.shapley_se(out[1], hip_ops.shapley_sq_accum_games(table, orders)[0], orders.shape[0]),)
+    return out
 
 
-def from_logits(logits, orders, args, classes=None, snap_counts=None):
+def from_logits(logits, orders, args, classes=None, snap_counts=None, se=False):
     """The permutation estimator on the logits (S*(R+1), C) of the prefix coalitions of ``orders`` ((S,R) ndarray), in the
     reference's row order (row o*(R+1)+i keeps orders[o][:i]) -> (running sums {count: (G,R)} at the ``snap_counts`` that do not
-    exceed S, total (G,R)), float64, not divided.  No model is run: fresh logits, or one pose's slice of a stored all_logits.pt."""
+    exceed S, total (G,R)), float64, not divided; ``se``: and the (G,R) standard error of total / S.  No model is run: fresh
+    logits, or one pose's slice of a stored all_logits.pt."""
     r = int(args.num_regions)
     orders = _orders(orders, r)
     if logits.dim() != 2 or logits.shape[0] != orders.shape[0] * (r + 1):
         raise IqError("logits must be (%d, C) for %d permutations of %d regions, got %s"
                       % (orders.shape[0] * (r + 1), orders.shape[0], r, tuple(logits.shape)))
-    return _reduce(rewards(logits, classes, args), orders, snap_counts)
+    return _reduce(rewards(logits, classes, args), orders, snap_counts, se)
 
 
-def shapley(model, data, region_id, orders, args, classes=None, snap_counts=None, route=None, coalitions=None):
+def shapley(model, data, region_id, orders, args, classes=None, snap_counts=None, route=None, coalitions=None, se=False):
     """The permutation estimator of one cloud ``data`` (1,N,3) for G labels on ONE evaluation of the prefix coalitions of
     ``orders`` ((S,R) ndarray) -> (running sums {count: (G,R)}, total (G,R)), float64, not divided: row g is the total (and the
     running sums) of shapley_stage.shapley_all_orders (up to 64 regions) or wide.shapley (above) with lbl = classes[g], bit for
     bit.  Up to 64 regions the logits are final_common.shapley_logits's; above, wide.shapley's checks, steps and routes run
     (``route``, ``coalitions``: as there; up to 64 regions they are not taken) and the (G, S*(R+1)) reward table is filled step
-    by step.  One iq_shapley_accum_games reduces it: no per-class row table."""
+    by step.  One iq_shapley_accum_games reduces it: no per-class row table.  ``se``: a third value, the (G,R) standard error of
+    total / S - the permutations are iid, so it is the column standard error of the per-permutation differences, from their sum of
+    squares (iq_shapley_sq_accum_games) and no further forward."""
     cls = _classes(classes)
     r = int(args.num_regions)
     if r <= NARROW_REGIONS:
@@ -100,7 +109,7 @@ def shapley(model, data, region_id, orders, args, classes=None, snap_counts=None
         with torch.no_grad():
             logits = final_common.shapley_logits(model, data, None, region_id, orders, args)
             table = final_common.get_reward_classes(logits, cls, args)
-        return _reduce(table, orders, snap_counts)
+        return _reduce(table, orders, snap_counts, se)
     route, mode, r, orders = wide._game(model, data, orders, args, route, coalitions)
     orders = _orders(orders, r)
     dev = data.device
@@ -111,7 +120,7 @@ def shapley(model, data, region_id, orders, args, classes=None, snap_counts=None
     sink = final_common.RewardSink(None, cls, args, orders.shape[0] * (r + 1), dev)
     with torch.no_grad():
         wide._rewards(model, data, rid, steps, keep, sink, r, mode)
-    return _reduce(sink.v, orders, snap_counts)
+    return _reduce(sink.v, orders, snap_counts, se)
 
 
 def ends(model, data, region_id, args, classes=None, coalitions=None):
@@ -132,12 +141,13 @@ def ends(model, data, region_id, args, classes=None, coalitions=None):
 
 
 def kernel_shapley(model, data, region_id, args, classes=None, samples=None, paired=True, gram=None, draw="stream", seed=0, stream=0,
-                   coalitions=None):
+                   coalitions=None, se=False):
     """The regression estimator of one cloud for G labels on ONE evaluation of the drawn rows -> (phi (G,R) float64, v_full (G,),
     v_empty (G,)).  The rows are drawn exactly as kernelshap.game (2 .. 64 regions; ``draw`` must be "stream", ``coalitions``
     None) or wide_kernelshap.game (65 .. 1024) draws them, the rewards of the G labels go into a (G,M) table and ``estimate``
     takes it whole: row g is ``kernelshap.shapley`` / ``wide_kernelshap.shapley`` with lbl = classes[g], bit for bit.  ``gram``:
-    None = "sampled" up to 64 regions, "analytic" above.  ``samples``: a count, None (default_samples) or "all"."""
+    None = "sampled" up to 64 regions, "analytic" above.  ``samples``: a count, None (default_samples) or "all".  ``se``: a
+    fourth value, the (G,R) standard error of phi (the analytic Gram matrix and drawn rows only: ``kernelshap.play``)."""
     cls = _classes(classes)
     narrow = int(args.num_regions) <= NARROW_REGIONS
     ks = kernelshap if narrow else wide_kernelshap
@@ -147,8 +157,8 @@ def kernel_shapley(model, data, region_id, args, classes=None, samples=None, pai
     if narrow and (draw != "stream" or coalitions is not None):
         raise IqError("draw=%r / coalitions=%r belong to games of more than %d regions" % (draw, coalitions, NARROW_REGIONS))
     how = {} if narrow else {"draw": wide_kernelshap.drawer(draw, seed, stream), "coalitions": coalitions}
-    g = kernelshap.play(ks, model, data, None, region_id, args, samples, paired, gram, (), classes=cls, **how)
-    return g["phi"], g["v_full"], g["v_empty"]
+    g = kernelshap.play(ks, model, data, None, region_id, args, samples, paired, gram, (), classes=cls, se=se, **how)
+    return (g["phi"], g["v_full"], g["v_empty"]) + ((g["phi_se"],) if se else ())
 
 
 def exact(model, data, region_id, args, classes=None, players=None, base=0):

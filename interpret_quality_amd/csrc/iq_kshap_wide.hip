@@ -114,6 +114,86 @@ __global__ __launch_bounds__(kThreads) void kshap_phi_analytic_kernel(const doub
     }
 }
 
+// ---- iq_kshap_moment_se_wide: the variance of phi under the analytic Gram matrix (include/iq.h, "Standard errors") -----------------
+// phi_i = delta / R + (1 / M) sum_u y_ui, y_ui = 2 H D_u (z_ui - s_u / R) over the iid units u (a row, or a row and its complement:
+// D_u = d_u or d_2u - d_2u+1; z, s of the unit's first row).  z^2 = z, so sum_u y_ui^2 = 4 H^2 (sum_u e_u z_ui + sum_u f_u) with
+// e_u = D_u^2 (1 - 2 s_u / R) and f_u = D_u^2 s_u^2 / R^2: a moment in moment_chunk_of's order with another per-row value, and a scalar.
+
+// One thread per unit: its size once, then e_u and f_u of every game into unit[(2 g + {0, 1}) * U + u].
+__global__ __launch_bounds__(kThreads) void kshap_se_unit_wide_kernel(const unsigned long long* __restrict__ keep, const float* __restrict__ v,
+                                                                      const double* __restrict__ v0, long long M, long long U, int R, int W,
+                                                                      int G, int paired, double* __restrict__ unit) {
+    const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (u >= U) return;
+    const long long m = paired ? 2 * u : u;
+    int s = 0;
+    for (int w = 0; w < W; ++w) {
+        const int bits = R - 64 * w;
+        s += __popcll(keep[(size_t)m * W + w] & (bits >= 64 ? ~0ull : (1ull << bits) - 1ull));
+    }
+    const double lin = 1.0 - (double)(2 * s) / (double)R, sq = (double)(s * s) / ((double)R * (double)R);
+    for (int g = 0; g < G; ++g) {
+        const float* vg = v + (size_t)g * M;
+        const double base = v0[g];
+        double d = (double)vg[m] - base;
+        if (paired) d = d - ((double)vg[m + 1] - base);
+        const double d2 = d * d;
+        unit[(size_t)(2 * g) * U + u] = d2 * lin;
+        unit[(size_t)(2 * g + 1) * U + u] = d2 * sq;
+    }
+}
+
+// Grid (chunk of chunks_of(U), word, game): partE[(g * nchunk + chunk) * R + 64 word + i] = the chunk's sum of e_u z_ui over the
+// units' first rows (row u starts at keep + u * stride words), in moment_chunk_of's order.
+__global__ __launch_bounds__(kThreads) void kshap_se_moment_wide_kernel(const unsigned long long* __restrict__ keep,
+                                                                        const double* __restrict__ unit, long long U, int R, int stride,
+                                                                        int tiles_per, double* __restrict__ partE) {
+    const int chunk = blockIdx.x, word = blockIdx.y, g = blockIdx.z;
+    const double* eu = unit + (size_t)(2 * g) * U;
+    iq::kshap::moment_chunk_of(
+        keep, stride, word, [=](long long u, double) { return eu[u]; }, nullptr, U, tiles_per, chunk,
+        partE + ((size_t)g * gridDim.x + chunk) * R + 64 * word, min(64, R - 64 * word), nullptr);
+}
+
+// Grid (chunk of chunks_of(U), game): partF[g * nchunk + chunk] = the chunk's sum of f_u, as a chunk's sum of weights is taken.
+__global__ __launch_bounds__(kThreads) void kshap_se_scalar_wide_kernel(const double* __restrict__ unit, long long U, int tiles_per,
+                                                                        double* __restrict__ partF) {
+    __shared__ double sh[kThreads];
+    const int chunk = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
+    const double* fu = unit + (size_t)(2 * g + 1) * U;
+    const long long row0 = (long long)chunk * tiles_per * iq::kshap::kTile;
+    double acc = 0.0;
+    for (int tile = 0; tile < tiles_per; ++tile) {
+        const long long u = row0 + (long long)tile * iq::kshap::kTile + t;
+        if (u < U) acc += fu[u];
+    }
+    const double s = iq::kshap::sum_threads_in_order(sh, acc);
+    if (t == 0) partF[(size_t)g * gridDim.x + chunk] = s;
+}
+
+// One workgroup per game.  c = (b_0 + b_1 + ... in index order) / R and F = the chunks' f in chunk order, by thread 0; then per
+// region E_i = the chunks' e in chunk order, S1 = two_h (b_i - c), S2 = (two_h two_h) (E_i + F),
+// var_i = ((U / (U - 1)) (S2 - S1 S1 / U)) / (M M).  Each operation rounded on its own.
+__global__ __launch_bounds__(kThreads) void kshap_moment_var_wide_kernel(const double* __restrict__ b, const double* __restrict__ partE,
+                                                                         const double* __restrict__ partF, int nchunk, long long M,
+                                                                         long long U, int R, double two_h, double* __restrict__ var) {
+    __shared__ double sh_mean, sh_f;
+    const int t = threadIdx.x, g = blockIdx.x;
+    if (t == 0) {
+        double s = 0.0;
+        for (int i = 0; i < R; ++i) s += b[(size_t)g * R + i];
+        sh_mean = s / (double)R;
+        sh_f = iq::kshap::fold_chunks(partF + (size_t)g * nchunk, 1, nchunk);
+    }
+    __syncthreads();
+    const double units = (double)U, rows = (double)M, scale = two_h * two_h;
+    for (int i = t; i < R; i += kThreads) {
+        const double e = iq::kshap::fold_chunks(partE + (size_t)g * nchunk * R + i, R, nchunk);
+        const double s1 = two_h * (b[(size_t)g * R + i] - sh_mean), s2 = scale * (e + sh_f);
+        var[(size_t)g * R + i] = ((units / (units - 1.0)) * (s2 - s1 * s1 / units)) / (rows * rows);
+    }
+}
+
 struct Scratch {
     double *partB, *partW;
     size_t bytes;
@@ -174,5 +254,70 @@ extern "C" int iq_kshap_phi_analytic(const double* b, const double* wsum, const 
     double h = 0.0;                                   // H_{R-1}, float64, ascending k: summed here on the host, passed by value
     for (int k = 1; k < R; ++k) h += 1.0 / (double)k;
     IQ_LAUNCH(kshap_phi_analytic_kernel, dim3(G), dim3(kThreads), 0, iq::as_stream(stream), b, wsum, delta, phi, R, 2.0 * h);
+    return IQ_OK;
+}
+
+namespace {
+
+// iq_kshap_moment_se_wide: the scratch of iq_kshap_moment_wide first, then its wsum, the units' (e, f) and their chunks' partials.
+struct SeScratch {
+    Scratch first;
+    double *wsum, *unit, *partE, *partF;
+    size_t bytes;
+};
+
+SeScratch carve_se(void* base, long long M, int R, int G, long long U) {
+    const Chunks ch = chunks_of(U);
+    SeScratch s;
+    s.first = carve(base, M, R, G);
+    iq::Carver c(base);
+    c.off = s.first.bytes;
+    s.wsum = c.take<double>(1);
+    s.unit = c.take<double>((size_t)2 * G * U);
+    s.partE = c.take<double>((size_t)G * ch.count * R);
+    s.partF = c.take<double>((size_t)G * ch.count);
+    s.bytes = c.bytes();
+    return s;
+}
+
+// the units of M rows; 0 where the rows do not make at least two whole units
+long long units_of(long long M, int paired) {
+    if (paired && (M & 1)) return 0;
+    const long long U = paired ? M / 2 : M;
+    return U >= 2 ? U : 0;
+}
+
+}  // namespace
+
+extern "C" size_t iq_kshap_moment_se_scratch_bytes_wide(int M, int R, int G, int paired) {
+    const long long U = units_of(M, paired);
+    return shape_ok(M, R, G) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
+}
+
+extern "C" int iq_kshap_moment_se_wide(const uint64_t* keep, const float* v, const double* v0, int M, int R, int G, int paired, double* b,
+                                       double* var, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
+    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_moment_se_wide: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G,
+               kMaxR);
+    const long long U = units_of(M, paired);
+    IQ_REQUIRE(U, "iq_kshap_moment_se_wide: M=%d %s rows are not two or more whole units", M, paired ? "paired" : "unpaired");
+    IQ_REQUIRE(keep && v && v0 && b && var && scratch, "iq_kshap_moment_se_wide: null pointer");
+    const SeScratch s = carve_se(scratch, M, R, G, U);
+    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
+        return iq::fail(IQ_EWORKSPACE, "iq_kshap_moment_se_wide: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes,
+                        scratch_bytes);
+    IQ_TRY(iq_kshap_moment_wide(keep, v, v0, nullptr, M, R, G, b, s.wsum, scratch, s.first.bytes, stream));
+    double h = 0.0;                                   // H_{R-1} as iq_kshap_phi_analytic sums it
+    for (int k = 1; k < R; ++k) h += 1.0 / (double)k;
+    const Chunks ch = chunks_of(U);
+    const int W = iq::keep_words(R), stride = paired ? 2 * W : W;
+    hipStream_t st = iq::as_stream(stream);
+    const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
+    IQ_LAUNCH(kshap_se_unit_wide_kernel, dim3((unsigned)((U + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, k, v, v0, (long long)M, U,
+              R, W, G, paired ? 1 : 0, s.unit);
+    IQ_LAUNCH(kshap_se_moment_wide_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
+              ch.tiles_per, s.partE);
+    IQ_LAUNCH(kshap_se_scalar_wide_kernel, dim3(ch.count, G), dim3(kThreads), 0, st, (const double*)s.unit, U, ch.tiles_per, s.partF);
+    IQ_LAUNCH(kshap_moment_var_wide_kernel, dim3(G), dim3(kThreads), 0, st, (const double*)b, (const double*)s.partE,
+              (const double*)s.partF, ch.count, (long long)M, U, R, 2.0 * h, var);
     return IQ_OK;
 }

@@ -117,7 +117,9 @@ __global__ __launch_bounds__(kInvThreads) void invert_orders_kernel(const int32_
     for (int i = threadIdx.x; i < n; i += kInvThreads) pos[base + i] = tab[i];
 }
 
-// shapley_sum_kernel's body (iq_shapley_sum.h) on a grid of (64 regions, game): the same float64 adds in permutation order
+// shapley_sum_kernel's body (iq_shapley_sum.h) on a grid of (64 regions, game): the same float64 adds in permutation order.
+// kSquare (iq_shapley_sq_accum_games): the widened difference squared - exact in float64 - before it is added.
+template <bool kSquare>
 __global__ __launch_bounds__(iq::kSumThreads) void shapley_sum_games_kernel(const float* __restrict__ v, size_t ldv,
                                                                             const uint16_t* __restrict__ pos, double* __restrict__ phi_sum,
                                                                             const int32_t* __restrict__ snap_counts, int n_snap,
@@ -129,7 +131,8 @@ __global__ __launch_bounds__(iq::kSumThreads) void shapley_sum_games_kernel(cons
             const unsigned p = pos[(size_t)o * R + r];
             if (p >= (unsigned)R) return 0.0;
             const float* vo = vg + (size_t)o * (R + 1) + p;
-            return (double)(vo[1] - vo[0]);
+            const double d = (double)(vo[1] - vo[0]);
+            return kSquare ? __dmul_rn(d, d) : d;
         },
         phi_sum + g * R, snap_counts, n_snap, snaps ? snaps + g * n_snap * R : nullptr, R, S, blockIdx.x * 64);
 }
@@ -193,17 +196,19 @@ extern "C" size_t iq_shapley_games_scratch_bytes(int R, int S, int G) {
     return iq::align_up((size_t)S * R * sizeof(uint16_t) + 1, 256);     // the position table; never 0 for accepted arguments
 }
 
-extern "C" int iq_shapley_accum_games(const float* v, size_t ldv, const int32_t* orders, double* phi_sum, const int32_t* snap_counts,
-                                      int n_snap, double* snaps, int R, int S, int G, void* scratch, size_t scratch_bytes,
-                                      iq_stream_t stream) {
-    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS && S >= 0, "iq_shapley_accum_games: R=%d S=%d", R, S);
-    IQ_REQUIRE(G >= 1 && G <= 65535, "iq_shapley_accum_games: G=%d not in [1,65535]", G);
-    IQ_REQUIRE(ldv >= (size_t)S * (R + 1), "iq_shapley_accum_games: ldv=%zu is shorter than S*(R+1)=%zu", ldv, (size_t)S * (R + 1));
-    IQ_REQUIRE(phi_sum, "iq_shapley_accum_games: phi_sum is required");
-    IQ_REQUIRE(n_snap >= 0 && (n_snap == 0 || (snap_counts && snaps)), "iq_shapley_accum_games: snapshots need counts and output");
-    IQ_REQUIRE(S == 0 || (v && orders), "iq_shapley_accum_games: null input");
+// iq_shapley_accum_games and, kSquare, iq_shapley_sq_accum_games: the same checks, position table and grid
+template <bool kSquare>
+int shapley_accum_games(const char* name, const float* v, size_t ldv, const int32_t* orders, double* phi_sum, const int32_t* snap_counts,
+                        int n_snap, double* snaps, int R, int S, int G, void* scratch, size_t scratch_bytes,
+                        iq_stream_t stream) {
+    IQ_REQUIRE(R >= 1 && R <= IQ_MAX_WIDE_REGIONS && S >= 0, "%s: R=%d S=%d", name, R, S);
+    IQ_REQUIRE(G >= 1 && G <= 65535, "%s: G=%d not in [1,65535]", name, G);
+    IQ_REQUIRE(ldv >= (size_t)S * (R + 1), "%s: ldv=%zu is shorter than S*(R+1)=%zu", name, ldv, (size_t)S * (R + 1));
+    IQ_REQUIRE(phi_sum, "%s: phi_sum is required", name);
+    IQ_REQUIRE(n_snap >= 0 && (n_snap == 0 || (snap_counts && snaps)), "%s: snapshots need counts and output", name);
+    IQ_REQUIRE(S == 0 || (v && orders), "%s: null input", name);
     IQ_REQUIRE(scratch && scratch_bytes >= iq_shapley_games_scratch_bytes(R, S, G),
-               "iq_shapley_accum_games: scratch of %zu bytes, iq_shapley_games_scratch_bytes asks for %zu", scratch_bytes,
+               "%s: scratch of %zu bytes, iq_shapley_games_scratch_bytes asks for %zu", name, scratch_bytes,
                iq_shapley_games_scratch_bytes(R, S, G));
     hipStream_t st = iq::as_stream(stream);
     uint16_t* pos = static_cast<uint16_t*>(scratch);
@@ -211,9 +216,23 @@ extern "C" int iq_shapley_accum_games(const float* v, size_t ldv, const int32_t*
         const int per = kInvEntries / R;
         IQ_LAUNCH(invert_orders_kernel, dim3((S + per - 1) / per), dim3(kInvThreads), 0, st, orders, pos, R, S);
     }
-    IQ_LAUNCH(shapley_sum_games_kernel, dim3((R + 63) / 64, G), dim3(iq::kSumThreads), 0, st, v, ldv, pos, phi_sum, snap_counts,
+    IQ_LAUNCH(shapley_sum_games_kernel<kSquare>, dim3((R + 63) / 64, G), dim3(iq::kSumThreads), 0, st, v, ldv, pos, phi_sum, snap_counts,
               n_snap, snaps, R, S);
     return IQ_OK;
+}
+
+extern "C" int iq_shapley_accum_games(const float* v, size_t ldv, const int32_t* orders, double* phi_sum, const int32_t* snap_counts,
+                                      int n_snap, double* snaps, int R, int S, int G, void* scratch, size_t scratch_bytes,
+                                      iq_stream_t stream) {
+    return shapley_accum_games<false>("iq_shapley_accum_games", v, ldv, orders, phi_sum, snap_counts, n_snap, snaps, R, S, G, scratch,
+                                      scratch_bytes, stream);
+}
+
+extern "C" int iq_shapley_sq_accum_games(const float* v, size_t ldv, const int32_t* orders, double* sq_sum, const int32_t* snap_counts,
+                                         int n_snap, double* sq_snaps, int R, int S, int G, void* scratch, size_t scratch_bytes,
+                                         iq_stream_t stream) {
+    return shapley_accum_games<true>("iq_shapley_sq_accum_games", v, ldv, orders, sq_sum, snap_counts, n_snap, sq_snaps, R, S, G,
+                                     scratch, scratch_bytes, stream);
 }
 
 extern "C" int iq_interaction_reduce(const float* v, float* out, int n, iq_stream_t stream) {

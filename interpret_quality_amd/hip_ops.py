@@ -622,7 +622,7 @@ def shapley_games_scratch_bytes(num_regions, num_samples, num_games):
     return int(_lib.load().iq_shapley_games_scratch_bytes(int(num_regions), int(num_samples), int(num_games)))
 
 
-def shapley_accum_games(v, orders, snap_counts=None, validate=True):
+def shapley_accum_games(v, orders, snap_counts=None, validate=True, entry="iq_shapley_accum_games"):
     """iq_shapley_accum_games: v (G,M) f32 with M >= S*(R+1) - row g the rewards of game g on the prefix coalitions of ``orders``,
     the table reward_classes fills - and orders (S,R), 1 <= R <= MAX_WIDE_REGIONS -> (phi_sum (G,R) f64, snaps (G,n_snap,R) f64 or
     None): per game the bits of shapley_accum_wide (for R <= 64 also shapley_accum's), without any per-game (S,R) row table.
@@ -654,9 +654,28 @@ def shapley_accum_games(v, orders, snap_counts=None, validate=True):
         counts = torch.tensor(list(snap_counts), dtype=torch.int32, device=dev)
         n_snap = counts.numel()
         snaps = torch.zeros((g, n_snap, r), dtype=torch.float64, device=dev)
-    _lib.check(lib.iq_shapley_accum_games(_dev(v, torch.float32, "v"), m, _p(orders), _p(phi), _p(counts), n_snap, _p(snaps), r, s, g,
-                                          _p(scratch), nbytes, _stream()), "iq_shapley_accum_games")
+    _lib.check(getattr(lib, entry)(_dev(v, torch.float32, "v"), m, _p(orders), _p(phi), _p(counts), n_snap, _p(snaps), r, s, g,
+                                   _p(scratch), nbytes, _stream()), entry)
     return phi, snaps
+
+
+def shapley_sq_accum_games(v, orders, snap_counts=None, validate=True):
+    """iq_shapley_sq_accum_games: ``shapley_accum_games`` with every widened float32 difference squared before it is added ->
+    (sq_sum (G,R) f64, sq_snaps (G,n_snap,R) f64 or None), strictly in permutation order: with the sums of ``shapley_accum_games``
+    the second moment a standard error needs (``shapley_se``)."""
+    return shapley_accum_games(v, orders, snap_counts, validate, "iq_shapley_sq_accum_games")
+
+
+def shapley_se(total, sq, count):
+    """The standard error of the permutation estimator's mean at ``count`` >= 2 permutations from the running sum ``total`` and
+    sum of squares ``sq`` (ndarrays or tensors of one shape): sqrt(max(sq - total^2 / n, 0) / (n (n - 1))) -> float64 ndarray.
+    Formed in extended precision where NumPy has it and rounded once: the difference cancels where the mean is large beside the
+    spread, and the two float64 sums should be all that is rounded before it."""
+    n = int(count)
+    if n < 2:
+        raise _lib.IqError("a standard error needs at least 2 permutations, got %d" % n)
+    t, q = (np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64).astype(np.longdouble) for x in (total, sq))
+    return np.sqrt(np.maximum(q - t * t / n, 0) / (n * (n - 1))).astype(np.float64)
 
 
 def kshap_regions_wide(r):
@@ -745,6 +764,82 @@ def kshap_pairs(keep, v, v0, delta, r, weights=None):
                                   _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0),
                                   _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()), "iq_kshap_pairs")
     return out
+
+
+def _sampled_rows(keep, r):
+    """The keep rows of a standard-error entry -> (pointer argument, M): narrow (M,) rows for r <= 64, or (M,W) wide rows."""
+    if isinstance(keep, torch.Tensor) and keep.dim() == 1:
+        if r > 64:
+            raise _lib.IqError("keep must be (M, %d) for %d regions, got %s" % (wide_words(r), r, tuple(keep.shape)))
+        return _dev(keep, torch.int64, "keep"), keep.shape[0]
+    return wide_keep(keep, r), keep.shape[0]
+
+
+def _units(what, m, paired):
+    """The iid units of M sampled rows (a row, or a row and its complement); IqError below two whole units."""
+    if paired and m % 2:
+        raise _lib.IqError("%s: %d paired rows are not whole pairs" % (what, m))
+    u = m // 2 if paired else m
+    if u < 2:
+        raise _lib.IqError("%s: a standard error needs at least 2 units, %d rows %s give %d" % (what, m, "paired" if paired else "unpaired", u))
+    return u
+
+
+SE_NEEDS_SAMPLES = "a standard error is the sampling error of drawn rows: enumerated or weighted rows have none"
+
+
+def kshap_pairs_se(keep, v, v0, delta, r, paired=True, weights=None):
+    """``kshap_pairs`` of SAMPLED rows (no weights) with the standard error of every entry -> (out (G,r,r) f64, the bits of
+    ``kshap_pairs``; se (G,r,r) f64, symmetric bit for bit with a zero diagonal).  iq_kshap_pairs_se: the second moment of the
+    same rows, its product on the f64 matrix pipe over the iid units - a row, or ``paired`` a row and its complement (M even) -
+    of which at least 2 are needed.  No further model evaluation.  ``weights`` other than None are refused."""
+    if weights is not None:
+        raise _lib.IqError("kshap_pairs_se: " + SE_NEEDS_SAMPLES)
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    kp, m = _sampled_rows(keep, r)
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    _shape(delta, "delta", g)
+    _units("kshap_pairs_se", m, paired)
+    dev = keep.device
+    nbytes = lib.iq_kshap_pairs_se_scratch_bytes(m, r, g, int(bool(paired)))
+    if nbytes == 0:
+        raise _lib.IqError("kshap_pairs_se: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
+    from . import kernelshap
+    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
+    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = torch.empty((g, r, r), dtype=torch.float64, device=dev)
+    se = torch.empty((g, r, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_pairs_se(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"), _dev(delta, torch.float64, "delta"),
+                                     _p(coef), m, r, g, int(bool(paired)), _p(out), _p(se), _p(scratch), nbytes, _stream()),
+               "iq_kshap_pairs_se")
+    return out, se
+
+
+def kshap_moment_se(keep, v, v0, r, paired=True, weights=None):
+    """SAMPLED rows (no weights), narrow (M,) or wide (M,W) -> (b (G,r) f64, the RAW moment with the bits of ``kshap_moment_wide``;
+    var (G,r) f64, the variance of phi under the analytic Gram matrix, phi_i = 2 H (b_i - mean(b)) / M + delta / r, from the second
+    moment of the same rows over the iid units (iq_kshap_moment_se_wide).  The standard error is sqrt(max(var, 0)).  ``weights``
+    other than None are refused."""
+    if weights is not None:
+        raise _lib.IqError("kshap_moment_se: " + SE_NEEDS_SAMPLES)
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    kp, m = _sampled_rows(keep, r)
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    _units("kshap_moment_se", m, paired)
+    dev = keep.device
+    nbytes = lib.iq_kshap_moment_se_scratch_bytes_wide(m, r, g, int(bool(paired)))
+    if nbytes == 0:
+        raise _lib.IqError("kshap_moment_se: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
+    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    b = torch.empty((g, r), dtype=torch.float64, device=dev)
+    var = torch.empty((g, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_moment_se_wide(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"), m, r, g, int(bool(paired)),
+                                           _p(b), _p(var), _p(scratch), nbytes, _stream()), "iq_kshap_moment_se_wide")
+    return b, var
 
 
 def kshap_draw_counter(seed, stream, first, count, r, cdf=None, paired=True, device="cuda"):

@@ -18,7 +18,15 @@ Per selected cloud, under the experiment folder that ``exp_folder`` derives from
                                                   sampling_error.json, its max and RMS error over the pairs against the exact index
                                                   (the mean over the orders of exact.interactions, from the same value table)
 
-Without --pairs every artefact is what it was before the flag existed, byte for byte.
+    kernelshap/region_shapley_se.npy              (n,) float64   with --se and --gram analytic: the standard error of
+                                                  region_shapley_value.npy (kernelshap.phi_se)
+    kernelshap/region_interaction_se.npy          (n, n) float64 with --se and --pairs: the standard error of every entry of
+                                                  region_interaction.npy (kernelshap.pairs_se; symmetric, zero diagonal)
+
+Without --pairs, and without --se, every artefact is what it was before the flag existed, byte for byte.  --se is the sampling
+error of drawn rows: with --samples all, or with the sampled Gram matrix and no --pairs, there is nothing it could write and the
+parser says so.  With --compare_exact, sampling_error.json gains "z_rms", the RMS of (estimate - exact) / se - about 1 for a
+calibrated bar - for the values whenever region_shapley_se.npy is written, and inside "pairs" for the interactions.
 
 ``--samples`` is the number of rows M (model evaluations; default 1000 (n + 1), stage 1's budget; ``all``: the enumerated game).
 With --compare_exact both estimates are read off ONE exact value table, not run through the network again; the permutations are
@@ -38,6 +46,7 @@ from .final_util import NUM_REGIONS, get_folder_name_list, load_model, mkdir
 
 
 FILES = ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value")
+OPTIONAL = {"interaction": "region_interaction", "phi_se": "region_shapley_se", "interaction_se": "region_interaction_se"}   # a game's key -> file
 
 
 def artefacts(g):
@@ -46,11 +55,11 @@ def artefacts(g):
     return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
             "running_counts": np.array(sorted(running), dtype=np.int64),
             "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), len(g["phi"])),
-            "v_full": g["v_full"], "v_empty": g["v_empty"], **({"region_interaction": g["interaction"]} if "interaction" in g else {})}
+            "v_full": g["v_full"], "v_empty": g["v_empty"], **{name: g[key] for key, name in OPTIONAL.items() if key in g}}
 
 
 def save(folder, out):
-    for key in FILES + (("region_interaction",) if "region_interaction" in out else ()):
+    for key in FILES + tuple(name for name in OPTIONAL.values() if name in out):
         np.save(folder + "%s.npy" % key, out[key])
 
 
@@ -63,6 +72,34 @@ def add_pairs_flag(parser):
 
 def wants_pairs(args):
     return bool(getattr(args, "pairs", False))
+
+
+def add_se_flag(parser):
+    """--se; a namespace parsed without it holds no trace of the flag (``wants_se`` reads it)."""
+    parser.add_argument("--se", action="store_true", default=argparse.SUPPRESS,
+                        help="also write the standard errors of the sampled estimates, from the second moment of the same rows: "
+                             "kernelshap/region_shapley_se.npy (analytic Gram matrix) and, with --pairs, region_interaction_se.npy")
+
+
+def wants_se(args):
+    return bool(getattr(args, "se", False))
+
+
+def check_se(parser, args, gram):
+    """--se needs drawn rows and something to put a bar on: a parser error with --samples all, and with the sampled Gram matrix
+    unless --pairs is there."""
+    if not wants_se(args):
+        return
+    if args.samples == "all":
+        parser.error("--se with --samples all: the enumerated game has no sampling error")
+    if gram != "analytic" and not wants_pairs(args):
+        parser.error("--se with --gram %s and no --pairs: phi under the sampled Gram matrix has no standard error here "
+                     "(--gram analytic, or --pairs)" % gram)
+
+
+def z_rms(est, exact_value, se):
+    """The RMS of (estimate - exact) / se over the entries: about 1 where the bars are calibrated."""
+    return float(np.sqrt(np.mean(((np.asarray(est) - exact_value) / se) ** 2)))
 
 
 def add_sample_flags(parser, enumerated=False):
@@ -127,8 +164,9 @@ def compare_exact(model, data, lbl, region_id, keep, args, v=None):
 
 def kernel_one_cloud(model, data, lbl, region_id, args):
     """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact, 'region_interaction' only with
-    --pairs, 'pairs_error' only with both)."""
-    g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram, pairs=wants_pairs(args))
+    --pairs, 'pairs_error' only with both; with --se the standard errors and, with --compare_exact, 'z_rms' / pairs_error's)."""
+    g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram, pairs=wants_pairs(args),
+                        **({"se": True} if wants_se(args) else {}))
     out = artefacts(g)
     if args.compare_exact:
         v = exact.value_table(model, data, lbl, region_id, args)
@@ -136,6 +174,10 @@ def kernel_one_cloud(model, data, lbl, region_id, args):
         if wants_pairs(args):
             upper = np.triu_indices(args.num_regions, 1)
             out["pairs_error"] = _errors(g["interaction"][upper], exact_pairs(v)[upper])
+            if "interaction_se" in g:
+                out["pairs_error"]["z_rms"] = z_rms(g["interaction"][upper], exact_pairs(v)[upper], g["interaction_se"][upper])
+        if "phi_se" in g:
+            out["z_rms"] = z_rms(g["phi"], out["exact"], g["phi_se"])
     return out
 
 
@@ -159,7 +201,8 @@ def run(args):
                 with open(result_path + "kernelshap/sampling_error.json", "w") as f:
                     json.dump({"num_regions": args.num_regions, "gram": args.gram, "paired": not args.unpaired, "v_full": out["v_full"], "v_empty": out["v_empty"],
                                "final": _errors(out["region_shapley_value"], out["exact"]), "sample_counts": out["sampling_error"],
-                               **({"pairs": out["pairs_error"]} if "pairs_error" in out else {})},
+                               **({"pairs": out["pairs_error"]} if "pairs_error" in out else {}),
+                               **({"z_rms": out["z_rms"]} if "z_rms" in out else {})},
                               f, indent=1)
                 if out["sampling_error"]:
                     last = out["sampling_error"][-1]
@@ -175,9 +218,11 @@ def make_args(argv=None):
     parser.add_argument("--compare_exact", action="store_true",
                         help="also enumerate the game (at most %d regions) and write sampling_error.json" % exact.MAX_PLAYERS)
     add_pairs_flag(parser)
+    add_se_flag(parser)
     args = stage1.parse_game_args(parser, argv, NUM_REGIONS, 2, kernelshap.MAX_REGIONS,
                                   "the regression estimator takes 2 to 64 regions (final_wide_kernel_shapley.py: 65 to 1024)")
     check_samples(parser, args, enumerated=True)
+    check_se(parser, args, args.gram)
     if (args.compare_exact or args.samples == "all") and args.num_regions > exact.MAX_PLAYERS:
         parser.error("--num_regions %d: --compare_exact and --samples all enumerate 2^num_regions coalitions; at most %d regions"
                      % (args.num_regions, exact.MAX_PLAYERS))

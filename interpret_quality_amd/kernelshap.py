@@ -205,6 +205,38 @@ def pairs(keep, v, v_empty, v_full, n, weights=None):
     return out[0] if v.dim() == 1 else out
 
 
+SE_NEEDS_SAMPLES = hip_ops.SE_NEEDS_SAMPLES
+SE_NEEDS_ANALYTIC = ("the standard error of phi exists for gram='analytic' only: under the sampled Gram matrix phi is no mean of "
+                     "independent units")
+
+
+def pairs_se(keep, v, v_empty, v_full, n, paired=True, weights=None):
+    """``pairs`` of SAMPLED rows with its standard error -> (interaction, se), float64 ndarrays (n,n) or (G,n,n): interaction the
+    bits of ``pairs``, se symmetric with a zero diagonal.  An unbiased variance estimate from the second moment of the same rows
+    over the iid units - a row, or ``paired`` a row and its complement - with no further model evaluation (include/iq.h,
+    "Standard errors").  At least 2 units."""
+    v2, v0, v1 = games(keep, v, v_empty, v_full)
+    out, se = hip_ops.kshap_pairs_se(keep, v2, v0, v1 - v0, n, paired, weights)
+    out, se = out.cpu().numpy(), se.cpu().numpy()
+    return (out[0], se[0]) if v.dim() == 1 else (out, se)
+
+
+def phi_se(keep, v, v_empty, v_full, n, paired=True, gram="analytic", ks=_NARROW, weights=None):
+    """``ks.estimate`` of SAMPLED rows under the analytic Gram matrix with its standard error -> (phi, se), float64 ndarrays (n,)
+    or (G,n): phi the bits of ``estimate``, se = sqrt(max(var, 0)) of ``hip_ops.kshap_moment_se``.  ``gram="sampled"`` is refused."""
+    n = ks.regions(n)
+    ks.check_gram(gram)
+    if gram != "analytic":
+        raise IqError(SE_NEEDS_ANALYTIC)
+    if weights is not None:
+        raise IqError(SE_NEEDS_SAMPLES)
+    phi = ks.estimate(keep, v, v_empty, v_full, n, None, gram)
+    v2, v0, _ = games(keep, v, v_empty, v_full)
+    var = hip_ops.kshap_moment_se(keep, v2, v0, n, paired)[1].cpu().numpy()
+    se = np.sqrt(np.maximum(var, 0.0))
+    return phi, (se[0] if v.dim() == 1 else se)
+
+
 def default_samples(n):
     """Stage 1's budget of model evaluations: 1000 permutations of n + 1 prefix coalitions, rounded down to even."""
     return 1000 * (n + 1) // 2 * 2
@@ -251,16 +283,22 @@ def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled", ks=_N
 
 
 def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, draw=None, classes=None,
-         pairs=False, **how):
+         pairs=False, se=False, **how):
     """The body of ``game``, wide_kernelshap.game and classwise.kernel_shapley, which check their own arguments first.  ``ks``:
     the estimator's module, this one or wide_kernelshap.  Refused before anything is drawn or run: the region count and
     ``gram``.  Then the rows - ``samples`` a count, None (``ks.default_samples``) or "all" (``ks.enumerated``); ``draw``:
     (n, samples, paired, device) -> (keep, sizes), default ``ks.draw`` - their rewards (``ks.rewards`` with ``classes`` and
     ``how``), ``ks.estimate`` and the running estimates at ``ks.running_counts`` (``counts=()``: none) -> the dict ``game``
     describes; ``pairs``: also "interaction", ``ks.pairs`` of the same rows and rewards ((n,n), or (G,n,n) with ``classes``; no
-    running estimates of it)."""
+    running estimates of it).  ``se``: also the standard errors of the sampled estimates, "phi_se" under the analytic Gram matrix
+    and "interaction_se" with ``pairs``; refused before anything is drawn with ``samples="all"`` and where neither exists (the
+    sampled Gram matrix without ``pairs``)."""
     n = ks.regions(args.num_regions)
     ks.check_gram(gram)
+    if se and isinstance(samples, str):
+        raise IqError(SE_NEEDS_SAMPLES)
+    if se and gram != "analytic" and not pairs:
+        raise IqError(SE_NEEDS_ANALYTIC)
     weights = None
     if isinstance(samples, str):
         if samples != "all":
@@ -274,17 +312,21 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
     if weights is None:
         running = running_estimates(keep, v, v_empty, v_full, n, ks.running_counts(n, keep.shape[0], paired, counts), gram, ks)
     out = {"keep": keep, "weights": weights, "v": v, "v_full": v_full, "v_empty": v_empty, "phi": phi, "running": running}
-    if pairs:
+    if pairs and se:
+        out["interaction"], out["interaction_se"] = ks.pairs_se(keep, v, v_empty, v_full, n, paired)
+    elif pairs:
         out["interaction"] = ks.pairs(keep, v, v_empty, v_full, n, weights)
+    if se and gram == "analytic":
+        out["phi_se"] = ks.phi_se(keep, v, v_empty, v_full, n, paired, gram)[1]
     return out
 
 
-def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, pairs=False):
+def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, pairs=False, se=False):
     """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
     sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows};
-    ``pairs``: also interaction (n,n), ``pairs`` of the same rows.  A ``gram`` outside GRAMS is refused before anything is
-    drawn or run."""
-    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs)
+    ``pairs``: also interaction (n,n), ``pairs`` of the same rows; ``se``: also phi_se (n,) under the analytic Gram matrix and,
+    with ``pairs``, interaction_se (n,n) (``play``).  A ``gram`` outside GRAMS is refused before anything is drawn or run."""
+    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs, se=se)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):

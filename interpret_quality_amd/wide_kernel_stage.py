@@ -9,10 +9,13 @@ Per selected cloud, under the wide experiment folder of that region count (``exp
     kernelshap/running_counts.npy                 (k,) int64     row counts c (R + 1), c in stage 1's sample counts, <= M
     kernelshap/running_region_shapley_value.npy   (k, R) float64 the estimate from the first count rows
     kernelshap/draw.json                          {"draw", "seed", "stream"}: the contract that made the rows; with --pairs also
-                                                  "pairs": true
+                                                  "pairs": true, with --se also "se": true
     kernelshap/region_interaction.npy             (R, R) float64 with --pairs: the SHAP-IQ estimate of the pairwise Shapley
                                                   interaction index of every pair of regions from the same M rows
                                                   (wide_kernelshap.pairs; symmetric, zero diagonal), no further model evaluation
+    kernelshap/region_shapley_se.npy              (R,) float64   with --se: the standard error of region_shapley_value.npy
+    kernelshap/region_interaction_se.npy          (R, R) float64 with --se and --pairs: the standard error of every entry of
+                                                  region_interaction.npy (symmetric, zero diagonal)
 
 ``--samples`` is the number of rows M (model evaluations; default 1000 (R + 1), stage 1's budget).  The clouds, the FPS centres and
 the region ids are final_wide_shapley.py's (wide_stage.cal_region_id).  The draws after the sizes come from the device sampler
@@ -46,7 +49,8 @@ def kernel_one_cloud(model, data, lbl, region_id, args, cloud=0):
     ``--draw counter``."""
     return kernel_stage.artefacts(wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired,
                                                        coalitions=args.coalitions, draw=args.draw, seed=args.seed, stream=cloud,
-                                                       pairs=kernel_stage.wants_pairs(args)))
+                                                       pairs=kernel_stage.wants_pairs(args),
+                                                       **({"se": True} if kernel_stage.wants_se(args) else {})))
 
 
 def stage1_estimate(result_path, i):
@@ -80,7 +84,8 @@ def run(args):
             kernel_stage.save(result_path + "kernelshap/", out)
             with open(result_path + "kernelshap/draw.json", "w") as f:
                 json.dump({"draw": args.draw, "seed": int(args.seed), "stream": i if args.draw == "counter" else None,
-                           **({"pairs": True} if kernel_stage.wants_pairs(args) else {})}, f)
+                           **({"pairs": True} if kernel_stage.wants_pairs(args) else {}),
+                           **({"se": True} if kernel_stage.wants_se(args) else {})}, f)
             phi = out["region_shapley_value"]
             line = "pointcloud:%s, index:%d, regions:%d, rows:%d, sum(phi)=%.6f, v_full - v_empty=%.6f" % (
                 name, i, args.num_regions, out["coalitions"].shape[0], phi.sum(), out["v_full"] - out["v_empty"])
@@ -100,8 +105,10 @@ def make_args(argv=None):
                         help="how the rows are drawn: from NumPy's MT19937 stream (default), or counter-based (Philox keyed by "
                              "--seed and the cloud's index): any cloud alone, no skip draws")
     kernel_stage.add_pairs_flag(parser)
+    kernel_stage.add_se_flag(parser)
     args = wide_stage.parse_wide_args(parser, argv, "final_kernel_shapley.py", samples=False)
     kernel_stage.check_samples(parser, args)
+    kernel_stage.check_se(parser, args, "analytic")
     return args
 
 

@@ -40,6 +40,7 @@ regions = hip_ops.kshap_regions_wide
 default_samples = kernelshap.default_samples      # 1000 (R + 1), even: no region count enters but through the argument
 running_counts = kernelshap.running_counts        # c (R + 1) for c in stage 1's sample counts
 pairs = kernelshap.pairs                          # all-pairs interactions: one entry for both row formats, here on (M,W) rows
+pairs_se = kernelshap.pairs_se                    # and their standard errors
 
 
 def check_gram(gram):
@@ -135,6 +136,11 @@ def estimate(keep, v, v_empty, v_full, r, weights=None, gram="analytic"):
     return phi[0] if v.dim() == 1 else phi
 
 
+def phi_se(keep, v, v_empty, v_full, r, paired=True, gram="analytic", weights=None):
+    """``estimate`` of SAMPLED wide rows with its standard error -> (phi, se): kernelshap.phi_se on this module."""
+    return kernelshap.phi_se(keep, v, v_empty, v_full, r, paired, gram, sys.modules[__name__], weights)
+
+
 def rewards(model, data, lbl, region_id, args, keep, coalitions=None, chunk=1 << 16, classes=None):
     """Rewards of the wide coalitions ``keep`` (M,W) of one cloud ``data`` (1,N,3), evaluated as ``wide.coalition_logits``
     evaluates them (``coalitions``: "dense" or "compact" for a family other than PointNet), ``chunk`` rows per call, the full and
@@ -155,17 +161,17 @@ def running_estimates(keep, v, v_empty, v_full, r, counts, gram="analytic"):
 
 
 def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",
-         seed=1, stream=0, pairs=False):
+         seed=1, stream=0, pairs=False, se=False):
     """One cloud's sampled (or, at most exact.MAX_PLAYERS regions, enumerated) game with everything the driver stores: dict of
     keep (M,W), weights (None when sampled), v (M,) float32 rewards, v_full, v_empty, phi (R,) and running {count: phi of the
     first ``count`` rows} (kernelshap.play on this module).  ``draw``: "stream" - ``draw`` on NumPy's global generator - or
     "counter" - ``draw_counter`` keyed by (``seed``, ``stream``), which the other kind ignores.  ``pairs``: also interaction
-    (R,R), ``pairs`` of the same rows.  The region count, ``gram`` and ``draw`` are refused, in that order, before anything else
+    (R,R), ``pairs`` of the same rows; ``se``: also phi_se (R,) and, with ``pairs``, interaction_se (R,R).  The region count, ``gram`` and ``draw`` are refused, in that order, before anything else
     is looked at."""
     regions(args.num_regions)
     check_gram(gram)
     return kernelshap.play(sys.modules[__name__], model, data, lbl, region_id, args, samples, paired, gram, counts,
-                           drawer(draw, seed, stream), pairs=pairs, coalitions=coalitions)
+                           drawer(draw, seed, stream), pairs=pairs, se=se, coalitions=coalitions)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",

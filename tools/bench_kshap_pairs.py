@@ -3,6 +3,7 @@
 how many rows a usable interaction map needs (not the flagship workload: that is bench.py).
 
     python tools/bench_kshap_pairs.py [--out profiles/kshap_pairs.json] [--seeds 20] [--runs 5]
+    python tools/bench_kshap_pairs.py --se [--out profiles/kshap_pairs_se.json]      the standard errors, see below
 
 Part 1 - time.  PointNet, synthetic cloud 0, (R, M) = (32, 33 000), (128, 129 000) and (1024, 1 025 000), G = 1 game (the cloud's
 label) and G = 10 (labels 0 .. 9 from the same forwards).  ``--runs`` runs each after a warm-up, wall clock around a synchronised
@@ -21,7 +22,14 @@ multiply-adds it performs).
 Part 2 - error.  PointNet, synthetic cloud 0, n = 16 regions, ``--seeds`` seeds: RMS over pairs and seeds of
 ``kernelshap.pairs_from_table`` against the exact index (the mean over the orders of ``hip_ops.exact_interactions`` of the
 cloud's value table) at 100 / 300 / 1000 permutations' worth of rows (c (n + 1), paired), beside the RMS of the exact index
-itself.  There is no rival estimator at equal evaluations: the number says how many rows a usable map needs."""
+itself.  There is no rival estimator at equal evaluations: the number says how many rows a usable map needs.
+
+``--se`` - the same two parts for ``hip_ops.kshap_pairs_se`` (the estimate and the standard error of every entry).  Time:
+``kshap_pairs_se``, ``kshap_pairs`` of the same build and the eager float64 form of BOTH products (Q over the rows, the second
+moment's product over the units' first rows) alternated in one process; reported are the ratio se / pairs of the medians (the
+arithmetic alone says about 1.5: the second product covers half the rows), whether it exceeds 2 beyond the spread, and the
+entry's share of forwards + reduction.  Error: at the same seeds and budgets the pooled z_rms = RMS of (estimate - exact) / se over
+pairs and seeds, the RMS and the mean of se, and the RMS error they should reproduce."""
 import argparse
 import json
 import os
@@ -83,7 +91,17 @@ def _eager_q(words, e, r, block, unpacked=None):
     return out
 
 
-def time_shape(r, m, games, runs, block, dev):
+def _unit_g(words, v2, v0, coef, sizes, r):
+    """The eager form's per-unit scalar of the second product, G_u = x(2)^2 - 2 x(1)^2 + x(0)^2 of paired rows -> (G,U) float64."""
+    mu = torch.stack([coef[:, 0], coef[:, 0] + coef[:, 1], coef[:, 0] + 2 * coef[:, 1] + coef[:, 2]], dim=1)
+    mu[1, 2] = 0.0
+    d = v2.to(torch.float64) - v0[:, None]
+    s = sizes[0::2]
+    x = d[:, 0::2, None] * mu[s][None] + d[:, 1::2, None] * mu[r - s].flip(1)[None]
+    return x[..., 2] ** 2 - 2 * x[..., 1] ** 2 + x[..., 0] ** 2
+
+
+def time_shape(r, m, games, runs, block, dev, se=False):
     model, data, lbl, rid, args = _setup(r, dev)
     ks = kernelshap if r <= kernelshap.MAX_REGIONS else wide_kernelshap
     np.random.seed(1)
@@ -108,6 +126,9 @@ def time_shape(r, m, games, runs, block, dev):
     kernel_call = lambda: hip_ops.kshap_pairs(keep, v2, v0, delta, r)           # noqa: E731
     kernel_call()
     _eager_q(words, e, r, block)
+    if se:
+        return _time_se(r, games, runs, block, words, e, _unit_g(words, v2, v0, coef, sizes, r), fwd, kernel_call,
+                        lambda: hip_ops.kshap_pairs_se(keep, v2, v0, delta, r, True))
     kern, eager, product = [], [], []
     for _ in range(runs):                                                       # alternated in one process
         kern.append(_wall(kernel_call)[0])
@@ -131,6 +152,54 @@ def time_shape(r, m, games, runs, block, dev):
         out.update({"eager_product_only": _spread(product), "eager_product_only_over_kernel": p / k,
                     "eager_product_only_tflops": square / p / 1e12})
     return out
+
+
+def _time_se(r, games, runs, block, words, e, e2, fwd, pairs_call, se_call):
+    """The --se rows of ``time_shape``: kshap_pairs_se, kshap_pairs and the eager form of both products, alternated."""
+    first = words[0::2].contiguous()
+    eager_both = lambda: (_eager_q(words, e, r, block), _eager_q(first, e2, r, block))      # noqa: E731
+    se_call()
+    eager_both()
+    pairs, with_se, eager = [], [], []
+    for _ in range(runs):
+        pairs.append(_wall(pairs_call)[0])
+        with_se.append(_wall(se_call)[0])
+        eager.append(_wall(eager_both)[0])
+    f, k, s, q = (float(np.median(x)) for x in (fwd, pairs, with_se, eager))
+    spread = max(max(pairs) - min(pairs), max(with_se) - min(with_se))
+    return {"num_regions": r, "rows": int(len(words)), "units": int(len(first)), "games": games, "pointnet_forwards": _spread(fwd),
+            "kshap_pairs": _spread(pairs), "kshap_pairs_se": _spread(with_se), "eager_both_products": _spread(eager),
+            "se_over_pairs": s / k, "larger_spread_seconds": spread, "se_costs_more_than_twice_pairs_beyond_the_spread": bool(s - 2 * k > spread),
+            "eager_both_over_se": q / s, "kshap_pairs_se_share_of_forwards_plus_reduction": s / (f + s),
+            "kshap_pairs_share_of_forwards_plus_reduction": k / (f + k), "eager_block_rows": block}
+
+
+def calibration_table(n, seeds, dev):
+    """``error_table``'s seeds and budgets through kernelshap.pairs_se: the error, and what the bars say it should be."""
+    model, data, lbl, rid, args = _setup(n, dev)
+    table = exact.value_table(model, data, lbl, rid, args)
+    ends = table[[0, table.numel() - 1]].cpu().numpy()
+    pr = hip_ops.all_pairs(n)
+    want = hip_ops.exact_interactions(table).cpu().numpy().mean(axis=1)
+    most = max(BUDGETS) * (n + 1)
+    err2, se2, z2, se1 = ({b: [] for b in BUDGETS} for _ in range(4))
+    for seed in range(seeds):
+        np.random.seed(1000 + seed)
+        keep, _ = kernelshap.draw(n, most, True, dev)
+        for b in BUDGETS:
+            rows = keep[:b * (n + 1) // 2 * 2].contiguous()
+            got, se = kernelshap.pairs_se(rows, table.index_select(0, rows).contiguous(), float(ends[0]), float(ends[1]), n)
+            got, se = got[pr[:, 0], pr[:, 1]], se[pr[:, 0], pr[:, 1]]
+            err2[b].append(float(((got - want) ** 2).mean()))
+            se2[b].append(float((se ** 2).mean()))
+            se1[b].append(float(se.mean()))
+            z2[b].append(float((((got - want) / se) ** 2).mean()))
+    return {"model": "pointnet", "cloud": "synthetic_00", "num_regions": n, "pairs": int(len(pr)), "seeds": seeds,
+            "exact_index_rms": float(np.sqrt((want ** 2).mean())),
+            "budgets": [{"permutations": b, "rows": b * (n + 1) // 2 * 2, "rms_error": float(np.sqrt(np.mean(err2[b]))),
+                         "rms_se": float(np.sqrt(np.mean(se2[b]))), "mean_se": float(np.mean(se1[b])),
+                         "z_rms": float(np.sqrt(np.mean(z2[b]))),
+                         "per_seed_z_rms": {"min": float(np.sqrt(min(z2[b]))), "max": float(np.sqrt(max(z2[b])))}} for b in BUDGETS]}
 
 
 def error_table(n, seeds, dev):
@@ -157,20 +226,22 @@ def error_table(n, seeds, dev):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "kshap_pairs.json"))
+    ap.add_argument("--se", action="store_true", help="time kshap_pairs_se and measure the calibration of its bars (profiles/kshap_pairs_se.json)")
+    ap.add_argument("--out", default=None, help="default profiles/kshap_pairs.json, with --se profiles/kshap_pairs_se.json")
     ap.add_argument("--seeds", type=int, default=20)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--block", type=int, default=1 << 16, help="rows per block of the eager form")
     ap.add_argument("--error_regions", type=int, default=16)
     ap.add_argument("--games", type=int, nargs="+", default=[1, 10])
     args = ap.parse_args(argv)
+    args.out = args.out or os.path.join(REPO, "profiles", "kshap_pairs_se.json" if args.se else "kshap_pairs.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_kshap_pairs.py needs a GPU: a time taken elsewhere says nothing about the MI355X")
     dev = torch.device("cuda:0")
     with torch.no_grad():
         res = {"device": torch.cuda.get_device_name(0),
-               "time": [time_shape(r, m, g, args.runs, args.block, dev) for r, m in SHAPES for g in args.games],
-               "error": error_table(args.error_regions, args.seeds, dev)}
+               "time": [time_shape(r, m, g, args.runs, args.block, dev, args.se) for r, m in SHAPES for g in args.games],
+               "error": (calibration_table if args.se else error_table)(args.error_regions, args.seeds, dev)}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
