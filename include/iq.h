@@ -10,7 +10,10 @@
  * Conventions
  *  - every pointer is a DEVICE pointer owned by the caller (e.g. torch.Tensor.data_ptr()),
  *    row-major contiguous, unless the parameter is documented as "host";
- *  - no allocation inside the library: scratch memory is a caller-provided workspace;
+ *  - no allocation inside the library: scratch memory is a caller-provided workspace.  Every `workspace` / `scratch` / `tmp`
+ *    argument may hold anything on entry, and no call writes outside [ptr, ptr + bytes) of the size its *_bytes function
+ *    returns; only iq_pointconv_coalitions_cached gives meaning to earlier contents, and only to the first
+ *    iq_pointconv_tables_bytes bytes (tests/test_workspace_contents_gpu.py);
  *  - every launch function takes a hipStream_t (passed as void*; NULL = default stream) and is
  *    asynchronous with respect to the host;
  *  - return value: IQ_OK (0) or a negative IQ_E* code; a message for the calling thread's last

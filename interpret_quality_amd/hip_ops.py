@@ -893,6 +893,10 @@ def knn(x, k=20):
     lib = _lib.load()
     b, n, c = x.shape
     out = torch.empty((b, n, k), dtype=torch.int32, device=x.device)
+    # The size formula restates iq_knn's own (csrc/iq_dgcnn.hip: the arrays it carves from tmp, B*N*84 + 16*B + 8192 bytes, and
+    # B*N*C*6 more for the bf16x3 operand image of C = 64 / 128, which it builds only when that room is there); the slack is 16384
+    # here so that the 256-byte rounding in front of the image cannot cost it.  tests/test_workspace_contents_gpu.py runs the call
+    # in exactly this many bytes between guard zones, so the two formulas cannot drift apart unnoticed.
     tmp = torch.empty((b * n * (84 + (6 * c if c in (64, 128) else 0)) + 16 * b + 16384,), dtype=torch.uint8, device=x.device)
     _lib.check(lib.iq_knn(_dev(x, torch.float32, "x"), _p(out), _p(tmp), tmp.numel(), b, n, c, k, _stream()), "iq_knn")
     return out
