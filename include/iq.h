@@ -81,8 +81,11 @@ enum {
  * 120: new entry points, no layout change (all-pairs interactions from the regression rows: iq_kshap_pairs_scratch_bytes,
  * iq_kshap_pairs).
  * 121: new entry points, no layout change (standard errors of the sampled estimates: iq_shapley_sq_accum_games,
- * iq_kshap_pairs_se_scratch_bytes, iq_kshap_pairs_se, iq_kshap_moment_se_scratch_bytes_wide, iq_kshap_moment_se_wide). */
-#define IQ_ABI_VERSION 121
+ * iq_kshap_pairs_se_scratch_bytes, iq_kshap_pairs_se, iq_kshap_moment_se_scratch_bytes_wide, iq_kshap_moment_se_wide).
+ * 122: new entry points, no layout change (control variates for the all-pairs map: iq_kshap_pairs_terms, iq_kshap_pairs_terms_se,
+ * iq_kshap_pair_features, iq_kshap_pair_gram, iq_kshap_pair_fit_scratch_bytes, iq_kshap_pair_fit, iq_kshap_pair_surrogate,
+ * iq_kshap_pair_shift_terms). */
+#define IQ_ABI_VERSION 122
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -846,6 +849,86 @@ size_t iq_kshap_moment_se_scratch_bytes_wide(int M, int R, int G, int paired);
 int iq_kshap_moment_se_wide(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, int M, int R, int G,
                             int paired, double* b /*G,R*/, double* var /*G,R*/, void* scratch, size_t scratch_bytes,
                             iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Control variates for the all-pairs map (csrc/iq_kshap_paircv.hip, csrc/iq_kshap_pairs.hip)
+ *
+ * The SHAP-IQ estimate above is unbiased and, at the budget of the Shapley stage, mostly noise.  Both estimators here run on the
+ * SAME sampled rows (weights == NULL) and rewards, with no further model evaluation, and subtract from every row a game whose
+ * pair interactions are known.  SHAPIQ(t) below is the estimator above on float64 per-row terms t_m in place of d_m and without
+ * its delta / (R-1) term: (((A + L_i) + L_j) + Q_ij) / W_sum (iq_kshap_pairs_terms), its standard error the formulas of "Standard
+ * errors" on t (iq_kshap_pairs_terms_se).  The delta term is the share of the full set, which no row holds: a subtracted game
+ * that is EFFICIENT, g(N) = delta, g(empty) = 0, leaves a residual game whose full and empty set are worth 0.
+ *
+ * shift, 2 <= R <= IQ_MAX_WIDE_REGIONS, narrow and wide rows, paired or not.  The additive game delta s / R has no pair
+ * interaction:
+ *     t_m = ((double)v_m - v0) - (delta (double)s_m) / (double)R       (iq_kshap_pair_shift_terms),      I = SHAPIQ(t).
+ * On paired rows mu(s,k) = mu(R-s, 2-k) makes a row and its complement enter as mu (d(S) + d(S^c)), to which an additive part of
+ * the game contributes only its total: the shift removes it.
+ *
+ * regression, 2 <= R <= IQ_MAX_REGIONS, narrow rows.  Features a = 0 .. d-1, d = R + R (R-1) / 2: the singles first, then the
+ * pairs (i < j) in row-major order; fm_a the 64-bit mask of the feature's regions, f_a(S) = [fm_a subset of S].  The U units of
+ * the rows (a row, or paired a row and its complement) are cut into two contiguous folds, units [0, U/2) and [U/2, U), each of at
+ * least 2 units.  Per fold f (M_f rows) and game:
+ *     Gram_f[a][b] = #{m in f : fm_a | fm_b subset of S_m}                      (iq_kshap_pair_gram: exact counts),
+ *     c_f[a] = sum_{m in f} f_a(S_m) ((double)v_m - v0)                         (float64, the moments' order on chunks_of(M_f)),
+ *     A = Gram_f + ridge I = L L^T,  beta_u = A^-1 c_f,  w = A^-1 1,            (ridge >= 0; the caller's default is M_f / 64)
+ *     beta = beta_u - w ((1 beta_u - delta) / (1 w))                            (iq_kshap_pair_fit: sum(beta) = delta),
+ * a pivot not above d 2^-52 max_i A_ii sets the status word (iq_kshap_solve's rule) and the betas are then meaningless.  The
+ * surrogate g_beta(S) = sum_a f_a(S) beta_a is 2-additive: its pair interaction C_ij(beta) is the coefficient of the pair.  Then
+ *     t_m = ((double)v_m - v0) - g_{beta of the OTHER fold}(S_m),   m in f      (iq_kshap_pair_surrogate),
+ *     I_f = C(beta_other) + (delta - 1 beta_other) / (R-1) + SHAPIQ_f(t),       se_f as in "Standard errors" on t over f's units,
+ *     I = (M_0 I_0 + M_1 I_1) / M,       se = sqrt(M_0^2 se_0^2 + M_1^2 se_1^2) / M          (host, float64).
+ * Each I_f is unbiased whatever the fit is, because beta_other does not depend on the rows of f; the fit decides the variance
+ * only.  (delta - 1 beta) is the rounding of the efficiency constraint, kept so that the identity is exact for any beta.  The two
+ * I_f are not independent (each fold's rows fit the other's surrogate); se NEGLECTS that cross-fold covariance.
+ *
+ * Order: the Gram matrix is sums of ones on v_mfma_f64_16x16x4_f64, exact in any order.  The Cholesky factor is blocked (panels of
+ * 32 columns: diagonal block in one workgroup's LDS, panel below it a row per thread, trailing update a thread per entry, the
+ * panel's columns subtracted in order), the triangular solves one workgroup per right-hand side, the surrogate one thread per
+ * row with the features added in index order in one chain.  One stream, no floating-point atomics, no grid chosen at run time:
+ * two calls give the same bits, a game's bits depend neither on G nor on a neighbouring game's rewards.
+ * ------------------------------------------------------------------------------------------- */
+
+/* iq_kshap_pairs on float64 terms t (G,M) in place of (v, v0, delta): out = SHAPIQ(t) as defined above.  weights as there (the
+ * enumerated rows with their weights give the exact index of a game whose full and empty set are worth 0).  Scratch:
+ * iq_kshap_pairs_scratch_bytes. */
+int iq_kshap_pairs_terms(const uint64_t* keep /*M,W*/, const double* t /*G,M*/, const double* weights /*M or NULL*/,
+                         const double* coef /*R+1,3 device*/, int M, int R, int G, double* out /*G,R,R*/, void* scratch,
+                         size_t scratch_bytes, iq_stream_t stream);
+
+/* iq_kshap_pairs_se on float64 terms t (G,M): out the bits of iq_kshap_pairs_terms with weights == NULL, se its standard error.
+ * Scratch: iq_kshap_pairs_se_scratch_bytes. */
+int iq_kshap_pairs_terms_se(const uint64_t* keep /*M,W*/, const double* t /*G,M*/, const double* coef /*R+1,3 device*/, int M, int R,
+                            int G, int paired, double* out /*G,R,R*/, double* se /*G,R,R*/, void* scratch, size_t scratch_bytes,
+                            iq_stream_t stream);
+
+/* d = R + R (R-1) / 2, the features of the surrogate; 0 outside 2 <= R <= IQ_MAX_REGIONS. */
+int iq_kshap_pair_features(int R);
+
+/* gram (d,d) float64, symmetric: the exact counts Gram[a][b] of the narrow rows keep (M); bits at or above R are ignored. */
+int iq_kshap_pair_gram(const uint64_t* keep /*M*/, int M, int R, double* gram /*d,d*/, iq_stream_t stream);
+
+/* Scratch (bytes) of iq_kshap_pair_fit: A (d,d), the right-hand sides' partials (G, chunks_of(M), d), the right-hand sides
+ * (G+1, d) and one float64, each rounded up to 256 bytes; 0 outside 1 <= M <= 2^30, 2 <= R <= IQ_MAX_REGIONS, 1 <= G <= 65535. */
+size_t iq_kshap_pair_fit_scratch_bytes(int M, int R, int G);
+
+/* beta (G,d) of the rows keep (M) with rewards v (G,M), from gram = iq_kshap_pair_gram of the same rows (unchanged).  solves
+ * (G+1,d) or NULL: rows 0 .. G-1 the unconstrained beta_u, row G w = A^-1 1, as the constraint read them.  *status (device): 0,
+ * or 1 where a pivot failed.  IQ_EINVAL for ridge < 0 or NaN. */
+int iq_kshap_pair_fit(const double* gram /*d,d*/, const uint64_t* keep /*M*/, const float* v /*G,M*/, const double* v0 /*G*/,
+                      const double* delta /*G*/, double ridge, int M, int R, int G, double* beta /*G,d*/,
+                      double* solves /*G+1,d or NULL*/, int32_t* status, void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* out_g[g][m] = g_{beta[g]}(S_m); out_t[g][m] = ((double)v[g][m] - v0[g]) - out_g[g][m].  Either output may be NULL (not both);
+ * v and v0 are read for out_t only. */
+int iq_kshap_pair_surrogate(const uint64_t* keep /*M*/, const double* beta /*G,d*/, const float* v /*G,M or NULL*/,
+                            const double* v0 /*G or NULL*/, int M, int R, int G, double* out_g /*G,M or NULL*/,
+                            double* out_t /*G,M or NULL*/, iq_stream_t stream);
+
+/* The terms of the shift, t[g][m] as defined above, for rows of W words, 2 <= R <= IQ_MAX_WIDE_REGIONS. */
+int iq_kshap_pair_shift_terms(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, const double* delta /*G*/,
+                              int M, int R, int G, double* t /*G,M*/, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

@@ -155,6 +155,14 @@ SIGNATURES = {
     "iq_kshap_pairs": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "iq_kshap_pairs_se_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
     "iq_kshap_pairs_se": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "iq_kshap_pairs_terms": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "iq_kshap_pairs_terms_se": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "iq_kshap_pair_features": (_I, [_I]),
+    "iq_kshap_pair_gram": (_I, [_P, _I, _I, _P, _P]),
+    "iq_kshap_pair_fit_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "iq_kshap_pair_fit": (_I, [_P, _P, _P, _P, _P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "iq_kshap_pair_surrogate": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "iq_kshap_pair_shift_terms": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "iq_kshap_moment_se_scratch_bytes_wide": (_SZ, [_I, _I, _I, _I]),
     "iq_kshap_moment_se_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "iq_kshap_draw_counter": (_I, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, _I, _I, _P, _I, _P, _P, _P]),
@@ -188,7 +196,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 121  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 122  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

@@ -53,6 +53,29 @@ __device__ __forceinline__ double row_term(double d, int s, int R, const double*
     return (s <= 0 || s >= R) ? 0.0 : d * coef[3 * s + k];
 }
 
+// What a row contributes before its weight, d_m of game g: the reward's difference (double)v_m - v0 of the estimator's own entries, or
+// a float64 term t_m the caller made (iq_kshap_pairs_terms: include/iq.h, "Control variates for the all-pairs map").  of(g, M) is
+// game g's view of the (G, M) array; the kernels below are written once over either.
+struct RewardDiff {
+    const float* v;
+    const double* v0;
+    struct Game {
+        const float* vg;
+        double base;
+        __device__ __forceinline__ double operator()(long long m) const { return (double)vg[m] - base; }
+    };
+    __device__ __forceinline__ Game of(int g, long long M) const { return {v + (size_t)g * M, v0[g]}; }
+};
+
+struct TermDiff {
+    const double* t;
+    struct Game {
+        const double* tg;
+        __device__ __forceinline__ double operator()(long long m) const { return tg[m]; }
+    };
+    __device__ __forceinline__ Game of(int g, long long M) const { return {t + (size_t)g * M}; }
+};
+
 // One thread per row: sizes[m] = the number of regions below R that row m keeps.
 __global__ __launch_bounds__(kThreads) void kshap_pairs_sizes_kernel(const unsigned long long* __restrict__ keep, long long M, int R,
                                                                      int W, unsigned short* __restrict__ sizes) {
@@ -147,51 +170,49 @@ __device__ __forceinline__ void pair_product_chunk(const unsigned long long* __r
 
 // Grid (block of Q, chunk, game): pair_product_chunk over every row with e_m = d_m gamma_s.
 // Two workgroups per CU by registers: 160 VGPRs, no scratch (left to itself the compiler takes 288 and one).
+template <typename Diff>
 __global__ __launch_bounds__(kThreads, 2) void kshap_pairs_q_kernel(const unsigned long long* __restrict__ keep,
-                                                                    const unsigned short* __restrict__ sizes, const float* __restrict__ v,
-                                                                    const double* __restrict__ v0, const double* __restrict__ weights,
+                                                                    const unsigned short* __restrict__ sizes, Diff diff,
+                                                                    const double* __restrict__ weights,
                                                                     const double* __restrict__ coef, long long M, int R, int W,
                                                                     int tiles_per, double* __restrict__ part) {
-    const float* vg = v + (size_t)blockIdx.z * M;
-    const double base = v0[blockIdx.z];
+    const auto d = diff.of(blockIdx.z, M);
     pair_product_chunk(
-        keep, (size_t)W,
-        [=](long long m) { return row_term((weights ? weights[m] : 1.0) * ((double)vg[m] - base), sizes[m], R, coef, 2); }, M, R,
+        keep, (size_t)W, [=](long long m) { return row_term((weights ? weights[m] : 1.0) * d(m), sizes[m], R, coef, 2); }, M, R,
         tiles_per, part);
 }
 
 // Grid (chunk of chunks_of(M), word, game): partL[(g * nchunk + chunk) * R + 64 word + i] = the chunk's sum of (d_m beta_s) z_mi in
 // moment_chunk's order; with weights, the workgroups of word 0 and game 0 also leave partW[chunk].
+template <typename Diff>
 __global__ __launch_bounds__(kThreads) void kshap_pairs_moment_kernel(const unsigned long long* __restrict__ keep,
-                                                                      const unsigned short* __restrict__ sizes,
-                                                                      const float* __restrict__ v, const double* __restrict__ v0,
+                                                                      const unsigned short* __restrict__ sizes, Diff diff,
                                                                       const double* __restrict__ weights, const double* __restrict__ coef,
                                                                       long long M, int R, int W, int tiles_per,
                                                                       double* __restrict__ partL, double* __restrict__ partW) {
     const int chunk = blockIdx.x, word = blockIdx.y, g = blockIdx.z;
-    const float* vg = v + (size_t)g * M;
-    const double base = v0[g];
+    const auto d = diff.of(g, M);
     iq::kshap::moment_chunk_of(
-        keep, W, word, [=](long long m, double w) { return row_term(w * ((double)vg[m] - base), sizes[m], R, coef, 1); }, weights, M,
-        tiles_per, chunk, partL + ((size_t)g * gridDim.x + chunk) * R + 64 * word, min(64, R - 64 * word),
+        keep, W, word, [=](long long m, double w) { return row_term(w * d(m), sizes[m], R, coef, 1); }, weights, M, tiles_per, chunk,
+        partL + ((size_t)g * gridDim.x + chunk) * R + 64 * word, min(64, R - 64 * word),
         weights && word == 0 && g == 0 ? partW + chunk : nullptr);
 }
 
 // Grid (chunk of chunks_of(M), game): partA[g * nchunk + chunk] = the chunk's sum of d_m alpha_s: per thread over its rows
 // t, t + 256, ... of the chunk, then the 256 threads in index order (the rule of a chunk's sum of weights).
-__global__ __launch_bounds__(kThreads) void kshap_pairs_alpha_kernel(const unsigned short* __restrict__ sizes, const float* __restrict__ v,
-                                                                     const double* __restrict__ v0, const double* __restrict__ weights,
+template <typename Diff>
+__global__ __launch_bounds__(kThreads) void kshap_pairs_alpha_kernel(const unsigned short* __restrict__ sizes, Diff diff,
+                                                                     const double* __restrict__ weights,
                                                                      const double* __restrict__ coef, long long M, int R, int tiles_per,
                                                                      double* __restrict__ partA) {
     __shared__ double sh[kThreads];
     const int chunk = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
-    const float* vg = v + (size_t)g * M;
-    const double base = v0[g];
+    const auto d = diff.of(g, M);
     const long long row0 = (long long)chunk * tiles_per * kTile;
     double acc = 0.0;
     for (int tile = 0; tile < tiles_per; ++tile) {
         const long long m = row0 + (long long)tile * kTile + t;
-        if (m < M) acc += row_term((weights ? weights[m] : 1.0) * ((double)vg[m] - base), sizes[m], R, coef, 0);
+        if (m < M) acc += row_term((weights ? weights[m] : 1.0) * d(m), sizes[m], R, coef, 0);
     }
     const double s = iq::kshap::sum_threads_in_order(sh, acc);
     if (t == 0) partA[(size_t)g * gridDim.x + chunk] = s;
@@ -216,6 +237,7 @@ __global__ __launch_bounds__(kThreads) void kshap_pairs_fold_kernel(const double
 
 // Grid (R^2 / 256, game), one thread per (i, j): the thread of i < j folds Q_ij over the chunks in chunk order and writes
 // out[i][j] = out[j][i] = delta / (R - 1) + (((A + L_i) + L_j) + Q_ij) / wsum, the same bits on both sides; i = j writes 0.
+// delta == nullptr (the terms entries): the quotient alone.
 __global__ __launch_bounds__(kThreads) void kshap_pairs_assemble_kernel(const double* __restrict__ part, const double* __restrict__ L,
                                                                         const double* __restrict__ A, const double* __restrict__ wsum,
                                                                         const double* __restrict__ delta, int R, int nchunk, int nblk,
@@ -230,7 +252,8 @@ __global__ __launch_bounds__(kThreads) void kshap_pairs_assemble_kernel(const do
     const int bi = i >> 6, bj = j >> 6, blk = bj * (bj + 1) / 2 + bi;
     const double qij = iq::kshap::fold_chunks(part + ((size_t)g * nchunk * nblk + blk) * kBlockElems + (i & 63) * kBlock + (j & 63),
                                               (size_t)nblk * kBlockElems, nchunk);
-    const double x = delta[g] / (double)(R - 1) + (((A[g] + L[(size_t)g * R + i]) + L[(size_t)g * R + j]) + qij) / *wsum;
+    const double y = (((A[g] + L[(size_t)g * R + i]) + L[(size_t)g * R + j]) + qij) / *wsum;
+    const double x = delta ? delta[g] / (double)(R - 1) + y : y;
     o[(size_t)i * R + j] = x;
     o[(size_t)j * R + i] = x;
 }
@@ -251,23 +274,23 @@ __device__ __forceinline__ double mu_of(int s, int k, int R, double two_h) {
 
 // Grid (U / 256, game), one thread per unit: P_u, B_u, G_u of game g once into unit[(3 g + {0, 1, 2}) * U + u].
 // x_u(k) = d_{cu} mu(s, k) [+ d_{cu+1} mu(R - s, 2 - k)], s the size of the unit's first row; 0 when that size is 0 or R.
-__global__ __launch_bounds__(kThreads) void kshap_pairs_unit_kernel(const unsigned short* __restrict__ sizes, const float* __restrict__ v,
-                                                                    const double* __restrict__ v0, long long M, long long U, int R,
-                                                                    int paired, double two_h, double* __restrict__ unit) {
+template <typename Diff>
+__global__ __launch_bounds__(kThreads) void kshap_pairs_unit_kernel(const unsigned short* __restrict__ sizes, Diff diff, long long M,
+                                                                    long long U, int R, int paired, double two_h,
+                                                                    double* __restrict__ unit) {
     const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
     const int g = blockIdx.y;
     if (u >= U) return;
-    const float* vg = v + (size_t)g * M;
-    const double base = v0[g];
+    const auto d = diff.of(g, M);
     const long long m = paired ? 2 * u : u;
     const int s = sizes[m];
     double x[3] = {0.0, 0.0, 0.0};
     if (s > 0 && s < R) {
-        const double d0 = (double)vg[m] - base;
+        const double d0 = d(m);
 #pragma unroll
         for (int k = 0; k < 3; ++k) x[k] = d0 * mu_of(s, k, R, two_h);
         if (paired) {
-            const double d1 = (double)vg[m + 1] - base;
+            const double d1 = d(m + 1);
 #pragma unroll
             for (int k = 0; k < 3; ++k) x[k] = x[k] + d1 * mu_of(R - s, 2 - k, R, two_h);
         }
@@ -374,18 +397,19 @@ Scratch carve(void* base, long long M, int R, int G) {
 bool shape_ok(long long M, int R, int G) { return M >= 1 && M <= (1ll << 30) && R >= 2 && R <= kMaxR && G >= 1 && G <= 65535; }
 
 // The launches of iq_kshap_pairs on a carved scratch: sizes, Q, L, A, the folds and the assembly of `out`.
-int launch_pairs(const Scratch& s, const unsigned long long* k, const float* v, const double* v0, const double* delta,
-                 const double* weights, const double* coef, int M, int R, int G, double* out, hipStream_t st) {
+template <typename Diff>
+int launch_pairs(const Scratch& s, const unsigned long long* k, Diff diff, const double* delta, const double* weights,
+                 const double* coef, int M, int R, int G, double* out, hipStream_t st) {
     const Chunks ch = chunks_of(M), qc = pair_chunks_of(M, R);
     const int W = iq::keep_words(R), nblk = blocks_of(R);
     const long long rows = M;
     IQ_LAUNCH(kshap_pairs_sizes_kernel, dim3((unsigned)((rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, k, rows, R, W, s.sizes);
-    IQ_LAUNCH(kshap_pairs_q_kernel, dim3(nblk, qc.count, G), dim3(kThreads), 0, st, k, (const unsigned short*)s.sizes, v, v0, weights,
-              coef, rows, R, W, qc.tiles_per, s.partQ);
-    IQ_LAUNCH(kshap_pairs_moment_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const unsigned short*)s.sizes, v, v0, weights,
-              coef, rows, R, W, ch.tiles_per, s.partL, s.partW);
-    IQ_LAUNCH(kshap_pairs_alpha_kernel, dim3(ch.count, G), dim3(kThreads), 0, st, (const unsigned short*)s.sizes, v, v0, weights, coef,
-              rows, R, ch.tiles_per, s.partA);
+    IQ_LAUNCH((kshap_pairs_q_kernel<Diff>), dim3(nblk, qc.count, G), dim3(kThreads), 0, st, k, (const unsigned short*)s.sizes, diff,
+              weights, coef, rows, R, W, qc.tiles_per, s.partQ);
+    IQ_LAUNCH((kshap_pairs_moment_kernel<Diff>), dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const unsigned short*)s.sizes, diff,
+              weights, coef, rows, R, W, ch.tiles_per, s.partL, s.partW);
+    IQ_LAUNCH((kshap_pairs_alpha_kernel<Diff>), dim3(ch.count, G), dim3(kThreads), 0, st, (const unsigned short*)s.sizes, diff, weights,
+              coef, rows, R, ch.tiles_per, s.partA);
     const long long folds = (long long)G * R + G + 1;
     IQ_LAUNCH(kshap_pairs_fold_kernel, dim3((unsigned)((folds + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const double*)s.partL,
               (const double*)s.partA, (const double*)s.partW, weights ? 1 : 0, rows, R, G, ch.count, s.L, s.A, s.wsum);
@@ -426,32 +450,18 @@ long long units_of(long long M, int paired) {
     return U >= 2 ? U : 0;
 }
 
-}  // namespace
-
-extern "C" size_t iq_kshap_pairs_se_scratch_bytes(int M, int R, int G, int paired) {
-    const long long U = units_of(M, paired);
-    return shape_ok(M, R, G) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
-}
-
-extern "C" int iq_kshap_pairs_se(const uint64_t* keep, const float* v, const double* v0, const double* delta, const double* coef, int M,
-                                 int R, int G, int paired, double* out, double* se, void* scratch, size_t scratch_bytes,
-                                 iq_stream_t stream) {
-    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_pairs_se: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
-    const long long U = units_of(M, paired);
-    IQ_REQUIRE(U, "iq_kshap_pairs_se: M=%d %s rows are not two or more whole units", M, paired ? "paired" : "unpaired");
-    IQ_REQUIRE(keep && v && v0 && delta && coef && out && se && scratch, "iq_kshap_pairs_se: null pointer");
-    const SeScratch s = carve_se(scratch, M, R, G, U);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_pairs_se: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
-    hipStream_t st = iq::as_stream(stream);
-    const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
-    IQ_TRY(launch_pairs(s.first, k, v, v0, delta, nullptr, coef, M, R, G, out, st));
+// The launches of iq_kshap_pairs_se on a carved scratch: launch_pairs, then the units, the second product, moment and scalar, their
+// folds and the assembly of `se`.
+template <typename Diff>
+int launch_pairs_se(const SeScratch& s, const unsigned long long* k, Diff diff, const double* delta, const double* coef, int M, int R,
+                    int G, int paired, long long U, double* out, double* se, hipStream_t st) {
+    IQ_TRY(launch_pairs(s.first, k, diff, delta, nullptr, coef, M, R, G, out, st));
     double h = 0.0;                                   // H_{R-1} as iq_kshap_phi_analytic sums it
     for (int i = 1; i < R; ++i) h += 1.0 / (double)i;
     const Chunks qc1 = pair_chunks_of(M, R), ch = chunks_of(U), qc = pair_chunks_of(U, R);
     const int W = iq::keep_words(R), nblk = blocks_of(R), stride = paired ? 2 * W : W;
-    IQ_LAUNCH(kshap_pairs_unit_kernel, dim3((unsigned)((U + kThreads - 1) / kThreads), G), dim3(kThreads), 0, st,
-              (const unsigned short*)s.first.sizes, v, v0, (long long)M, U, R, paired ? 1 : 0, 2.0 * h, s.unit);
+    IQ_LAUNCH((kshap_pairs_unit_kernel<Diff>), dim3((unsigned)((U + kThreads - 1) / kThreads), G), dim3(kThreads), 0, st,
+              (const unsigned short*)s.first.sizes, diff, (long long)M, U, R, paired ? 1 : 0, 2.0 * h, s.unit);
     IQ_LAUNCH(kshap_pairs_se_q_kernel, dim3(nblk, qc.count, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
               qc.tiles_per, s.partQ);
     IQ_LAUNCH(kshap_pairs_se_moment_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
@@ -466,6 +476,49 @@ extern "C" int iq_kshap_pairs_se(const uint64_t* keep, const float* v, const dou
     return IQ_OK;
 }
 
+// The checks and the carving shared by iq_kshap_pairs_se and iq_kshap_pairs_terms_se (`name`: the entry, for the message; `pointers`:
+// whether all of its pointer arguments are there) -> a status; with IQ_OK, *units and *carved are set.
+int check_se_call(const char* name, bool pointers, int M, int R, int G, int paired, void* scratch, size_t scratch_bytes,
+                  long long* units, SeScratch* carved) {
+    IQ_REQUIRE(shape_ok(M, R, G), "%s: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", name, M, R, G, kMaxR);
+    *units = units_of(M, paired);
+    IQ_REQUIRE(*units, "%s: M=%d %s rows are not two or more whole units", name, M, paired ? "paired" : "unpaired");
+    IQ_REQUIRE(pointers, "%s: null pointer", name);
+    *carved = carve_se(scratch, M, R, G, *units);
+    if (scratch_bytes < carved->bytes || ((uintptr_t)scratch & 7))
+        return iq::fail(IQ_EWORKSPACE, "%s: scratch of %zu bytes (8-byte aligned) needed, got %zu", name, carved->bytes, scratch_bytes);
+    return IQ_OK;
+}
+
+}  // namespace
+
+extern "C" size_t iq_kshap_pairs_se_scratch_bytes(int M, int R, int G, int paired) {
+    const long long U = units_of(M, paired);
+    return shape_ok(M, R, G) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
+}
+
+extern "C" int iq_kshap_pairs_se(const uint64_t* keep, const float* v, const double* v0, const double* delta, const double* coef, int M,
+                                 int R, int G, int paired, double* out, double* se, void* scratch, size_t scratch_bytes,
+                                 iq_stream_t stream) {
+    long long U;
+    SeScratch s;
+    IQ_TRY(check_se_call("iq_kshap_pairs_se", keep && v && v0 && delta && coef && out && se && scratch, M, R, G, paired, scratch,
+                         scratch_bytes, &U, &s));
+    return launch_pairs_se(s, reinterpret_cast<const unsigned long long*>(keep), RewardDiff{v, v0}, delta, coef, M, R, G, paired, U, out,
+                           se, iq::as_stream(stream));
+}
+
+// The same machinery on float64 per-row terms t in place of (v, v0, delta): out = (((A + L_i) + L_j) + Q_ij) / M, no delta term.
+extern "C" int iq_kshap_pairs_terms_se(const uint64_t* keep, const double* t, const double* coef, int M, int R, int G, int paired,
+                                       double* out, double* se, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
+    long long U;
+    SeScratch s;
+    IQ_TRY(check_se_call("iq_kshap_pairs_terms_se", keep && t && coef && out && se && scratch, M, R, G, paired, scratch, scratch_bytes, &U,
+                         &s));
+    return launch_pairs_se(s, reinterpret_cast<const unsigned long long*>(keep), TermDiff{t}, nullptr, coef, M, R, G, paired, U, out, se,
+                           iq::as_stream(stream));
+}
+
 extern "C" size_t iq_kshap_pairs_scratch_bytes(int M, int R, int G) {
     return shape_ok(M, R, G) ? carve(nullptr, M, R, G).bytes : 0;
 }
@@ -478,6 +531,19 @@ extern "C" int iq_kshap_pairs(const uint64_t* keep, const float* v, const double
     const Scratch s = carve(scratch, M, R, G);
     if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
         return iq::fail(IQ_EWORKSPACE, "iq_kshap_pairs: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
-    return launch_pairs(s, reinterpret_cast<const unsigned long long*>(keep), v, v0, delta, weights, coef, M, R, G, out,
+    return launch_pairs(s, reinterpret_cast<const unsigned long long*>(keep), RewardDiff{v, v0}, delta, weights, coef, M, R, G, out,
+                        iq::as_stream(stream));
+}
+
+// iq_kshap_pairs on float64 per-row terms t in place of (v, v0, delta): out = (((A + L_i) + L_j) + Q_ij) / W_sum, no delta term.
+// The scratch is iq_kshap_pairs_scratch_bytes.
+extern "C" int iq_kshap_pairs_terms(const uint64_t* keep, const double* t, const double* weights, const double* coef, int M, int R,
+                                    int G, double* out, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
+    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_pairs_terms: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
+    IQ_REQUIRE(keep && t && coef && out && scratch, "iq_kshap_pairs_terms: null pointer");
+    const Scratch s = carve(scratch, M, R, G);
+    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
+        return iq::fail(IQ_EWORKSPACE, "iq_kshap_pairs_terms: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
+    return launch_pairs(s, reinterpret_cast<const unsigned long long*>(keep), TermDiff{t}, nullptr, weights, coef, M, R, G, out,
                         iq::as_stream(stream));
 }

@@ -842,6 +842,169 @@ def kshap_moment_se(keep, v, v0, r, paired=True, weights=None):
     return b, var
 
 
+# The wrappers of the control-variate entries (below, to ``kshap_pair_shift_terms``) lend the library ZEROED memory: what a call
+# returns then cannot depend on an earlier call's bytes whatever a kernel reads, at the price of a memset of at most the 35 MB
+# factor beside a fit of milliseconds.  The library itself does not rely on it: tests/test_kshap_paircv_gpu.py hands the same
+# calls memory with hostile contents between guard zones and asks for the same bits.
+def _terms(t, m, what):
+    """The float64 per-row terms of a terms entry, (G,M) -> G."""
+    g, _ = _shape(t, what, None, m)
+    return g
+
+
+def kshap_pairs_terms(keep, t, r, weights=None):
+    """``kshap_pairs`` on float64 per-row terms t (G,M) in place of (v, v0, delta) -> (G,r,r) f64: (((A + L_i) + L_j) + Q_ij) / W_sum,
+    the estimator without its delta / (r-1) term (iq_kshap_pairs_terms; include/iq.h, "Control variates for the all-pairs map").
+    Narrow (M,) or wide (M,W) rows; ``weights`` as ``kshap_pairs`` takes them."""
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    kp, m = _sampled_rows(keep, r)
+    g = _terms(t, m, "t")
+    if weights is not None:
+        _shape(weights, "weights", m)
+    dev = keep.device
+    nbytes = lib.iq_kshap_pairs_scratch_bytes(m, r, g)
+    if nbytes == 0:
+        raise _lib.IqError("kshap_pairs_terms: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
+    from . import kernelshap
+    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
+    scratch = torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = torch.zeros((g, r, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_pairs_terms(kp, _dev(t, torch.float64, "t"),
+                                        _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0),
+                                        _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()), "iq_kshap_pairs_terms")
+    return out
+
+
+def kshap_pairs_terms_se(keep, t, r, paired=True, weights=None):
+    """``kshap_pairs_se`` on float64 per-row terms t (G,M) of SAMPLED rows -> (out, se), both (G,r,r) f64: out the bits of
+    ``kshap_pairs_terms``, se its standard error over the iid units (iq_kshap_pairs_terms_se).  ``weights`` other than None are
+    refused."""
+    if weights is not None:
+        raise _lib.IqError("kshap_pairs_terms_se: " + SE_NEEDS_SAMPLES)
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    kp, m = _sampled_rows(keep, r)
+    g = _terms(t, m, "t")
+    _units("kshap_pairs_terms_se", m, paired)
+    dev = keep.device
+    nbytes = lib.iq_kshap_pairs_se_scratch_bytes(m, r, g, int(bool(paired)))
+    if nbytes == 0:
+        raise _lib.IqError("kshap_pairs_terms_se: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
+    from . import kernelshap
+    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
+    scratch = torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev)
+    out = torch.zeros((g, r, r), dtype=torch.float64, device=dev)
+    se = torch.zeros((g, r, r), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_pairs_terms_se(kp, _dev(t, torch.float64, "t"), _p(coef), m, r, g, int(bool(paired)), _p(out), _p(se),
+                                           _p(scratch), nbytes, _stream()), "iq_kshap_pairs_terms_se")
+    return out, se
+
+
+SURROGATE_NEEDS_SHIFT = ("the regression surrogate has R + R (R-1) / 2 unknowns and takes 2 .. %d regions: use control='shift' above"
+                         % MAX_KSHAP_REGIONS)
+
+
+def kshap_pair_features(r):
+    """d = r + r (r-1) / 2, the features of the 2-additive surrogate: the singles, then the pairs (i < j) row-major.  IqError
+    that names ``shift`` above 64 regions."""
+    r = int(r)
+    if r > MAX_KSHAP_REGIONS:
+        raise _lib.IqError(SURROGATE_NEEDS_SHIFT + ", got %d" % r)
+    r = kshap_regions(r)
+    return r + r * (r - 1) // 2
+
+
+def _narrow_rows(keep, what):
+    if not isinstance(keep, torch.Tensor) or keep.dim() != 1:
+        raise _lib.IqError("%s: keep must be (M,) narrow rows" % what)
+    return _dev(keep, torch.int64, "keep"), keep.shape[0]
+
+
+def kshap_pair_gram(keep, r):
+    """keep (M,) int64-typed narrow rows -> (d,d) f64: Gram[a][b] = the number of rows that hold feature a and feature b, exact
+    counts (iq_kshap_pair_gram: the d x d x M product on the f64 matrix pipe; bits at or above r are ignored)."""
+    lib = _lib.load()
+    d = kshap_pair_features(r)
+    kp, m = _narrow_rows(keep, "kshap_pair_gram")
+    if not 1 <= m <= 1 << 30:
+        raise _lib.IqError("kshap_pair_gram: M=%d rows is out of range" % m)
+    gram = torch.zeros((d, d), dtype=torch.float64, device=keep.device)
+    _lib.check(lib.iq_kshap_pair_gram(kp, m, int(r), _p(gram), _stream()), "iq_kshap_pair_gram")
+    return gram
+
+
+def kshap_pair_fit(gram, keep, v, v0, delta, r, ridge, solves=False):
+    """gram (d,d) of ``kshap_pair_gram`` on the same rows, keep (M,), v (G,M) f32, v0 and delta (G,) f64, ridge >= 0 -> beta (G,d)
+    f64: the ridge regression of the rewards on the features under sum(beta[g]) = delta[g] (iq_kshap_pair_fit: blocked float64
+    Cholesky of gram + ridge I, one factor for all games).  ``solves``: -> (beta, (G+1,d) f64: rows 0 .. G-1 the unconstrained
+    solutions beta_u, row G the solution w for the ones vector).  KshapSingular when a pivot fails (a status word read back)."""
+    lib = _lib.load()
+    d = kshap_pair_features(r)
+    kp, m = _narrow_rows(keep, "kshap_pair_fit")
+    _shape(gram, "gram", d, d)
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    _shape(delta, "delta", g)
+    ridge = float(ridge)
+    if not ridge >= 0.0:
+        raise _lib.IqError("kshap_pair_fit: ridge must be a number >= 0, got %r" % ridge)
+    dev = keep.device
+    nbytes = lib.iq_kshap_pair_fit_scratch_bytes(m, int(r), g)
+    if nbytes == 0:
+        raise _lib.IqError("kshap_pair_fit: M=%d rows, R=%d regions, G=%d games is out of range" % (m, int(r), g))
+    scratch = torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev)
+    beta = torch.zeros((g, d), dtype=torch.float64, device=dev)
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    both = torch.zeros((g + 1, d), dtype=torch.float64, device=dev) if solves else None
+    _lib.check(lib.iq_kshap_pair_fit(_dev(gram, torch.float64, "gram"), kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"),
+                                     _dev(delta, torch.float64, "delta"), ridge, m, int(r), g, _p(beta), _p(both), _p(status), _p(scratch),
+                                     nbytes, _stream()), "iq_kshap_pair_fit")
+    if int(status.item()):
+        raise KshapSingular("the rows do not determine the 2-additive surrogate (%d rows, %d unknowns, ridge %g): draw more samples "
+                            "or use a ridge > 0" % (m, d, ridge))
+    return (beta, both) if solves else beta
+
+
+def kshap_pair_surrogate(keep, beta, r, v=None, v0=None):
+    """keep (M,), beta (G,d) f64 -> g (G,M) f64, g[g][m] = the sum of beta[g] over the features row m holds, in index order
+    (iq_kshap_pair_surrogate).  With v (G,M) f32 and v0 (G,) f64: -> (g, t), t = ((double)v - v0) - g, the residual terms."""
+    lib = _lib.load()
+    d = kshap_pair_features(r)
+    kp, m = _narrow_rows(keep, "kshap_pair_surrogate")
+    g, _ = _shape(beta, "beta", None, d)
+    if not 1 <= m <= 1 << 30:
+        raise _lib.IqError("kshap_pair_surrogate: M=%d rows is out of range" % m)
+    dev = keep.device
+    out = torch.zeros((g, m), dtype=torch.float64, device=dev)
+    t = None
+    if v is not None:
+        _shape(v, "v", g, m)
+        _shape(v0, "v0", g)
+        t = torch.zeros((g, m), dtype=torch.float64, device=dev)
+    _lib.check(lib.iq_kshap_pair_surrogate(kp, _dev(beta, torch.float64, "beta"), _dev(v, torch.float32, "v") if t is not None else _p(None),
+                                           _dev(v0, torch.float64, "v0") if t is not None else _p(None), m, int(r), g, _p(out), _p(t),
+                                           _stream()), "iq_kshap_pair_surrogate")
+    return out if t is None else (out, t)
+
+
+def kshap_pair_shift_terms(keep, v, v0, delta, r):
+    """Narrow (M,) or wide (M,W) rows, v (G,M) f32, v0 and delta (G,) f64 -> t (G,M) f64 = ((double)v - v0) - delta s / r, s the
+    row's size: the rewards less the additive game that spreads delta evenly (iq_kshap_pair_shift_terms)."""
+    lib = _lib.load()
+    r = kshap_regions_wide(r)
+    kp, m = _sampled_rows(keep, r)
+    g, _ = _shape(v, "v", None, m)
+    _shape(v0, "v0", g)
+    _shape(delta, "delta", g)
+    if not 1 <= m <= 1 << 30:
+        raise _lib.IqError("kshap_pair_shift_terms: M=%d rows is out of range" % m)
+    t = torch.zeros((g, m), dtype=torch.float64, device=keep.device)
+    _lib.check(lib.iq_kshap_pair_shift_terms(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"),
+                                             _dev(delta, torch.float64, "delta"), m, r, g, _p(t), _stream()), "iq_kshap_pair_shift_terms")
+    return t
+
+
 def kshap_draw_counter(seed, stream, first, count, r, cdf=None, paired=True, device="cuda"):
     """The counter-based draw of samples ``first .. first + count - 1`` of one cloud (iq_kshap_draw_counter: Philox4x32-10 keyed by
     (seed, stream), each sample a pure function of (seed, stream, index, r)) -> (keep (2 count or count, W) int64-typed wide rows,

@@ -23,8 +23,15 @@ Per selected cloud, under the experiment folder that ``exp_folder`` derives from
     kernelshap/region_interaction_se.npy          (n, n) float64 with --se and --pairs: the standard error of every entry of
                                                   region_interaction.npy (kernelshap.pairs_se; symmetric, zero diagonal)
 
-Without --pairs, and without --se, every artefact is what it was before the flag existed, byte for byte.  --se is the sampling
-error of drawn rows: with --samples all, or with the sampled Gram matrix and no --pairs, there is nothing it could write and the
+    kernelshap/region_interaction_cv.npy          (n, n) float64 with --pairs and --control shift|regression: the control-variate
+                                                  estimate of the same index from the same rows (kernelshap.pairs_cv; DESIGN.md
+                                                  5j), beside region_interaction.npy, which is still written
+    kernelshap/region_interaction_cv_se.npy       (n, n) float64 its standard error (symmetric, zero diagonal)
+    kernelshap/control.json                       {"control", "ridge", "fold_rows", "paired"} of that estimate; with
+                                                  --compare_exact sampling_error.json gains "pairs_cv": max error, RMS error, z_rms
+
+Without --pairs, without --se and without --control, every artefact is what it was before the flag existed, byte for byte.
+--se is the sampling error of drawn rows: with --samples all, or with the sampled Gram matrix and no --pairs, there is nothing it could write and the
 parser says so.  With --compare_exact, sampling_error.json gains "z_rms", the RMS of (estimate - exact) / se - about 1 for a
 calibrated bar - for the values whenever region_shapley_se.npy is written, and inside "pairs" for the interactions.
 
@@ -46,7 +53,8 @@ from .final_util import NUM_REGIONS, get_folder_name_list, load_model, mkdir
 
 
 FILES = ("coalitions", "rewards", "region_shapley_value", "running_counts", "running_region_shapley_value")
-OPTIONAL = {"interaction": "region_interaction", "phi_se": "region_shapley_se", "interaction_se": "region_interaction_se"}   # a game's key -> file
+OPTIONAL = {"interaction": "region_interaction", "phi_se": "region_shapley_se", "interaction_se": "region_interaction_se",
+            "interaction_cv": "region_interaction_cv", "interaction_cv_se": "region_interaction_cv_se"}   # a game's key -> file
 
 
 def artefacts(g):
@@ -55,12 +63,16 @@ def artefacts(g):
     return {"coalitions": g["keep"].cpu().numpy().view(np.uint64), "rewards": g["v"].cpu().numpy(), "region_shapley_value": g["phi"],
             "running_counts": np.array(sorted(running), dtype=np.int64),
             "running_region_shapley_value": np.array([running[c] for c in sorted(running)], dtype=np.float64).reshape(len(running), len(g["phi"])),
-            "v_full": g["v_full"], "v_empty": g["v_empty"], **{name: g[key] for key, name in OPTIONAL.items() if key in g}}
+            "v_full": g["v_full"], "v_empty": g["v_empty"], **{name: g[key] for key, name in OPTIONAL.items() if key in g},
+            **({"control": g["control"]} if "control" in g else {})}
 
 
 def save(folder, out):
     for key in FILES + tuple(name for name in OPTIONAL.values() if name in out):
         np.save(folder + "%s.npy" % key, out[key])
+    if "control" in out:
+        with open(folder + "control.json", "w") as f:
+            json.dump({key: out["control"][key] for key in ("control", "ridge", "fold_rows", "paired")}, f)
 
 
 def add_pairs_flag(parser):
@@ -95,6 +107,28 @@ def check_se(parser, args, gram):
     if gram != "analytic" and not wants_pairs(args):
         parser.error("--se with --gram %s and no --pairs: phi under the sampled Gram matrix has no standard error here "
                      "(--gram analytic, or --pairs)" % gram)
+
+
+def add_control_flag(parser, choices):
+    """--control; a namespace parsed without it holds no trace of the flag (``control_of`` reads it)."""
+    parser.add_argument("--control", choices=list(choices), default=argparse.SUPPRESS,
+                        help="with --pairs: also write kernelshap/region_interaction_cv.npy, its standard error and control.json - the "
+                             "control-variate estimate of the all-pairs map from the same rows (shift: the additive game; regression: "
+                             "a cross-fitted 2-additive surrogate), no further model evaluation; default none")
+
+
+def control_of(args):
+    return getattr(args, "control", "none")
+
+
+def check_control(parser, args):
+    """--control shift|regression needs --pairs and drawn rows: a parser error without --pairs and with --samples all."""
+    if control_of(args) == "none":
+        return
+    if not wants_pairs(args):
+        parser.error("--control %s without --pairs: the control variate belongs to the all-pairs map" % control_of(args))
+    if args.samples == "all":
+        parser.error("--control with --samples all: the enumerated game has no sampling error to reduce")
 
 
 def z_rms(est, exact_value, se):
@@ -166,7 +200,8 @@ def kernel_one_cloud(model, data, lbl, region_id, args):
     """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact, 'region_interaction' only with
     --pairs, 'pairs_error' only with both; with --se the standard errors and, with --compare_exact, 'z_rms' / pairs_error's)."""
     g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram, pairs=wants_pairs(args),
-                        **({"se": True} if wants_se(args) else {}))
+                        **({"se": True} if wants_se(args) else {}),
+                        **({"control": control_of(args)} if control_of(args) != "none" else {}))
     out = artefacts(g)
     if args.compare_exact:
         v = exact.value_table(model, data, lbl, region_id, args)
@@ -176,6 +211,10 @@ def kernel_one_cloud(model, data, lbl, region_id, args):
             out["pairs_error"] = _errors(g["interaction"][upper], exact_pairs(v)[upper])
             if "interaction_se" in g:
                 out["pairs_error"]["z_rms"] = z_rms(g["interaction"][upper], exact_pairs(v)[upper], g["interaction_se"][upper])
+            if "interaction_cv" in g:
+                out["pairs_cv_error"] = dict(_errors(g["interaction_cv"][upper], exact_pairs(v)[upper]),
+                                             z_rms=z_rms(g["interaction_cv"][upper], exact_pairs(v)[upper],
+                                                         g["interaction_cv_se"][upper]))
         if "phi_se" in g:
             out["z_rms"] = z_rms(g["phi"], out["exact"], g["phi_se"])
     return out
@@ -202,6 +241,7 @@ def run(args):
                     json.dump({"num_regions": args.num_regions, "gram": args.gram, "paired": not args.unpaired, "v_full": out["v_full"], "v_empty": out["v_empty"],
                                "final": _errors(out["region_shapley_value"], out["exact"]), "sample_counts": out["sampling_error"],
                                **({"pairs": out["pairs_error"]} if "pairs_error" in out else {}),
+                               **({"pairs_cv": out["pairs_cv_error"]} if "pairs_cv_error" in out else {}),
                                **({"z_rms": out["z_rms"]} if "z_rms" in out else {})},
                               f, indent=1)
                 if out["sampling_error"]:
@@ -219,10 +259,12 @@ def make_args(argv=None):
                         help="also enumerate the game (at most %d regions) and write sampling_error.json" % exact.MAX_PLAYERS)
     add_pairs_flag(parser)
     add_se_flag(parser)
+    add_control_flag(parser, kernelshap.CONTROLS)
     args = stage1.parse_game_args(parser, argv, NUM_REGIONS, 2, kernelshap.MAX_REGIONS,
                                   "the regression estimator takes 2 to 64 regions (final_wide_kernel_shapley.py: 65 to 1024)")
     check_samples(parser, args, enumerated=True)
     check_se(parser, args, args.gram)
+    check_control(parser, args)
     if (args.compare_exact or args.samples == "all") and args.num_regions > exact.MAX_PLAYERS:
         parser.error("--num_regions %d: --compare_exact and --samples all enumerate 2^num_regions coalitions; at most %d regions"
                      % (args.num_regions, exact.MAX_PLAYERS))

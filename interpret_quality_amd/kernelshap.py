@@ -221,6 +221,111 @@ def pairs_se(keep, v, v_empty, v_full, n, paired=True, weights=None):
     return (out[0], se[0]) if v.dim() == 1 else (out, se)
 
 
+CONTROLS = ("none", "shift", "regression")
+CONTROL_NEEDS_PAIRS = "a control variate belongs to the all-pairs map: control=%r needs pairs=True"
+RIDGE_SHARE = 64     # the default ridge of a fold's fit: its rows / 64 (a near-zero ridge is worse than no control)
+
+
+def check_control(control):
+    if control not in CONTROLS:
+        raise IqError("control must be one of %s, got %r" % (CONTROLS, control))
+
+
+def fold_units(rows, paired=True):
+    """(U_0, U_1): the units of the two contiguous folds of ``rows`` sampled rows, units [0, U/2) and [U/2, U) - a unit a row, or
+    ``paired`` a row and its complement.  IqError unless both folds hold at least 2 whole units."""
+    rows = int(rows)
+    if paired and rows % 2:
+        raise IqError("pairs_cv: %d paired rows are not whole pairs" % rows)
+    u = rows // 2 if paired else rows
+    if u < 4:
+        raise IqError("pairs_cv: two folds of at least 2 units need 4 units, %d rows %s give %d" % (rows, "paired" if paired else "unpaired", u))
+    return u // 2, u - u // 2
+
+
+def pair_features(n):
+    """d = n + n (n-1) / 2: the unknowns of the 2-additive surrogate (singles, then the pairs (i < j) row-major)."""
+    return hip_ops.kshap_pair_features(n)
+
+
+def fit_scratch_bytes(m, n, games):
+    """The scratch of iq_kshap_pair_fit restated: A (d,d), the partials (G, chunks(m), d), the right-hand sides (G+1, d) and one
+    float64, each rounded up to 256 bytes (tests hold it against the library's)."""
+    d = int(n) + int(n) * (int(n) - 1) // 2
+    up = lambda count: (8 * count + 255) // 256 * 256
+    return up(d * d) + up(int(games) * chunks(m)[0] * d) + up((int(games) + 1) * d) + up(1)
+
+
+def pair_coefficient_map(beta, n):
+    """C(beta): (..., d) coefficients -> (..., n, n) float64, the pair coefficients mirrored, zero on the diagonal - the pair
+    interactions of the 2-additive game the coefficients describe."""
+    beta = np.asarray(beta, dtype=np.float64)
+    out = np.zeros(beta.shape[:-1] + (n, n))
+    i, j = np.triu_indices(n, 1)          # row-major over i < j: the order of the pair features
+    out[..., i, j] = beta[..., n:]
+    out[..., j, i] = beta[..., n:]
+    return out
+
+
+def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", ridge=None, weights=None):
+    """The control-variate estimate of the all-pairs Shapley interaction index from SAMPLED rows, with its standard error, on the
+    rows and rewards ``pairs_se`` takes and with no further model evaluation -> (interaction, se, info): float64 ndarrays (n,n)
+    or (G,n,n), symmetric bit for bit with a zero diagonal, and a dict (include/iq.h, "Control variates for the all-pairs map";
+    DESIGN.md 5j).
+
+    ``control="shift"`` (2 .. 1024 regions, narrow or wide rows): SHAP-IQ on the rewards less the additive game delta s / n.
+    ``control="regression"`` (2 .. 64 regions, narrow rows): two contiguous folds of units; a 2-additive surrogate is fitted to
+    each fold (ridge ``ridge``, default a fold's rows / 64, under sum(beta) = delta), its pair coefficients are read off and SHAP-IQ
+    runs on the OTHER fold's residuals; the two estimates are averaged by rows.  Unbiased whatever the fit; the standard error
+    neglects the covariance between the folds.  info: control, paired, fold_rows, ridge (per fold), status, beta ((2,G,d) or
+    (2,d)) - for the shift fold_rows is the one range of rows and ridge, beta are None."""
+    check_control(control)
+    if control == "none":
+        raise IqError("pairs_cv: control='none' is pairs_se")
+    if weights is not None:
+        raise IqError("pairs_cv: " + hip_ops.SE_NEEDS_SAMPLES)
+    v2, v0, v1 = games(keep, v, v_empty, v_full)
+    delta = v1 - v0
+    single = v.dim() == 1
+    m = keep.shape[0]
+    if control == "shift":
+        t = hip_ops.kshap_pair_shift_terms(keep, v2, v0, delta, n)
+        out, se = hip_ops.kshap_pairs_terms_se(keep, t, n, paired)
+        out, se = out.cpu().numpy(), se.cpu().numpy()
+        info = {"control": control, "paired": bool(paired), "fold_rows": [m], "ridge": None, "status": 0, "beta": None}
+        return (out[0], se[0], info) if single else (out, se, info)
+    d = pair_features(n)                      # refuses more than 64 regions, naming the shift
+    n = int(n)
+    if ridge is not None and not float(ridge) >= 0.0:
+        raise IqError("pairs_cv: ridge must be a number >= 0, got %r" % (ridge,))
+    u0, u1 = fold_units(m, paired)
+    c = 2 if paired else 1
+    cuts = ((0, c * u0), (c * u0, c * (u0 + u1)))
+    rows = [hi - lo for lo, hi in cuts]
+    kf = [keep[lo:hi].contiguous() for lo, hi in cuts]
+    vf = [v2[:, lo:hi].contiguous() for lo, hi in cuts]
+    ridges = [rows[f] / float(RIDGE_SHARE) if ridge is None else float(ridge) for f in range(2)]
+    beta = [hip_ops.kshap_pair_fit(hip_ops.kshap_pair_gram(kf[f], n), kf[f], vf[f], v0, delta, n, ridges[f]) for f in range(2)]
+    est, var = [], []
+    for f in range(2):
+        other = beta[1 - f]
+        _, t = hip_ops.kshap_pair_surrogate(kf[f], other, n, vf[f], v0)
+        res, se_f = hip_ops.kshap_pairs_terms_se(kf[f], t, n, paired)
+        b = other.cpu().numpy()
+        slack = (delta.cpu().numpy() - b.sum(axis=1)) / (n - 1)          # the rounding of the efficiency constraint
+        i_f = pair_coefficient_map(b, n) + res.cpu().numpy()
+        i_f[:, ~np.eye(n, dtype=bool)] += slack[:, None]
+        est.append(i_f)
+        var.append(se_f.cpu().numpy() ** 2)
+    total = float(rows[0] + rows[1])
+    out = (rows[0] * est[0] + rows[1] * est[1]) / total
+    se = np.sqrt(rows[0] ** 2 * var[0] + rows[1] ** 2 * var[1]) / total
+    betas = np.stack([b.cpu().numpy() for b in beta])
+    info = {"control": control, "paired": bool(paired), "fold_rows": rows, "ridge": ridges, "status": 0,
+            "beta": betas[:, 0] if single else betas}
+    return (out[0], se[0], info) if single else (out, se, info)
+
+
 def phi_se(keep, v, v_empty, v_full, n, paired=True, gram="analytic", ks=_NARROW, weights=None):
     """``ks.estimate`` of SAMPLED rows under the analytic Gram matrix with its standard error -> (phi, se), float64 ndarrays (n,)
     or (G,n): phi the bits of ``estimate``, se = sqrt(max(var, 0)) of ``hip_ops.kshap_moment_se``.  ``gram="sampled"`` is refused."""
@@ -283,7 +388,7 @@ def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled", ks=_N
 
 
 def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, draw=None, classes=None,
-         pairs=False, se=False, **how):
+         pairs=False, se=False, control="none", **how):
     """The body of ``game``, wide_kernelshap.game and classwise.kernel_shapley, which check their own arguments first.  ``ks``:
     the estimator's module, this one or wide_kernelshap.  Refused before anything is drawn or run: the region count and
     ``gram``.  Then the rows - ``samples`` a count, None (``ks.default_samples``) or "all" (``ks.enumerated``); ``draw``:
@@ -292,9 +397,19 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
     describes; ``pairs``: also "interaction", ``ks.pairs`` of the same rows and rewards ((n,n), or (G,n,n) with ``classes``; no
     running estimates of it).  ``se``: also the standard errors of the sampled estimates, "phi_se" under the analytic Gram matrix
     and "interaction_se" with ``pairs``; refused before anything is drawn with ``samples="all"`` and where neither exists (the
-    sampled Gram matrix without ``pairs``)."""
+    sampled Gram matrix without ``pairs``).  ``control`` other than "none" (with ``pairs``, sampled rows): also
+    "interaction_cv", "interaction_cv_se" and "control" (the info dict) of ``ks.pairs_cv`` on the same rows; everything else is
+    what it is without it."""
     n = ks.regions(args.num_regions)
     ks.check_gram(gram)
+    check_control(control)
+    if control != "none":
+        if not pairs:
+            raise IqError(CONTROL_NEEDS_PAIRS % control)
+        if isinstance(samples, str):
+            raise IqError(SE_NEEDS_SAMPLES)
+        if control not in ks.CONTROLS:
+            raise IqError("control=%r is not available for %d regions here: one of %s" % (control, n, ks.CONTROLS))
     if se and isinstance(samples, str):
         raise IqError(SE_NEEDS_SAMPLES)
     if se and gram != "analytic" and not pairs:
@@ -318,15 +433,19 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
         out["interaction"] = ks.pairs(keep, v, v_empty, v_full, n, weights)
     if se and gram == "analytic":
         out["phi_se"] = ks.phi_se(keep, v, v_empty, v_full, n, paired, gram)[1]
+    if control != "none":
+        out["interaction_cv"], out["interaction_cv_se"], out["control"] = ks.pairs_cv(keep, v, v_empty, v_full, n, paired, control)
     return out
 
 
-def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, pairs=False, se=False):
+def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, pairs=False, se=False,
+         control="none"):
     """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
     sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows};
     ``pairs``: also interaction (n,n), ``pairs`` of the same rows; ``se``: also phi_se (n,) under the analytic Gram matrix and,
-    with ``pairs``, interaction_se (n,n) (``play``).  A ``gram`` outside GRAMS is refused before anything is drawn or run."""
-    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs, se=se)
+    with ``pairs``, interaction_se (n,n); ``control``: also interaction_cv, interaction_cv_se (n,n) and control (``play``).  A
+    ``gram`` outside GRAMS is refused before anything is drawn or run."""
+    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs, se=se, control=control)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):

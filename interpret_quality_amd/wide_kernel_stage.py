@@ -16,6 +16,11 @@ Per selected cloud, under the wide experiment folder of that region count (``exp
     kernelshap/region_shapley_se.npy              (R,) float64   with --se: the standard error of region_shapley_value.npy
     kernelshap/region_interaction_se.npy          (R, R) float64 with --se and --pairs: the standard error of every entry of
                                                   region_interaction.npy (symmetric, zero diagonal)
+    kernelshap/region_interaction_cv.npy          (R, R) float64 with --pairs and --control shift: SHAP-IQ on the rewards less the
+                                                  additive game that spreads v_full - v_empty evenly (wide_kernelshap.pairs_cv;
+                                                  DESIGN.md 5j), beside region_interaction.npy, which is still written
+    kernelshap/region_interaction_cv_se.npy       (R, R) float64 its standard error
+    kernelshap/control.json                       {"control", "ridge", "fold_rows", "paired"} of that estimate
 
 ``--samples`` is the number of rows M (model evaluations; default 1000 (R + 1), stage 1's budget).  The clouds, the FPS centres and
 the region ids are final_wide_shapley.py's (wide_stage.cal_region_id).  The draws after the sizes come from the device sampler
@@ -50,7 +55,9 @@ def kernel_one_cloud(model, data, lbl, region_id, args, cloud=0):
     return kernel_stage.artefacts(wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired,
                                                        coalitions=args.coalitions, draw=args.draw, seed=args.seed, stream=cloud,
                                                        pairs=kernel_stage.wants_pairs(args),
-                                                       **({"se": True} if kernel_stage.wants_se(args) else {})))
+                                                       **({"se": True} if kernel_stage.wants_se(args) else {}),
+                                                       **({"control": kernel_stage.control_of(args)}
+                                                          if kernel_stage.control_of(args) != "none" else {})))
 
 
 def stage1_estimate(result_path, i):
@@ -106,9 +113,11 @@ def make_args(argv=None):
                              "--seed and the cloud's index): any cloud alone, no skip draws")
     kernel_stage.add_pairs_flag(parser)
     kernel_stage.add_se_flag(parser)
+    kernel_stage.add_control_flag(parser, wide_kernelshap.CONTROLS)
     args = wide_stage.parse_wide_args(parser, argv, "final_kernel_shapley.py", samples=False)
     kernel_stage.check_samples(parser, args)
     kernel_stage.check_se(parser, args, "analytic")
+    kernel_stage.check_control(parser, args)
     return args
 
 

@@ -4,6 +4,7 @@ how many rows a usable interaction map needs (not the flagship workload: that is
 
     python tools/bench_kshap_pairs.py [--out profiles/kshap_pairs.json] [--seeds 20] [--runs 5]
     python tools/bench_kshap_pairs.py --se [--out profiles/kshap_pairs_se.json]      the standard errors, see below
+    python tools/bench_kshap_pairs.py --control [--out profiles/kshap_pairs_cv.json] the control variates, see below
 
 Part 1 - time.  PointNet, synthetic cloud 0, (R, M) = (32, 33 000), (128, 129 000) and (1024, 1 025 000), G = 1 game (the cloud's
 label) and G = 10 (labels 0 .. 9 from the same forwards).  ``--runs`` runs each after a warm-up, wall clock around a synchronised
@@ -29,7 +30,13 @@ itself.  There is no rival estimator at equal evaluations: the number says how m
 moment's product over the units' first rows) alternated in one process; reported are the ratio se / pairs of the medians (the
 arithmetic alone says about 1.5: the second product covers half the rows), whether it exceeds 2 beyond the spread, and the
 entry's share of forwards + reduction.  Error: at the same seeds and budgets the pooled z_rms = RMS of (estimate - exact) / se over
-pairs and seeds, the RMS and the mean of se, and the RMS error they should reproduce."""
+pairs and seeds, the RMS and the mean of se, and the RMS error they should reproduce.
+
+``--control`` - the control-variate estimators (``kernelshap.pairs_cv``).  Error: the same seeds and budgets for none (``pairs_se``),
+shift and regression: RMS error, mean se and pooled z_rms.  Time: ``kernelshap.pairs_cv(control="regression")`` - the whole entry, both
+folds: Gram, fit, surrogate, residual SHAP-IQ with its standard error, the host's combination - and ``control="shift"`` against
+``hip_ops.kshap_pairs_se`` of the same build on the same rows, R = 16 / 32 / 64 at 1000 (R + 1) rows, G = 1 and 10, alternated in one
+process; reported are the ratios of the medians and each entry's share of forwards + reduction."""
 import argparse
 import json
 import os
@@ -174,6 +181,76 @@ def _time_se(r, games, runs, block, words, e, e2, fwd, pairs_call, se_call):
             "kshap_pairs_share_of_forwards_plus_reduction": k / (f + k), "eager_block_rows": block}
 
 
+CONTROL_REGIONS = (16, 32, 64)
+
+
+def time_control(r, games, runs, dev):
+    """The --control rows: pairs_cv (regression, shift) and kshap_pairs_se on 1000 (R + 1) paired rows, alternated."""
+    model, data, lbl, rid, args = _setup(r, dev)
+    m = kernelshap.default_samples(r)
+    np.random.seed(1)
+    keep = kernelshap.draw(r, m, True, dev)[0]
+    classes = None if games == 1 else list(range(games))
+    forwards = lambda: kernelshap.rewards(model, data, None if classes else lbl, rid, args, keep, classes=classes)      # noqa: E731
+    kernelshap.rewards(model, data, lbl, rid, args, keep[:4096].contiguous())
+    fwd = []
+    for _ in range(runs):
+        t, (v, v_full, v_empty) = _wall(forwards)
+        fwd.append(t)
+    v2, v0, v1 = kernelshap.games(keep, v, v_empty, v_full)
+    calls = {"kshap_pairs_se": lambda: hip_ops.kshap_pairs_se(keep, v2, v0, v1 - v0, r, True),
+             "pairs_cv_shift": lambda: kernelshap.pairs_cv(keep, v2, v0, v1, r, True, "shift"),
+             "pairs_cv_regression": lambda: kernelshap.pairs_cv(keep, v2, v0, v1, r, True, "regression")}
+    times = {name: [] for name in calls}
+    for fn in calls.values():
+        fn()
+    for _ in range(runs):                                                       # alternated in one process
+        for name, fn in calls.items():
+            times[name].append(_wall(fn)[0])
+    f = float(np.median(fwd))
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    out = {"num_regions": r, "rows": int(len(keep)), "unknowns": kernelshap.pair_features(r), "games": games, "pointnet_forwards": _spread(fwd)}
+    for name, t in times.items():
+        out[name] = _spread(t)
+        out[name + "_share_of_forwards_plus_reduction"] = med[name] / (f + med[name])
+    out["regression_over_pairs_se"] = med["pairs_cv_regression"] / med["kshap_pairs_se"]
+    out["shift_over_pairs_se"] = med["pairs_cv_shift"] / med["kshap_pairs_se"]
+    out["regression_costs_more_than_the_forwards_it_serves"] = bool(med["pairs_cv_regression"] > f)
+    return out
+
+
+def control_table(n, seeds, dev):
+    """``error_table``'s seeds and budgets for none / shift / regression: the error, the bars and their calibration."""
+    model, data, lbl, rid, args = _setup(n, dev)
+    table = exact.value_table(model, data, lbl, rid, args)
+    ends = table[[0, table.numel() - 1]].cpu().numpy()
+    pr = hip_ops.all_pairs(n)
+    want = hip_ops.exact_interactions(table).cpu().numpy().mean(axis=1)
+    most = max(BUDGETS) * (n + 1)
+    controls = ("none", "shift", "regression")
+    err2, se1, z2 = ({(c, b): [] for c in controls for b in BUDGETS} for _ in range(3))
+    for seed in range(seeds):
+        np.random.seed(1000 + seed)
+        keep, _ = kernelshap.draw(n, most, True, dev)
+        for b in BUDGETS:
+            rows = keep[:b * (n + 1) // 2 * 2].contiguous()
+            v = table.index_select(0, rows).contiguous()
+            for c in controls:
+                if c == "none":
+                    got, se = kernelshap.pairs_se(rows, v, float(ends[0]), float(ends[1]), n)
+                else:
+                    got, se, _ = kernelshap.pairs_cv(rows, v, float(ends[0]), float(ends[1]), n, True, c)
+                got, se = got[pr[:, 0], pr[:, 1]], se[pr[:, 0], pr[:, 1]]
+                err2[c, b].append(float(((got - want) ** 2).mean()))
+                se1[c, b].append(float(se.mean()))
+                z2[c, b].append(float((((got - want) / se) ** 2).mean()))
+    return {"model": "pointnet", "cloud": "synthetic_00", "num_regions": n, "pairs": int(len(pr)), "seeds": seeds,
+            "exact_index_rms": float(np.sqrt((want ** 2).mean())),
+            "budgets": [{"permutations": b, "rows": b * (n + 1) // 2 * 2,
+                         **{c: {"rms_error": float(np.sqrt(np.mean(err2[c, b]))), "mean_se": float(np.mean(se1[c, b])),
+                                "z_rms": float(np.sqrt(np.mean(z2[c, b])))} for c in controls}} for b in BUDGETS]}
+
+
 def calibration_table(n, seeds, dev):
     """``error_table``'s seeds and budgets through kernelshap.pairs_se: the error, and what the bars say it should be."""
     model, data, lbl, rid, args = _setup(n, dev)
@@ -227,21 +304,30 @@ def error_table(n, seeds, dev):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--se", action="store_true", help="time kshap_pairs_se and measure the calibration of its bars (profiles/kshap_pairs_se.json)")
-    ap.add_argument("--out", default=None, help="default profiles/kshap_pairs.json, with --se profiles/kshap_pairs_se.json")
+    ap.add_argument("--control", action="store_true", help="the control-variate estimators: error table and time (profiles/kshap_pairs_cv.json)")
+    ap.add_argument("--out", default=None, help="default profiles/kshap_pairs.json, with --se profiles/kshap_pairs_se.json, with --control "
+                                                "profiles/kshap_pairs_cv.json")
     ap.add_argument("--seeds", type=int, default=20)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--block", type=int, default=1 << 16, help="rows per block of the eager form")
     ap.add_argument("--error_regions", type=int, default=16)
     ap.add_argument("--games", type=int, nargs="+", default=[1, 10])
     args = ap.parse_args(argv)
-    args.out = args.out or os.path.join(REPO, "profiles", "kshap_pairs_se.json" if args.se else "kshap_pairs.json")
+    if args.se and args.control:
+        ap.error("--se and --control are two runs")
+    args.out = args.out or os.path.join(REPO, "profiles", "kshap_pairs_cv.json" if args.control else
+                                        "kshap_pairs_se.json" if args.se else "kshap_pairs.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_kshap_pairs.py needs a GPU: a time taken elsewhere says nothing about the MI355X")
     dev = torch.device("cuda:0")
     with torch.no_grad():
-        res = {"device": torch.cuda.get_device_name(0),
-               "time": [time_shape(r, m, g, args.runs, args.block, dev, args.se) for r, m in SHAPES for g in args.games],
-               "error": (calibration_table if args.se else error_table)(args.error_regions, args.seeds, dev)}
+        if args.control:
+            timed = [time_control(r, g, args.runs, dev) for r in CONTROL_REGIONS for g in args.games]
+            errors = control_table(args.error_regions, args.seeds, dev)
+        else:
+            timed = [time_shape(r, m, g, args.runs, args.block, dev, args.se) for r, m in SHAPES for g in args.games]
+            errors = (calibration_table if args.se else error_table)(args.error_regions, args.seeds, dev)
+        res = {"device": torch.cuda.get_device_name(0), "time": timed, "error": errors}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
