@@ -222,12 +222,10 @@ Scratch carve(void* base, long long M, int n, int G) {
     return s;
 }
 
-bool shape_ok(long long M, int n, int G) { return M >= 1 && M <= (1ll << 30) && n >= 2 && n <= kMaxN && G >= 1 && G <= 65535; }
-
 }  // namespace
 
 extern "C" size_t iq_kshap_scratch_bytes(int M, int n, int G) {
-    return shape_ok(M, n, G) ? carve(nullptr, M, n, G).bytes : 0;
+    return iq::kshap::rows_ok(M, n, G, kMaxN) ? carve(nullptr, M, n, G).bytes : 0;
 }
 
 extern "C" int iq_kshap_keep_masks(const int32_t* orders, const int32_t* sizes, uint64_t* keep, int S, int n, int paired,
@@ -243,11 +241,10 @@ extern "C" int iq_kshap_keep_masks(const int32_t* orders, const int32_t* sizes, 
 
 extern "C" int iq_kshap_accum(const uint64_t* keep, const float* v, const double* v0, const double* weights, int M, int n, int G,
                               double* A, double* b, double* wsum, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
-    IQ_REQUIRE(shape_ok(M, n, G), "iq_kshap_accum: M=%d, n=%d, G=%d (1 <= M <= 2^30, 2 <= n <= %d, 1 <= G <= 65535)", M, n, G, kMaxN);
+    IQ_REQUIRE(iq::kshap::rows_ok(M, n, G, kMaxN), "iq_kshap_accum: M=%d, n=%d, G=%d (1 <= M <= 2^30, 2 <= n <= %d, 1 <= G <= 65535)", M, n, G, kMaxN);
     IQ_REQUIRE(keep && v && v0 && A && b && wsum && scratch, "iq_kshap_accum: null pointer");
     const Scratch s = carve(scratch, M, n, G);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_accum: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
+    IQ_TRY(iq::kshap::scratch_ok("iq_kshap_accum", scratch, scratch_bytes, s.bytes));
     const Chunks ch = chunks_of(M);
     hipStream_t st = iq::as_stream(stream);
     const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);

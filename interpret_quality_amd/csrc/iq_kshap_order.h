@@ -1,8 +1,12 @@
 // The summation order of the regression estimator's moments, written once for the narrow kernels (iq_kshap.hip: a row is one
 // uint64) and the wide ones (iq_kshap_wide.hip: a row is W words): the cut of the rows into chunks, the moment b of one chunk,
-// a chunk's sum of weights and the fold of the chunks.  include/iq.h, "The regression (KernelSHAP) estimator", has the contract.
+// a chunk's sum of weights and the fold of the chunks; then what the estimators built on them (iq_kshap_pairs.hip, iq_kshap_paircv.hip
+// and the standard errors) share: a row's size, a chunk's scalar sum, the kernels over the iid units, the fold of the moments and
+// the host's checks.  include/iq.h, "The regression (KernelSHAP) estimator", has the contract.
 #pragma once
 #include "iq_common.h"
+
+#include <cstdint>
 
 namespace iq {
 namespace kshap {
@@ -34,6 +38,19 @@ __host__ __device__ inline Chunks pair_chunks_of(long long M, int R) {
     return {(int)((tiles + per - 1) / per), (int)per};
 }
 
+// the bits of word `word` of a row that exist: all 64, or the low R - 64 word of the last word
+__device__ __forceinline__ unsigned long long live_mask(int word, int R) {
+    const int bits = R - 64 * word;
+    return bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
+}
+
+// the number of regions below R that a row of W words keeps
+__device__ __forceinline__ int row_size(const unsigned long long* __restrict__ row, int W, int R) {
+    int s = 0;
+    for (int w = 0; w < W; ++w) s += __popcll(row[w] & live_mask(w, R));
+    return s;
+}
+
 // The workgroup's values x, one per thread, added in thread order through the kThreads words of `sh` (free to be overwritten:
 // every thread is past its last read of them); the sum is thread 0's return value.
 template <typename T>
@@ -50,11 +67,17 @@ __device__ __forceinline__ T sum_threads_in_order(T* sh, T x) {
 // live row, on a workgroup of kThreads: lane i of wave q adds rows 64 q .. 64 q + 63 of every tile in row order, then the four
 // waves are added as ((0 + 1) + 2) + 3.  Every LDS read of the inner loop is a broadcast.  Threads t < 64 write out[t] when
 // t < live_bits (the regions of this word that exist).  With wpart the workgroup also leaves the chunk's sum of weights there: per
-// thread over its rows t, t + 256, ... of the chunk, then the 256 threads in index order.
-template <typename RowValue>
+// thread over its rows t, t + 256, ... of the chunk, then the 256 threads in index order.  What lane i sums over is member(word, i):
+// bit i of the word, or whatever else a lane stands for (iq_kshap_paircv.hip: a feature of the surrogate).
+struct BitOfLane {
+    __device__ __forceinline__ bool operator()(unsigned long long word, int lane) const { return (word >> lane) & 1ull; }
+};
+
+template <typename RowValue, typename Member = BitOfLane>
 __device__ __forceinline__ void moment_chunk_of(const unsigned long long* __restrict__ keep, int W, int word, RowValue value,
                                                 const double* __restrict__ weights, long long M, int tiles_per, int chunk,
-                                                double* __restrict__ out, int live_bits, double* __restrict__ wpart) {
+                                                double* __restrict__ out, int live_bits, double* __restrict__ wpart,
+                                                Member member = Member()) {
     __shared__ unsigned long long sh_keep[kTile];
     __shared__ double sh_d[kTile];
     __shared__ double sh_fold[4][64];
@@ -70,7 +93,7 @@ __device__ __forceinline__ void moment_chunk_of(const unsigned long long* __rest
         wacc += w;
         __syncthreads();
 #pragma unroll 8
-        for (int r = q * 64; r < q * 64 + 64; ++r) acc += (sh_keep[r] >> lane) & 1ull ? sh_d[r] : 0.0;
+        for (int r = q * 64; r < q * 64 + 64; ++r) acc += member(sh_keep[r], lane) ? sh_d[r] : 0.0;
         __syncthreads();
     }
     sh_fold[q][lane] = acc;
@@ -100,6 +123,98 @@ __device__ __forceinline__ double fold_chunks(const double* __restrict__ p, size
 // wsum: the chunks' sums of weights in chunk order; without weights it is M.
 __device__ __forceinline__ double fold_wsum(const double* __restrict__ partW, int weighted, long long M, int nchunk) {
     return weighted ? fold_chunks(partW, 1, nchunk) : (double)M;
+}
+
+// One chunk's sum of value(m) over its rows m < M, on a workgroup of kThreads: per thread over its rows t, t + 256, ... of the chunk,
+// then the 256 threads in index order (the rule of a chunk's sum of weights); the sum is thread 0's return value.
+template <typename RowValue>
+__device__ __forceinline__ double scalar_chunk_of(RowValue value, long long M, int tiles_per, int chunk) {
+    __shared__ double sh[kThreads];
+    const long long row0 = (long long)chunk * tiles_per * kTile;
+    double acc = 0.0;
+    for (int tile = 0; tile < tiles_per; ++tile) {
+        const long long m = row0 + (long long)tile * kTile + threadIdx.x;
+        if (m < M) acc += value(m);
+    }
+    return sum_threads_in_order(sh, acc);
+}
+
+// The two kernels over the iid units u of a standard error (a unit's first row starts at keep + u * stride words).  `unit` holds
+// kArrays arrays of U values per game; x0 is game 0's array of the value summed, game g's is x0 + kArrays g U.
+// Grid (chunk of chunks_of(U), word, game): part[(g * nchunk + chunk) * R + 64 word + i] = the chunk's sum of x_u z_ui in
+// moment_chunk_of's order.
+template <int kArrays>
+__global__ __launch_bounds__(kThreads) void unit_moment_kernel(const unsigned long long* __restrict__ keep, const double* __restrict__ x0,
+                                                               long long U, int R, int stride, int tiles_per, double* __restrict__ part) {
+    const int chunk = blockIdx.x, word = blockIdx.y, g = blockIdx.z;
+    const double* x = x0 + (size_t)kArrays * g * U;
+    moment_chunk_of(
+        keep, stride, word, [=](long long u, double) { return x[u]; }, nullptr, U, tiles_per, chunk,
+        part + ((size_t)g * gridDim.x + chunk) * R + 64 * word, min(64, R - 64 * word), nullptr);
+}
+
+// Grid (chunk of chunks_of(U), game): part[g * nchunk + chunk] = the chunk's sum of x_u by scalar_chunk_of.
+template <int kArrays>
+__global__ __launch_bounds__(kThreads) void unit_scalar_kernel(const double* __restrict__ x0, long long U, int tiles_per,
+                                                               double* __restrict__ part) {
+    const int chunk = blockIdx.x, g = blockIdx.y;
+    const double* x = x0 + (size_t)kArrays * g * U;
+    const double s = scalar_chunk_of([=](long long u) { return x[u]; }, U, tiles_per, chunk);
+    if (threadIdx.x == 0) part[(size_t)g * gridDim.x + chunk] = s;
+}
+
+// One thread per output: the chunks' partials added in chunk order.  Entries [0, G R): L; with kScalars then G of A; the last one wsum.
+template <bool kScalars>
+__global__ __launch_bounds__(kThreads) void fold_moments_kernel(const double* __restrict__ partL, const double* __restrict__ partA,
+                                                                const double* __restrict__ partW, int weighted, long long M, int R, int G,
+                                                                int nchunk, double* __restrict__ L, double* __restrict__ A,
+                                                                double* __restrict__ wsum) {
+    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x, nl = (long long)G * R, na = kScalars ? G : 0;
+    if (e < nl) {
+        const long long g = e / R, i = e % R;
+        L[e] = fold_chunks(partL + (size_t)g * nchunk * R + i, R, nchunk);
+    } else if (e < nl + na) {
+        const long long g = e - nl;
+        A[g] = fold_chunks(partA + (size_t)g * nchunk, 1, nchunk);
+    } else if (e == nl + na) {
+        *wsum = fold_wsum(partW, weighted, M, nchunk);
+    }
+}
+
+// The variance of an estimate (1 / M) sum_u x_u from S1 = sum_u x_u and S2 = sum_u x_u^2 over the U iid units of M rows, every
+// operation rounded on its own.
+__device__ __forceinline__ double unit_variance(double s1, double s2, long long U, long long M) {
+#pragma clang fp contract(off)
+    const double units = (double)U, rows = (double)M;
+    return ((units / (units - 1.0)) * (s2 - s1 * s1 / units)) / (rows * rows);
+}
+
+// ---- the host's side ------------------------------------------------------------------------------------------------------------
+
+// the units of M rows; 0 where the rows do not make at least two whole units
+inline long long units_of(long long M, int paired) {
+    if (paired && (M & 1)) return 0;
+    const long long U = paired ? M / 2 : M;
+    return U >= 2 ? U : 0;
+}
+
+// 2 H_{R-1}, float64, the harmonic sum ascending: summed on the host, passed to the kernels by value
+inline double two_harmonic(int R) {
+    double h = 0.0;
+    for (int k = 1; k < R; ++k) h += 1.0 / (double)k;
+    return 2.0 * h;
+}
+
+// the rows, regions and games an entry of the family takes; max_r: IQ_MAX_REGIONS or IQ_MAX_WIDE_REGIONS
+inline bool rows_ok(long long M, int R, int G, int max_r) {
+    return M >= 1 && M <= (1ll << 30) && R >= 2 && R <= max_r && G >= 1 && G <= 65535;
+}
+
+// IQ_OK when the caller's scratch holds `need` bytes and is 8-byte aligned
+inline int scratch_ok(const char* name, const void* scratch, size_t got, size_t need) {
+    if (got < need || ((uintptr_t)scratch & 7))
+        return fail(IQ_EWORKSPACE, "%s: scratch of %zu bytes (8-byte aligned) needed, got %zu", name, need, got);
+    return IQ_OK;
 }
 
 }  // namespace kshap

@@ -16,7 +16,7 @@
 // One stream, every launch in a fixed order, every element owned by one thread, no floating-point atomics, no grid that depends on
 // the data: two calls give the same bits, a game's bits depend neither on G nor on a neighbouring game's rewards.
 #include "iq_common.h"
-#include "iq_kshap_order.h"
+#include "iq_kshap_block.h"
 
 // every sum is a chain of individually rounded operations: no fused multiply-add
 #pragma clang fp contract(off)
@@ -25,22 +25,19 @@ namespace {
 
 using iq::kshap::Chunks;
 using iq::kshap::chunks_of;
+using iq::kshap::kBlockElems;
 using iq::kshap::kThreads;
 using iq::kshap::kTile;
+using iq::kshap::live_mask;
+using iq::kshap::rows_ok;
 
 constexpr int kMaxR = IQ_MAX_REGIONS;
 constexpr int kMaxD = kMaxR + kMaxR * (kMaxR - 1) / 2;      // 2080
-constexpr int kBlock = 64;                                  // a block of the Gram matrix: 64 features against 64
-constexpr int kBlockElems = kBlock * kBlock;
 constexpr int kPanel = 32;                                  // columns of a Cholesky panel
 constexpr int kPanelLd = kPanel + 1;
 constexpr int kTrsmThreads = 128;
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 __host__ __device__ inline int features_of(int R) { return R + R * (R - 1) / 2; }
-
-__device__ __forceinline__ unsigned long long low_bits(int R) { return R >= 64 ? ~0ull : (1ull << R) - 1ull; }
 
 // fm_a: bit a for a single; bits i and j of the pair (i < j) number a - R in row-major order.  a < d.
 __device__ __forceinline__ unsigned long long feature_mask(int a, int R) {
@@ -53,78 +50,42 @@ __device__ __forceinline__ unsigned long long feature_mask(int a, int R) {
     return (1ull << i) | (1ull << (i + 1 + p));
 }
 
-// Grid (block): the workgroup owns block (bi, bj), bi <= bj, blk = bj (bj + 1) / 2 + bi, of the Gram matrix and walks every row;
-// its four waves take rows 64 q .. 64 q + 63 of every 256-row tile, each wave 4 x 4 tiles of 16 x 16.  Operands are selects on the
-// staged row words: (keep & fm) == fm ? 1.0 : 0.0.  Bits at or above R are masked when a tile is staged, rows at or above M are
-// staged as the empty set, which holds no feature.  Features at or above d get the mask 0 and are never written; tiles of a block
-// that lie past d, or below the diagonal of a diagonal block, are skipped.  Sums of ones: exact in any order.
+// The rows of block_product for a block of the Gram matrix: a staged row is its word, bits at or above R masked, a row at or above
+// M the empty set, which holds no feature; an operand is a select, (word & fm) == fm ? 1.0 : 0.0, on this lane's features.
+struct GramRows {
+    unsigned long long* sh_k;
+    const unsigned long long* keep;
+    long long M;
+    unsigned long long live;
+    unsigned long long ma[4], mb[4];             // this lane's features: row 16 a + col of the block, column 16 a + col
+    __device__ __forceinline__ void stage(int t, long long m) const { sh_k[t] = m < M ? keep[m] & live : 0ull; }
+    __device__ __forceinline__ void operands(int r, int, double (&fa)[4], double (&fb)[4]) const {
+        const unsigned long long w = sh_k[r];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            fa[a] = (w & ma[a]) == ma[a] ? 1.0 : 0.0;                    // A[i = 16 a + col][k]
+            fb[a] = (w & mb[a]) == mb[a] ? 1.0 : 0.0;                    // B[k][j = 16 a + col]
+        }
+    }
+};
+
+// Grid (block): the workgroup owns block (bi, bj), bi <= bj, blk = bj (bj + 1) / 2 + bi, of the Gram matrix and walks every row
+// (iq_kshap_block.h: block_product, shared with the pairwise product Q).  Features at or above d get the mask 0 and are never
+// written; a skipped tile of a diagonal block is written by its mirror image.  Sums of ones: exact in any order.
 __global__ __launch_bounds__(kThreads, 2) void kshap_paircv_gram_kernel(const unsigned long long* __restrict__ keep, long long M, int R,
                                                                         int d, double* __restrict__ gram) {
     __shared__ unsigned long long sh_k[kTile];
     __shared__ double sh_acc[kBlockElems];
-    const int t = threadIdx.x, lane = t & 63, q = t >> 6, col = lane & 15, kk = lane >> 4;
-    const int blk = blockIdx.x;
-    int bj = 0;
-    while ((bj + 1) * (bj + 2) / 2 <= blk) ++bj;
-    const int bi = blk - bj * (bj + 1) / 2;
-    const unsigned long long live = low_bits(R);
-    const int na = min(4, (d - 64 * bi + 15) >> 4), nb = min(4, (d - 64 * bj + 15) >> 4);
-    unsigned tiles_live = 0;                     // bit 4 a + b: tile (a, b) of the block is computed
-    for (int a = 0; a < na; ++a)
-        for (int b = 0; b < nb; ++b)
-            if (bi != bj || b >= a) tiles_live |= 1u << (4 * a + b);
-    unsigned long long ma[4], mb[4];             // this lane's features: row 16 a + col of the block, column 16 a + col
+    const int t = threadIdx.x, col = t & 15;
+    const auto [bi, bj] = iq::kshap::block_of(blockIdx.x);
+    GramRows rows{sh_k, keep, M, live_mask(0, R)};
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int fa = 64 * bi + 16 * a + col, fb = 64 * bj + 16 * a + col;
-        ma[a] = fa < d ? feature_mask(fa, R) : 0ull;
-        mb[a] = fb < d ? feature_mask(fb, R) : 0ull;
+        rows.ma[a] = fa < d ? feature_mask(fa, R) : 0ull;
+        rows.mb[a] = fb < d ? feature_mask(fb, R) : 0ull;
     }
-
-    f64x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-    const long long tiles = (M + kTile - 1) / kTile;
-    for (long long tile = 0; tile < tiles; ++tile) {
-        const long long m = tile * kTile + t;
-        sh_k[t] = m < M ? keep[m] & live : 0ull;
-        __syncthreads();
-#pragma unroll 2
-        for (int step = 0; step < 16; ++step) {
-            const unsigned long long w = sh_k[q * 64 + step * 4 + kk];      // this lane's row of the four: k = lane >> 4
-            double fa[4], fb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                fa[a] = (w & ma[a]) == ma[a] ? 1.0 : 0.0;                    // A[i = 16 a + col][k]
-                fb[a] = (w & mb[a]) == mb[a] ? 1.0 : 0.0;                    // B[k][j = 16 a + col]
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    if ((tiles_live >> (4 * a + b)) & 1u)
-                        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // the four waves in wave order; C/D of the f64 form: column = lane & 15, row = (lane >> 4) + 4 reg
-    for (int turn = 0; turn < 4; ++turn) {
-        if (q == turn) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int at = (16 * a + kk + 4 * reg) * kBlock + 16 * b + col;
-                        sh_acc[at] = turn == 0 ? acc[a][b][reg] : sh_acc[at] + acc[a][b][reg];
-                    }
-        }
-        __syncthreads();
-    }
+    iq::kshap::block_product(rows, bi, bj, d, 0, (int)((M + kTile - 1) / kTile), sh_acc);
     for (int e = t; e < kBlockElems; e += kThreads) {
         const int r = e >> 6, c = e & 63, gi = 64 * bi + r, gj = 64 * bj + c;
         if (gi >= d || gj >= d) continue;
@@ -136,35 +97,20 @@ __global__ __launch_bounds__(kThreads, 2) void kshap_paircv_gram_kernel(const un
 }
 
 // Grid (chunk of chunks_of(M), block of 64 features, game): part[(g * nchunk + chunk) * d + a] = the chunk's sum of
-// f_a(S_m) ((double)v_m - v0) in the order of moment_chunk_of: lane a of wave q adds rows 64 q .. 64 q + 63 of every tile in row
-// order, then the four waves are added as ((0 + 1) + 2) + 3.
+// f_a(S_m) ((double)v_m - v0): moment_chunk_of on the one word of a narrow row, lane a standing for feature a - the row is a member
+// when it holds fm_a (a feature mask has no bit at or above R, so the row's own are not masked).  Lanes at or above d sum every row
+// (their mask is 0) and are not written.
 __global__ __launch_bounds__(kThreads) void kshap_paircv_rhs_kernel(const unsigned long long* __restrict__ keep, const float* __restrict__ v,
                                                                     const double* __restrict__ v0, long long M, int R, int d,
                                                                     int tiles_per, double* __restrict__ part) {
-    __shared__ unsigned long long sh_keep[kTile];
-    __shared__ double sh_d[kTile];
-    __shared__ double sh_fold[4][64];
-    const int t = threadIdx.x, lane = t & 63, q = t >> 6;
-    const int chunk = blockIdx.x, a = 64 * blockIdx.y + lane, g = blockIdx.z;
+    const int chunk = blockIdx.x, a0 = 64 * blockIdx.y, a = a0 + (threadIdx.x & 63), g = blockIdx.z;
     const float* vg = v + (size_t)g * M;
     const double base = v0[g];
-    const unsigned long long live = low_bits(R);
     const unsigned long long fm = a < d ? feature_mask(a, R) : 0ull;
-    const long long row0 = (long long)chunk * tiles_per * kTile;
-    double acc = 0.0;
-    for (int tile = 0; tile < tiles_per; ++tile) {
-        const long long m = row0 + (long long)tile * kTile + t;
-        const bool in = m < M;
-        sh_keep[t] = in ? keep[m] & live : 0ull;
-        sh_d[t] = in ? (double)vg[m] - base : 0.0;
-        __syncthreads();
-#pragma unroll 8
-        for (int r = q * 64; r < q * 64 + 64; ++r) acc += (sh_keep[r] & fm) == fm ? sh_d[r] : 0.0;
-        __syncthreads();
-    }
-    sh_fold[q][lane] = acc;
-    __syncthreads();
-    if (t < 64 && a < d) part[((size_t)g * gridDim.x + chunk) * d + a] = ((sh_fold[0][t] + sh_fold[1][t]) + sh_fold[2][t]) + sh_fold[3][t];
+    iq::kshap::moment_chunk_of(
+        keep, 1, 0, [=](long long m, double) { return (double)vg[m] - base; }, nullptr, M, tiles_per, chunk,
+        part + ((size_t)g * gridDim.x + chunk) * d + a0, min(64, d - a0), nullptr,
+        [fm](unsigned long long word, int) { return (word & fm) == fm; });
 }
 
 // One thread per entry of X ((G + 1, d)): rows 0 .. G-1 the chunks' partials added in chunk order, row G the ones vector.
@@ -378,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void kshap_paircv_surrogate_kernel(const 
     __syncthreads();
     const long long m = (long long)blockIdx.x * kThreads + t;
     if (m >= M) return;
-    const unsigned long long k = keep[m] & low_bits(R);
+    const unsigned long long k = keep[m] & live_mask(0, R);
     double acc = 0.0;
     for (int i = 0; i < R; ++i)
         if ((k >> i) & 1ull) acc += sh_beta[i];
@@ -401,11 +347,7 @@ __global__ __launch_bounds__(kThreads) void kshap_paircv_shift_kernel(const unsi
     const long long m = (long long)blockIdx.x * kThreads + threadIdx.x;
     const int g = blockIdx.y;
     if (m >= M) return;
-    int s = 0;
-    for (int w = 0; w < W; ++w) {
-        const int bits = R - 64 * w;
-        s += __popcll(keep[(size_t)m * W + w] & (bits >= 64 ? ~0ull : (1ull << bits) - 1ull));
-    }
+    const int s = iq::kshap::row_size(keep + (size_t)m * W, W, R);
     out[(size_t)g * M + m] = ((double)v[(size_t)g * M + m] - v0[g]) - (delta[g] * (double)s) / (double)R;
 }
 
@@ -426,8 +368,6 @@ FitScratch carve_fit(void* base, long long M, int R, int G) {
     return s;
 }
 
-bool narrow_ok(long long M, int R, int G) { return M >= 1 && M <= (1ll << 30) && R >= 2 && R <= kMaxR && G >= 1 && G <= 65535; }
-
 unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
@@ -435,25 +375,24 @@ unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThrea
 extern "C" int iq_kshap_pair_features(int R) { return R >= 2 && R <= kMaxR ? features_of(R) : 0; }
 
 extern "C" int iq_kshap_pair_gram(const uint64_t* keep, int M, int R, double* gram, iq_stream_t stream) {
-    IQ_REQUIRE(narrow_ok(M, R, 1), "iq_kshap_pair_gram: M=%d, R=%d (1 <= M <= 2^30, 2 <= R <= %d)", M, R, kMaxR);
+    IQ_REQUIRE(rows_ok(M, R, 1, kMaxR), "iq_kshap_pair_gram: M=%d, R=%d (1 <= M <= 2^30, 2 <= R <= %d)", M, R, kMaxR);
     IQ_REQUIRE(keep && gram, "iq_kshap_pair_gram: null pointer");
-    const int d = features_of(R), nb = (d + kBlock - 1) / kBlock;
-    IQ_LAUNCH(kshap_paircv_gram_kernel, dim3(nb * (nb + 1) / 2), dim3(kThreads), 0, iq::as_stream(stream),
+    const int d = features_of(R);
+    IQ_LAUNCH(kshap_paircv_gram_kernel, dim3(iq::kshap::blocks_of(d)), dim3(kThreads), 0, iq::as_stream(stream),
               reinterpret_cast<const unsigned long long*>(keep), (long long)M, R, d, gram);
     return IQ_OK;
 }
 
-extern "C" size_t iq_kshap_pair_fit_scratch_bytes(int M, int R, int G) { return narrow_ok(M, R, G) ? carve_fit(nullptr, M, R, G).bytes : 0; }
+extern "C" size_t iq_kshap_pair_fit_scratch_bytes(int M, int R, int G) { return rows_ok(M, R, G, kMaxR) ? carve_fit(nullptr, M, R, G).bytes : 0; }
 
 extern "C" int iq_kshap_pair_fit(const double* gram, const uint64_t* keep, const float* v, const double* v0, const double* delta,
                                  double ridge, int M, int R, int G, double* beta, double* solves, int32_t* status, void* scratch,
                                  size_t scratch_bytes, iq_stream_t stream) {
-    IQ_REQUIRE(narrow_ok(M, R, G), "iq_kshap_pair_fit: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
+    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "iq_kshap_pair_fit: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
     IQ_REQUIRE(ridge >= 0.0, "iq_kshap_pair_fit: ridge must be a number >= 0");
     IQ_REQUIRE(gram && keep && v && v0 && delta && beta && status && scratch, "iq_kshap_pair_fit: null pointer");
     const FitScratch s = carve_fit(scratch, M, R, G);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_pair_fit: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
+    IQ_TRY(iq::kshap::scratch_ok("iq_kshap_pair_fit", scratch, scratch_bytes, s.bytes));
     hipStream_t st = iq::as_stream(stream);
     const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
     const int d = features_of(R);
@@ -483,7 +422,7 @@ extern "C" int iq_kshap_pair_fit(const double* gram, const uint64_t* keep, const
 
 extern "C" int iq_kshap_pair_surrogate(const uint64_t* keep, const double* beta, const float* v, const double* v0, int M, int R, int G,
                                        double* out_g, double* out_t, iq_stream_t stream) {
-    IQ_REQUIRE(narrow_ok(M, R, G), "iq_kshap_pair_surrogate: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G,
+    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "iq_kshap_pair_surrogate: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G,
                kMaxR);
     IQ_REQUIRE(keep && beta && (out_g || out_t) && (!out_t || (v && v0)), "iq_kshap_pair_surrogate: null pointer");
     IQ_LAUNCH(kshap_paircv_surrogate_kernel, dim3(blocks_for(M), G), dim3(kThreads), 0, iq::as_stream(stream),
@@ -493,7 +432,7 @@ extern "C" int iq_kshap_pair_surrogate(const uint64_t* keep, const double* beta,
 
 extern "C" int iq_kshap_pair_shift_terms(const uint64_t* keep, const float* v, const double* v0, const double* delta, int M, int R, int G,
                                          double* t, iq_stream_t stream) {
-    IQ_REQUIRE(M >= 1 && M <= (1 << 30) && R >= 2 && R <= IQ_MAX_WIDE_REGIONS && G >= 1 && G <= 65535,
+    IQ_REQUIRE(rows_ok(M, R, G, IQ_MAX_WIDE_REGIONS),
                "iq_kshap_pair_shift_terms: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, IQ_MAX_WIDE_REGIONS);
     IQ_REQUIRE(keep && v && v0 && delta && t, "iq_kshap_pair_shift_terms: null pointer");
     IQ_LAUNCH(kshap_paircv_shift_kernel, dim3(blocks_for(M), G), dim3(kThreads), 0, iq::as_stream(stream),

@@ -8,45 +8,38 @@
 //
 // Q is the hot part, an R x R x M product over 0/1 rows, on v_mfma_f64_16x16x4_f64.  A workgroup owns one 64 x 64 block of Q on or
 // above the diagonal (word bi of the rows against word bj), one chunk of rows and one game; its four waves take rows
-// 64 q .. 64 q + 63 of every 256-row tile, each wave 4 x 4 tiles of 16 x 16 in 128 accumulator registers.  Operands are made in
-// registers from the staged words: A = bit ? e_m : 0.0 with e_m = d_m gamma_s, B = bit ? 1.0 : 0.0 - selects, never a product, so
-// a row's e_m reaches only the pairs the row holds.  Ragged R and ragged M are zero operands (bits at or above R are masked when
-// the tile is staged, rows at or above M are staged as 0); tiles of a block that lie past R, or below the diagonal of a diagonal
-// block, are skipped.  The rows' sizes are counted once, by a kernel of their own, into scratch: 136 blocks at R = 1024 would
-// otherwise each re-read every word of every row.
+// 64 q .. 64 q + 63 of every 256-row tile (iq_kshap_block.h: block_product, shared with the surrogate's Gram matrix).  Operands are
+// made in registers from the staged words: A = bit ? e_m : 0.0 with e_m = d_m gamma_s, B = bit ? 1.0 : 0.0 - selects, never a
+// product, so a row's e_m reaches only the pairs the row holds.  Ragged R and ragged M are zero operands (bits at or above R are
+// masked when the tile is staged, rows at or above M are staged as 0).  The rows' sizes are counted once, by a kernel of their own,
+// into scratch: 136 blocks at R = 1024 would otherwise each re-read every word of every row.
 //
-// Order: rows in row order within a wave (four rows per MFMA, the instruction's own fixed order within them), the four waves as
-// ((0 + 1) + 2) + 3 through LDS, the chunks - pair_chunks_of(M, R), a function of (M, R) alone - in chunk order by the assemble
-// kernel.  L, A and W_sum take the order of the regression estimator's moments (iq_kshap_order.h: moment_chunk_of,
-// sum_threads_in_order, fold_chunks, fold_wsum) on chunks_of(M).  No floating-point atomics; a game's sums never meet another's.
+// Order: block_product's within a chunk, the chunks - pair_chunks_of(M, R), a function of (M, R) alone - in chunk order by the
+// assemble kernel.  L, A and W_sum take the order of the regression estimator's moments (iq_kshap_order.h: moment_chunk_of,
+// scalar_chunk_of, fold_moments_kernel) on chunks_of(M).  No floating-point atomics; a game's sums never meet another's.
 //
 // iq_kshap_pairs_se (below the assemble kernel; include/iq.h, "Standard errors of the sampled estimates") adds the
 // standard error of every entry from the second moment of the same rows: the same product body once more, over the iid units.
 #include "iq_common.h"
-#include "iq_kshap_order.h"
+#include "iq_kshap_block.h"
 
 // every sum and the assembly of I_ij are chains of individually rounded operations: no fused multiply-add
 #pragma clang fp contract(off)
 
 namespace {
 
+using iq::kshap::blocks_of;
 using iq::kshap::Chunks;
 using iq::kshap::chunks_of;
+using iq::kshap::kBlock;
+using iq::kshap::kBlockElems;
 using iq::kshap::kThreads;
 using iq::kshap::kTile;
+using iq::kshap::live_mask;
 using iq::kshap::pair_chunks_of;
+using iq::kshap::rows_ok;
 
 constexpr int kMaxR = IQ_MAX_WIDE_REGIONS;
-constexpr int kBlock = 64;                       // a block of Q: one word of the rows against one word
-constexpr int kBlockElems = kBlock * kBlock;
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// the words of a row's bits that exist: all 64, or the low R - 64 word of the last word
-__device__ __forceinline__ unsigned long long live_mask(int word, int R) {
-    const int bits = R - 64 * word;
-    return bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
-}
 
 // d times column k of the coefficient table at size s; a row of size 0 or R contributes 0 whatever its reward
 __device__ __forceinline__ double row_term(double d, int s, int R, const double* __restrict__ coef, int k) {
@@ -81,10 +74,43 @@ __global__ __launch_bounds__(kThreads) void kshap_pairs_sizes_kernel(const unsig
                                                                      int W, unsigned short* __restrict__ sizes) {
     const long long m = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (m >= M) return;
-    int s = 0;
-    for (int w = 0; w < W; ++w) s += __popcll(keep[(size_t)m * W + w] & live_mask(w, R));
-    sizes[m] = (unsigned short)s;
+    sizes[m] = (unsigned short)iq::kshap::row_size(keep + (size_t)m * W, W, R);
 }
+
+// The rows of block_product for block (bi, bj) of Q: a staged row is its words bi and bj and its scalar e_m; A = bit ? e_m : 0.0,
+// B = bit ? 1.0 : 0.0.
+template <typename RowScalar>
+struct PairRows {
+    unsigned long long *sh_a, *sh_b;             // the tile's words bi and bj, bits at or above R masked
+    double* sh_e;                                // the tile's e_m
+    const unsigned long long* keep;
+    size_t stride;
+    RowScalar scalar;
+    long long rows;
+    int bi, bj;
+    unsigned long long mask_a, mask_b;
+    __device__ __forceinline__ void stage(int t, long long m) const {
+        double e = 0.0;
+        unsigned long long ka = 0ull, kb = 0ull;
+        if (m < rows) {
+            e = scalar(m);
+            ka = keep[(size_t)m * stride + bi] & mask_a;
+            kb = keep[(size_t)m * stride + bj] & mask_b;
+        }
+        sh_a[t] = ka;
+        sh_b[t] = kb;
+        sh_e[t] = e;
+    }
+    __device__ __forceinline__ void operands(int r, int col, double (&fa)[4], double (&fb)[4]) const {
+        const unsigned long long wa = sh_a[r] >> col, wb = sh_b[r] >> col;
+        const double er = sh_e[r];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            fa[a] = (wa >> (16 * a)) & 1ull ? er : 0.0;          // A[i = 16 a + col][k]
+            fb[a] = (wb >> (16 * a)) & 1ull ? 1.0 : 0.0;         // B[k][j = 16 a + col]
+        }
+    }
+};
 
 // The body of both pairwise products: part[((g * nchunk + chunk) * nblk + blk) * 4096 + 64 r + c] = the chunk's sum of
 // e_m z_m(64 bi + r) z_m(64 bj + c) over the rows m < rows of the workgroup's chunk, blk = bj (bj + 1) / 2 + bi, bi <= bj, on the
@@ -96,74 +122,10 @@ __device__ __forceinline__ void pair_product_chunk(const unsigned long long* __r
     __shared__ unsigned long long sh_a[kTile], sh_b[kTile];
     __shared__ double sh_e[kTile];
     __shared__ double sh_acc[kBlockElems];
-    const int t = threadIdx.x, lane = t & 63, q = t >> 6, col = lane & 15, kk = lane >> 4;
-    const int blk = blockIdx.x, chunk = blockIdx.y, g = blockIdx.z;
-    int bj = 0;
-    while ((bj + 1) * (bj + 2) / 2 <= blk) ++bj;
-    const int bi = blk - bj * (bj + 1) / 2;
-    const unsigned long long mask_a = live_mask(bi, R), mask_b = live_mask(bj, R);
-    const int na = min(4, (R - 64 * bi + 15) >> 4), nb = min(4, (R - 64 * bj + 15) >> 4);
-    unsigned tiles_live = 0;                     // bit 4 a + b: tile (a, b) of the block is computed
-    for (int a = 0; a < na; ++a)
-        for (int b = 0; b < nb; ++b)
-            if (bi != bj || b >= a) tiles_live |= 1u << (4 * a + b);
-    const long long row0 = (long long)chunk * tiles_per * kTile;
-
-    f64x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-    for (int tile = 0; tile < tiles_per; ++tile) {
-        const long long m = row0 + (long long)tile * kTile + t;
-        const bool live = m < rows;
-        double e = 0.0;
-        unsigned long long ka = 0ull, kb = 0ull;
-        if (live) {
-            e = scalar(m);
-            ka = keep[(size_t)m * stride + bi] & mask_a;
-            kb = keep[(size_t)m * stride + bj] & mask_b;
-        }
-        sh_a[t] = ka;
-        sh_b[t] = kb;
-        sh_e[t] = e;
-        __syncthreads();
-#pragma unroll 2
-        for (int step = 0; step < 16; ++step) {
-            const int r = q * 64 + step * 4 + kk;                   // this lane's row of the four: k = lane >> 4
-            const unsigned long long wa = sh_a[r] >> col, wb = sh_b[r] >> col;
-            const double er = sh_e[r];
-            double fa[4], fb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                fa[a] = (wa >> (16 * a)) & 1ull ? er : 0.0;          // A[i = 16 a + col][k]
-                fb[a] = (wb >> (16 * a)) & 1ull ? 1.0 : 0.0;         // B[k][j = 16 a + col]
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    if ((tiles_live >> (4 * a + b)) & 1u)
-                        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // the four waves in wave order; C/D of the f64 form: column = lane & 15, row = (lane >> 4) + 4 reg
-    for (int turn = 0; turn < 4; ++turn) {
-        if (q == turn) {
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) {
-                        const int at = (16 * a + kk + 4 * reg) * kBlock + 16 * b + col;
-                        sh_acc[at] = turn == 0 ? acc[a][b][reg] : sh_acc[at] + acc[a][b][reg];
-                    }
-        }
-        __syncthreads();
-    }
+    const int t = threadIdx.x, blk = blockIdx.x, chunk = blockIdx.y, g = blockIdx.z;
+    const auto [bi, bj] = iq::kshap::block_of(blk);
+    const PairRows<RowScalar> staged{sh_a, sh_b, sh_e, keep, stride, scalar, rows, bi, bj, live_mask(bi, R), live_mask(bj, R)};
+    iq::kshap::block_product(staged, bi, bj, R, (long long)chunk * tiles_per * kTile, tiles_per, sh_acc);
     double* dst = part + (((size_t)g * gridDim.y + chunk) * gridDim.x + blk) * kBlockElems;
     for (int e = t; e < kBlockElems; e += kThreads) dst[e] = sh_acc[e];
 }
@@ -198,41 +160,17 @@ __global__ __launch_bounds__(kThreads) void kshap_pairs_moment_kernel(const unsi
         weights && word == 0 && g == 0 ? partW + chunk : nullptr);
 }
 
-// Grid (chunk of chunks_of(M), game): partA[g * nchunk + chunk] = the chunk's sum of d_m alpha_s: per thread over its rows
-// t, t + 256, ... of the chunk, then the 256 threads in index order (the rule of a chunk's sum of weights).
+// Grid (chunk of chunks_of(M), game): partA[g * nchunk + chunk] = the chunk's sum of d_m alpha_s by scalar_chunk_of.
 template <typename Diff>
 __global__ __launch_bounds__(kThreads) void kshap_pairs_alpha_kernel(const unsigned short* __restrict__ sizes, Diff diff,
                                                                      const double* __restrict__ weights,
                                                                      const double* __restrict__ coef, long long M, int R, int tiles_per,
                                                                      double* __restrict__ partA) {
-    __shared__ double sh[kThreads];
-    const int chunk = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
+    const int chunk = blockIdx.x, g = blockIdx.y;
     const auto d = diff.of(g, M);
-    const long long row0 = (long long)chunk * tiles_per * kTile;
-    double acc = 0.0;
-    for (int tile = 0; tile < tiles_per; ++tile) {
-        const long long m = row0 + (long long)tile * kTile + t;
-        if (m < M) acc += row_term((weights ? weights[m] : 1.0) * d(m), sizes[m], R, coef, 0);
-    }
-    const double s = iq::kshap::sum_threads_in_order(sh, acc);
-    if (t == 0) partA[(size_t)g * gridDim.x + chunk] = s;
-}
-
-// One thread per output: the chunks' partials added in chunk order.  Entries [0, G R): L; then G of A; the last one wsum.
-__global__ __launch_bounds__(kThreads) void kshap_pairs_fold_kernel(const double* __restrict__ partL, const double* __restrict__ partA,
-                                                                    const double* __restrict__ partW, int weighted, long long M, int R,
-                                                                    int G, int nchunk, double* __restrict__ L, double* __restrict__ A,
-                                                                    double* __restrict__ wsum) {
-    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x, nl = (long long)G * R;
-    if (e < nl) {
-        const long long g = e / R, i = e % R;
-        L[e] = iq::kshap::fold_chunks(partL + (size_t)g * nchunk * R + i, R, nchunk);
-    } else if (e < nl + G) {
-        const long long g = e - nl;
-        A[g] = iq::kshap::fold_chunks(partA + (size_t)g * nchunk, 1, nchunk);
-    } else if (e == nl + G) {
-        *wsum = iq::kshap::fold_wsum(partW, weighted, M, nchunk);
-    }
+    const double s = iq::kshap::scalar_chunk_of(
+        [=](long long m) { return row_term((weights ? weights[m] : 1.0) * d(m), sizes[m], R, coef, 0); }, M, tiles_per, chunk);
+    if (threadIdx.x == 0) partA[(size_t)g * gridDim.x + chunk] = s;
 }
 
 // Grid (R^2 / 256, game), one thread per (i, j): the thread of i < j folds Q_ij over the chunks in chunk order and writes
@@ -310,37 +248,11 @@ __global__ __launch_bounds__(kThreads, 2) void kshap_pairs_se_q_kernel(const uns
     pair_product_chunk(keep, (size_t)stride, [=](long long u) { return gu[u]; }, U, R, tiles_per, part);
 }
 
-// Grid (chunk of chunks_of(U), word, game): partL[(g * nchunk + chunk) * R + 64 word + i] = the chunk's sum of B_u z_ui in
-// moment_chunk's order over the units' first rows.
-__global__ __launch_bounds__(kThreads) void kshap_pairs_se_moment_kernel(const unsigned long long* __restrict__ keep,
-                                                                         const double* __restrict__ unit, long long U, int R, int stride,
-                                                                         int tiles_per, double* __restrict__ partL) {
-    const int chunk = blockIdx.x, word = blockIdx.y, g = blockIdx.z;
-    const double* bu = unit + ((size_t)3 * g + 1) * U;
-    iq::kshap::moment_chunk_of(
-        keep, stride, word, [=](long long u, double) { return bu[u]; }, nullptr, U, tiles_per, chunk,
-        partL + ((size_t)g * gridDim.x + chunk) * R + 64 * word, min(64, R - 64 * word), nullptr);
-}
-
-// Grid (chunk of chunks_of(U), game): partA[g * nchunk + chunk] = the chunk's sum of P_u, by the rule of kshap_pairs_alpha_kernel.
-__global__ __launch_bounds__(kThreads) void kshap_pairs_se_scalar_kernel(const double* __restrict__ unit, long long U, int tiles_per,
-                                                                         double* __restrict__ partA) {
-    __shared__ double sh[kThreads];
-    const int chunk = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
-    const double* pu = unit + (size_t)3 * g * U;
-    const long long row0 = (long long)chunk * tiles_per * kTile;
-    double acc = 0.0;
-    for (int tile = 0; tile < tiles_per; ++tile) {
-        const long long u = row0 + (long long)tile * kTile + t;
-        if (u < U) acc += pu[u];
-    }
-    const double s = iq::kshap::sum_threads_in_order(sh, acc);
-    if (t == 0) partA[(size_t)g * gridDim.x + chunk] = s;
-}
+// The sums of B_u z_ui and of P_u over the units are iq_kshap_order.h's unit_moment_kernel<3> and unit_scalar_kernel<3>.
 
 // Grid (R^2 / 256, game), one thread per (i, j); the thread of i < j folds both products over their chunks in chunk order,
 //     S1 = ((A + L_i) + L_j) + Q_ij  (the sum the estimate is made of),   S2 = ((A2 + L2_i) + L2_j) + Q2_ij,
-//     var = ((U / (U - 1)) (S2 - S1 S1 / U)) / (M M),   se = sqrt(var), 0 where var < 0,
+//     var = unit_variance(S1, S2, U, M),   se = sqrt(var), 0 where var < 0,
 // every operation rounded on its own, and writes se[i][j] = se[j][i], the same bits on both sides; i = j writes 0.
 __global__ __launch_bounds__(kThreads) void kshap_pairs_se_assemble_kernel(const double* __restrict__ part, const double* __restrict__ L,
                                                                            const double* __restrict__ A, int nchunk,
@@ -360,8 +272,7 @@ __global__ __launch_bounds__(kThreads) void kshap_pairs_se_assemble_kernel(const
     const double q2 = iq::kshap::fold_chunks(part2 + (size_t)g * nchunk2 * step + at, step, nchunk2);
     const double s1 = ((A[g] + L[(size_t)g * R + i]) + L[(size_t)g * R + j]) + q1;
     const double s2 = ((A2[g] + L2[(size_t)g * R + i]) + L2[(size_t)g * R + j]) + q2;
-    const double units = (double)U, rows = (double)M;
-    const double var = ((units / (units - 1.0)) * (s2 - s1 * s1 / units)) / (rows * rows);
+    const double var = iq::kshap::unit_variance(s1, s2, U, M);
     const double x = var < 0.0 ? 0.0 : sqrt(var);
     o[(size_t)i * R + j] = x;
     o[(size_t)j * R + i] = x;
@@ -372,11 +283,6 @@ struct Scratch {
     double *partQ, *partL, *partA, *partW, *L, *A, *wsum;
     size_t bytes;
 };
-
-int blocks_of(int R) {
-    const int nb = (R + kBlock - 1) / kBlock;
-    return nb * (nb + 1) / 2;
-}
 
 Scratch carve(void* base, long long M, int R, int G) {
     const Chunks ch = chunks_of(M), qc = pair_chunks_of(M, R);
@@ -394,8 +300,6 @@ Scratch carve(void* base, long long M, int R, int G) {
     return s;
 }
 
-bool shape_ok(long long M, int R, int G) { return M >= 1 && M <= (1ll << 30) && R >= 2 && R <= kMaxR && G >= 1 && G <= 65535; }
-
 // The launches of iq_kshap_pairs on a carved scratch: sizes, Q, L, A, the folds and the assembly of `out`.
 template <typename Diff>
 int launch_pairs(const Scratch& s, const unsigned long long* k, Diff diff, const double* delta, const double* weights,
@@ -411,8 +315,9 @@ int launch_pairs(const Scratch& s, const unsigned long long* k, Diff diff, const
     IQ_LAUNCH((kshap_pairs_alpha_kernel<Diff>), dim3(ch.count, G), dim3(kThreads), 0, st, (const unsigned short*)s.sizes, diff, weights,
               coef, rows, R, ch.tiles_per, s.partA);
     const long long folds = (long long)G * R + G + 1;
-    IQ_LAUNCH(kshap_pairs_fold_kernel, dim3((unsigned)((folds + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const double*)s.partL,
-              (const double*)s.partA, (const double*)s.partW, weights ? 1 : 0, rows, R, G, ch.count, s.L, s.A, s.wsum);
+    IQ_LAUNCH(iq::kshap::fold_moments_kernel<true>, dim3((unsigned)((folds + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+              (const double*)s.partL, (const double*)s.partA, (const double*)s.partW, weights ? 1 : 0, rows, R, G, ch.count, s.L, s.A,
+              s.wsum);
     IQ_LAUNCH(kshap_pairs_assemble_kernel, dim3((unsigned)(((long long)R * R + kThreads - 1) / kThreads), G), dim3(kThreads), 0, st,
               (const double*)s.partQ, (const double*)s.L, (const double*)s.A, (const double*)s.wsum, delta, R, qc.count, nblk, out);
     return IQ_OK;
@@ -443,58 +348,60 @@ SeScratch carve_se(void* base, long long M, int R, int G, long long U) {
     return s;
 }
 
-// the units of M rows; 0 where the rows do not make at least two whole units
-long long units_of(long long M, int paired) {
-    if (paired && (M & 1)) return 0;
-    const long long U = paired ? M / 2 : M;
-    return U >= 2 ? U : 0;
-}
-
 // The launches of iq_kshap_pairs_se on a carved scratch: launch_pairs, then the units, the second product, moment and scalar, their
 // folds and the assembly of `se`.
 template <typename Diff>
 int launch_pairs_se(const SeScratch& s, const unsigned long long* k, Diff diff, const double* delta, const double* coef, int M, int R,
                     int G, int paired, long long U, double* out, double* se, hipStream_t st) {
     IQ_TRY(launch_pairs(s.first, k, diff, delta, nullptr, coef, M, R, G, out, st));
-    double h = 0.0;                                   // H_{R-1} as iq_kshap_phi_analytic sums it
-    for (int i = 1; i < R; ++i) h += 1.0 / (double)i;
     const Chunks qc1 = pair_chunks_of(M, R), ch = chunks_of(U), qc = pair_chunks_of(U, R);
     const int W = iq::keep_words(R), nblk = blocks_of(R), stride = paired ? 2 * W : W;
     IQ_LAUNCH((kshap_pairs_unit_kernel<Diff>), dim3((unsigned)((U + kThreads - 1) / kThreads), G), dim3(kThreads), 0, st,
-              (const unsigned short*)s.first.sizes, diff, (long long)M, U, R, paired ? 1 : 0, 2.0 * h, s.unit);
+              (const unsigned short*)s.first.sizes, diff, (long long)M, U, R, paired ? 1 : 0, iq::kshap::two_harmonic(R), s.unit);
     IQ_LAUNCH(kshap_pairs_se_q_kernel, dim3(nblk, qc.count, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
               qc.tiles_per, s.partQ);
-    IQ_LAUNCH(kshap_pairs_se_moment_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
-              ch.tiles_per, s.partL);
-    IQ_LAUNCH(kshap_pairs_se_scalar_kernel, dim3(ch.count, G), dim3(kThreads), 0, st, (const double*)s.unit, U, ch.tiles_per, s.partA);
+    IQ_LAUNCH(iq::kshap::unit_moment_kernel<3>, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const double*)s.unit + U, U, R, stride,
+              ch.tiles_per, s.partL);                 // B_u: the second of a game's three arrays
+    IQ_LAUNCH(iq::kshap::unit_scalar_kernel<3>, dim3(ch.count, G), dim3(kThreads), 0, st, (const double*)s.unit, U, ch.tiles_per,
+              s.partA);                               // P_u: the first
     const long long folds = (long long)G * R + G + 1;
-    IQ_LAUNCH(kshap_pairs_fold_kernel, dim3((unsigned)((folds + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, (const double*)s.partL,
-              (const double*)s.partA, (const double*)nullptr, 0, U, R, G, ch.count, s.L, s.A, s.wsum);
+    IQ_LAUNCH(iq::kshap::fold_moments_kernel<true>, dim3((unsigned)((folds + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+              (const double*)s.partL, (const double*)s.partA, (const double*)nullptr, 0, U, R, G, ch.count, s.L, s.A, s.wsum);
     IQ_LAUNCH(kshap_pairs_se_assemble_kernel, dim3((unsigned)(((long long)R * R + kThreads - 1) / kThreads), G), dim3(kThreads), 0, st,
               (const double*)s.first.partQ, (const double*)s.first.L, (const double*)s.first.A, qc1.count, (const double*)s.partQ,
               (const double*)s.L, (const double*)s.A, qc.count, (long long)M, U, R, nblk, se);
     return IQ_OK;
 }
 
-// The checks and the carving shared by iq_kshap_pairs_se and iq_kshap_pairs_terms_se (`name`: the entry, for the message; `pointers`:
-// whether all of its pointer arguments are there) -> a status; with IQ_OK, *units and *carved are set.
+// The checks and the carving of the four entries (`name`: the entry, for the message; `pointers`: whether all of its pointer
+// arguments are there) -> a status; with IQ_OK, *carved is set.  The _se entries: *units too, after the shape and before the pointers.
+int check_shape(const char* name, int M, int R, int G) {
+    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "%s: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", name, M, R, G, kMaxR);
+    return IQ_OK;
+}
+
+int check_call(const char* name, bool pointers, int M, int R, int G, void* scratch, size_t scratch_bytes, Scratch* carved) {
+    IQ_TRY(check_shape(name, M, R, G));
+    IQ_REQUIRE(pointers, "%s: null pointer", name);
+    *carved = carve(scratch, M, R, G);
+    return iq::kshap::scratch_ok(name, scratch, scratch_bytes, carved->bytes);
+}
+
 int check_se_call(const char* name, bool pointers, int M, int R, int G, int paired, void* scratch, size_t scratch_bytes,
                   long long* units, SeScratch* carved) {
-    IQ_REQUIRE(shape_ok(M, R, G), "%s: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", name, M, R, G, kMaxR);
-    *units = units_of(M, paired);
+    IQ_TRY(check_shape(name, M, R, G));
+    *units = iq::kshap::units_of(M, paired);
     IQ_REQUIRE(*units, "%s: M=%d %s rows are not two or more whole units", name, M, paired ? "paired" : "unpaired");
     IQ_REQUIRE(pointers, "%s: null pointer", name);
     *carved = carve_se(scratch, M, R, G, *units);
-    if (scratch_bytes < carved->bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "%s: scratch of %zu bytes (8-byte aligned) needed, got %zu", name, carved->bytes, scratch_bytes);
-    return IQ_OK;
+    return iq::kshap::scratch_ok(name, scratch, scratch_bytes, carved->bytes);
 }
 
 }  // namespace
 
 extern "C" size_t iq_kshap_pairs_se_scratch_bytes(int M, int R, int G, int paired) {
-    const long long U = units_of(M, paired);
-    return shape_ok(M, R, G) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
+    const long long U = iq::kshap::units_of(M, paired);
+    return rows_ok(M, R, G, kMaxR) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
 }
 
 extern "C" int iq_kshap_pairs_se(const uint64_t* keep, const float* v, const double* v0, const double* delta, const double* coef, int M,
@@ -520,17 +427,14 @@ extern "C" int iq_kshap_pairs_terms_se(const uint64_t* keep, const double* t, co
 }
 
 extern "C" size_t iq_kshap_pairs_scratch_bytes(int M, int R, int G) {
-    return shape_ok(M, R, G) ? carve(nullptr, M, R, G).bytes : 0;
+    return rows_ok(M, R, G, kMaxR) ? carve(nullptr, M, R, G).bytes : 0;
 }
 
 extern "C" int iq_kshap_pairs(const uint64_t* keep, const float* v, const double* v0, const double* delta, const double* weights,
                               const double* coef, int M, int R, int G, double* out, void* scratch, size_t scratch_bytes,
                               iq_stream_t stream) {
-    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_pairs: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
-    IQ_REQUIRE(keep && v && v0 && delta && coef && out && scratch, "iq_kshap_pairs: null pointer");
-    const Scratch s = carve(scratch, M, R, G);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_pairs: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
+    Scratch s;
+    IQ_TRY(check_call("iq_kshap_pairs", keep && v && v0 && delta && coef && out && scratch, M, R, G, scratch, scratch_bytes, &s));
     return launch_pairs(s, reinterpret_cast<const unsigned long long*>(keep), RewardDiff{v, v0}, delta, weights, coef, M, R, G, out,
                         iq::as_stream(stream));
 }
@@ -539,11 +443,8 @@ extern "C" int iq_kshap_pairs(const uint64_t* keep, const float* v, const double
 // The scratch is iq_kshap_pairs_scratch_bytes.
 extern "C" int iq_kshap_pairs_terms(const uint64_t* keep, const double* t, const double* weights, const double* coef, int M, int R,
                                     int G, double* out, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
-    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_pairs_terms: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
-    IQ_REQUIRE(keep && t && coef && out && scratch, "iq_kshap_pairs_terms: null pointer");
-    const Scratch s = carve(scratch, M, R, G);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_pairs_terms: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
+    Scratch s;
+    IQ_TRY(check_call("iq_kshap_pairs_terms", keep && t && coef && out && scratch, M, R, G, scratch, scratch_bytes, &s));
     return launch_pairs(s, reinterpret_cast<const unsigned long long*>(keep), TermDiff{t}, nullptr, weights, coef, M, R, G, out,
                         iq::as_stream(stream));
 }

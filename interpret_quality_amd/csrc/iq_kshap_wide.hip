@@ -21,6 +21,8 @@ namespace {
 using iq::kshap::Chunks;
 using iq::kshap::chunks_of;
 using iq::kshap::kThreads;
+using iq::kshap::rows_ok;
+using iq::kshap::units_of;
 
 constexpr int kMaxW = iq::kMaxKeepWords;
 constexpr int kMaxR = IQ_MAX_WIDE_REGIONS;
@@ -71,18 +73,7 @@ __global__ __launch_bounds__(kThreads) void kshap_moment_wide_kernel(const unsig
                             weights && word == 0 && g == 0 ? partW + chunk : nullptr);
 }
 
-// One thread per output: the chunks' partials added in chunk order.  Entries [0, G R): b; the last one wsum.
-__global__ __launch_bounds__(kThreads) void kshap_fold_wide_kernel(const double* __restrict__ partB, const double* __restrict__ partW,
-                                                                   int weighted, long long M, int R, int G, int nchunk,
-                                                                   double* __restrict__ b, double* __restrict__ wsum) {
-    const long long e = (long long)blockIdx.x * kThreads + threadIdx.x, nb = (long long)G * R;
-    if (e < nb) {
-        const long long g = e / R, i = e % R;
-        b[e] = iq::kshap::fold_chunks(partB + (size_t)g * nchunk * R + i, R, nchunk);
-    } else if (e == nb) {
-        *wsum = iq::kshap::fold_wsum(partW, weighted, M, nchunk);
-    }
-}
+// The chunks are folded into b and wsum by iq_kshap_order.h's fold_moments_kernel<false>.
 
 // One workgroup per game.  x_i = b_i / wsum; c = (x_0 + x_1 + ... in index order) / R; y_i = x_i - c; the mean of the centred
 // values once more, d = (y_0 + y_1 + ... in index order) / R (zero but for the rounding of c: x is R nearly equal numbers whose
@@ -126,11 +117,7 @@ __global__ __launch_bounds__(kThreads) void kshap_se_unit_wide_kernel(const unsi
     const long long u = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (u >= U) return;
     const long long m = paired ? 2 * u : u;
-    int s = 0;
-    for (int w = 0; w < W; ++w) {
-        const int bits = R - 64 * w;
-        s += __popcll(keep[(size_t)m * W + w] & (bits >= 64 ? ~0ull : (1ull << bits) - 1ull));
-    }
+    const int s = iq::kshap::row_size(keep + (size_t)m * W, W, R);
     const double lin = 1.0 - (double)(2 * s) / (double)R, sq = (double)(s * s) / ((double)R * (double)R);
     for (int g = 0; g < G; ++g) {
         const float* vg = v + (size_t)g * M;
@@ -143,37 +130,11 @@ __global__ __launch_bounds__(kThreads) void kshap_se_unit_wide_kernel(const unsi
     }
 }
 
-// Grid (chunk of chunks_of(U), word, game): partE[(g * nchunk + chunk) * R + 64 word + i] = the chunk's sum of e_u z_ui over the
-// units' first rows (row u starts at keep + u * stride words), in moment_chunk_of's order.
-__global__ __launch_bounds__(kThreads) void kshap_se_moment_wide_kernel(const unsigned long long* __restrict__ keep,
-                                                                        const double* __restrict__ unit, long long U, int R, int stride,
-                                                                        int tiles_per, double* __restrict__ partE) {
-    const int chunk = blockIdx.x, word = blockIdx.y, g = blockIdx.z;
-    const double* eu = unit + (size_t)(2 * g) * U;
-    iq::kshap::moment_chunk_of(
-        keep, stride, word, [=](long long u, double) { return eu[u]; }, nullptr, U, tiles_per, chunk,
-        partE + ((size_t)g * gridDim.x + chunk) * R + 64 * word, min(64, R - 64 * word), nullptr);
-}
-
-// Grid (chunk of chunks_of(U), game): partF[g * nchunk + chunk] = the chunk's sum of f_u, as a chunk's sum of weights is taken.
-__global__ __launch_bounds__(kThreads) void kshap_se_scalar_wide_kernel(const double* __restrict__ unit, long long U, int tiles_per,
-                                                                        double* __restrict__ partF) {
-    __shared__ double sh[kThreads];
-    const int chunk = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
-    const double* fu = unit + (size_t)(2 * g + 1) * U;
-    const long long row0 = (long long)chunk * tiles_per * iq::kshap::kTile;
-    double acc = 0.0;
-    for (int tile = 0; tile < tiles_per; ++tile) {
-        const long long u = row0 + (long long)tile * iq::kshap::kTile + t;
-        if (u < U) acc += fu[u];
-    }
-    const double s = iq::kshap::sum_threads_in_order(sh, acc);
-    if (t == 0) partF[(size_t)g * gridDim.x + chunk] = s;
-}
+// The chunks' sums of e_u z_ui and of f_u over the units are iq_kshap_order.h's unit_moment_kernel<2> and unit_scalar_kernel<2>.
 
 // One workgroup per game.  c = (b_0 + b_1 + ... in index order) / R and F = the chunks' f in chunk order, by thread 0; then per
 // region E_i = the chunks' e in chunk order, S1 = two_h (b_i - c), S2 = (two_h two_h) (E_i + F),
-// var_i = ((U / (U - 1)) (S2 - S1 S1 / U)) / (M M).  Each operation rounded on its own.
+// var_i = unit_variance(S1, S2, U, M).  Each operation rounded on its own.
 __global__ __launch_bounds__(kThreads) void kshap_moment_var_wide_kernel(const double* __restrict__ b, const double* __restrict__ partE,
                                                                          const double* __restrict__ partF, int nchunk, long long M,
                                                                          long long U, int R, double two_h, double* __restrict__ var) {
@@ -186,11 +147,11 @@ __global__ __launch_bounds__(kThreads) void kshap_moment_var_wide_kernel(const d
         sh_f = iq::kshap::fold_chunks(partF + (size_t)g * nchunk, 1, nchunk);
     }
     __syncthreads();
-    const double units = (double)U, rows = (double)M, scale = two_h * two_h;
+    const double scale = two_h * two_h;
     for (int i = t; i < R; i += kThreads) {
         const double e = iq::kshap::fold_chunks(partE + (size_t)g * nchunk * R + i, R, nchunk);
         const double s1 = two_h * (b[(size_t)g * R + i] - sh_mean), s2 = scale * (e + sh_f);
-        var[(size_t)g * R + i] = ((units / (units - 1.0)) * (s2 - s1 * s1 / units)) / (rows * rows);
+        var[(size_t)g * R + i] = iq::kshap::unit_variance(s1, s2, U, M);
     }
 }
 
@@ -209,8 +170,6 @@ Scratch carve(void* base, long long M, int R, int G) {
     return s;
 }
 
-bool shape_ok(long long M, int R, int G) { return M >= 1 && M <= (1ll << 30) && R >= 2 && R <= kMaxR && G >= 1 && G <= 65535; }
-
 }  // namespace
 
 extern "C" int iq_kshap_keep_masks_wide(const int32_t* orders, const int32_t* sizes, uint64_t* keep, int S, int R, int paired,
@@ -226,24 +185,24 @@ extern "C" int iq_kshap_keep_masks_wide(const int32_t* orders, const int32_t* si
 }
 
 extern "C" size_t iq_kshap_scratch_bytes_wide(int M, int R, int G) {
-    return shape_ok(M, R, G) ? carve(nullptr, M, R, G).bytes : 0;
+    return rows_ok(M, R, G, kMaxR) ? carve(nullptr, M, R, G).bytes : 0;
 }
 
 extern "C" int iq_kshap_moment_wide(const uint64_t* keep, const float* v, const double* v0, const double* weights, int M, int R, int G,
                                     double* b, double* wsum, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
-    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_moment_wide: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
+    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "iq_kshap_moment_wide: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
     IQ_REQUIRE(keep && v && v0 && b && wsum && scratch, "iq_kshap_moment_wide: null pointer");
     const Scratch s = carve(scratch, M, R, G);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_moment_wide: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes, scratch_bytes);
+    IQ_TRY(iq::kshap::scratch_ok("iq_kshap_moment_wide", scratch, scratch_bytes, s.bytes));
     const Chunks ch = chunks_of(M);
     const int W = iq::keep_words(R);
     hipStream_t st = iq::as_stream(stream);
     IQ_LAUNCH(kshap_moment_wide_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st,
               reinterpret_cast<const unsigned long long*>(keep), v, v0, weights, (long long)M, R, W, ch.tiles_per, s.partB, s.partW);
     const long long outputs = (long long)G * R + 1;
-    IQ_LAUNCH(kshap_fold_wide_kernel, dim3((unsigned)((outputs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-              (const double*)s.partB, (const double*)s.partW, weights ? 1 : 0, (long long)M, R, G, ch.count, b, wsum);
+    IQ_LAUNCH(iq::kshap::fold_moments_kernel<false>, dim3((unsigned)((outputs + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+              (const double*)s.partB, (const double*)nullptr, (const double*)s.partW, weights ? 1 : 0, (long long)M, R, G, ch.count, b,
+              (double*)nullptr, wsum);
     return IQ_OK;
 }
 
@@ -251,9 +210,8 @@ extern "C" int iq_kshap_phi_analytic(const double* b, const double* wsum, const 
                                      iq_stream_t stream) {
     IQ_REQUIRE(R >= 2 && R <= kMaxR && G >= 1 && G <= 65535, "iq_kshap_phi_analytic: R=%d, G=%d (2 <= R <= %d, 1 <= G <= 65535)", R, G, kMaxR);
     IQ_REQUIRE(b && wsum && delta && phi, "iq_kshap_phi_analytic: null pointer");
-    double h = 0.0;                                   // H_{R-1}, float64, ascending k: summed here on the host, passed by value
-    for (int k = 1; k < R; ++k) h += 1.0 / (double)k;
-    IQ_LAUNCH(kshap_phi_analytic_kernel, dim3(G), dim3(kThreads), 0, iq::as_stream(stream), b, wsum, delta, phi, R, 2.0 * h);
+    IQ_LAUNCH(kshap_phi_analytic_kernel, dim3(G), dim3(kThreads), 0, iq::as_stream(stream), b, wsum, delta, phi, R,
+              iq::kshap::two_harmonic(R));
     return IQ_OK;
 }
 
@@ -280,44 +238,34 @@ SeScratch carve_se(void* base, long long M, int R, int G, long long U) {
     return s;
 }
 
-// the units of M rows; 0 where the rows do not make at least two whole units
-long long units_of(long long M, int paired) {
-    if (paired && (M & 1)) return 0;
-    const long long U = paired ? M / 2 : M;
-    return U >= 2 ? U : 0;
-}
-
 }  // namespace
 
 extern "C" size_t iq_kshap_moment_se_scratch_bytes_wide(int M, int R, int G, int paired) {
     const long long U = units_of(M, paired);
-    return shape_ok(M, R, G) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
+    return rows_ok(M, R, G, kMaxR) && U ? carve_se(nullptr, M, R, G, U).bytes : 0;
 }
 
 extern "C" int iq_kshap_moment_se_wide(const uint64_t* keep, const float* v, const double* v0, int M, int R, int G, int paired, double* b,
                                        double* var, void* scratch, size_t scratch_bytes, iq_stream_t stream) {
-    IQ_REQUIRE(shape_ok(M, R, G), "iq_kshap_moment_se_wide: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G,
+    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "iq_kshap_moment_se_wide: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G,
                kMaxR);
     const long long U = units_of(M, paired);
     IQ_REQUIRE(U, "iq_kshap_moment_se_wide: M=%d %s rows are not two or more whole units", M, paired ? "paired" : "unpaired");
     IQ_REQUIRE(keep && v && v0 && b && var && scratch, "iq_kshap_moment_se_wide: null pointer");
     const SeScratch s = carve_se(scratch, M, R, G, U);
-    if (scratch_bytes < s.bytes || ((uintptr_t)scratch & 7))
-        return iq::fail(IQ_EWORKSPACE, "iq_kshap_moment_se_wide: scratch of %zu bytes (8-byte aligned) needed, got %zu", s.bytes,
-                        scratch_bytes);
+    IQ_TRY(iq::kshap::scratch_ok("iq_kshap_moment_se_wide", scratch, scratch_bytes, s.bytes));
     IQ_TRY(iq_kshap_moment_wide(keep, v, v0, nullptr, M, R, G, b, s.wsum, scratch, s.first.bytes, stream));
-    double h = 0.0;                                   // H_{R-1} as iq_kshap_phi_analytic sums it
-    for (int k = 1; k < R; ++k) h += 1.0 / (double)k;
     const Chunks ch = chunks_of(U);
     const int W = iq::keep_words(R), stride = paired ? 2 * W : W;
     hipStream_t st = iq::as_stream(stream);
     const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
     IQ_LAUNCH(kshap_se_unit_wide_kernel, dim3((unsigned)((U + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, k, v, v0, (long long)M, U,
               R, W, G, paired ? 1 : 0, s.unit);
-    IQ_LAUNCH(kshap_se_moment_wide_kernel, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
-              ch.tiles_per, s.partE);
-    IQ_LAUNCH(kshap_se_scalar_wide_kernel, dim3(ch.count, G), dim3(kThreads), 0, st, (const double*)s.unit, U, ch.tiles_per, s.partF);
+    IQ_LAUNCH(iq::kshap::unit_moment_kernel<2>, dim3(ch.count, W, G), dim3(kThreads), 0, st, k, (const double*)s.unit, U, R, stride,
+              ch.tiles_per, s.partE);                 // e_u: the first of a game's two arrays
+    IQ_LAUNCH(iq::kshap::unit_scalar_kernel<2>, dim3(ch.count, G), dim3(kThreads), 0, st, (const double*)s.unit + U, U, ch.tiles_per,
+              s.partF);                               // f_u: the second
     IQ_LAUNCH(kshap_moment_var_wide_kernel, dim3(G), dim3(kThreads), 0, st, (const double*)b, (const double*)s.partE,
-              (const double*)s.partF, ch.count, (long long)M, U, R, 2.0 * h, var);
+              (const double*)s.partF, ch.count, (long long)M, U, R, iq::kshap::two_harmonic(R), var);
     return IQ_OK;
 }

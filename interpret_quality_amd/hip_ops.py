@@ -390,6 +390,30 @@ def kshap_keep_masks(orders, sizes, paired=True):
     return _kshap_keep_masks("iq_kshap_keep_masks", kshap_regions, lambda n: (), orders, sizes, paired)
 
 
+def _opt(t, dtype, name):
+    """The pointer of an optional tensor argument: NULL for None."""
+    return _dev(t, dtype, name) if t is not None else ctypes.c_void_p(0)
+
+
+def _kshap_scratch_words(what, nbytes, m, r, g, regions="R"):
+    """The answer of a regression entry's ``*_scratch_bytes`` -> the float64 words of its scratch; 0 bytes refuses the shape."""
+    if nbytes == 0:
+        raise _lib.IqError("%s: M=%d rows, %s=%d regions, G=%d games is out of range" % (what, m, regions, r, g))
+    return nbytes // 8
+
+
+def _kshap_scratch(what, nbytes, m, r, g, dev, regions="R"):
+    """The scratch of a regression entry, uninitialised.  (The control-variate wrappers lend zeroed memory on purpose and allocate
+    their own: the note above ``kshap_pairs_terms``.)"""
+    return torch.empty((_kshap_scratch_words(what, nbytes, m, r, g, regions),), dtype=torch.float64, device=dev)
+
+
+def _pair_coef(r, dev):
+    """The (r+1, 3) float64 table (alpha, beta, gamma) of the all-pairs entries, on the device."""
+    from . import kernelshap
+    return torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
+
+
 def kshap_accum(keep, v, v0, n, weights=None):
     """keep (M,) int64-typed rows, v (G,M) f32 rewards of G games on those rows, v0 (G,) f64, weights (M,) f64 or None (all 1) ->
     (A (n,n) f64, b (G,n) f64, wsum (1,) f64): the RAW sums A = sum w z z^T, b[g] = sum w z (v[g] - v0[g]), wsum = sum w
@@ -403,15 +427,12 @@ def kshap_accum(keep, v, v0, n, weights=None):
         _shape(weights, "weights", m)
     dev = keep.device
     nbytes = lib.iq_kshap_scratch_bytes(m, n, g)
-    if nbytes == 0:
-        raise _lib.IqError("kshap_accum: M=%d rows, n=%d regions, G=%d games is out of range" % (m, n, g))
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = _kshap_scratch("kshap_accum", nbytes, m, n, g, dev, regions="n")
     a = torch.empty((n, n), dtype=torch.float64, device=dev)
     b = torch.empty((g, n), dtype=torch.float64, device=dev)
     wsum = torch.empty((1,), dtype=torch.float64, device=dev)
     _lib.check(lib.iq_kshap_accum(_dev(keep, torch.int64, "keep"), _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"),
-                                  _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0), m, n, g,
-                                  _p(a), _p(b), _p(wsum), _p(scratch), nbytes, _stream()), "iq_kshap_accum")
+                                  _opt(weights, torch.float64, "weights"), m, n, g, _p(a), _p(b), _p(wsum), _p(scratch), nbytes, _stream()), "iq_kshap_accum")
     return a, b, wsum
 
 
@@ -707,14 +728,11 @@ def kshap_moment_wide(keep, v, v0, num_regions, weights=None):
         _shape(weights, "weights", m)
     dev = keep.device
     nbytes = lib.iq_kshap_scratch_bytes_wide(m, r, g)
-    if nbytes == 0:
-        raise _lib.IqError("kshap_moment_wide: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = _kshap_scratch("kshap_moment_wide", nbytes, m, r, g, dev)
     b = torch.empty((g, r), dtype=torch.float64, device=dev)
     wsum = torch.empty((1,), dtype=torch.float64, device=dev)
     _lib.check(lib.iq_kshap_moment_wide(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"),
-                                        _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0), m, r, g,
-                                        _p(b), _p(wsum), _p(scratch), nbytes, _stream()), "iq_kshap_moment_wide")
+                                        _opt(weights, torch.float64, "weights"), m, r, g, _p(b), _p(wsum), _p(scratch), nbytes, _stream()), "iq_kshap_moment_wide")
     return b, wsum
 
 
@@ -740,13 +758,7 @@ def kshap_pairs(keep, v, v0, delta, r, weights=None):
     diagonal is 0, the matrix symmetric bit for bit).  One entry for both row formats: a narrow row is a wide row of one word."""
     lib = _lib.load()
     r = kshap_regions_wide(r)
-    if isinstance(keep, torch.Tensor) and keep.dim() == 1:
-        if r > 64:
-            raise _lib.IqError("keep must be (M, %d) for %d regions, got %s" % (wide_words(r), r, tuple(keep.shape)))
-        kp = _dev(keep, torch.int64, "keep")
-    else:
-        kp = wide_keep(keep, r)
-    m = keep.shape[0]
+    kp, m = _sampled_rows(keep, r)
     g, _ = _shape(v, "v", None, m)
     _shape(v0, "v0", g)
     _shape(delta, "delta", g)
@@ -754,20 +766,18 @@ def kshap_pairs(keep, v, v0, delta, r, weights=None):
         _shape(weights, "weights", m)
     dev = keep.device
     nbytes = lib.iq_kshap_pairs_scratch_bytes(m, r, g)
-    if nbytes == 0:
-        raise _lib.IqError("kshap_pairs: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
-    from . import kernelshap
-    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = _kshap_scratch("kshap_pairs", nbytes, m, r, g, dev)
+    coef = _pair_coef(r, dev)
     out = torch.empty((g, r, r), dtype=torch.float64, device=dev)
     _lib.check(lib.iq_kshap_pairs(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"), _dev(delta, torch.float64, "delta"),
-                                  _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0),
-                                  _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()), "iq_kshap_pairs")
+                                  _opt(weights, torch.float64, "weights"), _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()),
+               "iq_kshap_pairs")
     return out
 
 
 def _sampled_rows(keep, r):
-    """The keep rows of a standard-error entry -> (pointer argument, M): narrow (M,) rows for r <= 64, or (M,W) wide rows."""
+    """The keep rows of an entry that takes both row formats -> (pointer argument, M): narrow (M,) rows for r <= 64, or (M,W) wide
+    rows."""
     if isinstance(keep, torch.Tensor) and keep.dim() == 1:
         if r > 64:
             raise _lib.IqError("keep must be (M, %d) for %d regions, got %s" % (wide_words(r), r, tuple(keep.shape)))
@@ -804,11 +814,8 @@ def kshap_pairs_se(keep, v, v0, delta, r, paired=True, weights=None):
     _units("kshap_pairs_se", m, paired)
     dev = keep.device
     nbytes = lib.iq_kshap_pairs_se_scratch_bytes(m, r, g, int(bool(paired)))
-    if nbytes == 0:
-        raise _lib.IqError("kshap_pairs_se: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
-    from . import kernelshap
-    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = _kshap_scratch("kshap_pairs_se", nbytes, m, r, g, dev)
+    coef = _pair_coef(r, dev)
     out = torch.empty((g, r, r), dtype=torch.float64, device=dev)
     se = torch.empty((g, r, r), dtype=torch.float64, device=dev)
     _lib.check(lib.iq_kshap_pairs_se(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"), _dev(delta, torch.float64, "delta"),
@@ -832,9 +839,7 @@ def kshap_moment_se(keep, v, v0, r, paired=True, weights=None):
     _units("kshap_moment_se", m, paired)
     dev = keep.device
     nbytes = lib.iq_kshap_moment_se_scratch_bytes_wide(m, r, g, int(bool(paired)))
-    if nbytes == 0:
-        raise _lib.IqError("kshap_moment_se: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
-    scratch = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = _kshap_scratch("kshap_moment_se", nbytes, m, r, g, dev)
     b = torch.empty((g, r), dtype=torch.float64, device=dev)
     var = torch.empty((g, r), dtype=torch.float64, device=dev)
     _lib.check(lib.iq_kshap_moment_se_wide(kp, _dev(v, torch.float32, "v"), _dev(v0, torch.float64, "v0"), m, r, g, int(bool(paired)),
@@ -864,15 +869,10 @@ def kshap_pairs_terms(keep, t, r, weights=None):
         _shape(weights, "weights", m)
     dev = keep.device
     nbytes = lib.iq_kshap_pairs_scratch_bytes(m, r, g)
-    if nbytes == 0:
-        raise _lib.IqError("kshap_pairs_terms: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
-    from . import kernelshap
-    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
-    scratch = torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = torch.zeros((_kshap_scratch_words("kshap_pairs_terms", nbytes, m, r, g),), dtype=torch.float64, device=dev)
+    coef = _pair_coef(r, dev)
     out = torch.zeros((g, r, r), dtype=torch.float64, device=dev)
-    _lib.check(lib.iq_kshap_pairs_terms(kp, _dev(t, torch.float64, "t"),
-                                        _dev(weights, torch.float64, "weights") if weights is not None else ctypes.c_void_p(0),
-                                        _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()), "iq_kshap_pairs_terms")
+    _lib.check(lib.iq_kshap_pairs_terms(kp, _dev(t, torch.float64, "t"), _opt(weights, torch.float64, "weights"), _p(coef), m, r, g, _p(out), _p(scratch), nbytes, _stream()), "iq_kshap_pairs_terms")
     return out
 
 
@@ -889,11 +889,8 @@ def kshap_pairs_terms_se(keep, t, r, paired=True, weights=None):
     _units("kshap_pairs_terms_se", m, paired)
     dev = keep.device
     nbytes = lib.iq_kshap_pairs_se_scratch_bytes(m, r, g, int(bool(paired)))
-    if nbytes == 0:
-        raise _lib.IqError("kshap_pairs_terms_se: M=%d rows, R=%d regions, G=%d games is out of range" % (m, r, g))
-    from . import kernelshap
-    coef = torch.from_numpy(kernelshap.pair_coefficients(r)).to(dev)
-    scratch = torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = torch.zeros((_kshap_scratch_words("kshap_pairs_terms_se", nbytes, m, r, g),), dtype=torch.float64, device=dev)
+    coef = _pair_coef(r, dev)
     out = torch.zeros((g, r, r), dtype=torch.float64, device=dev)
     se = torch.zeros((g, r, r), dtype=torch.float64, device=dev)
     _lib.check(lib.iq_kshap_pairs_terms_se(kp, _dev(t, torch.float64, "t"), _p(coef), m, r, g, int(bool(paired)), _p(out), _p(se),
@@ -951,9 +948,7 @@ def kshap_pair_fit(gram, keep, v, v0, delta, r, ridge, solves=False):
         raise _lib.IqError("kshap_pair_fit: ridge must be a number >= 0, got %r" % ridge)
     dev = keep.device
     nbytes = lib.iq_kshap_pair_fit_scratch_bytes(m, int(r), g)
-    if nbytes == 0:
-        raise _lib.IqError("kshap_pair_fit: M=%d rows, R=%d regions, G=%d games is out of range" % (m, int(r), g))
-    scratch = torch.zeros((nbytes // 8,), dtype=torch.float64, device=dev)
+    scratch = torch.zeros((_kshap_scratch_words("kshap_pair_fit", nbytes, m, int(r), g),), dtype=torch.float64, device=dev)
     beta = torch.zeros((g, d), dtype=torch.float64, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     both = torch.zeros((g + 1, d), dtype=torch.float64, device=dev) if solves else None
@@ -982,8 +977,8 @@ def kshap_pair_surrogate(keep, beta, r, v=None, v0=None):
         _shape(v, "v", g, m)
         _shape(v0, "v0", g)
         t = torch.zeros((g, m), dtype=torch.float64, device=dev)
-    _lib.check(lib.iq_kshap_pair_surrogate(kp, _dev(beta, torch.float64, "beta"), _dev(v, torch.float32, "v") if t is not None else _p(None),
-                                           _dev(v0, torch.float64, "v0") if t is not None else _p(None), m, int(r), g, _p(out), _p(t),
+    _lib.check(lib.iq_kshap_pair_surrogate(kp, _dev(beta, torch.float64, "beta"), _opt(v if t is not None else None, torch.float32, "v"),
+                                           _opt(v0 if t is not None else None, torch.float64, "v0"), m, int(r), g, _p(out), _p(t),
                                            _stream()), "iq_kshap_pair_surrogate")
     return out if t is None else (out, t)
 
