@@ -48,6 +48,7 @@ enum {
 #define IQ_NUM_FEAT 1024
 #define IQ_MAX_EXACT_PLAYERS 24
 #define IQ_MAX_WIDE_REGIONS 1024   /* iq_*_wide: a coalition is a row of at most 16 words */
+#define IQ_KSHAP_SPARSE_MAX_FEATURES 2080   /* iq_kshap_feat_*: the unknowns of a fitted surrogate, 64 + 64 63 / 2 */
 
 /* ABI version: 100 * major + minor.  101 (round 4): every weight descriptor (iq_dense_layer, iq_pointnet_weights, ...) gained
  * optional `*_bf3` fields (weights split into three bf16 terms, iq_pack_weight_bf3).  Descriptors MUST be zero-initialised before
@@ -84,8 +85,10 @@ enum {
  * iq_kshap_pairs_se_scratch_bytes, iq_kshap_pairs_se, iq_kshap_moment_se_scratch_bytes_wide, iq_kshap_moment_se_wide).
  * 122: new entry points, no layout change (control variates for the all-pairs map: iq_kshap_pairs_terms, iq_kshap_pairs_terms_se,
  * iq_kshap_pair_features, iq_kshap_pair_gram, iq_kshap_pair_fit_scratch_bytes, iq_kshap_pair_fit, iq_kshap_pair_surrogate,
- * iq_kshap_pair_shift_terms). */
-#define IQ_ABI_VERSION 122
+ * iq_kshap_pair_shift_terms).
+ * 123: new entry points, no layout change (sparse regression control variate: iq_kshap_sparse_expand, iq_kshap_feat_gram,
+ * iq_kshap_feat_fit_scratch_bytes, iq_kshap_feat_fit, iq_kshap_feat_surrogate). */
+#define IQ_ABI_VERSION 123
 int iq_version(void);
 const char* iq_last_error(void);
 
@@ -929,6 +932,59 @@ int iq_kshap_pair_surrogate(const uint64_t* keep /*M*/, const double* beta /*G,d
 /* The terms of the shift, t[g][m] as defined above, for rows of W words, 2 <= R <= IQ_MAX_WIDE_REGIONS. */
 int iq_kshap_pair_shift_terms(const uint64_t* keep /*M,W*/, const float* v /*G,M*/, const double* v0 /*G*/, const double* delta /*G*/,
                               int M, int R, int G, double* t /*G,M*/, iq_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sparse regression control variate (csrc/iq_kshap_sparsecv.hip, csrc/iq_kshap_fit.h)
+ *
+ * The regression control above with a surrogate of all R singles and a caller-chosen list of K pairs, for narrow and wide rows of
+ * 2 <= R <= IQ_MAX_WIDE_REGIONS regions.  A pair list is pairs (K,2) int32 with 0 <= i < j < R, strictly increasing in row-major
+ * order (so without duplicates), K >= 0.  Features a = 0 .. d-1, d = R + K <= IQ_KSHAP_SPARSE_MAX_FEATURES: the singles first, then
+ * the listed pairs in list order; f_a(S) = 1 when the feature's one or two regions are all in S.  K = 0 is a fitted additive
+ * control; the complete row-major list at R <= IQ_MAX_REGIONS is the regression control above, bit for bit.
+ *
+ * Everything else is the regression control's contract with this d and these features: the two contiguous folds of units; per
+ * fold Gram = exact counts, c, A = Gram + ridge I, beta under sum(beta) = delta; the OTHER fold's beta gives
+ * t_m = ((double)v_m - v0) - g_beta(S_m); I_f = C(beta) + (delta - 1 beta) / (R-1) + SHAPIQ_f(t) (iq_kshap_pairs_terms_se on the
+ * original rows, narrow or wide); the row-weighted average; the se that neglects the cross-fold covariance.  C(beta) holds
+ * beta_{R+k} at (i_k, j_k) and (j_k, i_k) and 0 elsewhere.
+ *
+ * Unbiased whatever the list and the fit are, PROVIDED THE LIST DOES NOT DEPEND ON THE REWARDS OF THE ROWS IT IS APPLIED TO: a
+ * list from the geometry of the regions (the neighbours of the caller's default) or from other rows satisfies it, a list screened
+ * on the same rows' rewards does not.
+ *
+ * The entries work on FEATURE ROWS: feat (M, Wd) uint64, Wd = ceil(d / 64), bit (a & 63) of word (a >> 6) of row m = f_a(S_m).
+ * Gram, right-hand sides and surrogate are then the kernels of the regression control on rows of Wd words; ridge, factor, solves
+ * and constraint are the very kernels of iq_kshap_pair_fit.  The Gram matrix is one workgroup per 64 x 64 block on or above the
+ * diagonal walking every row (561 workgroups at d = 2080), not cut into chunks: the counts are exact in any order.  The same
+ * guarantees: one stream, no floating-point atomics, no grid chosen at run time, two calls give the same bits, a game's bits
+ * depend neither on G nor on a neighbouring game's rewards.
+ * ------------------------------------------------------------------------------------------- */
+
+/* feat (M, ceil((R + K) / 64)) of the rows keep (M, W = ceil(R / 64)): bits of keep at or above R are ignored, bits of feat at or
+ * above d = R + K are written 0.  A list entry outside 0 <= i < j < R is never used as an index: it yields a feature that no row
+ * holds (the order of the list is not checked here: the entry cannot see the list without a synchronisation; callers check it).
+ * pairs may be NULL when K == 0. */
+int iq_kshap_sparse_expand(const uint64_t* keep /*M,W*/, const int32_t* pairs /*K,2*/, int M, int R, int K, uint64_t* feat /*M,Wd*/,
+                           iq_stream_t stream);
+
+/* gram (d,d) float64, symmetric: Gram[a][b] = the number of feature rows that hold bits a and b, exact counts; bits at or above
+ * d are ignored.  1 <= M <= 2^30, 2 <= d <= IQ_KSHAP_SPARSE_MAX_FEATURES. */
+int iq_kshap_feat_gram(const uint64_t* feat /*M,Wd*/, int M, int d, double* gram /*d,d*/, iq_stream_t stream);
+
+/* Scratch (bytes) of iq_kshap_feat_fit: that of iq_kshap_pair_fit with this d; 0 outside 1 <= M <= 2^30,
+ * 2 <= d <= IQ_KSHAP_SPARSE_MAX_FEATURES, 1 <= G <= 65535. */
+size_t iq_kshap_feat_fit_scratch_bytes(int M, int d, int G);
+
+/* iq_kshap_pair_fit on feature rows: beta (G,d) from gram = iq_kshap_feat_gram of the same rows; solves, *status, ridge as there. */
+int iq_kshap_feat_fit(const double* gram /*d,d*/, const uint64_t* feat /*M,Wd*/, const float* v /*G,M*/, const double* v0 /*G*/,
+                      const double* delta /*G*/, double ridge, int M, int d, int G, double* beta /*G,d*/,
+                      double* solves /*G+1,d or NULL*/, int32_t* status, void* scratch, size_t scratch_bytes, iq_stream_t stream);
+
+/* iq_kshap_pair_surrogate on feature rows: out_g[g][m] = the beta[g] of the set bits of row m below d, added in index order in
+ * one chain; out_t[g][m] = ((double)v[g][m] - v0[g]) - out_g[g][m].  Either output may be NULL (not both). */
+int iq_kshap_feat_surrogate(const uint64_t* feat /*M,Wd*/, const double* beta /*G,d*/, const float* v /*G,M or NULL*/,
+                            const double* v0 /*G or NULL*/, int M, int d, int G, double* out_g /*G,M or NULL*/,
+                            double* out_t /*G,M or NULL*/, iq_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Wide coalitions: region games of more than 64 regions, up to one region per point (csrc/iq_wide.hip, csrc/iq_pointnet.hip)

@@ -163,6 +163,11 @@ SIGNATURES = {
     "iq_kshap_pair_fit": (_I, [_P, _P, _P, _P, _P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "iq_kshap_pair_surrogate": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "iq_kshap_pair_shift_terms": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "iq_kshap_sparse_expand": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "iq_kshap_feat_gram": (_I, [_P, _I, _I, _P, _P]),
+    "iq_kshap_feat_fit_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "iq_kshap_feat_fit": (_I, [_P, _P, _P, _P, _P, ctypes.c_double, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "iq_kshap_feat_surrogate": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "iq_kshap_moment_se_scratch_bytes_wide": (_SZ, [_I, _I, _I, _I]),
     "iq_kshap_moment_se_wide": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "iq_kshap_draw_counter": (_I, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, _I, _I, _P, _I, _P, _P, _P]),
@@ -196,7 +201,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 122  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
+ABI_VERSION = 123  # IQ_ABI_VERSION of include/iq.h these struct layouts were written for
 
 
 def lib_path():

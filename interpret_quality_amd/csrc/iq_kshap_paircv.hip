@@ -17,14 +17,17 @@
 // the data: two calls give the same bits, a game's bits depend neither on G nor on a neighbouring game's rewards.
 #include "iq_common.h"
 #include "iq_kshap_block.h"
+#include "iq_kshap_fit.h"
 
 // every sum is a chain of individually rounded operations: no fused multiply-add
 #pragma clang fp contract(off)
 
 namespace {
 
+using iq::kshap::carve_fit;
 using iq::kshap::Chunks;
 using iq::kshap::chunks_of;
+using iq::kshap::FitScratch;
 using iq::kshap::kBlockElems;
 using iq::kshap::kThreads;
 using iq::kshap::kTile;
@@ -33,6 +36,7 @@ using iq::kshap::rows_ok;
 
 constexpr int kMaxR = IQ_MAX_REGIONS;
 constexpr int kMaxD = kMaxR + kMaxR * (kMaxR - 1) / 2;      // 2080
+static_assert(kMaxD == iq::kshap::kFitMaxFeatures, "the solve keeps a right-hand side of the largest fit in LDS");
 constexpr int kPanel = 32;                                  // columns of a Cholesky panel
 constexpr int kPanelLd = kPanel + 1;
 constexpr int kTrsmThreads = 128;
@@ -351,57 +355,14 @@ __global__ __launch_bounds__(kThreads) void kshap_paircv_shift_kernel(const unsi
     out[(size_t)g * M + m] = ((double)v[(size_t)g * M + m] - v0[g]) - (delta[g] * (double)s) / (double)R;
 }
 
-struct FitScratch {
-    double *A, *part, *X, *tol;
-    size_t bytes;
-};
-
-FitScratch carve_fit(void* base, long long M, int R, int G) {
-    const int d = features_of(R);
-    iq::Carver c(base);
-    FitScratch s;
-    s.A = c.take<double>((size_t)d * d);
-    s.part = c.take<double>((size_t)G * chunks_of(M).count * d);
-    s.X = c.take<double>((size_t)(G + 1) * d);
-    s.tol = c.take<double>(1);
-    s.bytes = c.bytes();
-    return s;
-}
-
 unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
 
-extern "C" int iq_kshap_pair_features(int R) { return R >= 2 && R <= kMaxR ? features_of(R) : 0; }
-
-extern "C" int iq_kshap_pair_gram(const uint64_t* keep, int M, int R, double* gram, iq_stream_t stream) {
-    IQ_REQUIRE(rows_ok(M, R, 1, kMaxR), "iq_kshap_pair_gram: M=%d, R=%d (1 <= M <= 2^30, 2 <= R <= %d)", M, R, kMaxR);
-    IQ_REQUIRE(keep && gram, "iq_kshap_pair_gram: null pointer");
-    const int d = features_of(R);
-    IQ_LAUNCH(kshap_paircv_gram_kernel, dim3(iq::kshap::blocks_of(d)), dim3(kThreads), 0, iq::as_stream(stream),
-              reinterpret_cast<const unsigned long long*>(keep), (long long)M, R, d, gram);
-    return IQ_OK;
-}
-
-extern "C" size_t iq_kshap_pair_fit_scratch_bytes(int M, int R, int G) { return rows_ok(M, R, G, kMaxR) ? carve_fit(nullptr, M, R, G).bytes : 0; }
-
-extern "C" int iq_kshap_pair_fit(const double* gram, const uint64_t* keep, const float* v, const double* v0, const double* delta,
-                                 double ridge, int M, int R, int G, double* beta, double* solves, int32_t* status, void* scratch,
-                                 size_t scratch_bytes, iq_stream_t stream) {
-    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "iq_kshap_pair_fit: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
-    IQ_REQUIRE(ridge >= 0.0, "iq_kshap_pair_fit: ridge must be a number >= 0");
-    IQ_REQUIRE(gram && keep && v && v0 && delta && beta && status && scratch, "iq_kshap_pair_fit: null pointer");
-    const FitScratch s = carve_fit(scratch, M, R, G);
-    IQ_TRY(iq::kshap::scratch_ok("iq_kshap_pair_fit", scratch, scratch_bytes, s.bytes));
-    hipStream_t st = iq::as_stream(stream);
-    const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
-    const int d = features_of(R);
-    const Chunks ch = chunks_of(M);
-    IQ_TRY(iq::hip_ok(hipMemsetAsync(status, 0, sizeof(int32_t), st), "iq_kshap_pair_fit: clearing the status word"));
-    IQ_LAUNCH(kshap_paircv_rhs_kernel, dim3(ch.count, (d + 63) / 64, G), dim3(kThreads), 0, st, k, v, v0, (long long)M, R, d, ch.tiles_per,
-              s.part);
+int iq::kshap::fit_from_partials(const char* copy_what, const double* gram, const double* delta, double ridge, int d, int G, int nchunk,
+                                 const FitScratch& s, double* beta, double* solves, int32_t* status, hipStream_t st) {
     IQ_LAUNCH(kshap_paircv_rhs_fold_kernel, dim3(blocks_for((long long)(G + 1) * d)), dim3(kThreads), 0, st, (const double*)s.part, d, G,
-              ch.count, s.X);
+              nchunk, s.X);
     IQ_LAUNCH(kshap_paircv_ridge_kernel, dim3(blocks_for((long long)d * d)), dim3(kThreads), 0, st, gram, ridge, d, s.A);
     for (int k0 = 0; k0 < d; k0 += kPanel) {
         const int nb = d - k0 < kPanel ? d - k0 : kPanel, rest = d - k0 - nb;
@@ -414,9 +375,40 @@ extern "C" int iq_kshap_pair_fit(const double* gram, const uint64_t* keep, const
     }
     IQ_LAUNCH(kshap_paircv_solve_kernel, dim3(G + 1), dim3(kThreads), 0, st, (const double*)s.A, d, s.X);
     if (solves)
-        IQ_TRY(iq::hip_ok(hipMemcpyAsync(solves, s.X, (size_t)(G + 1) * d * sizeof(double), hipMemcpyDeviceToDevice, st),
-                          "iq_kshap_pair_fit: copying the solves"));
+        IQ_TRY(iq::hip_ok(hipMemcpyAsync(solves, s.X, (size_t)(G + 1) * d * sizeof(double), hipMemcpyDeviceToDevice, st), copy_what));
     IQ_LAUNCH(kshap_paircv_constrain_kernel, dim3(G), dim3(kThreads), 0, st, (const double*)s.X, delta, d, G, beta);
+    return IQ_OK;
+}
+
+extern "C" int iq_kshap_pair_features(int R) { return R >= 2 && R <= kMaxR ? features_of(R) : 0; }
+
+extern "C" int iq_kshap_pair_gram(const uint64_t* keep, int M, int R, double* gram, iq_stream_t stream) {
+    IQ_REQUIRE(rows_ok(M, R, 1, kMaxR), "iq_kshap_pair_gram: M=%d, R=%d (1 <= M <= 2^30, 2 <= R <= %d)", M, R, kMaxR);
+    IQ_REQUIRE(keep && gram, "iq_kshap_pair_gram: null pointer");
+    const int d = features_of(R);
+    IQ_LAUNCH(kshap_paircv_gram_kernel, dim3(iq::kshap::blocks_of(d)), dim3(kThreads), 0, iq::as_stream(stream),
+              reinterpret_cast<const unsigned long long*>(keep), (long long)M, R, d, gram);
+    return IQ_OK;
+}
+
+extern "C" size_t iq_kshap_pair_fit_scratch_bytes(int M, int R, int G) { return rows_ok(M, R, G, kMaxR) ? carve_fit(nullptr, M, features_of(R), G).bytes : 0; }
+
+extern "C" int iq_kshap_pair_fit(const double* gram, const uint64_t* keep, const float* v, const double* v0, const double* delta,
+                                 double ridge, int M, int R, int G, double* beta, double* solves, int32_t* status, void* scratch,
+                                 size_t scratch_bytes, iq_stream_t stream) {
+    IQ_REQUIRE(rows_ok(M, R, G, kMaxR), "iq_kshap_pair_fit: M=%d, R=%d, G=%d (1 <= M <= 2^30, 2 <= R <= %d, 1 <= G <= 65535)", M, R, G, kMaxR);
+    IQ_REQUIRE(ridge >= 0.0, "iq_kshap_pair_fit: ridge must be a number >= 0");
+    IQ_REQUIRE(gram && keep && v && v0 && delta && beta && status && scratch, "iq_kshap_pair_fit: null pointer");
+    const FitScratch s = carve_fit(scratch, M, features_of(R), G);
+    IQ_TRY(iq::kshap::scratch_ok("iq_kshap_pair_fit", scratch, scratch_bytes, s.bytes));
+    hipStream_t st = iq::as_stream(stream);
+    const unsigned long long* k = reinterpret_cast<const unsigned long long*>(keep);
+    const int d = features_of(R);
+    const Chunks ch = chunks_of(M);
+    IQ_TRY(iq::hip_ok(hipMemsetAsync(status, 0, sizeof(int32_t), st), "iq_kshap_pair_fit: clearing the status word"));
+    IQ_LAUNCH(kshap_paircv_rhs_kernel, dim3(ch.count, (d + 63) / 64, G), dim3(kThreads), 0, st, k, v, v0, (long long)M, R, d, ch.tiles_per,
+              s.part);
+    IQ_TRY(iq::kshap::fit_from_partials("iq_kshap_pair_fit: copying the solves", gram, delta, ridge, d, G, ch.count, s, beta, solves, status, st));
     return IQ_OK;
 }
 

@@ -898,8 +898,8 @@ def kshap_pairs_terms_se(keep, t, r, paired=True, weights=None):
     return out, se
 
 
-SURROGATE_NEEDS_SHIFT = ("the regression surrogate has R + R (R-1) / 2 unknowns and takes 2 .. %d regions: use control='shift' above"
-                         % MAX_KSHAP_REGIONS)
+SURROGATE_NEEDS_SHIFT = ("the regression surrogate has R + R (R-1) / 2 unknowns and takes 2 .. %d regions: use control='shift' or "
+                         "control='sparse' above" % MAX_KSHAP_REGIONS)
 
 
 def kshap_pair_features(r):

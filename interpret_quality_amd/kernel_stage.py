@@ -30,6 +30,11 @@ Per selected cloud, under the experiment folder that ``exp_folder`` derives from
     kernelshap/control.json                       {"control", "ridge", "fold_rows", "paired"} of that estimate; with
                                                   --compare_exact sampling_error.json gains "pairs_cv": max error, RMS error, z_rms
 
+    kernelshap/control_pairs.npy                  (K, 2) int32   with --control sparse: the listed pairs of the sparse
+                                                  surrogate, the --control_pairs K (default min(3 n, 2080 - n)) nearest pairs of
+                                                  FPS centres; control.json is then {"control", "select": "neighbours", "pairs",
+                                                  "features", "fold_rows", "ridge", "status"}
+
 Without --pairs, without --se and without --control, every artefact is what it was before the flag existed, byte for byte.
 --se is the sampling error of drawn rows: with --samples all, or with the sampled Gram matrix and no --pairs, there is nothing it could write and the
 parser says so.  With --compare_exact, sampling_error.json gains "z_rms", the RMS of (estimate - exact) / se - about 1 for a
@@ -70,7 +75,14 @@ def artefacts(g):
 def save(folder, out):
     for key in FILES + tuple(name for name in OPTIONAL.values() if name in out):
         np.save(folder + "%s.npy" % key, out[key])
-    if "control" in out:
+    if "control" in out and "pairs" in out["control"]:           # the sparse control: its list beside what it made of it
+        info = out["control"]
+        np.save(folder + "control_pairs.npy", info["pairs"])
+        with open(folder + "control.json", "w") as f:
+            json.dump({"control": info["control"], "select": "neighbours", "pairs": int(len(info["pairs"])),
+                       "features": int(info["features"]), "fold_rows": info["fold_rows"], "ridge": info["ridge"],
+                       "status": info["status"]}, f)
+    elif "control" in out:
         with open(folder + "control.json", "w") as f:
             json.dump({key: out["control"][key] for key in ("control", "ridge", "fold_rows", "paired")}, f)
 
@@ -110,19 +122,51 @@ def check_se(parser, args, gram):
 
 
 def add_control_flag(parser, choices):
-    """--control; a namespace parsed without it holds no trace of the flag (``control_of`` reads it)."""
-    parser.add_argument("--control", choices=list(choices), default=argparse.SUPPRESS,
+    """--control and --control_pairs; a namespace parsed without one holds no trace of it (``control_of``, ``control_pairs_of``)."""
+    parser.add_argument("--control", choices=list(choices) + list(kernelshap.LIST_CONTROLS), default=argparse.SUPPRESS,
                         help="with --pairs: also write kernelshap/region_interaction_cv.npy, its standard error and control.json - the "
                              "control-variate estimate of the all-pairs map from the same rows (shift: the additive game; regression: "
-                             "a cross-fitted 2-additive surrogate), no further model evaluation; default none")
+                             "a cross-fitted 2-additive surrogate; sparse: the same with all singles and the --control_pairs nearest "
+                             "pairs of regions, 2 to 1024 regions), no further model evaluation; default none")
+    parser.add_argument("--control_pairs", type=int, default=argparse.SUPPRESS, metavar="K",
+                        help="with --control sparse: the pairs of the surrogate, the K pairs of regions whose FPS centres are "
+                             "nearest; default min(3 num_regions, 2080 - num_regions); num_regions + K <= 2080")
 
 
 def control_of(args):
     return getattr(args, "control", "none")
 
 
+def control_pairs_of(args):
+    """The K of --control sparse: --control_pairs, or kernelshap.default_control_pairs; None for any other control."""
+    if control_of(args) not in kernelshap.LIST_CONTROLS:
+        return None
+    return getattr(args, "control_pairs", kernelshap.default_control_pairs(args.num_regions))
+
+
+def control_arguments(args, data, fps_index):
+    """What a stage hands ``game`` for --control: nothing without the flag; for the sparse control also the count of pairs and the
+    FPS centres of the regions ((R,3): point fps_index[r] of the cloud is the centre of region r)."""
+    if control_of(args) == "none":
+        return {}
+    if control_of(args) not in kernelshap.LIST_CONTROLS:
+        return {"control": control_of(args)}
+    idx = torch.as_tensor(np.asarray(fps_index).reshape(-1)[:args.num_regions].astype(np.int64), device=data.device)
+    return {"control": control_of(args), "control_pairs": control_pairs_of(args), "centres": data[0].index_select(0, idx).cpu().numpy()}
+
+
 def check_control(parser, args):
-    """--control shift|regression needs --pairs and drawn rows: a parser error without --pairs and with --samples all."""
+    """--control other than none needs --pairs and drawn rows: a parser error without --pairs and with --samples all.
+    --control_pairs belongs to --control sparse: a parser error without it, below 0 and where num_regions + K exceeds 2080 or K the
+    pairs there are."""
+    if hasattr(args, "control_pairs"):
+        n, k = args.num_regions, args.control_pairs
+        if control_of(args) not in kernelshap.LIST_CONTROLS:
+            parser.error("--control_pairs without --control sparse: only the sparse surrogate takes a list of pairs")
+        if k < 0 or n + k > kernelshap.MAX_SPARSE_FEATURES:
+            parser.error("--control_pairs %d: 0 <= K and num_regions + K <= %d" % (k, kernelshap.MAX_SPARSE_FEATURES))
+        if k > n * (n - 1) // 2:
+            parser.error("--control_pairs %d: %d regions have %d pairs" % (k, n, n * (n - 1) // 2))
     if control_of(args) == "none":
         return
     if not wants_pairs(args):
@@ -196,12 +240,12 @@ def compare_exact(model, data, lbl, region_id, keep, args, v=None):
     return phi, rows
 
 
-def kernel_one_cloud(model, data, lbl, region_id, args):
+def kernel_one_cloud(model, data, lbl, region_id, args, fps_index=None):
     """-> dict of one cloud's artefacts (ndarrays; 'sampling_error' only with --compare_exact, 'region_interaction' only with
-    --pairs, 'pairs_error' only with both; with --se the standard errors and, with --compare_exact, 'z_rms' / pairs_error's)."""
+    --pairs, 'pairs_error' only with both; with --se the standard errors and, with --compare_exact, 'z_rms' / pairs_error's).
+    ``fps_index``: the cloud's FPS centres, read by --control sparse alone."""
     g = kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired, args.gram, pairs=wants_pairs(args),
-                        **({"se": True} if wants_se(args) else {}),
-                        **({"control": control_of(args)} if control_of(args) != "none" else {}))
+                        **({"se": True} if wants_se(args) else {}), **control_arguments(args, data, fps_index))
     out = artefacts(g)
     if args.compare_exact:
         v = exact.value_table(model, data, lbl, region_id, args)
@@ -232,7 +276,7 @@ def run(args):
         for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), _skip_draw):
             mkdir(result_path + "kernelshap/")
             region_id = stage1.cal_region_id(data, fps_index, result_path, save=False)
-            out = kernel_one_cloud(model, data, lbl, region_id, args)
+            out = kernel_one_cloud(model, data, lbl, region_id, args, fps_index)
             save(result_path + "kernelshap/", out)
             line = "pointcloud:%s, index:%d, rows:%d, sum(phi)=%.6f, v_full - v_empty=%.6f" % (
                 name, i, out["coalitions"].size, out["region_shapley_value"].sum(), out["v_full"] - out["v_empty"])

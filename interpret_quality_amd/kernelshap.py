@@ -22,7 +22,7 @@ import sys
 import numpy as np
 import torch
 
-from . import final_common, hip_ops, work
+from . import final_common, hip_ops, sparse_ops, work
 from ._lib import IqError
 
 MAX_REGIONS = hip_ops.MAX_KSHAP_REGIONS
@@ -222,13 +222,41 @@ def pairs_se(keep, v, v_empty, v_full, n, paired=True, weights=None):
 
 
 CONTROLS = ("none", "shift", "regression")
+LIST_CONTROLS = ("sparse",)     # the controls that take a pair list: offered beside CONTROLS at every region count
+MAX_SPARSE_FEATURES = sparse_ops.MAX_FEATURES
 CONTROL_NEEDS_PAIRS = "a control variate belongs to the all-pairs map: control=%r needs pairs=True"
 RIDGE_SHARE = 64     # the default ridge of a fold's fit: its rows / 64 (a near-zero ridge is worse than no control)
 
 
 def check_control(control):
-    if control not in CONTROLS:
-        raise IqError("control must be one of %s, got %r" % (CONTROLS, control))
+    if control not in CONTROLS + LIST_CONTROLS:
+        raise IqError("control must be one of %s, got %r" % (CONTROLS + LIST_CONTROLS, control))
+
+
+def default_control_pairs(n):
+    """The listed pairs of control="sparse" where the caller names none: min(3 n, 2080 - n) - the cells of a surface have about six
+    neighbours, so 3 n pairs are about the adjacent ones; at 1024 regions the cap leaves 1056 - and never more than the
+    n (n-1) / 2 pairs there are (below 7 regions)."""
+    n = int(n)
+    return min(3 * n, MAX_SPARSE_FEATURES - n, n * (n - 1) // 2)
+
+
+def neighbour_pairs(centres, k):
+    """The ``k`` pairs of regions (i < j) with the smallest squared distance between their centres ((R,3)) -> (k,2) int32, sorted
+    row-major: a pair list of control="sparse".  The distance is float64 on the host, ties go to the lexicographically smaller
+    (i, j).  It depends on the geometry only, never on a reward: the condition under which the sparse control is unbiased."""
+    c = centres.detach().cpu().numpy() if isinstance(centres, torch.Tensor) else np.asarray(centres)
+    c = np.asarray(c, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] < 2:
+        raise IqError("neighbour_pairs: centres must be (R,3) with R >= 2, got %s" % (tuple(c.shape),))
+    r, k = c.shape[0], int(k)
+    i, j = np.triu_indices(r, 1)                 # row-major over i < j: a stable sort keeps that order among ties
+    if not 0 <= k <= len(i):
+        raise IqError("neighbour_pairs: %d regions have %d pairs, k=%d" % (r, len(i), k))
+    diff = c[i] - c[j]
+    d2 = (diff * diff).sum(axis=1)
+    pick = np.sort(np.argsort(d2, kind="stable")[:k])
+    return np.stack([i[pick], j[pick]], axis=1).astype(np.int32).reshape(k, 2)
 
 
 def fold_units(rows, paired=True):
@@ -267,7 +295,18 @@ def pair_coefficient_map(beta, n):
     return out
 
 
-def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", ridge=None, weights=None):
+def sparse_coefficient_map(beta, n, pair_list):
+    """C(beta) of a sparse surrogate: (..., n + K) coefficients -> (..., n, n) float64, beta_{n+k} at (i_k, j_k) and (j_k, i_k), 0
+    elsewhere."""
+    beta = np.asarray(beta, dtype=np.float64)
+    out = np.zeros(beta.shape[:-1] + (n, n))
+    i, j = pair_list[:, 0].astype(np.int64), pair_list[:, 1].astype(np.int64)
+    out[..., i, j] = beta[..., n:]
+    out[..., j, i] = beta[..., n:]
+    return out
+
+
+def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", ridge=None, weights=None, pair_list=None):
     """The control-variate estimate of the all-pairs Shapley interaction index from SAMPLED rows, with its standard error, on the
     rows and rewards ``pairs_se`` takes and with no further model evaluation -> (interaction, se, info): float64 ndarrays (n,n)
     or (G,n,n), symmetric bit for bit with a zero diagonal, and a dict (include/iq.h, "Control variates for the all-pairs map";
@@ -278,8 +317,17 @@ def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", rid
     each fold (ridge ``ridge``, default a fold's rows / 64, under sum(beta) = delta), its pair coefficients are read off and SHAP-IQ
     runs on the OTHER fold's residuals; the two estimates are averaged by rows.  Unbiased whatever the fit; the standard error
     neglects the covariance between the folds.  info: control, paired, fold_rows, ridge (per fold), status, beta ((2,G,d) or
-    (2,d)) - for the shift fold_rows is the one range of rows and ridge, beta are None."""
+    (2,d)) - for the shift fold_rows is the one range of rows and ridge, beta are None.
+
+    ``control="sparse"`` (2 .. 1024 regions, narrow or wide rows): the regression control with a surrogate of all n
+    singles and the K pairs of ``pair_list`` ((K,2), 0 <= i < j < n, strictly increasing row-major, n + K <= 2080; K = 0: a
+    fitted additive control; the complete list at n <= 64: ``regression`` bit for bit).  Unbiased whatever the list, PROVIDED
+    the list does not depend on the rewards of these rows (``neighbour_pairs`` depends on geometry only).  info gains "pairs",
+    the (K,2) int32 list, and "features", d = n + K."""
     check_control(control)
+    if (pair_list is not None) != (control in LIST_CONTROLS):
+        raise IqError("pairs_cv: pair_list belongs to control='sparse' and control='sparse' needs one, got control=%r with%s a list"
+                      % (control, "out" if pair_list is None else ""))
     if control == "none":
         raise IqError("pairs_cv: control='none' is pairs_se")
     if weights is not None:
@@ -294,7 +342,12 @@ def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", rid
         out, se = out.cpu().numpy(), se.cpu().numpy()
         info = {"control": control, "paired": bool(paired), "fold_rows": [m], "ridge": None, "status": 0, "beta": None}
         return (out[0], se[0], info) if single else (out, se, info)
-    d = pair_features(n)                      # refuses more than 64 regions, naming the shift
+    sparse = control in LIST_CONTROLS
+    if sparse:
+        pair_list = sparse_ops.check_pair_list(pair_list, n)
+        d = int(n) + len(pair_list)
+    else:
+        d = pair_features(n)                  # refuses more than 64 regions, naming the shift and the sparse control
     n = int(n)
     if ridge is not None and not float(ridge) >= 0.0:
         raise IqError("pairs_cv: ridge must be a number >= 0, got %r" % (ridge,))
@@ -305,15 +358,22 @@ def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", rid
     kf = [keep[lo:hi].contiguous() for lo, hi in cuts]
     vf = [v2[:, lo:hi].contiguous() for lo, hi in cuts]
     ridges = [rows[f] / float(RIDGE_SHARE) if ridge is None else float(ridge) for f in range(2)]
-    beta = [hip_ops.kshap_pair_fit(hip_ops.kshap_pair_gram(kf[f], n), kf[f], vf[f], v0, delta, n, ridges[f]) for f in range(2)]
+    if sparse:
+        ff = [sparse_ops.kshap_sparse_expand(kf[f], pair_list, n) for f in range(2)]
+        beta = [sparse_ops.kshap_feat_fit(sparse_ops.kshap_feat_gram(ff[f], d), ff[f], vf[f], v0, delta, d, ridges[f]) for f in range(2)]
+    else:
+        beta = [hip_ops.kshap_pair_fit(hip_ops.kshap_pair_gram(kf[f], n), kf[f], vf[f], v0, delta, n, ridges[f]) for f in range(2)]
     est, var = [], []
     for f in range(2):
         other = beta[1 - f]
-        _, t = hip_ops.kshap_pair_surrogate(kf[f], other, n, vf[f], v0)
+        if sparse:
+            _, t = sparse_ops.kshap_feat_surrogate(ff[f], other, d, vf[f], v0)
+        else:
+            _, t = hip_ops.kshap_pair_surrogate(kf[f], other, n, vf[f], v0)
         res, se_f = hip_ops.kshap_pairs_terms_se(kf[f], t, n, paired)
         b = other.cpu().numpy()
         slack = (delta.cpu().numpy() - b.sum(axis=1)) / (n - 1)          # the rounding of the efficiency constraint
-        i_f = pair_coefficient_map(b, n) + res.cpu().numpy()
+        i_f = (sparse_coefficient_map(b, n, pair_list) if sparse else pair_coefficient_map(b, n)) + res.cpu().numpy()
         i_f[:, ~np.eye(n, dtype=bool)] += slack[:, None]
         est.append(i_f)
         var.append(se_f.cpu().numpy() ** 2)
@@ -323,6 +383,8 @@ def pairs_cv(keep, v, v_empty, v_full, n, paired=True, control="regression", rid
     betas = np.stack([b.cpu().numpy() for b in beta])
     info = {"control": control, "paired": bool(paired), "fold_rows": rows, "ridge": ridges, "status": 0,
             "beta": betas[:, 0] if single else betas}
+    if sparse:
+        info.update(pairs=pair_list, features=d)
     return (out[0], se[0], info) if single else (out, se, info)
 
 
@@ -388,7 +450,7 @@ def running_estimates(keep, v, v_empty, v_full, n, counts, gram="sampled", ks=_N
 
 
 def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, draw=None, classes=None,
-         pairs=False, se=False, control="none", **how):
+         pairs=False, se=False, control="none", control_pairs=None, centres=None, **how):
     """The body of ``game``, wide_kernelshap.game and classwise.kernel_shapley, which check their own arguments first.  ``ks``:
     the estimator's module, this one or wide_kernelshap.  Refused before anything is drawn or run: the region count and
     ``gram``.  Then the rows - ``samples`` a count, None (``ks.default_samples``) or "all" (``ks.enumerated``); ``draw``:
@@ -399,7 +461,9 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
     and "interaction_se" with ``pairs``; refused before anything is drawn with ``samples="all"`` and where neither exists (the
     sampled Gram matrix without ``pairs``).  ``control`` other than "none" (with ``pairs``, sampled rows): also
     "interaction_cv", "interaction_cv_se" and "control" (the info dict) of ``ks.pairs_cv`` on the same rows; everything else is
-    what it is without it."""
+    what it is without it.  ``control="sparse"`` takes ``control_pairs``: a pair list, or a count k (None:
+    ``default_control_pairs``) - then ``neighbour_pairs`` of ``centres`` (n,3), the FPS centres of the regions; the list is checked
+    before anything is drawn."""
     n = ks.regions(args.num_regions)
     ks.check_gram(gram)
     check_control(control)
@@ -408,8 +472,20 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
             raise IqError(CONTROL_NEEDS_PAIRS % control)
         if isinstance(samples, str):
             raise IqError(SE_NEEDS_SAMPLES)
-        if control not in ks.CONTROLS:
-            raise IqError("control=%r is not available for %d regions here: one of %s" % (control, n, ks.CONTROLS))
+        if control not in ks.CONTROLS + ks.LIST_CONTROLS:
+            raise IqError("control=%r is not available for %d regions here: one of %s" % (control, n, ks.CONTROLS + ks.LIST_CONTROLS))
+    if control_pairs is not None and control not in LIST_CONTROLS:
+        raise IqError("control_pairs belongs to control='sparse', got control=%r" % (control,))
+    pair_list = None
+    if control in LIST_CONTROLS:
+        if control_pairs is None or isinstance(control_pairs, (int, np.integer)):
+            k = default_control_pairs(n) if control_pairs is None else int(control_pairs)
+            if k < 0 or k > min(MAX_SPARSE_FEATURES - n, n * (n - 1) // 2):
+                raise IqError("control_pairs=%d: 0 .. %d pairs beside %d regions" % (k, min(MAX_SPARSE_FEATURES - n, n * (n - 1) // 2), n))
+            if centres is None or len(centres) != n:
+                raise IqError("control='sparse' with a count of pairs needs centres (%d,3): the FPS centres of the regions" % n)
+            control_pairs = neighbour_pairs(centres, k)
+        pair_list = sparse_ops.check_pair_list(control_pairs, n)
     if se and isinstance(samples, str):
         raise IqError(SE_NEEDS_SAMPLES)
     if se and gram != "analytic" and not pairs:
@@ -434,18 +510,21 @@ def play(ks, model, data, lbl, region_id, args, samples=None, paired=True, gram=
     if se and gram == "analytic":
         out["phi_se"] = ks.phi_se(keep, v, v_empty, v_full, n, paired, gram)[1]
     if control != "none":
-        out["interaction_cv"], out["interaction_cv_se"], out["control"] = ks.pairs_cv(keep, v, v_empty, v_full, n, paired, control)
+        out["interaction_cv"], out["interaction_cv_se"], out["control"] = ks.pairs_cv(
+            keep, v, v_empty, v_full, n, paired, control, **({"pair_list": pair_list} if pair_list is not None else {}))
     return out
 
 
 def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None, pairs=False, se=False,
-         control="none"):
+         control="none", control_pairs=None, centres=None):
     """One cloud's sampled (or enumerated) game with everything the driver stores: dict of keep (M,), weights (None when
     sampled), v (M,) float32 rewards, v_full, v_empty, phi (n,) and running {count: phi of the first ``count`` rows};
     ``pairs``: also interaction (n,n), ``pairs`` of the same rows; ``se``: also phi_se (n,) under the analytic Gram matrix and,
-    with ``pairs``, interaction_se (n,n); ``control``: also interaction_cv, interaction_cv_se (n,n) and control (``play``).  A
+    with ``pairs``, interaction_se (n,n); ``control``: also interaction_cv, interaction_cv_se (n,n) and control (``play``, which
+    describes ``control_pairs`` and ``centres`` of control="sparse").  A
     ``gram`` outside GRAMS is refused before anything is drawn or run."""
-    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs, se=se, control=control)
+    return play(_NARROW, model, data, lbl, region_id, args, samples, paired, gram, counts, pairs=pairs, se=se, control=control,
+                control_pairs=control_pairs, centres=centres)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="sampled", counts=None):

@@ -21,6 +21,10 @@ Per selected cloud, under the wide experiment folder of that region count (``exp
                                                   DESIGN.md 5j), beside region_interaction.npy, which is still written
     kernelshap/region_interaction_cv_se.npy       (R, R) float64 its standard error
     kernelshap/control.json                       {"control", "ridge", "fold_rows", "paired"} of that estimate
+    kernelshap/control_pairs.npy                  (K, 2) int32   with --control sparse: region_interaction_cv.npy is
+                                                  then the cross-fitted surrogate of all R singles and these pairs, the
+                                                  --control_pairs K (default min(3 R, 2080 - R)) nearest pairs of FPS centres, and
+                                                  control.json {"control", "select", "pairs", "features", "fold_rows", "ridge", "status"}
 
 ``--samples`` is the number of rows M (model evaluations; default 1000 (R + 1), stage 1's budget).  The clouds, the FPS centres and
 the region ids are final_wide_shapley.py's (wide_stage.cal_region_id).  The draws after the sizes come from the device sampler
@@ -49,15 +53,14 @@ from .final_util import get_folder_name_list, load_model, mkdir
 FILES = kernel_stage.FILES
 
 
-def kernel_one_cloud(model, data, lbl, region_id, args, cloud=0):
+def kernel_one_cloud(model, data, lbl, region_id, args, cloud=0, fps_index=None):
     """-> dict of one cloud's artefacts (kernel_stage.artefacts).  ``cloud``: its index, the key's second word under
-    ``--draw counter``."""
+    ``--draw counter``; ``fps_index``: its FPS centres, read by --control sparse alone."""
     return kernel_stage.artefacts(wide_kernelshap.game(model, data, lbl, region_id, args, args.samples, not args.unpaired,
                                                        coalitions=args.coalitions, draw=args.draw, seed=args.seed, stream=cloud,
                                                        pairs=kernel_stage.wants_pairs(args),
                                                        **({"se": True} if kernel_stage.wants_se(args) else {}),
-                                                       **({"control": kernel_stage.control_of(args)}
-                                                          if kernel_stage.control_of(args) != "none" else {})))
+                                                       **kernel_stage.control_arguments(args, data, fps_index)))
 
 
 def stage1_estimate(result_path, i):
@@ -87,7 +90,7 @@ def run(args):
         for i, name, result_path, data, lbl, fps_index in stage1.selected_clouds(args, get_folder_name_list(args), _skip_draw):
             mkdir(result_path + "kernelshap/")
             region_id = wide_stage.cal_region_id(data, fps_index, result_path, save=False)
-            out = kernel_one_cloud(model, data, lbl, region_id, args, i)
+            out = kernel_one_cloud(model, data, lbl, region_id, args, i, fps_index)
             kernel_stage.save(result_path + "kernelshap/", out)
             with open(result_path + "kernelshap/draw.json", "w") as f:
                 json.dump({"draw": args.draw, "seed": int(args.seed), "stream": i if args.draw == "counter" else None,

@@ -43,6 +43,7 @@ pairs = kernelshap.pairs                          # all-pairs interactions: one 
 pairs_se = kernelshap.pairs_se                    # and their standard errors
 pairs_cv = kernelshap.pairs_cv                    # and the control-variate estimate (the regression surrogate: 64 regions at most)
 CONTROLS = ("none", "shift")                      # what ``game`` offers: a wide game's rows are wide whatever its region count
+LIST_CONTROLS = kernelshap.LIST_CONTROLS          # and the sparse surrogate on a pair list, which takes wide rows
 
 
 def check_gram(gram):
@@ -163,17 +164,18 @@ def running_estimates(keep, v, v_empty, v_full, r, counts, gram="analytic"):
 
 
 def game(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",
-         seed=1, stream=0, pairs=False, se=False, control="none"):
+         seed=1, stream=0, pairs=False, se=False, control="none", control_pairs=None, centres=None):
     """One cloud's sampled (or, at most exact.MAX_PLAYERS regions, enumerated) game with everything the driver stores: dict of
     keep (M,W), weights (None when sampled), v (M,) float32 rewards, v_full, v_empty, phi (R,) and running {count: phi of the
     first ``count`` rows} (kernelshap.play on this module).  ``draw``: "stream" - ``draw`` on NumPy's global generator - or
     "counter" - ``draw_counter`` keyed by (``seed``, ``stream``), which the other kind ignores.  ``pairs``: also interaction
-    (R,R), ``pairs`` of the same rows; ``se``: also phi_se (R,) and, with ``pairs``, interaction_se (R,R); ``control="shift"`` (with ``pairs``): also interaction_cv, interaction_cv_se and control (``pairs_cv``).  The region count, ``gram`` and ``draw`` are refused, in that order, before anything else
+    (R,R), ``pairs`` of the same rows; ``se``: also phi_se (R,) and, with ``pairs``, interaction_se (R,R); ``control="shift"`` or "sparse" (with ``pairs``; ``control_pairs`` and ``centres`` as kernelshap.play takes them): also interaction_cv, interaction_cv_se and control (``pairs_cv``).  The region count, ``gram`` and ``draw`` are refused, in that order, before anything else
     is looked at."""
     regions(args.num_regions)
     check_gram(gram)
     return kernelshap.play(sys.modules[__name__], model, data, lbl, region_id, args, samples, paired, gram, counts,
-                           drawer(draw, seed, stream), pairs=pairs, se=se, control=control, coalitions=coalitions)
+                           drawer(draw, seed, stream), pairs=pairs, se=se, control=control, control_pairs=control_pairs,
+                           centres=centres, coalitions=coalitions)
 
 
 def shapley(model, data, lbl, region_id, args, samples=None, paired=True, gram="analytic", counts=None, coalitions=None, draw="stream",

@@ -36,7 +36,13 @@ pairs and seeds, the RMS and the mean of se, and the RMS error they should repro
 shift and regression: RMS error, mean se and pooled z_rms.  Time: ``kernelshap.pairs_cv(control="regression")`` - the whole entry, both
 folds: Gram, fit, surrogate, residual SHAP-IQ with its standard error, the host's combination - and ``control="shift"`` against
 ``hip_ops.kshap_pairs_se`` of the same build on the same rows, R = 16 / 32 / 64 at 1000 (R + 1) rows, G = 1 and 10, alternated in one
-process; reported are the ratios of the medians and each entry's share of forwards + reduction."""
+process; reported are the ratios of the medians and each entry's share of forwards + reduction.
+
+``--control --sparse`` - the sparse control alone (``control="sparse"``), merged into the file under "sparse".  Error:
+the same seeds and budgets for K = 0, the 48 nearest pairs of FPS centres and all 120 pairs, beside shift and regression.  Bars: at
+128 and 1024 regions, 1000 (R + 1) counter-drawn rows, default K, the mean se of sparse against shift on the same rows, for listed
+and unlisted pairs (no exact index there: the bars are what 5i calibrated).  Time: the entry with both folds and the wrapper against
+``kshap_pairs_se``, the shift and the forwards, at R = 64 with the complete list (beside the regression entry) and at 128 and 1024."""
 import argparse
 import json
 import os
@@ -182,6 +188,7 @@ def _time_se(r, games, runs, block, words, e, e2, fwd, pairs_call, se_call):
 
 
 CONTROL_REGIONS = (16, 32, 64)
+SPARSE_REGIONS = (64, 128, 1024)
 
 
 def time_control(r, games, runs, dev):
@@ -216,6 +223,95 @@ def time_control(r, games, runs, dev):
     out["regression_over_pairs_se"] = med["pairs_cv_regression"] / med["kshap_pairs_se"]
     out["shift_over_pairs_se"] = med["pairs_cv_shift"] / med["kshap_pairs_se"]
     out["regression_costs_more_than_the_forwards_it_serves"] = bool(med["pairs_cv_regression"] > f)
+    return out
+
+
+def _centres(data, r):
+    """(R,3) float64: the FPS centres of the regions ``_setup`` assigns."""
+    return data[0].index_select(0, hip_ops.fps(data, r)[0].to(torch.int64)).cpu().numpy().astype(np.float64)
+
+
+def sparse_table(n, seeds, dev, counts=(0, 48, 120)):
+    """``control_table``'s seeds and budgets for the sparse control at K neighbour pairs, beside shift and regression."""
+    model, data, lbl, rid, args = _setup(n, dev)
+    table = exact.value_table(model, data, lbl, rid, args)
+    ends = table[[0, table.numel() - 1]].cpu().numpy()
+    pr = hip_ops.all_pairs(n)
+    want = hip_ops.exact_interactions(table).cpu().numpy().mean(axis=1)
+    most = max(BUDGETS) * (n + 1)
+    lists = {"sparse_%d" % k: kernelshap.neighbour_pairs(_centres(data, n), k) for k in counts}
+    names = ("shift", "regression") + tuple(lists)
+    err2, se1, z2 = ({(c, b): [] for c in names for b in BUDGETS} for _ in range(3))
+    for seed in range(seeds):
+        np.random.seed(1000 + seed)
+        keep, _ = kernelshap.draw(n, most, True, dev)
+        for b in BUDGETS:
+            rows = keep[:b * (n + 1) // 2 * 2].contiguous()
+            v = table.index_select(0, rows).contiguous()
+            for c in names:
+                how = {"control": "sparse", "pair_list": lists[c]} if c in lists else {"control": c}
+                got, se, _ = kernelshap.pairs_cv(rows, v, float(ends[0]), float(ends[1]), n, True, **how)
+                got, se = got[pr[:, 0], pr[:, 1]], se[pr[:, 0], pr[:, 1]]
+                err2[c, b].append(float(((got - want) ** 2).mean()))
+                se1[c, b].append(float(se.mean()))
+                z2[c, b].append(float((((got - want) / se) ** 2).mean()))
+    return {"model": "pointnet", "cloud": "synthetic_00", "num_regions": n, "pairs": int(len(pr)), "seeds": seeds,
+            "exact_index_rms": float(np.sqrt((want ** 2).mean())),
+            "budgets": [{"permutations": b, "rows": b * (n + 1) // 2 * 2,
+                         **{c: {"rms_error": float(np.sqrt(np.mean(err2[c, b]))), "mean_se": float(np.mean(se1[c, b])),
+                                "z_rms": float(np.sqrt(np.mean(z2[c, b])))} for c in names}} for b in BUDGETS]}
+
+
+def time_sparse(r, runs, dev):
+    """The sparse entry (both folds, the wrapper) on 1000 (R + 1) paired rows against kshap_pairs_se, the shift, the forwards and -
+    at 64 regions, where the list is the complete one - the regression entry, alternated; and the bars of sparse against shift on
+    those rows, for listed and unlisted pairs."""
+    model, data, lbl, rid, args = _setup(r, dev)
+    ks = kernelshap if r <= kernelshap.MAX_REGIONS else wide_kernelshap
+    m = kernelshap.default_samples(r)
+    np.random.seed(1)
+    keep = kernelshap.draw(r, m, True, dev)[0] if ks is kernelshap else wide_kernelshap.draw_counter(r, m, 1, 0, True, dev)[0]
+    k = r * (r - 1) // 2 if r <= kernelshap.MAX_REGIONS else kernelshap.default_control_pairs(r)
+    pairs = kernelshap.neighbour_pairs(_centres(data, r), k)
+    forwards = lambda: ks.rewards(model, data, lbl, rid, args, keep)      # noqa: E731
+    ks.rewards(model, data, lbl, rid, args, keep[:4096].contiguous())
+    fwd = []
+    for _ in range(runs):
+        t, (v, v_full, v_empty) = _wall(forwards)
+        fwd.append(t)
+    v2, v0, v1 = kernelshap.games(keep, v, v_empty, v_full)
+    calls = {"kshap_pairs_se": lambda: hip_ops.kshap_pairs_se(keep, v2, v0, v1 - v0, r, True),
+             "pairs_cv_shift": lambda: kernelshap.pairs_cv(keep, v2, v0, v1, r, True, "shift"),
+             "pairs_cv_sparse": lambda: kernelshap.pairs_cv(keep, v2, v0, v1, r, True, "sparse", pair_list=pairs)}
+    if ks is kernelshap:
+        calls["pairs_cv_regression"] = lambda: kernelshap.pairs_cv(keep, v2, v0, v1, r, True, "regression")
+    times = {name: [] for name in calls}
+    last = {name: fn() for name, fn in calls.items()}
+    for _ in range(runs):                                                       # alternated in one process
+        for name, fn in calls.items():
+            times[name].append(_wall(fn)[0])
+    f = float(np.median(fwd))
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    out = {"num_regions": r, "rows": int(len(keep)), "listed_pairs": int(k), "unknowns": int(r + k), "games": 1,
+           "draw": "stream" if ks is kernelshap else "counter", "pointnet_forwards": _spread(fwd)}
+    for name, t in times.items():
+        out[name] = _spread(t)
+        out[name + "_share_of_forwards_plus_reduction"] = med[name] / (f + med[name])
+    out["sparse_over_pairs_se"] = med["pairs_cv_sparse"] / med["kshap_pairs_se"]
+    out["sparse_costs_more_than_the_forwards_it_serves"] = bool(med["pairs_cv_sparse"] > f)
+    if "pairs_cv_regression" in med:
+        out["sparse_over_regression"] = med["pairs_cv_sparse"] / med["pairs_cv_regression"]
+        out["sparse_is_regression_bit_for_bit"] = bool(np.array_equal(last["pairs_cv_sparse"][0], last["pairs_cv_regression"][0])
+                                                       and np.array_equal(last["pairs_cv_sparse"][1], last["pairs_cv_regression"][1]))
+    listed = np.zeros((r, r), dtype=bool)
+    listed[pairs[:, 0], pairs[:, 1]] = True
+    upper = np.triu(np.ones((r, r), dtype=bool), 1)
+    host = lambda x: (x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)).reshape(r, r)      # noqa: E731
+    se = {name: host(last[name][1]) for name in ("kshap_pairs_se", "pairs_cv_shift", "pairs_cv_sparse")}
+    out["mean_se"] = {which: {name: float(x[mask].mean()) for name, x in se.items()}
+                      for which, mask in (("all", upper), ("listed", listed), ("unlisted", upper & ~listed)) if mask.any()}
+    out["sparse_over_shift_mean_se"] = {which: row["pairs_cv_sparse"] / row["pairs_cv_shift"] for which, row in out["mean_se"].items()}
+    out["sparse_beats_shift"] = bool(out["sparse_over_shift_mean_se"]["all"] < 1.0)
     return out
 
 
@@ -305,6 +401,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--se", action="store_true", help="time kshap_pairs_se and measure the calibration of its bars (profiles/kshap_pairs_se.json)")
     ap.add_argument("--control", action="store_true", help="the control-variate estimators: error table and time (profiles/kshap_pairs_cv.json)")
+    ap.add_argument("--sparse", action="store_true", help="with --control: the sparse control alone (DESIGN.md 5k), merged into the file "
+                                                         "under \"sparse\"")
     ap.add_argument("--out", default=None, help="default profiles/kshap_pairs.json, with --se profiles/kshap_pairs_se.json, with --control "
                                                 "profiles/kshap_pairs_cv.json")
     ap.add_argument("--seeds", type=int, default=20)
@@ -315,11 +413,24 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.se and args.control:
         ap.error("--se and --control are two runs")
+    if args.sparse and not args.control:
+        ap.error("--sparse belongs to --control")
     args.out = args.out or os.path.join(REPO, "profiles", "kshap_pairs_cv.json" if args.control else
                                         "kshap_pairs_se.json" if args.se else "kshap_pairs.json")
     if not torch.cuda.is_available():
         raise SystemExit("bench_kshap_pairs.py needs a GPU: a time taken elsewhere says nothing about the MI355X")
     dev = torch.device("cuda:0")
+    if args.sparse:
+        with torch.no_grad():
+            part = {"device": torch.cuda.get_device_name(0), "time": [time_sparse(r, args.runs, dev) for r in SPARSE_REGIONS],
+                    "error": sparse_table(args.error_regions, args.seeds, dev)}
+        res = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        res["sparse"] = part
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(part))
+        return
     with torch.no_grad():
         if args.control:
             timed = [time_control(r, g, args.runs, dev) for r in CONTROL_REGIONS for g in args.games]
